@@ -885,9 +885,10 @@ int aggregate_device(const glx_features* f, int op, const int64_t* d_ids, const 
   // scratch: seg_start (Sg+1) [+ rows (N) for hashed ids]
   const bool hashed = f->idmap.any();  // raw ids are not rows: translate first (a table lookup, or arithmetic)
   const size_t n_i32 = (size_t)num_segments + 1 + kSegScratchExtra + (hashed ? (size_t)num_ids : 0);
-  int32_t* scratch = nullptr;
-  int rc = glx_scratch_alloc(reinterpret_cast<void**>(&scratch), n_i32 * sizeof(int32_t), s, 1);
+  GlxScratch lease;
+  int rc = lease.alloc(n_i32 * sizeof(int32_t), s, 1);
   if (rc != GLX_OK) return rc;
+  int32_t* scratch = lease.as<int32_t>();
   int32_t* rows = hashed ? scratch + num_segments + 1 + kSegScratchExtra : nullptr;
   AggArgs a;
   memset(&a, 0, sizeof(a));
@@ -908,9 +909,7 @@ int aggregate_device(const glx_features* f, int op, const int64_t* d_ids, const 
   a.num_segments = num_segments;
   a.default_attr = default_attr;
   run_aggregate(a, op, d_seg, num_ids, s);
-  hipError_t le = hipGetLastError();
-  glx_scratch_free(scratch, s);
-  GLX_HIP(le);
+  GLX_HIP(hipGetLastError());
   return GLX_OK;
 }
 
@@ -979,9 +978,10 @@ void launch_agg_stitch(bool vec4, const float* parts, const int32_t* cnts, int32
 int glx_aggregate_vrows_device(const GlxRowSource* src, int nsrc, int32_t dim, int op, const int32_t* vrows,
                                const int32_t* d_seg, int32_t num_ids, int32_t num_segments, float default_attr,
                                float* d_emb, int32_t* d_cnt, hipStream_t s) {
-  int32_t* scratch = nullptr;
-  int rc = glx_scratch_alloc(reinterpret_cast<void**>(&scratch), ((size_t)num_segments + 1 + kSegScratchExtra) * sizeof(int32_t), s, 1);
+  GlxScratch lease;
+  int rc = lease.alloc(((size_t)num_segments + 1 + kSegScratchExtra) * sizeof(int32_t), s, 1);
   if (rc != GLX_OK) return rc;
+  int32_t* scratch = lease.as<int32_t>();
   AggArgs a;
   memset(&a, 0, sizeof(a));
   rc = prepare_segments(a, d_seg, num_ids, num_segments, scratch, s);
@@ -1011,9 +1011,7 @@ int glx_aggregate_vrows_device(const GlxRowSource* src, int nsrc, int32_t dim, i
   a.num_segments = num_segments;
   a.default_attr = default_attr;
   run_aggregate(a, op, d_seg, num_ids, s);
-  hipError_t le = hipGetLastError();
-  glx_scratch_free(scratch, s);
-  GLX_HIP(le);
+  GLX_HIP(hipGetLastError());
   return GLX_OK;
 }
 
@@ -1194,46 +1192,20 @@ extern "C" int glx_aggregate(const glx_features* f, int op, const int64_t* node_
               "segment_ids == NULL means equal segments: num_ids must be a multiple of num_segments");
   GlxDeviceGuard guard(f->device);
   GLX_REQUIRE(guard.ok, "cannot select device %d", f->device);
-  hipStream_t s = ptr_kind == GLX_PTR_HOST ? glx_host_call_stream(stream, f->device) : glx_stream(stream);
-  if (ptr_kind == GLX_PTR_DEVICE) {
-    return aggregate_device(f, op, node_ids, segment_ids, num_ids, num_segments, default_attr,
-                            emb_out, cnt_out, s);
-  }
-  GlxHostCallSlot admitted(f->device);
-  const size_t emb_n = (size_t)num_segments * f->dim;
-  // outputs go straight into the caller's buffers when those are pinned (glx_mapped_ptr): the embeddings are
-  // by far the largest part of a response (4 * dim bytes per segment)
-  float* m_emb = static_cast<float*>(glx_mapped_ptr(emb_out, emb_n * 4));
-  int32_t* m_cnt = static_cast<int32_t*>(glx_mapped_ptr(cnt_out, (size_t)num_segments * 4));
-  const bool direct = m_emb != nullptr && m_cnt != nullptr;
-  const size_t out_b = direct ? 0 : ((emb_n * 4 + 15) & ~(size_t)15) + (size_t)num_segments * 4;
-  const size_t bytes = (size_t)num_ids * 8 + (size_t)num_ids * 4 + out_b + 64;
-  char* d = nullptr;
-  int rc = glx_scratch_alloc(reinterpret_cast<void**>(&d), bytes, s, 0);
-  if (rc != GLX_OK) return rc;
-  int64_t* d_ids = reinterpret_cast<int64_t*>(d);
-  int32_t* d_seg = reinterpret_cast<int32_t*>(d + (size_t)num_ids * 8);
-  char* d_out = d + (((size_t)num_ids * 12 + 15) & ~(size_t)15);
-  float* d_emb = direct ? m_emb : reinterpret_cast<float*>(d_out);
-  int32_t* d_cnt = direct ? m_cnt : reinterpret_cast<int32_t*>(d_out + ((emb_n * 4 + 15) & ~(size_t)15));
-  hipError_t e = hipSuccess;
-  if (num_ids > 0) {
-    e = hipMemcpyAsync(d_ids, node_ids, (size_t)num_ids * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && segment_ids) e = hipMemcpyAsync(d_seg, segment_ids, (size_t)num_ids * 4, hipMemcpyHostToDevice, s);
-  }
-  if (e == hipSuccess) {
-    rc = aggregate_device(f, op, d_ids, segment_ids ? d_seg : nullptr, num_ids, num_segments, default_attr, d_emb, d_cnt, s);
-    if (rc == GLX_OK && !direct) {
-      e = hipMemcpyAsync(emb_out, d_emb, emb_n * 4, hipMemcpyDeviceToHost, s);
-      if (e == hipSuccess) e = hipMemcpyAsync(cnt_out, d_cnt, (size_t)num_segments * 4, hipMemcpyDeviceToHost, s);
-    }
-  }
-  hipError_t e2 = hipStreamSynchronize(s);
-  glx_scratch_free(d, s);
-  if (rc != GLX_OK) return rc;
-  GLX_HIP(e);
-  GLX_HIP(e2);
-  return GLX_OK;
+  // outputs go straight into the caller's buffers when those are pinned: the embeddings are by far the largest part
+  // of a response (4 * dim bytes per segment)
+  GlxHostStage st(f->device, ptr_kind, stream, GlxHostStage::ADMIT | GlxHostStage::DIRECT_PINNED);
+  const int64_t* d_ids;
+  const int32_t* d_seg;
+  float* d_emb;
+  int32_t* d_cnt;
+  st.in(&d_ids, node_ids, (size_t)num_ids);
+  st.in(&d_seg, segment_ids, (size_t)num_ids);
+  st.out(&d_emb, emb_out, (size_t)num_segments * f->dim);
+  st.out(&d_cnt, cnt_out, (size_t)num_segments);
+  int rc = st.begin();
+  if (rc == GLX_OK) rc = aggregate_device(f, op, d_ids, d_seg, num_ids, num_segments, default_attr, d_emb, d_cnt, st.s);
+  return st.finish(rc);
 }
 
 extern "C" int glx_lookup(const glx_features* f, const int64_t* node_ids, int64_t n,
@@ -1245,39 +1217,24 @@ extern "C" int glx_lookup(const glx_features* f, const int64_t* node_ids, int64_
   GLX_REQUIRE(node_ids && out, "NULL data pointer");
   GlxDeviceGuard guard(f->device);
   GLX_REQUIRE(guard.ok, "cannot select device %d", f->device);
-  hipStream_t s = ptr_kind == GLX_PTR_HOST ? glx_host_call_stream(stream, f->device) : glx_stream(stream);
   int G = 1;
   const int want = (f->dim & 3) == 0 ? f->dim / 4 : f->dim;
   while (G < 64 && G < want) G <<= 1;
   const int64_t threads = n * G;
-  if (ptr_kind == GLX_PTR_DEVICE) {
-    GlxKernelTimer timer(GLX_KERNEL_LOOKUP, s);
-    glx_lookup_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, s>>>(f->map(), f->X, f->stride, f->swizzle_rows, f->dim, node_ids,
-                                                                       n, default_attr, out, G);
+  // a pinned caller buffer is written by the kernel directly
+  GlxHostStage st(f->device, ptr_kind, stream, GlxHostStage::ADMIT | GlxHostStage::DIRECT_PINNED);
+  const int64_t* d_ids;
+  float* d_out;
+  st.in(&d_ids, node_ids, (size_t)n);
+  st.out(&d_out, out, (size_t)n * f->dim);
+  int rc = st.begin();
+  if (rc == GLX_OK) {
+    GlxKernelTimer timer(GLX_KERNEL_LOOKUP, st.s);
+    glx_lookup_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, st.s>>>(f->map(), f->X, f->stride, f->swizzle_rows, f->dim,
+                                                                          d_ids, n, default_attr, d_out, G);
     timer.stop();
-    GLX_HIP(hipGetLastError());
-    return GLX_OK;
   }
-  GlxHostCallSlot admitted(f->device);
-  const size_t out_bytes = (size_t)n * f->dim * 4;
-  float* m_out = static_cast<float*>(glx_mapped_ptr(out, out_bytes));  // pinned caller buffer: the kernel writes it directly
-  const size_t ids_b = ((size_t)n * 8 + 15) & ~(size_t)15;  // ids first, 16-byte aligned rows after them
-  char* d = nullptr;
-  int rc = glx_scratch_alloc(reinterpret_cast<void**>(&d), ids_b + (m_out ? 0 : out_bytes), s, 0);
-  if (rc != GLX_OK) return rc;
-  int64_t* d_ids = reinterpret_cast<int64_t*>(d);
-  float* d_out = m_out ? m_out : reinterpret_cast<float*>(d + ids_b);
-  hipError_t e = hipMemcpyAsync(d_ids, node_ids, (size_t)n * 8, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) {
-    glx_lookup_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, s>>>(f->map(), f->X, f->stride, f->swizzle_rows, f->dim, d_ids, n,
-                                                                       default_attr, d_out, G);
-    if (!m_out) e = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, s);
-  }
-  hipError_t e2 = hipStreamSynchronize(s);
-  glx_scratch_free(d, s);
-  GLX_HIP(e);
-  GLX_HIP(e2);
-  return GLX_OK;
+  return st.finish(rc);
 }
 
 extern "C" int glx_aggregate_stitch(int device, int op, int32_t num_parts, const float* parts,

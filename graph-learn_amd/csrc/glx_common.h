@@ -47,12 +47,32 @@ struct GlxDeviceGuard {
   }
 };
 
-// Cached per-(thread, device, stream, slot) workspaces (glx_graph.hip).  slot 0 =
-// host-pointer staging of an entry point, slot 1 = kernel-internal scratch.
+// Cached per-(thread, device, stream, slot) workspaces (glx_graph.hip).  A slot is leased to one user at a time:
+// glx_scratch_alloc refuses (GLX_INTERNAL) a slot whose lease has not ended, glx_scratch_free ends it.  Work on one
+// stream is ordered, so a lease may end as soon as the last launch that uses the buffer is queued.  Slot 0 belongs to
+// GlxHostStage (host-pointer staging of an entry point); device-pointer bodies lease slots 1 and up.
 int glx_init_device(int device);
 int glx_scratch_alloc(void** p, size_t bytes, hipStream_t s, int slot);
 void glx_scratch_free(void* p, hipStream_t s);
-void glx_scratch_trim(hipStream_t s, int slot, size_t keep_bytes);
+void glx_scratch_trim(hipStream_t s, int slot, size_t keep_bytes);  // also ends the lease of what it frees
+
+// One workspace lease, ended on every exit path.
+struct GlxScratch {
+  void* p = nullptr;
+  hipStream_t s = nullptr;
+  int alloc(size_t bytes, hipStream_t stream, int slot) {
+    s = stream;
+    return glx_scratch_alloc(&p, bytes, stream, slot);
+  }
+  template <typename T>
+  T* as() const { return static_cast<T*>(p); }
+  ~GlxScratch() {
+    if (p) glx_scratch_free(p, s);
+  }
+  GlxScratch() = default;
+  GlxScratch(const GlxScratch&) = delete;
+  GlxScratch& operator=(const GlxScratch&) = delete;
+};
 
 // Request plans (glx_plan.hip) capture a sequence of entry points into a hipGraph.  While a plan is
 // being built on this thread: (1) workspaces must not be allocated inside the capture, and must belong to
@@ -65,7 +85,8 @@ void glx_capture_set_cc_dev(const uint64_t* p);
 const uint64_t* glx_capture_cc_dev();
 bool glx_profile_suspend(bool suspend);  // returns the previous "enabled" state when suspending
 
-// Temporary device allocation released on every exit path.
+// Temporary device allocation released on every exit path.  For one-off build-time allocations: hipFree
+// synchronises the device, so per-request paths stage through GlxHostStage / GlxScratch instead.
 struct GlxTemp {
   void* p = nullptr;
   ~GlxTemp() {
@@ -769,5 +790,52 @@ hipStream_t glx_thread_stream(int device);
 static inline hipStream_t glx_host_call_stream(void* s, int device) {
   return s ? reinterpret_cast<hipStream_t>(s) : glx_thread_stream(device);
 }
+
+// Host-pointer staging of one entry point (glx_graph.hip).  Every buffer is declared first; begin() then leases
+// workspace slot 0 once, carves it (256-byte aligned pieces) and queues the host->device copies; the body runs on
+// `s`; finish(rc) queues the device->host copies (only when everything succeeded), always synchronises `s`, ends the
+// lease and returns the first error of: rc, the launch error, the copies, the synchronisation.  An early return
+// before finish() synchronises and ends the lease in the destructor.
+// For GLX_PTR_DEVICE calls every declared pointer passes through unchanged (scratch() must not be used then),
+// begin() does nothing and finish(rc) only adds the launch check.
+struct GlxHostStage {
+  enum : int {
+    ADMIT = 1,          // hold a GlxHostCallSlot for the call
+    DIRECT_PINNED = 2,  // outputs wholly inside a glx_host_register range are written directly (glx_mapped_ptr)
+  };
+  const bool host;
+  const hipStream_t s;
+  GlxHostStage(int device, int ptr_kind, void* stream, int options = 0);
+  ~GlxHostStage();
+  GlxHostStage(const GlxHostStage&) = delete;
+  GlxHostStage& operator=(const GlxHostStage&) = delete;
+
+  template <typename T>
+  void in(const T** d, const T* h, size_t n) { declare(reinterpret_cast<void**>(const_cast<T**>(d)), h, n * sizeof(T), kIn); }
+  template <typename T>
+  void out(T** d, T* h, size_t n) { declare(reinterpret_cast<void**>(d), h, n * sizeof(T), kOut); }
+  template <typename T>
+  void scratch(T** d, size_t n) { declare(reinterpret_cast<void**>(d), nullptr, n * sizeof(T), kScratch); }
+  int begin();
+  // A device->host copy whose size the body only learnt (`d` lies in a scratch piece); queued by finish().
+  void out_after(void* h, const void* d, size_t bytes);
+  int finish(int rc);
+
+ private:
+  enum { kIn, kOut, kScratch, kAfter, kMaxPieces = 40 };  // glx_sample_hops: 2 pieces + 2 copies per hop, 16 hops
+  struct Piece {
+    void** d;         // filled by begin() (kAfter: unused)
+    const void* h;    // host buffer; nullptr = an absent optional buffer
+    const void* src;  // kAfter: the device source
+    size_t bytes;
+    int kind;
+  };
+  void declare(void** d, const void* h, size_t bytes, int kind);
+  Piece pieces_[kMaxPieces];
+  int n_ = 0;
+  bool overflow_ = false, direct_ = false, done_ = false;
+  void* block_ = nullptr;
+  GlxHostCallSlot admitted_;
+};
 
 #endif  // GLX_COMMON_H_

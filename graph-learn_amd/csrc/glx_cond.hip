@@ -469,27 +469,18 @@ extern "C" int glx_cond_negative_sample(const glx_cond_table* t, const glx_graph
   GLX_REQUIRE(t->num_cols == 0 || (dst_keys && props), "NULL dst_keys / props");
   GlxDeviceGuard guard(t->device);
   GLX_REQUIRE(guard.ok, "cannot select device %d", t->device);
-  hipStream_t s = ptr_kind == GLX_PTR_HOST ? glx_host_call_stream(stream, t->device) : glx_stream(stream);
   const int32_t ncols = t->num_cols;
-  // staged inputs
-  GlxTemp d_src, d_dst, d_keys, d_out, d_num, d_set, d_total;
-  const int64_t* p_src = src;
-  const int64_t* p_dst = dst;
-  const int64_t* p_keys = dst_keys;
-  int64_t* p_out = out;
-  if (ptr_kind == GLX_PTR_HOST) {
-    GLX_HIP(hipMalloc(&d_src.p, (size_t)batch * 8));
-    GLX_HIP(hipMalloc(&d_dst.p, (size_t)batch * 8));
-    GLX_HIP(hipMalloc(&d_keys.p, (size_t)batch * (size_t)(ncols > 0 ? ncols : 1) * 8));
-    GLX_HIP(hipMalloc(&d_out.p, (size_t)batch * count * 8));
-    GLX_HIP(hipMemcpyAsync(d_src.p, src, (size_t)batch * 8, hipMemcpyHostToDevice, s));
-    GLX_HIP(hipMemcpyAsync(d_dst.p, dst, (size_t)batch * 8, hipMemcpyHostToDevice, s));
-    if (ncols > 0) GLX_HIP(hipMemcpyAsync(d_keys.p, dst_keys, (size_t)batch * ncols * 8, hipMemcpyHostToDevice, s));
-    p_src = d_src.as<int64_t>();
-    p_dst = d_dst.as<int64_t>();
-    p_keys = d_keys.as<int64_t>();
-    p_out = d_out.as<int64_t>();
-  }
+  GlxHostStage st(t->device, ptr_kind, stream);
+  const hipStream_t s = st.s;
+  const int64_t *p_src, *p_dst, *p_keys;
+  int64_t* p_out;
+  st.in(&p_src, src, (size_t)batch);
+  st.in(&p_dst, dst, (size_t)batch);
+  st.in(&p_keys, ncols > 0 ? dst_keys : nullptr, (size_t)batch * ncols);
+  st.out(&p_out, out, (size_t)batch * count);
+  int rc = st.begin();
+  if (rc != GLX_OK) return st.finish(rc);
+  GlxTemp d_num, d_set, d_total;
   std::vector<int32_t> num_c((size_t)(ncols > 0 ? ncols : 1), 0);
   int64_t by_columns = 0;
   for (int32_t c = 0; c < ncols; ++c) {
@@ -583,9 +574,6 @@ extern "C" int glx_cond_negative_sample(const glx_cond_table* t, const glx_graph
     glx_cond_sample_kernel<<<1, 64, 0, s>>>(a);
   }
   GLX_HIP(hipGetLastError());
-  if (ptr_kind == GLX_PTR_HOST) {
-    GLX_HIP(hipMemcpyAsync(out, p_out, (size_t)batch * count * 8, hipMemcpyDeviceToHost, s));
-  }
-  GLX_HIP(hipStreamSynchronize(s));  // the temporaries are released on return
-  return GLX_OK;
+  if (!st.host) GLX_HIP(hipStreamSynchronize(s));  // the temporaries are released on return (finish() synchronises host calls)
+  return st.finish(GLX_OK);
 }

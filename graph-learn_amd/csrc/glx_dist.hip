@@ -2169,39 +2169,23 @@ extern "C" int glx_dist_sample(glx_dist_store* st, int sampler, const int64_t* s
               "tables cover its own edges only");
   GlxDeviceGuard guard(st->device);
   GLX_REQUIRE(guard.ok, "cannot select device %d", st->device);
-  if (ptr_kind == GLX_PTR_DEVICE) {
-    return dist_sample_device(st, sampler, src, batch, k, padding_mode, default_neighbor_id, seed, call_counter,
-                              filter, nbr_out, eid_out, glx_stream(stream));
-  }
-  hipStream_t s = glx_host_call_stream(stream, st->device);
+  GlxHostStage hs(st->device, ptr_kind, stream);
   const size_t n_out = (size_t)batch * k;
-  GlxTemp d;
-  GLX_HIP(hipMalloc(&d.p, ((size_t)batch * 2 + 2 * n_out + 4) * 8));
-  int64_t* d_src = d.as<int64_t>();
-  int64_t* d_val = d_src + batch;
-  int64_t* d_nbr = d_val + batch;
-  int64_t* d_eid = d_nbr + n_out;
-  if (batch) GLX_HIP(hipMemcpyAsync(d_src, src, (size_t)batch * 8, hipMemcpyHostToDevice, s));
+  const int64_t* d_src;
+  int64_t *d_nbr, *d_eid;
   glx_filter dev_filter;
-  const glx_filter* fp = nullptr;
-  if (filtered) {
-    if (batch) GLX_HIP(hipMemcpyAsync(d_val, filter->values, (size_t)batch * 8, hipMemcpyHostToDevice, s));
-    dev_filter = *filter;
-    dev_filter.values = d_val;
-    fp = &dev_filter;
+  const glx_filter* fp = filtered ? &dev_filter : nullptr;
+  if (filtered) dev_filter = *filter;
+  hs.in(&d_src, src, (size_t)batch);
+  if (filtered) hs.in(&dev_filter.values, filter->values, (size_t)batch);
+  hs.out(&d_nbr, nbr_out, n_out);
+  hs.out(&d_eid, eid_out, n_out);
+  rc = hs.begin();
+  if (rc == GLX_OK) {
+    rc = dist_sample_device(st, sampler, d_src, batch, k, padding_mode, default_neighbor_id, seed, call_counter,
+                            fp, d_nbr, d_eid, hs.s);
   }
-  rc = dist_sample_device(st, sampler, d_src, batch, k, padding_mode, default_neighbor_id, seed, call_counter, fp,
-                          d_nbr, d_eid, s);
-  hipError_t e = hipSuccess;
-  if (rc == GLX_OK && n_out) {
-    e = hipMemcpyAsync(nbr_out, d_nbr, n_out * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(eid_out, d_eid, n_out * 8, hipMemcpyDeviceToHost, s);
-  }
-  hipError_t e2 = hipStreamSynchronize(s);
-  if (rc != GLX_OK) return rc;
-  GLX_HIP(e);
-  GLX_HIP(e2);
-  return GLX_OK;
+  return hs.finish(rc);
 }
 
 namespace {
@@ -2220,32 +2204,26 @@ int dist_sample_full_any(glx_dist_store* st, const int64_t* src, int32_t batch, 
   GLX_REQUIRE(!fill || (capacity >= 0 && (capacity == 0 || (nbr_out && eid_out))), "bad response buffers");
   GlxDeviceGuard guard(st->device);
   GLX_REQUIRE(guard.ok, "cannot select device %d", st->device);
-  hipStream_t s = ptr_kind == GLX_PTR_HOST ? glx_host_call_stream(stream, st->device) : glx_stream(stream);
+  // the response's size is known only after the body: its copies are queued then
+  GlxHostStage hs(st->device, ptr_kind, stream);
+  const hipStream_t s = hs.s;
   const size_t nb = (size_t)batch;
-  GlxTemp stage;
-  const int64_t* d_src = src;
-  int32_t* d_deg = degrees_out;
-  int64_t* d_off = offsets_out;
-  int64_t* d_nbr = nbr_out;
-  int64_t* d_eid = eid_out;
+  const bool host = hs.host;
+  const int64_t* d_src;
+  int32_t* d_deg;
+  int64_t *d_off, *d_nbr = nbr_out, *d_eid = eid_out;
   glx_filter dev_filter;
   if (filtered) dev_filter = *filter;
-  if (ptr_kind == GLX_PTR_HOST) {
-    const size_t cap = fill ? (size_t)capacity : 0;
-    GLX_HIP(hipMalloc(&stage.p, (nb + (nb + 1) + 2 * cap + 2 + nb) * 8 + (nb + 2) * 4));
-    int64_t* b = stage.as<int64_t>();
-    if (nb) GLX_HIP(hipMemcpyAsync(b, src, nb * 8, hipMemcpyHostToDevice, s));
-    d_src = b;
-    d_off = b + nb;
-    d_nbr = d_off + nb + 1;
-    d_eid = d_nbr + cap;
-    int64_t* d_val = d_eid + cap;
-    d_deg = reinterpret_cast<int32_t*>(d_val + nb);
-    if (filtered && nb) {
-      GLX_HIP(hipMemcpyAsync(d_val, filter->values, nb * 8, hipMemcpyHostToDevice, s));
-      dev_filter.values = d_val;
-    }
+  hs.in(&d_src, src, nb);
+  if (filtered) hs.in(&dev_filter.values, filter->values, nb);
+  hs.out(&d_deg, degrees_out, nb);
+  hs.out(&d_off, offsets_out, nb + 1);
+  if (host && fill) {
+    hs.scratch(&d_nbr, (size_t)capacity);
+    hs.scratch(&d_eid, (size_t)capacity);
   }
+  rc = hs.begin();
+  if (rc != GLX_OK) return hs.finish(rc);
   int64_t total = 0;
   if (st->world == 1 && st->shortcut) {
     rc = glx_sample_full_sizes(st->graph, d_src, batch, max_limit, d_deg, d_off, GLX_PTR_DEVICE, s);
@@ -2263,16 +2241,12 @@ int dist_sample_full_any(glx_dist_store* st, const int64_t* src, int32_t batch, 
                                  filtered ? &dev_filter : nullptr, padding_mode, default_neighbor_id);
     if (rc != GLX_OK) return rc;
   }
-  if (ptr_kind == GLX_PTR_HOST) {
-    if (nb) GLX_HIP(hipMemcpyAsync(degrees_out, d_deg, nb * 4, hipMemcpyDeviceToHost, s));
-    GLX_HIP(hipMemcpyAsync(offsets_out, d_off, (nb + 1) * 8, hipMemcpyDeviceToHost, s));
-    if (fill && total > 0) {
-      GLX_HIP(hipMemcpyAsync(nbr_out, d_nbr, (size_t)total * 8, hipMemcpyDeviceToHost, s));
-      GLX_HIP(hipMemcpyAsync(eid_out, d_eid, (size_t)total * 8, hipMemcpyDeviceToHost, s));
-    }
+  if (fill && total > 0) {
+    hs.out_after(nbr_out, d_nbr, (size_t)total * 8);
+    hs.out_after(eid_out, d_eid, (size_t)total * 8);
   }
-  GLX_HIP(hipStreamSynchronize(s));
-  return GLX_OK;
+  if (!host) GLX_HIP(hipStreamSynchronize(s));
+  return hs.finish(GLX_OK);
 }
 }  // namespace
 
@@ -2311,22 +2285,26 @@ int dist_random_walk(glx_dist_store* st, const int64_t* seeds, int32_t batch, in
               full_nbr_num);
   GlxDeviceGuard guard(st->device);
   GLX_REQUIRE(guard.ok, "cannot select device %d", st->device);
-  hipStream_t s = ptr_kind == GLX_PTR_HOST ? glx_host_call_stream(stream, st->device) : glx_stream(stream);
   if (!deep && st->world == 1 && st->shortcut) {
     return glx_random_walk(st->graph, seeds, batch, walk_len, p, q, full_nbr_num, default_weight, default_neighbor_id, seed,
                            call_counter, walks_out, ptr_kind, stream);
   }
   const size_t nb = (size_t)(batch > 0 ? batch : 1), total = (size_t)batch * (size_t)walk_len;
-  GlxTemp buf;
-  GLX_HIP(hipMalloc(&buf.p, (nb * 4 + (ptr_kind == GLX_PTR_HOST ? total : 0) + 2) * 8));
+  GlxHostStage hs(st->device, ptr_kind, stream);
+  const hipStream_t s = hs.s;
+  const int64_t* d_seeds;
+  int64_t* d_walks;
+  hs.in(&d_seeds, seeds, (size_t)batch);
+  hs.out(&d_walks, walks_out, total);
+  rc = hs.begin();
+  if (rc != GLX_OK) return hs.finish(rc);
+  GlxTemp buf;  // the walkers' state: a device body's own space, whatever the pointer kind
+  GLX_HIP(hipMalloc(&buf.p, (nb * 4 + 2) * 8));
   int64_t* cur = buf.as<int64_t>();
   int64_t* nxt = cur + nb;
   int64_t* eid = nxt + nb;
   int64_t* par = eid + nb;  // node2vec: the vertex each walker came from
-  int64_t* d_walks = ptr_kind == GLX_PTR_HOST ? par + nb : walks_out;
-  if (batch > 0) {
-    GLX_HIP(hipMemcpyAsync(cur, seeds, (size_t)batch * 8, ptr_kind == GLX_PTR_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
-  }
+  if (batch > 0) GLX_HIP(hipMemcpyAsync(cur, d_seeds, (size_t)batch * 8, hipMemcpyDeviceToDevice, s));
   if (deep) {
     // DeepWalk (random_walk.cc:168-190): step t of walker i = RandomSampler's draw 0 of the stream (seed, call_counter + t,
     // i) on the vertex it stands on -- one partitioned request with neighbor_count 1 per step, every walker a row; a
@@ -2398,12 +2376,8 @@ int dist_random_walk(glx_dist_store* st, const int64_t* seeds, int32_t batch, in
     }
     GLX_HIP(hipStreamSynchronize(s));  // `lists` is released on return
   }
-  GLX_HIP(hipGetLastError());
-  if (ptr_kind == GLX_PTR_HOST && total > 0) {
-    GLX_HIP(hipMemcpyAsync(walks_out, d_walks, total * 8, hipMemcpyDeviceToHost, s));
-  }
-  GLX_HIP(hipStreamSynchronize(s));
-  return GLX_OK;
+  if (!hs.host) GLX_HIP(hipStreamSynchronize(s));
+  return hs.finish(GLX_OK);
 }
 }  // namespace
 
@@ -2444,30 +2418,18 @@ extern "C" int glx_dist_aggregate(glx_dist_store* st, int op, const int64_t* nod
     return glx_aggregate(f, op, node_ids, segment_ids, num_ids, num_segments, default_attr, emb_out, cnt_out,
                          ptr_kind, stream);
   }
-  hipStream_t s = ptr_kind == GLX_PTR_HOST ? glx_host_call_stream(stream, st->device) : glx_stream(stream);
-  const int64_t* d_ids = node_ids;
-  const int32_t* d_seg = segment_ids;
-  float* d_emb = emb_out;
-  int32_t* d_cnt = cnt_out;
-  GlxTemp stage;
-  const size_t emb_n = (size_t)num_segments * f->dim;
-  if (ptr_kind == GLX_PTR_HOST) {
-    const size_t emb_b = (emb_n * 4 + 255) & ~(size_t)255;
-    const size_t ids_b = ((size_t)num_ids * 8 + 255) & ~(size_t)255;
-    const size_t seg_b = ((size_t)num_ids * 4 + 255) & ~(size_t)255;
-    GLX_HIP(hipMalloc(&stage.p, emb_b + ids_b + seg_b + (size_t)num_segments * 4 + 256));
-    char* b = stage.as<char>();
-    d_emb = reinterpret_cast<float*>(b);
-    int64_t* ids_w = reinterpret_cast<int64_t*>(b + emb_b);
-    int32_t* seg_w = reinterpret_cast<int32_t*>(b + emb_b + ids_b);
-    d_cnt = reinterpret_cast<int32_t*>(b + emb_b + ids_b + seg_b);
-    if (num_ids) GLX_HIP(hipMemcpyAsync(ids_w, node_ids, (size_t)num_ids * 8, hipMemcpyHostToDevice, s));
-    if (num_ids && segment_ids) {
-      GLX_HIP(hipMemcpyAsync(seg_w, segment_ids, (size_t)num_ids * 4, hipMemcpyHostToDevice, s));
-    }
-    d_ids = ids_w;
-    d_seg = segment_ids ? seg_w : nullptr;
-  }
+  GlxHostStage hs(st->device, ptr_kind, stream);
+  const hipStream_t s = hs.s;
+  const int64_t* d_ids;
+  const int32_t* d_seg;
+  float* d_emb;
+  int32_t* d_cnt;
+  hs.in(&d_ids, node_ids, (size_t)num_ids);
+  hs.in(&d_seg, segment_ids, (size_t)num_ids);
+  hs.out(&d_emb, emb_out, (size_t)num_segments * f->dim);
+  hs.out(&d_cnt, cnt_out, (size_t)num_segments);
+  rc = hs.begin();
+  if (rc != GLX_OK) return hs.finish(rc);
   Resolved rs;
   rc = resolve_and_fetch(st, 0, d_ids, num_ids, default_attr, s, &rs);
   st->slots[0].num_ids = -1;  // a whole call: nothing left pending in the slot
@@ -2475,18 +2437,7 @@ extern "C" int glx_dist_aggregate(glx_dist_store* st, int op, const int64_t* nod
     rc = glx_aggregate_vrows_device(rs.src, 3, f->dim, op, rs.loc, d_seg, num_ids, num_segments, default_attr, d_emb,
                                     d_cnt, s);
   }
-  if (ptr_kind == GLX_PTR_HOST) {
-    hipError_t e = hipSuccess;
-    if (rc == GLX_OK && num_segments > 0) {
-      e = hipMemcpyAsync(emb_out, d_emb, emb_n * 4, hipMemcpyDeviceToHost, s);
-      if (e == hipSuccess) e = hipMemcpyAsync(cnt_out, d_cnt, (size_t)num_segments * 4, hipMemcpyDeviceToHost, s);
-    }
-    hipError_t e2 = hipStreamSynchronize(s);
-    if (rc != GLX_OK) return rc;
-    GLX_HIP(e);
-    GLX_HIP(e2);
-  }
-  return rc;
+  return hs.finish(rc);
 }
 
 namespace {
@@ -2628,24 +2579,20 @@ extern "C" int glx_dist_aggregate_partial(glx_dist_store* st, int op, const int6
     return dist_aggregate_partial_device(st, op, node_ids, segment_ids, num_ids, num_segments, default_attr, emb_out,
                                          cnt_out, s);
   }
-  const glx_features* f = st->feats;
-  const size_t emb_n = (size_t)num_segments * f->dim;
-  GlxTemp d_ids, d_seg, d_emb, d_cnt;
-  GLX_HIP(hipMalloc(&d_ids.p, (size_t)(num_ids > 0 ? num_ids : 1) * 8));
-  GLX_HIP(hipMalloc(&d_seg.p, (size_t)(num_ids > 0 ? num_ids : 1) * 4));
-  GLX_HIP(hipMalloc(&d_emb.p, (emb_n > 0 ? emb_n : 1) * 4));
-  GLX_HIP(hipMalloc(&d_cnt.p, (size_t)(num_segments > 0 ? num_segments : 1) * 4));
-  if (num_ids) GLX_HIP(hipMemcpyAsync(d_ids.p, node_ids, (size_t)num_ids * 8, hipMemcpyHostToDevice, s));
-  if (num_ids && segment_ids) GLX_HIP(hipMemcpyAsync(d_seg.p, segment_ids, (size_t)num_ids * 4, hipMemcpyHostToDevice, s));
-  rc = dist_aggregate_partial_device(st, op, d_ids.as<int64_t>(), segment_ids ? d_seg.as<int32_t>() : nullptr, num_ids,
-                                     num_segments, default_attr, d_emb.as<float>(), d_cnt.as<int32_t>(), s);
-  if (rc != GLX_OK) return rc;
-  if (num_segments > 0) {
-    GLX_HIP(hipMemcpyAsync(emb_out, d_emb.p, emb_n * 4, hipMemcpyDeviceToHost, s));
-    GLX_HIP(hipMemcpyAsync(cnt_out, d_cnt.p, (size_t)num_segments * 4, hipMemcpyDeviceToHost, s));
+  GlxHostStage hs(st->device, ptr_kind, stream);
+  const int64_t* d_ids;
+  const int32_t* d_seg;
+  float* d_emb;
+  int32_t* d_cnt;
+  hs.in(&d_ids, node_ids, (size_t)num_ids);
+  hs.in(&d_seg, segment_ids, (size_t)num_ids);
+  hs.out(&d_emb, emb_out, (size_t)num_segments * st->feats->dim);
+  hs.out(&d_cnt, cnt_out, (size_t)num_segments);
+  rc = hs.begin();
+  if (rc == GLX_OK) {
+    rc = dist_aggregate_partial_device(st, op, d_ids, d_seg, num_ids, num_segments, default_attr, d_emb, d_cnt, hs.s);
   }
-  GLX_HIP(hipStreamSynchronize(s));
-  return GLX_OK;
+  return hs.finish(rc);
 }
 
 // The two halves of glx_dist_aggregate for software pipelining (device pointers only).
@@ -2712,18 +2659,14 @@ extern "C" int glx_dist_lookup(glx_dist_store* st, const int64_t* node_ids, int6
   GlxDeviceGuard guard(st->device);
   GLX_REQUIRE(guard.ok, "cannot select device %d", st->device);
   const glx_features* f = st->feats;
-  hipStream_t s = ptr_kind == GLX_PTR_HOST ? glx_host_call_stream(stream, st->device) : glx_stream(stream);
-  const int64_t* d_ids = node_ids;
-  float* d_out = out;
-  GlxTemp stage;
-  const size_t out_b = (size_t)n * f->dim * 4;
-  if (ptr_kind == GLX_PTR_HOST) {
-    GLX_HIP(hipMalloc(&stage.p, ((out_b + 255) & ~(size_t)255) + (size_t)n * 8 + 256));
-    d_out = stage.as<float>();
-    int64_t* ids_w = reinterpret_cast<int64_t*>(stage.as<char>() + ((out_b + 255) & ~(size_t)255));
-    if (n) GLX_HIP(hipMemcpyAsync(ids_w, node_ids, (size_t)n * 8, hipMemcpyHostToDevice, s));
-    d_ids = ids_w;
-  }
+  GlxHostStage hs(st->device, ptr_kind, stream);
+  const hipStream_t s = hs.s;
+  const int64_t* d_ids;
+  float* d_out;
+  hs.in(&d_ids, node_ids, (size_t)n);
+  hs.out(&d_out, out, (size_t)n * f->dim);
+  rc = hs.begin();
+  if (rc != GLX_OK) return hs.finish(rc);
   Resolved rs;
   rc = resolve_and_fetch(st, 0, d_ids, n, default_attr, s, &rs);
   st->slots[0].num_ids = -1;
@@ -2741,21 +2684,8 @@ extern "C" int glx_dist_lookup(glx_dist_store* st, const int64_t* node_ids, int6
     while (G < 64 && G < f->dim) G <<= 1;
     const int64_t threads = n * G;
     glx_dist_gather_rows_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, s>>>(g, G);
-    hipError_t le = hipGetLastError();
-    if (le != hipSuccess) {
-      glx_set_error("gather launch failed: %s", hipGetErrorString(le));
-      rc = GLX_INTERNAL;
-    }
   }
-  if (ptr_kind == GLX_PTR_HOST) {
-    hipError_t e = hipSuccess;
-    if (rc == GLX_OK && n > 0) e = hipMemcpyAsync(out, d_out, out_b, hipMemcpyDeviceToHost, s);
-    hipError_t e2 = hipStreamSynchronize(s);
-    if (rc != GLX_OK) return rc;
-    GLX_HIP(e);
-    GLX_HIP(e2);
-  }
-  return rc;
+  return hs.finish(rc);
 }
 
 // Collective: every rank holds the same hot id list; each fetches its owned rows once and
@@ -3115,21 +3045,19 @@ extern "C" int glx_dist_in_degrees(glx_dist_store* st, const int64_t* ids, int32
   GLX_REQUIRE(n >= 0 && (n == 0 || (ids && degrees_out)), "bad request");
   GlxDeviceGuard guard(st->device);
   GLX_REQUIRE(guard.ok, "cannot select device %d", st->device);
-  hipStream_t s = ptr_kind == GLX_PTR_HOST ? glx_host_call_stream(stream, st->device) : glx_stream(stream);
+  GlxHostStage hs(st->device, ptr_kind, stream);
+  const hipStream_t s = hs.s;
   rc = ensure_owner_table(st, s);
   if (rc != GLX_OK) return rc;
   const int P = st->world;
   const int64_t n1 = n > 0 ? n : 1;
-  GlxTemp d_ids, buck, ord, ids_in, cnt_in, cnt_b, d_out;
-  const int64_t* p_ids = ids;
-  int32_t* p_out = degrees_out;
-  if (ptr_kind == GLX_PTR_HOST) {
-    GLX_HIP(hipMalloc(&d_ids.p, (size_t)n1 * 8));
-    GLX_HIP(hipMalloc(&d_out.p, (size_t)n1 * 4));
-    if (n > 0) GLX_HIP(hipMemcpyAsync(d_ids.p, ids, (size_t)n * 8, hipMemcpyHostToDevice, s));
-    p_ids = d_ids.as<int64_t>();
-    p_out = d_out.as<int32_t>();
-  }
+  const int64_t* p_ids;
+  int32_t* p_out;
+  hs.in(&p_ids, ids, (size_t)n);
+  hs.out(&p_out, degrees_out, (size_t)n);
+  rc = hs.begin();
+  if (rc != GLX_OK) return hs.finish(rc);
+  GlxTemp buck, ord, ids_in, cnt_in, cnt_b;
   GLX_HIP(hipMalloc(&buck.p, (size_t)n1 * 8));
   GLX_HIP(hipMalloc(&ord.p, (size_t)n1 * 8));
   GLX_HIP(hipMalloc(&cnt_b.p, (size_t)n1 * 8));
@@ -3157,11 +3085,9 @@ extern "C" int glx_dist_in_degrees(glx_dist_store* st, const int64_t* ids, int32
   if (rc != GLX_OK) return rc;
   if (n > 0) {
     glx_dist_stitch_narrow_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(cnt_b.as<int64_t>(), ord.as<int64_t>(), n, p_out);
-    GLX_HIP(hipGetLastError());
-    if (ptr_kind == GLX_PTR_HOST) GLX_HIP(hipMemcpyAsync(degrees_out, p_out, (size_t)n * 4, hipMemcpyDeviceToHost, s));
   }
-  GLX_HIP(hipStreamSynchronize(s));
-  return GLX_OK;
+  if (!hs.host) GLX_HIP(hipStreamSynchronize(s));  // the temporaries are released on return
+  return hs.finish(GLX_OK);
 }
 
 // Collective.  The candidate list of the negative samplers over the WHOLE edge type, on every rank
@@ -3238,19 +3164,17 @@ extern "C" int glx_dist_negative_sample(glx_dist_store* st, const glx_negative* 
   GLX_REQUIRE(batch == 0 || count == 0 || (src && out), "NULL data pointer");
   GlxDeviceGuard guard(st->device);
   GLX_REQUIRE(guard.ok, "cannot select device %d", st->device);
-  hipStream_t s = ptr_kind == GLX_PTR_HOST ? glx_host_call_stream(stream, st->device) : glx_stream(stream);
   const int P = st->world;
   const int64_t n = batch, n1 = n > 0 ? n : 1, k = count, k1 = k > 0 ? k : 1;
-  GlxTemp d_src, d_out, buck, ord, back, ids_in, rows_in, loc;
-  const int64_t* p_src = src;
-  int64_t* p_out = out;
-  if (ptr_kind == GLX_PTR_HOST) {
-    GLX_HIP(hipMalloc(&d_src.p, (size_t)n1 * 8));
-    GLX_HIP(hipMalloc(&d_out.p, (size_t)n1 * k1 * 8));
-    if (n > 0) GLX_HIP(hipMemcpyAsync(d_src.p, src, (size_t)n * 8, hipMemcpyHostToDevice, s));
-    p_src = d_src.as<int64_t>();
-    p_out = d_out.as<int64_t>();
-  }
+  GlxHostStage hs(st->device, ptr_kind, stream);
+  const hipStream_t s = hs.s;
+  const int64_t* p_src;
+  int64_t* p_out;
+  hs.in(&p_src, src, (size_t)n);
+  hs.out(&p_out, out, (size_t)(n * k));
+  rc = hs.begin();
+  if (rc != GLX_OK) return hs.finish(rc);
+  GlxTemp buck, ord, back, ids_in, rows_in, loc;
   GLX_HIP(hipMalloc(&buck.p, (size_t)n1 * 8));
   GLX_HIP(hipMalloc(&ord.p, (size_t)n1 * 8));
   GLX_HIP(hipMalloc(&back.p, (size_t)n1 * k1 * 8));
@@ -3302,11 +3226,9 @@ extern "C" int glx_dist_negative_sample(glx_dist_store* st, const glx_negative* 
     const int64_t total = n * k;
     glx_dist_stitch2_kernel<<<(unsigned)((total + 255) / 256), 256, 0, s>>>(back.as<int64_t>(), back.as<int64_t>(),
                                                                             ord.as<int64_t>(), n, count, p_out, p_out);
-    GLX_HIP(hipGetLastError());
-    if (ptr_kind == GLX_PTR_HOST) GLX_HIP(hipMemcpyAsync(out, p_out, (size_t)total * 8, hipMemcpyDeviceToHost, s));
   }
-  GLX_HIP(hipStreamSynchronize(s));
-  return GLX_OK;
+  if (!hs.host) GLX_HIP(hipStreamSynchronize(s));  // the temporaries are released on return
+  return hs.finish(GLX_OK);
 }
 
 // Collective: InDegreeSampler on a partitioned edge type.  A neighbour's weight is its in-degree over ALL

@@ -728,9 +728,10 @@ int dedup_min_rows() {
     size_t bytes__ = 0;                                                        \
     void* tmp__ = nullptr;                                                     \
     GLX_HIP(call_with(tmp__, bytes__));                                        \
-    int rc__ = glx_scratch_alloc(&tmp__, bytes__ ? bytes__ : 8, s, 3);         \
+    GlxScratch lease__;                                                        \
+    int rc__ = lease__.alloc(bytes__ ? bytes__ : 8, s, 3);                     \
     if (rc__ != GLX_OK) return rc__;                                           \
-    GLX_HIP(call_with(tmp__, bytes__));                                        \
+    GLX_HIP(call_with(lease__.p, bytes__));                                    \
   } while (0)
 
 // EdgeWeight / InDegree under circular padding, any filter: start / deg are the request rows' (filled by the caller).
@@ -740,9 +741,10 @@ int filtered_alias_dedup(const glx_graph* g, int sampler, const int64_t* d_rng, 
   const size_t nb = (size_t)batch;
   const bool same_value = f.field == GLX_FILTER_FIELD_TIMESTAMP && f.type == GLX_FILTER_LARGER_THAN;
   // i64: key1 key2 k1s k2s sub_start sub_val soff_u[nb + 1] ; i32: iota permA perm flag uid1 sub_deg cnt_u run_begin[nb + 1]
-  char* buf = nullptr;
-  int rc = glx_scratch_alloc(reinterpret_cast<void**>(&buf), (nb * 7 + 1) * 8 + (nb * 8 + 1) * 4 + 16, s, 6);
+  GlxScratch buf_lease;
+  int rc = buf_lease.alloc((nb * 7 + 1) * 8 + (nb * 8 + 1) * 4 + 16, s, 6);
   if (rc != GLX_OK) return rc;
+  char* buf = buf_lease.as<char>();
   int64_t* key1 = reinterpret_cast<int64_t*>(buf);
   int64_t* key2 = key1 + nb;
   int64_t* k1s = key2 + nb;
@@ -806,9 +808,10 @@ int filtered_alias_dedup(const glx_graph* g, int sampler, const int64_t* d_rng, 
     a = b;
   }
   const size_t span = ((size_t)widest + 1) & ~(size_t)1;
-  char* work = nullptr;
-  rc = glx_scratch_alloc(reinterpret_cast<void**>(&work), span * 24 + 16, s, 2);
+  GlxScratch work_lease;
+  rc = work_lease.alloc(span * 24 + 16, s, 2);
   if (rc != GLX_OK) return rc;
+  char* work = work_lease.as<char>();
   GlxAlias* tab = reinterpret_cast<GlxAlias*>(work);
   GlxAlias* stk = reinterpret_cast<GlxAlias*>(work + span * 8);
   int32_t* res = reinterpret_cast<int32_t*>(work + span * 16);
@@ -848,9 +851,10 @@ int filtered_general(const glx_graph* g, int sampler, const int64_t* d_src, cons
   const bool circular = padding_mode == GLX_PAD_CIRCULAR;
   const size_t nb = (size_t)batch;
   // row info: start[batch] i64 | soff[batch + 1] i64 | deg[batch] i32 | cnt[batch] i32
-  char* info = nullptr;
-  int rc = glx_scratch_alloc(reinterpret_cast<void**>(&info), (nb * 2 + 1) * 8 + nb * 2 * 4, s, 1);
+  GlxScratch info_lease;
+  int rc = info_lease.alloc((nb * 2 + 1) * 8 + nb * 2 * 4, s, 1);
   if (rc != GLX_OK) return rc;
+  char* info = info_lease.as<char>();
   int64_t* start = reinterpret_cast<int64_t*>(info);
   int64_t* soff = start + nb;
   int32_t* deg = reinterpret_cast<int32_t*>(soff + nb + 1);
@@ -898,10 +902,10 @@ int filtered_general(const glx_graph* g, int sampler, const int64_t* d_src, cons
   {
     size_t bytes = 0;
     GLX_HIP(rocprim::inclusive_scan(nullptr, bytes, soff + 1, soff + 1, nb, rocprim::plus<int64_t>(), s));
-    void* tmp = nullptr;
-    rc = glx_scratch_alloc(&tmp, bytes, s, 3);
+    GlxScratch tmp;
+    rc = tmp.alloc(bytes, s, 3);
     if (rc != GLX_OK) return rc;
-    GLX_HIP(rocprim::inclusive_scan(tmp, bytes, soff + 1, soff + 1, nb, rocprim::plus<int64_t>(), s));
+    GLX_HIP(rocprim::inclusive_scan(tmp.p, bytes, soff + 1, soff + 1, nb, rocprim::plus<int64_t>(), s));
   }
   std::vector<int64_t> h_soff(nb + 1);
   GLX_HIP(hipMemcpyAsync(h_soff.data(), soff, (nb + 1) * 8, hipMemcpyDeviceToHost, s));
@@ -920,9 +924,10 @@ int filtered_general(const glx_graph* g, int sampler, const int64_t* d_src, cons
   }
   // [alias table 8 B | stack pairs 8 B |] reserved positions i32 [| weights f32], each `span` long
   const size_t span = ((size_t)widest + 1) & ~(size_t)1;  // keeps the 8-byte table aligned
-  char* work = nullptr;
-  rc = glx_scratch_alloc(reinterpret_cast<void**>(&work), span * (alias_draw ? 24 : 4) + 16, s, 2);
+  GlxScratch work_lease;
+  rc = work_lease.alloc(span * (alias_draw ? 24 : 4) + 16, s, 2);
   if (rc != GLX_OK) return rc;
+  char* work = work_lease.as<char>();
   GlxAlias* tab = reinterpret_cast<GlxAlias*>(work);
   GlxAlias* stk = reinterpret_cast<GlxAlias*>(work + span * 8);
   int32_t* res = alias_draw ? reinterpret_cast<int32_t*>(work + span * 16) : reinterpret_cast<int32_t*>(work);
@@ -980,10 +985,10 @@ int filtered_device(const glx_graph* g, int sampler, const int64_t* d_src, const
   // start | sub_src | sub_rng | sub_val (i64) ; deg | nhits | general | gidx | hit_lo (i32) ; hits (i32 x kMaxHits,
   // only without the index) ; count
   const bool indexed = g->nbr_sorted && g->slot_sorted;
-  char* buf = nullptr;
-  int rc = glx_scratch_alloc(reinterpret_cast<void**>(&buf),
-                             nb * 4 * 8 + nb * 5 * 4 + (indexed ? 0 : nb * kMaxHits * 4) + 64, s, 4);
+  GlxScratch buf_lease;
+  int rc = buf_lease.alloc(nb * 4 * 8 + nb * 5 * 4 + (indexed ? 0 : nb * kMaxHits * 4) + 64, s, 4);
   if (rc != GLX_OK) return rc;
+  char* buf = buf_lease.as<char>();
   int64_t* start = reinterpret_cast<int64_t*>(buf);
   int64_t* sub_src = start + nb;
   int64_t* sub_rng = sub_src + nb;
@@ -1034,9 +1039,10 @@ int filtered_device(const glx_graph* g, int sampler, const int64_t* d_src, const
   GLX_HIP(hipGetLastError());
   GLX_HIP(hipStreamSynchronize(s));
   if (G > 0) {
-    int64_t* sub_out = nullptr;
-    rc = glx_scratch_alloc(reinterpret_cast<void**>(&sub_out), (size_t)G * k * 2 * 8, s, 5);
+    GlxScratch sub_lease;
+    rc = sub_lease.alloc((size_t)G * k * 2 * 8, s, 5);
     if (rc != GLX_OK) return rc;
+    int64_t* sub_out = sub_lease.as<int64_t>();
     FilterDev fs = f;
     fs.values = sub_val;
     rc = filtered_general(g, sampler, sub_src, sub_rng, G, k, nullptr, padding_mode, default_nbr, seed, cc, fs, sub_out,
@@ -1062,16 +1068,6 @@ int check_filter(const glx_graph* g, const glx_filter* filter) {
 
 // Stages host arrays next to each other in one slot-0 workspace; entries with a NULL source
 // are outputs (or absent).
-struct Staged {
-  int64_t* d = nullptr;
-  size_t used = 0;
-  int64_t* take(size_t n) {
-    int64_t* p = d + used;
-    used += n;
-    return p;
-  }
-};
-
 }  // namespace
 
 extern "C" int glx_graph_set_timestamps(glx_graph* g, const int64_t* ts_slot, int ptr_kind, void* stream) {
@@ -1120,41 +1116,23 @@ extern "C" int glx_sample_filtered(const glx_graph* g, int sampler, const int64_
               "InDegreeSampler needs glx_graph_enable_in_degree()");
   GlxDeviceGuard guard(g->device);
   GLX_REQUIRE(guard.ok, "cannot select device %d", g->device);
-  hipStream_t s = ptr_kind == GLX_PTR_HOST ? glx_host_call_stream(stream, g->device) : glx_stream(stream);
   FilterDev f{filter->type, filter->field, filter->values, g->ts, filter->default_timestamp, filter->retry_times};
-  if (ptr_kind == GLX_PTR_DEVICE) {
-    return filtered_device(g, sampler, src, rng_rows, batch, k, nullptr, padding_mode, default_neighbor_id, seed,
-                           call_counter, f, nbr_out, eid_out, s);
-  }
-  GlxHostCallSlot admitted(g->device);
+  // pinned caller buffers are written directly
+  GlxHostStage st(g->device, ptr_kind, stream, GlxHostStage::ADMIT | GlxHostStage::DIRECT_PINNED);
   const size_t nb = (size_t)batch, n_out = nb * (size_t)k;
-  int64_t* m_nbr = static_cast<int64_t*>(glx_mapped_ptr(nbr_out, n_out * 8));  // pinned caller buffers are written directly
-  int64_t* m_eid = static_cast<int64_t*>(glx_mapped_ptr(eid_out, n_out * 8));
-  const bool direct = m_nbr != nullptr && m_eid != nullptr;
-  Staged st;
-  rc = glx_scratch_alloc(reinterpret_cast<void**>(&st.d), (nb * 3 + (direct ? 0 : n_out * 2)) * 8, s, 0);
-  if (rc != GLX_OK) return rc;
-  int64_t* d_src = st.take(nb);
-  int64_t* d_val = st.take(nb);
-  int64_t* d_rng = rng_rows ? st.take(nb) : nullptr;
-  int64_t* d_nbr = direct ? m_nbr : st.take(n_out);
-  int64_t* d_eid = direct ? m_eid : st.take(n_out);
-  GLX_HIP(hipMemcpyAsync(d_src, src, nb * 8, hipMemcpyHostToDevice, s));
-  GLX_HIP(hipMemcpyAsync(d_val, filter->values, nb * 8, hipMemcpyHostToDevice, s));
-  if (rng_rows) GLX_HIP(hipMemcpyAsync(d_rng, rng_rows, nb * 8, hipMemcpyHostToDevice, s));
-  f.values = d_val;
-  rc = filtered_device(g, sampler, d_src, d_rng, batch, k, nullptr, padding_mode, default_neighbor_id, seed,
-                       call_counter, f, d_nbr, d_eid, s);
-  if (rc != GLX_OK) {
-    (void)hipStreamSynchronize(s);
-    return rc;
+  const int64_t *d_src, *d_rng;
+  int64_t *d_nbr, *d_eid;
+  st.in(&d_src, src, nb);
+  st.in(&f.values, filter->values, nb);
+  st.in(&d_rng, rng_rows, nb);
+  st.out(&d_nbr, nbr_out, n_out);
+  st.out(&d_eid, eid_out, n_out);
+  rc = st.begin();
+  if (rc == GLX_OK) {
+    rc = filtered_device(g, sampler, d_src, d_rng, batch, k, nullptr, padding_mode, default_neighbor_id, seed,
+                         call_counter, f, d_nbr, d_eid, st.s);
   }
-  if (!direct) {
-    GLX_HIP(hipMemcpyAsync(nbr_out, d_nbr, n_out * 8, hipMemcpyDeviceToHost, s));
-    GLX_HIP(hipMemcpyAsync(eid_out, d_eid, n_out * 8, hipMemcpyDeviceToHost, s));
-  }
-  GLX_HIP(hipStreamSynchronize(s));
-  return GLX_OK;
+  return st.finish(rc);
 }
 
 extern "C" int glx_sample_full_filtered(const glx_graph* g, const int64_t* src, int32_t batch, int32_t max_limit,
@@ -1189,31 +1167,23 @@ extern "C" int glx_sample_full_filtered(const glx_graph* g, const int64_t* src, 
     return filtered_device(g, kFullSampler, src, nullptr, batch, 0, offsets, padding_mode, default_neighbor_id, 0, 0,
                            f, nbr_out, eid_out, s);
   }
-  const size_t nb = (size_t)batch;
   const int64_t total = offsets[batch];
   GLX_REQUIRE(total >= 0, "bad offsets");
   if (total == 0) return GLX_OK;
   GLX_REQUIRE(nbr_out && eid_out, "NULL output pointer");
-  Staged st;
-  rc = glx_scratch_alloc(reinterpret_cast<void**>(&st.d), (nb * 3 + 1 + (size_t)total * 2) * 8, s, 0);
-  if (rc != GLX_OK) return rc;
-  int64_t* d_src = st.take(nb);
-  int64_t* d_val = st.take(nb);
-  int64_t* d_off = st.take(nb + 1);
-  int64_t* d_nbr = st.take((size_t)total);
-  int64_t* d_eid = st.take((size_t)total);
-  GLX_HIP(hipMemcpyAsync(d_src, src, nb * 8, hipMemcpyHostToDevice, s));
-  GLX_HIP(hipMemcpyAsync(d_val, filter->values, nb * 8, hipMemcpyHostToDevice, s));
-  GLX_HIP(hipMemcpyAsync(d_off, offsets, (nb + 1) * 8, hipMemcpyHostToDevice, s));
-  f.values = d_val;
-  rc = filtered_device(g, kFullSampler, d_src, nullptr, batch, 0, d_off, padding_mode, default_neighbor_id, 0, 0, f,
-                       d_nbr, d_eid, s);
-  if (rc != GLX_OK) {
-    (void)hipStreamSynchronize(s);
-    return rc;
+  GlxHostStage st(g->device, ptr_kind, stream);
+  const size_t nb = (size_t)batch;
+  const int64_t *d_src, *d_off;
+  int64_t *d_nbr, *d_eid;
+  st.in(&d_src, src, nb);
+  st.in(&f.values, filter->values, nb);
+  st.in(&d_off, offsets, nb + 1);
+  st.out(&d_nbr, nbr_out, (size_t)total);
+  st.out(&d_eid, eid_out, (size_t)total);
+  rc = st.begin();
+  if (rc == GLX_OK) {
+    rc = filtered_device(g, kFullSampler, d_src, nullptr, batch, 0, d_off, padding_mode, default_neighbor_id, 0, 0, f,
+                         d_nbr, d_eid, st.s);
   }
-  GLX_HIP(hipMemcpyAsync(nbr_out, d_nbr, (size_t)total * 8, hipMemcpyDeviceToHost, s));
-  GLX_HIP(hipMemcpyAsync(eid_out, d_eid, (size_t)total * 8, hipMemcpyDeviceToHost, s));
-  GLX_HIP(hipStreamSynchronize(s));
-  return GLX_OK;
+  return st.finish(rc);
 }

@@ -205,30 +205,20 @@ extern "C" int glx_graph_in_degrees(const glx_graph* g, const int64_t* ids, int6
   if (n == 0) return GLX_OK;
   GlxDeviceGuard guard(g->device);
   GLX_REQUIRE(guard.ok, "cannot select device %d", g->device);
-  const bool host = ptr_kind == GLX_PTR_HOST;
-  hipStream_t s = host ? glx_host_call_stream(stream, g->device) : glx_stream(stream);
-  const int64_t* d_ids = ids;
-  int64_t* d_out = deg_out;
-  int64_t* scratch = nullptr;
-  if (host) {
-    int rc = glx_scratch_alloc(reinterpret_cast<void**>(&scratch), (size_t)n * 16, s, 0);
-    if (rc != GLX_OK) return rc;
-    GLX_HIP(hipMemcpyAsync(scratch, ids, (size_t)n * 8, hipMemcpyHostToDevice, s));
-    d_ids = scratch;
-    d_out = scratch + n;
-  }
+  GlxHostStage st(g->device, ptr_kind, stream);
+  const int64_t* d_ids;
+  int64_t* d_out;
+  st.in(&d_ids, ids, (size_t)n);
+  st.out(&d_out, deg_out, (size_t)n);
+  int rc = st.begin();
+  if (rc != GLX_OK) return st.finish(rc);
   if (g->num_dst == 0) {
-    GLX_HIP(hipMemsetAsync(d_out, 0, (size_t)n * 8, s));
+    GLX_HIP(hipMemsetAsync(d_out, 0, (size_t)n * 8, st.s));
   } else {
     const GlxIdMap map{g->dst_map.keys, g->dst_map.vals, g->dst_map.cap - 1, g->num_dst};
-    glx_in_degrees_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(map, g->dst_count, d_ids, n, d_out);
+    glx_in_degrees_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st.s>>>(map, g->dst_count, d_ids, n, d_out);
   }
-  hipError_t e = hipGetLastError();
-  if (host && e == hipSuccess) e = hipMemcpyAsync(deg_out, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, s);
-  if (host && e == hipSuccess) e = hipStreamSynchronize(s);
-  if (scratch) glx_scratch_free(scratch, s);
-  GLX_HIP(e);
-  return GLX_OK;
+  return st.finish(GLX_OK);
 }
 
 extern "C" int glx_sample_full_sizes(const glx_graph* g, const int64_t* src, int32_t batch,
@@ -247,20 +237,16 @@ extern "C" int glx_sample_full_sizes(const glx_graph* g, const int64_t* src, int
     return GLX_OK;
   }
   if (ptr_kind == GLX_PTR_DEVICE) return full_sizes_device(g, src, batch, max_limit, degrees_out, offsets_out, s);
-  char* d = nullptr;
-  const size_t bytes = (size_t)batch * 8 + ((size_t)batch + 1) * 8 + (size_t)batch * 4;
-  int rc = glx_scratch_alloc(reinterpret_cast<void**>(&d), bytes, s, 0);
-  if (rc != GLX_OK) return rc;
-  int64_t* d_src = reinterpret_cast<int64_t*>(d);
-  int64_t* d_off = d_src + batch;
-  int32_t* d_deg = reinterpret_cast<int32_t*>(d_off + batch + 1);
-  GLX_HIP(hipMemcpyAsync(d_src, src, (size_t)batch * 8, hipMemcpyHostToDevice, s));
-  rc = full_sizes_device(g, d_src, batch, max_limit, d_deg, d_off, s);
-  if (rc != GLX_OK) return rc;
-  GLX_HIP(hipMemcpyAsync(degrees_out, d_deg, (size_t)batch * 4, hipMemcpyDeviceToHost, s));
-  GLX_HIP(hipMemcpyAsync(offsets_out, d_off, ((size_t)batch + 1) * 8, hipMemcpyDeviceToHost, s));
-  GLX_HIP(hipStreamSynchronize(s));
-  return GLX_OK;
+  GlxHostStage st(g->device, ptr_kind, stream);
+  const int64_t* d_src;
+  int32_t* d_deg;
+  int64_t* d_off;
+  st.in(&d_src, src, (size_t)batch);
+  st.out(&d_deg, degrees_out, (size_t)batch);
+  st.out(&d_off, offsets_out, (size_t)batch + 1);
+  int rc = st.begin();
+  if (rc == GLX_OK) rc = full_sizes_device(g, d_src, batch, max_limit, d_deg, d_off, st.s);
+  return st.finish(rc);
 }
 
 extern "C" int glx_sample_full(const glx_graph* g, const int64_t* src, int32_t batch, int32_t max_limit,
@@ -295,19 +281,16 @@ extern "C" int glx_sample_full(const glx_graph* g, const int64_t* src, int32_t b
   GLX_REQUIRE(total >= 0 && total <= INT32_MAX, "response exceeds int32 values (tensor.h:47)");
   if (total == 0) return GLX_OK;
   GLX_REQUIRE(nbr_out && eid_out, "NULL output pointer");
-  int64_t* d = nullptr;
-  int rc = glx_scratch_alloc(reinterpret_cast<void**>(&d), ((size_t)batch * 2 + 1 + (size_t)total * 2) * 8, s, 0);
-  if (rc != GLX_OK) return rc;
-  int64_t* d_src = d;
-  int64_t* d_off = d + batch;
-  int64_t* d_nbr = d_off + batch + 1;
-  int64_t* d_eid = d_nbr + total;
-  GLX_HIP(hipMemcpyAsync(d_src, src, (size_t)batch * 8, hipMemcpyHostToDevice, s));
-  GLX_HIP(hipMemcpyAsync(d_off, offsets, ((size_t)batch + 1) * 8, hipMemcpyHostToDevice, s));
-  glx_full_copy_kernel<<<blocks, 256, 0, s>>>(g->map(), g->row_ptr, g->adj, d_src, batch, d_off, d_nbr, d_eid);
-  GLX_HIP(hipMemcpyAsync(nbr_out, d_nbr, (size_t)total * 8, hipMemcpyDeviceToHost, s));
-  GLX_HIP(hipMemcpyAsync(eid_out, d_eid, (size_t)total * 8, hipMemcpyDeviceToHost, s));
-  GLX_HIP(hipStreamSynchronize(s));
-  GLX_HIP(hipGetLastError());
-  return GLX_OK;
+  GlxHostStage st(g->device, ptr_kind, stream);
+  const int64_t *d_src, *d_off;
+  int64_t *d_nbr, *d_eid;
+  st.in(&d_src, src, (size_t)batch);
+  st.in(&d_off, offsets, (size_t)batch + 1);
+  st.out(&d_nbr, nbr_out, (size_t)total);
+  st.out(&d_eid, eid_out, (size_t)total);
+  int rc = st.begin();
+  if (rc == GLX_OK) {
+    glx_full_copy_kernel<<<blocks, 256, 0, st.s>>>(g->map(), g->row_ptr, g->adj, d_src, batch, d_off, d_nbr, d_eid);
+  }
+  return st.finish(rc);
 }

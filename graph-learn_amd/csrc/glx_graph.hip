@@ -227,6 +227,7 @@ struct WsBuf {
   WsKey key;
   void* p;
   size_t cap;
+  bool leased;
 };
 struct WsCache {
   std::vector<WsBuf> bufs;
@@ -296,8 +297,12 @@ int glx_scratch_alloc(void** p, size_t bytes, hipStream_t s, int slot) {
     }
   }
   if (!hit) {
-    g_ws.bufs.push_back(WsBuf{key, nullptr, 0});
+    g_ws.bufs.push_back(WsBuf{key, nullptr, 0, false});
     hit = &g_ws.bufs.back();
+  }
+  if (hit->leased) {
+    glx_set_error("workspace slot %d is already leased on this thread and stream (nested use of one slot)", slot);
+    return GLX_INTERNAL;
   }
   if (hit->cap < bytes) {
     if (hit->p) GLX_HIP(hipFree(hit->p));
@@ -309,6 +314,7 @@ int glx_scratch_alloc(void** p, size_t bytes, hipStream_t s, int slot) {
     GLX_HIP(hipMalloc(&hit->p, want));
     hit->cap = want;
   }
+  hit->leased = true;
   *p = hit->p;
   return GLX_OK;
 }
@@ -325,13 +331,131 @@ void glx_scratch_trim(hipStream_t s, int slot, size_t keep_bytes) {
       (void)hipFree(b.p);
       b.p = nullptr;
       b.cap = 0;
+      b.leased = false;
     }
   }
 }
 
 void glx_scratch_free(void* p, hipStream_t s) {
-  (void)p;
-  (void)s;  // workspaces are cached per thread/stream; nothing to release per call
+  // the buffer stays cached for the next lease; a plan's arena (REPLAY) matches no cached buffer
+  if (p == nullptr) return;
+  for (auto& b : g_ws.bufs) {
+    if (b.p == p && b.key.stream == s) {
+      b.leased = false;
+      return;
+    }
+  }
+}
+
+// ------------------------------------------------------ host-pointer staging --
+GlxHostStage::GlxHostStage(int device, int ptr_kind, void* stream, int options)
+    : host(ptr_kind == GLX_PTR_HOST),
+      s(host ? glx_host_call_stream(stream, device) : glx_stream(stream)),
+      direct_(host && (options & DIRECT_PINNED)),
+      admitted_(host && (options & ADMIT) ? device : -1) {}
+
+void GlxHostStage::declare(void** d, const void* h, size_t bytes, int kind) {
+  if (!host) {
+    *d = const_cast<void*>(h);
+    return;
+  }
+  if (kind == kOut && direct_ && h != nullptr) {
+    void* m = glx_mapped_ptr(h, bytes);
+    if (m) {
+      *d = m;
+      return;
+    }
+  }
+  if (n_ == kMaxPieces) {
+    overflow_ = true;
+    return;
+  }
+  pieces_[n_++] = Piece{d, h, nullptr, bytes, kind};
+}
+
+int GlxHostStage::begin() {
+  if (!host) return GLX_OK;
+  if (overflow_) {
+    glx_set_error("GlxHostStage: more than %d buffers declared", (int)kMaxPieces);
+    return GLX_INTERNAL;
+  }
+  size_t total = 0;
+  for (int i = 0; i < n_; ++i) {
+    if (pieces_[i].kind != kScratch && pieces_[i].h == nullptr) continue;  // absent optional buffer
+    total += (pieces_[i].bytes + 255) & ~(size_t)255;
+  }
+  if (total > 0) {
+    int rc = glx_scratch_alloc(&block_, total, s, 0);
+    if (rc != GLX_OK) {
+      block_ = nullptr;
+      return rc;
+    }
+  }
+  char* at = static_cast<char*>(block_);
+  for (int i = 0; i < n_; ++i) {
+    Piece& p = pieces_[i];
+    if (p.kind != kScratch && p.h == nullptr) {
+      *p.d = nullptr;
+      continue;
+    }
+    *p.d = at;
+    at += (p.bytes + 255) & ~(size_t)255;
+    if (p.kind == kIn && p.bytes > 0) GLX_HIP(hipMemcpyAsync(*p.d, p.h, p.bytes, hipMemcpyHostToDevice, s));
+  }
+  return GLX_OK;
+}
+
+void GlxHostStage::out_after(void* h, const void* d, size_t bytes) {
+  if (!host || bytes == 0) return;
+  if (n_ == kMaxPieces) {
+    overflow_ = true;
+    return;
+  }
+  pieces_[n_++] = Piece{nullptr, h, d, bytes, kAfter};
+}
+
+int GlxHostStage::finish(int rc) {
+  hipError_t launch = hipGetLastError();
+  if (!host) {
+    if (rc == GLX_OK && launch != hipSuccess) {
+      glx_set_error("kernel launch failed: %s", hipGetErrorString(launch));
+      return GLX_INTERNAL;
+    }
+    return rc;
+  }
+  hipError_t copy = hipSuccess;
+  if (rc == GLX_OK && launch == hipSuccess && !overflow_) {
+    for (int i = 0; i < n_ && copy == hipSuccess; ++i) {
+      const Piece& p = pieces_[i];
+      if (p.kind == kOut && p.h != nullptr && p.bytes > 0) {
+        copy = hipMemcpyAsync(const_cast<void*>(p.h), *p.d, p.bytes, hipMemcpyDeviceToHost, s);
+      } else if (p.kind == kAfter) {
+        copy = hipMemcpyAsync(const_cast<void*>(p.h), p.src, p.bytes, hipMemcpyDeviceToHost, s);
+      }
+    }
+  }
+  const hipError_t sync = hipStreamSynchronize(s);
+  glx_scratch_free(block_, s);
+  block_ = nullptr;
+  done_ = true;
+  if (rc != GLX_OK) return rc;
+  if (overflow_) {
+    glx_set_error("GlxHostStage: more than %d buffers declared", (int)kMaxPieces);
+    return GLX_INTERNAL;
+  }
+  for (hipError_t e : {launch, copy, sync}) {
+    if (e != hipSuccess) {
+      glx_set_error("host-pointer call failed: %s", hipGetErrorString(e));
+      return e == hipErrorOutOfMemory ? GLX_RESOURCE_EXHAUSTED : GLX_INTERNAL;
+    }
+  }
+  return GLX_OK;
+}
+
+GlxHostStage::~GlxHostStage() {
+  if (!host || done_) return;
+  (void)hipStreamSynchronize(s);
+  glx_scratch_free(block_, s);
 }
 
 // ------------------------------------------------------- per-thread streams --
@@ -857,20 +981,12 @@ extern "C" int glx_graph_degrees(const glx_graph* g, const int64_t* src, int64_t
   GLX_REQUIRE(n >= 0, "negative n");
   if (n == 0) return GLX_OK;
   GlxDeviceGuard guard(g->device);
-  hipStream_t s = ptr_kind == GLX_PTR_HOST ? glx_host_call_stream(stream, g->device) : glx_stream(stream);
-  if (ptr_kind == GLX_PTR_DEVICE) {
-    glx_degrees_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(g->map(), g->row_ptr, src, n,
-                                                                   deg_out);
-    GLX_HIP(hipGetLastError());
-    return GLX_OK;
-  }
-  int64_t* d = nullptr;
-  int rc = glx_scratch_alloc(reinterpret_cast<void**>(&d), (size_t)n * 2 * sizeof(int64_t), s, 0);
-  if (rc != GLX_OK) return rc;
-  GLX_HIP(hipMemcpyAsync(d, src, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, s));
-  glx_degrees_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(g->map(), g->row_ptr, d, n, d + n);
-  GLX_HIP(hipMemcpyAsync(deg_out, d + n, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  GLX_HIP(hipStreamSynchronize(s));
-  glx_scratch_free(d, s);
-  return GLX_OK;
+  GlxHostStage st(g->device, ptr_kind, stream);
+  const int64_t* d_src;
+  int64_t* d_out;
+  st.in(&d_src, src, (size_t)n);
+  st.out(&d_out, deg_out, (size_t)n);
+  int rc = st.begin();
+  if (rc == GLX_OK) glx_degrees_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st.s>>>(g->map(), g->row_ptr, d_src, n, d_out);
+  return st.finish(rc);
 }

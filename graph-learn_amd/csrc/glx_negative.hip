@@ -447,32 +447,15 @@ extern "C" int glx_negative_sample(const glx_negative* t, int exclude, const glx
   }
   GlxDeviceGuard guard(t->device);
   GLX_REQUIRE(guard.ok, "cannot select device %d", t->device);
-  const bool host = ptr_kind == GLX_PTR_HOST;
-  hipStream_t s = host ? glx_host_call_stream(stream, t->device) : glx_stream(stream);
-  // scratch: [out (host calls)] [src (host calls)] [sorted batch (node-weight)]
-  const bool need_src = exclude != GLX_NEG_EXCLUDE_NONE;
-  const size_t out_bytes = host ? (size_t)total * 8 : 0;
-  const size_t src_bytes = host && need_src ? (size_t)batch * 8 : 0;
-  const size_t sort_bytes = exclude == GLX_NEG_EXCLUDE_BATCH ? (size_t)batch * 8 + 8 : 0;  // + first_dropped
-  char* scratch = nullptr;
-  if (out_bytes + src_bytes + sort_bytes > 0) {
-    int rc = glx_scratch_alloc(reinterpret_cast<void**>(&scratch), out_bytes + src_bytes + sort_bytes, s, 0);
-    if (rc != GLX_OK) return rc;
-  }
-  struct Release {
-    void* p;
-    hipStream_t s;
-    ~Release() {
-      if (p) glx_scratch_free(p, s);
-    }
-  } release{scratch, s};
-  int64_t* d_out = host ? reinterpret_cast<int64_t*>(scratch) : out;
-  const int64_t* d_src = src;
-  if (host && need_src) {
-    int64_t* p = reinterpret_cast<int64_t*>(scratch + out_bytes);
-    GLX_HIP(hipMemcpyAsync(p, src, src_bytes, hipMemcpyHostToDevice, s));
-    d_src = p;
-  }
+  GlxHostStage st(t->device, ptr_kind, stream);
+  const hipStream_t s = st.s;
+  const int64_t* d_src;
+  int64_t* d_out;
+  st.in(&d_src, exclude != GLX_NEG_EXCLUDE_NONE ? src : nullptr, (size_t)batch);
+  st.out(&d_out, out, (size_t)total);
+  int rc = st.begin();
+  if (rc != GLX_OK) return st.finish(rc);
+  GlxScratch sort_space;
   if (t->num_ids == 0) {
     // no candidates at all (random_negative_sampler.cc:50-54): the default neighbour id
     glx_neg_fill_kernel<<<grid_for(total), 256, 0, s>>>(d_out, total, default_neighbor_id);
@@ -492,16 +475,14 @@ extern "C" int glx_negative_sample(const glx_negative* t, int exclude, const glx
       a.row_ptr = g->row_ptr;
       a.nbr_sorted = g->nbr_sorted;
     } else if (exclude == GLX_NEG_EXCLUDE_BATCH) {
-      // the request's own ids, ascending (per request: temp storage from the workspace cache)
-      int64_t* sorted = reinterpret_cast<int64_t*>(scratch + out_bytes + src_bytes);
+      // the request's own ids, ascending, + first_dropped, then the sort's temp storage: one slot-1 lease per request
+      const size_t sorted_bytes = ((size_t)batch * 8 + 8 + 255) & ~(size_t)255;
       size_t tmp_bytes = 0;
-      GLX_HIP(rocprim::radix_sort_keys(nullptr, tmp_bytes, d_src, sorted, (size_t)batch, 0, 64, s));
-      void* tmp = nullptr;
-      int rc = glx_scratch_alloc(&tmp, tmp_bytes ? tmp_bytes : 16, s, 1);
-      if (rc != GLX_OK) return rc;
-      hipError_t e = rocprim::radix_sort_keys(tmp, tmp_bytes, d_src, sorted, (size_t)batch, 0, 64, s);
-      glx_scratch_free(tmp, s);
-      GLX_HIP(e);
+      GLX_HIP(rocprim::radix_sort_keys(nullptr, tmp_bytes, d_src, (int64_t*)nullptr, (size_t)batch, 0, 64, s));
+      rc = sort_space.alloc(sorted_bytes + tmp_bytes, s, 1);
+      if (rc != GLX_OK) return st.finish(rc);
+      int64_t* sorted = sort_space.as<int64_t>();
+      GLX_HIP(rocprim::radix_sort_keys(sort_space.as<char>() + sorted_bytes, tmp_bytes, d_src, sorted, (size_t)batch, 0, 64, s));
       a.batch_sorted = sorted;
       a.first_dropped = reinterpret_cast<unsigned long long*>(sorted + batch);
       glx_neg_fill_kernel<<<1, 64, 0, s>>>(reinterpret_cast<int64_t*>(a.first_dropped), 1, (int64_t)batch);
@@ -517,10 +498,5 @@ extern "C" int glx_negative_sample(const glx_negative* t, int exclude, const glx
     }
     timer.stop();
   }
-  GLX_HIP(hipGetLastError());
-  if (host) {
-    GLX_HIP(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, s));
-    GLX_HIP(hipStreamSynchronize(s));
-  }
-  return GLX_OK;
+  return st.finish(GLX_OK);
 }

@@ -201,12 +201,13 @@ static int partition_impl(int device, const int64_t* ids, int64_t n, int32_t num
   }
   const int32_t tile = n <= kSmallIds ? kTileSmall : kTile;
   const int64_t nblocks = (n + tile - 1) / tile;
-  int64_t* block_counts = nullptr;
   const size_t cells_b = (size_t)num_buckets * nblocks * sizeof(int64_t);
   // a bucket that costs a hash probe is remembered (one byte per id); a bitmap or arithmetic test is cheaper recomputed
   const bool probe = divert.keys != nullptr && member.bits == nullptr;
-  int rc = glx_scratch_alloc(reinterpret_cast<void**>(&block_counts), cells_b + (probe ? (size_t)n : 0), s, 1);
+  GlxScratch lease;
+  int rc = lease.alloc(cells_b + (probe ? (size_t)n : 0), s, 1);
   if (rc != GLX_OK) return rc;
+  int64_t* block_counts = lease.as<int64_t>();
   uint8_t* bucket_cache = probe ? reinterpret_cast<uint8_t*>(block_counts) + cells_b : nullptr;
   glx_part_count_kernel<<<(unsigned)nblocks, 256, 0, s>>>(ids, n, num_buckets, nblocks, tile, divert, member, block_counts,
                                                           bucket_cache);
@@ -219,9 +220,7 @@ static int partition_impl(int device, const int64_t* ids, int64_t n, int32_t num
                                                                     block_counts, bucket_cache, bucketed, order, counts,
                                                                     GlxPartitionTail{{0}, 0, 0});
   }
-  hipError_t e = hipGetLastError();
-  glx_scratch_free(block_counts, s);
-  GLX_HIP(e);
+  GLX_HIP(hipGetLastError());
   return GLX_OK;
 }
 

@@ -493,7 +493,6 @@ extern "C" int glx_sample_ex(const glx_graph* g, int sampler, const int64_t* src
   GLX_REQUIRE(src && nbr_out && eid_out, "NULL data pointer");
   GlxDeviceGuard guard(g->device);
   GLX_REQUIRE(guard.ok, "cannot select device %d", g->device);
-  hipStream_t s = ptr_kind == GLX_PTR_HOST ? glx_host_call_stream(stream, g->device) : glx_stream(stream);
 
   SampleArgs a;
   a.map = g->map();
@@ -510,42 +509,17 @@ extern "C" int glx_sample_ex(const glx_graph* g, int sampler, const int64_t* src
   a.prefix = nullptr;
   a.reversed = 0;
   a.out_rows = nullptr;
-  if (ptr_kind == GLX_PTR_DEVICE) {
-    a.src = src;
-    a.rng_rows = rng_rows;
-    a.nbr_out = nbr_out;
-    a.eid_out = eid_out;
-    return sample_device(g, sampler, a, padding_mode, s);
-  }
-  // Host pointers: inputs are staged through a device workspace; outputs are written by the kernel straight
-  // into the caller's buffers when those are pinned (glx_mapped_ptr), else staged and copied.  Synchronous.
-  GlxHostCallSlot admitted(g->device);
+  // Host pointers: inputs are staged through a device workspace; outputs are written by the kernel straight into the
+  // caller's buffers when those are pinned, else staged and copied.  Synchronous.
+  GlxHostStage st(g->device, ptr_kind, stream, GlxHostStage::ADMIT | GlxHostStage::DIRECT_PINNED);
   const size_t n_out = (size_t)batch * k;
-  int64_t* m_nbr = static_cast<int64_t*>(glx_mapped_ptr(nbr_out, n_out * 8));
-  int64_t* m_eid = static_cast<int64_t*>(glx_mapped_ptr(eid_out, n_out * 8));
-  const bool direct = m_nbr != nullptr && m_eid != nullptr;
-  int64_t* d = nullptr;
-  int rc = glx_scratch_alloc(reinterpret_cast<void**>(&d), ((size_t)batch * 2 + (direct ? 0 : 2 * n_out)) * 8, s, 0);
-  if (rc != GLX_OK) return rc;
-  a.src = d;
-  a.rng_rows = rng_rows ? d + batch : nullptr;
-  a.nbr_out = direct ? m_nbr : d + 2 * (size_t)batch;
-  a.eid_out = direct ? m_eid : d + 2 * (size_t)batch + n_out;
-  hipError_t e = hipMemcpyAsync(d, src, (size_t)batch * 8, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess && rng_rows) e = hipMemcpyAsync(d + batch, rng_rows, (size_t)batch * 8, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) {
-    rc = sample_device(g, sampler, a, padding_mode, s);
-    if (rc == GLX_OK && !direct) {
-      e = hipMemcpyAsync(nbr_out, a.nbr_out, n_out * 8, hipMemcpyDeviceToHost, s);
-      if (e == hipSuccess) e = hipMemcpyAsync(eid_out, a.eid_out, n_out * 8, hipMemcpyDeviceToHost, s);
-    }
-  }
-  hipError_t e2 = hipStreamSynchronize(s);
-  glx_scratch_free(d, s);
-  if (rc != GLX_OK) return rc;
-  GLX_HIP(e);
-  GLX_HIP(e2);
-  return GLX_OK;
+  st.in(&a.src, src, (size_t)batch);
+  st.in(&a.rng_rows, rng_rows, (size_t)batch);
+  st.out(&a.nbr_out, nbr_out, n_out);
+  st.out(&a.eid_out, eid_out, n_out);
+  int rc = st.begin();
+  if (rc == GLX_OK) rc = sample_device(g, sampler, a, padding_mode, st.s);
+  return st.finish(rc);
 }
 
 extern "C" int glx_sample(const glx_graph* g, int sampler, const int64_t* src, int32_t batch,
@@ -593,8 +567,8 @@ extern "C" int glx_sample_hops(const glx_graph* const* graphs, int32_t num_hops,
   // hop's device buffer, one download per hop output.
   GlxDeviceGuard guard(graphs[0]->device);
   GLX_REQUIRE(guard.ok, "cannot select device %d", graphs[0]->device);
-  hipStream_t s = glx_host_call_stream(stream, graphs[0]->device);
-  size_t total = (size_t)batch;
+  GlxHostStage st(graphs[0]->device, ptr_kind, stream);
+  size_t total = 0;
   {
     int64_t n = batch;
     for (int32_t h = 0; h < num_hops; ++h) {
@@ -602,36 +576,27 @@ extern "C" int glx_sample_hops(const glx_graph* const* graphs, int32_t num_hops,
       total += 2 * (size_t)n;
     }
   }
-  int64_t* d = nullptr;
-  int rc = glx_scratch_alloc(reinterpret_cast<void**>(&d), total * 8, s, 0);
-  if (rc != GLX_OK) return rc;
-  // Errors are collected, not returned on the spot: copies already queued into the caller's
-  // buffers must drain (and the shared staging buffer must be idle) before this call returns.
-  hipError_t e = hipMemcpyAsync(d, seeds, (size_t)batch * 8, hipMemcpyHostToDevice, s);
-  const int64_t* frontier = d;
-  int64_t* cursor = d + batch;
+  const int64_t* d_seeds;
+  int64_t* d;
+  st.in(&d_seeds, seeds, (size_t)batch);
+  st.scratch(&d, total);
+  int rc = st.begin();
+  const int64_t* frontier = d_seeds;
+  int64_t* cursor = d;
   int64_t n = batch;
-  for (int32_t h = 0; h < num_hops && e == hipSuccess && rc == GLX_OK; ++h) {
+  for (int32_t h = 0; h < num_hops && rc == GLX_OK; ++h) {
     const int64_t slots = n * fanouts[h];
     int64_t* dn = cursor;
     int64_t* de = cursor + slots;
     cursor += 2 * slots;
     if (slots > 0) {
       rc = glx_sample(graphs[h], sampler, frontier, (int32_t)n, fanouts[h], padding_mode,
-                      default_neighbor_id, seed, call_counter + (uint64_t)h, dn, de, GLX_PTR_DEVICE, s);
-      if (rc != GLX_OK) break;
-      e = hipMemcpyAsync(nbr_out[h], dn, (size_t)slots * 8, hipMemcpyDeviceToHost, s);
-      if (e == hipSuccess && eid_out && eid_out[h]) {
-        e = hipMemcpyAsync(eid_out[h], de, (size_t)slots * 8, hipMemcpyDeviceToHost, s);
-      }
+                      default_neighbor_id, seed, call_counter + (uint64_t)h, dn, de, GLX_PTR_DEVICE, st.s);
+      st.out_after(nbr_out[h], dn, (size_t)slots * 8);
+      if (eid_out && eid_out[h]) st.out_after(eid_out[h], de, (size_t)slots * 8);
     }
     frontier = dn;
     n = slots;
   }
-  hipError_t e2 = hipStreamSynchronize(s);
-  glx_scratch_free(d, s);
-  if (rc != GLX_OK) return rc;
-  GLX_HIP(e);
-  GLX_HIP(e2);
-  return GLX_OK;
+  return st.finish(rc);
 }

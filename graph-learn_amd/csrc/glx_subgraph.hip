@@ -186,37 +186,30 @@ extern "C" int glx_subgraph_induce(int device, const int64_t* nodes, int32_t n, 
   if (rc != GLX_OK) return rc;
   GlxDeviceGuard guard(device);
   GLX_REQUIRE(guard.ok, "cannot select device %d", device);
-  hipStream_t s = ptr_kind == GLX_PTR_HOST ? glx_host_call_stream(stream, device) : glx_stream(stream);
   if (ptr_kind == GLX_PTR_DEVICE) {
-    return induce_device(nodes, n, offsets, nbr, eid, row_out, col_out, eid_out, capacity, count_out, s);
+    return induce_device(nodes, n, offsets, nbr, eid, row_out, col_out, eid_out, capacity, count_out, glx_stream(stream));
   }
   const int64_t total_in = offsets[n];
   GLX_REQUIRE(total_in >= 0 && (total_in == 0 || (nbr && eid)), "bad offsets / NULL rows");
-  GlxTemp d_nodes, d_off, d_nbr, d_eid, d_row, d_col, d_eout;
-  GLX_HIP(hipMalloc(&d_nodes.p, (size_t)n * 8));
-  GLX_HIP(hipMalloc(&d_off.p, ((size_t)n + 1) * 8));
-  GLX_HIP(hipMalloc(&d_nbr.p, (size_t)(total_in > 0 ? total_in : 1) * 8));
-  GLX_HIP(hipMalloc(&d_eid.p, (size_t)(total_in > 0 ? total_in : 1) * 8));
-  GLX_HIP(hipMemcpyAsync(d_nodes.p, nodes, (size_t)n * 8, hipMemcpyHostToDevice, s));
-  GLX_HIP(hipMemcpyAsync(d_off.p, offsets, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, s));
-  if (total_in > 0) {
-    GLX_HIP(hipMemcpyAsync(d_nbr.p, nbr, (size_t)total_in * 8, hipMemcpyHostToDevice, s));
-    GLX_HIP(hipMemcpyAsync(d_eid.p, eid, (size_t)total_in * 8, hipMemcpyHostToDevice, s));
+  // the response holds *count_out edges, known only after the body: its copies are queued then
+  GlxHostStage st(device, ptr_kind, stream);
+  const int64_t *d_nodes, *d_off, *d_nbr, *d_eid;
+  int32_t *d_row, *d_col;
+  int64_t* d_eout;
+  st.in(&d_nodes, nodes, (size_t)n);
+  st.in(&d_off, offsets, (size_t)n + 1);
+  st.in(&d_nbr, nbr, (size_t)total_in);
+  st.in(&d_eid, eid, (size_t)total_in);
+  st.scratch(&d_row, (size_t)capacity);
+  st.scratch(&d_col, (size_t)capacity);
+  st.scratch(&d_eout, (size_t)capacity);
+  rc = st.begin();
+  if (rc == GLX_OK) rc = induce_device(d_nodes, n, d_off, d_nbr, d_eid, d_row, d_col, d_eout, capacity, count_out, st.s);
+  if (rc == GLX_OK) {
+    const int64_t got = *count_out < capacity ? *count_out : capacity;
+    st.out_after(row_out, d_row, (size_t)got * 4);
+    st.out_after(col_out, d_col, (size_t)got * 4);
+    st.out_after(eid_out, d_eout, (size_t)got * 8);
   }
-  if (capacity > 0) {
-    GLX_HIP(hipMalloc(&d_row.p, (size_t)capacity * 4));
-    GLX_HIP(hipMalloc(&d_col.p, (size_t)capacity * 4));
-    GLX_HIP(hipMalloc(&d_eout.p, (size_t)capacity * 8));
-  }
-  rc = induce_device(d_nodes.as<int64_t>(), n, d_off.as<int64_t>(), d_nbr.as<int64_t>(), d_eid.as<int64_t>(), d_row.as<int32_t>(),
-                     d_col.as<int32_t>(), d_eout.as<int64_t>(), capacity, count_out, s);
-  if (rc != GLX_OK) return rc;
-  const int64_t got = *count_out < capacity ? *count_out : capacity;
-  if (got > 0) {
-    GLX_HIP(hipMemcpyAsync(row_out, d_row.p, (size_t)got * 4, hipMemcpyDeviceToHost, s));
-    GLX_HIP(hipMemcpyAsync(col_out, d_col.p, (size_t)got * 4, hipMemcpyDeviceToHost, s));
-    GLX_HIP(hipMemcpyAsync(eid_out, d_eout.p, (size_t)got * 8, hipMemcpyDeviceToHost, s));
-    GLX_HIP(hipStreamSynchronize(s));
-  }
-  return GLX_OK;
+  return st.finish(rc);
 }

@@ -193,7 +193,8 @@ extern "C" int glx_random_walk(const glx_graph* g, const int64_t* seeds, int32_t
               full_nbr_num);
   GlxDeviceGuard guard(g->device);
   GLX_REQUIRE(guard.ok, "cannot select device %d", g->device);
-  hipStream_t s = ptr_kind == GLX_PTR_HOST ? glx_host_call_stream(stream, g->device) : glx_stream(stream);
+  GlxHostStage st(g->device, ptr_kind, stream);
+  const hipStream_t s = st.s;
   WalkArgs a;
   a.map = g->map();
   a.row_ptr = g->row_ptr;
@@ -209,27 +210,18 @@ extern "C" int glx_random_walk(const glx_graph* g, const int64_t* seeds, int32_t
   a.walk_len = walk_len;
   a.full_nbr_num = full_nbr_num;
   const size_t nb = (size_t)batch, n_out = nb * (size_t)walk_len;
-  int64_t* d = nullptr;
-  if (ptr_kind == GLX_PTR_HOST) {
-    int rc = glx_scratch_alloc(reinterpret_cast<void**>(&d), (nb + n_out) * 8, s, 0);
-    if (rc != GLX_OK) return rc;
-    GLX_HIP(hipMemcpyAsync(d, seeds, nb * 8, hipMemcpyHostToDevice, s));
-    a.seeds = d;
-    a.walks = d + nb;
-  } else {
-    a.seeds = seeds;
-    a.walks = walks_out;
-  }
+  st.in(&a.seeds, seeds, nb);
+  st.out(&a.walks, walks_out, n_out);
+  int rc = st.begin();
+  if (rc != GLX_OK) return st.finish(rc);
   a.seg = nullptr;
   a.off_true = a.off_used = nullptr;
-  int32_t* d_seg = nullptr;
+  GlxScratch seg;
   if (!deep && walk_len > 1) {  // [seg i32 | seg_live i32 | off_true i64 | off_used i64] per walker
-    int rc = glx_scratch_alloc(reinterpret_cast<void**>(&d_seg), nb * 24 + 16, s, 1);
-    if (rc != GLX_OK) {
-      if (d) glx_scratch_free(d, s);
-      return rc;
-    }
+    rc = seg.alloc(nb * 24 + 16, s, 1);
+    if (rc != GLX_OK) return st.finish(rc);
   }
+  int32_t* d_seg = seg.as<int32_t>();
   int32_t* d_live = d_seg ? d_seg + nb : nullptr;
   int64_t* d_true = d_seg ? reinterpret_cast<int64_t*>(d_seg + 2 * nb)  /* 8 nb bytes in: 8-byte aligned */ : nullptr;
   int64_t* d_used = d_seg ? d_true + nb : nullptr;
@@ -250,11 +242,5 @@ extern "C" int glx_random_walk(const glx_graph* g, const int64_t* seeds, int32_t
     }
   }
   timer.stop();
-  if (d_seg) glx_scratch_free(d_seg, s);
-  GLX_HIP(hipGetLastError());
-  if (ptr_kind == GLX_PTR_HOST) {
-    GLX_HIP(hipMemcpyAsync(walks_out, a.walks, n_out * 8, hipMemcpyDeviceToHost, s));
-    GLX_HIP(hipStreamSynchronize(s));
-  }
-  return GLX_OK;
+  return st.finish(GLX_OK);
 }
