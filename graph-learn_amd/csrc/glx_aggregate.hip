@@ -178,6 +178,8 @@ struct AggArgs {
   int32_t store_mode;        // glx_aggregate_grp_kernel: 0 non-temporal output stores (default), 1 plain stores (ablation)
   int32_t segs_per_group;    // glx_aggregate_grp_kernel: consecutive segments one lane group reduces
   int32_t xcd_slices;        // glx_aggregate_grp_kernel: > 1 = workgroup b reduces column slice b % xcd_slices (ncols each)
+  int32_t stripe_chunk;      // glx_aggregate_grp_kernel: > 0 = XCD stripes of this many segment blocks (agg_stripe_block)
+  uint32_t stripe_full;      // ... the slice-local block indices [0, stripe_full) that the stripes permute
   // further row sources of the distributed store (glx_dist.hip): virtual row r lives in
   // source 0 when r < base1, in source 1 (the hot-row replica) when r < base2, else in
   // source 2 (the halo rows of this request, plain row-major, no swizzle).
@@ -354,6 +356,22 @@ __device__ __forceinline__ void agg_grp_batch(const AggArgs& a, const int32_t (&
   }
 }
 
+// XCD stripes: the slice-local workgroup index j (j = b / n for workgroup b and n column slices) -> the segment block
+// it reduces.  Workgroup b runs on XCD b % 8 (observed placement, used for speed only), so the P = 8 / n XCDs that
+// share a slice see j = P k + m (m = the XCD's label, k = its k-th workgroup of the launch).  The permutation hands
+// label m the m-th chunk of `chunk` consecutive blocks out of every run of P * chunk, so each XCD walks contiguous
+// stripes of segments -- a seed's hop-1 samples, and the rows their twins share, stay in one L2 -- instead of every
+// P-th block.  It is a bijection of [0, full) (full = whole runs only) and the identity beyond: every (segment block,
+// slice) pair is reduced exactly once whatever the placement.
+__device__ __forceinline__ uint32_t agg_stripe_block(uint32_t j, uint32_t P, uint32_t chunk, uint32_t full) {
+  if (j >= full) return j;
+  const uint32_t span = P * chunk;
+  const uint32_t run = j / span;
+  const uint32_t r = j - run * span;
+  const uint32_t k = r / P;
+  return run * span + (r - k * P) * chunk + k;
+}
+
 template <int OP, int G, int VEC, int U, int NSRC, int IDR>
 __global__ __launch_bounds__(256) void glx_aggregate_grp_kernel(AggArgs a) {
   typedef float vec_t __attribute__((ext_vector_type(VEC)));
@@ -362,8 +380,11 @@ __global__ __launch_bounds__(256) void glx_aggregate_grp_kernel(AggArgs a) {
   constexpr int kGroupsPerBlock = 256 / G;
   // XCD-affine column slices (a.xcd_slices > 1): workgroup b runs on XCD b % 8 (observed placement, used for speed
   // only), so slice = b % xcd_slices keeps one column slice of EVERY row in one XCD's L2
-  const int32_t slice = a.xcd_slices > 1 ? (int32_t)(blockIdx.x % (unsigned)a.xcd_slices) : 0;
-  const int64_t blk = a.xcd_slices > 1 ? blockIdx.x / (unsigned)a.xcd_slices : blockIdx.x;
+  const uint32_t nsl = a.xcd_slices > 1 ? (uint32_t)a.xcd_slices : 1u;
+  const int32_t slice = (int32_t)(blockIdx.x % nsl);
+  uint32_t j = blockIdx.x / nsl;
+  if (a.stripe_chunk > 0) j = agg_stripe_block(j, 8u / nsl, (uint32_t)a.stripe_chunk, a.stripe_full);
+  const int64_t blk = j;
   int64_t grp = blk * kGroupsPerBlock + threadIdx.x / G;
   const int c = threadIdx.x & (G - 1);
   const int32_t S = a.segs_per_group;
@@ -533,6 +554,8 @@ struct AggKnobs {
   std::atomic<int> xcd{0};      // GLX_AGG_XCD_SLICES=1|2|4|8: column slice = workgroup % n (XCD-affine); 0 = 2 for big requests
   std::atomic<int> occ{0};      // GLX_AGG_OCCUPANCY=3..7: workgroups per CU, capped with an unused LDS allocation
   std::atomic<int> store{0};    // GLX_AGG_STORE=1: plain output stores instead of non-temporal ones (ablation)
+  std::atomic<int> stripes{-1}; // GLX_AGG_XCD_STRIPES=0: workgroup j of a slice reduces segment block j (no XCD stripes); 1 = on; -1 = default
+  std::atomic<int> chunk{0};    // GLX_AGG_XCD_CHUNK: segment blocks per XCD stripe chunk (0 = kXcdStripeChunk)
 };
 
 AggKnobs& agg_knobs() {
@@ -551,6 +574,8 @@ AggKnobs& agg_knobs() {
     k.xcd = env("GLX_AGG_XCD_SLICES");
     k.occ = env("GLX_AGG_OCCUPANCY");
     k.store = env("GLX_AGG_STORE");
+    if (getenv("GLX_AGG_XCD_STRIPES")) k.stripes = env("GLX_AGG_XCD_STRIPES");
+    k.chunk = env("GLX_AGG_XCD_CHUNK");
   });
   return k;
 }
@@ -625,8 +650,18 @@ void launch_agg_grp(AggArgs a, int32_t num_ids, hipStream_t s) {
   a.segs_per_group = S;
   a.store_mode = agg_knobs().store.load(std::memory_order_relaxed);
   const int64_t groups = ((int64_t)a.num_segments + S - 1) / S;
-  const int64_t blocks = (groups + (256 / G) - 1) / (256 / G) * (a.xcd_slices > 1 ? a.xcd_slices : 1);
+  const int64_t seg_blocks = (groups + (256 / G) - 1) / (256 / G);
+  const int32_t nsl = a.xcd_slices > 1 ? a.xcd_slices : 1;
+  const int64_t blocks = seg_blocks * nsl;
   const unsigned grid = (unsigned)blocks;
+  // XCD stripes (agg_stripe_block): whole runs of (8 / n) * chunk segment blocks are permuted, the tail stays in order
+  if (a.stripe_chunk > 0 && nsl < 8) {
+    const int64_t span = (int64_t)(8 / nsl) * a.stripe_chunk;
+    a.stripe_full = (uint32_t)(seg_blocks / span * span);
+  } else {
+    a.stripe_chunk = 0;
+    a.stripe_full = 0;
+  }
   // occupancy cap (experiment): k workgroups per CU by declaring 160 KiB / k of LDS nobody touches
   const int occ = agg_knobs().occ.load(std::memory_order_relaxed);
   const size_t lds = (occ >= 3 && occ <= 7) ? (size_t)(160 * 1024 / occ) & ~(size_t)255 : 0;
@@ -692,8 +727,22 @@ void launch_agg_cols(const AggArgs& a0, int32_t num_ids, int want_xcd, hipStream
 //    random rows; C2 (D = 128) 0.633 / 0.561 / 0.596 and 0.853 / 0.881 / 0.929; C4's shape 1.03 / 0.96 / 1.07 and
 //    1.86 / 1.90 / 1.98.  n = 2 is the default: -6 .. -11 % where rows are re-used, +1 .. 3 % where none is; small
 //    requests (C3 hop 1: 0.098 -> 0.120 ms) stay whole.  GLX_AGG_XCD_SLICES = 1 (off) | 2 | 4 | 8 overrides.
+//  * XCD stripes (agg_stripe_block; the default for the same requests of >= 4 M ids): the XCDs that share a slice
+//    walk contiguous chunks of kXcdStripeChunk segment blocks instead of every (8 / n)-th block, so a seed's hop-1
+//    samples and their twins' shared rows are fetched into ONE L2.  This moves the slice trade-off: measured
+//    (profiles/r07/stripe_ab.txt, same process, 6 alternations, ms; old default = n 2 without stripes): C3 hop-2
+//    1.829 -> 1.609 with n = 1 (n = 2 with stripes: 1.690), degree-biased seeds 1.991 -> 1.977 (n = 2: 1.957), C2 0.552
+//    -> 0.535 with n = 2 (n = 1: 0.579), C4's shape 0.962 -> 0.926 with n = 2 (n = 1: 0.947), uniformly random rows
+//    3.295 -> 3.217.  So with stripes, rows of >= 256 floats take n = 1 and narrower rows keep n = 2.  Chunks of
+//    16 / 32 / 64 / 256 blocks are within 1 % of each other; requests under 4 M ids stay in order (C3 hop 1:
+//    0.098 -> 0.100 with stripes).  The other users of the grouped kernel take the stripes under the same rule: three
+//    segments per group (C5's item -> shop reduce, 6.55 M ids: bench.py --workload c5, three interleaved runs each,
+//    0.677 -> 0.686 ms/step by median -- inside its 2 % run-to-run spread, profiles/r07/bench_ab_interleaved.txt), the
+//    3-source distributed reduce and explicit segment_ids (the permutation moves whole segment blocks, so neither the
+//    row source nor the segment bounds see it).  GLX_AGG_XCD_STRIPES = 0 (off) | 1 and GLX_AGG_XCD_CHUNK override.
 //  * GLX_AGG_SLICES = n: the columns in n slices, one LAUNCH after the other (ablation; profiles/r02: no gain).
 constexpr int32_t kXcdSliceMinIds = 4 << 20;
+constexpr int32_t kXcdStripeChunk = 64;
 
 template <int OP, int NSRC>
 void launch_agg_n(const AggArgs& a0, int32_t num_ids, hipStream_t s) {
@@ -701,11 +750,19 @@ void launch_agg_n(const AggArgs& a0, int32_t num_ids, hipStream_t s) {
   a.col0 = 0;
   a.ncols = a.dim;
   a.xcd_slices = 0;
+  int stripes = agg_knobs().stripes.load(std::memory_order_relaxed);
+  if (stripes < 0) stripes = num_ids >= kXcdSliceMinIds ? 1 : 0;
   int xcd = agg_knobs().xcd.load(std::memory_order_relaxed);
-  if (xcd == 0) xcd = (num_ids >= kXcdSliceMinIds && a.dim % 8 == 0 && a.dim >= 128) ? 2 : 1;
+  if (xcd == 0) {
+    xcd = (num_ids >= kXcdSliceMinIds && a.dim % 8 == 0 && a.dim >= 128) ? 2 : 1;
+    if (xcd == 2 && stripes > 0 && a.dim >= 256) xcd = 1;
+  }
   int slices = agg_knobs().slices.load(std::memory_order_relaxed);
   if ((slices != 2 && slices != 4 && slices != 8) || a.dim % (4 * slices) != 0) slices = 1;
   if (xcd != 2 && xcd != 4 && xcd != 8) xcd = 1;
+  int chunk = agg_knobs().chunk.load(std::memory_order_relaxed);
+  if (chunk <= 0) chunk = kXcdStripeChunk;
+  a.stripe_chunk = stripes > 0 ? chunk : 0;
   for (int c = 0; c < slices; ++c) {
     a.ncols = a.dim / slices;
     a.col0 = c * a.ncols;
@@ -1027,6 +1084,8 @@ extern "C" int glx_tune(const char* name, int32_t value) {
   else if (strcmp(name, "agg_xcd_slices") == 0) slot = &k.xcd;
   else if (strcmp(name, "agg_occupancy") == 0) slot = &k.occ;
   else if (strcmp(name, "agg_store") == 0) slot = &k.store;
+  else if (strcmp(name, "agg_xcd_stripes") == 0) slot = &k.stripes;
+  else if (strcmp(name, "agg_xcd_chunk") == 0) slot = &k.chunk;
   else if (strcmp(name, "seg_epochs_before_wrap") == 0) {
     // test aid: the calling thread's segment-word buffers hand out `value` more epochs before their counter wraps
     GLX_REQUIRE(value >= 0, "seg_epochs_before_wrap must be >= 0");
