@@ -17,6 +17,7 @@
 #include <atomic>
 #include <mutex>
 #include <new>
+#include <type_traits>
 
 #include "glx_common.h"
 
@@ -159,8 +160,86 @@ __device__ __forceinline__ float agg_combine(float l, float r) {
   return l + r;  // sum, mean
 }
 
+// ---- storage types -----------------------------------------------------------------------------------------
+// A table stores float32, bfloat16 or float16 elements (glx_features::dtype).  Every kernel that reads one upcasts
+// each element to float32 in registers right after the load -- exact for both half types -- and then folds, finishes
+// and stores exactly as for a float32 table: a half table's results are those of the float32 table of its upcast
+// values, bit for bit.  Only the bytes per row change.
+template <int DT>
+struct AggElem;
+template <>
+struct AggElem<GLX_DTYPE_F32> {
+  typedef float raw;
+  static __device__ __forceinline__ float up(float x) { return x; }
+};
+template <>
+struct AggElem<GLX_DTYPE_BF16> {
+  typedef uint16_t raw;
+  static __device__ __forceinline__ float up(uint16_t x) { return __uint_as_float((uint32_t)x << 16); }
+};
+template <>
+struct AggElem<GLX_DTYPE_F16> {
+  typedef _Float16 raw;
+  static __device__ __forceinline__ float up(_Float16 x) { return (float)x; }
+};
+
+// VEC consecutive elements: ONE load of VEC * sizeof(raw) bytes (16 for 4 floats or 8 halves), kept raw until
+// agg_up converts them in registers -- so a batch issues all its loads before the first conversion waits for data.
+template <int DT, int VEC>
+using agg_raw_vec = typename AggElem<DT>::raw __attribute__((ext_vector_type(VEC)));
+
+template <int DT, int VEC>
+__device__ __forceinline__ agg_raw_vec<DT, VEC> agg_load_raw(const typename AggElem<DT>::raw* p) {
+  return *reinterpret_cast<const agg_raw_vec<DT, VEC>*>(p);
+}
+
+template <int DT, int VEC>
+__device__ __forceinline__ float __attribute__((ext_vector_type(VEC))) agg_up(agg_raw_vec<DT, VEC> q) {
+  if constexpr (DT == GLX_DTYPE_F32) {
+    return q;
+  } else {
+    float __attribute__((ext_vector_type(VEC))) r;
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) r[v] = AggElem<DT>::up(q[v]);
+    return r;
+  }
+}
+
+template <int DT, int VEC>
+__device__ __forceinline__ float __attribute__((ext_vector_type(VEC))) agg_load(const typename AggElem<DT>::raw* p) {
+  return agg_up<DT, VEC>(agg_load_raw<DT, VEC>(p));
+}
+
+// float32 -> half for the upload, round to nearest even, bit-identical -- all 2^32 inputs -- to
+// torch.Tensor.to(torch.bfloat16 / torch.float16) of a contiguous CPU tensor, i.e. torch's vectorised conversion.
+// NaN included: the vectorised bfloat16 conversion emits 0xFFFF for every NaN (torch's scalar fallback, used for
+// strided tensors, emits 0x7FC0; the uploads convert contiguous matrices), the float16 one keeps the sign and the top
+// ten payload bits and sets the quiet bit (sign | 0x7E00 | payload >> 13).  Integer arithmetic only, so no
+// floating-point mode (denormal flushing) can change a result.
+__host__ __device__ __forceinline__ uint16_t glx_f32_to_bf16_bits(uint32_t u) {
+  if ((u & 0x7fffffffu) > 0x7f800000u) return 0xFFFF;
+  return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);  // a carry out of the mantissa rounds up to the next binade / inf
+}
+__host__ __device__ __forceinline__ uint16_t glx_f32_to_f16_bits(uint32_t u) {
+  const uint32_t sign = (u >> 16) & 0x8000u;
+  const uint32_t a = u & 0x7fffffffu;
+  if (a > 0x7f800000u) return (uint16_t)(sign | 0x7E00u | ((a >> 13) & 0x3FFu));  // NaN: quiet, top payload bits
+  if (a >= 0x477FF000u) return (uint16_t)(sign | 0x7C00u);  // >= 65520 (half-way past 65504, ties to even = 2^16): inf
+  if (a >= 0x38800000u) {  // a normal half (>= 2^-14): rebias the exponent by 127 - 15, round off 13 mantissa bits
+    const uint32_t m = a - 0x38000000u;
+    return (uint16_t)(sign | ((m + 0xFFFu + ((m >> 13) & 1u)) >> 13));
+  }
+  // a half subnormal: round(|x| / 2^-24); |x| = mant 2^(e - 150), so shift the 24-bit significand by 126 - e
+  const uint32_t e = a >> 23;
+  const uint32_t sh = 126u - e;  // >= 14
+  if (sh >= 25u) return (uint16_t)sign;  // < 2^-25 (float32 subnormals and zeros included): +-0
+  const uint32_t mant = (a & 0x7fffffu) | 0x800000u;
+  const uint32_t q = mant >> sh, rem = mant & ((1u << sh) - 1u), half = 1u << (sh - 1u);
+  return (uint16_t)(sign | (q + ((rem > half || (rem == half && (q & 1u))) ? 1u : 0u)));  // q + 1 may be 0x400 = 2^-14
+}
+
 struct AggArgs {
-  const float* X;
+  const void* X;             // elements of `dtype` (X1 / X2 below: float32 only)
   const int64_t* node_ids;   // raw ids (dense map) ...
   const int32_t* rows;       // ... or pre-translated rows (hashed map / multi-source); one is null
   const int32_t* seg_start;  // [num_segments + 1], or null: uniform segments of `fanout` ids
@@ -187,6 +266,7 @@ struct AggArgs {
   const float* X2;
   int64_t stride1, swizzle1, stride2;
   int32_t base1, base2;
+  int32_t dtype;  // X's storage type (host side: picks the instantiation; last, so no field above moves)
 };
 
 // Feature rows are < 2^31 (checked at creation), so a row index fits an int32 --
@@ -197,18 +277,24 @@ __device__ __forceinline__ int32_t agg_row_at(const AggArgs& a, int32_t pos) {
   return (id >= 0 && id < a.num_rows) ? (int32_t)id : -1;
 }
 
-template <int NSRC>
-__device__ __forceinline__ const float* agg_row_ptr(const AggArgs& a, int32_t row) {
-  if (NSRC == 1 || row < a.base1) return a.X + glx_swizzle_row(row, a.swizzle_rows) * a.stride;
-  if (row < a.base2) return a.X1 + glx_swizzle_row(row - a.base1, a.swizzle1) * a.stride1;
-  return a.X2 + (int64_t)(row - a.base2) * a.stride2;
+template <int NSRC, int DT = GLX_DTYPE_F32>
+__device__ __forceinline__ const typename AggElem<DT>::raw* agg_row_ptr(const AggArgs& a, int32_t row) {
+  const typename AggElem<DT>::raw* X = static_cast<const typename AggElem<DT>::raw*>(a.X);
+  if constexpr (NSRC == 1) {
+    return X + glx_swizzle_row(row, a.swizzle_rows) * a.stride;
+  } else {
+    static_assert(DT == GLX_DTYPE_F32, "the distributed store's row sources are float32");
+    if (row < a.base1) return X + glx_swizzle_row(row, a.swizzle_rows) * a.stride;
+    if (row < a.base2) return a.X1 + glx_swizzle_row(row - a.base1, a.swizzle1) * a.stride1;
+    return a.X2 + (int64_t)(row - a.base2) * a.stride2;
+  }
 }
 
-// G lanes per segment, VEC floats per lane per pass (VEC = 4: one dwordx4 per
-// row per lane; VEC = 1 for dims that are not a multiple of 4).  U rows are
-// issued back-to-back before the first is consumed.  NSRC = 3: rows come from the
-// three sources of a distributed store.
-template <int OP, int G, int VEC, int U, int NSRC>
+// G lanes per segment, VEC elements per lane per pass (VEC = 4: one 16-byte load of
+// floats, 8 bytes of halves, per row per lane; VEC = 1 for dims that are not a multiple of 4).
+// U rows are issued back-to-back before the first is consumed.  NSRC = 3: rows come from the
+// three sources of a distributed store.  DT: the table's storage type.
+template <int OP, int G, int VEC, int U, int NSRC, int DT>
 __global__ __launch_bounds__(256) void glx_aggregate_kernel(AggArgs a) {
   typedef float vec_t __attribute__((ext_vector_type(VEC)));
   const int64_t gid = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / G;
@@ -238,7 +324,7 @@ __global__ __launch_bounds__(256) void glx_aggregate_kernel(AggArgs a) {
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         if (row[u] >= 0) {
-          val[u] = *reinterpret_cast<const vec_t*>(agg_row_ptr<NSRC>(a, row[u]) + col);
+          val[u] = agg_load<DT, VEC>(agg_row_ptr<NSRC, DT>(a, row[u]) + col);
         } else {
 #pragma unroll
           for (int v = 0; v < VEC; ++v) val[u][v] = a.default_attr;
@@ -315,39 +401,46 @@ __device__ __forceinline__ uint32_t agg_swizzle32(uint32_t r, uint32_t swizzle_r
   return r < swizzle_rows ? r ^ m : r;
 }
 
-template <int NSRC>
-__device__ __forceinline__ const float* agg_row_ptr32(const AggArgs& a, int32_t row) {
-  if (NSRC == 1 || row < a.base1) {
-    return a.X + (uint64_t)agg_swizzle32((uint32_t)row, (uint32_t)a.swizzle_rows) * (uint32_t)a.stride;
+// The pitch is in elements (< 2^31 of them), so the product scales by the element size in the pointer arithmetic.
+template <int NSRC, int DT>
+__device__ __forceinline__ const typename AggElem<DT>::raw* agg_row_ptr32(const AggArgs& a, int32_t row) {
+  const typename AggElem<DT>::raw* X = static_cast<const typename AggElem<DT>::raw*>(a.X);
+  if constexpr (NSRC == 1) {
+    return X + (uint64_t)agg_swizzle32((uint32_t)row, (uint32_t)a.swizzle_rows) * (uint32_t)a.stride;
+  } else {
+    static_assert(DT == GLX_DTYPE_F32, "the distributed store's row sources are float32");
+    if (row < a.base1) {
+      return X + (uint64_t)agg_swizzle32((uint32_t)row, (uint32_t)a.swizzle_rows) * (uint32_t)a.stride;
+    }
+    if (row < a.base2) {
+      return a.X1 + (uint64_t)agg_swizzle32((uint32_t)(row - a.base1), (uint32_t)a.swizzle1) * (uint32_t)a.stride1;
+    }
+    return a.X2 + (uint64_t)(uint32_t)(row - a.base2) * (uint32_t)a.stride2;
   }
-  if (row < a.base2) {
-    return a.X1 + (uint64_t)agg_swizzle32((uint32_t)(row - a.base1), (uint32_t)a.swizzle1) * (uint32_t)a.stride1;
-  }
-  return a.X2 + (uint64_t)(uint32_t)(row - a.base2) * (uint32_t)a.stride2;
 }
 
 // One batch: rows of chunk slots [slot0, slot0 + count), count <= U (kFull: count == U, no tests at all), all
 // loads issued before the first is folded into acc, in slot order.
-template <int OP, int G, int VEC, int U, int NSRC, int IDR, bool kFull>
+template <int OP, int G, int VEC, int U, int NSRC, int IDR, bool kFull, int DT>
 __device__ __forceinline__ void agg_grp_batch(const AggArgs& a, const int32_t (&myrow)[IDR], int32_t slot0, int32_t count,
                                               uint32_t col_ld, float __attribute__((ext_vector_type(VEC)))& acc) {
   typedef float vec_t __attribute__((ext_vector_type(VEC)));
   int32_t row[U];
 #pragma unroll
   for (int u = 0; u < U; ++u) row[u] = agg_chunk_get<G, IDR>(myrow, slot0 + u);
-  vec_t val[U];
+  agg_raw_vec<DT, VEC> val[U];
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     if (kFull || u < count) {
       // an unknown id (row -1) reads row 0 and is replaced below: no divergent branch around the load
       const int32_t r = row[u] >= 0 ? row[u] : 0;
-      val[u] = *reinterpret_cast<const vec_t*>(agg_row_ptr32<NSRC>(a, r) + col_ld);
+      val[u] = agg_load_raw<DT, VEC>(agg_row_ptr32<NSRC, DT>(a, r) + col_ld);
     }
   }
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     if (kFull || u < count) {
-      vec_t x = val[u];
+      vec_t x = agg_up<DT, VEC>(val[u]);
 #pragma unroll
       for (int v = 0; v < VEC; ++v) x[v] = row[u] < 0 ? a.default_attr : x[v];
 #pragma unroll
@@ -372,7 +465,13 @@ __device__ __forceinline__ uint32_t agg_stripe_block(uint32_t j, uint32_t P, uin
   return run * span + (r - k * P) * chunk + k;
 }
 
-template <int OP, int G, int VEC, int U, int NSRC, int IDR>
+__device__ __forceinline__ void agg_store4(int32_t store_mode, float* dst, float __attribute__((ext_vector_type(4))) v) {
+  typedef float f4 __attribute__((ext_vector_type(4)));
+  if (store_mode == 1) *reinterpret_cast<f4*>(dst) = v;
+  else __builtin_nontemporal_store(v, reinterpret_cast<f4*>(dst));
+}
+
+template <int OP, int G, int VEC, int U, int NSRC, int IDR, int DT>
 __global__ __launch_bounds__(256) void glx_aggregate_grp_kernel(AggArgs a) {
   typedef float vec_t __attribute__((ext_vector_type(VEC)));
   constexpr int kChunk = G * IDR;
@@ -428,8 +527,8 @@ __global__ __launch_bounds__(256) void glx_aggregate_grp_kernel(AggArgs a) {
           chunk_base = base;
           agg_chunk_load<G, IDR>(a, chunk_base, pos_end, c, myrow);
         }
-        if (stop - base == U) agg_grp_batch<OP, G, VEC, U, NSRC, IDR, true>(a, myrow, base - chunk_base, U, col_ld, acc);
-        else agg_grp_batch<OP, G, VEC, U, NSRC, IDR, false>(a, myrow, base - chunk_base, stop - base, col_ld, acc);
+        if (stop - base == U) agg_grp_batch<OP, G, VEC, U, NSRC, IDR, true, DT>(a, myrow, base - chunk_base, U, col_ld, acc);
+        else agg_grp_batch<OP, G, VEC, U, NSRC, IDR, false, DT>(a, myrow, base - chunk_base, stop - base, col_ld, acc);
       }
       // FinalFunc: aggregator.cc:74-86 (empty -> default), mean_aggregator.cc:45-61.
       const int32_t n = s1 - s0;
@@ -442,12 +541,18 @@ __global__ __launch_bounds__(256) void glx_aggregate_grp_kernel(AggArgs a) {
         for (int v = 0; v < VEC; ++v) acc[v] = acc[v] / fn;
       }
       if (col_ok) {
-        vec_t* dst = reinterpret_cast<vec_t*>(a.emb_out + sg * (int64_t)a.dim + col);
+        float* const dst = a.emb_out + sg * (int64_t)a.dim + col;
         // the outputs are written once and never read by this launch: the non-temporal hint (round 4, A/B in
         // profiles/r04/agg_probe_run8_nt_stores.txt: uniform rows -2.4 .. -5 %, the power-law requests -1 %, L2-resident -12 .. -20 %;
-        // `sc1` write-through stores: no gain).  GLX_AGG_STORE=1 restores plain stores.
-        if (a.store_mode == 1) *dst = acc;
-        else __builtin_nontemporal_store(acc, dst);
+        // `sc1` write-through stores: no gain).  GLX_AGG_STORE=1 restores plain stores.  A half table's lane owns 8
+        // columns: two 16-byte stores (emb_out is only known to be 16-byte aligned).
+        if constexpr (VEC == 8) {
+          agg_store4(a.store_mode, dst, acc.lo);
+          agg_store4(a.store_mode, dst + 4, acc.hi);
+        } else {
+          if (a.store_mode == 1) *reinterpret_cast<vec_t*>(dst) = acc;
+          else __builtin_nontemporal_store(acc, reinterpret_cast<vec_t*>(dst));
+        }
       }
       if (c == 0 && col_pass == 0) a.cnt_out[sg] = n;
     }
@@ -556,6 +661,8 @@ struct AggKnobs {
   std::atomic<int> store{0};    // GLX_AGG_STORE=1: plain output stores instead of non-temporal ones (ablation)
   std::atomic<int> stripes{-1}; // GLX_AGG_XCD_STRIPES=0: workgroup j of a slice reduces segment block j (no XCD stripes); 1 = on; -1 = default
   std::atomic<int> chunk{0};    // GLX_AGG_XCD_CHUNK: segment blocks per XCD stripe chunk (0 = kXcdStripeChunk)
+  std::atomic<int> half_ld16{0};// GLX_AGG_HALF_LD16=1: half tables in the grouped kernel with 16-byte loads of 8 columns per
+                                // lane instead of 8-byte loads over the float32 lane-to-column map (ablation)
 };
 
 AggKnobs& agg_knobs() {
@@ -576,13 +683,15 @@ AggKnobs& agg_knobs() {
     k.store = env("GLX_AGG_STORE");
     if (getenv("GLX_AGG_XCD_STRIPES")) k.stripes = env("GLX_AGG_XCD_STRIPES");
     k.chunk = env("GLX_AGG_XCD_CHUNK");
+    k.half_ld16 = env("GLX_AGG_HALF_LD16");
   });
   return k;
 }
 
 bool agg_use_mfma(const AggArgs& a, int op) {
   if (agg_knobs().mfma.load(std::memory_order_relaxed) == 0) return false;
-  return (op == GLX_AGG_SUM || op == GLX_AGG_MEAN) && a.seg_start == nullptr && a.fanout > 0 && a.X1 == nullptr &&
+  // float32 tables only: a half table takes the VALU kernel with the knob set
+  return a.dtype == GLX_DTYPE_F32 && (op == GLX_AGG_SUM || op == GLX_AGG_MEAN) && a.seg_start == nullptr && a.fanout > 0 && a.X1 == nullptr &&
          a.X2 == nullptr && (a.dim == 64 || a.dim == 128 || a.dim == 256) && (a.stride % 4) == 0 &&
          (reinterpret_cast<uintptr_t>(a.X) & 15) == 0;
 }
@@ -599,12 +708,12 @@ void launch_agg_mfma(const AggArgs& a, hipStream_t s) {
 // ---- legacy kernel launch (narrow / unaligned shapes, and GLX_AGG_LEGACY=1) --------------------------------
 // Rows in flight per lane of glx_aggregate_kernel: A/B on the C3 hop-2 request (profiles/r02/agg_unroll_probe.txt)
 // 3 / 4 / 5 / 6 / 8 / 10 / 12 rows -> 2.26 / 2.19 / 2.11 / 2.10 / 2.21 / 2.49 / 2.48 ms; wide float4 shapes 6, narrow 8.
-template <int OP, int G, int VEC, int NSRC>
+template <int OP, int G, int VEC, int NSRC, int DT>
 void launch_agg_g(const AggArgs& a, hipStream_t s) {
   const int64_t threads = (int64_t)a.num_segments * G;
   const unsigned grid = (unsigned)((threads + 255) / 256);
   constexpr bool kWide = VEC == 4 && G >= 32;
-  glx_aggregate_kernel<OP, G, VEC, kWide ? 6 : 8, NSRC><<<grid, 256, 0, s>>>(a);
+  glx_aggregate_kernel<OP, G, VEC, kWide ? 6 : 8, NSRC, DT><<<grid, 256, 0, s>>>(a);
 }
 
 // ---- grouped kernel launch ---------------------------------------------------------------------------------
@@ -628,7 +737,7 @@ int agg_grp_unroll(int32_t fanout, int32_t avg_len) {
   return best;
 }
 
-template <int OP, int G, int VEC, int NSRC, int IDR>
+template <int OP, int G, int VEC, int NSRC, int IDR, int DT>
 void launch_agg_grp(AggArgs a, int32_t num_ids, hipStream_t s) {
   const int32_t avg = a.num_segments > 0 ? (int32_t)(num_ids / a.num_segments) : 0;
   // segments per group: one.  More (a chunk of ids then serves several segments: one id load per G * IDR / fanout
@@ -643,7 +752,9 @@ void launch_agg_grp(AggArgs a, int32_t num_ids, hipStream_t s) {
   // third of the waves to launch and drain) took 0.49 -> 0.43 ms, while the same setting LOSES on the tables HBM
   // serves: C2 (1.2 GB) 0.55 -> 0.63, C4 0.98 -> 1.08, C3 (10 GB) 1.84 -> 1.84 (profiles/r06/agg_probe_*_segs.txt).
   // Small requests stay at one (a group per segment fills the chip sooner).
-  if (NSRC == 1 && (int64_t)a.num_rows * a.stride * 4 <= ((int64_t)1 << 30) && a.num_segments >= 3 * 32768) S = 3;
+  // (the test is on the table's bytes: a half table of twice the rows is as small)
+  constexpr int64_t kElemBytes = sizeof(typename AggElem<DT>::raw);
+  if (NSRC == 1 && (int64_t)a.num_rows * a.stride * kElemBytes <= ((int64_t)1 << 30) && a.num_segments >= 3 * 32768) S = 3;
   if (want > 0) S = want;
   if (S > G - 1) S = G - 1;  // lane j of the group holds the start of its j-th segment (and lane S the end)
   if (S < 1) S = 1;
@@ -666,55 +777,75 @@ void launch_agg_grp(AggArgs a, int32_t num_ids, hipStream_t s) {
   const int occ = agg_knobs().occ.load(std::memory_order_relaxed);
   const size_t lds = (occ >= 3 && occ <= 7) ? (size_t)(160 * 1024 / occ) & ~(size_t)255 : 0;
   switch (agg_grp_unroll(a.seg_start ? 0 : a.fanout, avg)) {
-    case 6: glx_aggregate_grp_kernel<OP, G, VEC, 6, NSRC, IDR><<<grid, 256, lds, s>>>(a); break;
-    case 8: glx_aggregate_grp_kernel<OP, G, VEC, 8, NSRC, IDR><<<grid, 256, lds, s>>>(a); break;
-    case 12: glx_aggregate_grp_kernel<OP, G, VEC, 12, NSRC, IDR><<<grid, 256, lds, s>>>(a); break;
-    case 15: glx_aggregate_grp_kernel<OP, G, VEC, 15, NSRC, IDR><<<grid, 256, lds, s>>>(a); break;
-    default: glx_aggregate_grp_kernel<OP, G, VEC, 10, NSRC, IDR><<<grid, 256, lds, s>>>(a); break;
+    case 6: glx_aggregate_grp_kernel<OP, G, VEC, 6, NSRC, IDR, DT><<<grid, 256, lds, s>>>(a); break;
+    case 8: glx_aggregate_grp_kernel<OP, G, VEC, 8, NSRC, IDR, DT><<<grid, 256, lds, s>>>(a); break;
+    case 12: glx_aggregate_grp_kernel<OP, G, VEC, 12, NSRC, IDR, DT><<<grid, 256, lds, s>>>(a); break;
+    case 15: glx_aggregate_grp_kernel<OP, G, VEC, 15, NSRC, IDR, DT><<<grid, 256, lds, s>>>(a); break;
+    default: glx_aggregate_grp_kernel<OP, G, VEC, 10, NSRC, IDR, DT><<<grid, 256, lds, s>>>(a); break;
   }
 }
 
-template <int OP, int NSRC>
+// The grouped kernel at G = 64 / 32 / 16 / 8 lanes per segment for `lanes` = columns / VEC.
+template <int OP, int VEC, int NSRC, int DT>
+void launch_agg_grp_g(const AggArgs& a, int lanes, int32_t num_ids, hipStream_t s) {
+  if (lanes >= 64) launch_agg_grp<OP, 64, VEC, NSRC, 1, DT>(a, num_ids, s);
+  else if (lanes >= 32) launch_agg_grp<OP, 32, VEC, NSRC, 1, DT>(a, num_ids, s);
+  else if (lanes >= 16) launch_agg_grp<OP, 16, VEC, NSRC, 1, DT>(a, num_ids, s);
+  else launch_agg_grp<OP, 8, VEC, NSRC, 2, DT>(a, num_ids, s);
+}
+
+template <int OP, int NSRC, int DT>
 void launch_agg_cols(const AggArgs& a0, int32_t num_ids, int want_xcd, hipStream_t s) {
   AggArgs a = a0;
+  // the per-segment kernel's VEC = 4 path: 4 elements per lane (16 bytes of floats, 8 of halves)
   bool vec4 = a.dim % 4 == 0 && a.ncols % 4 == 0 && a.col0 % 4 == 0 && (reinterpret_cast<uintptr_t>(a.emb_out) & 15) == 0 &&
               (reinterpret_cast<uintptr_t>(a.X) & 15) == 0 && (a.stride % 4) == 0;
   if (NSRC > 1) {
     vec4 = vec4 && (reinterpret_cast<uintptr_t>(a.X1) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.X2) & 15) == 0 &&
            (a.stride1 % 4) == 0 && (a.stride2 % 4) == 0;
   }
+  // the grouped kernel: EV = 4 elements per lane, one load per row -- 16 bytes of floats, 8 of halves -- so a half
+  // table keeps the float32 lane-to-column map, group size and slicing.  Measured on the C3 hop-2 request
+  // (profiles/r08/half_features.txt, bfloat16, same process, ms): 8-byte loads 1.24 (whole rows) / 1.33 (two slices)
+  // against 16-byte loads of 8 columns per lane -- half the lanes per segment, so G = 32 at D = 256 and no scalar
+  // row path -- 1.62 / 1.65, no faster than the float32 table's 1.63.  GLX_AGG_HALF_LD16=1 selects the 16-byte
+  // loads (every dimension, pitch and offset a multiple of 8 elements).
+  const int ev = (DT != GLX_DTYPE_F32 && agg_knobs().half_ld16.load(std::memory_order_relaxed) != 0) ? 8 : 4;
+  const bool wide = vec4 && a.dim % ev == 0 && a.ncols % ev == 0 && a.col0 % ev == 0 && (a.stride % ev) == 0;
   // the grouped kernel reads row 0 in place of an unknown id's row: some row must exist
   const bool has_rows = NSRC > 1 ? (a.X2 != nullptr || a.base2 > 0) : a.num_rows > 0;
-  if (vec4 && has_rows && a.ncols >= 32 && agg_knobs().legacy.load(std::memory_order_relaxed) == 0) {
-    if (want_xcd > 1 && a.col0 == 0 && a.ncols == a.dim && a.dim % (4 * want_xcd) == 0 && a.dim / want_xcd >= 32) {
+  if (wide && has_rows && a.ncols >= 8 * ev && agg_knobs().legacy.load(std::memory_order_relaxed) == 0) {
+    if (want_xcd > 1 && a.col0 == 0 && a.ncols == a.dim && a.dim % (ev * want_xcd) == 0 && a.dim / want_xcd >= 8 * ev) {
       a.xcd_slices = want_xcd;  // only the grouped kernel knows about slices
       a.ncols = a.dim / want_xcd;
     }
     // lanes per segment, 16-byte loads each.  (8-byte loads over twice the lanes -- a whole wave per 128-column slice
     // keeps the scalar row path -- were measured and dropped: equal on uniform rows, 13 % slower on the power-law
     // request; profiles/r04/agg_probe_*_run4.txt.  The kernel keeps its VEC parameter.)
-    const int lanes = a.ncols / 4;
-    if (lanes >= 64) launch_agg_grp<OP, 64, 4, NSRC, 1>(a, num_ids, s);
-    else if (lanes >= 32) launch_agg_grp<OP, 32, 4, NSRC, 1>(a, num_ids, s);
-    else if (lanes >= 16) launch_agg_grp<OP, 16, 4, NSRC, 1>(a, num_ids, s);
-    else launch_agg_grp<OP, 8, 4, NSRC, 2>(a, num_ids, s);
+    if constexpr (DT != GLX_DTYPE_F32) {
+      if (ev == 8) {
+        launch_agg_grp_g<OP, 8, NSRC, DT>(a, a.ncols / 8, num_ids, s);
+        return;
+      }
+    }
+    launch_agg_grp_g<OP, 4, NSRC, DT>(a, a.ncols / 4, num_ids, s);
     return;
   }
   if (vec4) {
     const int lanes = a.ncols / 4;
-    if (lanes >= 64) launch_agg_g<OP, 64, 4, NSRC>(a, s);
-    else if (lanes >= 32) launch_agg_g<OP, 32, 4, NSRC>(a, s);
-    else if (lanes >= 16) launch_agg_g<OP, 16, 4, NSRC>(a, s);
-    else if (lanes >= 8) launch_agg_g<OP, 8, 4, NSRC>(a, s);
-    else if (lanes >= 4) launch_agg_g<OP, 4, 4, NSRC>(a, s);
-    else if (lanes >= 2) launch_agg_g<OP, 2, 4, NSRC>(a, s);
-    else launch_agg_g<OP, 1, 4, NSRC>(a, s);
+    if (lanes >= 64) launch_agg_g<OP, 64, 4, NSRC, DT>(a, s);
+    else if (lanes >= 32) launch_agg_g<OP, 32, 4, NSRC, DT>(a, s);
+    else if (lanes >= 16) launch_agg_g<OP, 16, 4, NSRC, DT>(a, s);
+    else if (lanes >= 8) launch_agg_g<OP, 8, 4, NSRC, DT>(a, s);
+    else if (lanes >= 4) launch_agg_g<OP, 4, 4, NSRC, DT>(a, s);
+    else if (lanes >= 2) launch_agg_g<OP, 2, 4, NSRC, DT>(a, s);
+    else launch_agg_g<OP, 1, 4, NSRC, DT>(a, s);
   } else {
     const int lanes = a.ncols;
-    if (lanes >= 64) launch_agg_g<OP, 64, 1, NSRC>(a, s);
-    else if (lanes >= 16) launch_agg_g<OP, 16, 1, NSRC>(a, s);
-    else if (lanes >= 4) launch_agg_g<OP, 4, 1, NSRC>(a, s);
-    else launch_agg_g<OP, 1, 1, NSRC>(a, s);
+    if (lanes >= 64) launch_agg_g<OP, 64, 1, NSRC, DT>(a, s);
+    else if (lanes >= 16) launch_agg_g<OP, 16, 1, NSRC, DT>(a, s);
+    else if (lanes >= 4) launch_agg_g<OP, 4, 1, NSRC, DT>(a, s);
+    else launch_agg_g<OP, 1, 1, NSRC, DT>(a, s);
   }
 }
 
@@ -744,7 +875,7 @@ void launch_agg_cols(const AggArgs& a0, int32_t num_ids, int want_xcd, hipStream
 constexpr int32_t kXcdSliceMinIds = 4 << 20;
 constexpr int32_t kXcdStripeChunk = 64;
 
-template <int OP, int NSRC>
+template <int OP, int NSRC, int DT>
 void launch_agg_n(const AggArgs& a0, int32_t num_ids, hipStream_t s) {
   AggArgs a = a0;
   a.col0 = 0;
@@ -753,7 +884,7 @@ void launch_agg_n(const AggArgs& a0, int32_t num_ids, hipStream_t s) {
   int stripes = agg_knobs().stripes.load(std::memory_order_relaxed);
   if (stripes < 0) stripes = num_ids >= kXcdSliceMinIds ? 1 : 0;
   int xcd = agg_knobs().xcd.load(std::memory_order_relaxed);
-  if (xcd == 0) {
+  if (xcd == 0) {  // by columns for every storage type: a half table at D = 256 is fastest whole, too (r08)
     xcd = (num_ids >= kXcdSliceMinIds && a.dim % 8 == 0 && a.dim >= 128) ? 2 : 1;
     if (xcd == 2 && stripes > 0 && a.dim >= 256) xcd = 1;
   }
@@ -766,47 +897,69 @@ void launch_agg_n(const AggArgs& a0, int32_t num_ids, hipStream_t s) {
   for (int c = 0; c < slices; ++c) {
     a.ncols = a.dim / slices;
     a.col0 = c * a.ncols;
-    launch_agg_cols<OP, NSRC>(a, num_ids, slices == 1 ? xcd : 1, s);
+    launch_agg_cols<OP, NSRC, DT>(a, num_ids, slices == 1 ? xcd : 1, s);
   }
 }
 
 template <int OP>
 void launch_agg(const AggArgs& a, int32_t num_ids, hipStream_t s) {
-  if (a.X1 || a.X2) launch_agg_n<OP, 3>(a, num_ids, s);
-  else launch_agg_n<OP, 1>(a, num_ids, s);
+  if (a.X1 || a.X2) launch_agg_n<OP, 3, GLX_DTYPE_F32>(a, num_ids, s);  // the distributed store: float32 only
+  else if (a.dtype == GLX_DTYPE_BF16) launch_agg_n<OP, 1, GLX_DTYPE_BF16>(a, num_ids, s);
+  else if (a.dtype == GLX_DTYPE_F16) launch_agg_n<OP, 1, GLX_DTYPE_F16>(a, num_ids, s);
+  else launch_agg_n<OP, 1, GLX_DTYPE_F32>(a, num_ids, s);
 }
 
-// Upload: row r of the caller's dense [V, D] matrix -> its (swizzled, pitched) slot.
-__global__ void glx_place_rows_kernel(const float* __restrict__ src, int64_t num_rows, int32_t dim,
-                                      int64_t stride, int64_t swizzle_rows, float* __restrict__ dst) {
+// Upload: row r of the caller's dense [V, D] matrix -> its (swizzled, pitched) slot.  SRC / DST: element types of
+// the caller's matrix and of the table; float32 -> half rounds (glx_f32_to_bf16_bits / glx_f32_to_f16_bits), equal
+// types copy the bits.
+template <int SRC, int DST>
+__global__ void glx_place_rows_kernel(const void* __restrict__ src_v, int64_t num_rows, int32_t dim,
+                                      int64_t stride, int64_t swizzle_rows, void* __restrict__ dst_v) {
+  typedef typename std::conditional<SRC == GLX_DTYPE_F32, uint32_t, uint16_t>::type src_t;
+  typedef typename std::conditional<DST == GLX_DTYPE_F32, uint32_t, uint16_t>::type dst_t;
+  const src_t* __restrict__ src = static_cast<const src_t*>(src_v);
+  dst_t* __restrict__ dst = static_cast<dst_t*>(dst_v);
   const int64_t total = num_rows * (int64_t)dim;
   const int64_t step = (int64_t)gridDim.x * blockDim.x;
   for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += step) {
     const int64_t r = t / dim;
     const int32_t c = (int32_t)(t - r * dim);
-    dst[glx_swizzle_row(r, swizzle_rows) * stride + c] = src[t];
+    dst_t v;
+    if constexpr (SRC == DST) v = src[t];
+    else if constexpr (DST == GLX_DTYPE_BF16) v = glx_f32_to_bf16_bits(src[t]);
+    else v = glx_f32_to_f16_bits(src[t]);
+    dst[glx_swizzle_row(r, swizzle_rows) * stride + c] = v;
   }
 }
 
-// Feature gather (LookupNodes float attributes): G lanes per output row.
-__global__ __launch_bounds__(256) void glx_lookup_kernel(GlxIdMap map, const float* __restrict__ X,
+// Feature gather (LookupNodes float attributes): G lanes per output row; a half table's rows are upcast to float32.
+template <int DT>
+__global__ __launch_bounds__(256) void glx_lookup_kernel(GlxIdMap map, const void* __restrict__ Xv,
                                                          int64_t stride, int64_t swizzle_rows, int32_t dim, const int64_t* __restrict__ ids,
                                                          int64_t n, float default_attr,
                                                          float* __restrict__ out, int G) {
+  const typename AggElem<DT>::raw* __restrict__ X = static_cast<const typename AggElem<DT>::raw*>(Xv);
   const int64_t gid = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / G;
   const int c = threadIdx.x % G;
   if (gid >= n) return;
   int64_t row = glx_row_of(map, ids[gid]);
   if (row >= 0) row = glx_swizzle_row(row, swizzle_rows);
   float* o = out + gid * (int64_t)dim;
-  if ((dim & 3) == 0) {
+  // 4 elements per lane: a float32 table's rows as they always were; a half table's only when its rows are 8-byte
+  // aligned (a view's pitch is its dim, its base the caller's)
+  bool vec4 = (dim & 3) == 0;
+  if constexpr (DT != GLX_DTYPE_F32) vec4 = vec4 && (stride & 3) == 0 && (reinterpret_cast<uintptr_t>(Xv) & 7) == 0;
+  if (vec4) {
     for (int32_t col = c * 4; col < dim; col += G * 4) {
       float4 v = make_float4(default_attr, default_attr, default_attr, default_attr);
-      if (row >= 0) v = *reinterpret_cast<const float4*>(X + row * stride + col);
+      if (row >= 0) {
+        const float __attribute__((ext_vector_type(4))) q = agg_load<DT, 4>(X + row * stride + col);
+        v = make_float4(q[0], q[1], q[2], q[3]);
+      }
       *reinterpret_cast<float4*>(o + col) = v;
     }
   } else {
-    for (int32_t col = c; col < dim; col += G) o[col] = row >= 0 ? X[row * stride + col] : default_attr;
+    for (int32_t col = c; col < dim; col += G) o[col] = row >= 0 ? AggElem<DT>::up(X[row * stride + col]) : default_attr;
   }
 }
 
@@ -955,6 +1108,7 @@ int aggregate_device(const glx_features* f, int op, const int64_t* d_ids, const 
     glx_rows_kernel<<<(unsigned)((num_ids + 255) / 256), 256, 0, s>>>(f->map(), d_ids, num_ids, rows);
   }
   a.X = f->X;
+  a.dtype = f->dtype;
   a.node_ids = hashed ? nullptr : d_ids;
   a.rows = rows;
   a.emb_out = d_emb;
@@ -1086,6 +1240,7 @@ extern "C" int glx_tune(const char* name, int32_t value) {
   else if (strcmp(name, "agg_store") == 0) slot = &k.store;
   else if (strcmp(name, "agg_xcd_stripes") == 0) slot = &k.stripes;
   else if (strcmp(name, "agg_xcd_chunk") == 0) slot = &k.chunk;
+  else if (strcmp(name, "agg_half_ld16") == 0) slot = &k.half_ld16;
   else if (strcmp(name, "seg_epochs_before_wrap") == 0) {
     // test aid: the calling thread's segment-word buffers hand out `value` more epochs before their counter wraps
     GLX_REQUIRE(value >= 0, "seg_epochs_before_wrap must be >= 0");
@@ -1116,17 +1271,32 @@ extern "C" int glx_tune(const char* name, int32_t value) {
 extern "C" int glx_features_create(int device, int64_t num_rows, int32_t dim, const float* X,
                                    const int64_t* ids, int ptr_kind, void* stream,
                                    glx_features** out) {
-  return glx_features_create_impl(device, num_rows, dim, X, ids, ptr_kind, stream, true, out);
+  return glx_features_create_impl(device, num_rows, dim, X, GLX_DTYPE_F32, GLX_DTYPE_F32, ids, ptr_kind, stream, true, out);
 }
 
-int glx_features_create_impl(int device, int64_t num_rows, int32_t dim, const float* X, const int64_t* ids, int ptr_kind,
-                             void* stream, bool allow_arithmetic_ids, glx_features** out) {
+extern "C" int glx_features_create_ex(int device, int64_t num_rows, int32_t dim, const void* X, int x_dtype,
+                                      int store_dtype, const int64_t* ids, int ptr_kind, void* stream,
+                                      glx_features** out) {
+  return glx_features_create_impl(device, num_rows, dim, X, x_dtype, store_dtype, ids, ptr_kind, stream, true, out);
+}
+
+namespace {
+bool glx_dtype_known(int dtype) { return dtype == GLX_DTYPE_F32 || dtype == GLX_DTYPE_BF16 || dtype == GLX_DTYPE_F16; }
+}  // namespace
+
+int glx_features_create_impl(int device, int64_t num_rows, int32_t dim, const void* X, int x_dtype, int store_dtype,
+                             const int64_t* ids, int ptr_kind, void* stream, bool allow_arithmetic_ids, glx_features** out) {
   GLX_REQUIRE(out != nullptr, "out is NULL");
   *out = nullptr;
   GLX_REQUIRE(num_rows >= 0 && dim > 0, "bad shape [%lld, %d]", (long long)num_rows, dim);
   GLX_REQUIRE(num_rows < INT32_MAX, "num_rows must be < 2^31");
   GLX_REQUIRE(num_rows == 0 || X != nullptr, "X is NULL");
   GLX_REQUIRE(ptr_kind == GLX_PTR_HOST || ptr_kind == GLX_PTR_DEVICE, "bad ptr_kind");
+  GLX_REQUIRE(glx_dtype_known(x_dtype), "unknown x_dtype %d", x_dtype);
+  GLX_REQUIRE(glx_dtype_known(store_dtype), "unknown store_dtype %d", store_dtype);
+  GLX_REQUIRE(x_dtype == store_dtype || x_dtype == GLX_DTYPE_F32,
+              "a %s matrix cannot be stored as %s (only float32 input converts)", glx_dtype_name(x_dtype),
+              glx_dtype_name(store_dtype));
   int rc = glx_init_device(device);
   if (rc != GLX_OK) return rc;
   GlxDeviceGuard guard(device);
@@ -1138,37 +1308,47 @@ int glx_features_create_impl(int device, int64_t num_rows, int32_t dim, const fl
   f->device = device;
   f->num_rows = num_rows;
   f->dim = dim;
+  f->dtype = store_dtype;
+  f->elem_size = store_dtype == GLX_DTYPE_F32 ? 4 : 2;
   f->owns_x = true;
   // Row pitch.  When a row is a multiple of 256 bytes, rows whose ids share low
   // zero bits (RMAT-style / power-of-two-structured ids are exactly the hub ids)
   // alias onto the same cache sets and HBM channels; one extra 64-byte sector per
   // row breaks the power-of-two stride.  GLX_FEATURE_ROW_PAD overrides (floats).
+  // The pad counts FLOATS for every storage type -- the same bytes, 2 pad elements per float of a half table --
+  // so a multiple of 4 keeps every row 16-byte aligned whatever the table stores.
   int64_t pad = 0;
   if (const char* env = getenv("GLX_FEATURE_ROW_PAD")) pad = atoll(env);  // experiment knob (floats)
   if (pad < 0 || (pad % 4) != 0) pad = 0;
-  f->stride = dim + pad;
+  f->stride = dim + pad * 4 / f->elem_size;
   f->swizzle_rows = (num_rows >> GLX_SWIZZLE_BITS) << GLX_SWIZZLE_BITS;
   if (const char* env = getenv("GLX_FEATURE_SWIZZLE")) {
     if (atoi(env) == 0) f->swizzle_rows = 0;
   }
-  const size_t bytes = (size_t)(num_rows > 0 ? num_rows : 1) * f->stride * sizeof(float);
+  const size_t bytes = (size_t)(num_rows > 0 ? num_rows : 1) * f->stride * f->elem_size;
   hipError_t e = hipMalloc(&f->X, bytes);
   GlxTemp staged;
   if (e == hipSuccess && num_rows > 0) {
-    const float* d_src = X;
+    const void* d_src = X;
+    const size_t src_bytes = (size_t)num_rows * dim * (x_dtype == GLX_DTYPE_F32 ? 4 : 2);
     if (ptr_kind == GLX_PTR_HOST) {
-      e = hipMalloc(&staged.p, (size_t)num_rows * dim * sizeof(float));
-      if (e == hipSuccess) {
-        e = hipMemcpyAsync(staged.p, X, (size_t)num_rows * dim * sizeof(float), hipMemcpyHostToDevice, s);
-      }
-      d_src = staged.as<float>();
+      e = hipMalloc(&staged.p, src_bytes);
+      if (e == hipSuccess) e = hipMemcpyAsync(staged.p, X, src_bytes, hipMemcpyHostToDevice, s);
+      d_src = staged.p;
     }
     if (e == hipSuccess) {
       const int64_t total = num_rows * (int64_t)dim;
       int64_t blocks = (total + 255) / 256;
       if (blocks > 65536) blocks = 65536;
-      glx_place_rows_kernel<<<(unsigned)blocks, 256, 0, s>>>(d_src, num_rows, dim, f->stride,
-                                                            f->swizzle_rows, f->X);
+      auto place = glx_place_rows_kernel<GLX_DTYPE_F32, GLX_DTYPE_F32>;
+      if (store_dtype == GLX_DTYPE_BF16) {
+        place = x_dtype == GLX_DTYPE_F32 ? glx_place_rows_kernel<GLX_DTYPE_F32, GLX_DTYPE_BF16>
+                                         : glx_place_rows_kernel<GLX_DTYPE_BF16, GLX_DTYPE_BF16>;
+      } else if (store_dtype == GLX_DTYPE_F16) {
+        place = x_dtype == GLX_DTYPE_F32 ? glx_place_rows_kernel<GLX_DTYPE_F32, GLX_DTYPE_F16>
+                                         : glx_place_rows_kernel<GLX_DTYPE_F16, GLX_DTYPE_F16>;
+      }
+      place<<<(unsigned)blocks, 256, 0, s>>>(d_src, num_rows, dim, f->stride, f->swizzle_rows, f->X);
     }
   }
   int64_t* tmp_ids = nullptr;
@@ -1196,11 +1376,17 @@ int glx_features_create_impl(int device, int64_t num_rows, int32_t dim, const fl
 
 extern "C" int glx_features_view(int device, int64_t num_rows, int32_t dim, const float* X_device,
                                  glx_features** out) {
+  return glx_features_view_ex(device, num_rows, dim, X_device, GLX_DTYPE_F32, out);
+}
+
+extern "C" int glx_features_view_ex(int device, int64_t num_rows, int32_t dim, const void* X_device, int dtype,
+                                    glx_features** out) {
   GLX_REQUIRE(out != nullptr, "out is NULL");
   *out = nullptr;
   GLX_REQUIRE(num_rows >= 0 && dim > 0, "bad shape [%lld, %d]", (long long)num_rows, dim);
   GLX_REQUIRE(num_rows < INT32_MAX, "num_rows must be < 2^31");
   GLX_REQUIRE(num_rows == 0 || X_device != nullptr, "X is NULL");
+  GLX_REQUIRE(glx_dtype_known(dtype), "unknown dtype %d", dtype);
   int rc = glx_init_device(device);
   if (rc != GLX_OK) return rc;
   glx_features* f = new (std::nothrow) glx_features();
@@ -1211,7 +1397,9 @@ extern "C" int glx_features_view(int device, int64_t num_rows, int32_t dim, cons
   f->dim = dim;
   f->stride = dim;
   f->swizzle_rows = 0;  // a view addresses the caller's rows as they are
-  f->X = const_cast<float*>(X_device);
+  f->X = const_cast<void*>(X_device);
+  f->dtype = dtype;
+  f->elem_size = dtype == GLX_DTYPE_F32 ? 4 : 2;
   f->owns_x = false;
   *out = f;
   return GLX_OK;
@@ -1232,6 +1420,13 @@ extern "C" int glx_features_info(const glx_features* f, int64_t* num_rows, int32
   if (dim) *dim = f->dim;
   if (has_id_map) *has_id_map = f->idmap.any();
   if (device) *device = f->device;
+  return GLX_OK;
+}
+
+extern "C" int glx_features_dtype(const glx_features* f, int* dtype) {
+  GLX_REQUIRE(f != nullptr, "features is NULL");
+  GLX_REQUIRE(dtype != nullptr, "dtype is NULL");
+  *dtype = f->dtype;
   return GLX_OK;
 }
 
@@ -1289,8 +1484,17 @@ extern "C" int glx_lookup(const glx_features* f, const int64_t* node_ids, int64_
   int rc = st.begin();
   if (rc == GLX_OK) {
     GlxKernelTimer timer(GLX_KERNEL_LOOKUP, st.s);
-    glx_lookup_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, st.s>>>(f->map(), f->X, f->stride, f->swizzle_rows, f->dim,
-                                                                          d_ids, n, default_attr, d_out, G);
+    const unsigned grid = (unsigned)((threads + 255) / 256);
+    if (f->dtype == GLX_DTYPE_BF16) {
+      glx_lookup_kernel<GLX_DTYPE_BF16><<<grid, 256, 0, st.s>>>(f->map(), f->X, f->stride, f->swizzle_rows, f->dim, d_ids, n,
+                                                               default_attr, d_out, G);
+    } else if (f->dtype == GLX_DTYPE_F16) {
+      glx_lookup_kernel<GLX_DTYPE_F16><<<grid, 256, 0, st.s>>>(f->map(), f->X, f->stride, f->swizzle_rows, f->dim, d_ids, n,
+                                                              default_attr, d_out, G);
+    } else {
+      glx_lookup_kernel<GLX_DTYPE_F32><<<grid, 256, 0, st.s>>>(f->map(), f->X, f->stride, f->swizzle_rows, f->dim, d_ids, n,
+                                                              default_attr, d_out, G);
+    }
     timer.stop();
   }
   return st.finish(rc);

@@ -207,9 +207,9 @@ int glx_partition_tail(int device, const int64_t* ids, int64_t n, int32_t num_sh
 void glx_idmap_free(GlxIdMapStorage* m);
 struct glx_features;
 // glx_features_create; allow_arithmetic_ids = false keeps a hash table whatever the ids look like (the hot-row replica
-// of a distributed store packs that table into its own slots).
-int glx_features_create_impl(int device, int64_t num_rows, int32_t dim, const float* X, const int64_t* ids, int ptr_kind,
-                             void* stream, bool allow_arithmetic_ids, glx_features** out);
+// of a distributed store packs that table into its own slots).  x_dtype / store_dtype: glx_features_create_ex.
+int glx_features_create_impl(int device, int64_t num_rows, int32_t dim, const void* X, int x_dtype, int store_dtype,
+                             const int64_t* ids, int ptr_kind, void* stream, bool allow_arithmetic_ids, glx_features** out);
 
 // ---------------------------------------------------------------- handles ---
 struct GlxAdj {  // one CSR slot: a single 16-byte gather per draw
@@ -276,13 +276,19 @@ struct glx_features {
   int device;
   int64_t num_rows;
   int32_t dim;
-  int64_t stride;  // floats between consecutive rows (>= dim; see glx_features_create)
+  int64_t stride;  // elements between consecutive rows (>= dim; see glx_features_create)
   int64_t swizzle_rows;  // rows [0, swizzle_rows) are stored at glx_swizzle_row(r); 0 = off
-  float* X;  // [V, stride] row-major, base 256-byte aligned
+  void* X;  // [V, stride] row-major elements of `dtype`, base 256-byte aligned
+  int dtype;       // GLX_DTYPE_F32 | GLX_DTYPE_BF16 | GLX_DTYPE_F16: the storage type (accumulation is always float32)
+  int32_t elem_size;  // bytes per element: 4 or 2
   bool owns_x;
   GlxIdMapStorage idmap;
   GlxIdMap map() const { return idmap.view(num_rows); }
 };
+
+inline const char* glx_dtype_name(int dtype) {
+  return dtype == GLX_DTYPE_F32 ? "float32" : dtype == GLX_DTYPE_BF16 ? "bfloat16" : dtype == GLX_DTYPE_F16 ? "float16" : "?";
+}
 
 // AliasMethod::Build (alias_method.cc:57-107) for ONE distribution of `count` weights,
 // bit-identical to the serial reference: LIFO low/high stacks (`low` grows up from its

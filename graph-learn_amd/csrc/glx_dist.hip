@@ -1381,8 +1381,9 @@ int resolve_and_fetch(glx_dist_store* st, int slot, const int64_t* d_ids, int64_
     stat.bytes_received = (m - rt.recv_counts[me]) * 8 + (rt.n_send - self_ids) * (int64_t)dim * 4;
   }
   out->loc = loc;
-  out->src[0] = GlxRowSource{f->X, f->stride, f->swizzle_rows, n_own};
-  out->src[1] = st->cache ? GlxRowSource{st->cache->X, st->cache->stride, st->cache->swizzle_rows, n_cache}
+  // float32 tables only: glx_dist_store_create refuses half ones
+  out->src[0] = GlxRowSource{static_cast<const float*>(f->X), f->stride, f->swizzle_rows, n_own};
+  out->src[1] = st->cache ? GlxRowSource{static_cast<const float*>(st->cache->X), st->cache->stride, st->cache->swizzle_rows, n_cache}
                           : GlxRowSource{nullptr, dim, 0, 0};
   out->src[2] = GlxRowSource{U > 0 ? halo : nullptr, dim, 0, U};
   return GLX_OK;
@@ -1844,6 +1845,11 @@ extern "C" int glx_dist_store_create(glx_comm* comm, const glx_graph* graph, con
   GLX_REQUIRE(!features || features->device == comm->device,
               "the feature shard lives on device %d, the communicator on %d", features ? features->device : -1,
               comm->device);
+  // halo rows, the hot-row replica and GlxRowSource are float32: a half table is refused, not converted behind the
+  // caller's back
+  GLX_REQUIRE(!features || features->dtype == GLX_DTYPE_F32,
+              "the distributed store takes float32 feature tables only; this shard's table is %s",
+              features ? glx_dtype_name(features->dtype) : "");
   GLX_REQUIRE(comm->world <= kMaxWorld, "world size above %d", kMaxWorld);
   GlxDeviceGuard guard(comm->device);
   GLX_REQUIRE(guard.ok, "cannot select device %d", comm->device);
@@ -2695,6 +2701,8 @@ extern "C" int glx_dist_store_set_cache(glx_dist_store* st, const int64_t* hot_i
   int rc = check_store(st, ptr_kind);
   if (rc != GLX_OK) return rc;
   GLX_REQUIRE(st->feats != nullptr, "this store has no feature shard");
+  GLX_REQUIRE(st->feats->dtype == GLX_DTYPE_F32, "the hot-row replica takes float32 feature tables only; this one is %s",
+              glx_dtype_name(st->feats->dtype));
   GLX_REQUIRE(n >= 0 && n < INT32_MAX, "bad n");
   GLX_REQUIRE(n == 0 || hot_ids, "NULL data pointer");
   GlxDeviceGuard guard(st->device);
@@ -2773,8 +2781,8 @@ extern "C" int glx_dist_store_set_cache(glx_dist_store* st, const int64_t* hot_i
   GLX_HIP(hipStreamSynchronize(s));
   (void)hipFree(table.p);
   table.p = nullptr;
-  rc = glx_features_create_impl(st->device, n, dim, table_sorted.as<float>(), sorted_masked.as<int64_t>(), GLX_PTR_DEVICE, s,
-                                false, &st->cache);
+  rc = glx_features_create_impl(st->device, n, dim, table_sorted.as<float>(), GLX_DTYPE_F32, GLX_DTYPE_F32,
+                                sorted_masked.as<int64_t>(), GLX_PTR_DEVICE, s, false, &st->cache);
   if (rc != GLX_OK) return rc;
   // from here on a failure must not leave a half-installed replica behind: st->cache set while cache_slots (or the
   // bitmap) is missing would have the next resolve kernel dereference null slots

@@ -43,6 +43,7 @@ EXPORTS = [
     "glx_graph_enable_in_degree", "glx_graph_enable_default_weight", "glx_sample_full_sizes", "glx_sample_full",
     "glx_graph_set_timestamps", "glx_sample_filtered", "glx_sample_full_filtered", "glx_random_walk",
     "glx_features_create", "glx_features_view", "glx_features_destroy", "glx_features_info",
+    "glx_features_create_ex", "glx_features_view_ex", "glx_features_dtype",
     "glx_aggregate", "glx_lookup",
     "glx_partition", "glx_stitch_i64", "glx_stitch_f32", "glx_aggregate_stitch",
     "glx_negative_create", "glx_negative_from_graph", "glx_negative_destroy", "glx_negative_info",
@@ -148,6 +149,9 @@ def lib():
         L.glx_sample_full_filtered.argtypes = [vp, vp, i32, i32, vp, ci, i64, ctypes.POINTER(Filter), vp, vp, ci, vp]
         L.glx_features_view.argtypes = [ci, i64, i32, vp, ctypes.POINTER(vp)]
         L.glx_features_create.argtypes = [ci, i64, i32, vp, vp, ci, vp, ctypes.POINTER(vp)]
+        L.glx_features_create_ex.argtypes = [ci, i64, i32, vp, ci, ci, vp, ci, vp, ctypes.POINTER(vp)]
+        L.glx_features_view_ex.argtypes = [ci, i64, i32, vp, ci, ctypes.POINTER(vp)]
+        L.glx_features_dtype.argtypes = [vp, ctypes.POINTER(ci)]
         L.glx_features_destroy.argtypes = [vp]
         L.glx_features_destroy.restype = None
         L.glx_features_info.argtypes = [vp, ctypes.POINTER(i64), ctypes.POINTER(i32), ctypes.POINTER(ci),
@@ -495,27 +499,58 @@ class Graph:
         return nbr, eid
 
 
-class Features:
-    """Device-resident [V, D] float32 node features of one node type (glx_features)."""
+# storage types of a feature table (GLX_DTYPE_*)
+FEATURE_DTYPES = {"float32": 0, "bfloat16": 1, "float16": 2}
+_FEATURE_DTYPE_NAMES = {v: k for k, v in FEATURE_DTYPES.items()}
 
-    def __init__(self, X, ids=None, device=0, view=False):
-        """view=True: non-owning view of a torch CUDA matrix (dense ids); keeps X alive."""
+
+def _feature_dtype_of(X):
+    """float32 / bfloat16 / float16 for a torch tensor or a numpy array; anything else raises."""
+    name = str(X.dtype).replace("torch.", "") if _is_torch(X) else str(np.dtype(X.dtype))
+    if name not in FEATURE_DTYPES:
+        raise ValueError("a feature matrix holds float32, bfloat16 or float16, not {}".format(X.dtype))
+    return name
+
+
+class Features:
+    """Device-resident [V, D] node features of one node type (glx_features), stored as float32 (the default),
+    bfloat16 or float16.  aggregate() and lookup() answer in float32 whatever the storage type."""
+
+    def __init__(self, X, ids=None, device=0, view=False, dtype=None):
+        """X: float32 / bfloat16 / float16 -- numpy (float32, float16) or torch (host or CUDA).  dtype=None stores
+        X's own type; "bfloat16" / "float16" rounds float32 input on the device (round to nearest even).
+        view=True: non-owning view of a torch CUDA matrix (dense ids, its own dtype); keeps X alive."""
+        if dtype is not None and dtype not in FEATURE_DTYPES:
+            raise ValueError("dtype must be None or one of {}, not {!r}".format(sorted(FEATURE_DTYPES), dtype))
+        x_dtype = _feature_dtype_of(X)
+        store = dtype or x_dtype
+        if store != x_dtype and x_dtype != "float32":
+            raise ValueError("only float32 input converts; a {} matrix cannot be stored as {}".format(x_dtype, store))
+        self.dtype = store
         if view:
             assert ids is None and _is_torch(X)
+            if store != x_dtype:
+                raise ValueError("a view reads the caller's {} rows as they are; it cannot store {}".format(x_dtype, store))
             self.num_rows, self.dim = int(X.shape[0]), int(X.shape[1])
             self.device = device
             self._keep = X
             h = ctypes.c_void_p()
-            _check(lib().glx_features_view(device, self.num_rows, self.dim, _ptr(X)[0], ctypes.byref(h)))
+            _check(lib().glx_features_view_ex(device, self.num_rows, self.dim, _ptr(X)[0], FEATURE_DTYPES[store],
+                                              ctypes.byref(h)))
             self._h = h
             return
+        if _is_torch(X) and not X.is_cuda:  # a host tensor: its bits as a numpy array (numpy has no bfloat16)
+            import torch
+            X = X.contiguous()
+            X = X.numpy() if x_dtype == "float32" else X.view(torch.int16).numpy()
         ptrs = [_ptr(X), _ptr(ids)]
         kind = _kind(*ptrs)
         self.num_rows, self.dim = int(X.shape[0]), int(X.shape[1])
         self.device = device
         h = ctypes.c_void_p()
-        _check(lib().glx_features_create(device, self.num_rows, self.dim, ptrs[0][0], ptrs[1][0], kind,
-                                         _stream(kind, self.device), ctypes.byref(h)))
+        _check(lib().glx_features_create_ex(device, self.num_rows, self.dim, ptrs[0][0], FEATURE_DTYPES[x_dtype],
+                                            FEATURE_DTYPES[store], ptrs[1][0], kind, _stream(kind, self.device),
+                                            ctypes.byref(h)))
         self._h = h
 
     @classmethod
@@ -528,6 +563,9 @@ class Features:
         _check(lib().glx_features_info(self._h, ctypes.byref(v), ctypes.byref(d), None, ctypes.byref(dv)))
         self.num_rows, self.dim = v.value, d.value
         self.device = dv.value  # the device the handle lives on, whatever the caller passed
+        dt = ctypes.c_int()
+        _check(lib().glx_features_dtype(self._h, ctypes.byref(dt)))
+        self.dtype = _FEATURE_DTYPE_NAMES[dt.value]
         return self
 
     def close(self):

@@ -39,6 +39,9 @@ extern int32_t gTrackerMode;       // :95 (1 = file system)
 // glx seeding contract, and the GPU this process' GraphStore lives on.
 extern int64_t gSamplingSeed;
 extern int32_t gDeviceId;
+// New: the storage type of the node feature tables Noder::Build uploads (GLX_DTYPE_*: 0 float32, 1 bfloat16,
+// 2 float16).  Aggregation and lookup still accumulate and answer in float32.
+extern int32_t gFeatureDtype;
 
 void SetGlobalFlagPaddingMode(int32_t v);
 void SetGlobalFlagDefaultNeighborId(int64_t v);
@@ -66,6 +69,7 @@ void SetGlobalFlagUnused(const char* name, int64_t v);
 void SetGlobalFlagUnused(const char* name, const std::string& v);
 void SetGlobalFlagSamplingSeed(int64_t v);
 void SetGlobalFlagDeviceId(int32_t v);
+void SetGlobalFlagFeatureDtype(int32_t v);
 
 enum PaddingMode { kReplicate = 0, kCircular = 1 };  // include/constants.h:119-122
 enum DeployMode { kLocal = 0, kServer = 1, kWorker = 2 };  // :109-113

@@ -54,6 +54,7 @@ int32_t gDatasetCapacity = 10;
 int32_t gTrackerMode = 1;
 int64_t gSamplingSeed = 0;
 int32_t gDeviceId = 0;
+int32_t gFeatureDtype = 0;
 
 void SetGlobalFlagPaddingMode(int32_t v) { gPaddingMode = v; }
 void SetGlobalFlagDefaultNeighborId(int64_t v) { gDefaultNeighborId = v; }
@@ -90,6 +91,7 @@ void SetGlobalFlagUnused(const char* name, const std::string& v) {
 }
 void SetGlobalFlagSamplingSeed(int64_t v) { gSamplingSeed = v; }
 void SetGlobalFlagDeviceId(int32_t v) { gDeviceId = v; }
+void SetGlobalFlagFeatureDtype(int32_t v) { gFeatureDtype = v; }
 
 // -------------------------------------------------------------- constants --
 // Key strings: the reference's values (service/constants.cc:20-72), see constants.h.

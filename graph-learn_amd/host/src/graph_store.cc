@@ -312,8 +312,9 @@ Status Noder::Build(const IndexOption&) {
   std::lock_guard<std::mutex> g(mtx_);
   if (dev_) return Status::OK();
   if (info_.f_num <= 0) return Status::OK();  // nothing for the aggregators to read
-  int rc = glx_features_create(GLOBAL_FLAG(DeviceId), (int64_t)ids_.size(), info_.f_num, feats_.data(),
-                               ids_.data(), GLX_PTR_HOST, nullptr, &dev_);
+  // the float32 attributes are rounded to GLOBAL_FLAG(FeatureDtype) on the device, while the rows are placed
+  int rc = glx_features_create_ex(GLOBAL_FLAG(DeviceId), (int64_t)ids_.size(), info_.f_num, feats_.data(), GLX_DTYPE_F32,
+                                  GLOBAL_FLAG(FeatureDtype), ids_.data(), GLX_PTR_HOST, nullptr, &dev_);
   return error::FromGlx(rc);
 }
 

@@ -161,6 +161,11 @@ class Graph(object):
     if replicate_features:
       raise NotImplementedError("replicate_features is not offered by sharded_store(); hot_nodes=K replicates the "
                                 "K hottest rows (K = the node count replicates everything that has in-edges)")
+    feats = self.device_features(node_type) if node_type is not None else None
+    if feats is not None and feats.dtype != "float32":
+      # glx_dist_store_create would refuse it too (GLX_INVALID_ARGUMENT): say so before any collective starts
+      raise ValueError("the distributed store takes float32 feature tables only; node type {} is stored as {} "
+                       "(settings.set_feature_dtype)".format(node_type, feats.dtype))
     if not torch_dist.is_initialized():
       raise RuntimeError("sharded_store needs torch.distributed.init_process_group (backend 'nccl' = RCCL)")
     world = torch_dist.get_world_size(group)
@@ -168,7 +173,6 @@ class Graph(object):
     if (torch_dist.get_rank(group), world) != shard:
       raise ValueError("the process group says rank {} of {}, the graph was initialised as shard {} of {}".format(
           torch_dist.get_rank(group), world, shard[0], shard[1]))
-    feats = self.device_features(node_type) if node_type is not None else None
     store = glx_dist.ShardedStore(glx_dist.DeviceOps(), self.device_graph(edge_type), feats, group)
     if hot_nodes:
       hot = store.native.hot_ids(int(hot_nodes))

@@ -1,7 +1,7 @@
 """Process-wide engine flags (graphlearn/python/config.py; GLOBAL_FLAG in
 graphlearn/src/include/config.h).  The thread-pool / RPC knobs of the reference's
 service layer are accepted and ignored: there is no service layer between Python and
-the GPU here.  `set_sampling_seed` and `set_device_id` are new."""
+the GPU here.  `set_sampling_seed`, `set_device_id` and `set_feature_dtype` are new."""
 from graphlearn import pywrap_graphlearn as pywrap
 
 __all__ = [
@@ -11,13 +11,16 @@ __all__ = [
     "set_default_full_nbr_num",
     "set_inter_threadnum", "set_intra_threadnum", "set_inner_threadnum", "set_datainit_batchsize",
     "set_inmemory_queuesize", "set_shuffle_buffer_size", "set_tracker_mode", "set_storage_mode",
-    "set_retry_times", "set_timeout", "set_sampling_seed", "set_device_id",
+    "set_retry_times", "set_timeout", "set_sampling_seed", "set_device_id", "set_feature_dtype",
 ]
 
 
 # flags the device-tensor path (NeighborSampler.get_device) passes to the C-ABI itself
 _MIRROR = {"padding_mode": 1, "default_neighbor_id": 0, "sampling_seed": 0, "default_float_attr": 0.0, "device_id": 0,
-           "default_full_nbr_num": 100, "default_weight": 0.0}
+           "default_full_nbr_num": 100, "default_weight": 0.0, "feature_dtype": "float32"}
+
+# storage types of the node feature tables (include/glx.h GLX_DTYPE_*)
+_FEATURE_DTYPES = {"float32": 0, "bfloat16": 1, "float16": 2}
 
 
 def set_default_neighbor_id(nbr_id):
@@ -88,6 +91,17 @@ def set_device_id(device):
   """GPU that holds this process' graph store (one process per GPU)."""
   pywrap.set_device_id(int(device))
   _MIRROR["device_id"] = int(device)
+
+
+def set_feature_dtype(dtype):
+  """Storage type of the node float attributes in HBM: "float32" (the default), "bfloat16" or "float16".  Half
+  tables hold half the bytes; aggregation and lookup still accumulate and answer in float32 (each result equals the
+  float32 one over the attributes rounded to `dtype`).  Takes effect for the node types Graph.init() builds after it;
+  the distributed store (sharded_store) takes float32 tables only."""
+  if dtype not in _FEATURE_DTYPES:
+    raise ValueError("feature dtype must be one of {}, not {!r}".format(sorted(_FEATURE_DTYPES), dtype))
+  pywrap.set_feature_dtype(_FEATURE_DTYPES[dtype])
+  _MIRROR["feature_dtype"] = dtype
 
 
 def _ignored(name):

@@ -6,7 +6,8 @@
 // Graph.init(), the samplers, GSL queries (the DAG API + Dataset, see host dag.h).  What the
 // engine does not have -- RPC clients / servers, KNN, vineyard, the actor engine -- exists by
 // name and fails when CALLED (flag setters of those layers just store their value).
-// New: set_sampling_seed / set_device_id (the glx seeding contract and GPU placement).
+// New: set_sampling_seed / set_device_id / set_feature_dtype (the glx seeding contract, GPU placement and the
+// storage type of the node feature tables).
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
@@ -99,6 +100,7 @@ PYBIND11_MODULE(pywrap_graphlearn, m) {
   m.def("set_shuffle_buffer_size", &SetGlobalFlagShuffleBufferSize);
   m.def("set_sampling_seed", &SetGlobalFlagSamplingSeed);
   m.def("set_device_id", &SetGlobalFlagDeviceId);
+  m.def("set_feature_dtype", &SetGlobalFlagFeatureDtype);
   m.def("set_deploy_mode", [](int32_t mode) { SetGlobalFlagDeployMode(mode); });
   m.def("set_deploy_mode", [](DeployMode mode) { SetGlobalFlagDeployMode((int32_t)mode); });
   m.def("set_client_id", &SetGlobalFlagClientId);

@@ -35,7 +35,8 @@ extern "C" {
  * induced sub-graph, conditional negative sampling.  4 (additions only): the speculation ledger of the distributed store
  * (glx_dist_ledger_*, glx_dist_confirm, GLX_ABORTED), glx_tune.  5 (additions only): glx_dist_sample_full_filtered,
  * glx_dist_in_degrees, glx_dist_negative_create, glx_dist_negative_sample, glx_dist_random_walk_ex (all added during
- * round 4 under 4), glx_graph_enable_default_weight. */
+ * round 4 under 4), glx_graph_enable_default_weight.  Added under 5 (additions only): half-precision
+ * feature tables -- GLX_DTYPE_*, glx_features_create_ex, glx_features_view_ex, glx_features_dtype. */
 #define GLX_ABI_VERSION 5
 
 /* Exported symbols: libglx.so is built with -fvisibility=hidden. */
@@ -327,6 +328,24 @@ GLX_API int glx_features_view(int device, int64_t num_rows, int32_t dim, const f
 GLX_API void glx_features_destroy(glx_features* f);
 GLX_API int glx_features_info(const glx_features* f, int64_t* num_rows, int32_t* dim, int* has_id_map,
                       int* device);
+/* Storage types of a feature table.  Aggregation and lookup read the stored elements, upcast them to float32
+ * (exact) and accumulate and write float32 in the same order as for a float32 table: a half table's results equal
+ * those of the float32 table holding the upcast values, bit for bit. */
+#define GLX_DTYPE_F32 0
+#define GLX_DTYPE_BF16 1
+#define GLX_DTYPE_F16 2
+/* glx_features_create with a storage type.  X holds [num_rows, dim] elements of x_dtype.  x_dtype == store_dtype
+ * copies them as they are; x_dtype == GLX_DTYPE_F32 with a half store_dtype converts on the device while the rows
+ * are placed: round to nearest even, overflow to +-inf, bit-identical to torch.Tensor.to() of a contiguous CPU
+ * tensor for every input, NaN included (bfloat16: 0xFFFF for every NaN; float16: sign | 0x7E00 | payload >> 13).
+ * Every other pair is GLX_INVALID_ARGUMENT.
+ * glx_features_create(...) is glx_features_create_ex(..., GLX_DTYPE_F32, GLX_DTYPE_F32, ...). */
+GLX_API int glx_features_create_ex(int device, int64_t num_rows, int32_t dim, const void* X, int x_dtype,
+                                   int store_dtype, const int64_t* ids, int ptr_kind, void* stream, glx_features** out);
+/* glx_features_view of a device-resident [num_rows, dim] matrix of `dtype` elements. */
+GLX_API int glx_features_view_ex(int device, int64_t num_rows, int32_t dim, const void* X_device, int dtype,
+                                 glx_features** out);
+GLX_API int glx_features_dtype(const glx_features* f, int* dtype);
 
 /* ---- aggregation: replaces Aggregator::Aggregate (aggregator.cc:25-59) with
  * Sum/Mean/Max/Min/Prod Init/Agg/Final (sum_aggregator.cc:25-33,
