@@ -568,10 +568,44 @@ __global__ __launch_bounds__(256) void glx_aggregate_grp_kernel(AggArgs a) {
 //   * wave w owns the columns [w D/4, (w+1) D/4) as NB = D/64 blocks of 16 and issues, per 4 rows,
 //     v_mfma_f32_16x16x4_f32 with A[m][k] = (row k belongs to segment m) and B[k][n] = the staged row;
 //   * f32 MFMA is an exact fmaf chain over k in order and the indicator is 0 or 1, so every output element
-//     is still accumulated in the reference's left-to-right order (sum_aggregator.cc:25-33): bit-identical.
+//     is still accumulated in the reference's left-to-right order (sum_aggregator.cc:25-33) -- as long as every
+//     staged element is finite: the other 15 segments' rows enter each column as 0 x row, and 0 x inf and 0 x NaN
+//     are NaN, so one non-finite element would turn its column into NaN for all 16 segments of the workgroup (the
+//     reference leaves them finite).  Staging therefore flags any element whose exponent field is all ones (an
+//     integer test on the bits), and a workgroup that staged one recomputes its <= 16 segments with the serial VALU
+//     fold straight from global memory (agg_mfma_serial) before the stores: bit-identical on any input.
 // 15/16 of the multiply-adds multiply by zero, f32 MFMA runs at the vector rate (157 TF), and the reduce is
 // 0.25 flop/byte: the matrix core cannot make it faster than the HBM stream -- the ablation measures what the
 // LDS round trip and the workgroup barriers cost instead.
+__device__ __forceinline__ bool agg_nonfinite4(float __attribute__((ext_vector_type(4))) v) {
+  // exponent field all ones (inf / NaN): (bits & 0x7f800000) == 0x7f800000 for any of the four
+  const uint32_t e = 0x7f800000u;
+  return ((__float_as_uint(v[0]) & e) == e) || ((__float_as_uint(v[1]) & e) == e) || ((__float_as_uint(v[2]) & e) == e) ||
+         ((__float_as_uint(v[3]) & e) == e);
+}
+
+// The reference's serial fold of one output element of a dense sampler response (segment sg, column col): what the
+// grouped VALU kernel computes, for the workgroups of the MFMA ablation that staged a non-finite element.  The fields
+// of AggArgs it reads come by value (a reference to the kernel argument would have it copied to scratch).
+__device__ __noinline__ float agg_mfma_serial(const float* X, const int64_t* node_ids, const int32_t* rows,
+                                              int64_t num_rows, int64_t stride, int64_t swizzle_rows,
+                                              float default_attr, int64_t sg, int32_t col, int32_t f) {
+  float acc = 0.0f;  // InitFunc (aggregator.cc:61-65)
+  for (int32_t r = 0; r < f; ++r) {
+    const int64_t pos = sg * f + r;
+    int64_t row;
+    if (rows) {
+      row = rows[pos];
+    } else {
+      const int64_t id = node_ids[pos];
+      row = (id >= 0 && id < num_rows) ? id : -1;
+    }
+    const float x = row >= 0 ? X[glx_swizzle_row(row, swizzle_rows) * stride + col] : default_attr;
+    acc = acc + x;
+  }
+  return acc;
+}
+
 template <int OP, int NB>
 __global__ __launch_bounds__(256) void glx_aggregate_mfma_kernel(AggArgs a) {
   typedef float f4 __attribute__((ext_vector_type(4)));
@@ -593,6 +627,7 @@ __global__ __launch_bounds__(256) void glx_aggregate_mfma_kernel(AggArgs a) {
   for (int b = 0; b < NB; ++b) acc[b] = f4{0.f, 0.f, 0.f, 0.f};
   constexpr int32_t row_f4 = D / 4;
   constexpr int32_t PT = KC * row_f4 / 256;  // 16-byte pieces per thread per round (2 NB)
+  bool nonfinite = false;  // this thread staged an inf / NaN (the default row's included)
   for (int32_t base = 0; base < nrows; base += KC) {
     // stage rows [base, base + KC): thread t moves pieces t, t + 256, ...; all loads issued before the first store
     f4 v[PT];
@@ -614,6 +649,7 @@ __global__ __launch_bounds__(256) void glx_aggregate_mfma_kernel(AggArgs a) {
       const int32_t r = p / row_f4;
       const int32_t c4 = p - r * row_f4;
       *reinterpret_cast<f4*>(tile + r * pitch + c4 * 4) = v[i];
+      nonfinite |= agg_nonfinite4(v[i]);
     }
     __syncthreads();
 #pragma unroll 2
@@ -628,6 +664,8 @@ __global__ __launch_bounds__(256) void glx_aggregate_mfma_kernel(AggArgs a) {
     }
     __syncthreads();
   }
+  // one flag per workgroup: every thread of it then either keeps the MFMA sums or refolds its own outputs serially
+  const bool refold = __syncthreads_or(nonfinite) != 0;
   // C/D: col = lane & 15, row = (lane >> 4) * 4 + reg
 #pragma unroll
   for (int reg = 0; reg < 4; ++reg) {
@@ -637,6 +675,10 @@ __global__ __launch_bounds__(256) void glx_aggregate_mfma_kernel(AggArgs a) {
 #pragma unroll
       for (int b = 0; b < NB; ++b) {
         float v = acc[b][reg];
+        if (refold) {
+          v = agg_mfma_serial(static_cast<const float*>(a.X), a.node_ids, a.rows, a.num_rows, a.stride, a.swizzle_rows,
+                              a.default_attr, seg0 + srow, wave * (D / 4) + m + b * 16, f);
+        }
         if (f == 0) v = a.default_attr;
         else if (OP == GLX_AGG_MEAN) v = v / (float)f;
         out[b * 16] = v;

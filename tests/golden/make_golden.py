@@ -324,6 +324,35 @@ def gen_agg_stitch(ref):
     np.savez_compressed(os.path.join(OUT_DIR, "agg_stitch.npz"), **out)
 
 
+def gen_agg_special(ref):
+    """The reference's Aggregator::Aggregate on the special-value tables of tests/agg_special_values.py: NaNs of both
+    signs and several payloads, infinities, signed zeros, subnormals, overflowing sums and products, values around
+    Max's -37 start; default_attr a NaN, -inf, -0.0 or a subnormal (unknown ids and empty segments)."""
+    import agg_special_values as sv
+    out = {}
+    case = 0
+    for D, defaults in ((1, sv.DEFAULTS), (3, sv.DEFAULTS[0::2]), (8, sv.DEFAULTS[1:2]), (17, sv.DEFAULTS[3:])):
+        for dflt in defaults:
+            X, nid, seg, Sg, d = sv.build_case(D, 500 + case, dflt, blocks=1, random_segments=24)
+            raw = np.arange(X.shape[0], dtype=np.int64)
+            ntype = "sp%d" % case
+            ref.set_flags(1, 0, float(d))
+            ref.add_nodes(ntype, raw, X)
+            out["c%d_X" % case] = X
+            out["c%d_ids" % case] = nid
+            out["c%d_seg" % case] = seg
+            out["c%d_default" % case] = d
+            out["c%d_num_segments" % case] = np.array(Sg)
+            for name in AGGREGATORS:
+                emb, cnt = ref.aggregate(ntype, name, nid, seg, Sg, D)
+                out["c%d_%s_emb" % (case, name)] = emb
+                out["c%d_%s_cnt" % (case, name)] = cnt
+            case += 1
+    ref.set_flags(1, 0, 0.0)
+    out["num_cases"] = np.array(case)
+    np.savez_compressed(os.path.join(OUT_DIR, "agg_special.npz"), **out)
+
+
 def gen_loader(ref):
     """Loader primitives of the reference: Hash64
     (common/base/hash.cc) on byte strings of every tail length, and ParseAttribute
@@ -741,6 +770,7 @@ def generate():
     gen_subgraph(ref)
     gen_cond_negative(ref)
     gen_refseq(ref)
+    gen_agg_special(ref)
     ref.close()
     gen_refpy_names()
 
