@@ -14,7 +14,13 @@ graph") is quoted on: RMAT (0.57,0.19,0.19,0.05) 10M nodes / 100M edges,
 EdgeWeightSampler (alias) fanout [25,10], MaxAggregator, dim=256.
 
   python bench.py --gpus 1 --steps 20 --warmup 3
+  python bench.py --gpus 1 --steps 20 --warmup 3 --full
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain N = 1 run does what its headline needs: build the store, warm up, time the steps (the three request-shape legs:
+the headline quotes the slowest of them), write --dump-outputs, print the line.  --full adds the side measurements of
+the N = 1 line: the oracle check of the last timed step, the roofline probes, the CPU baseline, the host boundary, small
+batches, the N > 1 code path with one rank, the other configs and eight ranks on one GPU.
 
 N > 1: one process per GPU; the graph is edge-cut partitioned (llabs(v) % N), every
 rank drives its own batch of B0 seeds (weak scaling) and each hop's requests are
@@ -970,9 +976,10 @@ def other_configs(args):
     out = {}
     for name in [x for x in args.other_configs.split(",") if x.strip()]:
         wl_name, _, variant = name.partition("-")
+        # --full: each config keeps its oracle check and roofline probes; its own CPU baseline etc. stay off
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--workload", wl_name,
                "--seed-dist", "degree" if variant == "degree-seeds" else "uniform", "--steps", str(args.steps),
-               "--warmup", str(args.warmup), "--cpu-baseline", "off", "--host-boundary", "off", "--edge-cut-probe", "off",
+               "--warmup", str(args.warmup), "--full", "--cpu-baseline", "off", "--host-boundary", "off", "--edge-cut-probe", "off",
                "--small-batches", "off", "--other-configs", ""]
         t0 = time.time()
         r = None
@@ -990,7 +997,11 @@ def other_configs(args):
     return out
 
 
-def main():
+FULL_OTHER_CONFIGS = "c2,c5,c4,c3-degree-seeds"  # --other-configs under --full
+SIDE_MEASUREMENTS = ("cpu_baseline", "host_boundary", "small_batches", "edge_cut_probe", "roofline_probes", "verify_oracle")
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -1033,17 +1044,21 @@ def main():
                          "round 6 (5 GB of rows + 6 GB of adjacency per GPU on the headline graph, 4 %% of the HBM): one "
                          "rank's step at P = 8 costs 3.12 / 2.72 / 2.50 / 2.51 ms of kernels at 0.10 / 0.25 / 0.50 / 1.0 "
                          "and moves 8x fewer halo rows at 0.5 than at 0.25 (profiles/r06/p8_sym_hot_sweep.txt)")
-    ap.add_argument("--host-boundary", default="on", choices=["on", "off"],
+    ap.add_argument("--full", action="store_true",
+                    help="N=1: also run every side measurement of the line (the options below marked 'default: --full'); "
+                         "a plain run builds, warms up, times the steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--host-boundary", default=None, choices=["on", "off"],
                     help="N=1: also run graph-learn_amd/lib/host_path_bench (requests through the C++ operator API "
-                         "with host buffers) and report its PCIe-inclusive rate under \"host_boundary\"")
+                         "with host buffers) and report its PCIe-inclusive rate under \"host_boundary\" (default: --full)")
     ap.add_argument("--host-boundary-threads", type=int, default=32)
-    ap.add_argument("--small-batches", default="on", choices=["on", "off"],
-                    help="N=1 at the default batch: also time B0 = 1024 and 8192 on the same store (\"small_batches\")")
-    ap.add_argument("--edge-cut-probe", default="on", choices=["on", "off"],
+    ap.add_argument("--small-batches", default=None, choices=["on", "off"],
+                    help="N=1 at the default batch: also time B0 = 1024 and 8192 on the same store (\"small_batches\") "
+                         "(default: --full)")
+    ap.add_argument("--edge-cut-probe", default=None, choices=["on", "off"],
                     help="N=1, C3: after the headline, time the same steps once more through the multi-GPU machinery with "
                          "ONE rank over RCCL (partition, exchanges, resolve, halo slots, 3-source reduce: the generic "
                          "path, GLX_DIST_NO_SHORTCUT=1), verified against the plain operators, and report it under "
-                         "\"edge_cut_world1\" -- what the edge-cut path costs before any link time")
+                         "\"edge_cut_world1\" -- what the edge-cut path costs before any link time (default: --full)")
     ap.add_argument("--graph", default="auto", choices=["auto", "on", "off"],
                     help="N=1: replay the step as one captured hipGraph (glx_plan) instead of 4 kernel launches; "
                          "auto = on for launch-bound batches (B0 <= 8192)")
@@ -1079,18 +1094,20 @@ def main():
                     help="N>1: how the replicated rows are chosen: by access count over a few profiling requests, or by "
                          "global in-degree (glx_dist_hot_ids: needs no request profile)")
     ap.add_argument("--hot-profile-steps", type=int, default=4)
-    ap.add_argument("--roofline-probes", default="on", choices=["on", "off"],
-                    help="N=1: also time the aggregation kernel on cache-free (uniform) rows and a device copy")
-    ap.add_argument("--verify-oracle", default="on", choices=["on", "off"],
+    ap.add_argument("--roofline-probes", default=None, choices=["on", "off"],
+                    help="N=1: also time the aggregation kernel on cache-free (uniform) rows and a device copy "
+                         "(default: --full)")
+    ap.add_argument("--verify-oracle", default=None, choices=["on", "off"],
                     help="N=1: after timing, re-check the last timed step's outputs on row subsets against the oracle "
-                         "(tests/headline_check.py) and emit \"verified_vs_oracle\"")
+                         "(tests/headline_check.py) and emit \"verified_vs_oracle\" (default: --full)")
     ap.add_argument("--seed-dist", default="uniform", choices=["uniform", "degree"],
                     help="seed vertices of a batch: uniform over the vertices that have out-edges, or degree-biased (the source "
                          "of a uniformly drawn edge: hubs are asked for in proportion to their out-degree) -- SURVEY 8(d)'s two "
                          "request mixes")
-    ap.add_argument("--other-configs", default="c2,c5,c4,c3-degree-seeds",
+    ap.add_argument("--other-configs", default=None,
                     help="N=1, headline workload at the default batch: also time these workloads (comma separated), each in a "
-                         "process of its own, and report them under \"other_configs\"")
+                         "process of its own, and report them under \"other_configs\" (default: %s with --full, else "
+                         "none)" % FULL_OTHER_CONFIGS)
     ap.add_argument("--request-shape-legs", default="on", choices=["on", "off"],
                     help="N=1: time the same steps twice more -- with an explicit segment_ids tensor per aggregation (the "
                          "reference's AggregatingRequest always carries one) and with seeds uniform over ALL vertices "
@@ -1098,7 +1115,8 @@ def main():
     ap.add_argument("--force-sharded", action="store_true",
                     help="use the sharded (RCCL) code path even with one process (testing)")
     ap.add_argument("--c5-scale", type=int, default=1, help="divide the c5 node / edge counts (test rig)")
-    ap.add_argument("--cpu-baseline", default="on", choices=["on", "off"])
+    ap.add_argument("--cpu-baseline", default=None, choices=["on", "off"], help="N=1: time the reference's CPU path beside "
+                    "the GPU (\"cpu_baseline\", \"gpu_over_cpu\") (default: --full)")
     ap.add_argument("--cpu-time-budget", type=float, default=3.0,
                     help="s of sampling and s of aggregation timed per (storage mode, thread count) leg of the CPU baseline")
     ap.add_argument("--cpu-seeds-per-request", type=int, default=128)
@@ -1111,9 +1129,20 @@ def main():
     ap.add_argument("--cpu-wall-limit", type=float, default=420.0, help="s a CPU baseline worker may take before it is abandoned")
     ap.add_argument("--cpu-worker", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--cpu-worker-dir", default=None, help=argparse.SUPPRESS)
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.backend == "auto":
         args.backend = "gloo" if args.share_device else "nccl"
+    # the side measurements run with --full unless named on the command line
+    for k in SIDE_MEASUREMENTS:
+        if getattr(args, k) is None:
+            setattr(args, k, "on" if args.full else "off")
+    if args.other_configs is None:
+        args.other_configs = FULL_OTHER_CONFIGS if args.full else ""
+    return args
+
+
+def main():
+    args = parse_args()
     if args.cpu_worker:
         cpu_worker(args)
         return

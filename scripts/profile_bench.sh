@@ -7,7 +7,7 @@ OUT=$R/gpurun_out/prof_$TAG
 RAW=/tmp/prof_raw
 rm -rf $RAW; mkdir -p $OUT $RAW
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $R/bench.py --cpu-baseline off"
+BENCH="python $R/bench.py --full --cpu-baseline off"
 rocprofv3 --kernel-trace --stats --output-format csv -d $RAW/trace -o trace -- $BENCH --steps 20 --warmup 5 --roofline-probes off > $OUT/bench_trace.json 2> $OUT/bench_trace.err
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $RAW/fetch -o fetch -- $BENCH --steps 5 --warmup 1 > $OUT/bench_fetch.json 2> $OUT/bench_fetch.err
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $RAW/write -o write -- $BENCH --steps 5 --warmup 1 > $OUT/bench_write.json 2> $OUT/bench_write.err

@@ -7,7 +7,7 @@ OUT=$R/gpurun_out/r04_prof
 RAW=/tmp/prof_raw_ea
 rm -rf $RAW; mkdir -p $OUT $RAW
 cd /tmp && export TMPDIR=/tmp
-LEAN="--cpu-baseline off --host-boundary off --edge-cut-probe off --small-batches off --other-configs= --verify-oracle off"
+LEAN="--full --cpu-baseline off --host-boundary off --edge-cut-probe off --small-batches off --other-configs= --verify-oracle off"
 B="python $R/bench.py --workload c3 $LEAN --steps 5 --warmup 1 --detail-out $OUT/ea_detail.json"
 i=0
 for pass in "TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_128B_sum" "TCC_EA0_RDREQ_DRAM_32B_sum TCC_EA0_RDREQ_GMI_32B_sum TCC_EA0_RDREQ_IO_32B_sum TCC_EA0_WRREQ_64B_sum"; do

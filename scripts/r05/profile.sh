@@ -11,7 +11,7 @@ RAW=/tmp/prof_raw
 rm -rf $RAW; mkdir -p $OUT $RAW
 WLS=${@:-c3}
 cd /tmp && export TMPDIR=/tmp
-LEAN="--cpu-baseline off --host-boundary off --edge-cut-probe off --small-batches off --other-configs= --verify-oracle off --request-shape-legs off"
+LEAN="--full --cpu-baseline off --host-boundary off --edge-cut-probe off --small-batches off --other-configs= --verify-oracle off --request-shape-legs off"
 keep() {  # keep <raw dir> <out prefix>: the glx rows of every trace / counter CSV
   for f in $(find $1 -name '*kernel_trace.csv' -o -name '*counter_collection.csv' -o -name '*kernel_stats.csv'); do
     b=$(basename $f)
@@ -39,7 +39,7 @@ done
 # the headline command as the driver runs it (three request-shape legs in the timed region), kernel trace only: shows the
 # segment bookkeeping kernels of the explicit-segment_ids leg beside the reduce
 if echo "$WLS" | grep -q c3; then
-  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $RAW/c3_shapes -o t -- python $R/bench.py --workload c3 --cpu-baseline off --host-boundary off --edge-cut-probe off --small-batches off --other-configs= --roofline-probes off --steps 20 --warmup 3 --detail-out $OUT/c3_shapes_detail.json > $OUT/c3_shapes_bench_trace.json 2> $OUT/c3_shapes_trace.err
+  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $RAW/c3_shapes -o t -- python $R/bench.py --workload c3 --full --cpu-baseline off --host-boundary off --edge-cut-probe off --small-batches off --other-configs= --roofline-probes off --steps 20 --warmup 3 --detail-out $OUT/c3_shapes_detail.json > $OUT/c3_shapes_bench_trace.json 2> $OUT/c3_shapes_trace.err
   keep $RAW/c3_shapes $OUT/c3_shapes_trace
   rm -rf $RAW/c3_shapes
 fi

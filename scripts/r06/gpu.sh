@@ -58,7 +58,7 @@ case "$what" in
     # 128-byte lines the hop-2 sampler launch asks L2 for, per draw (would staging a row in LDS cut lines?)
     cd /tmp && export TMPDIR=/tmp
     timeout 600 rocprofv3 --pmc TCP_TCC_READ_REQ_sum TCP_TOTAL_CACHE_ACCESSES_sum --kernel-include-regex "glx_sample_slots|glx_probe_gather32" --kernel-trace --output-format csv -d /tmp/smpl -o p -- \
-      python $R/bench.py --workload c3 --cpu-baseline off --host-boundary off --edge-cut-probe off --small-batches off --other-configs= --verify-oracle off --request-shape-legs off --steps 5 --warmup 1 > $O/smp_lines_bench.json 2> $O/smp_lines.err
+      python $R/bench.py --workload c3 --full --cpu-baseline off --host-boundary off --edge-cut-probe off --small-batches off --other-configs= --verify-oracle off --request-shape-legs off --steps 5 --warmup 1 > $O/smp_lines_bench.json 2> $O/smp_lines.err
     f=$(find /tmp/smpl -name '*counter_collection.csv' | head -1); (head -1 $f; grep -E "glx_sample_slots|glx_probe_gather32" $f) > $O/smp_lines_pmc.csv
     rm -rf /tmp/smpl; wc -l $O/smp_lines_pmc.csv; cd $R ;;
   p8)

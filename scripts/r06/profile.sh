@@ -11,7 +11,7 @@ RAW=/tmp/prof_raw
 rm -rf $RAW; mkdir -p $OUT $RAW
 WLS=${@:-c3}
 cd /tmp && export TMPDIR=/tmp
-LEAN="--cpu-baseline off --host-boundary off --edge-cut-probe off --small-batches off --other-configs= --verify-oracle off --request-shape-legs off"
+LEAN="--full --cpu-baseline off --host-boundary off --edge-cut-probe off --small-batches off --other-configs= --verify-oracle off --request-shape-legs off"
 keep() {  # keep <raw dir> <out prefix>: the glx rows of every trace / counter CSV
   for f in $(find $1 -name '*kernel_trace.csv' -o -name '*counter_collection.csv' -o -name '*kernel_stats.csv'); do
     b=$(basename $f)

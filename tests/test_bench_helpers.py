@@ -192,6 +192,20 @@ def test_side_measurements_are_n1_only():
     assert not off["cpu_baseline"] and not off["other_configs"]
 
 
+def test_plain_run_times_the_headline_alone_and_full_runs_every_side_measurement():
+    """A plain `bench.py --gpus 1` run does what its headline needs: the request-shape legs (the headline quotes the slowest
+    of them) and nothing else; --full turns every side measurement on, and an option named on the command line wins."""
+    plain = bench.n1_extras(bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "3"]), world=1, sharded=False)
+    assert plain.pop("request_shape_legs") and not any(plain.values()), plain
+    full_args = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "3", "--full"])
+    assert all(bench.n1_extras(full_args, world=1, sharded=False).values())
+    assert full_args.other_configs == "c2,c5,c4,c3-degree-seeds"
+    one = bench.n1_extras(bench.parse_args(["--roofline-probes", "on"]), world=1, sharded=False)
+    assert one["roofline_probes"] and not one["cpu_baseline"] and not one["other_configs"]
+    less = bench.n1_extras(bench.parse_args(["--full", "--cpu-baseline", "off", "--other-configs", ""]), world=1, sharded=False)
+    assert not less["cpu_baseline"] and not less["other_configs"] and less["verify_oracle"]
+
+
 def test_compact_line_keeps_whole_clauses_and_the_request_shape_legs():
     res = {"metric": "m", "value": 1.0, "unit": "edges/s", "n_gpus": 1, "steps": 2, "warmup": 1, "ms_per_step": 2.3,
            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
