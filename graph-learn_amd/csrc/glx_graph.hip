@@ -949,6 +949,12 @@ extern "C" int glx_graph_info(const glx_graph* g, int64_t* num_rows, int64_t* nu
   return GLX_OK;
 }
 
+extern "C" int glx_graph_edge_weight_packed(const glx_graph* g, int* packed) {
+  GLX_REQUIRE(g != nullptr && packed != nullptr, "NULL argument");
+  *packed = g->ew != nullptr;
+  return GLX_OK;
+}
+
 extern "C" int glx_graph_export_alias(const glx_graph* g, float* prob, int32_t* alias,
                                       int ptr_kind, void* stream) {
   GLX_REQUIRE(g && prob && alias, "NULL argument");

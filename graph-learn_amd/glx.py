@@ -39,6 +39,7 @@ AGGREGATOR_IDS = {
 EXPORTS = [
     "glx_abi_version", "glx_device_count", "glx_last_error", "glx_host_register", "glx_host_unregister",
     "glx_graph_create", "glx_graph_build", "glx_graph_build_ordered", "glx_graph_destroy", "glx_graph_info", "glx_graph_export_alias",
+    "glx_graph_edge_weight_packed",
     "glx_graph_degrees", "glx_graph_in_degrees", "glx_sample", "glx_sample_ex", "glx_sample_hops",
     "glx_graph_enable_in_degree", "glx_graph_enable_default_weight", "glx_sample_full_sizes", "glx_sample_full",
     "glx_graph_set_timestamps", "glx_sample_filtered", "glx_sample_full_filtered", "glx_random_walk",
@@ -131,6 +132,7 @@ def lib():
         L.glx_graph_destroy.restype = None
         L.glx_graph_info.argtypes = [vp, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(ci),
                                      ctypes.POINTER(ci), ctypes.POINTER(ci)]
+        L.glx_graph_edge_weight_packed.argtypes = [vp, ctypes.POINTER(ci)]
         L.glx_graph_export_alias.argtypes = [vp, vp, vp, ci, vp]
         L.glx_graph_build_ordered.argtypes = [ci, i64, vp, vp, vp, vp, vp, ci, ci, vp, ctypes.POINTER(vp)]
         L.glx_graph_degrees.argtypes = [vp, vp, i64, vp, ci, vp]
@@ -448,6 +450,12 @@ class Graph:
         _check(lib().glx_random_walk(self._h, ps[0], batch, walk_len, p, q, full_nbr_num, default_weight,
                                      default_neighbor_id, seed, call_counter, pw[0], kind, _stream(kind, self.device)))
         return walks
+
+    def edge_weight_packed(self):
+        """True when EdgeWeightSampler draws from the packed per-slot records (every edge id fits an int32)."""
+        p = ctypes.c_int(0)
+        _check(lib().glx_graph_edge_weight_packed(self._h, ctypes.byref(p)))
+        return bool(p.value)
 
     def export_alias(self):
         prob = np.empty(self.num_edges, np.float32)

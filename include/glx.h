@@ -36,7 +36,8 @@ extern "C" {
  * (glx_dist_ledger_*, glx_dist_confirm, GLX_ABORTED), glx_tune.  5 (additions only): glx_dist_sample_full_filtered,
  * glx_dist_in_degrees, glx_dist_negative_create, glx_dist_negative_sample, glx_dist_random_walk_ex (all added during
  * round 4 under 4), glx_graph_enable_default_weight.  Added under 5 (additions only): half-precision
- * feature tables -- GLX_DTYPE_*, glx_features_create_ex, glx_features_view_ex, glx_features_dtype. */
+ * feature tables -- GLX_DTYPE_*, glx_features_create_ex, glx_features_view_ex, glx_features_dtype;
+ * glx_graph_edge_weight_packed. */
 #define GLX_ABI_VERSION 5
 
 /* Exported symbols: libglx.so is built with -fvisibility=hidden. */
@@ -156,6 +157,10 @@ GLX_API int glx_graph_build_ordered(int device, int64_t num_edges, const int64_t
 GLX_API void glx_graph_destroy(glx_graph* g);
 GLX_API int glx_graph_info(const glx_graph* g, int64_t* num_rows, int64_t* num_edges, int* weighted,
                    int* has_id_map, int* device);
+/* *packed = 1 when EdgeWeightSampler (circular padding) draws from the packed per-slot records {prob, own (nbr, eid),
+ * alias partner's (nbr, eid)}: built for a weighted graph whose edge ids all fit an int32, unless GLX_EW_PACKED was "0"
+ * when the graph was created.  0: it draws from the alias tables and the adjacency (same answers).  Added under 5. */
+GLX_API int glx_graph_edge_weight_packed(const glx_graph* g, int* packed);
 /* EdgeWeightSampler on an UNWEIGHTED edge type: the reference reads GLOBAL_FLAG(DefaultWeight) for every edge
  * (MemoryEdgeStorage::GetWeight, memory_edge_storage.cc:97-103: an id beyond the empty weight array) and builds its
  * alias row from that (edge_weight_sampler.cc:78-92) -- with the default 0.0 every prob is 0/0 = NaN, no slot takes its

@@ -107,6 +107,49 @@ def test_rows_beyond_the_pairwise_shuffle_and_rejected_variates(orc):
         ref.close()
 
 
+def test_without_replacement_at_the_largest_k_equals_the_reference(orc):
+    """k = 4096, 5462 and 8192 (the device's LDS kernel; 8192 is the largest k it serves) on rows shorter than, as long
+    as and longer than k: the whole-row std::shuffle, then either padder, draw for draw."""
+    degrees = [0, 1, 4095, 4096, 5462, 8191, 8192, 8193, 20000]
+    ref, g = _graph(17, degrees, "bigk")
+    try:
+        src = np.tile(np.arange(len(degrees) + 1, dtype=np.int64), 2)  # + an unknown id
+        for k in (4096, 5462, 8192):
+            for padding in (1, 0):
+                ref.set_flags(padding_mode=padding, default_neighbor_id=-3)
+                ref.set_seed(k + padding)
+                want_n, want_e = ref.sample("bigk", RWOR, src, k, fresh_thread=True)
+                orc.set_reference_entropy(True, k + padding)
+                got_n, got_e = orc.sample(g, RWOR, src, k, padding_mode=padding, default_neighbor_id=-3)
+                assert np.array_equal(got_n, want_n) and np.array_equal(got_e, want_e), (k, padding)
+    finally:
+        ref.set_flags(padding_mode=1, default_neighbor_id=-3)
+        ref.close()
+        orc.set_reference_entropy(False)
+
+
+@pytest.mark.parametrize("weights", ["sixty_fourths", "uniform"])
+def test_alias_build_of_a_row_beyond_2_24_equals_the_reference(orc, weights):
+    """AliasMethod's tables for one row of 2^24 + 5 weights (zeros and ties among them), bit for bit: the oracle
+    builds the tables the device is compared with at that size (tests/test_gpu_sampler_boundaries.py)."""
+    n = (1 << 24) + 5
+    rng = np.random.default_rng(n)
+    if weights == "sixty_fourths":
+        w = (rng.integers(0, 1000, n) / 64.0).astype(np.float32)
+    else:
+        w = (rng.random(n) * 0.99 + 0.01).astype(np.float32)
+        w[::997] = 0.0
+    w[-1] = 0.0
+    prob, alias = orc.alias_build(np.array([0, n], np.int64), w)
+    ref = RefLib()
+    try:
+        want_p, want_a = ref.alias_build(w)
+    finally:
+        ref.close()
+    assert np.array_equal(prob.view(np.uint32), want_p.view(np.uint32))
+    assert np.array_equal(alias, want_a)
+
+
 def test_the_contract_path_is_untouched_by_the_switch(orc, small):
     _, g, V = small
     src = np.arange(V, dtype=np.int64)
