@@ -470,17 +470,7 @@ extern "C" int glx_cond_negative_sample(const glx_cond_table* t, const glx_graph
   GlxDeviceGuard guard(t->device);
   GLX_REQUIRE(guard.ok, "cannot select device %d", t->device);
   const int32_t ncols = t->num_cols;
-  GlxHostStage st(t->device, ptr_kind, stream);
-  const hipStream_t s = st.s;
-  const int64_t *p_src, *p_dst, *p_keys;
-  int64_t* p_out;
-  st.in(&p_src, src, (size_t)batch);
-  st.in(&p_dst, dst, (size_t)batch);
-  st.in(&p_keys, ncols > 0 ? dst_keys : nullptr, (size_t)batch * ncols);
-  st.out(&p_out, out, (size_t)batch * count);
-  int rc = st.begin();
-  if (rc != GLX_OK) return st.finish(rc);
-  GlxTemp d_num, d_set, d_total;
+  // props is a host array whatever ptr_kind says: its refusals are decided before anything is staged or allocated
   std::vector<int32_t> num_c((size_t)(ncols > 0 ? ncols : 1), 0);
   int64_t by_columns = 0;
   for (int32_t c = 0; c < ncols; ++c) {
@@ -493,6 +483,17 @@ extern "C" int glx_cond_negative_sample(const glx_cond_table* t, const glx_graph
   // refused them already; the C entry point must too: a full set makes its probe loop spin)
   GLX_REQUIRE(by_columns <= count, "the column proportions ask for %lld of %d negatives per row (sum(props) > 1)",
               (long long)by_columns, count);
+  GlxHostStage st(t->device, ptr_kind, stream);
+  const hipStream_t s = st.s;
+  const int64_t *p_src, *p_dst, *p_keys;
+  int64_t* p_out;
+  st.in(&p_src, src, (size_t)batch);
+  st.in(&p_dst, dst, (size_t)batch);
+  st.in(&p_keys, ncols > 0 ? dst_keys : nullptr, (size_t)batch * ncols);
+  st.out(&p_out, out, (size_t)batch * count);
+  int rc = st.begin();
+  if (rc != GLX_OK) return st.finish(rc);
+  GlxTemp d_num, d_set, d_total;
   GLX_HIP(hipMalloc(&d_num.p, num_c.size() * 4));
   GLX_HIP(hipMemcpyAsync(d_num.p, num_c.data(), num_c.size() * 4, hipMemcpyHostToDevice, s));
   // everything the request can insert: its dst ids, the neighbours of its src ids, every accepted id

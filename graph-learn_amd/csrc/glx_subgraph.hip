@@ -206,7 +206,8 @@ extern "C" int glx_subgraph_induce(int device, const int64_t* nodes, int32_t n, 
   rc = st.begin();
   if (rc == GLX_OK) rc = induce_device(d_nodes, n, d_off, d_nbr, d_eid, d_row, d_col, d_eout, capacity, count_out, st.s);
   if (rc == GLX_OK) {
-    const int64_t got = *count_out < capacity ? *count_out : capacity;
+    // entries are written in pairs: with an odd capacity below the total the last slot was never written on the device
+    const int64_t got = *count_out < capacity ? *count_out : (capacity & ~(int64_t)1);
     st.out_after(row_out, d_row, (size_t)got * 4);
     st.out_after(col_out, d_col, (size_t)got * 4);
     st.out_after(eid_out, d_eout, (size_t)got * 8);

@@ -787,7 +787,11 @@ GLX_API int glx_cond_negative_sample(const glx_cond_table* t, const glx_graph* g
  * (glx_sample_full, or glx_dist_sample_full across shards).  For every node i, in order, and every j in list order whose
  * id is among row i's neighbours, the entries (i, j, e) and (j, i, e) are appended, e = the edge id of the LAST slot of row
  * i holding that neighbour (node2edge[nbrs[k]] = edge_ids[k], :60-64).  *count_out (host) = the number of entries, 2 per
- * match; at most `capacity` are written (capacity 0: count only).  The call returns when the outputs are valid. */
+ * match, whatever `capacity` is (capacity 0: count only).  Entries are written in whole pairs: when the total exceeds
+ * `capacity`, the first `capacity` rounded down to even entries of the full answer are written and nothing beyond them
+ * is touched, the odd slot included.  INT64_MIN is the empty-slot key of the per-row tables: a node or neighbour with
+ * that id matches nothing, where the reference would match the two (the answer is the reference's for the same rows
+ * without those neighbours).  The call returns when the outputs are valid. */
 GLX_API int glx_subgraph_induce(int device, const int64_t* nodes, int32_t n, const int64_t* offsets, const int64_t* nbr,
                                 const int64_t* eid, int32_t* row_out, int32_t* col_out, int64_t* eid_out, int64_t capacity,
                                 int64_t* count_out, int ptr_kind, void* stream);

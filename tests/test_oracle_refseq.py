@@ -519,3 +519,134 @@ def test_node2vec_walks_with_dead_ends_equal_the_reference(orc, case):
     finally:
         ref.close()
         orc.set_reference_entropy(False)
+
+
+# ---- the shapes of tests/test_gpu_op_boundaries.py: the oracle itself against the reference there --------------------
+def test_node2vec_walk_of_2049_walkers_with_stuck_ones_equals_the_reference(orc):
+    """2049 walkers (three per thread of the device's one-workgroup scan) over a graph where a third of the vertices
+    have no out-edges and two rows hold 65 and 70 neighbours: hundreds of stuck walkers shift the later windows."""
+    rng = np.random.default_rng(2049)
+    V = 300
+    deg = rng.integers(0, 9, V)
+    deg[rng.random(V) < 0.3] = 0
+    deg[0], deg[1] = 70, 65
+    src = np.repeat(np.arange(V, dtype=np.int64), deg)
+    dst = rng.integers(0, V, src.shape[0]).astype(np.int64)
+    w = (rng.random(src.shape[0]) * 0.9 + 0.05 + np.arange(src.shape[0]) * 2.0 ** -20).astype(np.float32)
+    ref = RefLib(default_neighbor_id=0)
+    try:
+        ref.add_edges("walk2049", src, dst, w)
+        rows = np.flatnonzero(deg > 0).astype(np.int64)
+        rp, col, eid, ws = ref.export_csr("walk2049", rows, 128)
+        og = dict(row_ptr=rp, col=col, eid=eid, weight=ws, ids=rows)
+        seeds = rng.integers(0, V, 2049).astype(np.int64)
+        seeds[:2] = (0, 1)
+        for seed, (p, q, F) in enumerate(((0.5, 2.0, 64), (4.0, 0.25, 100))):
+            ref.set_seed(seed)
+            want = ref.random_walk("walk2049", seeds, 6, p, q, full_nbr_num=F, fresh_thread=True)
+            assert (deg[want[:, 0]] == 0).sum() > 200  # stuck from step 1 on
+            orc.set_reference_entropy(True, seed)
+            got = orc.random_walk(og, seeds, 6, p=p, q=q, full_nbr_num=F, default_neighbor_id=0)
+            assert np.array_equal(got, want), (p, q, F)
+    finally:
+        ref.close()
+        orc.set_reference_entropy(False)
+
+
+def test_strict_negative_samplers_with_count_129_equal_the_reference(orc):
+    """count = 129: a retry block of the device kernel takes three passes of 64 lanes; both strict modes."""
+    g = _load("negative.npz")
+    ref = RefLib()
+    try:
+        ref.add_edges("neg129", g["src"], g["dst"], g["w"])
+        ref.add_weighted_nodes("nw129", g["node_ids"], g["node_weights"])
+        graph = dict(row_ptr=g["row_ptr"], col=g["col"], eid=g["eid"], weight=g["w_slot"], ids=g["rows"])
+        rng = np.random.default_rng(129)
+        src = rng.choice(g["rows"], 40)
+        batch = g["node_ids"][rng.integers(0, g["node_ids"].shape[0], 300)]
+        for seed in (1, 2):
+            ref.set_seed(seed)
+            want = ref.negative_sample("neg129", "InDegreeNegativeSampler", src, 129, fresh_thread=True)
+            orc.set_reference_entropy(True, seed)
+            got = orc.negative_sample(g["dst_ids"], (g["indeg_prob"], g["indeg_alias"]), 1, graph, src, 129)
+            assert np.array_equal(got, want), seed
+            ref.set_seed(seed)
+            want = ref.negative_sample("nw129", "NodeWeightNegativeSampler", batch, 129, fresh_thread=True)
+            orc.set_reference_entropy(True, seed)
+            got = orc.negative_sample(g["node_ids"], (g["node_prob"], g["node_alias"]), 2, None, batch, 129)
+            assert np.array_equal(got, want), seed
+            assert not np.isin(want[0], batch).any()  # the set was alive
+    finally:
+        ref.close()
+        orc.set_reference_entropy(False)
+
+
+@pytest.mark.parametrize("strategy", ["random", "in_degree"])
+def test_conditional_negative_count_129_unique_and_a_source_row_of_200_equal_the_reference(orc, strategy):
+    """count = 129 (86 + 43 by two columns: blocks of more than one 64-lane chunk of the device's loop), `unique` on, and a source whose row holds 200 neighbours (multi-edges) -- on a world of its own:
+    1200 attributed items under fresh type names, so that the reference builds a new condition table and the groups
+    (300 / 400 / 600 members) can fill their unique slots.  Draw for draw against the reference's operator."""
+    from test_oracle_cond_negative import float_key
+    rng = np.random.default_rng(129)
+    U = 1200
+    items = (np.arange(U, dtype=np.int64) * 7 + 1000)[rng.permutation(U)]
+    item_w = (rng.random(U) + 0.05).astype(np.float32)
+    int_attr = (np.arange(U) % 4).astype(np.int64)
+    float_attr = np.array([0.5, 1.0, 0.0], np.float32)[np.arange(U) % 3]
+    str_attr = [b"A" if i % 2 == 0 else b"B" for i in range(U)]
+    attr = {int(i): (int(a), float(f), s) for i, a, f, s in zip(items, int_attr, float_attr, str_attr)}
+    # every item is somebody's destination (the candidates are the distinct destinations in first-appearance order);
+    # sources 0 .. 19 hold 0 .. 8 neighbours, source 20 holds 200
+    deg = rng.integers(0, 9, 20)
+    src = np.concatenate([21 + np.arange(U) // 10, np.repeat(np.arange(20), deg), np.full(200, 20)]).astype(np.int64)
+    dst = np.concatenate([items, rng.choice(items, int(deg.sum())), rng.choice(items[:400], 200)]).astype(np.int64)
+    _, first = np.unique(dst, return_index=True)
+    cand = dst[np.sort(first)]
+    w = np.array([np.sum(dst == c) for c in cand], np.float32) if strategy == "in_degree" else None
+    order = np.argsort(src, kind="stable")
+    rp = np.zeros(int(src.max()) + 2, np.int64)
+    np.add.at(rp, src + 1, 1)
+    rp = np.cumsum(rp)
+    g = dict(row_ptr=rp, col=np.ascontiguousarray(dst[order]), eid=np.ascontiguousarray(order.astype(np.int64)))
+    assert rp[21] - rp[20] == 200 and np.unique(g["col"][rp[20]:rp[21]]).shape[0] < 200
+    sdict = {b"A": 0, b"B": 1}
+
+    def keys_of(ids):
+        return np.stack([np.array([attr[int(c)][0] for c in ids], np.int64), float_key([attr[int(c)][1] for c in ids]),
+                         np.array([sdict[attr[int(c)][2]] for c in ids], np.int64)])
+    keys = keys_of(cand)
+    req_src = np.array([0, 20, 1], np.int64)
+    req_dst = items[[5, 17, 400]]
+    dk = np.ascontiguousarray(keys_of(req_dst).T)
+    # the reference's response is complete only where the columns fill the row themselves (its fill loop is dead code,
+    # quirk 14): 86 + 43 + 0 = 129, the first column beyond one chunk of 64
+    props = np.array([2.0 / 3.0, 1.0 / 3.0, 0.0], np.float32)
+    count = 129
+    assert [int(np.float32(count) * x) for x in props] == [86, 43, 0]
+    ref = RefLib()
+    compared = 0
+    try:
+        ntype, etype = "item129_" + strategy, "buy129_" + strategy
+        ref.add_attr_nodes(ntype, items, weights=item_w, int_attrs=int_attr.reshape(-1, 1),
+                           float_attrs=float_attr.reshape(-1, 1), str_attrs=[[s] for s in str_attr])
+        ref.set_flags(1, 0, 0.0)
+        ref.add_edges(etype, src, dst, None)
+        for t in range(20):
+            ref.set_seed(9000 + t)
+            want = ref.cond_neg_sample(etype, strategy, ntype, req_src, req_dst, count, int_cols=[0], int_props=props[:1],
+                                       float_cols=[0], float_props=props[1:2], str_cols=[0], str_props=props[2:],
+                                       batch_share=False, unique=True)
+            orc.set_reference_entropy(True, 9000 + t)
+            got, filled = orc.cond_negative_sample(cand, w, keys, props, g, req_src, req_dst, dk, count, unique=True,
+                                                   with_filled=True)
+            if want.shape[0] != req_src.shape[0] * count:
+                continue  # a column came up short: the reference's response is misaligned there (quirk 14)
+            assert np.all(filled == count)
+            assert np.array_equal(got.reshape(-1), want), (strategy, t)
+            assert np.unique(want).shape[0] == want.shape[0]  # unique across the whole request
+            assert not np.isin(want[count:2 * count], g["col"][rp[20]:rp[21]]).any()  # the 200 neighbours were excluded
+            compared += 1
+        assert compared >= 15, compared
+    finally:
+        ref.close()
+        orc.set_reference_entropy(False)

@@ -55,3 +55,33 @@ def test_oracle_equals_live_reference_on_random_requests():
                 assert np.array_equal(a[k], b[k]), (seeds, nn, full, k)
     finally:
         ref.close()
+
+
+@pytest.mark.skipif(not have_ref(), reason="reference library not built")
+def test_oracle_equals_live_reference_on_a_row_of_129_neighbours_with_repeats():
+    """Degree 129 over 40 vertices: every neighbour id repeats, inside a run of 64 slots and across runs; the later slot's
+    edge id must win (the device resolves this with atomicMax over chunks of 64)."""
+    rng = np.random.default_rng(129)
+    deg = rng.integers(1, 11, 40)
+    deg[0], deg[1] = 129, 65
+    src = np.repeat(np.arange(40, dtype=np.int64), deg)
+    dst = rng.integers(0, 40, src.shape[0]).astype(np.int64)
+    w = (rng.random(src.shape[0]) * 0.9 + 0.05 + np.arange(src.shape[0]) * 2.0 ** -20).astype(np.float32)
+    ref = RefLib(storage_mode=2)
+    try:
+        ref.add_edges("sub129", src, dst, w)
+        ref.set_flags(1, 0, 0.0)
+        rows = np.arange(40, dtype=np.int64)
+        rp, col, eid, ws = ref.export_csr("sub129", rows, 256)
+        g = dict(row_ptr=rp, col=col, eid=eid, weight=ws, ids=rows)
+        first = col[rp[0]:rp[1]]
+        assert first.shape[0] == 129 and np.unique(first[:64]).shape[0] < 64 and np.isin(first[64:], first[:64]).any()
+        orc = Oracle()
+        for seeds, nn in (([0, 1, 2], [10]), ([0], [129]), ([5, 0, 0, 1], [3])):
+            a = ref.subgraph("sub129", np.array(seeds, np.int64), nn, full_nbr_num=200)
+            b = orc.subgraph(g, np.array(seeds, np.int64), nn, full_nbr_num=200)
+            assert a["row"].shape[0] > 50
+            for k in a:
+                assert np.array_equal(a[k], b[k]), (seeds, nn, k)
+    finally:
+        ref.close()
