@@ -64,6 +64,7 @@ EXPORTS = [
     "glx_plan_create", "glx_plan_run", "glx_plan_output", "glx_plan_destroy",
     "glx_probe_bandwidth", "glx_tune", "glx_subgraph_induce",
     "glx_cond_table_create", "glx_cond_table_destroy", "glx_cond_negative_sample",
+    "glx_unique",
 ]
 
 
@@ -231,6 +232,7 @@ def lib():
         L.glx_probe_bandwidth.argtypes = [ci, ci, i64, i64, i32, i32, ctypes.POINTER(ctypes.c_double),
                                           ctypes.POINTER(ctypes.c_double), vp]
         L.glx_tune.argtypes = [ctypes.c_char_p, i32]
+        L.glx_unique.argtypes = [ci, vp, vp, i32, vp, vp, vp, ci, vp]
         L.glx_plan_destroy.restype = None
         _lib = L
     return _lib
@@ -677,6 +679,51 @@ def stitch(rows, order):
     assert rows.dtype in (torch.int64, torch.float32)
     _check(fn(dev, _ptr(rows)[0], _ptr(order)[0], n, width, _ptr(out)[0], _stream(PTR_DEVICE, dev)))
     return out
+
+
+def unique(parts, return_inverse=True):
+    """Distinct ids of the stream parts[0], parts[1], ... (1 .. 16 int64 arrays of any shape, at most 2^31 - 1 ids in
+    all) in order of first occurrence -- no sort, the same answer on every run.
+    -> (nodes[m], [inverse of each part, shaped like the part] or None, part_end[len(parts)]):
+    nodes[inverse[p]] == parts[p], and nodes[:part_end[p]] is the distinct set of parts[0 .. p].
+    Torch CUDA tensors are device pointers on the current stream (the outputs are CUDA tensors, part_end included);
+    numpy arrays are host pointers.  The device path reads m = part_end[-1] back with ONE host read, to slice nodes."""
+    parts = list(parts)
+    assert parts, "unique() needs at least one part"
+    torch_mode = _is_torch(parts[0])
+    if any(_is_torch(p) != torch_mode for p in parts):
+        raise ValueError("unique(): every part must be of one kind, numpy arrays or torch CUDA tensors")
+    if torch_mode and any(p.device != parts[0].device for p in parts):
+        raise ValueError("unique(): every part must live on one device, got {}".format(sorted({str(p.device) for p in parts})))
+    lens = [int(np.prod(p.shape)) for p in parts]
+    n, P = sum(lens), len(parts)
+    if torch_mode:
+        import torch
+        dev = parts[0].device
+        nodes = torch.empty(n, dtype=torch.int64, device=dev)
+        inverse = torch.empty(n, dtype=torch.int64, device=dev) if return_inverse else None
+        part_end = torch.empty(P, dtype=torch.int64, device=dev)
+        assert all(p.dtype == torch.int64 for p in parts)
+        device = dev.index or 0
+    else:
+        nodes = np.empty(n, np.int64)
+        inverse = np.empty(n, np.int64) if return_inverse else None
+        part_end = np.empty(P, np.int64)
+        device = 0
+    ptrs = [_ptr(p, None if torch_mode else np.int64) for p in parts]
+    kind = _kind(*ptrs, _ptr(nodes))
+    pp = (ctypes.c_void_p * P)(*[p[0] for p in ptrs])
+    pl = (ctypes.c_int64 * P)(*lens)
+    _check(lib().glx_unique(device, pp, pl, P, _ptr(nodes)[0], _ptr(inverse)[0], _ptr(part_end)[0], kind,
+                            _stream(kind, device)))
+    m = int(part_end[-1])
+    inv = None
+    if return_inverse:
+        inv, at = [], 0
+        for p, k in zip(parts, lens):
+            inv.append(inverse[at:at + k].reshape(p.shape))
+            at += k
+    return nodes[:m], inv, part_end
 
 
 NEG_EXCLUDE_NONE, NEG_EXCLUDE_NEIGHBORS, NEG_EXCLUDE_BATCH = 0, 1, 2

@@ -15,12 +15,25 @@ kernel launches on the current torch stream.
         batch.x[h]                       # float attributes of frontier h ([B, D], [B*f1, D], ...)
         src, dst = batch.edge_index(h)   # COO of hop h+1 in frontier-local positions
 
+With dedup=True a batch is a CompactBatch: the same sample, plus the distinct node set of the batch (seeds first, in
+order of first occurrence -- glx_unique, no sort), every sampled slot's position in it and ONE feature row per distinct
+node instead of one per slot:
+
+    for batch in gl.NeighborLoader(..., dedup=True):
+        batch.nodes                      # [M] distinct ids; nodes[:num_nodes_upto[h]] = frontiers 0 .. h
+        batch.local[h]                   # positions of frontier h in nodes, shaped like the frontier
+        batch.x_nodes                    # [M, D] float attributes of nodes
+        src, dst = batch.edge_index(h)   # COO of hop h+1 in node-set positions
+
+The node set's size decides the shape of nodes / x_nodes, so each glx.unique call reads one int64 back from the device:
+with dedup=True the loader waits for the stream once per node type per batch (the plain loader never does).
+
 Seeding: batch i of epoch e uses call counter (e * batches_per_epoch + i) * hops, so a
 (sampling seed, epoch, batch) triple always reproduces the same sample.
 """
 import numpy as np
 
-__all__ = ["NeighborLoader", "NeighborBatch"]
+__all__ = ["NeighborLoader", "NeighborBatch", "CompactBatch"]
 
 
 class NeighborBatch(object):
@@ -46,10 +59,38 @@ class NeighborBatch(object):
     return torch.div(dst, k, rounding_mode="floor"), dst
 
 
+class CompactBatch(NeighborBatch):
+  """A mini-batch over its distinct nodes (NeighborLoader(..., dedup=True)).  seeds / nbr / eid are those of the plain
+  batch.  The node set is kept per node type: frontiers of one type share a set, in hop order, so with distinct seeds
+  nodes[:B] == seeds and nodes[:num_nodes_upto[h]] holds exactly the nodes of frontiers 0 .. h of that type.
+
+    nodes            [M] int64 distinct ids -- a dict keyed by node type when the meta-path visits several types
+    local[h]         positions of frontier h in the node set of its type, shaped like the frontier
+    num_nodes_upto   [hops + 1] int64 CUDA tensor: size of frontier h's node set once frontier h is in
+    x_nodes          [M, D] float attributes of nodes (dict keyed by type like nodes; None without float attributes)
+    types[h]         node type of frontier h
+  Building one costs a host read of the node set's size per node type (glx.unique), i.e. a wait for the stream.
+  """
+
+  def __init__(self, seeds, nbr, eid, types, nodes, local, num_nodes_upto, x_nodes):
+    super(CompactBatch, self).__init__(seeds, nbr, eid, None)
+    self.types, self.nodes, self.local = types, nodes, local
+    self.num_nodes_upto, self.x_nodes = num_nodes_upto, x_nodes
+
+  def nodes_of(self, h):
+    """the node set frontier h is numbered in"""
+    return self.nodes[self.types[h]] if isinstance(self.nodes, dict) else self.nodes
+
+  def edge_index(self, h):
+    """(src, dst) of hop h+1 in node-set positions: local[h] repeated over the fan-out, local[h+1]."""
+    k = self.nbr[h].shape[1]
+    return self.local[h].reshape(-1).repeat_interleave(k), self.local[h + 1].reshape(-1)
+
+
 class NeighborLoader(object):
 
   def __init__(self, graph, node_type, meta_path, fanouts, batch_size, strategy="random", shuffle=True,
-               drop_last=False, with_features=True, seed_ids=None):
+               drop_last=False, with_features=True, seed_ids=None, dedup=False):
     import torch
     from graphlearn import settings
     self._graph = graph
@@ -64,6 +105,8 @@ class NeighborLoader(object):
     self._epoch = 0
     topo = graph.get_topology()
     types = [node_type] + [topo.get_dst_type(e) for e in (meta_path if isinstance(meta_path, (list, tuple)) else [meta_path])]
+    self._types = types
+    self._dedup = bool(dedup)
     self._feats = None
     if with_features:
       self._feats = []
@@ -94,6 +137,9 @@ class NeighborLoader(object):
       hops = self._sampler.get_device(seeds, call_counter=cc)
       nbr = [h[0] for h in hops]
       eid = [h[1] for h in hops]
+      if self._dedup:
+        yield self._compact(seeds, nbr, eid, default_attr)
+        continue
       x = None
       if self._feats is not None:
         x = []
@@ -102,3 +148,30 @@ class NeighborLoader(object):
           x.append(f.lookup(ids, default_attr) if f is not None else None)
       yield NeighborBatch(seeds, nbr, eid, x)
     self._epoch += 1
+
+  def _compact(self, seeds, nbr, eid, default_attr):
+    """One glx_unique over the frontiers of every node type (seeds, hop 1, ... in hop order), then one glx_lookup of
+    the distinct nodes per type.  glx.unique reads the set's size on the host: one stream wait per node type."""
+    import glx
+    import torch
+    frontiers = [seeds] + nbr
+    kinds = list(dict.fromkeys(self._types))  # node types in order of first visit
+    nodes, x_nodes = {}, {}
+    local = [None] * len(frontiers)
+    upto = torch.empty(len(frontiers), dtype=torch.int64, device=seeds.device)
+    for t in kinds:
+      hs = [h for h, th in enumerate(self._types) if th == t]
+      nodes[t], inverse, part_end = glx.unique([frontiers[h] for h in hs])
+      for h, inv in zip(hs, inverse):
+        local[h] = inv
+      for j, h in enumerate(hs):
+        upto[h] = part_end[j]
+      if self._feats is not None:
+        f = self._feats[hs[0]]
+        x_nodes[t] = f.lookup(nodes[t], default_attr) if f is not None else None
+    if self._feats is None:
+      x_nodes = None
+    if len(kinds) == 1:
+      nodes = nodes[kinds[0]]
+      x_nodes = x_nodes[kinds[0]] if x_nodes is not None else None
+    return CompactBatch(seeds, nbr, eid, list(self._types), nodes, local, upto, x_nodes)

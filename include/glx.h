@@ -37,7 +37,7 @@ extern "C" {
  * glx_dist_in_degrees, glx_dist_negative_create, glx_dist_negative_sample, glx_dist_random_walk_ex (all added during
  * round 4 under 4), glx_graph_enable_default_weight.  Added under 5 (additions only): half-precision
  * feature tables -- GLX_DTYPE_*, glx_features_create_ex, glx_features_view_ex, glx_features_dtype;
- * glx_graph_edge_weight_packed. */
+ * glx_graph_edge_weight_packed; frontier dedup -- glx_unique. */
 #define GLX_ABI_VERSION 5
 
 /* Exported symbols: libglx.so is built with -fvisibility=hidden. */
@@ -795,6 +795,24 @@ GLX_API int glx_cond_negative_sample(const glx_cond_table* t, const glx_graph* g
 GLX_API int glx_subgraph_induce(int device, const int64_t* nodes, int32_t n, const int64_t* offsets, const int64_t* nbr,
                                 const int64_t* eid, int32_t* row_out, int32_t* col_out, int64_t* eid_out, int64_t capacity,
                                 int64_t* count_out, int ptr_kind, void* stream);
+
+/* ---- frontier dedup: the distinct node set of a sampled batch, every sampled slot's position in it, and the set's
+ * size after each frontier.  Stands in for what the reference's loaders do on the host or with sort-based tensor calls:
+ * examples/pytorch/tgn/temporal_batch_loader.py:99-121 (torch.cat(...).unique() and an `assoc` array as long as the node
+ * type) and the node set of SubGraphSampler::Process (core/operator/subgraph/subgraph_sampler.h:47-72).
+ * parts[num_parts] (a host array of 1 .. 16 data pointers) and part_len[num_parts] (host) describe ONE stream
+ * x[0 .. n) = part 0, part 1, ... (a loader passes the seeds and every hop's neighbour ids; nothing is concatenated).
+ * n <= 2^31 - 1; empty parts (pointer may be NULL) and n == 0 are legal.  Every int64 value is an id, INT64_MIN included.
+ *   nodes_out[capacity n]    the distinct ids in order of first occurrence in x; entries from m on are not written
+ *   inverse_out[n] or NULL   nodes_out[inverse_out[i]] == x[i]
+ *   part_end_out[num_parts]  distinct ids among parts 0 .. p, so nodes_out[0 .. part_end_out[p]) is the node set of
+ *                            the first p + 1 parts; m = part_end_out[num_parts - 1].  All zeros when n == 0.
+ * The three outputs are a function of the input alone (no sort; a hash table keeps the smallest position of every id,
+ * DESIGN.md 4).  The data pointers AND part_end_out follow ptr_kind: a device-pointer call leaves the counts in device
+ * memory and never waits for the device; a host-pointer call returns with everything in host memory.  The workspace
+ * comes from the calling thread's per-(device, stream) cache: no allocation once it has grown to the largest n. */
+GLX_API int glx_unique(int device, const int64_t* const* parts, const int64_t* part_len, int32_t num_parts,
+                       int64_t* nodes_out, int64_t* inverse_out, int64_t* part_end_out, int ptr_kind, void* stream);
 
 /* ---- memory-system probes: the measured ceilings the kernels above are priced against -- an addition of this
  * engine with no counterpart in the reference (its PROFILING timers, common/base/profiling.h:24-71, time scopes; they
