@@ -65,6 +65,7 @@ EXPORTS = [
     "glx_probe_bandwidth", "glx_tune", "glx_subgraph_induce",
     "glx_cond_table_create", "glx_cond_table_destroy", "glx_cond_negative_sample",
     "glx_unique",
+    "glx_columns_create", "glx_columns_destroy", "glx_columns_info", "glx_columns_lookup",
 ]
 
 
@@ -233,6 +234,12 @@ def lib():
                                           ctypes.POINTER(ctypes.c_double), vp]
         L.glx_tune.argtypes = [ctypes.c_char_p, i32]
         L.glx_unique.argtypes = [ci, vp, vp, i32, vp, vp, vp, ci, vp]
+        L.glx_columns_create.argtypes = [ci, i64, i32, vp, vp, vp, vp, vp, vp, ci, vp, ctypes.POINTER(vp)]
+        L.glx_columns_destroy.argtypes = [vp]
+        L.glx_columns_destroy.restype = None
+        L.glx_columns_info.argtypes = [vp, ctypes.POINTER(i64), ctypes.POINTER(i32), ctypes.POINTER(ci), ctypes.POINTER(ci),
+                                       ctypes.POINTER(ci), ctypes.POINTER(i32), ctypes.POINTER(ci), ctypes.POINTER(ci)]
+        L.glx_columns_lookup.argtypes = [vp, vp, i64, f32, i32, i64, i64, vp, vp, vp, vp, ci, vp]
         L.glx_plan_destroy.restype = None
         _lib = L
     return _lib
@@ -621,6 +628,120 @@ class Features:
         pi, po = _ptr(node_ids), _ptr(out)
         kind = _kind(pi, po)
         _check(lib().glx_lookup(self._h, pi[0], n, default_attr, po[0], kind, _stream(kind, self.device)))
+        return out
+
+
+COLUMN_NAMES = ("weights", "labels", "timestamps", "int_attrs")
+COLUMNS_MAP_DENSE, COLUMNS_MAP_OWN, COLUMNS_MAP_BORROWED = 0, 1, 2
+# what a requested column answers for an id the table does not know (the reference's Default* flags, config.cc)
+COLUMN_DEFAULTS = {"weights": 0.0, "labels": -1, "timestamps": -1, "int_attrs": 0}
+
+
+def columns_layout(i_num, has_weight=False, has_label=False, has_timestamp=False):
+    """The record of a glx_columns table (include/glx.h): byte offsets of the fields a type has
+    (None for the others) and the padded record size.  int_attrs int64[i_num] | timestamp int64 | weight float32 |
+    label int32, padded to 8 bytes and to a multiple of 16 from 16 bytes on; 0 bytes without any column."""
+    at = 8 * i_num
+    off = {"int_attrs": 0 if i_num > 0 else None, "timestamps": None, "weights": None, "labels": None}
+    if has_timestamp:
+        off["timestamps"] = at
+        at += 8
+    if has_weight:
+        off["weights"] = at
+        at += 4
+    if has_label:
+        off["labels"] = at
+        at += 4
+    at = (at + 7) // 8 * 8
+    if at >= 16:
+        at = (at + 15) // 16 * 16
+    off["record_bytes"] = at
+    return off
+
+
+class Columns:
+    """Device-resident label / weight / timestamp / int-attribute columns of one node or edge type (glx_columns)."""
+
+    def __init__(self, num_rows, weights=None, labels=None, timestamps=None, int_attrs=None, ids=None, map_of=None,
+                 device=0):
+        """Columns: numpy arrays or torch CUDA tensors (all of one kind) -- weights float32[V], labels int32[V],
+        timestamps int64[V], int_attrs int64[V, i_num]; None = the type does not have it.  ids: the rows' raw ids (an
+        own id map); map_of: a glx.Features of the same rows whose map is borrowed (kept alive); neither: id r is row r."""
+        i_num = 0 if int_attrs is None else int(int_attrs.shape[1])
+        ptrs = [_ptr(weights), _ptr(labels), _ptr(timestamps), _ptr(int_attrs), _ptr(ids)]
+        kinds = set(k for _, k in ptrs if k is not None)
+        assert len(kinds) <= 1, "all data pointers of a call must be host (numpy) or device (torch)"
+        kind = kinds.pop() if kinds else PTR_HOST
+        for x, dt in ((weights, "float32"), (labels, "int32"), (timestamps, "int64"), (int_attrs, "int64"), (ids, "int64")):
+            assert x is None or str(x.dtype).replace("torch.", "") == dt, (x.dtype, dt)
+        self.device = device
+        self._keep = map_of
+        h = ctypes.c_void_p()
+        _check(lib().glx_columns_create(device, int(num_rows), i_num, ptrs[0][0], ptrs[1][0], ptrs[2][0], ptrs[3][0],
+                                        ptrs[4][0], map_of._h if map_of is not None else None, kind,
+                                        _stream(kind, device), ctypes.byref(h)))
+        self._h = h
+        self._read_info()
+
+    def _read_info(self):
+        v, i, w, l, t, rb, m, dv = (ctypes.c_int64(), ctypes.c_int32(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int(),
+                                    ctypes.c_int32(), ctypes.c_int(), ctypes.c_int())
+        _check(lib().glx_columns_info(self._h, ctypes.byref(v), ctypes.byref(i), ctypes.byref(w), ctypes.byref(l),
+                                      ctypes.byref(t), ctypes.byref(rb), ctypes.byref(m), ctypes.byref(dv)))
+        self.num_rows, self.i_num = v.value, i.value
+        self.has = {"weights": bool(w.value), "labels": bool(l.value), "timestamps": bool(t.value),
+                    "int_attrs": i.value > 0}
+        self.record_bytes, self.id_map, self.device = rb.value, m.value, dv.value
+
+    @classmethod
+    def from_handle(cls, handle, device=0):
+        """Borrow a glx_columns* owned by someone else (the C++ host layer's Noder / Graph)."""
+        self = cls.__new__(cls)
+        self._h = ctypes.c_void_p(int(handle))
+        self._borrowed = True
+        self._keep = None
+        self._read_info()
+        return self
+
+    def close(self):
+        if getattr(self, "_borrowed", False):
+            self._h = None
+        if getattr(self, "_h", None):
+            try:
+                lib().glx_columns_destroy(self._h)
+            except Exception:  # interpreter shutdown
+                pass
+            self._h = None
+
+    __del__ = close
+
+    def lookup(self, ids, want=COLUMN_NAMES, defaults=None):
+        """-> {name: values} for the names in `want`: weights float32[n], labels int32[n], timestamps int64[n],
+        int_attrs int64[n, i_num]; CUDA tensors for CUDA ids, numpy arrays for numpy ids.  defaults: {name: value} an
+        unknown id answers with (COLUMN_DEFAULTS for the names left out); a column the type lacks answers 0.0 / -1 / -1."""
+        want = tuple(want)
+        for name in want:
+            if name not in COLUMN_NAMES:
+                raise ValueError("unknown column {!r}: one of {}".format(name, COLUMN_NAMES))
+        dflt = dict(COLUMN_DEFAULTS)
+        dflt.update(defaults or {})
+        n = int(ids.shape[0])
+        shapes = {"weights": ((n,), "float32"), "labels": ((n,), "int32"), "timestamps": ((n,), "int64"),
+                  "int_attrs": ((n, self.i_num), "int64")}
+        out = {}
+        for name in want:
+            shape, dt = shapes[name]
+            if _is_torch(ids):
+                import torch
+                out[name] = torch.empty(shape, dtype=getattr(torch, dt), device=ids.device)
+            else:
+                out[name] = np.empty(shape, dt)
+        pi = _ptr(ids)
+        po = [_ptr(out.get(name)) for name in COLUMN_NAMES]
+        kind = pi[1]
+        _check(lib().glx_columns_lookup(self._h, pi[0], n, dflt["weights"], dflt["labels"], dflt["timestamps"],
+                                        dflt["int_attrs"], po[0][0], po[1][0], po[2][0], po[3][0], kind,
+                                        _stream(kind, self.device)))
         return out
 
 

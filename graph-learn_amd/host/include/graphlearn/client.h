@@ -66,6 +66,14 @@ public:
   // users go straight to the C-ABI with these): 0 when the type is unknown or not built.
   uintptr_t DeviceGraph(const std::string& edge_type);
   uintptr_t DeviceFeatures(const std::string& node_type);
+  // Device mirrors that are built on first use (Noder::DeviceColumns, Graph::DeviceColumns / DeviceEdgeFeatures): the
+  // glx_columns of a node / edge type's weight, label, timestamp and int attributes, and the glx_features of an edge
+  // type's float attributes.  0 when the type is unknown, not built, or (edge features) has no float attributes.
+  uintptr_t DeviceColumns(const std::string& node_type);
+  uintptr_t DeviceEdgeColumns(const std::string& edge_type);
+  uintptr_t DeviceEdgeFeatures(const std::string& edge_type);
+  // Which of them exist right now, without building any: bit 0 columns, bit 1 edge features.
+  int DeviceMirrorsBuilt(const std::string& type, bool edge_type);
 
 private:
   Server();

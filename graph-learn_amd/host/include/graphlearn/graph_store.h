@@ -22,6 +22,7 @@
 
 struct glx_graph;
 struct glx_features;
+struct glx_columns;
 struct glx_negative;
 struct glx_dist_store;
 
@@ -166,6 +167,14 @@ public:
   Status EnsureGlobalInDegree(glx_dist_store* store);
   // Per-row id-sorted index for id == value filters (and strict negative sampling), built on first use.
   Status EnsureIdIndex();
+  // Device mirrors of the per-edge properties below, by edge id (the dense map: an id outside [0, E) is unknown), built on
+  // first use; a store that never asks allocates nothing.  DeviceColumns: weight / label / timestamp / int attributes as
+  // one glx_columns table.  DeviceEdgeFeatures: the float attributes as a glx_features that glx_lookup serves (*out stays
+  // nullptr for a type without float attributes).
+  Status DeviceColumns(const glx_columns** out);
+  Status DeviceEdgeFeatures(const glx_features** out);
+  // 1: DeviceColumns() has built its table, 2: DeviceEdgeFeatures() has; asks for nothing to be built.
+  int DeviceMirrorsBuilt();
 
   // Per-edge properties by edge id, host resident (they are not read by the samplers):
   // EdgeStorage::GetWeight/GetLabel/GetTimestamp/GetAttribute
@@ -193,6 +202,8 @@ private:
   glx_graph* dev_;
   glx_negative* neg_uniform_;
   glx_negative* neg_in_degree_;
+  glx_columns* cols_ = nullptr;
+  glx_features* edge_feats_ = nullptr;
   bool neg_strict_ready_;
   bool in_degree_ready_;
   bool default_weights_ready_ = false;
@@ -217,6 +228,10 @@ public:
   const std::vector<float>& Weights() const { return weights_; }  // NodeStorage::GetWeights (weighted types)
   // Candidate list of NodeWeightNegativeSampler: this type's ids weighted by node weight.
   Status Negative(const glx_negative** out);
+  // Device mirror of the host-resident properties below (weight / label / timestamp / int attributes) as one
+  // glx_columns table, built on first use; it borrows the id map of Device() when the type has float attributes.
+  Status DeviceColumns(const glx_columns** out);
+  int DeviceMirrorsBuilt();  // 1: DeviceColumns() has built its table; asks for nothing to be built
 
   // NodeStorage::GetWeight/GetLabel/GetTimestamp/GetAttribute
   // (memory_node_storage.cc:88-138) for the host-resident properties; -1 = unknown id.
@@ -244,6 +259,7 @@ private:
   std::unordered_map<int64_t, int32_t> index_;
   glx_features* dev_;
   glx_negative* neg_;
+  glx_columns* cols_ = nullptr;
   std::mutex mtx_;
 };
 

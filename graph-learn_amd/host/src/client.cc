@@ -91,6 +91,29 @@ uintptr_t Server::DeviceFeatures(const std::string& node_type) {
   return store_ ? reinterpret_cast<uintptr_t>(store_->GetNoder(node_type)->Device()) : 0;
 }
 
+uintptr_t Server::DeviceColumns(const std::string& node_type) {
+  const glx_columns* c = nullptr;
+  if (store_) (void)store_->GetNoder(node_type)->DeviceColumns(&c);  // a failure leaves 0; InitStatus() stays Init's
+  return reinterpret_cast<uintptr_t>(c);
+}
+
+uintptr_t Server::DeviceEdgeColumns(const std::string& edge_type) {
+  const glx_columns* c = nullptr;
+  if (store_) (void)store_->GetGraph(edge_type)->DeviceColumns(&c);
+  return reinterpret_cast<uintptr_t>(c);
+}
+
+uintptr_t Server::DeviceEdgeFeatures(const std::string& edge_type) {
+  const glx_features* f = nullptr;
+  if (store_) (void)store_->GetGraph(edge_type)->DeviceEdgeFeatures(&f);
+  return reinterpret_cast<uintptr_t>(f);
+}
+
+int Server::DeviceMirrorsBuilt(const std::string& type, bool edge_type) {
+  if (!store_) return 0;
+  return edge_type ? store_->GetGraph(type)->DeviceMirrorsBuilt() : store_->GetNoder(type)->DeviceMirrorsBuilt();
+}
+
 void Server::Stop() {
   if (store_) {
     // Queries reach a store only through the process-wide OpFactory, i.e. they read the store that is being served

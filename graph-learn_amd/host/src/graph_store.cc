@@ -40,6 +40,8 @@ Graph::Graph(const std::string& type)
 Graph::~Graph() {
   glx_negative_destroy(neg_uniform_);
   glx_negative_destroy(neg_in_degree_);
+  glx_columns_destroy(cols_);
+  glx_features_destroy(edge_feats_);
   glx_graph_destroy(dev_);
 }
 
@@ -212,12 +214,76 @@ Status Graph::EnsureIdIndex() {
   return Status::OK();
 }
 
+Status Graph::DeviceColumns(const glx_columns** out) {
+  // EdgeStorage::GetWeight / GetLabel / GetTimestamp / GetAttribute (memory_edge_storage.cc:90-125) from HBM: the
+  // host columns above, interleaved per edge id (glx_columns_create), the first time a device caller asks.
+  std::lock_guard<std::mutex> g(mtx_);
+  *out = nullptr;
+  if (!cols_) {
+    if (!dev_) return error::InvalidArgument("edge type '" + type_ + "' is not built on the device");
+    int rc = glx_columns_create(GLOBAL_FLAG(DeviceId), (int64_t)src_.size(), info_.i_num,
+                                info_.IsWeighted() ? weight_.data() : nullptr, info_.IsLabeled() ? label_.data() : nullptr,
+                                info_.IsTimestamped() ? timestamp_.data() : nullptr,
+                                info_.i_num > 0 ? i_attrs_.data() : nullptr, nullptr, nullptr, GLX_PTR_HOST, nullptr, &cols_);
+    if (rc != GLX_OK) return error::FromGlx(rc);
+  }
+  *out = cols_;
+  return Status::OK();
+}
+
+Status Graph::DeviceEdgeFeatures(const glx_features** out) {
+  // the float attributes by edge id; glx_row_of answers -1 for ids outside [0, E), so glx_lookup fills those rows
+  // with its default like GetAttribute does (memory_edge_storage.cc:121-131)
+  std::lock_guard<std::mutex> g(mtx_);
+  *out = nullptr;
+  if (info_.f_num <= 0) return Status::OK();
+  if (!edge_feats_) {
+    if (!dev_) return error::InvalidArgument("edge type '" + type_ + "' is not built on the device");
+    int rc = glx_features_create(GLOBAL_FLAG(DeviceId), (int64_t)src_.size(), info_.f_num, f_attrs_.data(), nullptr,
+                                 GLX_PTR_HOST, nullptr, &edge_feats_);
+    if (rc != GLX_OK) return error::FromGlx(rc);
+  }
+  *out = edge_feats_;
+  return Status::OK();
+}
+
+int Graph::DeviceMirrorsBuilt() {
+  std::lock_guard<std::mutex> g(mtx_);
+  return (cols_ ? 1 : 0) | (edge_feats_ ? 2 : 0);
+}
+
 // ------------------------------------------------------------------ Noder --
 Noder::Noder(const std::string& type) : type_(type), dev_(nullptr), neg_(nullptr) {}
 
 Noder::~Noder() {
   glx_negative_destroy(neg_);
+  glx_columns_destroy(cols_);  // before dev_: it may borrow dev_'s id map
   glx_features_destroy(dev_);
+}
+
+Status Noder::DeviceColumns(const glx_columns** out) {
+  // NodeStorage::GetWeight / GetLabel / GetTimestamp / GetAttribute (memory_node_storage.cc:88-138) from HBM, built the
+  // first time a device caller asks.  A type with float attributes already has its id map on the device: borrow it.
+  std::lock_guard<std::mutex> g(mtx_);
+  *out = nullptr;
+  if (!cols_) {
+    // a type declared without any column has no format bit set (IsInitialized() is false for it): "unknown" is a type
+    // that holds no node and never saw a side info
+    if (ids_.empty() && !info_.IsInitialized()) return error::InvalidArgument("node type '" + type_ + "' is not loaded");
+    int rc = glx_columns_create(GLOBAL_FLAG(DeviceId), (int64_t)ids_.size(), info_.i_num,
+                                info_.IsWeighted() ? weights_.data() : nullptr, info_.IsLabeled() ? labels_.data() : nullptr,
+                                info_.IsTimestamped() ? timestamps_.data() : nullptr,
+                                info_.i_num > 0 ? i_attrs_.data() : nullptr, dev_ ? nullptr : ids_.data(), dev_,
+                                GLX_PTR_HOST, nullptr, &cols_);
+    if (rc != GLX_OK) return error::FromGlx(rc);
+  }
+  *out = cols_;
+  return Status::OK();
+}
+
+int Noder::DeviceMirrorsBuilt() {
+  std::lock_guard<std::mutex> g(mtx_);
+  return cols_ ? 1 : 0;
 }
 
 Status Noder::Negative(const glx_negative** out) {

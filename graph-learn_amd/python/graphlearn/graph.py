@@ -409,6 +409,32 @@ class Graph(object):
       raise ValueError("node type {} has no float attributes on the device".format(node_type))
     return glx.Features.from_handle(h)
 
+  def device_columns(self, node_type):
+    """The node type's weights / labels / timestamps / int attributes in HBM as a borrowed glx.Columns (built on the
+    device the first time it is asked for)."""
+    import glx
+    h = self._server.device_columns(node_type)
+    if not h:
+      raise ValueError("node type {} is not loaded".format(node_type))
+    return glx.Columns.from_handle(h)
+
+  def device_edge_columns(self, edge_type):
+    """The edge type's weights / labels / timestamps / int attributes by edge id, as a borrowed glx.Columns (built on
+    first use); ids outside [0, E) -- the -1 of a default-filled sample -- answer the defaults."""
+    import glx
+    h = self._server.device_edge_columns(edge_type)
+    if not h:
+      raise ValueError("edge type {} is not built on the device".format(edge_type))
+    return glx.Columns.from_handle(h)
+
+  def device_edge_features(self, edge_type):
+    """The edge type's float attributes by edge id as a borrowed glx.Features (built on first use)."""
+    import glx
+    h = self._server.device_edge_features(edge_type)
+    if not h:
+      raise ValueError("edge type {} has no float attributes on the device".format(edge_type))
+    return glx.Features.from_handle(h)
+
   def random_walk(self, edge_type, ids, walk_len, p=1.0, q=1.0, call_counter=None):
     """Random walks over one edge type -- the reference's "RandomWalk" operator
     (core/operator/random_walk/random_walk.cc), which its own Python API reaches through GSL's

@@ -25,6 +25,17 @@ node instead of one per slot:
         batch.x_nodes                    # [M, D] float attributes of nodes
         src, dst = batch.edge_index(h)   # COO of hop h+1 in node-set positions
 
+Labels, weights, timestamps and int attributes ride along from HBM the same way (glx.Columns, one lookup per frontier,
+or per node type with dedup=True); the names come from {"labels", "weights", "timestamps", "int_attrs"}:
+
+    for batch in gl.NeighborLoader(..., node_columns=("labels", "int_attrs"), edge_columns=("weights",),
+                                   edge_features=True):
+        batch.y                          # [B] int32 labels of the seeds (when "labels" is asked for)
+        batch.node_cols[h]["int_attrs"]  # shaped like frontier h, plus a trailing i_num axis
+        batch.edge_cols[h]["weights"]    # shaped like nbr[h], gathered by eid[h] (-1 edge ids: the Default* flags)
+        batch.edge_x[h]                  # [rows_h, fanout_h, D] float attributes of hop h+1's edges
+        batch.node_cols_nodes[name]      # dedup=True: one row per distinct node (a dict per type like nodes)
+
 The node set's size decides the shape of nodes / x_nodes, so each glx.unique call reads one int64 back from the device:
 with dedup=True the loader waits for the stream once per node type per batch (the plain loader never does).
 
@@ -36,11 +47,21 @@ import numpy as np
 __all__ = ["NeighborLoader", "NeighborBatch", "CompactBatch"]
 
 
+_COLUMN_NAMES = ("labels", "weights", "timestamps", "int_attrs")
+
+
+def _shaped(cols, shape):
+  """a glx.Columns.lookup answer over flattened ids, back in the ids' shape (int_attrs keep their trailing axis)"""
+  return {name: v.reshape(tuple(shape) + tuple(v.shape[1:])) for name, v in cols.items()}  # i_num may be 0: no -1
+
+
 class NeighborBatch(object):
   """Tensors of one mini-batch (all on the GPU)."""
 
   def __init__(self, seeds, nbr, eid, x):
     self.seeds, self.nbr, self.eid, self.x = seeds, nbr, eid, x
+    # filled when the loader was asked for them (node_columns / edge_columns / edge_features)
+    self.node_cols = self.edge_cols = self.edge_x = self.y = None
 
   @property
   def num_hops(self):
@@ -76,6 +97,7 @@ class CompactBatch(NeighborBatch):
     super(CompactBatch, self).__init__(seeds, nbr, eid, None)
     self.types, self.nodes, self.local = types, nodes, local
     self.num_nodes_upto, self.x_nodes = num_nodes_upto, x_nodes
+    self.node_cols_nodes = None  # {name: one row per distinct node} (a dict per type like nodes) with node_columns
 
   def nodes_of(self, h):
     """the node set frontier h is numbered in"""
@@ -90,9 +112,13 @@ class CompactBatch(NeighborBatch):
 class NeighborLoader(object):
 
   def __init__(self, graph, node_type, meta_path, fanouts, batch_size, strategy="random", shuffle=True,
-               drop_last=False, with_features=True, seed_ids=None, dedup=False):
+               drop_last=False, with_features=True, seed_ids=None, dedup=False, node_columns=(), edge_columns=(),
+               edge_features=False):
     import torch
     from graphlearn import settings
+    for name in tuple(node_columns) + tuple(edge_columns):
+      if name not in _COLUMN_NAMES:
+        raise ValueError("unknown column {!r}: one of {}".format(name, _COLUMN_NAMES))
     self._graph = graph
     self._sampler = graph.neighbor_sampler(meta_path, fanouts, strategy=strategy)
     self._hops = len(fanouts)
@@ -115,6 +141,18 @@ class NeighborLoader(object):
           self._feats.append(graph.device_features(t))
         except ValueError:
           self._feats.append(None)  # a type without float attributes
+    edge_types = list(meta_path) if isinstance(meta_path, (list, tuple)) else [meta_path]
+    self._node_columns, self._edge_columns = tuple(node_columns), tuple(edge_columns)
+    self._ncols = [graph.device_columns(t) for t in types] if self._node_columns else None
+    self._ecols = [graph.device_edge_columns(e) for e in edge_types] if self._edge_columns else None
+    self._efeats = None
+    if edge_features:
+      self._efeats = []
+      for e in edge_types:
+        try:
+          self._efeats.append(graph.device_edge_features(e))
+        except ValueError:
+          self._efeats.append(None)  # an edge type without float attributes
 
   def __len__(self):
     n = self._ids.shape[0]
@@ -138,7 +176,7 @@ class NeighborLoader(object):
       nbr = [h[0] for h in hops]
       eid = [h[1] for h in hops]
       if self._dedup:
-        yield self._compact(seeds, nbr, eid, default_attr)
+        yield self._with_edge_data(self._compact(seeds, nbr, eid, default_attr), default_attr)
         continue
       x = None
       if self._feats is not None:
@@ -146,8 +184,28 @@ class NeighborLoader(object):
         for h, f in enumerate(self._feats):
           ids = seeds if h == 0 else nbr[h - 1].reshape(-1)
           x.append(f.lookup(ids, default_attr) if f is not None else None)
-      yield NeighborBatch(seeds, nbr, eid, x)
+      batch = NeighborBatch(seeds, nbr, eid, x)
+      if self._ncols is not None:
+        defaults = settings.column_defaults()
+        batch.node_cols = []
+        for h, c in enumerate(self._ncols):
+          ids = seeds if h == 0 else nbr[h - 1]
+          batch.node_cols.append(_shaped(c.lookup(ids.reshape(-1), self._node_columns, defaults), ids.shape))
+        batch.y = batch.node_cols[0].get("labels")
+      yield self._with_edge_data(batch, default_attr)
     self._epoch += 1
+
+  def _with_edge_data(self, batch, default_attr):
+    """edge_cols / edge_x of every hop, gathered by the hop's edge ids (the -1 of a default-filled row is unknown)."""
+    from graphlearn import settings
+    if self._ecols is not None:
+      defaults = settings.column_defaults()
+      batch.edge_cols = [_shaped(c.lookup(e.reshape(-1), self._edge_columns, defaults), e.shape)
+                         for c, e in zip(self._ecols, batch.eid)]
+    if self._efeats is not None:
+      batch.edge_x = [f.lookup(e.reshape(-1), default_attr).reshape(tuple(e.shape) + (-1,)) if f is not None else None
+                      for f, e in zip(self._efeats, batch.eid)]
+    return batch
 
   def _compact(self, seeds, nbr, eid, default_attr):
     """One glx_unique over the frontiers of every node type (seeds, hop 1, ... in hop order), then one glx_lookup of
@@ -156,7 +214,7 @@ class NeighborLoader(object):
     import torch
     frontiers = [seeds] + nbr
     kinds = list(dict.fromkeys(self._types))  # node types in order of first visit
-    nodes, x_nodes = {}, {}
+    nodes, x_nodes, cols_nodes = {}, {}, {}
     local = [None] * len(frontiers)
     upto = torch.empty(len(frontiers), dtype=torch.int64, device=seeds.device)
     for t in kinds:
@@ -169,9 +227,19 @@ class NeighborLoader(object):
       if self._feats is not None:
         f = self._feats[hs[0]]
         x_nodes[t] = f.lookup(nodes[t], default_attr) if f is not None else None
+      if self._ncols is not None:  # one glx_columns_lookup per type, beside the one glx_lookup
+        from graphlearn import settings
+        cols_nodes[t] = self._ncols[hs[0]].lookup(nodes[t], self._node_columns, settings.column_defaults())
     if self._feats is None:
       x_nodes = None
+    y = None
+    if self._ncols is not None and "labels" in self._node_columns:
+      y = cols_nodes[self._types[0]]["labels"][local[0]]
     if len(kinds) == 1:
       nodes = nodes[kinds[0]]
       x_nodes = x_nodes[kinds[0]] if x_nodes is not None else None
-    return CompactBatch(seeds, nbr, eid, list(self._types), nodes, local, upto, x_nodes)
+      cols_nodes = cols_nodes.get(kinds[0])
+    batch = CompactBatch(seeds, nbr, eid, list(self._types), nodes, local, upto, x_nodes)
+    if self._ncols is not None:
+      batch.node_cols_nodes, batch.y = cols_nodes, y
+    return batch

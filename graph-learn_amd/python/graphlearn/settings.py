@@ -17,7 +17,15 @@ __all__ = [
 
 # flags the device-tensor path (NeighborSampler.get_device) passes to the C-ABI itself
 _MIRROR = {"padding_mode": 1, "default_neighbor_id": 0, "sampling_seed": 0, "default_float_attr": 0.0, "device_id": 0,
-           "default_full_nbr_num": 100, "default_weight": 0.0, "feature_dtype": "float32"}
+           "default_full_nbr_num": 100, "default_weight": 0.0, "feature_dtype": "float32", "default_int_attr": 0,
+           "default_label": -1, "default_timestamp": -1}
+
+
+def column_defaults():
+  """What the device column lookups (glx.Columns.lookup) answer for an unknown id: the Default* flags as the host
+  operators read them."""
+  return {"weights": _MIRROR["default_weight"], "labels": _MIRROR["default_label"],
+          "timestamps": _MIRROR["default_timestamp"], "int_attrs": _MIRROR["default_int_attr"]}
 
 # storage types of the node feature tables (include/glx.h GLX_DTYPE_*)
 _FEATURE_DTYPES = {"float32": 0, "bfloat16": 1, "float16": 2}
@@ -36,6 +44,7 @@ def set_padding_mode(mode):
 
 def set_default_int_attribute(value=0):
   pywrap.set_default_int_attr(int(value))
+  _MIRROR["default_int_attr"] = int(value)
 
 
 def set_default_float_attribute(value=0.0):
@@ -60,10 +69,12 @@ def set_default_full_nbr_num(num):
 
 def set_default_label(value=-1):
   pywrap.set_default_label(int(value))
+  _MIRROR["default_label"] = int(value)
 
 
 def set_default_timestamp(value=-1):
   pywrap.set_default_timestamp(int(value))
+  _MIRROR["default_timestamp"] = int(value)
 
 
 def set_ignore_invalid(value):

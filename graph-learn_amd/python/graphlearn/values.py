@@ -227,12 +227,15 @@ class DeviceNodes(object):
   asks with .to_host()).  Torch CUDA tensors throughout:
     ids [rows, k] int64, shape, type;
     float_attrs [rows, k, D] float32 (one glx_lookup on the device, on first access);
+    labels / weights / timestamps [rows, k] and int_attrs [rows, k, i_num] (one glx_columns_lookup each, on first access;
+    unknown ids answer the Default* flags of `settings`, like the host values);
     embedding_agg(func) [rows, D] (one device aggregation over each row's k vertices -- Nodes.embedding_agg's result);
     to_host() -> the ordinary Nodes value (one copy)."""
 
   def __init__(self, ids, node_type, graph):
     self._ids, self._type, self._graph = ids, node_type, graph
     self._float_attrs = None
+    self._cols = {}
 
   ids = property(lambda self: self._ids)
   type = property(lambda self: self._type)
@@ -240,6 +243,19 @@ class DeviceNodes(object):
 
   def _features(self):
     return self._graph.device_features(self._type)
+
+  def _column(self, name):
+    if name not in self._cols:
+      from graphlearn import settings
+      flat = self._graph.device_columns(self._type).lookup(self._ids.reshape(-1), want=(name,),
+                                                           defaults=settings.column_defaults())[name]
+      self._cols[name] = flat.reshape(self.shape + tuple(flat.shape[1:]))  # i_num may be 0: no -1
+    return self._cols[name]
+
+  labels = property(lambda self: self._column("labels"))
+  weights = property(lambda self: self._column("weights"))
+  timestamps = property(lambda self: self._column("timestamps"))
+  int_attrs = property(lambda self: self._column("int_attrs"))
 
   @property
   def float_attrs(self):

@@ -261,6 +261,10 @@ PYBIND11_MODULE(pywrap_graphlearn, m) {
         return CopyOut(ids.data(), ids.size());
       })
       .def("device_features", &Server::DeviceFeatures)
+      .def("device_columns", &Server::DeviceColumns, py::call_guard<py::gil_scoped_release>())
+      .def("device_edge_columns", &Server::DeviceEdgeColumns, py::call_guard<py::gil_scoped_release>())
+      .def("device_edge_features", &Server::DeviceEdgeFeatures, py::call_guard<py::gil_scoped_release>())
+      .def("device_mirrors_built", &Server::DeviceMirrorsBuilt, py::arg("type"), py::arg("edge_type") = false)
       .def("stop", &Server::Stop, py::call_guard<py::gil_scoped_release>())
       .def("stop_sampling", [](Server&) { DagScheduler::StopAll(); }, py::call_guard<py::gil_scoped_release>())
       .def("get_stats", [](Server& self) { return self.Store() ? self.Store()->GetStatistics().GetCounts() : Counts(); });

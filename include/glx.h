@@ -37,7 +37,8 @@ extern "C" {
  * glx_dist_in_degrees, glx_dist_negative_create, glx_dist_negative_sample, glx_dist_random_walk_ex (all added during
  * round 4 under 4), glx_graph_enable_default_weight.  Added under 5 (additions only): half-precision
  * feature tables -- GLX_DTYPE_*, glx_features_create_ex, glx_features_view_ex, glx_features_dtype;
- * glx_graph_edge_weight_packed; frontier dedup -- glx_unique. */
+ * glx_graph_edge_weight_packed; frontier dedup -- glx_unique; device-resident label / weight / timestamp / int-attribute
+ * columns -- glx_columns_create, glx_columns_lookup, glx_columns_info, glx_columns_destroy. */
 #define GLX_ABI_VERSION 5
 
 /* Exported symbols: libglx.so is built with -fvisibility=hidden. */
@@ -418,6 +419,43 @@ GLX_API int glx_negative_sample(const glx_negative* t, int exclude, const glx_gr
  * (node_lookuper.cc:24-52); out[n*dim], unknown ids -> default_attr. */
 GLX_API int glx_lookup(const glx_features* f, const int64_t* node_ids, int64_t n, float default_attr,
                float* out, int ptr_kind, void* stream);
+
+/* ---- property columns: replaces NodeStorage::GetWeight / GetLabel / GetTimestamp / GetAttribute()->GetInts()
+ * (memory_node_storage.cc:88-138) and EdgeStorage's (memory_edge_storage.cc:90-125) as LookupNodes / LookupEdges read them
+ * (node_lookuper.cc:24-52, edge_lookuper.cc:24-52) for everything but the float block (glx_lookup) and strings. --------
+ * A glx_columns is a device table of fixed-width records, one per node row or per edge id, holding whichever of these
+ * the type has, interleaved:  int_attrs int64[i_num] | timestamp int64 | weight float32 | label int32  -- padded to 8
+ * bytes, and to a multiple of 16 once the record is 16 bytes or longer, so that one id translation
+ * and one contiguous read serve every column a request asks for.
+ * glx_columns_create: weights[num_rows], labels[num_rows], timestamps[num_rows], int_attrs[num_rows * i_num]; any of them
+ *   may be NULL = the type does not have it (int_attrs exactly when i_num == 0).  The id map is one of
+ *     ids[num_rows]  raw id of every row: the table builds its own map;
+ *     map_of         a glx_features of the same rows whose map is BORROWED (it must outlive the table): a node type that
+ *                    already has a feature table does not pay for a second hash table;
+ *     neither        dense: id r is row r (edge ids).  Both: GLX_INVALID_ARGUMENT.
+ * glx_columns_lookup: ids[n] -> weights_out[n], labels_out[n], timestamps_out[n], int_attrs_out[n * i_num] (the reference's
+ *   response layout); any out pointer may be NULL.  For an output that is asked for:
+ *     the type lacks the column   weight 0.0, label -1, timestamp -1 (memory_node_storage.cc:88-112);
+ *     the id is unknown           the caller's default_* (GLOBAL_FLAG(DefaultWeight) ...; for a dense table: an id outside
+ *                                 [0, num_rows), e.g. the -1 edge id of a default-filled sample);
+ *   values are moved, never converted: a weight's bits arrive as they were stored (NaN payloads included).
+ *   n == 0 is GLX_OK without a launch.
+ * glx_columns_info: any out pointer may be NULL; *record_bytes is the padded record (0: no column at all), *id_map one of
+ *   GLX_COLUMNS_MAP_*. */
+#define GLX_COLUMNS_MAP_DENSE 0
+#define GLX_COLUMNS_MAP_OWN 1
+#define GLX_COLUMNS_MAP_BORROWED 2
+typedef struct glx_columns glx_columns;
+GLX_API int glx_columns_create(int device, int64_t num_rows, int32_t i_num, const float* weights, const int32_t* labels,
+                               const int64_t* timestamps, const int64_t* int_attrs, const int64_t* ids,
+                               const glx_features* map_of, int ptr_kind, void* stream, glx_columns** out);
+GLX_API void glx_columns_destroy(glx_columns* c);
+GLX_API int glx_columns_info(const glx_columns* c, int64_t* num_rows, int32_t* i_num, int* has_weight, int* has_label,
+                             int* has_timestamp, int32_t* record_bytes, int* id_map, int* device);
+GLX_API int glx_columns_lookup(const glx_columns* c, const int64_t* ids, int64_t n, float default_weight,
+                               int32_t default_label, int64_t default_timestamp, int64_t default_int_attr,
+                               float* weights_out, int32_t* labels_out, int64_t* timestamps_out, int64_t* int_attrs_out,
+                               int ptr_kind, void* stream);
 
 /* ---- shard exchange helpers: replace HashPartitioner::Partition
  * (hash_partitioner.h:33-92; shard = llabs(id) % P, stable inside a shard) and
