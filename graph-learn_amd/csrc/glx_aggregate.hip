@@ -45,21 +45,7 @@ namespace {
 // spent on resetting them (a launch costs as much as the whole scan of a small request).
 constexpr int32_t kSegRunMax = 64;
 
-struct SegState {
-  const unsigned long long* words;  // [0]: epoch << 32 | n - valid_len   [1]: epoch << 32 | level
-  uint32_t epoch;
-  int32_t floor_level;  // level the host already knows: 1 = the ids do not divide evenly, 2 = no ids at all
-};
-
-__device__ __forceinline__ int32_t seg_level(const SegState& st) {
-  const unsigned long long w = st.words[1];
-  const int32_t raised = (uint32_t)(w >> 32) == st.epoch ? (int32_t)(uint32_t)w : 0;
-  return raised > st.floor_level ? raised : st.floor_level;
-}
-__device__ __forceinline__ int32_t seg_valid_len(const SegState& st, int32_t n) {
-  const unsigned long long w = st.words[0];
-  return (uint32_t)(w >> 32) == st.epoch ? n - (int32_t)(uint32_t)w : n;
-}
+// (SegState, seg_level and seg_valid_len live in glx_common.h: glx_aggregate_grad.hip reads the same words)
 
 __global__ void glx_seg_reset_kernel(unsigned long long* words) {  // captured launches only (see prepare_segments)
   words[0] = 0;
@@ -144,71 +130,7 @@ __global__ void glx_rows_kernel(GlxIdMap map, const int64_t* __restrict__ ids, i
   rows[i] = (int32_t)glx_row_of(map, ids[i]);
 }
 
-template <int OP>
-__device__ __forceinline__ float agg_init() {
-  if (OP == GLX_AGG_MAX) return (float)FLT_MIN_10_EXP;  // max_aggregator.cc:28 (-37, sic)
-  if (OP == GLX_AGG_MIN) return FLT_MAX;                // min_aggregator.cc:28
-  if (OP == GLX_AGG_PROD) return 1.0f;                  // prod_aggregator.cc
-  return 0.0f;                                          // aggregator.cc:61-65
-}
-
-template <int OP>
-__device__ __forceinline__ float agg_combine(float l, float r) {
-  if (OP == GLX_AGG_MAX) return (l < r) ? r : l;  // std::max(l, r)
-  if (OP == GLX_AGG_MIN) return (r < l) ? r : l;  // std::min(l, r)
-  if (OP == GLX_AGG_PROD) return l * r;
-  return l + r;  // sum, mean
-}
-
-// ---- storage types -----------------------------------------------------------------------------------------
-// A table stores float32, bfloat16 or float16 elements (glx_features::dtype).  Every kernel that reads one upcasts
-// each element to float32 in registers right after the load -- exact for both half types -- and then folds, finishes
-// and stores exactly as for a float32 table: a half table's results are those of the float32 table of its upcast
-// values, bit for bit.  Only the bytes per row change.
-template <int DT>
-struct AggElem;
-template <>
-struct AggElem<GLX_DTYPE_F32> {
-  typedef float raw;
-  static __device__ __forceinline__ float up(float x) { return x; }
-};
-template <>
-struct AggElem<GLX_DTYPE_BF16> {
-  typedef uint16_t raw;
-  static __device__ __forceinline__ float up(uint16_t x) { return __uint_as_float((uint32_t)x << 16); }
-};
-template <>
-struct AggElem<GLX_DTYPE_F16> {
-  typedef _Float16 raw;
-  static __device__ __forceinline__ float up(_Float16 x) { return (float)x; }
-};
-
-// VEC consecutive elements: ONE load of VEC * sizeof(raw) bytes (16 for 4 floats or 8 halves), kept raw until
-// agg_up converts them in registers -- so a batch issues all its loads before the first conversion waits for data.
-template <int DT, int VEC>
-using agg_raw_vec = typename AggElem<DT>::raw __attribute__((ext_vector_type(VEC)));
-
-template <int DT, int VEC>
-__device__ __forceinline__ agg_raw_vec<DT, VEC> agg_load_raw(const typename AggElem<DT>::raw* p) {
-  return *reinterpret_cast<const agg_raw_vec<DT, VEC>*>(p);
-}
-
-template <int DT, int VEC>
-__device__ __forceinline__ float __attribute__((ext_vector_type(VEC))) agg_up(agg_raw_vec<DT, VEC> q) {
-  if constexpr (DT == GLX_DTYPE_F32) {
-    return q;
-  } else {
-    float __attribute__((ext_vector_type(VEC))) r;
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) r[v] = AggElem<DT>::up(q[v]);
-    return r;
-  }
-}
-
-template <int DT, int VEC>
-__device__ __forceinline__ float __attribute__((ext_vector_type(VEC))) agg_load(const typename AggElem<DT>::raw* p) {
-  return agg_up<DT, VEC>(agg_load_raw<DT, VEC>(p));
-}
+// (agg_init, agg_combine, AggElem and the raw-vector loads live in glx_common.h, shared with glx_aggregate_grad.hip)
 
 // float32 -> half for the upload, round to nearest even, bit-identical -- all 2^32 inputs -- to
 // torch.Tensor.to(torch.bfloat16 / torch.float16) of a contiguous CPU tensor, i.e. torch's vectorised conversion.
@@ -1089,8 +1011,7 @@ int seg_words_for(hipStream_t s, unsigned long long** out, uint32_t* epoch) {
 }
 }  // namespace
 
-// int32 words a caller adds to its scratch allocation behind seg_start[num_segments + 1] for prepare_segments
-constexpr size_t kSegScratchExtra = 6;  // two 8-byte aligned 64-bit words
+// (kSegScratchExtra -- the int32 words behind seg_start[num_segments + 1] -- is declared in glx_common.h)
 
 int prepare_segments(AggArgs& a, const int32_t* d_seg, int32_t num_ids, int32_t num_segments, int32_t* scratch,
                      hipStream_t s) {
@@ -1265,6 +1186,19 @@ int glx_aggregate_vrows_device(const GlxRowSource* src, int nsrc, int32_t dim, i
   a.default_attr = default_attr;
   run_aggregate(a, op, d_seg, num_ids, s);
   GLX_HIP(hipGetLastError());
+  return GLX_OK;
+}
+
+// glx_common.h: the segment bookkeeping for the kernels of glx_aggregate_grad.hip (prepare_segments above).
+int glx_segments_prepare(const int32_t* d_seg, int32_t num_ids, int32_t num_segments, int32_t* scratch, hipStream_t s,
+                         GlxSegments* out) {
+  AggArgs a;
+  memset(&a, 0, sizeof(a));
+  const int rc = prepare_segments(a, d_seg, num_ids, num_segments, scratch, s);
+  if (rc != GLX_OK) return rc;
+  out->seg_start = a.seg_start;
+  out->state = a.seg_state;
+  out->fanout = a.fanout;
   return GLX_OK;
 }
 

@@ -3,6 +3,7 @@
 #ifndef GLX_COMMON_H_
 #define GLX_COMMON_H_
 #include <atomic>
+#include <float.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -762,6 +763,104 @@ int glx_negative_sample_rows_device(const glx_negative* t, const glx_graph* g, c
 int glx_aggregate_vrows_device(const GlxRowSource* src, int nsrc, int32_t dim, int op, const int32_t* vrows,
                                const int32_t* d_seg, int32_t num_ids, int32_t num_segments, float default_attr,
                                float* d_emb, int32_t* d_cnt, hipStream_t s);
+
+// ---- pieces of the segmented reduce that glx_aggregate.hip shares with glx_aggregate_grad.hip -----------------
+// The state of one call's segment bookkeeping (glx_aggregate.hip, prepare_segments): two epoch-tagged words that the
+// scan raises; the reduce kernels read them through seg_level / seg_valid_len.
+struct SegState {
+  const unsigned long long* words;  // [0]: epoch << 32 | n - valid_len   [1]: epoch << 32 | level
+  uint32_t epoch;
+  int32_t floor_level;  // level the host already knows: 1 = the ids do not divide evenly, 2 = no ids at all
+};
+
+__device__ __forceinline__ int32_t seg_level(const SegState& st) {
+  const unsigned long long w = st.words[1];
+  const int32_t raised = (uint32_t)(w >> 32) == st.epoch ? (int32_t)(uint32_t)w : 0;
+  return raised > st.floor_level ? raised : st.floor_level;
+}
+__device__ __forceinline__ int32_t seg_valid_len(const SegState& st, int32_t n) {
+  const unsigned long long w = st.words[0];
+  return (uint32_t)(w >> 32) == st.epoch ? n - (int32_t)(uint32_t)w : n;
+}
+
+// int32 words a caller adds to its scratch allocation behind seg_start[num_segments + 1] for the segment bookkeeping
+constexpr size_t kSegScratchExtra = 6;  // two 8-byte aligned 64-bit words
+// What a reduce kernel needs to find segment s of a request: seg_start == nullptr, or seg_level(state) == 0, means
+// ids [s fanout, (s + 1) fanout); otherwise ids [seg_start[s], seg_start[s + 1]).
+struct GlxSegments {
+  const int32_t* seg_start;
+  SegState state;
+  int32_t fanout;
+};
+// Queues the bookkeeping kernels of one request on `s`.  scratch: num_segments + 1 + kSegScratchExtra int32.
+int glx_segments_prepare(const int32_t* d_seg, int32_t num_ids, int32_t num_segments, int32_t* scratch, hipStream_t s,
+                         GlxSegments* out);
+
+template <int OP>
+__device__ __forceinline__ float agg_init() {
+  if (OP == GLX_AGG_MAX) return (float)FLT_MIN_10_EXP;  // max_aggregator.cc:28 (-37, sic)
+  if (OP == GLX_AGG_MIN) return FLT_MAX;                // min_aggregator.cc:28
+  if (OP == GLX_AGG_PROD) return 1.0f;                  // prod_aggregator.cc
+  return 0.0f;                                          // aggregator.cc:61-65
+}
+
+template <int OP>
+__device__ __forceinline__ float agg_combine(float l, float r) {
+  if (OP == GLX_AGG_MAX) return (l < r) ? r : l;  // std::max(l, r)
+  if (OP == GLX_AGG_MIN) return (r < l) ? r : l;  // std::min(l, r)
+  if (OP == GLX_AGG_PROD) return l * r;
+  return l + r;  // sum, mean
+}
+
+// ---- storage types -----------------------------------------------------------------------------------------
+// A table stores float32, bfloat16 or float16 elements (glx_features::dtype).  Every kernel that reads one upcasts
+// each element to float32 in registers right after the load -- exact for both half types -- and then folds, finishes
+// and stores exactly as for a float32 table: a half table's results are those of the float32 table of its upcast
+// values, bit for bit.  Only the bytes per row change.
+template <int DT>
+struct AggElem;
+template <>
+struct AggElem<GLX_DTYPE_F32> {
+  typedef float raw;
+  static __device__ __forceinline__ float up(float x) { return x; }
+};
+template <>
+struct AggElem<GLX_DTYPE_BF16> {
+  typedef uint16_t raw;
+  static __device__ __forceinline__ float up(uint16_t x) { return __uint_as_float((uint32_t)x << 16); }
+};
+template <>
+struct AggElem<GLX_DTYPE_F16> {
+  typedef _Float16 raw;
+  static __device__ __forceinline__ float up(_Float16 x) { return (float)x; }
+};
+
+// VEC consecutive elements: ONE load of VEC * sizeof(raw) bytes (16 for 4 floats or 8 halves), kept raw until
+// agg_up converts them in registers -- so a batch issues all its loads before the first conversion waits for data.
+template <int DT, int VEC>
+using agg_raw_vec = typename AggElem<DT>::raw __attribute__((ext_vector_type(VEC)));
+
+template <int DT, int VEC>
+__device__ __forceinline__ agg_raw_vec<DT, VEC> agg_load_raw(const typename AggElem<DT>::raw* p) {
+  return *reinterpret_cast<const agg_raw_vec<DT, VEC>*>(p);
+}
+
+template <int DT, int VEC>
+__device__ __forceinline__ float __attribute__((ext_vector_type(VEC))) agg_up(agg_raw_vec<DT, VEC> q) {
+  if constexpr (DT == GLX_DTYPE_F32) {
+    return q;
+  } else {
+    float __attribute__((ext_vector_type(VEC))) r;
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) r[v] = AggElem<DT>::up(q[v]);
+    return r;
+  }
+}
+
+template <int DT, int VEC>
+__device__ __forceinline__ float __attribute__((ext_vector_type(VEC))) agg_load(const typename AggElem<DT>::raw* p) {
+  return agg_up<DT, VEC>(agg_load_raw<DT, VEC>(p));
+}
 
 // Admission control for host-pointer calls.  The reference's servers run up to 32 pool threads on one
 // operator (in_memory_service.cc:64-71); on one GPU more than a dozen host-pointer calls in flight only contend

@@ -45,7 +45,7 @@ EXPORTS = [
     "glx_graph_set_timestamps", "glx_sample_filtered", "glx_sample_full_filtered", "glx_random_walk",
     "glx_features_create", "glx_features_view", "glx_features_destroy", "glx_features_info",
     "glx_features_create_ex", "glx_features_view_ex", "glx_features_dtype",
-    "glx_aggregate", "glx_lookup",
+    "glx_aggregate", "glx_lookup", "glx_aggregate_arg", "glx_aggregate_backward",
     "glx_partition", "glx_stitch_i64", "glx_stitch_f32", "glx_aggregate_stitch",
     "glx_negative_create", "glx_negative_from_graph", "glx_negative_destroy", "glx_negative_info",
     "glx_negative_export", "glx_graph_enable_negative", "glx_negative_sample",
@@ -162,6 +162,8 @@ def lib():
                                         ctypes.POINTER(ci)]
         L.glx_aggregate.argtypes = [vp, ci, vp, vp, i32, i32, f32, vp, vp, ci, vp]
         L.glx_lookup.argtypes = [vp, vp, i64, f32, vp, ci, vp]
+        L.glx_aggregate_arg.argtypes = [vp, ci, vp, vp, i32, i32, f32, vp, vp, vp, ci, vp]
+        L.glx_aggregate_backward.argtypes = [ci, ci, vp, vp, vp, i32, i32, i64, i32, vp, vp, ci, vp]
         L.glx_partition.argtypes = [ci, vp, i64, i32, vp, vp, vp, vp]
         L.glx_stitch_i64.argtypes = [ci, vp, vp, i64, i32, vp, vp]
         L.glx_stitch_f32.argtypes = [ci, vp, vp, i64, i32, vp, vp]
@@ -618,6 +620,29 @@ class Features:
                                    pc[0], kind, _stream(kind, self.device)))
         return emb, cnt
 
+    def aggregate_arg(self, op, node_ids, segment_ids, num_segments, default_attr=0.0):
+        """aggregate() for Max / Min that also records where each extreme came from (glx_aggregate_arg)
+        -> (emb[num_segments, D] float32, counts[num_segments] int32, arg[num_segments, D] int32): emb and counts are
+        aggregate()'s bit for bit; arg is the request position of the first element that attains the extreme, -1 when
+        nothing replaced the fold's start value.  aggregate_backward() takes counts and arg."""
+        if isinstance(op, str):
+            op = AGGREGATOR_IDS[op]
+        n = int(node_ids.shape[0])
+        if _is_torch(node_ids):
+            import torch
+            emb = torch.empty((num_segments, self.dim), dtype=torch.float32, device=node_ids.device)
+            cnt = torch.empty((num_segments,), dtype=torch.int32, device=node_ids.device)
+            arg = torch.empty((num_segments, self.dim), dtype=torch.int32, device=node_ids.device)
+        else:
+            emb = np.empty((num_segments, self.dim), np.float32)
+            cnt = np.empty((num_segments,), np.int32)
+            arg = np.empty((num_segments, self.dim), np.int32)
+        pi, pg, pe, pc, pa = _ptr(node_ids), _ptr(segment_ids), _ptr(emb), _ptr(cnt), _ptr(arg)
+        kind = _kind(pi, pg, pe, pc, pa)
+        _check(lib().glx_aggregate_arg(self._h, op, pi[0], pg[0], n, num_segments, default_attr, pe[0], pc[0], pa[0],
+                                       kind, _stream(kind, self.device)))
+        return emb, cnt, arg
+
     def lookup(self, node_ids, default_attr=0.0):
         n = int(node_ids.shape[0])
         if _is_torch(node_ids):
@@ -629,6 +654,35 @@ class Features:
         kind = _kind(pi, po)
         _check(lib().glx_lookup(self._h, pi[0], n, default_attr, po[0], kind, _stream(kind, self.device)))
         return out
+
+
+def aggregate_backward(op, rows, cnt, grad_out, num_rows, arg=None, out=None, device=0):
+    """Gradient of Features.aggregate with respect to the rows of a [num_rows, D] float32 table with dense ids
+    (glx_aggregate_backward) -> grad_x[num_rows, D] float32, every row written (rows nobody references: zeros).
+    rows[n] int64: the request's ids; cnt[num_segments] int32: the counts the forward returned (None: the implied
+    layout of n // num_segments positions per segment); grad_out[num_segments, D] float32; arg: Max / Min only, what
+    Features.aggregate_arg recorded.  Each element adds its terms in ascending request position and no float atomic is
+    used: the same inputs give the same bits on every run.  Prod raises (its gradient divides by the element).
+    Torch CUDA tensors are device pointers on the current stream, numpy arrays host pointers."""
+    if isinstance(op, str):
+        op = AGGREGATOR_IDS[op]
+    n = int(rows.shape[0])
+    num_segments, dim = int(grad_out.shape[0]), int(grad_out.shape[1])
+    if out is not None:
+        grad_x = out
+    elif _is_torch(grad_out):
+        import torch
+        grad_x = torch.empty((num_rows, dim), dtype=torch.float32, device=grad_out.device)
+        device = grad_out.device.index or 0
+    else:
+        grad_x = np.empty((num_rows, dim), np.float32)
+    pr, pc, pa, pg, px = _ptr(rows), _ptr(cnt), _ptr(arg), _ptr(grad_out), _ptr(grad_x)
+    kind = _kind(pr, pc, pa, pg, px)
+    if kind == PTR_DEVICE:
+        device = grad_x.device.index or 0
+    _check(lib().glx_aggregate_backward(device, op, pr[0], pc[0], pa[0], n, num_segments, num_rows, dim, pg[0], px[0],
+                                        kind, _stream(kind, device)))
+    return grad_x
 
 
 COLUMN_NAMES = ("weights", "labels", "timestamps", "int_attrs")

@@ -38,7 +38,8 @@ extern "C" {
  * round 4 under 4), glx_graph_enable_default_weight.  Added under 5 (additions only): half-precision
  * feature tables -- GLX_DTYPE_*, glx_features_create_ex, glx_features_view_ex, glx_features_dtype;
  * glx_graph_edge_weight_packed; frontier dedup -- glx_unique; device-resident label / weight / timestamp / int-attribute
- * columns -- glx_columns_create, glx_columns_lookup, glx_columns_info, glx_columns_destroy. */
+ * columns -- glx_columns_create, glx_columns_lookup, glx_columns_info, glx_columns_destroy; differentiable aggregation --
+ * glx_aggregate_arg, glx_aggregate_backward. */
 #define GLX_ABI_VERSION 5
 
 /* Exported symbols: libglx.so is built with -fvisibility=hidden. */
@@ -372,6 +373,36 @@ GLX_API int glx_aggregate(const glx_features* f, int op, const int64_t* node_ids
                   const int32_t* segment_ids, int32_t num_ids, int32_t num_segments,
                   float default_attr, float* emb_out, int32_t* cnt_out, int ptr_kind,
                   void* stream);
+
+/* ---- differentiable aggregation: the gradient of glx_aggregate with respect to the table rows.  The reference's
+ * model layers sit on differentiable segment reductions (python/nn/tf/layers/sage_conv.py:69-73: unsorted_segment_sum /
+ * unsorted_segment_mean; gcn_conv.py:73); its operator API (aggregator.cc:25-59) has no backward to mirror. -----------
+ * glx_aggregate_arg: glx_aggregate for GLX_AGG_MAX / GLX_AGG_MIN (any other op: GLX_INVALID_ARGUMENT) that also
+ * records where each extreme came from.  emb_out and cnt_out equal glx_aggregate's bit for bit, for every storage type
+ * and id map of `f`.  arg_out[num_segments * dim]: the request position whose element the fold's select (Max:
+ * (l < r) ? r : l, max_aggregator.cc:26-40) last moved into the accumulator -- the FIRST position that attains the
+ * extreme -- or -1 when nothing replaced the start value (every element <= -37 for Max, an empty segment, a NaN the
+ * comparison never selects).  A default-filled position (unknown id) can be the argument. */
+GLX_API int glx_aggregate_arg(const glx_features* f, int op, const int64_t* node_ids, const int32_t* segment_ids,
+                              int32_t num_ids, int32_t num_segments, float default_attr, float* emb_out,
+                              int32_t* cnt_out, int32_t* arg_out, int ptr_kind, void* stream);
+/* glx_aggregate_backward: grad_x[num_rows * dim] from grad_out[num_segments * dim], for Sum / Mean / Max / Min over a
+ * float32 table with dense ids (GLX_AGG_PROD: GLX_INVALID_ARGUMENT -- its gradient divides by the element).
+ *   rows[num_ids]       the request's ids, i.e. row indices into the [num_rows, dim] table
+ *   cnt[num_segments]   the counts the forward returned: segment s is positions [sum(cnt[:s]), sum(cnt[:s]) + cnt[s]),
+ *                       what the forward's cursor consumed (aggregating_request.cc:86-105); positions from sum(cnt) on
+ *                       give nothing.  NULL: the implied layout, num_segments segments of num_ids / num_segments
+ *                       positions (a remainder gives nothing)
+ *   arg                 Max / Min: what glx_aggregate_arg recorded (NULL: GLX_INVALID_ARGUMENT); ignored otherwise
+ * A position whose row is outside [0, num_rows) contributed the default row and gives nothing.  grad_x[r, c] starts at
+ * +0.0f and adds one float32 term per consumed position p with rows[p] == r, in ascending p: grad_out[s(p), c] (Sum),
+ * grad_out[s(p), c] / float(cnt[s(p)]) (Mean), grad_out[s(p), c] when arg[s(p), c] == p (Max / Min).  EVERY row of
+ * grad_x is written (rows nobody references: zeros); the call overwrites and never accumulates.  No float atomics: the
+ * result is a function of the inputs alone, bit for bit (a stable sort by row, then one lane group per row).
+ * A device-pointer call only enqueues work; the workspace comes from the calling thread's per-(device, stream) cache. */
+GLX_API int glx_aggregate_backward(int device, int op, const int64_t* rows, const int32_t* cnt, const int32_t* arg,
+                                   int32_t num_ids, int32_t num_segments, int64_t num_rows, int32_t dim,
+                                   const float* grad_out, float* grad_x, int ptr_kind, void* stream);
 
 /* ---- negative sampling: replaces RandomNegativeSampler (random_negative_sampler.cc:30-63),
  * InDegreeNegativeSampler / SoftInDegreeNegativeSampler (in_degree_negative_sampler.cc:29-135)
