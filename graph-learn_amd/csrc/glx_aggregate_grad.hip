@@ -19,6 +19,8 @@
 //             lane c owns columns [4c, 4c + 4), the row's list entries are fetched coalesced (G at a time) and handed
 //             round with cross-lane reads, U grad_out row loads are issued before the first is folded.
 // The workspace is the per-(thread, device, stream) arena; nothing is read back on the host between the launches.
+// The transpose (glx_agg_transpose, declared in glx_common.h) also serves the weighted reduce's row gradient
+// (glx_aggregate_weighted.hip).
 #include <string.h>  // rocprim's texture_cache_iterator uses memset
 
 #include <rocprim/rocprim.hpp>
@@ -180,6 +182,80 @@ __global__ __launch_bounds__(256) void glx_bwd_row_ptr_kernel(const uint32_t* __
   row_ptr[r] = lo;
 }
 
+}  // namespace
+
+// The transpose of one request (glx_common.h): keys, stable sort, row_ptr.  One lease of workspace slot 1 holds every
+// piece; it ends with the caller's GlxScratch.
+int glx_agg_transpose(const int64_t* rows, const int32_t* cnt, int32_t n, int32_t num_segments, int64_t num_rows,
+                      hipStream_t s, GlxScratch* lease, GlxAggTranspose* out) {
+  int bits = 1;
+  while (bits < 32 && ((uint64_t)1 << bits) <= (uint64_t)num_rows) ++bits;  // the sentinel key num_rows fits
+  const bool ragged = cnt != nullptr;
+  uint32_t* const no_keys = nullptr;
+  int32_t* const no_vals = nullptr;
+  size_t sort_tmp = 0, scan_tmp = 0;
+  GLX_HIP(rocprim::radix_sort_pairs(nullptr, sort_tmp, no_keys, no_keys, no_vals, no_vals, (size_t)n, 0, bits, s));
+  if (ragged) {
+    GLX_HIP(rocprim::inclusive_scan(nullptr, scan_tmp, rocprim::make_transform_iterator(cnt, ClampCount()),
+                                    static_cast<int64_t*>(nullptr), (size_t)num_segments, rocprim::plus<int64_t>(), s));
+  }
+  const size_t tmp_b = align256(sort_tmp > scan_tmp ? sort_tmp : scan_tmp);
+  const size_t ids_b = align256((size_t)n * sizeof(int32_t));
+  const size_t end_b = ragged ? align256((size_t)num_segments * sizeof(int64_t)) : 0;
+  const size_t ptr_b = align256((size_t)(num_rows + 1) * sizeof(int32_t));
+  int rc = lease->alloc(tmp_b + (ragged ? 5 : 4) * ids_b + end_b + ptr_b, s, 1);
+  if (rc != GLX_OK) return rc;
+  char* at = lease->as<char>();
+  void* tmp = at;
+  at += tmp_b;
+  uint32_t* keys = reinterpret_cast<uint32_t*>(at);
+  uint32_t* keys_s = reinterpret_cast<uint32_t*>(at + ids_b);
+  int32_t* vals = reinterpret_cast<int32_t*>(at + 2 * ids_b);
+  int32_t* vals_s = reinterpret_cast<int32_t*>(at + 3 * ids_b);
+  at += 4 * ids_b;
+  int32_t* seg_of = nullptr;
+  int64_t* seg_end = nullptr;
+  if (ragged) {
+    seg_of = reinterpret_cast<int32_t*>(at);
+    seg_end = reinterpret_cast<int64_t*>(at + ids_b);
+    at += ids_b + end_b;
+  }
+  int32_t* row_ptr = reinterpret_cast<int32_t*>(at);
+  if (ragged) {
+    GLX_HIP(rocprim::inclusive_scan(tmp, scan_tmp, rocprim::make_transform_iterator(cnt, ClampCount()), seg_end,
+                                    (size_t)num_segments, rocprim::plus<int64_t>(), s));
+  }
+  const int32_t fanout = n / num_segments;
+  glx_bwd_keys_kernel<<<(unsigned)(((int64_t)n + 255) / 256), 256, 0, s>>>(rows, n, num_rows, seg_end, num_segments, fanout,
+                                                                         keys, vals, seg_of);
+  GLX_HIP(rocprim::radix_sort_pairs(tmp, sort_tmp, keys, keys_s, vals, vals_s, (size_t)n, 0, bits, s));
+  glx_bwd_row_ptr_kernel<<<(unsigned)((num_rows + 1 + 255) / 256), 256, 0, s>>>(keys_s, n, num_rows, row_ptr);
+  out->row_ptr = row_ptr;
+  out->pos = vals_s;
+  out->seg_of = seg_of;
+  out->seg_end = seg_end;
+  out->fanout = fanout > 0 ? fanout : 1;  // fanout == 0 consumes nothing: every list is empty, nothing divides by it
+  return GLX_OK;
+}
+
+// Inclusive prefix sums of the clamped counts (the segment ends of a ragged request), in a lease of workspace slot 1.
+int glx_agg_segment_ends(const int32_t* cnt, int32_t num_segments, hipStream_t s, GlxScratch* lease,
+                         const int64_t** seg_end) {
+  size_t scan_tmp = 0;
+  GLX_HIP(rocprim::inclusive_scan(nullptr, scan_tmp, rocprim::make_transform_iterator(cnt, ClampCount()),
+                                  static_cast<int64_t*>(nullptr), (size_t)num_segments, rocprim::plus<int64_t>(), s));
+  const size_t tmp_b = align256(scan_tmp);
+  int rc = lease->alloc(tmp_b + (size_t)num_segments * sizeof(int64_t), s, 1);
+  if (rc != GLX_OK) return rc;
+  int64_t* ends = reinterpret_cast<int64_t*>(lease->as<char>() + tmp_b);
+  GLX_HIP(rocprim::inclusive_scan(lease->p, scan_tmp, rocprim::make_transform_iterator(cnt, ClampCount()), ends,
+                                  (size_t)num_segments, rocprim::plus<int64_t>(), s));
+  *seg_end = ends;
+  return GLX_OK;
+}
+
+namespace {
+
 // ---- backward: reduce --------------------------------------------------------------------------------------
 struct BwdArgs {
   const int32_t* row_ptr;  // [num_rows + 1] into pos
@@ -294,60 +370,21 @@ void launch_bwd(const BwdArgs& a, hipStream_t s) {
 // Device pointers only, device selected; num_ids, num_segments, num_rows >= 1.
 int backward_device(int op, const int64_t* rows, const int32_t* cnt, const int32_t* arg, int32_t n, int32_t num_segments,
                     int64_t num_rows, int32_t dim, const float* grad_out, float* grad_x, hipStream_t s) {
-  int bits = 1;
-  while (bits < 32 && ((uint64_t)1 << bits) <= (uint64_t)num_rows) ++bits;  // the sentinel key num_rows fits
-  const bool ragged = cnt != nullptr;
-  uint32_t* const no_keys = nullptr;
-  int32_t* const no_vals = nullptr;
-  size_t sort_tmp = 0, scan_tmp = 0;
-  GLX_HIP(rocprim::radix_sort_pairs(nullptr, sort_tmp, no_keys, no_keys, no_vals, no_vals, (size_t)n, 0, bits, s));
-  if (ragged) {
-    GLX_HIP(rocprim::inclusive_scan(nullptr, scan_tmp, rocprim::make_transform_iterator(cnt, ClampCount()),
-                                    static_cast<int64_t*>(nullptr), (size_t)num_segments, rocprim::plus<int64_t>(), s));
-  }
-  const size_t tmp_b = align256(sort_tmp > scan_tmp ? sort_tmp : scan_tmp);
-  const size_t ids_b = align256((size_t)n * sizeof(int32_t));
-  const size_t end_b = ragged ? align256((size_t)num_segments * sizeof(int64_t)) : 0;
-  const size_t ptr_b = align256((size_t)(num_rows + 1) * sizeof(int32_t));
   GlxScratch lease;
-  int rc = lease.alloc(tmp_b + (ragged ? 5 : 4) * ids_b + end_b + ptr_b, s, 1);
+  GlxAggTranspose t;
+  int rc = glx_agg_transpose(rows, cnt, n, num_segments, num_rows, s, &lease, &t);
   if (rc != GLX_OK) return rc;
-  char* at = lease.as<char>();
-  void* tmp = at;
-  at += tmp_b;
-  uint32_t* keys = reinterpret_cast<uint32_t*>(at);
-  uint32_t* keys_s = reinterpret_cast<uint32_t*>(at + ids_b);
-  int32_t* vals = reinterpret_cast<int32_t*>(at + 2 * ids_b);
-  int32_t* vals_s = reinterpret_cast<int32_t*>(at + 3 * ids_b);
-  at += 4 * ids_b;
-  int32_t* seg_of = nullptr;
-  int64_t* seg_end = nullptr;
-  if (ragged) {
-    seg_of = reinterpret_cast<int32_t*>(at);
-    seg_end = reinterpret_cast<int64_t*>(at + ids_b);
-    at += ids_b + end_b;
-  }
-  int32_t* row_ptr = reinterpret_cast<int32_t*>(at);
-  if (ragged) {
-    GLX_HIP(rocprim::inclusive_scan(tmp, scan_tmp, rocprim::make_transform_iterator(cnt, ClampCount()), seg_end,
-                                    (size_t)num_segments, rocprim::plus<int64_t>(), s));
-  }
-  const int32_t fanout = n / num_segments;
-  glx_bwd_keys_kernel<<<(unsigned)(((int64_t)n + 255) / 256), 256, 0, s>>>(rows, n, num_rows, seg_end, num_segments, fanout,
-                                                                         keys, vals, seg_of);
-  GLX_HIP(rocprim::radix_sort_pairs(tmp, sort_tmp, keys, keys_s, vals, vals_s, (size_t)n, 0, bits, s));
-  glx_bwd_row_ptr_kernel<<<(unsigned)((num_rows + 1 + 255) / 256), 256, 0, s>>>(keys_s, n, num_rows, row_ptr);
   BwdArgs a;
-  a.row_ptr = row_ptr;
-  a.pos = vals_s;
-  a.seg_of = seg_of;
+  a.row_ptr = t.row_ptr;
+  a.pos = t.pos;
+  a.seg_of = t.seg_of;
   a.cnt = cnt;
   a.arg = arg;
   a.grad_out = grad_out;
   a.grad_x = grad_x;
   a.num_rows = num_rows;
   a.dim = dim;
-  a.fanout = fanout > 0 ? fanout : 1;  // fanout == 0 consumes nothing: every list is empty, nothing divides by it
+  a.fanout = t.fanout;
   switch (op) {
     case GLX_AGG_SUM: launch_bwd<GLX_AGG_SUM>(a, s); break;
     case GLX_AGG_MEAN: launch_bwd<GLX_AGG_MEAN>(a, s); break;

@@ -1,0 +1,551 @@
+// glx weighted segment aggregation: a per-position, optionally multi-head, weighted Sum / Mean over segments of
+// gathered rows, with its gradients with respect to the rows and to the weights.  The reference's GCN layer scales every
+// neighbour row by an edge coefficient before the segment sum (graphlearn/python/nn/tf/layers/gcn_conv.py:52-73), its
+// GAT layers by a learned per-head attention coefficient (gat_conv.py:96-110, ego_gat_conv.py:98-103).
+//
+// Contract (include/glx.h).  x[num_rows, dim] float32, rows[num_ids] int64, w[num_ids, heads]
+// float32, C = dim / heads, column c belongs to head c / C.  Segments as in glx_aggregate_backward: the prefix sums of
+// the clamped cnt, or the implied layout of num_ids / num_segments positions each.  A row outside [0, num_rows) reads a
+// row of default_attr.
+//   forward      acc = +0.0f; for each position p of the segment in ascending order
+//                acc = fadd_rn(acc, fmul_rn(w[p, head(c)], xrow(p)[c])); Mean: acc / float(count); empty: default_attr
+//   grad_x       grad_x[r, c] = +0.0f, then for each consumed p with rows[p] == r in ascending p
+//                fadd_rn(., fmul_rn(w[p, head(c)], t)), t = grad_out[s(p), c] (Sum) or grad_out[s(p), c] / float(count)
+//   grad_w       grad_w[p, h] = sum over the columns of head h of grad_out[s(p), c] * xrow(p)[c] (Mean: / float(count));
+//                a fixed lane-to-column mapping and a fixed cross-lane tree -- the same bits on every run, but the order
+//                over the columns is the mapping's, so this one is checked against a bound, not bit for bit
+// No float atomics anywhere.
+#include "glx_common.h"
+
+// Two roundings per term: the multiply must never contract into the add, whatever -ffp-contract the build passes.
+// Neither __fmul_rn / __fadd_rn (plain `x * y` / `x + y` in this toolchain's headers, parsed before any pragma here)
+// nor `#pragma clang fp contract(off)` alone guarantees that: an explicit -ffp-contract=fast lets the backend fuse any
+// multiply with any add.  So the product goes through an empty asm that pins it in a register: the add that follows
+// takes an opaque operand and cannot become an FMA under any flag.  The pragma stays for the front end.
+#pragma clang fp contract(off)
+
+namespace {
+
+__device__ __forceinline__ float fold_rn(float acc, float w, float x) {
+  float t = w * x;        // rounded
+  asm("" : "+v"(t));      // opaque to the optimiser: no instruction, no contraction
+  return acc + t;         // rounded again
+}
+
+constexpr int kWU = 4;  // row loads in flight per lane
+
+// Positions of segment sg that the request really has: cnt[sg] clamped at 0 and, when the counts promise more than
+// num_ids positions, cut at num_ids -- Mean's divisor and the test for "empty" in all three kernels.  seg_end: the
+// inclusive prefix sums of the clamped counts, or nullptr for the implied layout (fanout positions each).
+__device__ __forceinline__ int32_t consumed_count(const int64_t* __restrict__ seg_end, int32_t sg, int32_t num_ids,
+                                                  int32_t fanout) {
+  if (seg_end == nullptr) return fanout;
+  int64_t b0 = sg ? seg_end[sg - 1] : 0, b1 = seg_end[sg];
+  if (b0 > num_ids) b0 = num_ids;
+  if (b1 > num_ids) b1 = num_ids;
+  return (int32_t)(b1 - b0);
+}
+
+const char* w_op_name(int op) {
+  static const char* const kNames[] = {"Sum", "Mean", "Max", "Min", "Prod"};
+  return kNames[op];
+}
+
+// ---- forward -----------------------------------------------------------------------------------------------
+struct WFwdArgs {
+  const float* x;          // [num_rows, dim]
+  const int64_t* rows;     // [num_ids]
+  const float* w;          // [num_ids, heads]
+  const int64_t* seg_end;  // [num_segments] inclusive prefix sums of the clamped counts, or nullptr: the implied layout
+  const int32_t* cnt;      // [num_segments], or nullptr
+  float* emb;              // [num_segments, dim]
+  int64_t num_rows;
+  int32_t dim, heads, C, fanout, num_ids, num_segments;
+  float default_attr;
+};
+
+// G lanes own one segment; lane c owns columns [VEC c, VEC c + VEC) of each column tile of G * VEC columns (VEC = 4
+// only when C % 4 == 0: a lane's columns then share one head).  Lane c fetches position base + c of the segment (its
+// row, already tested against [0, num_rows)) and every lane of the group reads entry j from lane j; kWU row loads and
+// their weights are issued before the first is folded.  The group walks its segment together, so the cross-lane reads
+// stay inside a group whose lanes all run the same iterations.
+template <int OP, int G, int VEC>
+__global__ __launch_bounds__(256) void glx_aggregate_weighted_kernel(WFwdArgs a) {
+  typedef float vec_t __attribute__((ext_vector_type(VEC)));
+  const int64_t gid = blockIdx.x * (int64_t)(256 / G) + threadIdx.x / G;
+  const int c = threadIdx.x & (G - 1);
+  if (gid >= a.num_segments) return;  // whole groups leave
+  int64_t b0, b1;
+  if (a.seg_end) {
+    b0 = gid ? a.seg_end[gid - 1] : 0;
+    b1 = a.seg_end[gid];
+  } else {
+    b0 = gid * (int64_t)a.fanout;
+    b1 = b0 + a.fanout;
+  }
+  if (b0 > a.num_ids) b0 = a.num_ids;  // a cnt that promises more positions than the request has reads none of them
+  if (b1 > a.num_ids) b1 = a.num_ids;
+  const int32_t s0 = (int32_t)b0, s1 = (int32_t)b1;
+  float* const out = a.emb + gid * (int64_t)a.dim;
+  for (int32_t col_pass = 0; col_pass < a.dim; col_pass += G * VEC) {
+    const int32_t col = col_pass + c * VEC;
+    const bool col_ok = col < a.dim;
+    const int32_t col_ld = col_ok ? col : 0;  // lanes past the end re-read the first columns, unused
+    const int32_t head = col_ld / a.C;
+    vec_t acc;
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) acc[v] = 0.0f;
+    for (int32_t base = s0; base < s1; base += G) {
+      int32_t my_row = -1;
+      if (base + c < s1) {
+        const int64_t r = a.rows[base + c];
+        my_row = (r >= 0 && r < a.num_rows) ? (int32_t)r : -1;
+      }
+      const int32_t m = (s1 - base) < G ? (s1 - base) : G;
+      for (int32_t j = 0; j < m; j += kWU) {
+        int32_t row[kWU];
+#pragma unroll
+        for (int u = 0; u < kWU; ++u) row[u] = __shfl(my_row, (j + u) & (G - 1), G);
+        vec_t val[kWU];
+        float wt[kWU];
+#pragma unroll
+        for (int u = 0; u < kWU; ++u) {
+          if (j + u < m) {
+            wt[u] = a.w[(int64_t)(base + j + u) * a.heads + head];
+            if (row[u] >= 0) {
+              val[u] = *reinterpret_cast<const vec_t*>(a.x + row[u] * (int64_t)a.dim + col_ld);
+            } else {
+#pragma unroll
+              for (int v = 0; v < VEC; ++v) val[u][v] = a.default_attr;
+            }
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < kWU; ++u) {
+          if (j + u < m) {
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) acc[v] = fold_rn(acc[v], wt[u], val[u][v]);
+          }
+        }
+      }
+    }
+    if (s1 == s0) {  // FinalFunc: aggregator.cc:74-86 (empty -> default)
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) acc[v] = a.default_attr;
+    } else if (OP == GLX_AGG_MEAN) {
+      const float fn = (float)(s1 - s0);  // the positions consumed
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) acc[v] = acc[v] / fn;
+    }
+    if (col_ok) *reinterpret_cast<vec_t*>(out + col) = acc;
+  }
+}
+
+// the smallest group of 8 .. 64 lanes that covers `lanes`
+int group_for(int lanes) { return lanes <= 8 ? 8 : lanes <= 16 ? 16 : lanes <= 32 ? 32 : 64; }
+
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+template <int OP, int VEC>
+void launch_wfwd_vec(const WFwdArgs& a, hipStream_t s) {
+  const int G = group_for((a.dim + VEC - 1) / VEC);
+  const unsigned blocks = (unsigned)(((int64_t)a.num_segments + (256 / G) - 1) / (256 / G));
+  switch (G) {
+    case 8: glx_aggregate_weighted_kernel<OP, 8, VEC><<<blocks, 256, 0, s>>>(a); break;
+    case 16: glx_aggregate_weighted_kernel<OP, 16, VEC><<<blocks, 256, 0, s>>>(a); break;
+    case 32: glx_aggregate_weighted_kernel<OP, 32, VEC><<<blocks, 256, 0, s>>>(a); break;
+    default: glx_aggregate_weighted_kernel<OP, 64, VEC><<<blocks, 256, 0, s>>>(a); break;
+  }
+}
+
+template <int OP>
+void launch_wfwd(const WFwdArgs& a, hipStream_t s) {
+  const bool vec4 = a.dim % 4 == 0 && a.C % 4 == 0 && aligned16(a.x) && aligned16(a.emb);
+  if (vec4) launch_wfwd_vec<OP, 4>(a, s);
+  else launch_wfwd_vec<OP, 1>(a, s);
+}
+
+// ---- gradient with respect to the rows ------------------------------------------------------------------------
+struct WBwdXArgs {
+  GlxAggTranspose t;
+  const float* w;         // [num_ids, heads]
+  const float* grad_out;  // [num_segments, dim]
+  float* grad_x;          // [num_rows, dim]
+  int64_t num_rows;
+  int32_t dim, heads, C, num_ids;
+};
+
+// The sibling of glx_aggregate_bwd_kernel (glx_aggregate_grad.hip) that also fetches the weight of each list entry:
+// G lanes own table row r, lane c fetches list entry base + c (its position, that position's segment and, for Mean,
+// the divisor), every lane reads entry j from lane j.  Every row is written, an empty list writes zeros.
+template <int OP, int G, int VEC>
+__global__ __launch_bounds__(256) void glx_aggregate_weighted_bwd_x_kernel(WBwdXArgs a) {
+  typedef float vec_t __attribute__((ext_vector_type(VEC)));
+  const int64_t r = blockIdx.x * (int64_t)(256 / G) + threadIdx.x / G;
+  const int c = threadIdx.x & (G - 1);
+  if (r >= a.num_rows) return;  // whole groups leave
+  const int32_t l0 = a.t.row_ptr[r], l1 = a.t.row_ptr[r + 1];
+  float* const out = a.grad_x + r * (int64_t)a.dim;
+  for (int32_t col_pass = 0; col_pass < a.dim; col_pass += G * VEC) {
+    const int32_t col = col_pass + c * VEC;
+    const bool col_ok = col < a.dim;
+    const int32_t col_ld = col_ok ? col : 0;  // lanes past the end re-read the first columns, unused
+    const int32_t head = col_ld / a.C;
+    vec_t acc;
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) acc[v] = 0.0f;
+    for (int32_t base = l0; base < l1; base += G) {
+      int32_t my_pos = 0, my_seg = 0;
+      float my_div = 1.0f;
+      if (base + c < l1) {
+        my_pos = a.t.pos[base + c];
+        my_seg = a.t.seg_of ? a.t.seg_of[my_pos] : my_pos / a.t.fanout;
+        if (OP == GLX_AGG_MEAN) my_div = (float)consumed_count(a.t.seg_end, my_seg, a.num_ids, a.t.fanout);
+      }
+      const int32_t m = (l1 - base) < G ? (l1 - base) : G;
+      for (int32_t j = 0; j < m; j += kWU) {
+        int64_t at[kWU], wat[kWU];
+        float dv[kWU];
+#pragma unroll
+        for (int u = 0; u < kWU; ++u) {
+          const int src = (j + u) & (G - 1);
+          wat[u] = (int64_t)__shfl(my_pos, src, G) * a.heads + head;
+          at[u] = (int64_t)__shfl(my_seg, src, G) * a.dim + col_ld;
+          dv[u] = OP == GLX_AGG_MEAN ? __shfl(my_div, src, G) : 1.0f;
+        }
+        vec_t g[kWU];
+        float wt[kWU];
+#pragma unroll
+        for (int u = 0; u < kWU; ++u) {
+          if (j + u < m) {
+            g[u] = *reinterpret_cast<const vec_t*>(a.grad_out + at[u]);
+            wt[u] = a.w[wat[u]];
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < kWU; ++u) {
+          if (j + u < m) {
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) {
+              const float t = OP == GLX_AGG_MEAN ? g[u][v] / dv[u] : g[u][v];
+              acc[v] = fold_rn(acc[v], wt[u], t);
+            }
+          }
+        }
+      }
+    }
+    if (col_ok) *reinterpret_cast<vec_t*>(out + col) = acc;
+  }
+}
+
+template <int OP, int VEC>
+void launch_wbwd_x_vec(const WBwdXArgs& a, hipStream_t s) {
+  const int G = group_for((a.dim + VEC - 1) / VEC);
+  const unsigned blocks = (unsigned)((a.num_rows + (256 / G) - 1) / (256 / G));
+  switch (G) {
+    case 8: glx_aggregate_weighted_bwd_x_kernel<OP, 8, VEC><<<blocks, 256, 0, s>>>(a); break;
+    case 16: glx_aggregate_weighted_bwd_x_kernel<OP, 16, VEC><<<blocks, 256, 0, s>>>(a); break;
+    case 32: glx_aggregate_weighted_bwd_x_kernel<OP, 32, VEC><<<blocks, 256, 0, s>>>(a); break;
+    default: glx_aggregate_weighted_bwd_x_kernel<OP, 64, VEC><<<blocks, 256, 0, s>>>(a); break;
+  }
+}
+
+template <int OP>
+void launch_wbwd_x(const WBwdXArgs& a, hipStream_t s) {
+  const bool vec4 = a.dim % 4 == 0 && a.C % 4 == 0 && aligned16(a.grad_out) && aligned16(a.grad_x);
+  if (vec4) launch_wbwd_x_vec<OP, 4>(a, s);
+  else launch_wbwd_x_vec<OP, 1>(a, s);
+}
+
+// ---- gradient with respect to the weights ---------------------------------------------------------------------
+struct WBwdWArgs {
+  const float* x;          // [num_rows, dim]
+  const int64_t* rows;     // [num_ids]
+  const int64_t* seg_end;  // [num_segments], or nullptr: the implied layout
+  const int32_t* cnt;      // [num_segments], or nullptr
+  const float* grad_out;   // [num_segments, dim]
+  float* grad_w;           // [num_ids, heads]
+  int64_t num_rows;
+  int32_t dim, heads, C, fanout, num_ids, num_segments;
+  int32_t sub;    // SUB: lanes of a sub-group (min(C / VEC, G))
+  int32_t steps;  // SUB: column tiles a head spans (C / VEC / G, at least 1)
+  float default_attr;
+};
+
+// G lanes own one POSITION p and write grad_w[p, 0 .. heads).  The lane-to-column mapping and the cross-lane tree are
+// fixed by (dim, heads, alignment) alone, so the same inputs give the same bits on every run.
+//   SUB  (L = C / VEC is a power of two)  lane c owns columns [VEC c, VEC c + VEC) of each tile of G * VEC columns; a
+//        head is a sub-group of min(L, G) consecutive lanes (times L / G tiles when L > G), reduced with __shfl_xor over
+//        the sub-group; its first lane writes.
+//   !SUB a loop over the heads: lane c owns elements c, c + G, .. of the head's L vectors, the whole group reduces,
+//        lane 0 writes.
+// A position that was not consumed writes +0.0f; an out-of-range row multiplies a row of default_attr.
+template <int OP, int G, int VEC, bool SUB>
+__global__ __launch_bounds__(256) void glx_aggregate_weighted_bwd_w_kernel(WBwdWArgs a) {
+  typedef float vec_t __attribute__((ext_vector_type(VEC)));
+  const int64_t p = blockIdx.x * (int64_t)(256 / G) + threadIdx.x / G;
+  const int c = threadIdx.x & (G - 1);
+  if (p >= a.num_ids) return;  // whole groups leave
+  float* const out = a.grad_w + p * (int64_t)a.heads;
+  bool consumed;
+  int32_t sg = 0;
+  if (a.seg_end) {
+    consumed = p < a.seg_end[a.num_segments - 1];
+    if (consumed) {  // the first segment whose end lies beyond p
+      int32_t lo = 0, hi = a.num_segments - 1;
+      while (lo < hi) {
+        const int32_t mid = lo + ((hi - lo) >> 1);
+        if (a.seg_end[mid] > p) hi = mid; else lo = mid + 1;
+      }
+      sg = lo;
+    }
+  } else {
+    consumed = a.fanout > 0 && p / a.fanout < a.num_segments;
+    if (consumed) sg = (int32_t)(p / a.fanout);
+  }
+  if (!consumed) {  // the same answer in every lane of the group
+    for (int32_t h = c; h < a.heads; h += G) out[h] = 0.0f;
+    return;
+  }
+  const float div = OP == GLX_AGG_MEAN ? (float)consumed_count(a.seg_end, sg, a.num_ids, a.fanout) : 1.0f;
+  const int64_t r = a.rows[p];
+  const bool in = r >= 0 && r < a.num_rows;
+  const float* const xr = a.x + (in ? r : 0) * (int64_t)a.dim;
+  const float* const go = a.grad_out + sg * (int64_t)a.dim;
+  if (SUB) {
+    const int32_t span = G * VEC * a.steps;  // columns per reduce: G / sub whole heads, or one
+    for (int32_t col_pass = 0; col_pass < a.dim; col_pass += span) {
+      float part = 0.0f;
+      for (int32_t k = 0; k < a.steps; ++k) {
+        const int32_t col = col_pass + (k * G + c) * VEC;
+        if (col < a.dim) {
+          const vec_t g = *reinterpret_cast<const vec_t*>(go + col);
+          vec_t xv;
+          if (in) {
+            xv = *reinterpret_cast<const vec_t*>(xr + col);
+          } else {
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) xv[v] = a.default_attr;
+          }
+#pragma unroll
+          for (int v = 0; v < VEC; ++v) part += g[v] * xv[v];
+        }
+      }
+      for (int off = a.sub >> 1; off > 0; off >>= 1) part += __shfl_xor(part, off, G);
+      const int32_t col0 = col_pass + c * VEC;
+      if ((c & (a.sub - 1)) == 0 && col0 < a.dim) out[col0 / a.C] = OP == GLX_AGG_MEAN ? part / div : part;
+    }
+  } else {
+    const int32_t L = a.C / VEC;
+    for (int32_t h = 0; h < a.heads; ++h) {
+      float part = 0.0f;
+      for (int32_t i = c; i < L; i += G) {
+        const int32_t col = h * a.C + i * VEC;
+        const vec_t g = *reinterpret_cast<const vec_t*>(go + col);
+        vec_t xv;
+        if (in) {
+          xv = *reinterpret_cast<const vec_t*>(xr + col);
+        } else {
+#pragma unroll
+          for (int v = 0; v < VEC; ++v) xv[v] = a.default_attr;
+        }
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) part += g[v] * xv[v];
+      }
+#pragma unroll
+      for (int off = G >> 1; off > 0; off >>= 1) part += __shfl_xor(part, off, G);
+      if (c == 0) out[h] = OP == GLX_AGG_MEAN ? part / div : part;
+    }
+  }
+}
+
+template <int OP, int VEC, bool SUB>
+void launch_wbwd_w_g(WBwdWArgs a, int lanes, hipStream_t s) {
+  const int G = group_for(lanes);
+  if (SUB) {
+    const int L = a.C / VEC;
+    a.sub = L < G ? L : G;
+    a.steps = L > G ? L / G : 1;
+  }
+  const unsigned blocks = (unsigned)(((int64_t)a.num_ids + (256 / G) - 1) / (256 / G));
+  switch (G) {
+    case 8: glx_aggregate_weighted_bwd_w_kernel<OP, 8, VEC, SUB><<<blocks, 256, 0, s>>>(a); break;
+    case 16: glx_aggregate_weighted_bwd_w_kernel<OP, 16, VEC, SUB><<<blocks, 256, 0, s>>>(a); break;
+    case 32: glx_aggregate_weighted_bwd_w_kernel<OP, 32, VEC, SUB><<<blocks, 256, 0, s>>>(a); break;
+    default: glx_aggregate_weighted_bwd_w_kernel<OP, 64, VEC, SUB><<<blocks, 256, 0, s>>>(a); break;
+  }
+}
+
+template <int OP, int VEC>
+void launch_wbwd_w_vec(const WBwdWArgs& a, hipStream_t s) {
+  const int L = a.C / VEC;
+  // sub-groups tile the row: the group covers all of it (up to 64 lanes); a loop over heads: the group covers one head
+  if ((L & (L - 1)) == 0) launch_wbwd_w_g<OP, VEC, true>(a, a.dim / VEC, s);
+  else launch_wbwd_w_g<OP, VEC, false>(a, L, s);
+}
+
+template <int OP>
+void launch_wbwd_w(const WBwdWArgs& a, hipStream_t s) {
+  const bool vec4 = a.dim % 4 == 0 && a.C % 4 == 0 && aligned16(a.x) && aligned16(a.grad_out);
+  if (vec4) launch_wbwd_w_vec<OP, 4>(a, s);
+  else launch_wbwd_w_vec<OP, 1>(a, s);
+}
+
+int zero_async(float* p, size_t count, hipStream_t s) {
+  hipError_t e = hipMemsetAsync(p, 0, count * sizeof(float), s);
+  if (e != hipSuccess) {
+    glx_set_error("hipMemsetAsync failed: %s", hipGetErrorString(e));
+    return GLX_INTERNAL;
+  }
+  return GLX_OK;
+}
+
+}  // namespace
+
+// what the three entry points check alike, before any device use
+#define GLX_WEIGHTED_REQUIRE(who)                                                                                       \
+  GLX_REQUIRE(op >= GLX_AGG_SUM && op <= GLX_AGG_PROD, "unknown aggregator id %d", op);                                 \
+  GLX_REQUIRE(op == GLX_AGG_SUM || op == GLX_AGG_MEAN, who " reduces with Sum or Mean only, not with %s",               \
+              w_op_name(op));                                                                                           \
+  GLX_REQUIRE(num_ids >= 0 && num_segments >= 0 && num_rows >= 0, "negative sizes");                                    \
+  GLX_REQUIRE(dim > 0, "dim must be positive, got %d", dim);                                                            \
+  GLX_REQUIRE(heads > 0, "heads must be positive, got %d", heads);                                                      \
+  GLX_REQUIRE(dim % heads == 0, "dim %d is not a multiple of heads %d", dim, heads);                                    \
+  GLX_REQUIRE(num_rows < INT32_MAX, "num_rows must be < 2^31");                                                         \
+  GLX_REQUIRE((int64_t)num_ids * heads <= INT32_MAX, "num_ids * heads exceeds int32");                                  \
+  GLX_REQUIRE((int64_t)num_segments * dim <= INT32_MAX, "num_segments * dim exceeds int32 (tensor.h:47)");              \
+  GLX_REQUIRE(ptr_kind == GLX_PTR_HOST || ptr_kind == GLX_PTR_DEVICE, "bad ptr_kind")
+
+extern "C" int glx_aggregate_weighted(int device, int op, const float* x, int64_t num_rows, int32_t dim,
+                                      const int64_t* rows, const float* w, int32_t heads, const int32_t* cnt,
+                                      int32_t num_ids, int32_t num_segments, float default_attr, float* emb_out,
+                                      int ptr_kind, void* stream) {
+  GLX_WEIGHTED_REQUIRE("glx_aggregate_weighted");
+  GLX_REQUIRE(num_rows == 0 || x != nullptr, "x is NULL");
+  GLX_REQUIRE(num_ids == 0 || rows != nullptr, "rows is NULL");
+  GLX_REQUIRE(num_ids == 0 || w != nullptr, "w is NULL");
+  GLX_REQUIRE(num_segments == 0 || emb_out != nullptr, "emb_out is NULL");
+  int rc = glx_init_device(device);
+  if (rc != GLX_OK) return rc;
+  if (num_segments == 0) return GLX_OK;
+  GlxDeviceGuard guard(device);
+  GLX_REQUIRE(guard.ok, "cannot select device %d", device);
+  GlxHostStage st(device, ptr_kind, stream, GlxHostStage::ADMIT);
+  WFwdArgs a;
+  st.in(&a.x, x, (size_t)num_rows * dim);
+  st.in(&a.rows, rows, (size_t)num_ids);
+  st.in(&a.w, w, (size_t)num_ids * heads);
+  st.in(&a.cnt, cnt, (size_t)num_segments);
+  st.out(&a.emb, emb_out, (size_t)num_segments * dim);
+  rc = st.begin();
+  GlxScratch lease;
+  a.seg_end = nullptr;
+  if (rc == GLX_OK && cnt != nullptr) rc = glx_agg_segment_ends(a.cnt, num_segments, st.s, &lease, &a.seg_end);
+  if (rc == GLX_OK) {
+    if (cnt == nullptr) a.cnt = nullptr;
+    a.num_rows = num_rows;
+    a.dim = dim;
+    a.heads = heads;
+    a.C = dim / heads;
+    a.fanout = num_ids / num_segments;
+    a.num_ids = num_ids;
+    a.num_segments = num_segments;
+    a.default_attr = default_attr;
+    if (op == GLX_AGG_SUM) launch_wfwd<GLX_AGG_SUM>(a, st.s);
+    else launch_wfwd<GLX_AGG_MEAN>(a, st.s);
+  }
+  return st.finish(rc);
+}
+
+extern "C" int glx_aggregate_weighted_backward_x(int device, int op, const int64_t* rows, const float* w, int32_t heads,
+                                                 const int32_t* cnt, int32_t num_ids, int32_t num_segments,
+                                                 int64_t num_rows, int32_t dim, const float* grad_out, float* grad_x,
+                                                 int ptr_kind, void* stream) {
+  GLX_WEIGHTED_REQUIRE("glx_aggregate_weighted_backward_x");
+  GLX_REQUIRE(num_ids == 0 || rows != nullptr, "rows is NULL");
+  GLX_REQUIRE(num_ids == 0 || w != nullptr, "w is NULL");
+  GLX_REQUIRE(num_segments == 0 || grad_out != nullptr, "grad_out is NULL");
+  GLX_REQUIRE(num_rows == 0 || grad_x != nullptr, "grad_x is NULL");
+  int rc = glx_init_device(device);
+  if (rc != GLX_OK) return rc;
+  if (num_rows == 0) return GLX_OK;
+  GlxDeviceGuard guard(device);
+  GLX_REQUIRE(guard.ok, "cannot select device %d", device);
+  GlxHostStage st(device, ptr_kind, stream, GlxHostStage::ADMIT);
+  const int64_t* d_rows;
+  const int32_t* d_cnt;
+  WBwdXArgs a;
+  st.in(&d_rows, rows, (size_t)num_ids);
+  st.in(&a.w, w, (size_t)num_ids * heads);
+  st.in(&d_cnt, cnt, (size_t)num_segments);
+  st.in(&a.grad_out, grad_out, (size_t)num_segments * dim);
+  st.out(&a.grad_x, grad_x, (size_t)num_rows * dim);
+  rc = st.begin();
+  GlxScratch lease;
+  if (rc == GLX_OK) {
+    if (num_ids == 0 || num_segments == 0) {  // nothing was consumed: every row is zeros
+      rc = zero_async(a.grad_x, (size_t)num_rows * dim, st.s);
+    } else {
+      rc = glx_agg_transpose(d_rows, cnt ? d_cnt : nullptr, num_ids, num_segments, num_rows, st.s, &lease, &a.t);
+      if (rc == GLX_OK) {
+        a.num_rows = num_rows;
+        a.dim = dim;
+        a.heads = heads;
+        a.C = dim / heads;
+        a.num_ids = num_ids;
+        if (op == GLX_AGG_SUM) launch_wbwd_x<GLX_AGG_SUM>(a, st.s);
+        else launch_wbwd_x<GLX_AGG_MEAN>(a, st.s);
+      }
+    }
+  }
+  return st.finish(rc);
+}
+
+extern "C" int glx_aggregate_weighted_backward_w(int device, int op, const float* x, int64_t num_rows, int32_t dim,
+                                                 const int64_t* rows, int32_t heads, const int32_t* cnt,
+                                                 int32_t num_ids, int32_t num_segments, float default_attr,
+                                                 const float* grad_out, float* grad_w, int ptr_kind, void* stream) {
+  GLX_WEIGHTED_REQUIRE("glx_aggregate_weighted_backward_w");
+  GLX_REQUIRE(num_rows == 0 || x != nullptr, "x is NULL");
+  GLX_REQUIRE(num_ids == 0 || rows != nullptr, "rows is NULL");
+  GLX_REQUIRE(num_segments == 0 || grad_out != nullptr, "grad_out is NULL");
+  GLX_REQUIRE(num_ids == 0 || grad_w != nullptr, "grad_w is NULL");
+  int rc = glx_init_device(device);
+  if (rc != GLX_OK) return rc;
+  if (num_ids == 0) return GLX_OK;
+  GlxDeviceGuard guard(device);
+  GLX_REQUIRE(guard.ok, "cannot select device %d", device);
+  GlxHostStage st(device, ptr_kind, stream, GlxHostStage::ADMIT);
+  WBwdWArgs a;
+  st.in(&a.x, x, (size_t)num_rows * dim);
+  st.in(&a.rows, rows, (size_t)num_ids);
+  st.in(&a.cnt, cnt, (size_t)num_segments);
+  st.in(&a.grad_out, grad_out, (size_t)num_segments * dim);
+  st.out(&a.grad_w, grad_w, (size_t)num_ids * heads);
+  rc = st.begin();
+  GlxScratch lease;
+  if (rc == GLX_OK) {
+    if (num_segments == 0) {  // nothing was consumed
+      rc = zero_async(a.grad_w, (size_t)num_ids * heads, st.s);
+    } else {
+      a.seg_end = nullptr;
+      if (cnt == nullptr) a.cnt = nullptr;
+      else rc = glx_agg_segment_ends(a.cnt, num_segments, st.s, &lease, &a.seg_end);
+      if (rc == GLX_OK) {
+        a.num_rows = num_rows;
+        a.dim = dim;
+        a.heads = heads;
+        a.C = dim / heads;
+        a.fanout = num_ids / num_segments;
+        a.num_ids = num_ids;
+        a.num_segments = num_segments;
+        a.sub = 1;
+        a.steps = 1;
+        a.default_attr = default_attr;
+        if (op == GLX_AGG_SUM) launch_wbwd_w<GLX_AGG_SUM>(a, st.s);
+        else launch_wbwd_w<GLX_AGG_MEAN>(a, st.s);
+      }
+    }
+  }
+  return st.finish(rc);
+}

@@ -796,6 +796,24 @@ struct GlxSegments {
 int glx_segments_prepare(const int32_t* d_seg, int32_t num_ids, int32_t num_segments, int32_t* scratch, hipStream_t s,
                          GlxSegments* out);
 
+// The transpose of one aggregation request (glx_aggregate_grad.hip), shared by the gradients with respect to the rows:
+// the consumed, in-range positions in a STABLE order by (row, position).  Row r's positions are
+// pos[row_ptr[r] .. row_ptr[r + 1]), ascending.  Everything lives in `lease` (workspace slot 1) and is valid for work
+// queued on `s` until the lease ends.  Device pointers; n, num_segments, num_rows >= 1; cnt may be nullptr (the implied
+// layout of n / num_segments positions per segment).
+struct GlxAggTranspose {
+  const int32_t* row_ptr;  // [num_rows + 1] into pos
+  const int32_t* pos;      // request positions by (row, position)
+  const int32_t* seg_of;   // [n] segment of a position (cnt != nullptr), or nullptr: position / fanout
+  const int64_t* seg_end;  // [num_segments] inclusive prefix sums of the clamped counts (cnt != nullptr), or nullptr
+  int32_t fanout;          // n / num_segments, at least 1
+};
+int glx_agg_transpose(const int64_t* rows, const int32_t* cnt, int32_t n, int32_t num_segments, int64_t num_rows,
+                      hipStream_t s, GlxScratch* lease, GlxAggTranspose* out);
+// seg_end[num_segments]: inclusive prefix sums of the clamped (>= 0) counts, in `lease` (workspace slot 1).
+int glx_agg_segment_ends(const int32_t* cnt, int32_t num_segments, hipStream_t s, GlxScratch* lease,
+                         const int64_t** seg_end);
+
 template <int OP>
 __device__ __forceinline__ float agg_init() {
   if (OP == GLX_AGG_MAX) return (float)FLT_MIN_10_EXP;  // max_aggregator.cc:28 (-37, sic)

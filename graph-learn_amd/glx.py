@@ -46,6 +46,7 @@ EXPORTS = [
     "glx_features_create", "glx_features_view", "glx_features_destroy", "glx_features_info",
     "glx_features_create_ex", "glx_features_view_ex", "glx_features_dtype",
     "glx_aggregate", "glx_lookup", "glx_aggregate_arg", "glx_aggregate_backward",
+    "glx_aggregate_weighted", "glx_aggregate_weighted_backward_x", "glx_aggregate_weighted_backward_w",
     "glx_partition", "glx_stitch_i64", "glx_stitch_f32", "glx_aggregate_stitch",
     "glx_negative_create", "glx_negative_from_graph", "glx_negative_destroy", "glx_negative_info",
     "glx_negative_export", "glx_graph_enable_negative", "glx_negative_sample",
@@ -164,6 +165,9 @@ def lib():
         L.glx_lookup.argtypes = [vp, vp, i64, f32, vp, ci, vp]
         L.glx_aggregate_arg.argtypes = [vp, ci, vp, vp, i32, i32, f32, vp, vp, vp, ci, vp]
         L.glx_aggregate_backward.argtypes = [ci, ci, vp, vp, vp, i32, i32, i64, i32, vp, vp, ci, vp]
+        L.glx_aggregate_weighted.argtypes = [ci, ci, vp, i64, i32, vp, vp, i32, vp, i32, i32, f32, vp, ci, vp]
+        L.glx_aggregate_weighted_backward_x.argtypes = [ci, ci, vp, vp, i32, vp, i32, i32, i64, i32, vp, vp, ci, vp]
+        L.glx_aggregate_weighted_backward_w.argtypes = [ci, ci, vp, i64, i32, vp, i32, vp, i32, i32, f32, vp, vp, ci, vp]
         L.glx_partition.argtypes = [ci, vp, i64, i32, vp, vp, vp, vp]
         L.glx_stitch_i64.argtypes = [ci, vp, vp, i64, i32, vp, vp]
         L.glx_stitch_f32.argtypes = [ci, vp, vp, i64, i32, vp, vp]
@@ -683,6 +687,84 @@ def aggregate_backward(op, rows, cnt, grad_out, num_rows, arg=None, out=None, de
     _check(lib().glx_aggregate_backward(device, op, pr[0], pc[0], pa[0], n, num_segments, num_rows, dim, pg[0], px[0],
                                         kind, _stream(kind, device)))
     return grad_x
+
+
+def _weighted_out(out, like, shape):
+    """the output of a weighted-aggregation call and its device: `out`, or a new buffer of `like`'s kind"""
+    if out is not None:
+        return out
+    if _is_torch(like):
+        import torch
+        return torch.empty(shape, dtype=torch.float32, device=like.device)
+    return np.empty(shape, np.float32)
+
+
+def _weighted_heads(w, n):
+    """heads of a weight buffer w[n] or w[n, heads]"""
+    assert int(w.shape[0]) == n, "one weight row per position"
+    return 1 if len(w.shape) == 1 else int(w.shape[1])
+
+
+def aggregate_weighted(op, x, rows, w, num_segments, cnt=None, default_attr=0.0, out=None, device=0):
+    """Weighted Sum / Mean over segments of gathered rows (glx_aggregate_weighted) -> emb[num_segments, D] float32.
+    x[num_rows, D] float32; rows[n] int64 (a value outside [0, num_rows) reads a row of default_attr); w[n] or
+    w[n, heads] float32, column c belongs to head c // (D // heads); cnt[num_segments] int32 (None: the implied layout
+    of n // num_segments positions per segment).  Every element folds fadd(acc, fmul(w, x)) left to right: bit-exact,
+    and with all-ones weights equal to Features(x, view=True).aggregate.  Max / Min / Prod raise.
+    Torch CUDA tensors are device pointers on the current stream, numpy arrays host pointers."""
+    if isinstance(op, str):
+        op = AGGREGATOR_IDS[op]
+    n = int(rows.shape[0])
+    num_rows, dim = int(x.shape[0]), int(x.shape[1])
+    heads = _weighted_heads(w, n)
+    emb = _weighted_out(out, x, (num_segments, dim))
+    px, pr, pw, pc, pe = _ptr(x), _ptr(rows), _ptr(w), _ptr(cnt), _ptr(emb)
+    kind = _kind(px, pr, pw, pc, pe)
+    if kind == PTR_DEVICE:
+        device = emb.device.index or 0
+    _check(lib().glx_aggregate_weighted(device, op, px[0], num_rows, dim, pr[0], pw[0], heads, pc[0], n, num_segments,
+                                        default_attr, pe[0], kind, _stream(kind, device)))
+    return emb
+
+
+def aggregate_weighted_backward_x(op, rows, w, cnt, grad_out, num_rows, out=None, device=0):
+    """Gradient of aggregate_weighted with respect to the rows (glx_aggregate_weighted_backward_x) ->
+    grad_x[num_rows, D] float32, every row written.  aggregate_backward's contract with one more factor: each element
+    adds fmul(w[p, head], term) in ascending request position, no float atomic: the same bits on every run."""
+    if isinstance(op, str):
+        op = AGGREGATOR_IDS[op]
+    n = int(rows.shape[0])
+    num_segments, dim = int(grad_out.shape[0]), int(grad_out.shape[1])
+    heads = _weighted_heads(w, n)
+    grad_x = _weighted_out(out, grad_out, (num_rows, dim))
+    pr, pw, pc, pg, px = _ptr(rows), _ptr(w), _ptr(cnt), _ptr(grad_out), _ptr(grad_x)
+    kind = _kind(pr, pw, pc, pg, px)
+    if kind == PTR_DEVICE:
+        device = grad_x.device.index or 0
+    _check(lib().glx_aggregate_weighted_backward_x(device, op, pr[0], pw[0], heads, pc[0], n, num_segments, num_rows, dim,
+                                                   pg[0], px[0], kind, _stream(kind, device)))
+    return grad_x
+
+
+def aggregate_weighted_backward_w(op, x, rows, heads, cnt, grad_out, default_attr=0.0, out=None, device=0):
+    """Gradient of aggregate_weighted with respect to the weights (glx_aggregate_weighted_backward_w) ->
+    grad_w[n, heads] float32, every element written (a position that was not consumed: +0.0).  grad_w[p, h] is the dot
+    product of grad_out[s(p)] and the gathered row over the columns of head h (Mean: / count); a fixed lane mapping
+    and reduction tree, no atomics: the same bits on every run, within C * 2^-23 * sum|terms| of the exact value."""
+    if isinstance(op, str):
+        op = AGGREGATOR_IDS[op]
+    n = int(rows.shape[0])
+    num_rows, dim = int(x.shape[0]), int(x.shape[1])
+    num_segments = int(grad_out.shape[0])
+    assert int(grad_out.shape[1]) == dim
+    grad_w = _weighted_out(out, grad_out, (n, heads))
+    px, pr, pc, pg, pw = _ptr(x), _ptr(rows), _ptr(cnt), _ptr(grad_out), _ptr(grad_w)
+    kind = _kind(px, pr, pc, pg, pw)
+    if kind == PTR_DEVICE:
+        device = grad_w.device.index or 0
+    _check(lib().glx_aggregate_weighted_backward_w(device, op, px[0], num_rows, dim, pr[0], heads, pc[0], n, num_segments,
+                                                   default_attr, pg[0], pw[0], kind, _stream(kind, device)))
+    return grad_w
 
 
 COLUMN_NAMES = ("weights", "labels", "timestamps", "int_attrs")

@@ -1,5 +1,6 @@
 """Differentiable segment reductions and row gathers over a device-resident matrix: the torch surface of
-glx_aggregate / glx_aggregate_arg / glx_aggregate_backward (include/glx.h).
+glx_aggregate / glx_aggregate_arg / glx_aggregate_backward and of glx_aggregate_weighted and its two gradients
+(include/glx.h).
 
 The role of tf.math.unsorted_segment_sum / unsorted_segment_mean under the reference's layers
 (graphlearn/python/nn/tf/layers/sage_conv.py:69-73, gcn_conv.py:73), for matrices that are computed on the way --
@@ -11,10 +12,18 @@ The role of tf.math.unsorted_segment_sum / unsorted_segment_mean under the refer
 Neither materialises the [n, D] gather `z[index]`, and neither backward uses a float atomic: every element of x.grad
 adds its terms in ascending request position, so two runs of one batch give the same bits (torch's `z[index]` goes
 backward through index_add_ with float atomics, in whatever order they land).
+
+weighted_segment_aggregate is the reduce under a GCN layer (every neighbour row scaled by an edge coefficient,
+gcn_conv.py:52-73) and a GAT layer (a learned coefficient per neighbour and head, gat_conv.py:96-110):
+
+    alpha = torch.softmax(e.view(S, k, H), dim=1)                      # dense sampler response: plain torch
+    h = weighted_segment_aggregate(z, batch.local[2], alpha.view(S * k, H), num_segments=S, op="sum")
+
+with a gradient for z and for alpha, neither through a float atomic.
 """
 import torch
 
-__all__ = ["segment_aggregate", "gather_rows"]
+__all__ = ["segment_aggregate", "gather_rows", "weighted_segment_aggregate"]
 
 _OPS = {"sum": 0, "mean": 1, "max": 2, "min": 3, "prod": 4}
 
@@ -144,3 +153,79 @@ def gather_rows(x, index, default_attr=0.0):
   shape = tuple(index.shape)
   out = _GatherRows.apply(x, index.reshape(-1).contiguous(), float(default_attr))
   return out.reshape(shape + (int(x.shape[1]),))
+
+
+class _WeightedSegmentAggregate(torch.autograd.Function):
+
+  @staticmethod
+  def forward(ctx, x, index, weights, counts, num_segments, op, default_attr):
+    glx = _glx()
+    xd, wd = x.detach(), weights.detach()
+    emb = glx.aggregate_weighted(op, xd, index, wd, num_segments, cnt=counts, default_attr=default_attr)
+    ctx.op, ctx.default_attr, ctx.has_counts = op, default_attr, counts is not None
+    ctx.save_for_backward(*([xd, index, wd] + ([counts] if counts is not None else [])))
+    return emb
+
+  @staticmethod
+  def backward(ctx, grad):
+    _no_double_backward("weighted_segment_aggregate")
+    glx = _glx()
+    saved = ctx.saved_tensors
+    x, index, w = saved[0], saved[1], saved[2]
+    counts = saved[3] if ctx.has_counts else None
+    grad = grad.to(torch.float32).contiguous()
+    gx = gw = None
+    if ctx.needs_input_grad[0]:
+      gx = glx.aggregate_weighted_backward_x(ctx.op, index, w, counts, grad, int(x.shape[0]))
+    if ctx.needs_input_grad[2]:
+      gw = glx.aggregate_weighted_backward_w(ctx.op, x, index, int(w.shape[1]), counts, grad, ctx.default_attr)
+    return gx, None, gw, None, None, None, None
+
+
+def weighted_segment_aggregate(x, index, weights, num_segments, op="sum", counts=None, default_attr=0.0):
+  """[num_segments, D]: segment s is the weighted "sum" or "mean" of the rows x[index[p]] of its positions p, each row
+  scaled per head by weights[p] before it is added -- fadd(acc, fmul(w, x)) left to right, bit-identical on every run.
+
+  x        [N, D] contiguous float32 CUDA tensor; may require grad
+  index    int64 CUDA tensor of any shape (flattened, n positions): rows of x; a value outside [0, N) reads a row of
+           `default_attr` and passes no gradient to x (its weight still gets one)
+  weights  [n] or [n, H] float32 on x's device, H dividing D: column c of a row is scaled by head c // (D // H); may
+           require grad.  The gradient has the shape of `weights`; each element is a dot product over its head's
+           columns with a fixed summation tree (the same bits on every run, no atomics)
+  counts   None: num_segments equal segments of n / num_segments consecutive positions (a dense sampler response); or
+           an int32 [num_segments] tensor: segment s is the next counts[s] positions, positions from counts.sum() on are
+           ignored and get a zero weight gradient
+  Empty segments are `default_attr` and pass no gradient on.  Anything else raises ValueError.
+  """
+  who = "weighted_segment_aggregate"
+  _check_inputs(x, index, who)
+  if op not in ("sum", "mean"):
+    raise ValueError("{}: op must be 'sum' or 'mean', not {!r} (max / min / prod take no weights)".format(who, op))
+  num_segments = int(num_segments)
+  if num_segments < 0:
+    raise ValueError("{}: num_segments must be >= 0".format(who))
+  index = index.reshape(-1).contiguous()
+  n, D = index.numel(), int(x.shape[1])
+  if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32:
+    raise ValueError("{}: weights must be a float32 tensor".format(who))
+  if weights.device != x.device:
+    raise ValueError("{}: weights live on {}, x on {}".format(who, weights.device, x.device))
+  if weights.dim() not in (1, 2) or weights.shape[0] != n:
+    raise ValueError("{}: weights must be [n] or [n, H] with one row per index ({}), not {}".format(
+        who, n, tuple(weights.shape)))
+  heads = 1 if weights.dim() == 1 else int(weights.shape[1])
+  if heads < 1 or D % heads != 0:
+    raise ValueError("{}: the number of heads ({}) must divide D ({})".format(who, heads, D))
+  if counts is not None:
+    if not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32 or counts.device != x.device:
+      raise ValueError("{}: counts must be an int32 tensor on x's device".format(who))
+    if counts.dim() != 1 or counts.numel() != num_segments:
+      raise ValueError("{}: counts must have one entry per segment".format(who))
+    counts = counts.contiguous()
+  elif num_segments == 0 or n % num_segments != 0:
+    raise ValueError("{}: without counts, index.numel() must be a multiple of num_segments".format(who))
+  if num_segments * D > 2 ** 31 - 1 or n * heads > 2 ** 31 - 1:
+    raise ValueError("{}: num_segments * D or n * H exceeds int32".format(who))
+  out = _WeightedSegmentAggregate.apply(x, index, weights.reshape(n, heads).contiguous(), counts, num_segments,
+                                        _OPS[op], float(default_attr))
+  return out

@@ -39,7 +39,8 @@ extern "C" {
  * feature tables -- GLX_DTYPE_*, glx_features_create_ex, glx_features_view_ex, glx_features_dtype;
  * glx_graph_edge_weight_packed; frontier dedup -- glx_unique; device-resident label / weight / timestamp / int-attribute
  * columns -- glx_columns_create, glx_columns_lookup, glx_columns_info, glx_columns_destroy; differentiable aggregation --
- * glx_aggregate_arg, glx_aggregate_backward. */
+ * glx_aggregate_arg, glx_aggregate_backward; weighted aggregation -- glx_aggregate_weighted,
+ * glx_aggregate_weighted_backward_x, glx_aggregate_weighted_backward_w. */
 #define GLX_ABI_VERSION 5
 
 /* Exported symbols: libglx.so is built with -fvisibility=hidden. */
@@ -403,6 +404,56 @@ GLX_API int glx_aggregate_arg(const glx_features* f, int op, const int64_t* node
 GLX_API int glx_aggregate_backward(int device, int op, const int64_t* rows, const int32_t* cnt, const int32_t* arg,
                                    int32_t num_ids, int32_t num_segments, int64_t num_rows, int32_t dim,
                                    const float* grad_out, float* grad_x, int ptr_kind, void* stream);
+
+/* ---- weighted aggregation: a per-position, optionally multi-head, weighted Sum / Mean over segments of gathered rows,
+ * with both gradients.  The reduce under the reference's GCN layer (python/nn/tf/layers/gcn_conv.py:52-73: every
+ * neighbour row scaled by an edge coefficient before the segment sum) and its GAT layers (gat_conv.py:96-110,
+ * ego_gat_conv.py:98-103: a learned attention coefficient per neighbour and head). ------------------------------------
+ * Common to the three entry points:
+ *   x[num_rows * dim]      float32, row-major; rows are dense indices into it
+ *   rows[num_ids]          int64; a position whose row is outside [0, num_rows) reads a row of default_attr
+ *   w[num_ids * heads]     float32; heads >= 1, dim % heads == 0, C = dim / heads; column c belongs to head c / C
+ *   cnt[num_segments]      segment s is positions [sum(cnt[:s]), sum(cnt[:s]) + cnt[s]) of the counts clamped at 0;
+ *                          positions from sum(cnt) on are not consumed.  Counts that promise more than num_ids
+ *                          positions are cut at num_ids: count(s) below is the number of positions segment s really
+ *                          has (cnt[s] for a well-formed request), and a segment cut to nothing is empty.  NULL: the
+ *                          implied layout, num_segments segments of num_ids / num_segments positions (a remainder is
+ *                          not consumed)
+ *   op                     GLX_AGG_SUM or GLX_AGG_MEAN; Max / Min / Prod: GLX_INVALID_ARGUMENT, the message names the op
+ * Arguments are checked before any device use; num_rows < 2^31, num_ids * heads and num_segments * dim <= INT32_MAX.
+ * A device-pointer call only enqueues work; the workspace comes from the calling thread's per-(device, stream) cache.
+ * No float atomics anywhere.
+ *
+ * glx_aggregate_weighted (bit-exact contract): for segment s and column c the accumulator starts where glx_aggregate's
+ * Sum starts (+0.0f); for each consumed position p of s in ascending order
+ *     acc = fadd_rn(acc, fmul_rn(w[p, head(c)], xrow(p)[c]))
+ * -- two roundings, never contracted into an FMA under any build flag.  Mean then divides by float(count(s)) exactly as
+ * glx_aggregate's Mean
+ * does; an empty segment is default_attr.  With every weight 1.0f and heads == 1 emb_out equals glx_aggregate on a
+ * glx_features_view of x bit for bit (Sum and Mean; signed zeros and non-finite rows included). */
+GLX_API int glx_aggregate_weighted(int device, int op, const float* x, int64_t num_rows, int32_t dim,
+                                   const int64_t* rows, const float* w, int32_t heads, const int32_t* cnt,
+                                   int32_t num_ids, int32_t num_segments, float default_attr, float* emb_out,
+                                   int ptr_kind, void* stream);
+/* glx_aggregate_weighted_backward_x (bit-exact contract): glx_aggregate_backward's contract with one more factor.
+ * grad_x[r, c] starts at +0.0f and, for each consumed position p with rows[p] == r in ascending p, becomes
+ *     fadd_rn(grad_x[r, c], fmul_rn(w[p, head(c)], t)),  t = grad_out[s(p), c] (Sum), grad_out[s(p), c] / float(count(s(p))) (Mean).
+ * EVERY row of grad_x[num_rows * dim] is written; the call overwrites.  (A stable sort by row shared with
+ * glx_aggregate_backward, then one lane group per row.) */
+GLX_API int glx_aggregate_weighted_backward_x(int device, int op, const int64_t* rows, const float* w, int32_t heads,
+                                              const int32_t* cnt, int32_t num_ids, int32_t num_segments,
+                                              int64_t num_rows, int32_t dim, const float* grad_out, float* grad_x,
+                                              int ptr_kind, void* stream);
+/* glx_aggregate_weighted_backward_w (tolerance contract): grad_w[p, h] = sum over the columns c of head h of
+ * grad_out[s(p), c] * xrow(p)[c], divided by float(count(s(p))) for Mean; a position that was not consumed gets +0.0f;
+ * EVERY element of grad_w[num_ids * heads] is written.  One lane group per position with a fixed lane-to-column mapping
+ * and a fixed cross-lane tree: the same inputs give the same bits on every run.  The ORDER of the sum over the columns
+ * is the mapping's and not part of the contract; for any order of a C-term float32 dot product
+ *     |grad_w - exact| <= C * 2^-23 * sum_c |grad_out * x| + 2^-126. */
+GLX_API int glx_aggregate_weighted_backward_w(int device, int op, const float* x, int64_t num_rows, int32_t dim,
+                                              const int64_t* rows, int32_t heads, const int32_t* cnt, int32_t num_ids,
+                                              int32_t num_segments, float default_attr, const float* grad_out,
+                                              float* grad_w, int ptr_kind, void* stream);
 
 /* ---- negative sampling: replaces RandomNegativeSampler (random_negative_sampler.cc:30-63),
  * InDegreeNegativeSampler / SoftInDegreeNegativeSampler (in_degree_negative_sampler.cc:29-135)
