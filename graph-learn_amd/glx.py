@@ -47,6 +47,7 @@ EXPORTS = [
     "glx_features_create_ex", "glx_features_view_ex", "glx_features_dtype",
     "glx_aggregate", "glx_lookup", "glx_aggregate_arg", "glx_aggregate_backward",
     "glx_aggregate_weighted", "glx_aggregate_weighted_backward_x", "glx_aggregate_weighted_backward_w",
+    "glx_segment_softmax", "glx_segment_softmax_backward",
     "glx_partition", "glx_stitch_i64", "glx_stitch_f32", "glx_aggregate_stitch",
     "glx_negative_create", "glx_negative_from_graph", "glx_negative_destroy", "glx_negative_info",
     "glx_negative_export", "glx_graph_enable_negative", "glx_negative_sample",
@@ -168,6 +169,8 @@ def lib():
         L.glx_aggregate_weighted.argtypes = [ci, ci, vp, i64, i32, vp, vp, i32, vp, i32, i32, f32, vp, ci, vp]
         L.glx_aggregate_weighted_backward_x.argtypes = [ci, ci, vp, vp, i32, vp, i32, i32, i64, i32, vp, vp, ci, vp]
         L.glx_aggregate_weighted_backward_w.argtypes = [ci, ci, vp, i64, i32, vp, i32, vp, i32, i32, f32, vp, vp, ci, vp]
+        L.glx_segment_softmax.argtypes = [ci, vp, i32, vp, i32, i32, vp, ci, vp]
+        L.glx_segment_softmax_backward.argtypes = [ci, vp, vp, i32, vp, i32, i32, vp, ci, vp]
         L.glx_partition.argtypes = [ci, vp, i64, i32, vp, vp, vp, vp]
         L.glx_stitch_i64.argtypes = [ci, vp, vp, i64, i32, vp, vp]
         L.glx_stitch_f32.argtypes = [ci, vp, vp, i64, i32, vp, vp]
@@ -765,6 +768,41 @@ def aggregate_weighted_backward_w(op, x, rows, heads, cnt, grad_out, default_att
     _check(lib().glx_aggregate_weighted_backward_w(device, op, px[0], num_rows, dim, pr[0], heads, pc[0], n, num_segments,
                                                    default_attr, pg[0], pw[0], kind, _stream(kind, device)))
     return grad_w
+
+
+def segment_softmax(e, num_segments, cnt=None, out=None, device=0):
+    """Softmax of the logits e[n] or e[n, heads] float32 over the segments of a request, per head
+    (glx_segment_softmax) -> alpha of e's shape.  cnt[num_segments] int32: aggregate_weighted's layout (None: the
+    implied layout of n // num_segments positions per segment).  Every element is written, a position that is not
+    consumed is +0.0; a column with a NaN or +inf logit, or only -inf ones, is NaN.  No atomics: the same bits on every
+    call.  Torch CUDA tensors are device pointers on the current stream, numpy arrays host pointers."""
+    n = int(e.shape[0])
+    heads = _weighted_heads(e, n)
+    alpha = _weighted_out(out, e, tuple(e.shape))
+    pe, pc, pa = _ptr(e), _ptr(cnt), _ptr(alpha)
+    kind = _kind(pe, pc, pa)
+    if kind == PTR_DEVICE:
+        device = alpha.device.index or 0
+    _check(lib().glx_segment_softmax(device, pe[0], heads, pc[0], n, num_segments, pa[0], kind, _stream(kind, device)))
+    return alpha
+
+
+def segment_softmax_backward(alpha, grad_alpha, cnt, num_segments, out=None, device=0):
+    """Gradient of segment_softmax with respect to the logits (glx_segment_softmax_backward) -> grad_e of alpha's
+    shape: alpha * (grad_alpha - sum over the segment of alpha * grad_alpha), from the forward's own output.  Every
+    element is written, a position that is not consumed is +0.0; a fixed reduction tree, no atomics: the same bits on
+    every call."""
+    n = int(alpha.shape[0])
+    heads = _weighted_heads(alpha, n)
+    assert tuple(grad_alpha.shape) == tuple(alpha.shape), "grad_alpha must have alpha's shape"
+    grad_e = _weighted_out(out, alpha, tuple(alpha.shape))
+    pa, pg, pc, po = _ptr(alpha), _ptr(grad_alpha), _ptr(cnt), _ptr(grad_e)
+    kind = _kind(pa, pg, pc, po)
+    if kind == PTR_DEVICE:
+        device = grad_e.device.index or 0
+    _check(lib().glx_segment_softmax_backward(device, pa[0], pg[0], heads, pc[0], n, num_segments, po[0], kind,
+                                              _stream(kind, device)))
+    return grad_e
 
 
 COLUMN_NAMES = ("weights", "labels", "timestamps", "int_attrs")

@@ -1,6 +1,6 @@
 """Differentiable segment reductions and row gathers over a device-resident matrix: the torch surface of
-glx_aggregate / glx_aggregate_arg / glx_aggregate_backward and of glx_aggregate_weighted and its two gradients
-(include/glx.h).
+glx_aggregate / glx_aggregate_arg / glx_aggregate_backward, of glx_aggregate_weighted and its two gradients and of
+glx_segment_softmax and its gradient (include/glx.h).
 
 The role of tf.math.unsorted_segment_sum / unsorted_segment_mean under the reference's layers
 (graphlearn/python/nn/tf/layers/sage_conv.py:69-73, gcn_conv.py:73), for matrices that are computed on the way --
@@ -19,11 +19,18 @@ gcn_conv.py:52-73) and a GAT layer (a learned coefficient per neighbour and head
     alpha = torch.softmax(e.view(S, k, H), dim=1)                      # dense sampler response: plain torch
     h = weighted_segment_aggregate(z, batch.local[2], alpha.view(S * k, H), num_segments=S, op="sum")
 
-with a gradient for z and for alpha, neither through a float atomic.
+with a gradient for z and for alpha, neither through a float atomic.  The ragged form -- a FullSampler hop, or any
+request with counts (unsorted_segment_softmax under the reference's gat_conv.py:101-112) -- is
+
+    alpha = segment_softmax(e, S, counts=deg)                          # e [n, H]: one row of logits per position
+    h = weighted_segment_aggregate(z, nbr_local, alpha, S, counts=deg)
+
+where segment_softmax normalises each head over each segment's own positions, again without an atomic in either
+direction.
 """
 import torch
 
-__all__ = ["segment_aggregate", "gather_rows", "weighted_segment_aggregate"]
+__all__ = ["segment_aggregate", "gather_rows", "weighted_segment_aggregate", "segment_softmax"]
 
 _OPS = {"sum": 0, "mean": 1, "max": 2, "min": 3, "prod": 4}
 
@@ -229,3 +236,62 @@ def weighted_segment_aggregate(x, index, weights, num_segments, op="sum", counts
   out = _WeightedSegmentAggregate.apply(x, index, weights.reshape(n, heads).contiguous(), counts, num_segments,
                                         _OPS[op], float(default_attr))
   return out
+
+
+class _SegmentSoftmax(torch.autograd.Function):
+
+  @staticmethod
+  def forward(ctx, e, counts, num_segments):
+    alpha = _glx().segment_softmax(e.detach(), num_segments, cnt=counts)
+    ctx.num_segments, ctx.has_counts = num_segments, counts is not None
+    ctx.save_for_backward(*([alpha] + ([counts] if counts is not None else [])))
+    return alpha
+
+  @staticmethod
+  def backward(ctx, grad):
+    _no_double_backward("segment_softmax")
+    if not ctx.needs_input_grad[0]:
+      return None, None, None
+    saved = ctx.saved_tensors
+    alpha = saved[0]
+    counts = saved[1] if ctx.has_counts else None
+    grad = grad.to(torch.float32).contiguous()
+    return _glx().segment_softmax_backward(alpha, grad, counts, ctx.num_segments), None, None
+
+
+def segment_softmax(e, num_segments, counts=None):
+  """A tensor of e's shape: the softmax of the logits over each segment's positions, independently per head --
+  exp(e - max) / sum exp(e - max) with the accurate exp and no epsilon, bit-identical on every run.
+
+  e        [n] or [n, H] contiguous float32 CUDA tensor: one row of logits per position; may require grad
+  counts   None: num_segments equal segments of n / num_segments consecutive positions (a dense sampler response); or
+           an int32 [num_segments] tensor (what Graph.sample_full returns as degrees): segment s is the next counts[s]
+           positions; positions from counts.sum() on are ignored: they are 0 and get a zero gradient
+  A -inf logit among finite ones is exactly 0 (a mask); a NaN or +inf logit, or a segment of -inf only, makes that
+  head's column of the segment NaN, as torch.softmax does.  Anything else raises ValueError.
+  """
+  who = "segment_softmax"
+  if not isinstance(e, torch.Tensor):
+    raise ValueError("{}: e must be a torch tensor".format(who))
+  if e.dtype != torch.float32:
+    raise ValueError("{}: e must be float32, not {} (half logits are not supported)".format(who, e.dtype))
+  if not e.is_cuda or e.dim() not in (1, 2) or not e.is_contiguous():
+    raise ValueError("{}: e must be a contiguous [n] or [n, H] CUDA tensor".format(who))
+  n = int(e.shape[0])
+  heads = 1 if e.dim() == 1 else int(e.shape[1])
+  if heads < 1:
+    raise ValueError("{}: e must have at least one head".format(who))
+  num_segments = int(num_segments)
+  if num_segments < 0:
+    raise ValueError("{}: num_segments must be >= 0".format(who))
+  if counts is not None:
+    if not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32 or counts.device != e.device:
+      raise ValueError("{}: counts must be an int32 tensor on e's device".format(who))
+    if counts.dim() != 1 or counts.numel() != num_segments:
+      raise ValueError("{}: counts must have one entry per segment".format(who))
+    counts = counts.contiguous()
+  elif num_segments == 0 or n % num_segments != 0:
+    raise ValueError("{}: without counts, e.shape[0] must be a multiple of num_segments".format(who))
+  if n * heads > 2 ** 31 - 1:
+    raise ValueError("{}: n * H exceeds int32".format(who))
+  return _SegmentSoftmax.apply(e, counts, num_segments)

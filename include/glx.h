@@ -40,7 +40,8 @@ extern "C" {
  * glx_graph_edge_weight_packed; frontier dedup -- glx_unique; device-resident label / weight / timestamp / int-attribute
  * columns -- glx_columns_create, glx_columns_lookup, glx_columns_info, glx_columns_destroy; differentiable aggregation --
  * glx_aggregate_arg, glx_aggregate_backward; weighted aggregation -- glx_aggregate_weighted,
- * glx_aggregate_weighted_backward_x, glx_aggregate_weighted_backward_w. */
+ * glx_aggregate_weighted_backward_x, glx_aggregate_weighted_backward_w; ragged segment softmax -- glx_segment_softmax,
+ * glx_segment_softmax_backward. */
 #define GLX_ABI_VERSION 5
 
 /* Exported symbols: libglx.so is built with -fvisibility=hidden. */
@@ -454,6 +455,39 @@ GLX_API int glx_aggregate_weighted_backward_w(int device, int op, const float* x
                                               const int64_t* rows, int32_t heads, const int32_t* cnt, int32_t num_ids,
                                               int32_t num_segments, float default_attr, const float* grad_out,
                                               float* grad_w, int ptr_kind, void* stream);
+
+/* ---- ragged segment softmax: attention logits normalised over the segments of a counts= request, with its gradient.
+ * The reference's GAT layer calls unsorted_segment_softmax (python/nn/tf/utils/softmax.py:24-50) and then
+ * unsorted_segment_sum(nbr * alpha) (gat_conv.py:101-112); the second half is glx_aggregate_weighted. ----------------
+ * Common to the two entry points:
+ *   e, alpha, grad_alpha, alpha_out, grad_e   [num_ids * heads] float32, row-major [num_ids, heads]; heads >= 1
+ *   cnt[num_segments]      glx_aggregate_weighted's layout: counts clamped at 0, segment s is positions
+ *                          [sum(cnt[:s]), sum(cnt[:s]) + cnt[s]) cut at num_ids, positions from sum(cnt) on are not
+ *                          consumed; NULL: the implied layout of num_ids / num_segments positions per segment (a
+ *                          remainder is not consumed).  k = count(s) below is what segment s really has.
+ * Arguments are checked before any device use; num_ids * heads <= INT32_MAX.  A device-pointer call only enqueues
+ * work; the workspace comes from the calling thread's per-(device, stream) cache.  EVERY element of the output is
+ * written: a position that is not consumed gets +0.0f (an empty segment has no position of its own).  No atomics: one
+ * lane group (a whole workgroup for a long segment) reduces each (segment, head) with a fixed mapping and tree, so the
+ * same inputs give the same bits on every call; the ORDER of the sums is the mapping's and not part of the contract.
+ *
+ * glx_segment_softmax: independently for each (segment s, head h), m = max_p e[p, h] and
+ *     alpha[p, h] = expf(e[p, h] - m) / sum_q expf(e[q, h] - m)
+ * with the accurate expf, a correctly rounded division and no epsilon.  Exact: k == 1 with a finite logit is 1.0f; k
+ * equal finite logits are 1.0f / (float)k; a -inf logit among finite ones is +0.0f; the whole (s, h) column is NaN when
+ * a logit of it is NaN or +inf or all of them are -inf (torch.softmax's answers); only e - m enters, so a shift of a
+ * segment's logits that is exact in float32 changes no bit.  Otherwise, against the float64 value of the float32 inputs,
+ * with d_p = e_p - m and E the ulp error of expf:
+ *     |alpha - exact| <= exact * (2 |d_p| + 2 k + 4 E + 4) * 2^-24 + 2^-126. */
+GLX_API int glx_segment_softmax(int device, const float* e, int32_t heads, const int32_t* cnt, int32_t num_ids,
+                                int32_t num_segments, float* alpha_out, int ptr_kind, void* stream);
+/* glx_segment_softmax_backward: from the forward's own output alpha and grad_alpha (no exp), for each consumed (p, h)
+ *     grad_e[p, h] = alpha[p, h] * (grad_alpha[p, h] - sum_q alpha[q, h] * grad_alpha[q, h]),  q over the segment.
+ * Non-finite inputs give the IEEE result of the formula.  Against the float64 value of the float32 inputs:
+ *     |grad_e - exact| <= |alpha_p| * (k + 2) * 2^-23 * (|g_p| + sum_q |alpha_q g_q|) + 2^-126. */
+GLX_API int glx_segment_softmax_backward(int device, const float* alpha, const float* grad_alpha, int32_t heads,
+                                         const int32_t* cnt, int32_t num_ids, int32_t num_segments, float* grad_e,
+                                         int ptr_kind, void* stream);
 
 /* ---- negative sampling: replaces RandomNegativeSampler (random_negative_sampler.cc:30-63),
  * InDegreeNegativeSampler / SoftInDegreeNegativeSampler (in_degree_negative_sampler.cc:29-135)
