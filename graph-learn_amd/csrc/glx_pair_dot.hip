@@ -1,0 +1,355 @@
+// glx pair scores: the per-pair, optionally multi-head, dot product of two gathered rows, with its gradients with
+// respect to both tables.  The reference's unsupervised models score an edge as the dot product of its two endpoint
+// embeddings, against sampled negatives (examples/tf/sage/train.py:56-57, examples/tf/bipartite_sage/train.py:59-60,
+// examples/tf/ultra_gcn/ultra_gcn.py:92-95, python/nn/tf/loss.py:58).
+//
+// Contract (include/glx.h).  xa[num_rows_a, dim], xb[num_rows_b, dim] float32 (they may be one
+// table), C = dim / heads, column c belongs to head c / C.  ia[num_pairs / repeat], ib[num_pairs] int64: pair p joins
+// row ia[p / repeat] of xa with row ib[p] of xb -- repeat = K scores a [B, K] negative-sampler response against its B
+// sources.  An index outside its table reads a row of default_attr.
+//   forward    out[p, h] = sum over the columns c of head h of xa_row(p)[c] * xb_row(p)[c]; one lane group per pair, a
+//              lane-to-column mapping and a cross-lane tree fixed by (dim, heads, alignment) alone: the same bits on
+//              every call, checked against a bound (the order over the columns is the mapping's)
+//   backward   side 0 (xa): grad[r, c] = +0.0f, then for each pair p with ia[p / repeat] == r in ascending p
+//              fadd_rn(., fmul_rn(g[p, head(c)], xb_row(p)[c])); side 1 (xb): pairs with ib[p] == r, factor xa_row(p)[c].
+//              An own index outside the table receives nothing.  Bit-exact.
+// No float atomics anywhere.
+#include "glx_common.h"
+
+// Two roundings per term of the backward: see glx_aggregate_weighted.hip for why the product goes through an empty asm.
+#pragma clang fp contract(off)
+
+namespace {
+
+__device__ __forceinline__ float fold_rn(float acc, float w, float x) {
+  float t = w * x;        // rounded
+  asm("" : "+v"(t));      // opaque to the optimiser: no instruction, no contraction
+  return acc + t;         // rounded again
+}
+
+constexpr int kWU = 4;  // row loads in flight per lane
+
+// the smallest group of 8 .. 64 lanes that covers `lanes`
+int group_for(int lanes) { return lanes <= 8 ? 8 : lanes <= 16 ? 16 : lanes <= 32 ? 32 : 64; }
+
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// ---- forward -----------------------------------------------------------------------------------------------
+struct PairFwdArgs {
+  const float* xa;     // [num_rows_a, dim]
+  const float* xb;     // [num_rows_b, dim]
+  const int64_t* ia;   // [num_pairs / repeat]
+  const int64_t* ib;   // [num_pairs]
+  float* out;          // [num_pairs, heads]
+  int64_t num_rows_a, num_rows_b;
+  int32_t dim, heads, C, num_pairs, repeat;
+  int32_t sub;    // SUB: lanes of a sub-group (min(C / VEC, G))
+  int32_t steps;  // SUB: column tiles a head spans (C / VEC / G, at least 1)
+  float default_attr;
+};
+
+// VEC columns from `col` on of a gathered row; `row` == nullptr: the index was outside its table
+template <int VEC>
+__device__ __forceinline__ float __attribute__((ext_vector_type(VEC))) pair_row_load(const float* row, int32_t col,
+                                                                                      float default_attr) {
+  typedef float vec_t __attribute__((ext_vector_type(VEC)));
+  vec_t v;
+  if (row != nullptr) {
+    v = *reinterpret_cast<const vec_t*>(row + col);
+  } else {
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) v[k] = default_attr;
+  }
+  return v;
+}
+
+// G lanes own one PAIR p and write out[p, 0 .. heads): the mappings of glx_aggregate_weighted_bwd_w_kernel.
+//   SUB  (L = C / VEC is a power of two)  lane c owns columns [VEC c, VEC c + VEC) of each tile of G * VEC columns; a
+//        head is a sub-group of min(L, G) consecutive lanes (times L / G tiles when L > G), reduced with __shfl_xor over
+//        the sub-group; its first lane writes.
+//   !SUB a loop over the heads: lane c owns elements c, c + G, .. of the head's L vectors, the whole group reduces,
+//        lane 0 writes.
+// The `repeat` pairs of one source are neighbouring groups of a workgroup: the shared row comes out of the L1 / L2.
+template <int G, int VEC, bool SUB>
+__global__ __launch_bounds__(256) void glx_pair_dot_kernel(PairFwdArgs a) {
+  typedef float vec_t __attribute__((ext_vector_type(VEC)));
+  const int64_t p = blockIdx.x * (int64_t)(256 / G) + threadIdx.x / G;
+  const int c = threadIdx.x & (G - 1);
+  if (p >= a.num_pairs) return;  // whole groups leave
+  float* const out = a.out + p * (int64_t)a.heads;
+  const int64_t ra = a.ia[p / a.repeat], rb = a.ib[p];
+  const float* const xa = (ra >= 0 && ra < a.num_rows_a) ? a.xa + ra * (int64_t)a.dim : nullptr;
+  const float* const xb = (rb >= 0 && rb < a.num_rows_b) ? a.xb + rb * (int64_t)a.dim : nullptr;
+  if (SUB) {
+    const int32_t span = G * VEC * a.steps;  // columns per reduce: G / sub whole heads, or one
+    for (int32_t col_pass = 0; col_pass < a.dim; col_pass += span) {
+      float part = 0.0f;
+      for (int32_t k = 0; k < a.steps; ++k) {
+        const int32_t col = col_pass + (k * G + c) * VEC;
+        if (col < a.dim) {
+          const vec_t u = pair_row_load<VEC>(xa, col, a.default_attr);
+          const vec_t w = pair_row_load<VEC>(xb, col, a.default_attr);
+#pragma unroll
+          for (int v = 0; v < VEC; ++v) part += u[v] * w[v];
+        }
+      }
+      for (int off = a.sub >> 1; off > 0; off >>= 1) part += __shfl_xor(part, off, G);
+      const int32_t col0 = col_pass + c * VEC;
+      if ((c & (a.sub - 1)) == 0 && col0 < a.dim) out[col0 / a.C] = part;
+    }
+  } else {
+    const int32_t L = a.C / VEC;
+    for (int32_t h = 0; h < a.heads; ++h) {
+      float part = 0.0f;
+      for (int32_t i = c; i < L; i += G) {
+        const int32_t col = h * a.C + i * VEC;
+        const vec_t u = pair_row_load<VEC>(xa, col, a.default_attr);
+        const vec_t w = pair_row_load<VEC>(xb, col, a.default_attr);
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) part += u[v] * w[v];
+      }
+#pragma unroll
+      for (int off = G >> 1; off > 0; off >>= 1) part += __shfl_xor(part, off, G);
+      if (c == 0) out[h] = part;
+    }
+  }
+}
+
+template <int VEC, bool SUB>
+void launch_pair_fwd_g(PairFwdArgs a, int lanes, hipStream_t s) {
+  const int G = group_for(lanes);
+  if (SUB) {
+    const int L = a.C / VEC;
+    a.sub = L < G ? L : G;
+    a.steps = L > G ? L / G : 1;
+  }
+  const unsigned blocks = (unsigned)(((int64_t)a.num_pairs + (256 / G) - 1) / (256 / G));
+  switch (G) {
+    case 8: glx_pair_dot_kernel<8, VEC, SUB><<<blocks, 256, 0, s>>>(a); break;
+    case 16: glx_pair_dot_kernel<16, VEC, SUB><<<blocks, 256, 0, s>>>(a); break;
+    case 32: glx_pair_dot_kernel<32, VEC, SUB><<<blocks, 256, 0, s>>>(a); break;
+    default: glx_pair_dot_kernel<64, VEC, SUB><<<blocks, 256, 0, s>>>(a); break;
+  }
+}
+
+template <int VEC>
+void launch_pair_fwd_vec(const PairFwdArgs& a, hipStream_t s) {
+  const int L = a.C / VEC;
+  // sub-groups tile the row: the group covers all of it (up to 64 lanes); a loop over heads: the group covers one head
+  if ((L & (L - 1)) == 0) launch_pair_fwd_g<VEC, true>(a, a.dim / VEC, s);
+  else launch_pair_fwd_g<VEC, false>(a, L, s);
+}
+
+void launch_pair_fwd(const PairFwdArgs& a, hipStream_t s) {
+  const bool vec4 = a.dim % 4 == 0 && a.C % 4 == 0 && aligned16(a.xa) && aligned16(a.xb);
+  if (vec4) launch_pair_fwd_vec<4>(a, s);
+  else launch_pair_fwd_vec<1>(a, s);
+}
+
+// ---- backward ----------------------------------------------------------------------------------------------
+struct PairBwdArgs {
+  GlxAggTranspose t;         // of the own side's index array: row r's entries are t.pos[t.row_ptr[r] .. t.row_ptr[r + 1])
+  const int64_t* other_idx;  // the other side's index array
+  const float* g;            // [num_pairs, heads]
+  const float* x_other;      // [num_rows_other, dim]
+  float* grad_self;          // [num_rows_self, dim]
+  int64_t num_rows_self, num_rows_other;
+  int32_t dim, heads, C;
+  int32_t own_rep;    // pairs per entry of the own index array: repeat (side 0) or 1 (side 1)
+  int32_t other_rep;  // pairs per entry of the other index array: 1 (side 0) or repeat (side 1)
+  float default_attr;
+};
+
+// The sibling of glx_aggregate_weighted_bwd_x_kernel with the factor's row gathered too: G lanes own table row r.  Its
+// list of own-side entries, each expanded to own_rep consecutive pairs, is one run of (l1 - l0) * own_rep pairs in
+// ascending p (ascending entries give ascending pairs).  Lane c fetches pair base + c of the run (its number and the
+// other side's row, already tested against the table), every lane reads entry j from lane j; kWU row loads and their
+// g are issued before the first is folded.  Every row is written, an empty list writes zeros.
+template <int G, int VEC>
+__global__ __launch_bounds__(256) void glx_pair_dot_bwd_kernel(PairBwdArgs a) {
+  typedef float vec_t __attribute__((ext_vector_type(VEC)));
+  const int64_t r = blockIdx.x * (int64_t)(256 / G) + threadIdx.x / G;
+  const int c = threadIdx.x & (G - 1);
+  if (r >= a.num_rows_self) return;  // whole groups leave
+  const int32_t l0 = a.t.row_ptr[r];
+  const int32_t total = (a.t.row_ptr[r + 1] - l0) * a.own_rep;  // at most num_pairs
+  float* const out = a.grad_self + r * (int64_t)a.dim;
+  for (int32_t col_pass = 0; col_pass < a.dim; col_pass += G * VEC) {
+    const int32_t col = col_pass + c * VEC;
+    const bool col_ok = col < a.dim;
+    const int32_t col_ld = col_ok ? col : 0;  // lanes past the end re-read the first columns, unused
+    const int32_t head = col_ld / a.C;
+    vec_t acc;
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) acc[v] = 0.0f;
+    for (int32_t base = 0; base < total; base += G) {
+      int32_t my_p = 0, my_row = -1;
+      if (base + c < total) {
+        const int32_t e = base + c;
+        my_p = a.t.pos[l0 + e / a.own_rep] * a.own_rep + e % a.own_rep;
+        const int64_t o = a.other_idx[my_p / a.other_rep];
+        my_row = (o >= 0 && o < a.num_rows_other) ? (int32_t)o : -1;
+      }
+      const int32_t m = (total - base) < G ? (total - base) : G;
+      for (int32_t j = 0; j < m; j += kWU) {
+        int32_t pr[kWU], row[kWU];
+#pragma unroll
+        for (int u = 0; u < kWU; ++u) {
+          const int src = (j + u) & (G - 1);
+          pr[u] = __shfl(my_p, src, G);
+          row[u] = __shfl(my_row, src, G);
+        }
+        vec_t val[kWU];
+        float gt[kWU];
+#pragma unroll
+        for (int u = 0; u < kWU; ++u) {
+          if (j + u < m) {
+            gt[u] = a.g[(int64_t)pr[u] * a.heads + head];
+            if (row[u] >= 0) {
+              val[u] = *reinterpret_cast<const vec_t*>(a.x_other + row[u] * (int64_t)a.dim + col_ld);
+            } else {
+#pragma unroll
+              for (int v = 0; v < VEC; ++v) val[u][v] = a.default_attr;
+            }
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < kWU; ++u) {
+          if (j + u < m) {
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) acc[v] = fold_rn(acc[v], gt[u], val[u][v]);
+          }
+        }
+      }
+    }
+    if (col_ok) *reinterpret_cast<vec_t*>(out + col) = acc;
+  }
+}
+
+template <int VEC>
+void launch_pair_bwd_vec(const PairBwdArgs& a, hipStream_t s) {
+  const int G = group_for((a.dim + VEC - 1) / VEC);
+  const unsigned blocks = (unsigned)((a.num_rows_self + (256 / G) - 1) / (256 / G));
+  switch (G) {
+    case 8: glx_pair_dot_bwd_kernel<8, VEC><<<blocks, 256, 0, s>>>(a); break;
+    case 16: glx_pair_dot_bwd_kernel<16, VEC><<<blocks, 256, 0, s>>>(a); break;
+    case 32: glx_pair_dot_bwd_kernel<32, VEC><<<blocks, 256, 0, s>>>(a); break;
+    default: glx_pair_dot_bwd_kernel<64, VEC><<<blocks, 256, 0, s>>>(a); break;
+  }
+}
+
+void launch_pair_bwd(const PairBwdArgs& a, hipStream_t s) {
+  const bool vec4 = a.dim % 4 == 0 && a.C % 4 == 0 && aligned16(a.x_other) && aligned16(a.grad_self);
+  if (vec4) launch_pair_bwd_vec<4>(a, s);
+  else launch_pair_bwd_vec<1>(a, s);
+}
+
+}  // namespace
+
+// what the two entry points check alike, before any device use
+#define GLX_PAIR_REQUIRE()                                                                                              \
+  GLX_REQUIRE(num_pairs >= 0, "negative sizes: num_pairs %d", num_pairs);                                               \
+  GLX_REQUIRE(dim > 0, "dim must be positive, got %d", dim);                                                            \
+  GLX_REQUIRE(heads > 0, "heads must be positive, got %d", heads);                                                      \
+  GLX_REQUIRE(dim % heads == 0, "dim %d is not a multiple of heads %d", dim, heads);                                    \
+  GLX_REQUIRE(repeat >= 1, "repeat must be at least 1, got %d", repeat);                                                \
+  GLX_REQUIRE(num_pairs % repeat == 0, "num_pairs %d is not a multiple of repeat %d", num_pairs, repeat);               \
+  GLX_REQUIRE((int64_t)num_pairs * heads <= INT32_MAX, "num_pairs * heads exceeds int32");                              \
+  GLX_REQUIRE(ptr_kind == GLX_PTR_HOST || ptr_kind == GLX_PTR_DEVICE, "bad ptr_kind")
+
+extern "C" int glx_pair_dot(int device, const float* xa, int64_t num_rows_a, const float* xb, int64_t num_rows_b,
+                            int32_t dim, int32_t heads, const int64_t* ia, const int64_t* ib, int32_t num_pairs,
+                            int32_t repeat, float default_attr, float* out, int ptr_kind, void* stream) {
+  GLX_PAIR_REQUIRE();
+  GLX_REQUIRE(num_rows_a >= 0 && num_rows_b >= 0, "negative sizes: num_rows");
+  GLX_REQUIRE(num_rows_a < INT32_MAX && num_rows_b < INT32_MAX, "num_rows must be < 2^31");
+  GLX_REQUIRE(num_rows_a == 0 || xa != nullptr, "xa is NULL");
+  GLX_REQUIRE(num_rows_b == 0 || xb != nullptr, "xb is NULL");
+  GLX_REQUIRE(num_pairs == 0 || ia != nullptr, "ia is NULL");
+  GLX_REQUIRE(num_pairs == 0 || ib != nullptr, "ib is NULL");
+  GLX_REQUIRE(num_pairs == 0 || out != nullptr, "out is NULL");
+  int rc = glx_init_device(device);
+  if (rc != GLX_OK) return rc;
+  if (num_pairs == 0) return GLX_OK;
+  GlxDeviceGuard guard(device);
+  GLX_REQUIRE(guard.ok, "cannot select device %d", device);
+  GlxHostStage st(device, ptr_kind, stream, GlxHostStage::ADMIT);
+  PairFwdArgs a;
+  st.in(&a.xa, xa, (size_t)num_rows_a * dim);
+  st.in(&a.xb, xb, (size_t)num_rows_b * dim);
+  st.in(&a.ia, ia, (size_t)(num_pairs / repeat));
+  st.in(&a.ib, ib, (size_t)num_pairs);
+  st.out(&a.out, out, (size_t)num_pairs * heads);
+  rc = st.begin();
+  if (rc == GLX_OK) {
+    a.num_rows_a = num_rows_a;
+    a.num_rows_b = num_rows_b;
+    a.dim = dim;
+    a.heads = heads;
+    a.C = dim / heads;
+    a.num_pairs = num_pairs;
+    a.repeat = repeat;
+    a.sub = 1;
+    a.steps = 1;
+    a.default_attr = default_attr;
+    launch_pair_fwd(a, st.s);
+  }
+  return st.finish(rc);
+}
+
+extern "C" int glx_pair_dot_backward(int device, int side, const int64_t* ia, const int64_t* ib, int32_t num_pairs,
+                                     int32_t repeat, const float* g, int32_t heads, const float* x_other,
+                                     int64_t num_rows_other, int32_t dim, int64_t num_rows_self, float default_attr,
+                                     float* grad_self, int ptr_kind, void* stream) {
+  GLX_PAIR_REQUIRE();
+  GLX_REQUIRE(side == 0 || side == 1, "side must be 0 (xa) or 1 (xb), got %d", side);
+  GLX_REQUIRE(num_rows_other >= 0 && num_rows_self >= 0, "negative sizes: num_rows");
+  GLX_REQUIRE(num_rows_other < INT32_MAX && num_rows_self < INT32_MAX, "num_rows must be < 2^31");
+  GLX_REQUIRE(num_pairs == 0 || ia != nullptr, "ia is NULL");
+  GLX_REQUIRE(num_pairs == 0 || ib != nullptr, "ib is NULL");
+  GLX_REQUIRE(num_pairs == 0 || g != nullptr, "g is NULL");
+  GLX_REQUIRE(num_rows_other == 0 || x_other != nullptr, "x_other is NULL");
+  GLX_REQUIRE(num_rows_self == 0 || grad_self != nullptr, "grad_self is NULL");
+  int rc = glx_init_device(device);
+  if (rc != GLX_OK) return rc;
+  if (num_rows_self == 0) return GLX_OK;
+  GlxDeviceGuard guard(device);
+  GLX_REQUIRE(guard.ok, "cannot select device %d", device);
+  GlxHostStage st(device, ptr_kind, stream, GlxHostStage::ADMIT);
+  const int64_t* d_ia;
+  const int64_t* d_ib;
+  PairBwdArgs a;
+  st.in(&d_ia, ia, (size_t)(num_pairs / repeat));
+  st.in(&d_ib, ib, (size_t)num_pairs);
+  st.in(&a.g, g, (size_t)num_pairs * heads);
+  st.in(&a.x_other, x_other, (size_t)num_rows_other * dim);
+  st.out(&a.grad_self, grad_self, (size_t)num_rows_self * dim);
+  rc = st.begin();
+  GlxScratch lease;
+  if (rc == GLX_OK) {
+    if (num_pairs == 0) {  // no pair: every row is zeros
+      hipError_t e = hipMemsetAsync(a.grad_self, 0, (size_t)num_rows_self * dim * sizeof(float), st.s);
+      if (e != hipSuccess) {
+        glx_set_error("hipMemsetAsync failed: %s", hipGetErrorString(e));
+        rc = GLX_INTERNAL;
+      }
+    } else {
+      // one position per segment; side 0 sorts the num_pairs / repeat entries of ia only
+      const int32_t own_n = side == 0 ? num_pairs / repeat : num_pairs;
+      rc = glx_agg_transpose(side == 0 ? d_ia : d_ib, nullptr, own_n, own_n, num_rows_self, st.s, &lease, &a.t);
+      if (rc == GLX_OK) {
+        a.other_idx = side == 0 ? d_ib : d_ia;
+        a.num_rows_self = num_rows_self;
+        a.num_rows_other = num_rows_other;
+        a.dim = dim;
+        a.heads = heads;
+        a.C = dim / heads;
+        a.own_rep = side == 0 ? repeat : 1;
+        a.other_rep = side == 0 ? 1 : repeat;
+        a.default_attr = default_attr;
+        launch_pair_bwd(a, st.s);
+      }
+    }
+  }
+  return st.finish(rc);
+}

@@ -48,6 +48,7 @@ EXPORTS = [
     "glx_aggregate", "glx_lookup", "glx_aggregate_arg", "glx_aggregate_backward",
     "glx_aggregate_weighted", "glx_aggregate_weighted_backward_x", "glx_aggregate_weighted_backward_w",
     "glx_segment_softmax", "glx_segment_softmax_backward",
+    "glx_pair_dot", "glx_pair_dot_backward",
     "glx_partition", "glx_stitch_i64", "glx_stitch_f32", "glx_aggregate_stitch",
     "glx_negative_create", "glx_negative_from_graph", "glx_negative_destroy", "glx_negative_info",
     "glx_negative_export", "glx_graph_enable_negative", "glx_negative_sample",
@@ -171,6 +172,8 @@ def lib():
         L.glx_aggregate_weighted_backward_w.argtypes = [ci, ci, vp, i64, i32, vp, i32, vp, i32, i32, f32, vp, vp, ci, vp]
         L.glx_segment_softmax.argtypes = [ci, vp, i32, vp, i32, i32, vp, ci, vp]
         L.glx_segment_softmax_backward.argtypes = [ci, vp, vp, i32, vp, i32, i32, vp, ci, vp]
+        L.glx_pair_dot.argtypes = [ci, vp, i64, vp, i64, i32, i32, vp, vp, i32, i32, f32, vp, ci, vp]
+        L.glx_pair_dot_backward.argtypes = [ci, ci, vp, vp, i32, i32, vp, i32, vp, i64, i32, i64, f32, vp, ci, vp]
         L.glx_partition.argtypes = [ci, vp, i64, i32, vp, vp, vp, vp]
         L.glx_stitch_i64.argtypes = [ci, vp, vp, i64, i32, vp, vp]
         L.glx_stitch_f32.argtypes = [ci, vp, vp, i64, i32, vp, vp]
@@ -803,6 +806,53 @@ def segment_softmax_backward(alpha, grad_alpha, cnt, num_segments, out=None, dev
     _check(lib().glx_segment_softmax_backward(device, pa[0], pg[0], heads, pc[0], n, num_segments, po[0], kind,
                                               _stream(kind, device)))
     return grad_e
+
+
+def _pair_counts(ia, ib, repeat):
+    """(num_pairs, repeat) of a pair request; ia has one entry per `repeat` entries of ib"""
+    n, repeat = int(np.prod(ib.shape)), int(repeat)
+    assert repeat >= 1 and int(np.prod(ia.shape)) * repeat == n, "ia needs one entry per `repeat` entries of ib"
+    return n, repeat
+
+
+def pair_dot(xa, ia, xb, ib, heads=1, repeat=1, default_attr=0.0, out=None, device=0):
+    """Per-pair, per-head dot products of gathered rows (glx_pair_dot) -> out[n, heads] float32, n = ib's size.
+    xa[Na, D], xb[Nb, D] float32 (they may be one table); ib[n] int64 and ia[n // repeat] int64: pair p joins row
+    ia[p // repeat] of xa with row ib[p] of xb (repeat = K: a [B, K] negative-sampler response against its B sources);
+    an index outside its table reads a row of default_attr; column c belongs to head c // (D // heads).  A fixed lane
+    mapping and reduction tree, no atomics: the same bits on every call, within (D // heads) * 2^-23 * sum|terms| of
+    the exact value.  Torch CUDA tensors are device pointers on the current stream, numpy arrays host pointers."""
+    n, repeat = _pair_counts(ia, ib, repeat)
+    num_rows_a, dim = int(xa.shape[0]), int(xa.shape[1])
+    num_rows_b = int(xb.shape[0])
+    assert int(xb.shape[1]) == dim, "xa and xb must have the same number of columns"
+    res = _weighted_out(out, xa, (n, heads))
+    pa, pia, pb, pib, po = _ptr(xa), _ptr(ia), _ptr(xb), _ptr(ib), _ptr(res)
+    kind = _kind(pa, pia, pb, pib, po)
+    if kind == PTR_DEVICE:
+        device = res.device.index or 0
+    _check(lib().glx_pair_dot(device, pa[0], num_rows_a, pb[0], num_rows_b, dim, heads, pia[0], pib[0], n, repeat,
+                              default_attr, po[0], kind, _stream(kind, device)))
+    return res
+
+
+def pair_dot_backward(side, ia, ib, g, x_other, num_rows_self, repeat=1, default_attr=0.0, out=None, device=0):
+    """Gradient of pair_dot with respect to xa (side 0) or xb (side 1) (glx_pair_dot_backward) ->
+    grad_self[num_rows_self, D] float32, every row written.  g[n, heads] (or g[n]) is the gradient of pair_dot's output,
+    x_other the other side's table.  Each element adds fmul(g[p, head], other_row(p)) over the pairs that refer to its
+    row in ascending p, no float atomic: the same bits on every run.  An own index outside the table gets nothing, an
+    other-side index outside its table multiplies a row of default_attr."""
+    n, repeat = _pair_counts(ia, ib, repeat)
+    heads = _weighted_heads(g, n)
+    num_rows_other, dim = int(x_other.shape[0]), int(x_other.shape[1])
+    grad = _weighted_out(out, x_other, (num_rows_self, dim))
+    pia, pib, pg, px, po = _ptr(ia), _ptr(ib), _ptr(g), _ptr(x_other), _ptr(grad)
+    kind = _kind(pia, pib, pg, px, po)
+    if kind == PTR_DEVICE:
+        device = grad.device.index or 0
+    _check(lib().glx_pair_dot_backward(device, side, pia[0], pib[0], n, repeat, pg[0], heads, px[0], num_rows_other, dim,
+                                       num_rows_self, default_attr, po[0], kind, _stream(kind, device)))
+    return grad
 
 
 COLUMN_NAMES = ("weights", "labels", "timestamps", "int_attrs")

@@ -1,6 +1,6 @@
-"""Differentiable segment reductions and row gathers over a device-resident matrix: the torch surface of
-glx_aggregate / glx_aggregate_arg / glx_aggregate_backward, of glx_aggregate_weighted and its two gradients and of
-glx_segment_softmax and its gradient (include/glx.h).
+"""Differentiable segment reductions, row gathers and pair scores over a device-resident matrix: the torch surface of
+glx_aggregate / glx_aggregate_arg / glx_aggregate_backward, of glx_aggregate_weighted and its two gradients, of
+glx_segment_softmax and its gradient and of glx_pair_dot and its gradient (include/glx.h).
 
 The role of tf.math.unsorted_segment_sum / unsorted_segment_mean under the reference's layers
 (graphlearn/python/nn/tf/layers/sage_conv.py:69-73, gcn_conv.py:73), for matrices that are computed on the way --
@@ -27,10 +27,19 @@ request with counts (unsorted_segment_softmax under the reference's gat_conv.py:
 
 where segment_softmax normalises each head over each segment's own positions, again without an atomic in either
 direction.
+
+pair_dot is the scoring step of the reference's unsupervised models (examples/tf/sage/train.py:56-57,
+python/nn/tf/loss.py:58): the dot product of the two endpoint embeddings of an edge, and of a source with each of its
+K sampled negatives,
+
+    pos = pair_dot(z, l_src, z, l_dst)                                 # [B]
+    neg = pair_dot(z, l_src, z, l_neg.view(B, K))                      # [B, K]
+
+without the two [n, D] gathers of `(z[src].unsqueeze(1) * z[neg]).sum(-1)` and without their index_add_ backwards.
 """
 import torch
 
-__all__ = ["segment_aggregate", "gather_rows", "weighted_segment_aggregate", "segment_softmax"]
+__all__ = ["segment_aggregate", "gather_rows", "weighted_segment_aggregate", "segment_softmax", "pair_dot"]
 
 _OPS = {"sum": 0, "mean": 1, "max": 2, "min": 3, "prod": 4}
 
@@ -295,3 +304,64 @@ def segment_softmax(e, num_segments, counts=None):
   if n * heads > 2 ** 31 - 1:
     raise ValueError("{}: n * H exceeds int32".format(who))
   return _SegmentSoftmax.apply(e, counts, num_segments)
+
+
+class _PairDot(torch.autograd.Function):
+
+  @staticmethod
+  def forward(ctx, xa, ia, xb, ib, heads, repeat, default_attr):
+    xad, xbd = xa.detach(), xb.detach()
+    out = _glx().pair_dot(xad, ia, xbd, ib, heads=heads, repeat=repeat, default_attr=default_attr)
+    ctx.repeat, ctx.default_attr = repeat, default_attr
+    ctx.save_for_backward(xad, ia, xbd, ib)
+    return out
+
+  @staticmethod
+  def backward(ctx, grad):
+    _no_double_backward("pair_dot")
+    glx = _glx()
+    xa, ia, xb, ib = ctx.saved_tensors
+    grad = grad.to(torch.float32).contiguous()
+    ga = gb = None
+    if ctx.needs_input_grad[0]:
+      ga = glx.pair_dot_backward(0, ia, ib, grad, xb, int(xa.shape[0]), repeat=ctx.repeat, default_attr=ctx.default_attr)
+    if ctx.needs_input_grad[2]:
+      gb = glx.pair_dot_backward(1, ia, ib, grad, xa, int(xb.shape[0]), repeat=ctx.repeat, default_attr=ctx.default_attr)
+    return ga, None, gb, None, None, None, None
+
+
+def pair_dot(xa, ia, xb, ib, heads=None, default_attr=0.0):
+  """The score of every pair (ia, ib): the dot product of row ia of xa with row ib of xb, per head -- a fixed summation
+  tree going forward, fadd(acc, fmul(g, row)) in ascending pair order going back, no atomics: bit-identical on every
+  run.  Neither [n, D] gather is materialised.
+
+  xa, xb   [Na, D], [Nb, D] contiguous float32 CUDA tensors on one device; either may require grad, and they may be one
+           tensor (autograd then adds the two sides' gradients: one more float32 add per element)
+  ib       int64 CUDA tensor of any shape (n pairs): rows of xb
+  ia       int64 CUDA tensor (flattened) whose numel divides n: rows of xa; pair p takes ia[p // (n / ia.numel())] -- ia
+           [B] with ib [B, K] scores each source against its K candidates; ia shaped like ib scores edges one to one
+  heads    None: a tensor of ib's shape; H (dividing D): ib.shape + (H,), column c belongs to head c // (D // H)
+  An index outside its table reads a row of `default_attr` and receives no gradient.  Only the gradients that are
+  needed are computed.  Anything else raises ValueError.
+  """
+  who = "pair_dot"
+  _check_inputs(xa, ia, who)
+  _check_inputs(xb, ib, who)
+  if xb.device != xa.device:
+    raise ValueError("{}: xb lives on {}, xa on {}".format(who, xb.device, xa.device))
+  D = int(xa.shape[1])
+  if int(xb.shape[1]) != D:
+    raise ValueError("{}: xa has {} columns, xb {}".format(who, D, int(xb.shape[1])))
+  H = 1 if heads is None else int(heads)
+  if H < 1 or D % H != 0:
+    raise ValueError("{}: the number of heads ({}) must divide D ({})".format(who, H, D))
+  shape = tuple(ib.shape)
+  ia, ib = ia.reshape(-1).contiguous(), ib.reshape(-1).contiguous()
+  n, m = ib.numel(), ia.numel()
+  if (m == 0 and n != 0) or (m != 0 and n % m != 0):
+    raise ValueError("{}: ia.numel() ({}) must divide ib.numel() ({})".format(who, m, n))
+  if n * H > 2 ** 31 - 1:
+    raise ValueError("{}: n * H exceeds int32".format(who))
+  repeat = n // m if n else 1
+  out = _PairDot.apply(xa, ia, xb, ib, H, repeat, float(default_attr))
+  return out.reshape(shape if heads is None else shape + (H,))

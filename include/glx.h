@@ -41,7 +41,7 @@ extern "C" {
  * columns -- glx_columns_create, glx_columns_lookup, glx_columns_info, glx_columns_destroy; differentiable aggregation --
  * glx_aggregate_arg, glx_aggregate_backward; weighted aggregation -- glx_aggregate_weighted,
  * glx_aggregate_weighted_backward_x, glx_aggregate_weighted_backward_w; ragged segment softmax -- glx_segment_softmax,
- * glx_segment_softmax_backward. */
+ * glx_segment_softmax_backward; pair scores -- glx_pair_dot, glx_pair_dot_backward. */
 #define GLX_ABI_VERSION 5
 
 /* Exported symbols: libglx.so is built with -fvisibility=hidden. */
@@ -488,6 +488,46 @@ GLX_API int glx_segment_softmax(int device, const float* e, int32_t heads, const
 GLX_API int glx_segment_softmax_backward(int device, const float* alpha, const float* grad_alpha, int32_t heads,
                                          const int32_t* cnt, int32_t num_ids, int32_t num_segments, float* grad_e,
                                          int ptr_kind, void* stream);
+
+/* ---- pair scores: the per-pair, optionally multi-head, dot product of two gathered rows, with its gradients with
+ * respect to both tables.  The reference's unsupervised models score an edge as the dot product of its two endpoint
+ * embeddings, against sampled negatives (examples/tf/sage/train.py:56-57, examples/tf/bipartite_sage/train.py:59-60,
+ * examples/tf/ultra_gcn/ultra_gcn.py:92-95, python/nn/tf/loss.py:58). -------------------------------------------------
+ * Common to the two entry points:
+ *   xa[num_rows_a * dim], xb[num_rows_b * dim]   float32, row-major; they may be the same pointer
+ *   heads >= 1, dim % heads == 0, C = dim / heads; column c belongs to head c / C
+ *   repeat >= 1, num_pairs % repeat == 0
+ *   ia[num_pairs / repeat], ib[num_pairs]        int64; pair p joins row ia[p / repeat] of xa with row ib[p] of xb:
+ *                          repeat = 1 scores positive edges, repeat = K a [B, K] negative-sampler response against its B
+ *                          sources, without a copy of each source K times.  An index outside its table reads a row of
+ *                          default_attr
+ * Arguments are checked before any device use; num_rows_* < 2^31, num_pairs * heads <= INT32_MAX.  A device-pointer
+ * call only enqueues work; the workspace comes from the calling thread's per-(device, stream) cache.  No float atomics
+ * anywhere.
+ *
+ * glx_pair_dot (tolerance contract, that of glx_aggregate_weighted_backward_w): out[p, h] = sum over the columns c of
+ * head h of xa_row(p)[c] * xb_row(p)[c]; EVERY element of out[num_pairs * heads] is written.  One lane group per pair
+ * with a lane-to-column mapping and a cross-lane tree fixed by (dim, heads, alignment) alone: the same inputs give the
+ * same bits on every call.  The ORDER of the sum over the columns is the mapping's and not part of the contract; for any
+ * order of a C-term float32 dot product, against the float64 value of the float32 inputs,
+ *     |out - exact| <= C * 2^-23 * sum_c |a * b| + 2^-126;
+ * non-finite inputs give the IEEE result. */
+GLX_API int glx_pair_dot(int device, const float* xa, int64_t num_rows_a, const float* xb, int64_t num_rows_b,
+                         int32_t dim, int32_t heads, const int64_t* ia, const int64_t* ib, int32_t num_pairs,
+                         int32_t repeat, float default_attr, float* out, int ptr_kind, void* stream);
+/* glx_pair_dot_backward (bit-exact contract, that of glx_aggregate_weighted_backward_x): the gradient of the table on
+ * `side` (0: xa, 1: xb) from g[num_pairs * heads], the gradient of out.  grad_self[r, c] starts at +0.0f and, for each
+ * pair p whose own index (side 0: ia[p / repeat], side 1: ib[p]) is r, in ascending p, becomes
+ *     fadd_rn(grad_self[r, c], fmul_rn(g[p, head(c)], other_row(p)[c]))
+ * -- two roundings, never contracted into an FMA under any build flag; other_row(p) is row ib[p] (side 0) or
+ * ia[p / repeat] (side 1) of x_other[num_rows_other * dim], a row of default_attr when that index is outside the table.
+ * An own index outside [0, num_rows_self) receives nothing.  EVERY row of grad_self[num_rows_self * dim] is written; the
+ * call overwrites.  (The stable sort by row of glx_aggregate_backward over the own index array -- for side 0 its
+ * num_pairs / repeat entries only -- then one lane group per row.) */
+GLX_API int glx_pair_dot_backward(int device, int side, const int64_t* ia, const int64_t* ib, int32_t num_pairs,
+                                  int32_t repeat, const float* g, int32_t heads, const float* x_other,
+                                  int64_t num_rows_other, int32_t dim, int64_t num_rows_self, float default_attr,
+                                  float* grad_self, int ptr_kind, void* stream);
 
 /* ---- negative sampling: replaces RandomNegativeSampler (random_negative_sampler.cc:30-63),
  * InDegreeNegativeSampler / SoftInDegreeNegativeSampler (in_degree_negative_sampler.cc:29-135)
