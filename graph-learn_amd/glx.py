@@ -49,6 +49,7 @@ EXPORTS = [
     "glx_aggregate_weighted", "glx_aggregate_weighted_backward_x", "glx_aggregate_weighted_backward_w",
     "glx_segment_softmax", "glx_segment_softmax_backward",
     "glx_pair_dot", "glx_pair_dot_backward",
+    "glx_rows_coalesce", "glx_embedding_update",
     "glx_partition", "glx_stitch_i64", "glx_stitch_f32", "glx_aggregate_stitch",
     "glx_negative_create", "glx_negative_from_graph", "glx_negative_destroy", "glx_negative_info",
     "glx_negative_export", "glx_graph_enable_negative", "glx_negative_sample",
@@ -174,6 +175,8 @@ def lib():
         L.glx_segment_softmax_backward.argtypes = [ci, vp, vp, i32, vp, i32, i32, vp, ci, vp]
         L.glx_pair_dot.argtypes = [ci, vp, i64, vp, i64, i32, i32, vp, vp, i32, i32, f32, vp, ci, vp]
         L.glx_pair_dot_backward.argtypes = [ci, ci, vp, vp, i32, i32, vp, i32, vp, i64, i32, i64, f32, vp, ci, vp]
+        L.glx_rows_coalesce.argtypes = [ci, vp, i32, i64, i32, vp, vp, vp, vp, ci, vp]
+        L.glx_embedding_update.argtypes = [ci, ci, vp, vp, vp, i64, i32, vp, vp, i32, f32, f32, f32, f32, f32, f32, vp]
         L.glx_partition.argtypes = [ci, vp, i64, i32, vp, vp, vp, vp]
         L.glx_stitch_i64.argtypes = [ci, vp, vp, i64, i32, vp, vp]
         L.glx_stitch_f32.argtypes = [ci, vp, vp, i64, i32, vp, vp]
@@ -853,6 +856,58 @@ def pair_dot_backward(side, ia, ib, g, x_other, num_rows_self, repeat=1, default
     _check(lib().glx_pair_dot_backward(device, side, pia[0], pib[0], n, repeat, pg[0], heads, px[0], num_rows_other, dim,
                                        num_rows_self, default_attr, po[0], kind, _stream(kind, device)))
     return grad
+
+
+EMB_SGD, EMB_ADAGRAD, EMB_ADAM = 0, 1, 2  # GLX_EMB_*
+COALESCE_CHUNK = 256  # GLX_COALESCE_CHUNK
+
+
+def rows_coalesce(rows, g, num_rows, out_rows=None, out_g=None, device=0):
+    """The gradient g[n, D] float32 of a lookup of rows[n] int64, summed per distinct row (glx_rows_coalesce) ->
+    (urows[n] int64, ug[n, D] float32, count).  A row outside [0, num_rows) is dropped; the U distinct remaining rows
+    are urows[:U], ascending, and urows[U:] is -1; ug[:U] holds their sums and ug[U:] is NOT written; count is U.  Each
+    list of positions is summed in ascending position in chunks of COALESCE_CHUNK entries whose partial sums are then
+    added in order, no float atomic: the same bits on every run, and for lists of at most COALESCE_CHUNK positions the
+    rows of aggregate_backward(SUM, ...).  Nothing scales with num_rows.  Torch CUDA tensors are device pointers on the
+    current stream and count stays a one-element CUDA tensor (no host read); numpy arrays are host pointers and count
+    is an int."""
+    n, dim = int(rows.shape[0]), int(g.shape[1])
+    assert int(g.shape[0]) == n, "one gradient row per position"
+    torch_in = _is_torch(g)
+    if torch_in:
+        import torch
+        urows = out_rows if out_rows is not None else torch.empty((n,), dtype=torch.int64, device=g.device)
+        ug = out_g if out_g is not None else torch.empty((n, dim), dtype=torch.float32, device=g.device)
+        count = torch.empty((1,), dtype=torch.int64, device=g.device)
+    else:
+        urows = out_rows if out_rows is not None else np.empty((n,), np.int64)
+        ug = out_g if out_g is not None else np.empty((n, dim), np.float32)
+        count = np.empty((1,), np.int64)
+    pr, pg, pu, po, pc = _ptr(rows), _ptr(g), _ptr(urows), _ptr(ug), _ptr(count)
+    kind = _kind(pr, pg, pu, po, pc)
+    if kind == PTR_DEVICE:
+        device = ug.device.index or 0
+    _check(lib().glx_rows_coalesce(device, pr[0], n, num_rows, dim, pg[0], pu[0], po[0], pc[0], kind,
+                                   _stream(kind, device)))
+    return urows, ug, (count if torch_in else int(count[0]))
+
+
+def embedding_update(algo, W, urows, ug, state1=None, state2=None, alpha=0.0, eps=0.0, beta1=0.0, c1=0.0, beta2=0.0,
+                     c2=0.0):
+    """One sparse optimizer step in place on the rows urows[n] names (glx_embedding_update); torch CUDA tensors only.
+    W[num_rows, D] float32 and the state tables of its shape: EMB_SGD none, EMB_ADAGRAD state1 (the accumulator),
+    EMB_ADAM state1 and state2 (first and second moment).  ug[n, D] is the gradient of entry u's row; an entry outside
+    [0, num_rows) -- the -1 tail of rows_coalesce -- is skipped.  The valid entries must name distinct rows (not
+    detected: a repeated row is a lost update).  Every operation is one correctly rounded float32 operation; the
+    scalars are rounded to float32 once (see include/glx.h for what they are per algorithm)."""
+    num_rows, dim = int(W.shape[0]), int(W.shape[1])
+    n = int(urows.shape[0])
+    assert int(ug.shape[0]) == n and int(ug.shape[1]) == dim, "ug must be [n, D]"
+    pw, pu, pg, p1, p2 = _ptr(W), _ptr(urows), _ptr(ug), _ptr(state1), _ptr(state2)
+    assert _kind(pw, pu, pg, p1, p2) == PTR_DEVICE, "the tables live on the device: torch CUDA tensors only"
+    device = W.device.index or 0
+    _check(lib().glx_embedding_update(device, algo, pw[0], p1[0], p2[0], num_rows, dim, pu[0], pg[0], n, alpha, eps,
+                                      beta1, c1, beta2, c2, _stream(PTR_DEVICE, device)))
 
 
 COLUMN_NAMES = ("weights", "labels", "timestamps", "int_attrs")

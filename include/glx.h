@@ -41,7 +41,8 @@ extern "C" {
  * columns -- glx_columns_create, glx_columns_lookup, glx_columns_info, glx_columns_destroy; differentiable aggregation --
  * glx_aggregate_arg, glx_aggregate_backward; weighted aggregation -- glx_aggregate_weighted,
  * glx_aggregate_weighted_backward_x, glx_aggregate_weighted_backward_w; ragged segment softmax -- glx_segment_softmax,
- * glx_segment_softmax_backward; pair scores -- glx_pair_dot, glx_pair_dot_backward. */
+ * glx_segment_softmax_backward; pair scores -- glx_pair_dot, glx_pair_dot_backward; trainable embedding tables --
+ * glx_rows_coalesce, glx_embedding_update. */
 #define GLX_ABI_VERSION 5
 
 /* Exported symbols: libglx.so is built with -fvisibility=hidden. */
@@ -528,6 +529,53 @@ GLX_API int glx_pair_dot_backward(int device, int side, const int64_t* ia, const
                                   int32_t repeat, const float* g, int32_t heads, const float* x_other,
                                   int64_t num_rows_other, int32_t dim, int64_t num_rows_self, float default_attr,
                                   float* grad_self, int ptr_kind, void* stream);
+
+/* ---- trainable embedding tables: the coalesced row gradient of a lookup and the sparse optimizer steps that apply it
+ * in place, on the touched rows only.  The reference trains tables in two places: one EmbeddingColumn per categorical
+ * attribute (python/nn/tf/data/feature_column.py:128-157) and the target / context id embeddings of DeepWalk / node2vec
+ * (examples/tf/node2vec/node2vec.py:49-50). -----------------------------------------------------------------------------
+ * Common to the two entry points: arguments are checked before any device use; 0 <= num_rows < 2^31, dim >= 1,
+ * n * dim <= INT32_MAX; row indices are dense (row r is r: no id map).  A device-pointer call only enqueues work; the
+ * workspace comes from the calling thread's per-(device, stream) cache.  No float atomics anywhere; nothing is
+ * allocated, cleared or launched in proportion to num_rows.  The build's -ffp-contract=off and
+ * -fhip-fp32-correctly-rounded-divide-sqrt give the single roundings the contracts name. */
+#define GLX_EMB_SGD 0
+#define GLX_EMB_ADAGRAD 1
+#define GLX_EMB_ADAM 2
+#define GLX_COALESCE_CHUNK 256
+/* glx_rows_coalesce (bit-exact contract): the gradient g[n * dim] of a lookup of rows[n], summed per distinct row.
+ * A position whose row is outside [0, num_rows) is dropped.  With U the number of distinct remaining rows,
+ * urows_out[0 .. U) holds them ascending, urows_out[U .. n) is -1, *num_unique_out = U (one word, of the same ptr_kind
+ * as the other buffers) and rows U .. n of ug_out[n * dim] are NOT written.  For u < U let p_0 < p_1 < ... < p_{L-1} be
+ * the positions with rows[p] == urows_out[u], cut into chunks of GLX_COALESCE_CHUNK consecutive list entries: chunk k's
+ * partial starts at +0.0f and becomes fadd_rn(partial, g[p, c]) in ascending p; ug_out[u, c] starts at +0.0f and becomes
+ * fadd_rn(ug_out[u, c], partial_k) in ascending k.  A list of at most GLX_COALESCE_CHUNK positions is therefore summed in
+ * plain ascending order and equals the row glx_aggregate_backward(GLX_AGG_SUM, implied layout, one position per segment)
+ * writes, bit for bit; a longer list -- a categorical value shared by a whole batch, a hub -- is reduced by
+ * ceil(L / GLX_COALESCE_CHUNK) lane groups and a second pass that adds their partial sums in that fixed order.
+ * (A stable radix sort of (row, position) over the bits num_rows needs, the sentinel key num_rows for dropped
+ * positions; run and chunk heads from flags and one scan over the n sorted keys; one lane group per chunk.) */
+GLX_API int glx_rows_coalesce(int device, const int64_t* rows, int32_t n, int64_t num_rows, int32_t dim, const float* g,
+                              int64_t* urows_out, float* ug_out, int64_t* num_unique_out, int ptr_kind, void* stream);
+/* glx_embedding_update (bit-exact contract): one optimizer step on the rows urows[n] names, DEVICE pointers only (the
+ * tables live in HBM).  For each entry u < n with urows[u] in [0, num_rows) and each column, with g = ug[u, c] and w, s,
+ * m, v the elements of row urows[u] of W, state1, state2 -- every operation one correctly rounded float32 operation, in
+ * this order:
+ *   GLX_EMB_SGD                                    w = w - alpha * g
+ *   GLX_EMB_ADAGRAD  (state1 = s)                  s = s + g * g;  w = w - alpha * (g / (sqrtf(s) + eps))
+ *   GLX_EMB_ADAM     (state1 = m, state2 = v)      m = beta1 * m + c1 * g;  v = beta2 * v + c2 * (g * g);
+ *                                                  w = w - alpha * (m / (sqrtf(v) + eps))
+ * The caller computes the scalars in double and rounds each to float32 once: alpha = lr for SGD and Adagrad; for Adam at
+ * global step t, alpha = lr * sqrt(1 - beta2^t) / (1 - beta1^t), c1 = 1 - beta1, c2 = 1 - beta2 -- in exact arithmetic
+ * torch.optim.SGD, Adagrad (lr_decay = 0, weight_decay = 0) and SparseAdam on the coalesced gradient.  An entry outside
+ * the table is skipped -- the -1 tail of glx_rows_coalesce among them, so a step is launched over n without U on the
+ * host.  Rows nobody names are not touched, not even rewritten.  A state table the algorithm does not use must be NULL,
+ * one it uses must not be.  PRECONDITION, not detected: the valid entries name distinct rows; a repeated row is a lost
+ * update, not a fault.  (One lane group per entry, 16-byte accesses when dim % 4 == 0 and every base is 16-byte aligned;
+ * each row read once, each written row written once, one kernel.) */
+GLX_API int glx_embedding_update(int device, int algo, float* W, float* state1, float* state2, int64_t num_rows,
+                                 int32_t dim, const int64_t* urows, const float* ug, int32_t n, float alpha, float eps,
+                                 float beta1, float c1, float beta2, float c2, void* stream);
 
 /* ---- negative sampling: replaces RandomNegativeSampler (random_negative_sampler.cc:30-63),
  * InDegreeNegativeSampler / SoftInDegreeNegativeSampler (in_degree_negative_sampler.cc:29-135)
