@@ -633,15 +633,25 @@ class Features:
                                    pc[0], kind, _stream(kind, self.device)))
         return emb, cnt
 
-    def aggregate_arg(self, op, node_ids, segment_ids, num_segments, default_attr=0.0):
+    def aggregate_arg(self, op, node_ids, segment_ids, num_segments, default_attr=0.0, out=None):
         """aggregate() for Max / Min that also records where each extreme came from (glx_aggregate_arg)
         -> (emb[num_segments, D] float32, counts[num_segments] int32, arg[num_segments, D] int32): emb and counts are
         aggregate()'s bit for bit; arg is the request position of the first element that attains the extreme, -1 when
-        nothing replaced the fold's start value.  aggregate_backward() takes counts and arg."""
+        nothing replaced the fold's start value.  aggregate_backward() takes counts and arg.
+        out=(emb, counts, arg): buffers of those shapes and types to write into (torch CUDA tensors or numpy arrays,
+        handed to the entry point as they are); anything of another shape or type raises ValueError."""
         if isinstance(op, str):
             op = AGGREGATOR_IDS[op]
         n = int(node_ids.shape[0])
-        if _is_torch(node_ids):
+        if out is not None:
+            emb, cnt, arg = out
+            want = (("emb", emb, (num_segments, self.dim), "float32"), ("counts", cnt, (num_segments,), "int32"),
+                    ("arg", arg, (num_segments, self.dim), "int32"))
+            for name, buf, shape, dtype in want:
+                if tuple(buf.shape) != shape or str(buf.dtype).replace("torch.", "") != dtype:
+                    raise ValueError("aggregate_arg: out's {} must be {} of shape {}, not {} of shape {}".format(
+                        name, dtype, shape, buf.dtype, tuple(buf.shape)))
+        elif _is_torch(node_ids):
             import torch
             emb = torch.empty((num_segments, self.dim), dtype=torch.float32, device=node_ids.device)
             cnt = torch.empty((num_segments,), dtype=torch.int32, device=node_ids.device)
