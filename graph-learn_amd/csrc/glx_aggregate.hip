@@ -177,6 +177,8 @@ struct AggArgs {
   float default_attr;
   int32_t col0, ncols;       // the columns [col0, col0 + ncols) this launch reduces (a column slice, or all)
   int32_t store_mode;        // glx_aggregate_grp_kernel: 0 non-temporal output stores (default), 1 plain stores (ablation)
+  int32_t load_repeats;      // glx_aggregate_grp_kernel, Max / Min over a whole wave: 0 a row the segment already folded is not
+                             // loaded again, 1 every position is loaded (launch_agg_grp chooses)
   int32_t segs_per_group;    // glx_aggregate_grp_kernel: consecutive segments one lane group reduces
   int32_t xcd_slices;        // glx_aggregate_grp_kernel: > 1 = workgroup b reduces column slice b % xcd_slices (ncols each)
   int32_t stripe_chunk;      // glx_aggregate_grp_kernel: > 0 = XCD stripes of this many segment blocks (agg_stripe_block)
@@ -371,6 +373,71 @@ __device__ __forceinline__ void agg_grp_batch(const AggArgs& a, const int32_t (&
   }
 }
 
+// ---- Max / Min over a whole wave: a row the segment has already folded is not loaded again -------------------
+// The fold is a select -- Max (l < r) ? r : l from -37, Min (r < l) ? r : l from FLT_MAX -- so the accumulator is never
+// NaN (a NaN operand is never selected, the start is none), once x has been folded it is >= x (Max; <= x for Min) in
+// the order of the non-NaN floats, and every later fold only moves it further: folding the same row AGAIN selects
+// nothing, whatever came in between (+-0, +-inf, NaN elements, values at or below -37, and the unknown ids, which all
+// fold default_attr).  Dropping the later occurrences and folding the rest in the same order is therefore exact, bit
+// for bit.  It pays where draws with replacement repeat the few neighbours of a low-degree seed: C3's hop 1 (fanout
+// 25) holds 5.7 distinct rows per segment, and every repeat was a 1 KiB wave load through the vector-memory pipeline
+// that launch is bound by.  Sum, Mean and Prod have no such property and never come here.
+//
+// Lane c holds the row of chunk slot c.  keep = the first slot of every distinct row among the slots [lo, hi): one
+// iteration per DISTINCT row -- the lowest pending slot survives and takes every slot that holds its row out of the
+// pending set.  The masks live in SGPRs and the branch is scalar.
+// (Not the 16-byte loads of a half table, GLX_AGG_HALF_LD16: an ablation already, and the masks cost it a wave of occupancy.)
+template <int OP, int G, int VEC>
+constexpr bool kAggSkipRepeats = G == 64 && VEC == 4 && (OP == GLX_AGG_MAX || OP == GLX_AGG_MIN);
+
+__device__ __forceinline__ uint64_t agg_first_occurrences(int32_t myrow, int32_t lo, int32_t hi) {
+  uint64_t pending = (hi >= 64 ? ~(uint64_t)0 : (((uint64_t)1 << hi) - 1)) & ~(((uint64_t)1 << lo) - 1);
+  uint64_t keep = 0;
+  while (pending != 0) {
+    const int u = __builtin_ctzll(pending);
+    const int32_t r = __builtin_amdgcn_readlane(myrow, u);
+    const uint64_t bit = (uint64_t)1 << u;
+    keep |= bit;
+    pending &= ~(__ballot(myrow == r) | bit);
+  }
+  return keep;
+}
+
+// agg_grp_batch over the next `count` set bits of keep (kFull: count == U), lowest first, instead of consecutive
+// slots: the same loads back to back, the same fold.  The bits taken are cleared.
+template <int OP, int VEC, int U, int NSRC, bool kFull, int DT>
+__device__ __forceinline__ void agg_keep_batch(const AggArgs& a, int32_t myrow, uint64_t& keep, int32_t count, uint32_t col_ld,
+                                               float __attribute__((ext_vector_type(VEC)))& acc) {
+  typedef float vec_t __attribute__((ext_vector_type(VEC)));
+  int32_t row[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    row[u] = -1;
+    if (kFull || u < count) {
+      row[u] = __builtin_amdgcn_readlane(myrow, __builtin_ctzll(keep));
+      keep &= keep - 1;
+    }
+  }
+  agg_raw_vec<DT, VEC> val[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    if (kFull || u < count) {
+      const int32_t r = row[u] >= 0 ? row[u] : 0;  // as in agg_grp_batch
+      val[u] = agg_load_raw<DT, VEC>(agg_row_ptr32<NSRC, DT>(a, r) + col_ld);
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    if (kFull || u < count) {
+      vec_t x = agg_up<DT, VEC>(val[u]);
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) x[v] = row[u] < 0 ? a.default_attr : x[v];
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) acc[v] = agg_combine<OP>(acc[v], x[v]);
+    }
+  }
+}
+
 // XCD stripes: the slice-local workgroup index j (j = b / n for workgroup b and n column slices) -> the segment block
 // it reduces.  Workgroup b runs on XCD b % 8 (observed placement, used for speed only), so the P = 8 / n XCDs that
 // share a slice see j = P k + m (m = the XCD's label, k = its k-th workgroup of the launch).  The permutation hands
@@ -443,7 +510,28 @@ __global__ __launch_bounds__(256) void glx_aggregate_grp_kernel(AggArgs a) {
       vec_t acc;
 #pragma unroll
       for (int v = 0; v < VEC; ++v) acc[v] = agg_init<OP>();
-      for (int32_t base = s0; base < s1; base += U) {
+      bool folded = false;
+      if constexpr (kAggSkipRepeats<OP, G, VEC>) {
+        static_assert(IDR == 1, "a whole wave keeps one id register");
+        if (a.load_repeats == 0) {
+          // piece by piece of up to kChunk positions, each resident in the chunk as a whole: the first occurrences of
+          // the piece, folded in order.  (A repeat across two pieces is loaded again: skipping any subset is exact.)
+          for (int32_t pos = s0; pos < s1;) {
+            const int32_t piece_end = (s1 - pos) < kChunk ? s1 : pos + kChunk;
+            if (piece_end - chunk_base > kChunk) {
+              chunk_base = pos;
+              agg_chunk_load<G, IDR>(a, chunk_base, pos_end, c, myrow);
+            }
+            uint64_t keep = agg_first_occurrences(myrow[0], pos - chunk_base, piece_end - chunk_base);
+            int32_t m = __builtin_popcountll(keep);
+            for (; m >= U; m -= U) agg_keep_batch<OP, VEC, U, NSRC, true, DT>(a, myrow[0], keep, U, col_ld, acc);
+            if (m > 0) agg_keep_batch<OP, VEC, U, NSRC, false, DT>(a, myrow[0], keep, m, col_ld, acc);
+            pos = piece_end;
+          }
+          folded = true;
+        }
+      }
+      for (int32_t base = s0; !folded && base < s1; base += U) {
         const int32_t stop = (s1 - base) < U ? s1 : base + U;
         if (stop > chunk_base + kChunk) {  // the batch runs past the chunk: next chunk starts at this batch
           chunk_base = base;
@@ -627,6 +715,8 @@ struct AggKnobs {
   std::atomic<int> chunk{0};    // GLX_AGG_XCD_CHUNK: segment blocks per XCD stripe chunk (0 = kXcdStripeChunk)
   std::atomic<int> half_ld16{0};// GLX_AGG_HALF_LD16=1: half tables in the grouped kernel with 16-byte loads of 8 columns per
                                 // lane instead of 8-byte loads over the float32 lane-to-column map (ablation)
+  std::atomic<int> repeats{0};  // GLX_AGG_REPEATS=1: Max / Min load every position of a segment, repeated rows included (ablation);
+                                // 2: first occurrences only whatever the segment length; 0 = by length (launch_agg_grp)
 };
 
 AggKnobs& agg_knobs() {
@@ -648,6 +738,7 @@ AggKnobs& agg_knobs() {
     if (getenv("GLX_AGG_XCD_STRIPES")) k.stripes = env("GLX_AGG_XCD_STRIPES");
     k.chunk = env("GLX_AGG_XCD_CHUNK");
     k.half_ld16 = env("GLX_AGG_HALF_LD16");
+    k.repeats = env("GLX_AGG_REPEATS");
   });
   return k;
 }
@@ -701,6 +792,8 @@ int agg_grp_unroll(int32_t fanout, int32_t avg_len) {
   return best;
 }
 
+constexpr int32_t kAggSkipMinLen = 16;
+
 template <int OP, int G, int VEC, int NSRC, int IDR, int DT>
 void launch_agg_grp(AggArgs a, int32_t num_ids, hipStream_t s) {
   const int32_t avg = a.num_segments > 0 ? (int32_t)(num_ids / a.num_segments) : 0;
@@ -724,6 +817,18 @@ void launch_agg_grp(AggArgs a, int32_t num_ids, hipStream_t s) {
   if (S < 1) S = 1;
   a.segs_per_group = S;
   a.store_mode = agg_knobs().store.load(std::memory_order_relaxed);
+  // Max / Min, a whole wave per segment: rows a segment has already folded are not loaded again (agg_first_occurrences)
+  // when the segments average kAggSkipMinLen positions or more.  Same process, six alternations, C3 store, ms with every
+  // position loaded -> first occurrences only (profiles/r16/agg_repeat_ab.txt): hop 1 (fanout 25, 5.25 distinct rows per
+  // segment) 0.0928 -> 0.0713; hop 2 (fanout 10, 8.78 distinct) 1.6026 -> 1.6384, a LOSS beyond the spread: its saved
+  // loads are cache hits of a fabric-bound launch and the mask loop delays every wave's first load; rows uniform over
+  // the table (nothing to skip) 3.5054 -> 3.5097.  Those two launches give 5 ns per mask iteration against 18 ns per
+  // load saved, i.e. the masks pay once more than a fifth of the positions repeat -- which the launcher cannot see, so
+  // the rule is on what it can: the longer a segment of draws with replacement, the larger that share, and 16 lies
+  // between the fanout that lost and the one that won.  GLX_AGG_REPEATS = 1 loads every position whatever the length
+  // (the behaviour before round 16), 2 skips whatever the length.
+  const int repeats = agg_knobs().repeats.load(std::memory_order_relaxed);
+  a.load_repeats = repeats == 1 ? 1 : (repeats == 2 ? 0 : (avg >= kAggSkipMinLen ? 0 : 1));
   const int64_t groups = ((int64_t)a.num_segments + S - 1) / S;
   const int64_t seg_blocks = (groups + (256 / G) - 1) / (256 / G);
   const int32_t nsl = a.xcd_slices > 1 ? a.xcd_slices : 1;
@@ -1217,6 +1322,7 @@ extern "C" int glx_tune(const char* name, int32_t value) {
   else if (strcmp(name, "agg_xcd_stripes") == 0) slot = &k.stripes;
   else if (strcmp(name, "agg_xcd_chunk") == 0) slot = &k.chunk;
   else if (strcmp(name, "agg_half_ld16") == 0) slot = &k.half_ld16;
+  else if (strcmp(name, "agg_repeats") == 0) slot = &k.repeats;
   else if (strcmp(name, "seg_epochs_before_wrap") == 0) {
     // test aid: the calling thread's segment-word buffers hand out `value` more epochs before their counter wraps
     GLX_REQUIRE(value >= 0, "seg_epochs_before_wrap must be >= 0");

@@ -1081,7 +1081,8 @@ GLX_API int glx_probe_bandwidth(int device, int kind, int64_t bytes, int64_t uni
  * process.  Each is read from the environment once (first use) and may be set here at any time; 0 restores the
  * product's default.  Names: "agg_mfma" (GLX_AGG_MFMA), "agg_unroll" (GLX_AGG_UNROLL), "agg_slices" (GLX_AGG_SLICES),
  * "agg_legacy" (GLX_AGG_LEGACY), "agg_segs" (GLX_AGG_SEGS), "agg_xcd_slices" (GLX_AGG_XCD_SLICES), "agg_occupancy"
- * (GLX_AGG_OCCUPANCY), "agg_store" (GLX_AGG_STORE).  Results are
+ * (GLX_AGG_OCCUPANCY), "agg_store" (GLX_AGG_STORE), "agg_repeats" (GLX_AGG_REPEATS: Max / Min load every position of a
+ * segment = 1, only the first occurrence of every row = 2, by segment length = 0).  Results are
  * bit-identical under every setting.  Unknown name: GLX_INVALID_ARGUMENT.
  * Test knobs of the side paths, same rules, -1 restores the default: "cond_sequential" (GLX_COND_SEQUENTIAL),
  * "dist_no_bitmap" (GLX_DIST_NO_BITMAP), "filter_span_cap" (GLX_FILTER_SPAN_CAP), "filter_dedup_min_rows"
