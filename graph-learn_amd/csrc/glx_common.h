@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <string.h>
 
 #include "glx.h"
 
@@ -236,6 +237,55 @@ struct GlxEwRec {
   int64_t nbr_alias;
 };
 
+// The same record without what an int32 graph does not use: the padding word and the high halves of the two
+// neighbour ids.  20 bytes, three to a 64-byte sector (six to a 128-byte line where GlxEwRec fits four), so a launch
+// whose time follows the lines it fetches touches fewer of them.  Built when every edge id AND every neighbour id
+// fits an int32 (negative ids stay signed and widen on the way out) and E <= 2^31.
+struct GlxEwRec20 {
+  float prob;
+  int32_t eid_self;
+  int32_t eid_alias;
+  int32_t nbr_self;
+  int32_t nbr_alias;
+};
+static_assert(sizeof(GlxEwRec20) == 20 && alignof(GlxEwRec20) == 4, "GlxEwRec20 is five packed words");
+
+// CSR slot g lives at byte (g / 3) * 64 + (g % 3) * 20 of a 256-byte-aligned table: no record crosses a 64-byte
+// boundary and the last 4 bytes of every sector are unused.  The byte offset passes 2^31 at 100.7 M edges and 2^32
+// at 201 M, so both the division and the offset stay 64-bit.
+__host__ __device__ inline uint64_t glx_ew20_offset(uint64_t g) {
+  const uint64_t sector = g / 3u;
+  return sector * 64u + (g - sector * 3u) * 20u;
+}
+// The same for a slot index below 2^32: a 32-bit division (the tables exist only where E <= 2^31).
+__host__ __device__ inline uint64_t glx_ew20_offset32(uint32_t g) {
+  const uint32_t sector = g / 3u;
+  return (uint64_t)sector * 64u + (g - sector * 3u) * 20u;
+}
+// The whole record in two loads, one of 16 bytes and one of 4, issued together (records are 4-byte aligned, which is
+// all a global dwordx4 load asks for).  Left to itself the compiler loads prob, waits, and only then loads the two
+// fields the comparison picked: two dependent round trips to the same sector.
+__device__ __forceinline__ GlxEwRec20 glx_ew20_load(const char* __restrict__ p) {
+  typedef uint32_t GlxU32x4 __attribute__((ext_vector_type(4)));
+  GlxU32x4 lo;
+  uint32_t hi;
+  __builtin_memcpy(&lo, __builtin_assume_aligned(p, 4), 16);
+  __builtin_memcpy(&hi, __builtin_assume_aligned(p + 16, 4), 4);
+  return GlxEwRec20{__uint_as_float(lo.x), (int32_t)lo.y, (int32_t)lo.z, (int32_t)lo.w, (int32_t)hi};
+}
+__host__ __device__ inline uint64_t glx_ew20_table_bytes(uint64_t num_edges) { return (num_edges + 2u) / 3u * 64u; }
+
+// Which EdgeWeight records a weighted graph keeps (glx_graph_build_alias): 20, 32 or 0 bytes per slot.  env is the
+// value of GLX_EW_PACKED at the build (nullptr = unset): "0" builds none, "32" forces the 32-byte records, anything
+// else takes the densest record the ids allow.
+inline int glx_ew_record_bytes_rule(bool eids_fit_int32, bool nbrs_fit_int32, int64_t num_edges, const char* env) {
+  if (num_edges <= 0 || (env && env[0] == '0')) return 0;
+  if (!eids_fit_int32) return 0;
+  const bool force32 = env && strcmp(env, "32") == 0;
+  if (!force32 && nbrs_fit_int32 && num_edges <= ((int64_t)1 << 31)) return 20;
+  return 32;
+}
+
 // Test / A-B knobs of the paths beside the hot one, read from the environment ONCE (first use: operators run on up to
 // 32 pool threads and getenv is not something to call per request) and settable at run time through glx_tune().
 // -1 = unset (the product's default).
@@ -267,7 +317,8 @@ struct glx_graph {
   GlxIdMapStorage dst_map;  // destination id -> index into dst_count (with alias_indeg), for in-degree lookups
   int64_t* dst_count;     // [num_dst] in-degree of every distinct destination id
   int64_t num_dst;
-  GlxEwRec* ew;           // [E] packed EdgeWeight records, or nullptr (edge ids beyond int32)
+  GlxEwRec* ew;           // [E] packed EdgeWeight records, or nullptr (edge ids beyond int32, or ew20 is kept)
+  char* ew20;             // GlxEwRec20 of slot g at byte glx_ew20_offset(g), or nullptr; at most one of ew / ew20 is kept
   int64_t* ts;            // [E] GetEdgeTimestamp of every slot (timestamp filters), or nullptr
   GlxIdMapStorage idmap;
   GlxIdMap map() const { return idmap.view(num_rows); }

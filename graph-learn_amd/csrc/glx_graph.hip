@@ -733,6 +733,35 @@ __global__ void glx_pack_ew_kernel(const int64_t* __restrict__ row_ptr, const Gl
   }
 }
 
+// The same into 20-byte records, three to a 64-byte sector (glx_ew20_offset); *bad is also set when a neighbour id
+// does not fit an int32.  The lane that writes the last record of a sector -- slot 2 of it, or slot E - 1 -- zeroes
+// the sector's 4 unused bytes (and those of the slots past E - 1), so the table has no uninitialised byte.
+__global__ void glx_pack_ew20_kernel(const int64_t* __restrict__ row_ptr, const GlxAdj* __restrict__ adj,
+                                     const GlxAlias* __restrict__ alias, int64_t V, int64_t E, char* __restrict__ out,
+                                     int* bad) {
+  // one wave per row: lanes stride over the row's slots
+  const int64_t row = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
+  const int lane = threadIdx.x & 63;
+  if (row >= V) return;
+  const int64_t s = row_ptr[row], e = row_ptr[row + 1];
+  for (int64_t i = s + lane; i < e; i += 64) {
+    const GlxAlias a = alias[i];
+    const GlxAdj self = adj[i];
+    const GlxAdj other = adj[s + a.alias];
+    if (self.eid > INT32_MAX || self.eid < INT32_MIN || other.eid > INT32_MAX || other.eid < INT32_MIN ||
+        self.nbr > INT32_MAX || self.nbr < INT32_MIN || other.nbr > INT32_MAX || other.nbr < INT32_MIN)
+      *bad = 1;
+    const uint64_t off = glx_ew20_offset((uint64_t)i);
+    *reinterpret_cast<GlxEwRec20*>(out + off) =
+        GlxEwRec20{a.prob, (int32_t)self.eid, (int32_t)other.eid, (int32_t)self.nbr, (int32_t)other.nbr};
+    const uint32_t in_sector = (uint32_t)(off & 63u) / 20u;
+    if (in_sector == 2u || i == E - 1) {
+      int32_t* rest = reinterpret_cast<int32_t*>(out + off + 20);
+      for (uint32_t w = 0; w < (2u - in_sector) * 5u + 1u; ++w) rest[w] = 0;
+    }
+  }
+}
+
 __global__ void glx_unpack_alias_kernel(const GlxAlias* __restrict__ tab, int64_t E,
                                         float* __restrict__ prob, int32_t* __restrict__ alias) {
   int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -772,6 +801,7 @@ void glx_graph_free(glx_graph* g) {
   if (g->dst_count) (void)hipFree(g->dst_count);
   glx_idmap_free(&g->dst_map);
   if (g->ew) (void)hipFree(g->ew);
+  if (g->ew20) (void)hipFree(g->ew20);
   if (g->ts) (void)hipFree(g->ts);
   glx_idmap_free(&g->idmap);
   delete g;
@@ -849,21 +879,32 @@ static int glx_graph_build_alias(glx_graph* g, hipStream_t s) {
     GLX_HIP(hipMalloc(&g->alias, (size_t)(E > 0 ? E : 1) * sizeof(GlxAlias)));
     int rc = glx_alias_build_launch(g->row_ptr, g->weight, V, E, g->alias, s);
     if (rc != GLX_OK) return rc;
-    const char* env = getenv("GLX_EW_PACKED");  // "0" disables the packed fast path
-    if (E > 0 && !(env && env[0] == '0')) {
-      GlxTemp bad;
-      GLX_HIP(hipMalloc(&bad.p, sizeof(int)));
+    // GLX_EW_PACKED, read once per build: "0" builds no records, "32" the 32-byte ones, anything else the densest
+    // the ids allow (glx_ew_record_bytes_rule).  The pack kernels find out whether the ids fit, so the build tries
+    // what the rule would pick for ids that do and steps down once per refusal; only one table is ever kept.
+    const char* env = getenv("GLX_EW_PACKED");
+    int bytes = glx_ew_record_bytes_rule(true, true, E, env);
+    GlxTemp bad;
+    if (bytes) GLX_HIP(hipMalloc(&bad.p, sizeof(int)));
+    const unsigned grid = (unsigned)((V * 64 + 255) / 256);
+    while (bytes) {
       GLX_HIP(hipMemsetAsync(bad.p, 0, sizeof(int), s));
-      GLX_HIP(hipMalloc(&g->ew, (size_t)E * sizeof(GlxEwRec)));
-      glx_pack_ew_kernel<<<(unsigned)((V * 64 + 255) / 256), 256, 0, s>>>(g->row_ptr, g->adj, g->alias, V, g->ew,
-                                                                         bad.as<int>());
+      if (bytes == 20) {
+        GLX_HIP(hipMalloc(&g->ew20, (size_t)glx_ew20_table_bytes((uint64_t)E)));
+        glx_pack_ew20_kernel<<<grid, 256, 0, s>>>(g->row_ptr, g->adj, g->alias, V, E, g->ew20, bad.as<int>());
+      } else {
+        GLX_HIP(hipMalloc(&g->ew, (size_t)E * sizeof(GlxEwRec)));
+        glx_pack_ew_kernel<<<grid, 256, 0, s>>>(g->row_ptr, g->adj, g->alias, V, g->ew, bad.as<int>());
+      }
       int h_bad = 0;
       GLX_HIP(hipMemcpyAsync(&h_bad, bad.p, sizeof(int), hipMemcpyDeviceToHost, s));
       GLX_HIP(hipStreamSynchronize(s));
-      if (h_bad) {
-        (void)hipFree(g->ew);
-        g->ew = nullptr;
-      }
+      if (!h_bad) break;
+      // 20 -> 32: a neighbour id or an edge id is beyond int32 (the 32-byte pack tells which); 32 -> 0: an edge id is
+      (void)hipFree(bytes == 20 ? (void*)g->ew20 : (void*)g->ew);
+      g->ew20 = nullptr;
+      g->ew = nullptr;
+      bytes = bytes == 20 ? 32 : 0;
     }
   }
   return GLX_OK;
@@ -951,7 +992,13 @@ extern "C" int glx_graph_info(const glx_graph* g, int64_t* num_rows, int64_t* nu
 
 extern "C" int glx_graph_edge_weight_packed(const glx_graph* g, int* packed) {
   GLX_REQUIRE(g != nullptr && packed != nullptr, "NULL argument");
-  *packed = g->ew != nullptr;
+  *packed = g->ew != nullptr || g->ew20 != nullptr;
+  return GLX_OK;
+}
+
+extern "C" int glx_graph_edge_weight_record_bytes(const glx_graph* g, int* bytes) {
+  GLX_REQUIRE(g != nullptr && bytes != nullptr, "NULL argument");
+  *bytes = g->ew20 ? 20 : g->ew ? 32 : 0;
   return GLX_OK;
 }
 

@@ -19,6 +19,7 @@ struct SampleArgs {
   const GlxAdj* adj;
   const GlxAlias* alias;
   const GlxEwRec* ew;
+  const char* ew20;  // GlxEwRec20 records at glx_ew20_offset(slot), or nullptr; a graph keeps at most one of ew / ew20
   const int64_t* src;
   const int64_t* rng_rows;  // nullptr: request row i uses stream i
   const int64_t* out_rows;  // nullptr: request row i answers into output row i (else into output row out_rows[i])
@@ -41,7 +42,8 @@ struct SampleArgs {
 
 __device__ __forceinline__ uint64_t sample_cc(const SampleArgs& a) { return a.cc_dev ? a.cc + *a.cc_dev : a.cc; }
 
-enum SlotOp { kSlotRandom = 0, kSlotEdgeWeight = 1, kSlotCircular = 2, kSlotReplicate = 3, kSlotEdgeWeightPacked = 4 };
+enum SlotOp { kSlotRandom = 0, kSlotEdgeWeight = 1, kSlotCircular = 2, kSlotReplicate = 3, kSlotEdgeWeightPacked = 4,
+              kSlotEdgeWeightCompact = 5 };
 
 // One thread = two consecutive output slots (2q, 2q+1) of one request row, i.e.
 // exactly one Philox block for the randomised ops.  Consecutive lanes own
@@ -63,7 +65,7 @@ __global__ __launch_bounds__(256) void glx_sample_slots_kernel(SampleArgs a, int
   if (a.prefix && row >= 0) deg = a.prefix[i];
   const int64_t obase = (a.out_rows ? a.out_rows[i] : (int64_t)i) * a.k;
   GlxPhilox blk;
-  if (OP == kSlotRandom || OP == kSlotEdgeWeight || OP == kSlotEdgeWeightPacked) {
+  if (OP == kSlotRandom || OP == kSlotEdgeWeight || OP == kSlotEdgeWeightPacked || OP == kSlotEdgeWeightCompact) {
     if (deg > 0) {
       const uint32_t rr = a.rng_rows ? (uint32_t)a.rng_rows[i] : (uint32_t)i;
       blk = glx_philox_block((uint32_t)q, rr, a.seed, sample_cc(a));
@@ -102,6 +104,20 @@ __global__ __launch_bounds__(256) void glx_sample_slots_kernel(SampleArgs a, int
         const GlxEwRec rec = a.ew[start + ix];
         const bool take_alias = rec.prob <= (rnd - (float)ix);
         r = take_alias ? GlxAdj{rec.nbr_alias, (int64_t)rec.eid_alias} : GlxAdj{rec.nbr_self, (int64_t)rec.eid_self};
+      }
+    } else if (OP == kSlotEdgeWeightCompact) {
+      if (deg > 0) {
+        // the same draw on a 20-byte record, three to a 64-byte sector: only the load differs, and the widening of
+        // the ids on the way out.  Compact records exist only where E <= 2^31 (glx_ew_record_bytes_rule), so the
+        // slot start + ix < 2^31 fits a uint32 and the division by 3 is a 32-bit one; the byte offset is 64-bit.
+        const uint64_t u = glx_draw_of(blk, (uint32_t)j);
+        const double rd = ((double)(u >> 11) * 0x1.0p-53) * (double)(deg - 1);
+        const float rnd = (float)rd;
+        const int32_t ix = (int32_t)rnd;
+        const GlxEwRec20 rec = glx_ew20_load(a.ew20 + glx_ew20_offset32((uint32_t)(start + ix)));
+        const bool take_alias = rec.prob <= (rnd - (float)ix);
+        r = take_alias ? GlxAdj{(int64_t)rec.nbr_alias, (int64_t)rec.eid_alias}
+                       : GlxAdj{(int64_t)rec.nbr_self, (int64_t)rec.eid_self};
       }
     } else if (pick >= 0) {
       r = a.adj[start + pick];
@@ -375,6 +391,7 @@ int sample_device(const glx_graph* g, int sampler, const SampleArgs& a, int padd
       // reference) reads neighbors_[0..k) -- out of bounds when deg < k.  glx
       // returns the first min(k, deg) slots then default-fills.
       if (!circular) launch_slots<kSlotReplicate>(a, s);
+      else if (a.ew20) launch_slots<kSlotEdgeWeightCompact>(a, s);
       else if (a.ew) launch_slots<kSlotEdgeWeightPacked>(a, s);
       else launch_slots<kSlotEdgeWeight>(a, s);
       break;
@@ -389,6 +406,7 @@ int sample_device(const glx_graph* g, int sampler, const SampleArgs& a, int padd
       SampleArgs b = a;
       b.alias = g->alias_indeg;
       b.ew = nullptr;
+      b.ew20 = nullptr;
       if (circular) launch_slots<kSlotEdgeWeight>(b, s);
       else launch_slots<kSlotReplicate>(b, s);
       break;
@@ -434,6 +452,7 @@ int glx_sample_prefix_device(const glx_graph* g, int sampler, const int64_t* d_s
   a.adj = g->adj;
   a.alias = nullptr;
   a.ew = nullptr;
+  a.ew20 = nullptr;
   a.src = d_src;
   a.rng_rows = d_rng;
   a.out_rows = nullptr;
@@ -462,6 +481,7 @@ int glx_sample_scatter_device(const glx_graph* g, int sampler, const int64_t* d_
   a.adj = g->adj;
   a.alias = g->alias;
   a.ew = g->ew;
+  a.ew20 = g->ew20;
   a.src = d_src;
   a.rng_rows = d_rows;
   a.out_rows = d_rows;
@@ -500,6 +520,7 @@ extern "C" int glx_sample_ex(const glx_graph* g, int sampler, const int64_t* src
   a.adj = g->adj;
   a.alias = g->alias;
   a.ew = g->ew;
+  a.ew20 = g->ew20;
   a.default_nbr = default_neighbor_id;
   a.seed = seed;
   a.cc = call_counter;

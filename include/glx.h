@@ -166,6 +166,15 @@ GLX_API int glx_graph_info(const glx_graph* g, int64_t* num_rows, int64_t* num_e
  * alias partner's (nbr, eid)}: built for a weighted graph whose edge ids all fit an int32, unless GLX_EW_PACKED was "0"
  * when the graph was created.  0: it draws from the alias tables and the adjacency (same answers).  Added under 5. */
 GLX_API int glx_graph_edge_weight_packed(const glx_graph* g, int* packed);
+/* *bytes = the size of those records: 20, 32 or 0 (none).  A weighted graph keeps ONE table, chosen when it is built:
+ *   20 -- {float prob, int32 eid_self, eid_alias, nbr_self, nbr_alias}, three to a 64-byte sector (slot g at byte
+ *         (g / 3) * 64 + (g % 3) * 20): every edge id and every neighbour id fits an int32 (negative ids included)
+ *         and num_edges <= 2^31;
+ *   32 -- the same with int64 neighbour ids: the edge ids fit an int32;
+ *    0 -- neither: the alias tables and the adjacency serve the draws.
+ * GLX_EW_PACKED at the build: "0" keeps none, "32" keeps the 32-byte records where the rule would keep either,
+ * anything else (or unset) is the rule above.  The answers are the same bit for bit under all three. */
+GLX_API int glx_graph_edge_weight_record_bytes(const glx_graph* g, int* bytes);
 /* EdgeWeightSampler on an UNWEIGHTED edge type: the reference reads GLOBAL_FLAG(DefaultWeight) for every edge
  * (MemoryEdgeStorage::GetWeight, memory_edge_storage.cc:97-103: an id beyond the empty weight array) and builds its
  * alias row from that (edge_weight_sampler.cc:78-92) -- with the default 0.0 every prob is 0/0 = NaN, no slot takes its
