@@ -11,13 +11,9 @@
 // EVERY element of the output is written; a position that is not consumed gets +0.0f.  No atomics: each (s, h) is
 // reduced by one lane group, or by one workgroup, with a fixed lane-to-element mapping and a fixed tree, so the same
 // inputs give the same bits on every call.  The ORDER of the sums is the mapping's and not part of the contract.
-#include "glx_common.h"
+#include "glx_segment_lanes.h"
 
 namespace {
-
-constexpr int kSmR = 4;                // items of a segment a lane keeps in registers between the passes
-constexpr int kSmLongItems = 1024;     // a segment with more items than this is walked by the whole workgroup
-constexpr int kSmTailBlocks = 1024;    // at most this many workgroups are launched for the unconsumed tail alone
 
 struct SmArgs {
   const float* a;          // forward: e; backward: alpha                 [num_ids, heads]
@@ -26,36 +22,6 @@ struct SmArgs {
   float* out;              // forward: alpha_out; backward: grad_e        [num_ids, heads]
   int32_t heads, fanout, num_ids, num_segments;
 };
-
-struct SmMax {
-  static __device__ __forceinline__ float op(float x, float y) { return fmaxf(x, y); }
-};
-struct SmAdd {
-  static __device__ __forceinline__ float op(float x, float y) { return x + y; }
-};
-
-// over the lanes of a G-lane group whose distance is a multiple of min_off: every one of them ends with the same bits
-// (both partners of an exchange compute the same commutative operation)
-template <typename OP, int G>
-__device__ __forceinline__ float sm_group_reduce(float x, int min_off) {
-  for (int off = G >> 1; off >= min_off; off >>= 1) x = OP::op(x, __shfl_xor(x, off, G));
-  return x;
-}
-
-// the same over the 256 threads of the workgroup, through LDS in a fixed tree; called by all 256 threads
-template <typename OP>
-__device__ __forceinline__ float sm_block_reduce(float x, int min_off, float* red) {
-  const int tid = threadIdx.x;
-  red[tid] = x;
-  __syncthreads();
-  for (int s = 128; s >= min_off; s >>= 1) {
-    if (tid < s) red[tid] = OP::op(red[tid], red[tid + s]);
-    __syncthreads();
-  }
-  const float r = red[tid & (min_off - 1)];
-  __syncthreads();  // red is free again
-  return r;
-}
 
 // One (segment, head set) by a group of G lanes.  The lane's items are base[i * stride], i = c, c + G, ..; the first
 // kSmR of them stay in registers between the passes, later ones are read again (and the exponentials parked in out).
@@ -146,22 +112,6 @@ __device__ __forceinline__ void sm_bwd_block(const float* __restrict__ alpha, co
   for (int64_t i = tid; i < items; i += 256) out[i * stride] = alpha[i * stride] * (grad[i * stride] - dot);
 }
 
-// the consumed positions [s0, s1) of segment sg
-__device__ __forceinline__ void sm_bounds(const SmArgs& a, int64_t sg, int32_t* s0, int32_t* s1) {
-  int64_t b0, b1;
-  if (a.seg_end) {
-    b0 = sg ? a.seg_end[sg - 1] : 0;
-    b1 = a.seg_end[sg];
-  } else {
-    b0 = sg * (int64_t)a.fanout;
-    b1 = b0 + a.fanout;
-  }
-  if (b0 > a.num_ids) b0 = a.num_ids;  // counts that promise more positions than the request has are cut
-  if (b1 > a.num_ids) b1 = a.num_ids;
-  *s0 = (int32_t)b0;
-  *s1 = (int32_t)b1;
-}
-
 // G lanes own one segment; a workgroup owns 256 / G consecutive segments.
 //   FLAT  (heads a power of two <= G)  the segment's [count, heads] block is one run of count * heads items; lane c
 //         owns items c, c + G, .. -- all of head c % heads, because heads divides G -- and a butterfly with strides
@@ -209,27 +159,14 @@ __global__ __launch_bounds__(256) void glx_segment_softmax_kernel(SmArgs a) {
       else sm_fwd_block(a.a + at, a.out + at, items, stride, min_off, red);
     }
   }
-  int64_t tail;  // the first position that no segment consumed
-  if (a.seg_end) {
-    tail = a.seg_end[a.num_segments - 1];
-    if (tail > a.num_ids) tail = a.num_ids;
-  } else {
-    tail = (int64_t)a.num_segments * a.fanout;
-  }
+  const int64_t tail = sm_tail(a);
   const int64_t end = (int64_t)a.num_ids * H;
   for (int64_t i = tail * H + blockIdx.x * 256LL + threadIdx.x; i < end; i += gridDim.x * 256LL) a.out[i] = 0.0f;
 }
 
-// the smallest group of 8 .. 64 lanes that covers `lanes`
-int sm_group_for(int64_t lanes) { return lanes <= 8 ? 8 : lanes <= 16 ? 16 : lanes <= 32 ? 32 : 64; }
-
 template <bool FLAT, bool BWD>
 void sm_launch_g(const SmArgs& a, int G, hipStream_t s) {
-  const int64_t seg_blocks = ((int64_t)a.num_segments + (256 / G) - 1) / (256 / G);
-  // enough workgroups for a tail nobody consumed, should the segments be few and the request long
-  int64_t tail_blocks = ((int64_t)a.num_ids * a.heads + 256 * 16 - 1) / (256 * 16);
-  if (tail_blocks > kSmTailBlocks) tail_blocks = kSmTailBlocks;
-  const unsigned blocks = (unsigned)(seg_blocks > tail_blocks ? seg_blocks : tail_blocks);
+  const unsigned blocks = sm_blocks(G, a.heads, a.num_ids, a.num_segments);
   switch (G) {
     case 8: glx_segment_softmax_kernel<8, FLAT, BWD><<<blocks, 256, 0, s>>>(a); break;
     case 16: glx_segment_softmax_kernel<16, FLAT, BWD><<<blocks, 256, 0, s>>>(a); break;
@@ -238,19 +175,13 @@ void sm_launch_g(const SmArgs& a, int G, hipStream_t s) {
   }
 }
 
-// The group width comes from the mean item count of a segment (the sizes alone: the counts live on the device).
+// the group width and the item mapping: sm_width (glx_segment_lanes.h)
 template <bool BWD>
 void sm_launch(const SmArgs& a, hipStream_t s) {
-  const int H = a.heads;
-  const bool flat = H <= 64 && (H & (H - 1)) == 0;
-  const int64_t items = flat ? (int64_t)a.num_ids * H : (int64_t)a.num_ids;
-  int G = sm_group_for((items + a.num_segments - 1) / a.num_segments);
-  if (flat) {
-    if (G < H) G = H;
-    sm_launch_g<true, BWD>(a, G, s);
-  } else {
-    sm_launch_g<false, BWD>(a, G, s);
-  }
+  bool flat;
+  const int G = sm_width(a.heads, a.num_ids, a.num_segments, &flat);
+  if (flat) sm_launch_g<true, BWD>(a, G, s);
+  else sm_launch_g<false, BWD>(a, G, s);
 }
 
 // the body both entry points share, behind their argument checks

@@ -48,6 +48,7 @@ EXPORTS = [
     "glx_aggregate", "glx_lookup", "glx_aggregate_arg", "glx_aggregate_backward",
     "glx_aggregate_weighted", "glx_aggregate_weighted_backward_x", "glx_aggregate_weighted_backward_w",
     "glx_segment_softmax", "glx_segment_softmax_backward",
+    "glx_gat_attention", "glx_gat_attention_backward",
     "glx_pair_dot", "glx_pair_dot_backward",
     "glx_rows_coalesce", "glx_embedding_update",
     "glx_partition", "glx_stitch_i64", "glx_stitch_f32", "glx_aggregate_stitch",
@@ -174,6 +175,9 @@ def lib():
         L.glx_aggregate_weighted_backward_w.argtypes = [ci, ci, vp, i64, i32, vp, i32, vp, i32, i32, f32, vp, vp, ci, vp]
         L.glx_segment_softmax.argtypes = [ci, vp, i32, vp, i32, i32, vp, ci, vp]
         L.glx_segment_softmax_backward.argtypes = [ci, vp, vp, i32, vp, i32, i32, vp, ci, vp]
+        L.glx_gat_attention.argtypes = [ci, vp, vp, i64, vp, i32, vp, i32, i32, f32, f32, f32, u64, u64, vp, vp, ci, vp]
+        L.glx_gat_attention_backward.argtypes = [ci, vp, vp, vp, vp, i64, vp, i32, vp, i32, i32, f32, f32, f32, u64, u64,
+                                                 vp, vp, vp, ci, vp]
         L.glx_pair_dot.argtypes = [ci, vp, i64, vp, i64, i32, i32, vp, vp, i32, i32, f32, vp, ci, vp]
         L.glx_pair_dot_backward.argtypes = [ci, ci, vp, vp, i32, i32, vp, i32, vp, i64, i32, i64, f32, vp, ci, vp]
         L.glx_rows_coalesce.argtypes = [ci, vp, i32, i64, i32, vp, vp, vp, vp, ci, vp]
@@ -827,6 +831,60 @@ def segment_softmax_backward(alpha, grad_alpha, cnt, num_segments, out=None, dev
     _check(lib().glx_segment_softmax_backward(device, pa[0], pg[0], heads, pc[0], n, num_segments, po[0], kind,
                                               _stream(kind, device)))
     return grad_e
+
+
+def _gat_shapes(s, t, rows):
+    """(n, num_segments, num_rows, heads) of a gat_attention request: s[S] or s[S, heads], t[M] or t[M, heads]"""
+    heads = 1 if len(s.shape) == 1 else int(s.shape[1])
+    assert (1 if len(t.shape) == 1 else int(t.shape[1])) == heads, "s and t must have the same number of heads"
+    return int(rows.shape[0]), int(s.shape[0]), int(t.shape[0]), heads
+
+
+def gat_attention(s, t, rows, cnt=None, negative_slope=0.2, default_attr=0.0, drop_p=0.0, seed=0, call=0,
+                  want_soft=True, out=None, soft_out=None, device=0):
+    """The attention coefficients of a GAT layer in one launch (glx_gat_attention) -> (alpha, soft), both [n, heads]
+    float32: the logit leaky_relu(s[segment, h] + t[rows[p], h]) of every position and head, its softmax over each
+    segment (`soft`, glx_segment_softmax's definition) and dropout on it (`alpha`: a kept element is soft / (1 - drop_p),
+    a dropped one +0.0; the mask is a pure function of (seed, call, p, h)).  s[S] or s[S, heads], t[M] or t[M, heads]
+    float32, rows[n] int64 (a value outside [0, M) reads default_attr: -inf masks the position), cnt[S] int32 (None: the
+    implied layout of n // S positions per segment).  want_soft=False with drop_p == 0 skips the second output (soft
+    is then None; alpha is it).  No atomics: the same bits on every call.  Torch CUDA tensors are device pointers on
+    the current stream, numpy arrays host pointers."""
+    n, num_segments, num_rows, heads = _gat_shapes(s, t, rows)
+    alpha = _weighted_out(out, s, (n, heads))
+    soft = soft_out
+    if soft is None and (want_soft or drop_p != 0.0):
+        soft = _weighted_out(None, s, (n, heads))
+    ps, pt, pr, pc, pso, pa = _ptr(s), _ptr(t), _ptr(rows), _ptr(cnt), _ptr(soft), _ptr(alpha)
+    kind = _kind(ps, pt, pr, pc, pso, pa)
+    if kind == PTR_DEVICE:
+        device = alpha.device.index or 0
+    _check(lib().glx_gat_attention(device, ps[0], pt[0], num_rows, pr[0], heads, pc[0], n, num_segments, negative_slope,
+                                   default_attr, drop_p, seed, call, pso[0], pa[0], kind, _stream(kind, device)))
+    return alpha, soft
+
+
+def gat_attention_backward(soft, grad_alpha, s, t, rows, cnt=None, negative_slope=0.2, default_attr=0.0, drop_p=0.0,
+                           seed=0, call=0, want_s=True, want_t=True, out=None, out_s=None, out_t=None, device=0):
+    """Gradients of gat_attention (glx_gat_attention_backward) -> (grad_e[n, heads], grad_s[S, heads] or None,
+    grad_t[M, heads] or None) from the forward's `soft`, the gradient of its `alpha` and the forward's own arguments
+    (the dropout mask is recomputed from seed and call).  grad_e is the gradient of the logits before leaky_relu;
+    grad_s sums it per segment (a fixed tree), grad_t per row of t in ascending position (the bits of
+    aggregate_backward(SUM, rows, None, grad_e, M)).  Every element is written; no atomics: the same bits on every
+    call.  want_s / want_t = False skips that gradient."""
+    n, num_segments, num_rows, heads = _gat_shapes(s, t, rows)
+    grad_e = _weighted_out(out, soft, (n, heads))
+    grad_s = _weighted_out(out_s, soft, (num_segments, heads)) if (want_s or out_s is not None) else None
+    grad_t = _weighted_out(out_t, soft, (num_rows, heads)) if (want_t or out_t is not None) else None
+    pso, pg, ps, pt, pr, pc = _ptr(soft), _ptr(grad_alpha), _ptr(s), _ptr(t), _ptr(rows), _ptr(cnt)
+    pe, pgs, pgt = _ptr(grad_e), _ptr(grad_s), _ptr(grad_t)
+    kind = _kind(pso, pg, ps, pt, pr, pc, pe, pgs, pgt)
+    if kind == PTR_DEVICE:
+        device = grad_e.device.index or 0
+    _check(lib().glx_gat_attention_backward(device, pso[0], pg[0], ps[0], pt[0], num_rows, pr[0], heads, pc[0], n,
+                                            num_segments, negative_slope, default_attr, drop_p, seed, call, pe[0],
+                                            pgs[0], pgt[0], kind, _stream(kind, device)))
+    return grad_e, grad_s, grad_t
 
 
 def _pair_counts(ia, ib, repeat):

@@ -1,6 +1,7 @@
 """Differentiable segment reductions, row gathers and pair scores over a device-resident matrix: the torch surface of
 glx_aggregate / glx_aggregate_arg / glx_aggregate_backward, of glx_aggregate_weighted and its two gradients, of
-glx_segment_softmax and its gradient and of glx_pair_dot and its gradient (include/glx.h).
+glx_segment_softmax and its gradient, of glx_gat_attention and its gradients and of glx_pair_dot and its gradient
+(include/glx.h).
 
 The role of tf.math.unsorted_segment_sum / unsorted_segment_mean under the reference's layers
 (graphlearn/python/nn/tf/layers/sage_conv.py:69-73, gcn_conv.py:73), for matrices that are computed on the way --
@@ -28,6 +29,13 @@ request with counts (unsorted_segment_softmax under the reference's gat_conv.py:
 where segment_softmax normalises each head over each segment's own positions, again without an atomic in either
 direction.
 
+gat_attention is the whole attention step of a GAT layer in one launch per direction (gat_conv.py:96-104): the logit
+leaky_relu(s[segment] + t[index]), its softmax over each segment and dropout on the coefficients,
+
+    alpha = gat_attention(src_e[seed_local], dst_e, nbr_local, S, counts=deg, dropout=0.4, seed=seed, call=step)
+
+with a dropout mask that is a function of (seed, call, position, head) alone: two runs give the same bits.
+
 pair_dot is the scoring step of the reference's unsupervised models (examples/tf/sage/train.py:56-57,
 python/nn/tf/loss.py:58): the dot product of the two endpoint embeddings of an edge, and of a source with each of its
 K sampled negatives,
@@ -39,7 +47,8 @@ without the two [n, D] gathers of `(z[src].unsqueeze(1) * z[neg]).sum(-1)` and w
 """
 import torch
 
-__all__ = ["segment_aggregate", "gather_rows", "weighted_segment_aggregate", "segment_softmax", "pair_dot"]
+__all__ = ["segment_aggregate", "gather_rows", "weighted_segment_aggregate", "segment_softmax", "gat_attention",
+           "pair_dot"]
 
 _OPS = {"sum": 0, "mean": 1, "max": 2, "min": 3, "prod": 4}
 
@@ -304,6 +313,97 @@ def segment_softmax(e, num_segments, counts=None):
   if n * heads > 2 ** 31 - 1:
     raise ValueError("{}: n * H exceeds int32".format(who))
   return _SegmentSoftmax.apply(e, counts, num_segments)
+
+
+class _GatAttention(torch.autograd.Function):
+
+  @staticmethod
+  def forward(ctx, s, t, index, counts, slope, drop_p, seed, call, default_attr):
+    sd, td = s.detach(), t.detach()
+    alpha, soft = _glx().gat_attention(sd, td, index, cnt=counts, negative_slope=slope, default_attr=default_attr,
+                                       drop_p=drop_p, seed=seed, call=call, want_soft=drop_p != 0.0)
+    ctx.cfg = (slope, default_attr, drop_p, seed, call)
+    ctx.has_counts = counts is not None
+    ctx.save_for_backward(*([alpha if soft is None else soft, sd, td, index] + ([counts] if counts is not None else [])))
+    return alpha
+
+  @staticmethod
+  def backward(ctx, grad):
+    _no_double_backward("gat_attention")
+    want_s, want_t = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    if not (want_s or want_t):
+      return (None,) * 9
+    saved = ctx.saved_tensors
+    soft, s, t, index = saved[:4]
+    counts = saved[4] if ctx.has_counts else None
+    slope, default_attr, drop_p, seed, call = ctx.cfg
+    grad = grad.to(torch.float32).contiguous()
+    _, gs, gt = _glx().gat_attention_backward(soft, grad, s, t, index, cnt=counts, negative_slope=slope,
+                                              default_attr=default_attr, drop_p=drop_p, seed=seed, call=call,
+                                              want_s=want_s, want_t=want_t)
+    return (gs, gt) + (None,) * 7
+
+
+def gat_attention(s, t, index, num_segments, counts=None, negative_slope=0.2, dropout=0.0, seed=0, call=0,
+                  default_attr=0.0):
+  """[n, H] attention coefficients of a GAT layer: for position p of segment sg and head h the logit
+  leaky_relu(s[sg, h] + t[index[p], h], negative_slope), its softmax over the segment's positions (segment_softmax's
+  definition and exact rules) and dropout on the result -- one kernel going forward, one going back, no atomics,
+  bit-identical on every run.
+
+  s        [S, H] or [S] contiguous float32 CUDA tensor, S == num_segments: the segment's half of the logit (a GAT
+           layer's attn_src of each seed); may require grad
+  t        [M, H] or [M] like s: the neighbour's half, one row per node; may require grad
+  index    int64 CUDA tensor of any shape (flattened, n positions): rows of t.  A value outside [0, M) reads
+           `default_attr` and passes no gradient to t; default_attr=float("-inf") is the mask for padded neighbours
+           (index -1): such a position gets exactly 0
+  counts   None: num_segments equal segments of n / num_segments positions; or an int32 [num_segments] tensor: segment
+           sg is the next counts[sg] positions, positions from counts.sum() on are 0
+  dropout  p in [0, 1): element (p, h) is kept, and scaled by 1 / (1 - p), iff word (p H + h) % 4 of Philox4x32-10
+           block (p H + h) // 4 under (seed, call) is >= floor(p 2^32) -- the engine's contract generator; the
+           backward recomputes the mask.  Use a new `call` for every step.
+  Only the gradients that are needed are computed.  Anything else raises ValueError.
+  """
+  who = "gat_attention"
+  for name, x in (("s", s), ("t", t)):
+    if not isinstance(x, torch.Tensor):
+      raise ValueError("{}: {} must be a torch tensor".format(who, name))
+    if x.dtype != torch.float32:
+      raise ValueError("{}: {} must be float32, not {}".format(who, name, x.dtype))
+    if not x.is_cuda or x.dim() not in (1, 2) or not x.is_contiguous():
+      raise ValueError("{}: {} must be a contiguous [N] or [N, H] CUDA tensor".format(who, name))
+  if not isinstance(index, torch.Tensor) or index.dtype != torch.int64:
+    raise ValueError("{}: index must be an int64 tensor".format(who))
+  if t.device != s.device or index.device != s.device:
+    raise ValueError("{}: s, t and index must live on one device".format(who))
+  heads = 1 if s.dim() == 1 else int(s.shape[1])
+  if heads < 1 or (1 if t.dim() == 1 else int(t.shape[1])) != heads:
+    raise ValueError("{}: s and t must have the same number (>= 1) of heads".format(who))
+  num_segments = int(num_segments)
+  if num_segments < 0 or int(s.shape[0]) != num_segments:
+    raise ValueError("{}: s must have one row per segment ({}), not {}".format(who, num_segments, int(s.shape[0])))
+  index = index.reshape(-1).contiguous()
+  n = index.numel()
+  if counts is not None:
+    if not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32 or counts.device != s.device:
+      raise ValueError("{}: counts must be an int32 tensor on s's device".format(who))
+    if counts.dim() != 1 or counts.numel() != num_segments:
+      raise ValueError("{}: counts must have one entry per segment".format(who))
+    counts = counts.contiguous()
+  elif num_segments == 0 or n % num_segments != 0:
+    raise ValueError("{}: without counts, index.numel() must be a multiple of num_segments".format(who))
+  if n * heads > 2 ** 31 - 1 or num_segments * heads > 2 ** 31 - 1:
+    raise ValueError("{}: n * H or num_segments * H exceeds int32".format(who))
+  negative_slope, dropout = float(negative_slope), float(dropout)
+  if not (negative_slope >= 0.0 and negative_slope != float("inf")):
+    raise ValueError("{}: negative_slope must be finite and >= 0".format(who))
+  if not 0.0 <= dropout < 1.0:
+    raise ValueError("{}: dropout must lie in [0, 1)".format(who))
+  seed, call = int(seed), int(call)
+  if not (0 <= seed < 2 ** 64 and 0 <= call < 2 ** 64):
+    raise ValueError("{}: seed and call must fit 64 unsigned bits".format(who))
+  return _GatAttention.apply(s.reshape(num_segments, heads), t.reshape(int(t.shape[0]), heads), index, counts,
+                             negative_slope, dropout, seed, call, float(default_attr))
 
 
 class _PairDot(torch.autograd.Function):

@@ -42,7 +42,7 @@ extern "C" {
  * glx_aggregate_arg, glx_aggregate_backward; weighted aggregation -- glx_aggregate_weighted,
  * glx_aggregate_weighted_backward_x, glx_aggregate_weighted_backward_w; ragged segment softmax -- glx_segment_softmax,
  * glx_segment_softmax_backward; pair scores -- glx_pair_dot, glx_pair_dot_backward; trainable embedding tables --
- * glx_rows_coalesce, glx_embedding_update. */
+ * glx_rows_coalesce, glx_embedding_update; fused GAT attention -- glx_gat_attention, glx_gat_attention_backward. */
 #define GLX_ABI_VERSION 5
 
 /* Exported symbols: libglx.so is built with -fvisibility=hidden. */
@@ -498,6 +498,52 @@ GLX_API int glx_segment_softmax(int device, const float* e, int32_t heads, const
 GLX_API int glx_segment_softmax_backward(int device, const float* alpha, const float* grad_alpha, int32_t heads,
                                          const int32_t* cnt, int32_t num_ids, int32_t num_segments, float* grad_e,
                                          int ptr_kind, void* stream);
+
+/* ---- fused GAT attention: logit, leaky_relu, softmax over the segments of a counts= request and dropout on the
+ * coefficients in one kernel, with its gradients.  The attention step of the reference's GATConv
+ * (python/nn/tf/layers/gat_conv.py:96-104: leaky_relu(self_e + nbr_e), unsorted_segment_softmax,
+ * python/nn/tf/utils/softmax.py:24-50, tf.nn.dropout on the coefficients). ------------------------------------------
+ * Common to the two entry points:
+ *   s[num_segments * heads]   float32, row-major: the segment-side half of the logit (attn_src of each seed)
+ *   t[num_rows * heads]       float32, row-major: the neighbour-side half, one row per node; num_rows < 2^31
+ *   rows[num_ids]             int64 rows of t; a value outside [0, num_rows) reads default_attr and gets no gradient
+ *   cnt[num_segments]         glx_segment_softmax's layout (clamped prefix sums cut at num_ids); NULL: the implied
+ *                             layout of num_ids / num_segments positions per segment, num_ids % num_segments == 0
+ *   negative_slope            finite and >= 0;  0 <= drop_p < 1;  heads >= 1;  num_ids * heads and
+ *                             num_segments * heads <= INT32_MAX
+ * Arguments are checked before any device use.  EVERY element of every output is written; a position that is not
+ * consumed gets +0.0f.  No float atomics: one lane group (a workgroup for a long segment) reduces each (segment,
+ * head) with a fixed mapping and tree -- the same inputs give the same bits on every call; the ORDER of the sums is
+ * the mapping's and not part of the contract.
+ *
+ * glx_gat_attention: for a consumed position p of segment sg and head h
+ *     tv = t[rows[p], h] (default_attr for a row out of range);  pre = fadd_rn(s[sg, h], tv);
+ *     e  = pre > 0 ? pre : fmul_rn(pre, negative_slope)          -- torch's leaky_relu(a + b), never contracted
+ *     soft = glx_segment_softmax of these e: its bound and its exact rules (k == 1 is 1.0f, k equal logits are
+ *            1.0f / (float)k, -inf among finite logits is +0.0f, a NaN or +inf logit or only -inf ones make the
+ *            column NaN).  default_attr = -inf is the masking idiom: a padded neighbour (row -1) gets exactly +0.0f.
+ *     word = Philox4x32-10(counter = (i >> 2, 0, call lo, call hi), key = (seed lo, seed hi)).w[i & 3],  i = p * heads + h
+ *     keep = word >= T,  T = (uint32_t)floor((double)drop_p * 2^32);  scale = 1.0f / (1.0f - drop_p)
+ *     alpha = keep ? fmul_rn(soft, scale) : +0.0f;  drop_p == 0: alpha == soft bit for bit and no Philox is evaluated
+ * soft_out (the softmax before dropout, what the backward needs) may be NULL iff drop_p == 0. */
+GLX_API int glx_gat_attention(int device, const float* s, const float* t, int64_t num_rows, const int64_t* rows,
+                              int32_t heads, const int32_t* cnt, int32_t num_ids, int32_t num_segments,
+                              float negative_slope, float default_attr, float drop_p, uint64_t seed, uint64_t call,
+                              float* soft_out, float* alpha_out, int ptr_kind, void* stream);
+/* glx_gat_attention_backward: the mask is recomputed from (seed, call), not stored:
+ *     ga = keep ? fmul_rn(grad_alpha, scale) : +0.0f;  d = soft * (ga - sum_q soft_q * ga_q)  (glx_segment_softmax_backward's
+ *     bound);  grad_e = pre > 0 ? d : fmul_rn(d, negative_slope), pre recomputed from s, t and rows
+ *     grad_s[sg, h] = the sum of the segment's grad_e, by the same lane group in a fixed tree: within
+ *                     k * 2^-24 * sum |terms| of the exact sum of the grad_e written; an empty segment is +0.0f
+ *     grad_t[r, h]  = +0.0f plus grad_e[p, h] over the consumed, in-range p with rows[p] == r in ascending p: the bits of
+ *                     glx_aggregate_backward(Sum) of grad_e with one position per segment; every row is written
+ * grad_e_out is required; grad_s_out and grad_t_out may each be NULL (not computed). */
+GLX_API int glx_gat_attention_backward(int device, const float* soft, const float* grad_alpha, const float* s,
+                                       const float* t, int64_t num_rows, const int64_t* rows, int32_t heads,
+                                       const int32_t* cnt, int32_t num_ids, int32_t num_segments, float negative_slope,
+                                       float default_attr, float drop_p, uint64_t seed, uint64_t call,
+                                       float* grad_e_out, float* grad_s_out, float* grad_t_out, int ptr_kind,
+                                       void* stream);
 
 /* ---- pair scores: the per-pair, optionally multi-head, dot product of two gathered rows, with its gradients with
  * respect to both tables.  The reference's unsupervised models score an edge as the dot product of its two endpoint
