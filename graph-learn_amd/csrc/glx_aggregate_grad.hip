@@ -25,11 +25,9 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "glx_common.h"
+#include "glx_segment_lanes.h"
 
 namespace {
-
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // ---- the recording forward (Max / Min) ---------------------------------------------------------------------
 struct ArgFwdArgs {
@@ -118,7 +116,7 @@ template <int OP, int DT>
 void launch_arg_fwd(ArgFwdArgs a, hipStream_t s) {
   constexpr size_t kElem = sizeof(typename AggElem<DT>::raw);
   const bool vec4 = a.dim % 4 == 0 && a.stride % 4 == 0 && (reinterpret_cast<uintptr_t>(a.X) % (4 * kElem)) == 0 &&
-                    (reinterpret_cast<uintptr_t>(a.emb) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.arg) & 15) == 0;
+                    glx_aligned16(a.emb) && glx_aligned16(a.arg);
   const int lanes = vec4 ? a.dim / 4 : a.dim;
   int G = 1;
   while (G < 64 && G < lanes) G <<= 1;
@@ -140,30 +138,15 @@ struct ClampCount {
   __host__ __device__ int64_t operator()(int32_t v) const { return v > 0 ? (int64_t)v : 0; }
 };
 
-// key / value / segment of every position.  seg_end: inclusive prefix sums of the (clamped) counts, or nullptr for
-// the implied layout of `fanout` positions per segment.
-__global__ __launch_bounds__(256) void glx_bwd_keys_kernel(const int64_t* __restrict__ rows, int32_t n, int64_t num_rows,
-                                                           const int64_t* __restrict__ seg_end, int32_t num_segments,
-                                                           int32_t fanout, uint32_t* __restrict__ keys,
+// key / value / segment of every position of the request L describes
+__global__ __launch_bounds__(256) void glx_bwd_keys_kernel(const int64_t* __restrict__ rows, int64_t num_rows,
+                                                           GlxSegLayout L, uint32_t* __restrict__ keys,
                                                            int32_t* __restrict__ vals, int32_t* __restrict__ seg_of) {
   const int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (p >= n) return;
-  bool consumed;
-  int32_t sg = 0;
-  if (seg_end != nullptr) {
-    consumed = p < seg_end[num_segments - 1];
-    if (consumed) {  // the first segment whose end lies beyond p
-      int32_t lo = 0, hi = num_segments - 1;
-      while (lo < hi) {
-        const int32_t mid = lo + ((hi - lo) >> 1);
-        if (seg_end[mid] > p) hi = mid; else lo = mid + 1;
-      }
-      sg = lo;
-    }
-    seg_of[p] = sg;
-  } else {
-    consumed = fanout > 0 && p / fanout < num_segments;
-  }
+  if (p >= L.num_ids) return;
+  int32_t sg;
+  const bool consumed = seg_of_position(L, p, &sg);
+  if (L.seg_end != nullptr) seg_of[p] = sg;
   const int64_t r = rows[p];
   const bool in = consumed && r >= 0 && r < num_rows;
   keys[p] = in ? (uint32_t)r : (uint32_t)num_rows;
@@ -199,10 +182,10 @@ int glx_agg_transpose(const int64_t* rows, const int32_t* cnt, int32_t n, int32_
     GLX_HIP(rocprim::inclusive_scan(nullptr, scan_tmp, rocprim::make_transform_iterator(cnt, ClampCount()),
                                     static_cast<int64_t*>(nullptr), (size_t)num_segments, rocprim::plus<int64_t>(), s));
   }
-  const size_t tmp_b = align256(sort_tmp > scan_tmp ? sort_tmp : scan_tmp);
-  const size_t ids_b = align256((size_t)n * sizeof(int32_t));
-  const size_t end_b = ragged ? align256((size_t)num_segments * sizeof(int64_t)) : 0;
-  const size_t ptr_b = align256((size_t)(num_rows + 1) * sizeof(int32_t));
+  const size_t tmp_b = glx_align256(sort_tmp > scan_tmp ? sort_tmp : scan_tmp);
+  const size_t ids_b = glx_align256((size_t)n * sizeof(int32_t));
+  const size_t end_b = ragged ? glx_align256((size_t)num_segments * sizeof(int64_t)) : 0;
+  const size_t ptr_b = glx_align256((size_t)(num_rows + 1) * sizeof(int32_t));
   int rc = lease->alloc(tmp_b + (ragged ? 5 : 4) * ids_b + end_b + ptr_b, s, 1);
   if (rc != GLX_OK) return rc;
   char* at = lease->as<char>();
@@ -225,16 +208,16 @@ int glx_agg_transpose(const int64_t* rows, const int32_t* cnt, int32_t n, int32_
     GLX_HIP(rocprim::inclusive_scan(tmp, scan_tmp, rocprim::make_transform_iterator(cnt, ClampCount()), seg_end,
                                     (size_t)num_segments, rocprim::plus<int64_t>(), s));
   }
-  const int32_t fanout = n / num_segments;
-  glx_bwd_keys_kernel<<<(unsigned)(((int64_t)n + 255) / 256), 256, 0, s>>>(rows, n, num_rows, seg_end, num_segments, fanout,
-                                                                         keys, vals, seg_of);
+  const int32_t fanout = n / num_segments;  // the keys kernel takes it raw: 0 consumes nothing
+  const GlxSegLayout L = {seg_end, fanout, n, num_segments};
+  glx_bwd_keys_kernel<<<(unsigned)(((int64_t)n + 255) / 256), 256, 0, s>>>(rows, num_rows, L, keys, vals, seg_of);
   GLX_HIP(rocprim::radix_sort_pairs(tmp, sort_tmp, keys, keys_s, vals, vals_s, (size_t)n, 0, bits, s));
   glx_bwd_row_ptr_kernel<<<(unsigned)((num_rows + 1 + 255) / 256), 256, 0, s>>>(keys_s, n, num_rows, row_ptr);
   out->row_ptr = row_ptr;
   out->pos = vals_s;
   out->seg_of = seg_of;
   out->seg_end = seg_end;
-  out->fanout = fanout > 0 ? fanout : 1;  // fanout == 0 consumes nothing: every list is empty, nothing divides by it
+  out->fanout = fanout > 0 ? fanout : 1;  // published at least 1: with 0 every list is empty, nothing divides by it
   return GLX_OK;
 }
 
@@ -244,7 +227,7 @@ int glx_agg_segment_ends(const int32_t* cnt, int32_t num_segments, hipStream_t s
   size_t scan_tmp = 0;
   GLX_HIP(rocprim::inclusive_scan(nullptr, scan_tmp, rocprim::make_transform_iterator(cnt, ClampCount()),
                                   static_cast<int64_t*>(nullptr), (size_t)num_segments, rocprim::plus<int64_t>(), s));
-  const size_t tmp_b = align256(scan_tmp);
+  const size_t tmp_b = glx_align256(scan_tmp);
   int rc = lease->alloc(tmp_b + (size_t)num_segments * sizeof(int64_t), s, 1);
   if (rc != GLX_OK) return rc;
   int64_t* ends = reinterpret_cast<int64_t*>(lease->as<char>() + tmp_b);
@@ -298,6 +281,7 @@ __global__ __launch_bounds__(256) void glx_aggregate_bwd_kernel(BwdArgs a) {
       if (base + c < l1) {
         my_pos = a.pos[base + c];
         my_seg = a.seg_of ? a.seg_of[my_pos] : my_pos / a.fanout;
+        // the RAW count, not seg_count: counts that promise more than the request has still divide by what they say
         if (OP == GLX_AGG_MEAN) my_div = (float)(a.cnt ? a.cnt[my_seg] : a.fanout);
       }
       const int32_t m = (l1 - base) < G ? (l1 - base) : G;
@@ -342,27 +326,18 @@ __global__ __launch_bounds__(256) void glx_aggregate_bwd_kernel(BwdArgs a) {
   }
 }
 
-template <int OP, int G, int VEC>
-void launch_bwd_g(const BwdArgs& a, hipStream_t s) {
-  const int64_t blocks = (a.num_rows + (256 / G) - 1) / (256 / G);
-  glx_aggregate_bwd_kernel<OP, G, VEC><<<(unsigned)blocks, 256, 0, s>>>(a);
-}
-
 // the smallest group that covers a row in one tile; rows wider than 64 lanes take column tiles
 template <int OP, int VEC>
 void launch_bwd_vec(const BwdArgs& a, hipStream_t s) {
-  const int lanes = (a.dim + VEC - 1) / VEC;
-  if (lanes <= 8) launch_bwd_g<OP, 8, VEC>(a, s);
-  else if (lanes <= 16) launch_bwd_g<OP, 16, VEC>(a, s);
-  else if (lanes <= 32) launch_bwd_g<OP, 32, VEC>(a, s);
-  else launch_bwd_g<OP, 64, VEC>(a, s);
+  const int G = glx_group_for((a.dim + VEC - 1) / VEC);
+  const unsigned blocks = (unsigned)((a.num_rows + (256 / G) - 1) / (256 / G));
+  glx_for_group(G, [&](auto g) { glx_aggregate_bwd_kernel<OP, decltype(g)::value, VEC><<<blocks, 256, 0, s>>>(a); });
 }
 
 template <int OP>
 void launch_bwd(const BwdArgs& a, hipStream_t s) {
-  bool vec4 = a.dim % 4 == 0 && (reinterpret_cast<uintptr_t>(a.grad_out) & 15) == 0 &&
-              (reinterpret_cast<uintptr_t>(a.grad_x) & 15) == 0;
-  if (OP == GLX_AGG_MAX || OP == GLX_AGG_MIN) vec4 = vec4 && (reinterpret_cast<uintptr_t>(a.arg) & 15) == 0;
+  bool vec4 = a.dim % 4 == 0 && glx_aligned16(a.grad_out) && glx_aligned16(a.grad_x);
+  if (OP == GLX_AGG_MAX || OP == GLX_AGG_MIN) vec4 = vec4 && glx_aligned16(a.arg);
   if (vec4) launch_bwd_vec<OP, 4>(a, s);
   else launch_bwd_vec<OP, 1>(a, s);
 }
@@ -395,11 +370,6 @@ int backward_device(int op, const int64_t* rows, const int32_t* cnt, const int32
   return GLX_OK;
 }
 
-const char* agg_op_name(int op) {
-  static const char* const kNames[] = {"Sum", "Mean", "Max", "Min", "Prod"};
-  return kNames[op];
-}
-
 }  // namespace
 
 extern "C" int glx_aggregate_arg(const glx_features* f, int op, const int64_t* node_ids, const int32_t* segment_ids,
@@ -408,7 +378,7 @@ extern "C" int glx_aggregate_arg(const glx_features* f, int op, const int64_t* n
   GLX_REQUIRE(f != nullptr, "features is NULL");
   GLX_REQUIRE(op >= GLX_AGG_SUM && op <= GLX_AGG_PROD, "unknown aggregator id %d", op);
   GLX_REQUIRE(op == GLX_AGG_MAX || op == GLX_AGG_MIN, "glx_aggregate_arg records the argument of Max and Min only, not of %s",
-              agg_op_name(op));
+              glx_agg_op_name(op));
   GLX_REQUIRE(num_ids >= 0 && num_segments >= 0, "negative sizes");
   GLX_REQUIRE(ptr_kind == GLX_PTR_HOST || ptr_kind == GLX_PTR_DEVICE, "bad ptr_kind");
   GLX_REQUIRE((int64_t)num_segments * f->dim <= INT32_MAX, "num_segments * dim exceeds int32 (tensor.h:47)");
@@ -465,7 +435,7 @@ extern "C" int glx_aggregate_backward(int device, int op, const int64_t* rows, c
   GLX_REQUIRE(num_segments == 0 || grad_out != nullptr, "grad_out is NULL");
   GLX_REQUIRE(num_rows == 0 || grad_x != nullptr, "grad_x is NULL");
   GLX_REQUIRE(num_segments == 0 || arg != nullptr || (op != GLX_AGG_MAX && op != GLX_AGG_MIN),
-              "arg is NULL: the %s backward needs the argument glx_aggregate_arg recorded", agg_op_name(op));
+              "arg is NULL: the %s backward needs the argument glx_aggregate_arg recorded", glx_agg_op_name(op));
   int rc = glx_init_device(device);
   if (rc != GLX_OK) return rc;
   if (num_rows == 0) return GLX_OK;
@@ -485,11 +455,7 @@ extern "C" int glx_aggregate_backward(int device, int op, const int64_t* rows, c
   rc = st.begin();
   if (rc == GLX_OK) {
     if (num_ids == 0 || num_segments == 0) {  // nothing was consumed: every row is zeros
-      hipError_t e = hipMemsetAsync(d_gx, 0, (size_t)num_rows * dim * sizeof(float), st.s);
-      if (e != hipSuccess) {
-        glx_set_error("hipMemsetAsync failed: %s", hipGetErrorString(e));
-        rc = GLX_INTERNAL;
-      }
+      rc = glx_zero_f32_async(d_gx, (size_t)num_rows * dim, st.s);
     } else {
       rc = backward_device(op, d_rows, d_cnt, d_arg, num_ids, num_segments, num_rows, dim, d_go, d_gx, st.s);
     }

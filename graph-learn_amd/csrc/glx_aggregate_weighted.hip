@@ -15,52 +15,25 @@
 //                a fixed lane-to-column mapping and a fixed cross-lane tree -- the same bits on every run, but the order
 //                over the columns is the mapping's, so this one is checked against a bound, not bit for bit
 // No float atomics anywhere.
-#include "glx_common.h"
+#include "glx_segment_lanes.h"
 
-// Two roundings per term: the multiply must never contract into the add, whatever -ffp-contract the build passes.
-// Neither __fmul_rn / __fadd_rn (plain `x * y` / `x + y` in this toolchain's headers, parsed before any pragma here)
-// nor `#pragma clang fp contract(off)` alone guarantees that: an explicit -ffp-contract=fast lets the backend fuse any
-// multiply with any add.  So the product goes through an empty asm that pins it in a register: the add that follows
-// takes an opaque operand and cannot become an FMA under any flag.  The pragma stays for the front end.
+// Two roundings per term: glx_fold_rn (glx_lane_groups.h) pins the product; the pragma is for the front end.
 #pragma clang fp contract(off)
 
 namespace {
 
-__device__ __forceinline__ float fold_rn(float acc, float w, float x) {
-  float t = w * x;        // rounded
-  asm("" : "+v"(t));      // opaque to the optimiser: no instruction, no contraction
-  return acc + t;         // rounded again
-}
-
 constexpr int kWU = 4;  // row loads in flight per lane
-
-// Positions of segment sg that the request really has: cnt[sg] clamped at 0 and, when the counts promise more than
-// num_ids positions, cut at num_ids -- Mean's divisor and the test for "empty" in all three kernels.  seg_end: the
-// inclusive prefix sums of the clamped counts, or nullptr for the implied layout (fanout positions each).
-__device__ __forceinline__ int32_t consumed_count(const int64_t* __restrict__ seg_end, int32_t sg, int32_t num_ids,
-                                                  int32_t fanout) {
-  if (seg_end == nullptr) return fanout;
-  int64_t b0 = sg ? seg_end[sg - 1] : 0, b1 = seg_end[sg];
-  if (b0 > num_ids) b0 = num_ids;
-  if (b1 > num_ids) b1 = num_ids;
-  return (int32_t)(b1 - b0);
-}
-
-const char* w_op_name(int op) {
-  static const char* const kNames[] = {"Sum", "Mean", "Max", "Min", "Prod"};
-  return kNames[op];
-}
 
 // ---- forward -----------------------------------------------------------------------------------------------
 struct WFwdArgs {
   const float* x;          // [num_rows, dim]
   const int64_t* rows;     // [num_ids]
   const float* w;          // [num_ids, heads]
-  const int64_t* seg_end;  // [num_segments] inclusive prefix sums of the clamped counts, or nullptr: the implied layout
+  GlxSegLayout seg;
   const int32_t* cnt;      // [num_segments], or nullptr
   float* emb;              // [num_segments, dim]
   int64_t num_rows;
-  int32_t dim, heads, C, fanout, num_ids, num_segments;
+  int32_t dim, heads, C;
   float default_attr;
 };
 
@@ -74,18 +47,9 @@ __global__ __launch_bounds__(256) void glx_aggregate_weighted_kernel(WFwdArgs a)
   typedef float vec_t __attribute__((ext_vector_type(VEC)));
   const int64_t gid = blockIdx.x * (int64_t)(256 / G) + threadIdx.x / G;
   const int c = threadIdx.x & (G - 1);
-  if (gid >= a.num_segments) return;  // whole groups leave
-  int64_t b0, b1;
-  if (a.seg_end) {
-    b0 = gid ? a.seg_end[gid - 1] : 0;
-    b1 = a.seg_end[gid];
-  } else {
-    b0 = gid * (int64_t)a.fanout;
-    b1 = b0 + a.fanout;
-  }
-  if (b0 > a.num_ids) b0 = a.num_ids;  // a cnt that promises more positions than the request has reads none of them
-  if (b1 > a.num_ids) b1 = a.num_ids;
-  const int32_t s0 = (int32_t)b0, s1 = (int32_t)b1;
+  if (gid >= a.seg.num_segments) return;  // whole groups leave
+  int32_t s0, s1;
+  seg_bounds(a.seg, gid, &s0, &s1);
   float* const out = a.emb + gid * (int64_t)a.dim;
   for (int32_t col_pass = 0; col_pass < a.dim; col_pass += G * VEC) {
     const int32_t col = col_pass + c * VEC;
@@ -124,7 +88,7 @@ __global__ __launch_bounds__(256) void glx_aggregate_weighted_kernel(WFwdArgs a)
         for (int u = 0; u < kWU; ++u) {
           if (j + u < m) {
 #pragma unroll
-            for (int v = 0; v < VEC; ++v) acc[v] = fold_rn(acc[v], wt[u], val[u][v]);
+            for (int v = 0; v < VEC; ++v) acc[v] = glx_fold_rn(acc[v], wt[u], val[u][v]);
           }
         }
       }
@@ -141,26 +105,18 @@ __global__ __launch_bounds__(256) void glx_aggregate_weighted_kernel(WFwdArgs a)
   }
 }
 
-// the smallest group of 8 .. 64 lanes that covers `lanes`
-int group_for(int lanes) { return lanes <= 8 ? 8 : lanes <= 16 ? 16 : lanes <= 32 ? 32 : 64; }
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 template <int OP, int VEC>
 void launch_wfwd_vec(const WFwdArgs& a, hipStream_t s) {
-  const int G = group_for((a.dim + VEC - 1) / VEC);
-  const unsigned blocks = (unsigned)(((int64_t)a.num_segments + (256 / G) - 1) / (256 / G));
-  switch (G) {
-    case 8: glx_aggregate_weighted_kernel<OP, 8, VEC><<<blocks, 256, 0, s>>>(a); break;
-    case 16: glx_aggregate_weighted_kernel<OP, 16, VEC><<<blocks, 256, 0, s>>>(a); break;
-    case 32: glx_aggregate_weighted_kernel<OP, 32, VEC><<<blocks, 256, 0, s>>>(a); break;
-    default: glx_aggregate_weighted_kernel<OP, 64, VEC><<<blocks, 256, 0, s>>>(a); break;
-  }
+  const int G = glx_group_for((a.dim + VEC - 1) / VEC);
+  const unsigned blocks = (unsigned)(((int64_t)a.seg.num_segments + (256 / G) - 1) / (256 / G));
+  glx_for_group(G, [&](auto g) {
+    glx_aggregate_weighted_kernel<OP, decltype(g)::value, VEC><<<blocks, 256, 0, s>>>(a);
+  });
 }
 
 template <int OP>
 void launch_wfwd(const WFwdArgs& a, hipStream_t s) {
-  const bool vec4 = a.dim % 4 == 0 && a.C % 4 == 0 && aligned16(a.x) && aligned16(a.emb);
+  const bool vec4 = a.dim % 4 == 0 && a.C % 4 == 0 && glx_aligned16(a.x) && glx_aligned16(a.emb);
   if (vec4) launch_wfwd_vec<OP, 4>(a, s);
   else launch_wfwd_vec<OP, 1>(a, s);
 }
@@ -171,8 +127,9 @@ struct WBwdXArgs {
   const float* w;         // [num_ids, heads]
   const float* grad_out;  // [num_segments, dim]
   float* grad_x;          // [num_rows, dim]
+  GlxSegLayout seg;       // the transpose's segment ends and fanout: Mean's divisor
   int64_t num_rows;
-  int32_t dim, heads, C, num_ids;
+  int32_t dim, heads, C;
 };
 
 // The sibling of glx_aggregate_bwd_kernel (glx_aggregate_grad.hip) that also fetches the weight of each list entry:
@@ -200,7 +157,7 @@ __global__ __launch_bounds__(256) void glx_aggregate_weighted_bwd_x_kernel(WBwdX
       if (base + c < l1) {
         my_pos = a.t.pos[base + c];
         my_seg = a.t.seg_of ? a.t.seg_of[my_pos] : my_pos / a.t.fanout;
-        if (OP == GLX_AGG_MEAN) my_div = (float)consumed_count(a.t.seg_end, my_seg, a.num_ids, a.t.fanout);
+        if (OP == GLX_AGG_MEAN) my_div = (float)seg_count(a.seg, my_seg);
       }
       const int32_t m = (l1 - base) < G ? (l1 - base) : G;
       for (int32_t j = 0; j < m; j += kWU) {
@@ -228,7 +185,7 @@ __global__ __launch_bounds__(256) void glx_aggregate_weighted_bwd_x_kernel(WBwdX
 #pragma unroll
             for (int v = 0; v < VEC; ++v) {
               const float t = OP == GLX_AGG_MEAN ? g[u][v] / dv[u] : g[u][v];
-              acc[v] = fold_rn(acc[v], wt[u], t);
+              acc[v] = glx_fold_rn(acc[v], wt[u], t);
             }
           }
         }
@@ -240,19 +197,16 @@ __global__ __launch_bounds__(256) void glx_aggregate_weighted_bwd_x_kernel(WBwdX
 
 template <int OP, int VEC>
 void launch_wbwd_x_vec(const WBwdXArgs& a, hipStream_t s) {
-  const int G = group_for((a.dim + VEC - 1) / VEC);
+  const int G = glx_group_for((a.dim + VEC - 1) / VEC);
   const unsigned blocks = (unsigned)((a.num_rows + (256 / G) - 1) / (256 / G));
-  switch (G) {
-    case 8: glx_aggregate_weighted_bwd_x_kernel<OP, 8, VEC><<<blocks, 256, 0, s>>>(a); break;
-    case 16: glx_aggregate_weighted_bwd_x_kernel<OP, 16, VEC><<<blocks, 256, 0, s>>>(a); break;
-    case 32: glx_aggregate_weighted_bwd_x_kernel<OP, 32, VEC><<<blocks, 256, 0, s>>>(a); break;
-    default: glx_aggregate_weighted_bwd_x_kernel<OP, 64, VEC><<<blocks, 256, 0, s>>>(a); break;
-  }
+  glx_for_group(G, [&](auto g) {
+    glx_aggregate_weighted_bwd_x_kernel<OP, decltype(g)::value, VEC><<<blocks, 256, 0, s>>>(a);
+  });
 }
 
 template <int OP>
 void launch_wbwd_x(const WBwdXArgs& a, hipStream_t s) {
-  const bool vec4 = a.dim % 4 == 0 && a.C % 4 == 0 && aligned16(a.grad_out) && aligned16(a.grad_x);
+  const bool vec4 = a.dim % 4 == 0 && a.C % 4 == 0 && glx_aligned16(a.grad_out) && glx_aligned16(a.grad_x);
   if (vec4) launch_wbwd_x_vec<OP, 4>(a, s);
   else launch_wbwd_x_vec<OP, 1>(a, s);
 }
@@ -261,143 +215,54 @@ void launch_wbwd_x(const WBwdXArgs& a, hipStream_t s) {
 struct WBwdWArgs {
   const float* x;          // [num_rows, dim]
   const int64_t* rows;     // [num_ids]
-  const int64_t* seg_end;  // [num_segments], or nullptr: the implied layout
+  GlxSegLayout seg;
   const int32_t* cnt;      // [num_segments], or nullptr
   const float* grad_out;   // [num_segments, dim]
   float* grad_w;           // [num_ids, heads]
   int64_t num_rows;
-  int32_t dim, heads, C, fanout, num_ids, num_segments;
-  int32_t sub;    // SUB: lanes of a sub-group (min(C / VEC, G))
-  int32_t steps;  // SUB: column tiles a head spans (C / VEC / G, at least 1)
+  int32_t dim, heads, C;
+  GlxHeadDots hd;
   float default_attr;
 };
 
-// G lanes own one POSITION p and write grad_w[p, 0 .. heads).  The lane-to-column mapping and the cross-lane tree are
-// fixed by (dim, heads, alignment) alone, so the same inputs give the same bits on every run.
-//   SUB  (L = C / VEC is a power of two)  lane c owns columns [VEC c, VEC c + VEC) of each tile of G * VEC columns; a
-//        head is a sub-group of min(L, G) consecutive lanes (times L / G tiles when L > G), reduced with __shfl_xor over
-//        the sub-group; its first lane writes.
-//   !SUB a loop over the heads: lane c owns elements c, c + G, .. of the head's L vectors, the whole group reduces,
-//        lane 0 writes.
-// A position that was not consumed writes +0.0f; an out-of-range row multiplies a row of default_attr.
+// G lanes own one POSITION p and write grad_w[p, 0 .. heads): glx_head_dots (glx_lane_groups.h) of the segment's
+// grad_out row and the position's table row.  A position that was not consumed writes +0.0f; an out-of-range row
+// multiplies a row of default_attr.
 template <int OP, int G, int VEC, bool SUB>
 __global__ __launch_bounds__(256) void glx_aggregate_weighted_bwd_w_kernel(WBwdWArgs a) {
-  typedef float vec_t __attribute__((ext_vector_type(VEC)));
   const int64_t p = blockIdx.x * (int64_t)(256 / G) + threadIdx.x / G;
   const int c = threadIdx.x & (G - 1);
-  if (p >= a.num_ids) return;  // whole groups leave
+  if (p >= a.seg.num_ids) return;  // whole groups leave
   float* const out = a.grad_w + p * (int64_t)a.heads;
-  bool consumed;
-  int32_t sg = 0;
-  if (a.seg_end) {
-    consumed = p < a.seg_end[a.num_segments - 1];
-    if (consumed) {  // the first segment whose end lies beyond p
-      int32_t lo = 0, hi = a.num_segments - 1;
-      while (lo < hi) {
-        const int32_t mid = lo + ((hi - lo) >> 1);
-        if (a.seg_end[mid] > p) hi = mid; else lo = mid + 1;
-      }
-      sg = lo;
-    }
-  } else {
-    consumed = a.fanout > 0 && p / a.fanout < a.num_segments;
-    if (consumed) sg = (int32_t)(p / a.fanout);
-  }
-  if (!consumed) {  // the same answer in every lane of the group
+  int32_t sg;
+  if (!seg_of_position(a.seg, p, &sg)) {  // the same answer in every lane of the group
     for (int32_t h = c; h < a.heads; h += G) out[h] = 0.0f;
     return;
   }
-  const float div = OP == GLX_AGG_MEAN ? (float)consumed_count(a.seg_end, sg, a.num_ids, a.fanout) : 1.0f;
-  const int64_t r = a.rows[p];
-  const bool in = r >= 0 && r < a.num_rows;
-  const float* const xr = a.x + (in ? r : 0) * (int64_t)a.dim;
-  const float* const go = a.grad_out + sg * (int64_t)a.dim;
-  if (SUB) {
-    const int32_t span = G * VEC * a.steps;  // columns per reduce: G / sub whole heads, or one
-    for (int32_t col_pass = 0; col_pass < a.dim; col_pass += span) {
-      float part = 0.0f;
-      for (int32_t k = 0; k < a.steps; ++k) {
-        const int32_t col = col_pass + (k * G + c) * VEC;
-        if (col < a.dim) {
-          const vec_t g = *reinterpret_cast<const vec_t*>(go + col);
-          vec_t xv;
-          if (in) {
-            xv = *reinterpret_cast<const vec_t*>(xr + col);
-          } else {
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) xv[v] = a.default_attr;
-          }
-#pragma unroll
-          for (int v = 0; v < VEC; ++v) part += g[v] * xv[v];
-        }
-      }
-      for (int off = a.sub >> 1; off > 0; off >>= 1) part += __shfl_xor(part, off, G);
-      const int32_t col0 = col_pass + c * VEC;
-      if ((c & (a.sub - 1)) == 0 && col0 < a.dim) out[col0 / a.C] = OP == GLX_AGG_MEAN ? part / div : part;
-    }
-  } else {
-    const int32_t L = a.C / VEC;
-    for (int32_t h = 0; h < a.heads; ++h) {
-      float part = 0.0f;
-      for (int32_t i = c; i < L; i += G) {
-        const int32_t col = h * a.C + i * VEC;
-        const vec_t g = *reinterpret_cast<const vec_t*>(go + col);
-        vec_t xv;
-        if (in) {
-          xv = *reinterpret_cast<const vec_t*>(xr + col);
-        } else {
-#pragma unroll
-          for (int v = 0; v < VEC; ++v) xv[v] = a.default_attr;
-        }
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) part += g[v] * xv[v];
-      }
-#pragma unroll
-      for (int off = G >> 1; off > 0; off >>= 1) part += __shfl_xor(part, off, G);
-      if (c == 0) out[h] = OP == GLX_AGG_MEAN ? part / div : part;
-    }
-  }
-}
-
-template <int OP, int VEC, bool SUB>
-void launch_wbwd_w_g(WBwdWArgs a, int lanes, hipStream_t s) {
-  const int G = group_for(lanes);
-  if (SUB) {
-    const int L = a.C / VEC;
-    a.sub = L < G ? L : G;
-    a.steps = L > G ? L / G : 1;
-  }
-  const unsigned blocks = (unsigned)(((int64_t)a.num_ids + (256 / G) - 1) / (256 / G));
-  switch (G) {
-    case 8: glx_aggregate_weighted_bwd_w_kernel<OP, 8, VEC, SUB><<<blocks, 256, 0, s>>>(a); break;
-    case 16: glx_aggregate_weighted_bwd_w_kernel<OP, 16, VEC, SUB><<<blocks, 256, 0, s>>>(a); break;
-    case 32: glx_aggregate_weighted_bwd_w_kernel<OP, 32, VEC, SUB><<<blocks, 256, 0, s>>>(a); break;
-    default: glx_aggregate_weighted_bwd_w_kernel<OP, 64, VEC, SUB><<<blocks, 256, 0, s>>>(a); break;
-  }
+  const float div = OP == GLX_AGG_MEAN ? (float)seg_count(a.seg, sg) : 1.0f;
+  const GlxRow go = {a.grad_out + sg * (int64_t)a.dim, true};
+  const GlxRow xr = glx_row(a.x, a.rows[p], a.num_rows, a.dim);
+  glx_head_dots<G, VEC, SUB, OP == GLX_AGG_MEAN>(go, xr, a.default_attr, a.dim, a.heads, a.C, a.hd, div, c, out);
 }
 
 template <int OP, int VEC>
-void launch_wbwd_w_vec(const WBwdWArgs& a, hipStream_t s) {
-  const int L = a.C / VEC;
-  // sub-groups tile the row: the group covers all of it (up to 64 lanes); a loop over heads: the group covers one head
-  if ((L & (L - 1)) == 0) launch_wbwd_w_g<OP, VEC, true>(a, a.dim / VEC, s);
-  else launch_wbwd_w_g<OP, VEC, false>(a, L, s);
+void launch_wbwd_w_vec(WBwdWArgs a, hipStream_t s) {
+  const GlxHeadDotPlan plan = glx_head_dot_plan(a.dim, a.C, VEC);
+  const int G = plan.G;
+  a.hd = plan.hd;
+  const unsigned blocks = (unsigned)(((int64_t)a.seg.num_ids + (256 / G) - 1) / (256 / G));
+  glx_for_group(G, [&](auto g) {
+    constexpr int kG = decltype(g)::value;
+    if (plan.sub_groups) glx_aggregate_weighted_bwd_w_kernel<OP, kG, VEC, true><<<blocks, 256, 0, s>>>(a);
+    else glx_aggregate_weighted_bwd_w_kernel<OP, kG, VEC, false><<<blocks, 256, 0, s>>>(a);
+  });
 }
 
 template <int OP>
 void launch_wbwd_w(const WBwdWArgs& a, hipStream_t s) {
-  const bool vec4 = a.dim % 4 == 0 && a.C % 4 == 0 && aligned16(a.x) && aligned16(a.grad_out);
+  const bool vec4 = a.dim % 4 == 0 && a.C % 4 == 0 && glx_aligned16(a.x) && glx_aligned16(a.grad_out);
   if (vec4) launch_wbwd_w_vec<OP, 4>(a, s);
   else launch_wbwd_w_vec<OP, 1>(a, s);
-}
-
-int zero_async(float* p, size_t count, hipStream_t s) {
-  hipError_t e = hipMemsetAsync(p, 0, count * sizeof(float), s);
-  if (e != hipSuccess) {
-    glx_set_error("hipMemsetAsync failed: %s", hipGetErrorString(e));
-    return GLX_INTERNAL;
-  }
-  return GLX_OK;
 }
 
 }  // namespace
@@ -406,7 +271,7 @@ int zero_async(float* p, size_t count, hipStream_t s) {
 #define GLX_WEIGHTED_REQUIRE(who)                                                                                       \
   GLX_REQUIRE(op >= GLX_AGG_SUM && op <= GLX_AGG_PROD, "unknown aggregator id %d", op);                                 \
   GLX_REQUIRE(op == GLX_AGG_SUM || op == GLX_AGG_MEAN, who " reduces with Sum or Mean only, not with %s",               \
-              w_op_name(op));                                                                                           \
+              glx_agg_op_name(op));                                                                                     \
   GLX_REQUIRE(num_ids >= 0 && num_segments >= 0 && num_rows >= 0, "negative sizes");                                    \
   GLX_REQUIRE(dim > 0, "dim must be positive, got %d", dim);                                                            \
   GLX_REQUIRE(heads > 0, "heads must be positive, got %d", heads);                                                      \
@@ -439,17 +304,13 @@ extern "C" int glx_aggregate_weighted(int device, int op, const float* x, int64_
   st.out(&a.emb, emb_out, (size_t)num_segments * dim);
   rc = st.begin();
   GlxScratch lease;
-  a.seg_end = nullptr;
-  if (rc == GLX_OK && cnt != nullptr) rc = glx_agg_segment_ends(a.cnt, num_segments, st.s, &lease, &a.seg_end);
+  if (cnt == nullptr) a.cnt = nullptr;
+  if (rc == GLX_OK) rc = glx_seg_layout(a.cnt, num_ids, num_segments, st.s, &lease, &a.seg);
   if (rc == GLX_OK) {
-    if (cnt == nullptr) a.cnt = nullptr;
     a.num_rows = num_rows;
     a.dim = dim;
     a.heads = heads;
     a.C = dim / heads;
-    a.fanout = num_ids / num_segments;
-    a.num_ids = num_ids;
-    a.num_segments = num_segments;
     a.default_attr = default_attr;
     if (op == GLX_AGG_SUM) launch_wfwd<GLX_AGG_SUM>(a, st.s);
     else launch_wfwd<GLX_AGG_MEAN>(a, st.s);
@@ -484,7 +345,7 @@ extern "C" int glx_aggregate_weighted_backward_x(int device, int op, const int64
   GlxScratch lease;
   if (rc == GLX_OK) {
     if (num_ids == 0 || num_segments == 0) {  // nothing was consumed: every row is zeros
-      rc = zero_async(a.grad_x, (size_t)num_rows * dim, st.s);
+      rc = glx_zero_f32_async(a.grad_x, (size_t)num_rows * dim, st.s);
     } else {
       rc = glx_agg_transpose(d_rows, cnt ? d_cnt : nullptr, num_ids, num_segments, num_rows, st.s, &lease, &a.t);
       if (rc == GLX_OK) {
@@ -492,7 +353,7 @@ extern "C" int glx_aggregate_weighted_backward_x(int device, int op, const int64
         a.dim = dim;
         a.heads = heads;
         a.C = dim / heads;
-        a.num_ids = num_ids;
+        a.seg = GlxSegLayout{a.t.seg_end, a.t.fanout, num_ids, num_segments};
         if (op == GLX_AGG_SUM) launch_wbwd_x<GLX_AGG_SUM>(a, st.s);
         else launch_wbwd_x<GLX_AGG_MEAN>(a, st.s);
       }
@@ -526,21 +387,15 @@ extern "C" int glx_aggregate_weighted_backward_w(int device, int op, const float
   GlxScratch lease;
   if (rc == GLX_OK) {
     if (num_segments == 0) {  // nothing was consumed
-      rc = zero_async(a.grad_w, (size_t)num_ids * heads, st.s);
+      rc = glx_zero_f32_async(a.grad_w, (size_t)num_ids * heads, st.s);
     } else {
-      a.seg_end = nullptr;
       if (cnt == nullptr) a.cnt = nullptr;
-      else rc = glx_agg_segment_ends(a.cnt, num_segments, st.s, &lease, &a.seg_end);
+      rc = glx_seg_layout(a.cnt, num_ids, num_segments, st.s, &lease, &a.seg);
       if (rc == GLX_OK) {
         a.num_rows = num_rows;
         a.dim = dim;
         a.heads = heads;
         a.C = dim / heads;
-        a.fanout = num_ids / num_segments;
-        a.num_ids = num_ids;
-        a.num_segments = num_segments;
-        a.sub = 1;
-        a.steps = 1;
         a.default_attr = default_attr;
         if (op == GLX_AGG_SUM) launch_wbwd_w<GLX_AGG_SUM>(a, st.s);
         else launch_wbwd_w<GLX_AGG_MEAN>(a, st.s);

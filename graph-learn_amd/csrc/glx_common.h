@@ -865,6 +865,12 @@ int glx_agg_transpose(const int64_t* rows, const int32_t* cnt, int32_t n, int32_
 int glx_agg_segment_ends(const int32_t* cnt, int32_t num_segments, hipStream_t s, GlxScratch* lease,
                          const int64_t** seg_end);
 
+// the name of aggregator GLX_AGG_SUM .. GLX_AGG_PROD, for messages
+inline const char* glx_agg_op_name(int op) {
+  static const char* const kNames[] = {"Sum", "Mean", "Max", "Min", "Prod"};
+  return kNames[op];
+}
+
 template <int OP>
 __device__ __forceinline__ float agg_init() {
   if (OP == GLX_AGG_MAX) return (float)FLT_MIN_10_EXP;  // max_aggregator.cc:28 (-37, sic)

@@ -27,9 +27,10 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "glx_common.h"
+#include "glx_lane_groups.h"
 
-// Two roundings per product-and-add: see glx_aggregate_weighted.hip for why the product goes through an empty asm.
+// Two roundings per product-and-add: glx_pin / glx_fold_rn (glx_lane_groups.h) pin the product; the pragma is for the
+// front end.
 #pragma clang fp contract(off)
 
 namespace {
@@ -37,18 +38,6 @@ namespace {
 constexpr int kChunk = GLX_COALESCE_CHUNK;
 constexpr int kWindow = kChunk + 1;  // sorted positions per group of the combine pass
 constexpr int kU = 4;                // row loads in flight per lane
-
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// the smallest group of 8 .. 64 lanes that covers `lanes` (glx_pair_dot.hip)
-int group_for(int lanes) { return lanes <= 8 ? 8 : lanes <= 16 ? 16 : lanes <= 32 ? 32 : 64; }
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-__device__ __forceinline__ float opaque(float t) {
-  asm("" : "+v"(t));  // no instruction; the optimiser cannot contract across it
-  return t;
-}
 
 // ---- coalesce: keys, flags -----------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void glx_emb_keys_kernel(const int64_t* __restrict__ rows, int32_t n, int64_t num_rows,
@@ -221,28 +210,14 @@ __global__ __launch_bounds__(256) void glx_emb_combine_kernel(CoalesceArgs a) {
 
 template <int VEC>
 void launch_coalesce_vec(const CoalesceArgs& a, hipStream_t s) {
-  const int G = group_for((a.dim + VEC - 1) / VEC);
+  const int G = glx_group_for((a.dim + VEC - 1) / VEC);
   const unsigned blocks = (unsigned)(((int64_t)a.n + (256 / G) - 1) / (256 / G));
   const int64_t windows = ((int64_t)a.n + kWindow - 1) / kWindow;
   const unsigned cblocks = (unsigned)((windows + (256 / G) - 1) / (256 / G));
-  switch (G) {
-    case 8:
-      glx_emb_reduce_kernel<8, VEC><<<blocks, 256, 0, s>>>(a);
-      glx_emb_combine_kernel<8, VEC><<<cblocks, 256, 0, s>>>(a);
-      break;
-    case 16:
-      glx_emb_reduce_kernel<16, VEC><<<blocks, 256, 0, s>>>(a);
-      glx_emb_combine_kernel<16, VEC><<<cblocks, 256, 0, s>>>(a);
-      break;
-    case 32:
-      glx_emb_reduce_kernel<32, VEC><<<blocks, 256, 0, s>>>(a);
-      glx_emb_combine_kernel<32, VEC><<<cblocks, 256, 0, s>>>(a);
-      break;
-    default:
-      glx_emb_reduce_kernel<64, VEC><<<blocks, 256, 0, s>>>(a);
-      glx_emb_combine_kernel<64, VEC><<<cblocks, 256, 0, s>>>(a);
-      break;
-  }
+  glx_for_group(G, [&](auto g) {
+    glx_emb_reduce_kernel<decltype(g)::value, VEC><<<blocks, 256, 0, s>>>(a);
+    glx_emb_combine_kernel<decltype(g)::value, VEC><<<cblocks, 256, 0, s>>>(a);
+  });
 }
 
 // Device pointers only, device selected; n >= 1.
@@ -256,11 +231,11 @@ int coalesce_device(const int64_t* rows, int32_t n, int64_t num_rows, int32_t di
   size_t sort_tmp = 0, scan_tmp = 0;
   GLX_HIP(rocprim::radix_sort_pairs(nullptr, sort_tmp, no_keys, no_keys, no_vals, no_vals, (size_t)n, 0, bits, s));
   GLX_HIP(rocprim::inclusive_scan(nullptr, scan_tmp, no_flags, no_flags, (size_t)n, rocprim::plus<uint64_t>(), s));
-  const size_t tmp_b = align256(sort_tmp > scan_tmp ? sort_tmp : scan_tmp);
-  const size_t ids_b = align256((size_t)n * sizeof(int32_t));
-  const size_t flag_b = align256((size_t)n * sizeof(uint64_t));
+  const size_t tmp_b = glx_align256(sort_tmp > scan_tmp ? sort_tmp : scan_tmp);
+  const size_t ids_b = glx_align256((size_t)n * sizeof(int32_t));
+  const size_t flag_b = glx_align256((size_t)n * sizeof(uint64_t));
   // a run of L > kChunk entries has ceil(L / kChunk) < L / (kChunk / 2) chunks: at most n / (kChunk / 2) slots
-  const size_t part_b = align256(((size_t)n / (kChunk / 2) + 1) * dim * sizeof(float));
+  const size_t part_b = glx_align256(((size_t)n / (kChunk / 2) + 1) * dim * sizeof(float));
   GlxScratch lease;
   int rc = lease.alloc(tmp_b + 4 * ids_b + 2 * flag_b + part_b, s, 1);
   if (rc != GLX_OK) return rc;
@@ -291,7 +266,7 @@ int coalesce_device(const int64_t* rows, int32_t n, int64_t num_rows, int32_t di
   a.num_unique = num_unique;
   a.n = n;
   a.dim = dim;
-  if (dim % 4 == 0 && aligned16(g) && aligned16(ug)) launch_coalesce_vec<4>(a, s);
+  if (dim % 4 == 0 && glx_aligned16(g) && glx_aligned16(ug)) launch_coalesce_vec<4>(a, s);
   else launch_coalesce_vec<1>(a, s);
   GLX_HIP(hipGetLastError());
   return GLX_OK;
@@ -311,7 +286,7 @@ struct UpdateArgs {
 
 // G lanes own entry u; lane c owns columns [VEC c, VEC c + VEC) of each column tile.  Every row is read once and each
 // written row written once.  Every float operation below is one rounding: the build forbids contraction, the products
-// pass through `opaque` besides, and the divide and the square root are the correctly rounded ones.
+// pass through `glx_pin` besides, and the divide and the square root are the correctly rounded ones.
 template <int ALGO, int G, int VEC>
 __global__ __launch_bounds__(256) void glx_emb_update_kernel(UpdateArgs a) {
   typedef float vec_t __attribute__((ext_vector_type(VEC)));
@@ -327,15 +302,15 @@ __global__ __launch_bounds__(256) void glx_emb_update_kernel(UpdateArgs a) {
     vec_t w = *reinterpret_cast<const vec_t*>(a.W + at + col);
     if (ALGO == GLX_EMB_SGD) {
 #pragma unroll
-      for (int v = 0; v < VEC; ++v) w[v] = w[v] - opaque(a.alpha * g[v]);
+      for (int v = 0; v < VEC; ++v) w[v] = w[v] - glx_pin(a.alpha * g[v]);
     } else if (ALGO == GLX_EMB_ADAGRAD) {
       vec_t st = *reinterpret_cast<const vec_t*>(a.s1 + at + col);
 #pragma unroll
       for (int v = 0; v < VEC; ++v) {
-        st[v] = st[v] + opaque(g[v] * g[v]);
-        const float den = opaque(sqrtf(st[v])) + a.eps;
-        const float q = opaque(g[v] / den);
-        w[v] = w[v] - opaque(a.alpha * q);
+        st[v] = glx_fold_rn(st[v], g[v], g[v]);
+        const float den = glx_pin(sqrtf(st[v])) + a.eps;
+        const float q = glx_pin(g[v] / den);
+        w[v] = w[v] - glx_pin(a.alpha * q);
       }
       *reinterpret_cast<vec_t*>(a.s1 + at + col) = st;
     } else {
@@ -343,12 +318,12 @@ __global__ __launch_bounds__(256) void glx_emb_update_kernel(UpdateArgs a) {
       vec_t sv = *reinterpret_cast<const vec_t*>(a.s2 + at + col);
 #pragma unroll
       for (int v = 0; v < VEC; ++v) {
-        m[v] = opaque(a.beta1 * m[v]) + opaque(a.c1 * g[v]);
-        const float gg = opaque(g[v] * g[v]);
-        sv[v] = opaque(a.beta2 * sv[v]) + opaque(a.c2 * gg);
-        const float den = opaque(sqrtf(sv[v])) + a.eps;
-        const float q = opaque(m[v] / den);
-        w[v] = w[v] - opaque(a.alpha * q);
+        m[v] = glx_pin(a.beta1 * m[v]) + glx_pin(a.c1 * g[v]);
+        const float gg = glx_pin(g[v] * g[v]);
+        sv[v] = glx_pin(a.beta2 * sv[v]) + glx_pin(a.c2 * gg);
+        const float den = glx_pin(sqrtf(sv[v])) + a.eps;
+        const float q = glx_pin(m[v] / den);
+        w[v] = w[v] - glx_pin(a.alpha * q);
       }
       *reinterpret_cast<vec_t*>(a.s1 + at + col) = m;
       *reinterpret_cast<vec_t*>(a.s2 + at + col) = sv;
@@ -359,19 +334,15 @@ __global__ __launch_bounds__(256) void glx_emb_update_kernel(UpdateArgs a) {
 
 template <int ALGO, int VEC>
 void launch_update_vec(const UpdateArgs& a, hipStream_t s) {
-  const int G = group_for((a.dim + VEC - 1) / VEC);
+  const int G = glx_group_for((a.dim + VEC - 1) / VEC);
   const unsigned blocks = (unsigned)(((int64_t)a.n + (256 / G) - 1) / (256 / G));
-  switch (G) {
-    case 8: glx_emb_update_kernel<ALGO, 8, VEC><<<blocks, 256, 0, s>>>(a); break;
-    case 16: glx_emb_update_kernel<ALGO, 16, VEC><<<blocks, 256, 0, s>>>(a); break;
-    case 32: glx_emb_update_kernel<ALGO, 32, VEC><<<blocks, 256, 0, s>>>(a); break;
-    default: glx_emb_update_kernel<ALGO, 64, VEC><<<blocks, 256, 0, s>>>(a); break;
-  }
+  glx_for_group(G, [&](auto g) { glx_emb_update_kernel<ALGO, decltype(g)::value, VEC><<<blocks, 256, 0, s>>>(a); });
 }
 
 template <int ALGO>
 void launch_update(const UpdateArgs& a, hipStream_t s) {
-  const bool vec4 = a.dim % 4 == 0 && aligned16(a.W) && aligned16(a.ug) && aligned16(a.s1) && aligned16(a.s2);
+  const bool vec4 =
+      a.dim % 4 == 0 && glx_aligned16(a.W) && glx_aligned16(a.ug) && glx_aligned16(a.s1) && glx_aligned16(a.s2);
   if (vec4) launch_update_vec<ALGO, 4>(a, s);
   else launch_update_vec<ALGO, 1>(a, s);
 }

@@ -26,14 +26,14 @@ struct GatArgs {
   const float* s;          // [num_segments, heads]
   const float* t;          // [num_rows, heads]
   const int64_t* rows;     // [num_ids]
-  const int64_t* seg_end;  // [num_segments] inclusive prefix sums of the clamped counts, or nullptr: the implied layout
+  GlxSegLayout seg;
   const float* soft;       // backward: the forward's softmax            [num_ids, heads]
   const float* g;          // backward: grad_alpha                       [num_ids, heads]
   float* soft_out;         // forward: softmax before dropout, or nullptr
   float* out;              // forward: alpha_out; backward: grad_e       [num_ids, heads]
   float* grad_s;           // backward: [num_segments, heads], or nullptr
   int64_t num_rows;
-  int32_t heads, fanout, num_ids, num_segments;
+  int32_t heads;
   float slope, default_attr, scale;
   uint32_t thresh;         // keep an element iff its word >= thresh
   uint64_t seed, call;
@@ -238,9 +238,9 @@ __global__ __launch_bounds__(256) void glx_gat_attention_kernel(GatArgs a) {
   it.hshift = FLAT ? __ffs(H) - 1 : 0;
   {
     const int64_t sg = first + threadIdx.x / G;
-    if (sg < a.num_segments) {  // the same answer in every lane of the group
+    if (sg < a.seg.num_segments) {  // the same answer in every lane of the group
       int32_t s0, s1;
-      sm_bounds(a, sg, &s0, &s1);
+      seg_bounds(a.seg, sg, &s0, &s1);
       const int64_t items = FLAT ? (int64_t)(s1 - s0) * H : (int64_t)(s1 - s0);
       it.s0 = s0;
       if (items > 0 && items <= kSmLongItems) {
@@ -262,9 +262,9 @@ __global__ __launch_bounds__(256) void glx_gat_attention_kernel(GatArgs a) {
   }
   for (int j = 0; j < kSegs; ++j) {  // every condition below is the same in all 256 threads
     const int64_t sg = first + j;
-    if (sg >= a.num_segments) break;
+    if (sg >= a.seg.num_segments) break;
     int32_t s0, s1;
-    sm_bounds(a, sg, &s0, &s1);
+    seg_bounds(a.seg, sg, &s0, &s1);
     const int64_t items = FLAT ? (int64_t)(s1 - s0) * H : (int64_t)(s1 - s0);
     if (items <= kSmLongItems) continue;
     it.s0 = s0;
@@ -280,8 +280,8 @@ __global__ __launch_bounds__(256) void glx_gat_attention_kernel(GatArgs a) {
       }
     }
   }
-  const int64_t tail = sm_tail(a);
-  const int64_t end = (int64_t)a.num_ids * H;
+  const int64_t tail = seg_tail(a.seg);
+  const int64_t end = (int64_t)a.seg.num_ids * H;
   for (int64_t i = tail * H + blockIdx.x * 256LL + threadIdx.x; i < end; i += gridDim.x * 256LL) {
     a.out[i] = 0.0f;
     if (!BWD && a.soft_out) a.soft_out[i] = 0.0f;
@@ -290,19 +290,16 @@ __global__ __launch_bounds__(256) void glx_gat_attention_kernel(GatArgs a) {
 
 template <bool FLAT, bool DROP, bool BWD>
 void gat_launch_g(const GatArgs& a, int G, hipStream_t s) {
-  const unsigned blocks = sm_blocks(G, a.heads, a.num_ids, a.num_segments);
-  switch (G) {
-    case 8: glx_gat_attention_kernel<8, FLAT, DROP, BWD><<<blocks, 256, 0, s>>>(a); break;
-    case 16: glx_gat_attention_kernel<16, FLAT, DROP, BWD><<<blocks, 256, 0, s>>>(a); break;
-    case 32: glx_gat_attention_kernel<32, FLAT, DROP, BWD><<<blocks, 256, 0, s>>>(a); break;
-    default: glx_gat_attention_kernel<64, FLAT, DROP, BWD><<<blocks, 256, 0, s>>>(a); break;
-  }
+  const unsigned blocks = sm_blocks(G, a.heads, a.seg.num_ids, a.seg.num_segments);
+  glx_for_group(G, [&](auto g) {
+    glx_gat_attention_kernel<decltype(g)::value, FLAT, DROP, BWD><<<blocks, 256, 0, s>>>(a);
+  });
 }
 
 template <bool BWD>
 void gat_launch(const GatArgs& a, bool drop, hipStream_t s) {
   bool flat;
-  const int G = sm_width(a.heads, a.num_ids, a.num_segments, &flat);
+  const int G = sm_width(a.heads, a.seg.num_ids, a.seg.num_segments, &flat);
   if (flat) {
     if (drop) gat_launch_g<true, true, BWD>(a, G, s);
     else gat_launch_g<true, false, BWD>(a, G, s);
@@ -329,19 +326,10 @@ __global__ __launch_bounds__(256) void glx_gat_grad_t_kernel(const int32_t* __re
   grad_t[i] = acc;
 }
 
-int gat_zero(float* p, size_t count, hipStream_t s) {
-  if (p == nullptr || count == 0) return GLX_OK;
-  GLX_HIP(hipMemsetAsync(p, 0, count * sizeof(float), s));
-  return GLX_OK;
-}
-
-void gat_fill(GatArgs* a, int64_t num_rows, int32_t heads, int32_t num_ids, int32_t num_segments, float negative_slope,
-              float default_attr, float drop_p, uint64_t seed, uint64_t call) {
+void gat_fill(GatArgs* a, int64_t num_rows, int32_t heads, float negative_slope, float default_attr, float drop_p,
+              uint64_t seed, uint64_t call) {
   a->num_rows = num_rows;
   a->heads = heads;
-  a->fanout = num_segments > 0 ? num_ids / num_segments : 0;
-  a->num_ids = num_ids;
-  a->num_segments = num_segments;
   a->slope = negative_slope;
   a->default_attr = default_attr;
   a->scale = 1.0f / (1.0f - drop_p);
@@ -394,15 +382,14 @@ extern "C" int glx_gat_attention(int device, const float* s, const float* t, int
   GlxScratch lease;
   if (rc == GLX_OK) {
     if (num_segments == 0) {  // nothing was consumed
-      rc = gat_zero(a.out, count, st.s);
-      if (rc == GLX_OK) rc = gat_zero(a.soft_out, count, st.s);
+      rc = glx_zero_f32_async(a.out, count, st.s);
+      if (rc == GLX_OK) rc = glx_zero_f32_async(a.soft_out, count, st.s);
     } else {
-      a.seg_end = nullptr;
-      if (cnt != nullptr) rc = glx_agg_segment_ends(d_cnt, num_segments, st.s, &lease, &a.seg_end);
+      rc = glx_seg_layout(cnt ? d_cnt : nullptr, num_ids, num_segments, st.s, &lease, &a.seg);
       if (rc == GLX_OK) {
         a.soft = a.g = nullptr;
         a.grad_s = nullptr;
-        gat_fill(&a, num_rows, heads, num_ids, num_segments, negative_slope, default_attr, drop_p, seed, call);
+        gat_fill(&a, num_rows, heads, negative_slope, default_attr, drop_p, seed, call);
         gat_launch<false>(a, drop_p != 0.0f, st.s);
       }
     }
@@ -444,22 +431,22 @@ extern "C" int glx_gat_attention_backward(int device, const float* soft, const f
   GlxScratch lease;
   if (rc == GLX_OK) {
     if (num_ids == 0 || num_segments == 0) {  // nothing was consumed: every output is zeros
-      rc = gat_zero(a.out, count, st.s);
-      if (rc == GLX_OK) rc = gat_zero(a.grad_s, s_count, st.s);
-      if (rc == GLX_OK) rc = gat_zero(d_gt, t_count, st.s);
+      rc = glx_zero_f32_async(a.out, count, st.s);
+      if (rc == GLX_OK) rc = glx_zero_f32_async(a.grad_s, s_count, st.s);
+      if (rc == GLX_OK) rc = glx_zero_f32_async(d_gt, t_count, st.s);
     } else {
       const bool want_t = d_gt != nullptr && num_rows > 0;
       GlxAggTranspose tr;
-      a.seg_end = nullptr;
-      if (want_t) {  // the transpose computes the segment ends on its way
+      if (want_t) {  // the transpose computes the segment ends on its way: the layout takes them, it scans nothing
         rc = glx_agg_transpose(a.rows, d_cnt, num_ids, num_segments, num_rows, st.s, &lease, &tr);
-        if (rc == GLX_OK) a.seg_end = tr.seg_end;
-      } else if (cnt != nullptr) {
-        rc = glx_agg_segment_ends(d_cnt, num_segments, st.s, &lease, &a.seg_end);
+        if (rc == GLX_OK) rc = glx_seg_layout(nullptr, num_ids, num_segments, st.s, &lease, &a.seg);
+        if (rc == GLX_OK) a.seg.seg_end = tr.seg_end;
+      } else {
+        rc = glx_seg_layout(cnt ? d_cnt : nullptr, num_ids, num_segments, st.s, &lease, &a.seg);
       }
       if (rc == GLX_OK) {
         a.soft_out = nullptr;
-        gat_fill(&a, num_rows, heads, num_ids, num_segments, negative_slope, default_attr, drop_p, seed, call);
+        gat_fill(&a, num_rows, heads, negative_slope, default_attr, drop_p, seed, call);
         gat_launch<true>(a, drop_p != 0.0f, st.s);
         if (want_t) {
           const int64_t total = (int64_t)t_count;

@@ -1,0 +1,156 @@
+// What the training-path kernels share below any knowledge of segments: the lane-group widths and their dispatch, the
+// alignment tests of the vector paths, the product that never contracts, and the float zero-fill of an output nobody
+// computes.  The segment layout and the per-segment lane mappings build on it in glx_segment_lanes.h.
+#ifndef GLX_LANE_GROUPS_H_
+#define GLX_LANE_GROUPS_H_
+#include <type_traits>
+
+#include "glx_common.h"
+
+// the smallest group of 8 .. 64 lanes that covers `lanes`
+inline int glx_group_for(int64_t lanes) { return lanes <= 8 ? 8 : lanes <= 16 ? 16 : lanes <= 32 ? 32 : 64; }
+
+// f(std::integral_constant<int, G>()) for the G of glx_group_for: a kernel template takes decltype(g)::value
+template <typename F>
+inline void glx_for_group(int G, F&& f) {
+  switch (G) {
+    case 8: f(std::integral_constant<int, 8>()); break;
+    case 16: f(std::integral_constant<int, 16>()); break;
+    case 32: f(std::integral_constant<int, 32>()); break;
+    default: f(std::integral_constant<int, 64>()); break;
+  }
+}
+
+// a float4 / int4 access needs it
+inline bool glx_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// the pieces of one workspace lease start on 256-byte boundaries
+inline size_t glx_align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// Opaque to the optimiser: no instruction, and nothing contracts across it.
+__device__ __forceinline__ float glx_pin(float t) {
+  asm("" : "+v"(t));
+  return t;
+}
+
+// acc + w * x in two roundings: the multiply must never contract into the add, whatever -ffp-contract the build passes.
+// Neither __fmul_rn / __fadd_rn (plain `x * y` / `x + y` in this toolchain's headers, parsed before any pragma of ours)
+// nor `#pragma clang fp contract(off)` alone guarantees that: an explicit -ffp-contract=fast lets the backend fuse any
+// multiply with any add.  So the product goes through an empty asm that pins it in a register: the add that follows
+// takes an opaque operand and cannot become an FMA under any flag.  The files that fold keep the pragma for the
+// front end.
+__device__ __forceinline__ float glx_fold_rn(float acc, float w, float x) {
+  return acc + glx_pin(w * x);  // the product is rounded, pinned, and the sum rounded again
+}
+
+// A gathered row of a float table; an index outside the table reads a row of default_attr instead (ok == false: `at`
+// is never read).
+struct GlxRow {
+  const float* at;
+  bool ok;
+};
+
+__device__ __forceinline__ GlxRow glx_row(const float* x, int64_t r, int64_t num_rows, int32_t dim) {
+  const bool in = r >= 0 && r < num_rows;
+  return GlxRow{x + (in ? r : 0) * (int64_t)dim, in};
+}
+
+// VEC columns of it from `col` on
+template <int VEC>
+__device__ __forceinline__ float __attribute__((ext_vector_type(VEC))) glx_row_load(GlxRow row, int32_t col,
+                                                                                     float default_attr) {
+  typedef float vec_t __attribute__((ext_vector_type(VEC)));
+  vec_t v;
+  if (row.ok) {
+    v = *reinterpret_cast<const vec_t*>(row.at + col);
+  } else {
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) v[k] = default_attr;
+  }
+  return v;
+}
+
+// The per-head dot products of two rows of `dim` = heads * C columns by a group of G lanes (lane c): out[h] = the sum
+// over the columns of head h of ra[col] * rb[col], divided by `div` when DIV (Mean).  The lane-to-column mapping and
+// the cross-lane tree are fixed by (dim, heads, alignment) alone, so the same inputs give the same bits on every run.
+//   SUB  (L = C / VEC is a power of two)  lane c owns columns [VEC c, VEC c + VEC) of each tile of G * VEC columns; a
+//        head is a sub-group of min(L, G) consecutive lanes (times L / G tiles when L > G), reduced with __shfl_xor
+//        over the sub-group; its first lane writes.
+//   !SUB a loop over the heads: lane c owns elements c, c + G, .. of the head's L vectors, the whole group reduces,
+//        lane 0 writes.
+// hd: glx_head_dot_plan's, for the same G and VEC.  Every lane of the group calls it.
+struct GlxHeadDots {
+  int32_t sub;    // SUB: lanes of a sub-group (min(C / VEC, G))
+  int32_t steps;  // SUB: column tiles a head spans (C / VEC / G, at least 1)
+};
+
+template <int G, int VEC, bool SUB, bool DIV>
+__device__ __forceinline__ void glx_head_dots(GlxRow ra, GlxRow rb, float default_attr, int32_t dim, int32_t heads,
+                                              int32_t C, GlxHeadDots hd, float div, int c, float* out) {
+  typedef float vec_t __attribute__((ext_vector_type(VEC)));
+  if (SUB) {
+    const int32_t span = G * VEC * hd.steps;  // columns per reduce: G / sub whole heads, or one
+    for (int32_t col_pass = 0; col_pass < dim; col_pass += span) {
+      float part = 0.0f;
+      for (int32_t k = 0; k < hd.steps; ++k) {
+        const int32_t col = col_pass + (k * G + c) * VEC;
+        if (col < dim) {
+          const vec_t u = glx_row_load<VEC>(ra, col, default_attr);
+          const vec_t w = glx_row_load<VEC>(rb, col, default_attr);
+#pragma unroll
+          for (int v = 0; v < VEC; ++v) part += u[v] * w[v];
+        }
+      }
+      for (int off = hd.sub >> 1; off > 0; off >>= 1) part += __shfl_xor(part, off, G);
+      const int32_t col0 = col_pass + c * VEC;
+      if ((c & (hd.sub - 1)) == 0 && col0 < dim) out[col0 / C] = DIV ? part / div : part;
+    }
+  } else {
+    const int32_t L = C / VEC;
+    for (int32_t h = 0; h < heads; ++h) {
+      float part = 0.0f;
+      for (int32_t i = c; i < L; i += G) {
+        const int32_t col = h * C + i * VEC;
+        const vec_t u = glx_row_load<VEC>(ra, col, default_attr);
+        const vec_t w = glx_row_load<VEC>(rb, col, default_attr);
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) part += u[v] * w[v];
+      }
+#pragma unroll
+      for (int off = G >> 1; off > 0; off >>= 1) part += __shfl_xor(part, off, G);
+      if (c == 0) out[h] = DIV ? part / div : part;
+    }
+  }
+}
+
+// The host side of glx_head_dots for rows of `dim` columns, C to a head, read VEC at a time: which mapping, the group
+// width and the sub-group shape.  SUB's sub-groups tile the row, so the group covers all of it (up to 64 lanes); the
+// loop over heads takes a group that covers one head.
+struct GlxHeadDotPlan {
+  bool sub_groups;  // the kernel's SUB
+  int G;
+  GlxHeadDots hd;
+};
+
+inline GlxHeadDotPlan glx_head_dot_plan(int32_t dim, int32_t C, int VEC) {
+  const int L = C / VEC;
+  GlxHeadDotPlan p;
+  p.sub_groups = (L & (L - 1)) == 0;
+  p.G = glx_group_for(p.sub_groups ? dim / VEC : L);
+  p.hd.sub = p.sub_groups ? (L < p.G ? L : p.G) : 1;
+  p.hd.steps = p.sub_groups && L > p.G ? L / p.G : 1;
+  return p;
+}
+
+// +0.0f into an output that no kernel will write; nothing to do for an absent or empty one
+inline int glx_zero_f32_async(float* p, size_t count, hipStream_t s) {
+  if (p == nullptr || count == 0) return GLX_OK;
+  hipError_t e = hipMemsetAsync(p, 0, count * sizeof(float), s);
+  if (e != hipSuccess) {
+    glx_set_error("hipMemsetAsync failed: %s", hipGetErrorString(e));
+    return GLX_INTERNAL;
+  }
+  return GLX_OK;
+}
+
+#endif  // GLX_LANE_GROUPS_H_

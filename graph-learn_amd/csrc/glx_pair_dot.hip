@@ -14,25 +14,15 @@
 //              fadd_rn(., fmul_rn(g[p, head(c)], xb_row(p)[c])); side 1 (xb): pairs with ib[p] == r, factor xa_row(p)[c].
 //              An own index outside the table receives nothing.  Bit-exact.
 // No float atomics anywhere.
-#include "glx_common.h"
+#include "glx_lane_groups.h"
 
-// Two roundings per term of the backward: see glx_aggregate_weighted.hip for why the product goes through an empty asm.
+// Two roundings per term of the backward: glx_fold_rn (glx_lane_groups.h) pins the product; the pragma is for the
+// front end.
 #pragma clang fp contract(off)
 
 namespace {
 
-__device__ __forceinline__ float fold_rn(float acc, float w, float x) {
-  float t = w * x;        // rounded
-  asm("" : "+v"(t));      // opaque to the optimiser: no instruction, no contraction
-  return acc + t;         // rounded again
-}
-
 constexpr int kWU = 4;  // row loads in flight per lane
-
-// the smallest group of 8 .. 64 lanes that covers `lanes`
-int group_for(int lanes) { return lanes <= 8 ? 8 : lanes <= 16 ? 16 : lanes <= 32 ? 32 : 64; }
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // ---- forward -----------------------------------------------------------------------------------------------
 struct PairFwdArgs {
@@ -43,36 +33,14 @@ struct PairFwdArgs {
   float* out;          // [num_pairs, heads]
   int64_t num_rows_a, num_rows_b;
   int32_t dim, heads, C, num_pairs, repeat;
-  int32_t sub;    // SUB: lanes of a sub-group (min(C / VEC, G))
-  int32_t steps;  // SUB: column tiles a head spans (C / VEC / G, at least 1)
+  GlxHeadDots hd;
   float default_attr;
 };
 
-// VEC columns from `col` on of a gathered row; `row` == nullptr: the index was outside its table
-template <int VEC>
-__device__ __forceinline__ float __attribute__((ext_vector_type(VEC))) pair_row_load(const float* row, int32_t col,
-                                                                                      float default_attr) {
-  typedef float vec_t __attribute__((ext_vector_type(VEC)));
-  vec_t v;
-  if (row != nullptr) {
-    v = *reinterpret_cast<const vec_t*>(row + col);
-  } else {
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) v[k] = default_attr;
-  }
-  return v;
-}
-
-// G lanes own one PAIR p and write out[p, 0 .. heads): the mappings of glx_aggregate_weighted_bwd_w_kernel.
-//   SUB  (L = C / VEC is a power of two)  lane c owns columns [VEC c, VEC c + VEC) of each tile of G * VEC columns; a
-//        head is a sub-group of min(L, G) consecutive lanes (times L / G tiles when L > G), reduced with __shfl_xor over
-//        the sub-group; its first lane writes.
-//   !SUB a loop over the heads: lane c owns elements c, c + G, .. of the head's L vectors, the whole group reduces,
-//        lane 0 writes.
+// G lanes own one PAIR p and write out[p, 0 .. heads): glx_head_dots (glx_lane_groups.h) of the pair's two rows.
 // The `repeat` pairs of one source are neighbouring groups of a workgroup: the shared row comes out of the L1 / L2.
 template <int G, int VEC, bool SUB>
 __global__ __launch_bounds__(256) void glx_pair_dot_kernel(PairFwdArgs a) {
-  typedef float vec_t __attribute__((ext_vector_type(VEC)));
   const int64_t p = blockIdx.x * (int64_t)(256 / G) + threadIdx.x / G;
   const int c = threadIdx.x & (G - 1);
   if (p >= a.num_pairs) return;  // whole groups leave
@@ -80,68 +48,25 @@ __global__ __launch_bounds__(256) void glx_pair_dot_kernel(PairFwdArgs a) {
   const int64_t ra = a.ia[p / a.repeat], rb = a.ib[p];
   const float* const xa = (ra >= 0 && ra < a.num_rows_a) ? a.xa + ra * (int64_t)a.dim : nullptr;
   const float* const xb = (rb >= 0 && rb < a.num_rows_b) ? a.xb + rb * (int64_t)a.dim : nullptr;
-  if (SUB) {
-    const int32_t span = G * VEC * a.steps;  // columns per reduce: G / sub whole heads, or one
-    for (int32_t col_pass = 0; col_pass < a.dim; col_pass += span) {
-      float part = 0.0f;
-      for (int32_t k = 0; k < a.steps; ++k) {
-        const int32_t col = col_pass + (k * G + c) * VEC;
-        if (col < a.dim) {
-          const vec_t u = pair_row_load<VEC>(xa, col, a.default_attr);
-          const vec_t w = pair_row_load<VEC>(xb, col, a.default_attr);
-#pragma unroll
-          for (int v = 0; v < VEC; ++v) part += u[v] * w[v];
-        }
-      }
-      for (int off = a.sub >> 1; off > 0; off >>= 1) part += __shfl_xor(part, off, G);
-      const int32_t col0 = col_pass + c * VEC;
-      if ((c & (a.sub - 1)) == 0 && col0 < a.dim) out[col0 / a.C] = part;
-    }
-  } else {
-    const int32_t L = a.C / VEC;
-    for (int32_t h = 0; h < a.heads; ++h) {
-      float part = 0.0f;
-      for (int32_t i = c; i < L; i += G) {
-        const int32_t col = h * a.C + i * VEC;
-        const vec_t u = pair_row_load<VEC>(xa, col, a.default_attr);
-        const vec_t w = pair_row_load<VEC>(xb, col, a.default_attr);
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) part += u[v] * w[v];
-      }
-#pragma unroll
-      for (int off = G >> 1; off > 0; off >>= 1) part += __shfl_xor(part, off, G);
-      if (c == 0) out[h] = part;
-    }
-  }
-}
-
-template <int VEC, bool SUB>
-void launch_pair_fwd_g(PairFwdArgs a, int lanes, hipStream_t s) {
-  const int G = group_for(lanes);
-  if (SUB) {
-    const int L = a.C / VEC;
-    a.sub = L < G ? L : G;
-    a.steps = L > G ? L / G : 1;
-  }
-  const unsigned blocks = (unsigned)(((int64_t)a.num_pairs + (256 / G) - 1) / (256 / G));
-  switch (G) {
-    case 8: glx_pair_dot_kernel<8, VEC, SUB><<<blocks, 256, 0, s>>>(a); break;
-    case 16: glx_pair_dot_kernel<16, VEC, SUB><<<blocks, 256, 0, s>>>(a); break;
-    case 32: glx_pair_dot_kernel<32, VEC, SUB><<<blocks, 256, 0, s>>>(a); break;
-    default: glx_pair_dot_kernel<64, VEC, SUB><<<blocks, 256, 0, s>>>(a); break;
-  }
+  // the null-pointer form, not glx_row: its clamped pointer costs this kernel up to two VGPRs
+  const GlxRow rowa = {xa, xa != nullptr}, rowb = {xb, xb != nullptr};
+  glx_head_dots<G, VEC, SUB, false>(rowa, rowb, a.default_attr, a.dim, a.heads, a.C, a.hd, 1.0f, c, out);
 }
 
 template <int VEC>
-void launch_pair_fwd_vec(const PairFwdArgs& a, hipStream_t s) {
-  const int L = a.C / VEC;
-  // sub-groups tile the row: the group covers all of it (up to 64 lanes); a loop over heads: the group covers one head
-  if ((L & (L - 1)) == 0) launch_pair_fwd_g<VEC, true>(a, a.dim / VEC, s);
-  else launch_pair_fwd_g<VEC, false>(a, L, s);
+void launch_pair_fwd_vec(PairFwdArgs a, hipStream_t s) {
+  const GlxHeadDotPlan plan = glx_head_dot_plan(a.dim, a.C, VEC);
+  const int G = plan.G;
+  a.hd = plan.hd;
+  const unsigned blocks = (unsigned)(((int64_t)a.num_pairs + (256 / G) - 1) / (256 / G));
+  glx_for_group(G, [&](auto g) {
+    if (plan.sub_groups) glx_pair_dot_kernel<decltype(g)::value, VEC, true><<<blocks, 256, 0, s>>>(a);
+    else glx_pair_dot_kernel<decltype(g)::value, VEC, false><<<blocks, 256, 0, s>>>(a);
+  });
 }
 
 void launch_pair_fwd(const PairFwdArgs& a, hipStream_t s) {
-  const bool vec4 = a.dim % 4 == 0 && a.C % 4 == 0 && aligned16(a.xa) && aligned16(a.xb);
+  const bool vec4 = a.dim % 4 == 0 && a.C % 4 == 0 && glx_aligned16(a.xa) && glx_aligned16(a.xb);
   if (vec4) launch_pair_fwd_vec<4>(a, s);
   else launch_pair_fwd_vec<1>(a, s);
 }
@@ -217,7 +142,7 @@ __global__ __launch_bounds__(256) void glx_pair_dot_bwd_kernel(PairBwdArgs a) {
         for (int u = 0; u < kWU; ++u) {
           if (j + u < m) {
 #pragma unroll
-            for (int v = 0; v < VEC; ++v) acc[v] = fold_rn(acc[v], gt[u], val[u][v]);
+            for (int v = 0; v < VEC; ++v) acc[v] = glx_fold_rn(acc[v], gt[u], val[u][v]);
           }
         }
       }
@@ -228,18 +153,13 @@ __global__ __launch_bounds__(256) void glx_pair_dot_bwd_kernel(PairBwdArgs a) {
 
 template <int VEC>
 void launch_pair_bwd_vec(const PairBwdArgs& a, hipStream_t s) {
-  const int G = group_for((a.dim + VEC - 1) / VEC);
+  const int G = glx_group_for((a.dim + VEC - 1) / VEC);
   const unsigned blocks = (unsigned)((a.num_rows_self + (256 / G) - 1) / (256 / G));
-  switch (G) {
-    case 8: glx_pair_dot_bwd_kernel<8, VEC><<<blocks, 256, 0, s>>>(a); break;
-    case 16: glx_pair_dot_bwd_kernel<16, VEC><<<blocks, 256, 0, s>>>(a); break;
-    case 32: glx_pair_dot_bwd_kernel<32, VEC><<<blocks, 256, 0, s>>>(a); break;
-    default: glx_pair_dot_bwd_kernel<64, VEC><<<blocks, 256, 0, s>>>(a); break;
-  }
+  glx_for_group(G, [&](auto g) { glx_pair_dot_bwd_kernel<decltype(g)::value, VEC><<<blocks, 256, 0, s>>>(a); });
 }
 
 void launch_pair_bwd(const PairBwdArgs& a, hipStream_t s) {
-  const bool vec4 = a.dim % 4 == 0 && a.C % 4 == 0 && aligned16(a.x_other) && aligned16(a.grad_self);
+  const bool vec4 = a.dim % 4 == 0 && a.C % 4 == 0 && glx_aligned16(a.x_other) && glx_aligned16(a.grad_self);
   if (vec4) launch_pair_bwd_vec<4>(a, s);
   else launch_pair_bwd_vec<1>(a, s);
 }
@@ -289,8 +209,6 @@ extern "C" int glx_pair_dot(int device, const float* xa, int64_t num_rows_a, con
     a.C = dim / heads;
     a.num_pairs = num_pairs;
     a.repeat = repeat;
-    a.sub = 1;
-    a.steps = 1;
     a.default_attr = default_attr;
     launch_pair_fwd(a, st.s);
   }
@@ -328,11 +246,7 @@ extern "C" int glx_pair_dot_backward(int device, int side, const int64_t* ia, co
   GlxScratch lease;
   if (rc == GLX_OK) {
     if (num_pairs == 0) {  // no pair: every row is zeros
-      hipError_t e = hipMemsetAsync(a.grad_self, 0, (size_t)num_rows_self * dim * sizeof(float), st.s);
-      if (e != hipSuccess) {
-        glx_set_error("hipMemsetAsync failed: %s", hipGetErrorString(e));
-        rc = GLX_INTERNAL;
-      }
+      rc = glx_zero_f32_async(a.grad_self, (size_t)num_rows_self * dim, st.s);
     } else {
       // one position per segment; side 0 sorts the num_pairs / repeat entries of ia only
       const int32_t own_n = side == 0 ? num_pairs / repeat : num_pairs;

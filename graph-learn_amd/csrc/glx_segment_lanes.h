@@ -1,9 +1,10 @@
-// The lane mapping that the per-segment normalisations share (glx_segment_softmax.hip, glx_gat_attention.hip): a
-// group of G lanes owns one segment, a segment of more than kSmLongItems items is walked by the whole workgroup, and
-// every reduction runs in a fixed tree -- the same inputs give the same bits on every call.
+// The segment layout of a counts= request, and the lane mapping that the per-segment normalisations share
+// (glx_segment_softmax.hip, glx_gat_attention.hip): a group of G lanes owns one segment, a segment of more than
+// kSmLongItems items is walked by the whole workgroup, and every reduction runs in a fixed tree -- the same inputs give
+// the same bits on every call.
 #ifndef GLX_SEGMENT_LANES_H_
 #define GLX_SEGMENT_LANES_H_
-#include "glx_common.h"
+#include "glx_lane_groups.h"
 
 constexpr int kSmR = 4;                // items of a segment a lane keeps in registers between the passes
 constexpr int kSmLongItems = 1024;     // a segment with more items than this is walked by the whole workgroup
@@ -39,36 +40,80 @@ __device__ __forceinline__ float sm_block_reduce(float x, int min_off, float* re
   return r;
 }
 
-// the consumed positions [s0, s1) of segment sg; A carries seg_end (inclusive prefix sums of the clamped counts, or
-// nullptr: the implied layout), fanout and num_ids
-template <typename A>
-__device__ __forceinline__ void sm_bounds(const A& a, int64_t sg, int32_t* s0, int32_t* s1) {
+// The ragged-or-implied layout of a counts= request: segment sg is positions [seg_end[sg - 1], seg_end[sg]) (seg_end:
+// the inclusive prefix sums of the counts clamped at 0), or, with seg_end == nullptr, `fanout` positions each.  Counts
+// that promise more positions than the request has are cut at num_ids; a position no segment reaches is not consumed.
+struct GlxSegLayout {
+  const int64_t* seg_end;  // [num_segments], or nullptr: the implied layout
+  int32_t fanout, num_ids, num_segments;
+};
+
+// the consumed positions [s0, s1) of segment sg
+__device__ __forceinline__ void seg_bounds(const GlxSegLayout& L, int64_t sg, int32_t* s0, int32_t* s1) {
   int64_t b0, b1;
-  if (a.seg_end) {
-    b0 = sg ? a.seg_end[sg - 1] : 0;
-    b1 = a.seg_end[sg];
+  if (L.seg_end) {
+    b0 = sg ? L.seg_end[sg - 1] : 0;
+    b1 = L.seg_end[sg];
   } else {
-    b0 = sg * (int64_t)a.fanout;
-    b1 = b0 + a.fanout;
+    b0 = sg * (int64_t)L.fanout;
+    b1 = b0 + L.fanout;
   }
-  if (b0 > a.num_ids) b0 = a.num_ids;  // counts that promise more positions than the request has are cut
-  if (b1 > a.num_ids) b1 = a.num_ids;
+  if (b0 > L.num_ids) b0 = L.num_ids;  // a cnt that promises more positions than the request has reads none of them
+  if (b1 > L.num_ids) b1 = L.num_ids;
   *s0 = (int32_t)b0;
   *s1 = (int32_t)b1;
 }
 
-// the first position that no segment consumed
-template <typename A>
-__device__ __forceinline__ int64_t sm_tail(const A& a) {
-  if (a.seg_end) {
-    const int64_t tail = a.seg_end[a.num_segments - 1];
-    return tail > a.num_ids ? a.num_ids : tail;
-  }
-  return (int64_t)a.num_segments * a.fanout;
+// s1 - s0 of seg_bounds, the positions of segment sg that the request really has: Mean's divisor
+__device__ __forceinline__ int32_t seg_count(const GlxSegLayout& L, int32_t sg) {
+  if (L.seg_end == nullptr) return L.fanout;
+  int64_t b0 = sg ? L.seg_end[sg - 1] : 0, b1 = L.seg_end[sg];
+  if (b0 > L.num_ids) b0 = L.num_ids;
+  if (b1 > L.num_ids) b1 = L.num_ids;
+  return (int32_t)(b1 - b0);
 }
 
-// the smallest group of 8 .. 64 lanes that covers `lanes`
-inline int sm_group_for(int64_t lanes) { return lanes <= 8 ? 8 : lanes <= 16 ? 16 : lanes <= 32 ? 32 : 64; }
+// the first position that no segment consumed
+__device__ __forceinline__ int64_t seg_tail(const GlxSegLayout& L) {
+  if (L.seg_end) {
+    const int64_t tail = L.seg_end[L.num_segments - 1];
+    return tail > L.num_ids ? L.num_ids : tail;
+  }
+  return (int64_t)L.num_segments * L.fanout;
+}
+
+// Is position p consumed?  *sg: its segment (0 when it is not) -- the first segment whose end lies beyond p, or
+// p / fanout.  The answer depends on p alone, so the lanes of a group that share p agree on it.
+__device__ __forceinline__ bool seg_of_position(const GlxSegLayout& L, int64_t p, int32_t* sg) {
+  bool consumed;
+  *sg = 0;
+  if (L.seg_end) {
+    consumed = p < L.seg_end[L.num_segments - 1];
+    if (consumed) {
+      int32_t lo = 0, hi = L.num_segments - 1;
+      while (lo < hi) {
+        const int32_t mid = lo + ((hi - lo) >> 1);
+        if (L.seg_end[mid] > p) hi = mid; else lo = mid + 1;
+      }
+      *sg = lo;
+    }
+  } else {
+    consumed = L.fanout > 0 && p / L.fanout < L.num_segments;
+    if (consumed) *sg = (int32_t)(p / L.fanout);
+  }
+  return consumed;
+}
+
+// The layout of a request of num_segments >= 1 segments; d_cnt: the counts on the device, or nullptr.  A ragged request
+// scans its counts into `lease` (workspace slot 1).
+inline int glx_seg_layout(const int32_t* d_cnt, int32_t num_ids, int32_t num_segments, hipStream_t s, GlxScratch* lease,
+                          GlxSegLayout* L) {
+  L->seg_end = nullptr;
+  L->fanout = num_ids / num_segments;
+  L->num_ids = num_ids;
+  L->num_segments = num_segments;
+  return d_cnt ? glx_agg_segment_ends(d_cnt, num_segments, s, lease, &L->seg_end) : GLX_OK;
+}
 
 // The group width comes from the mean item count of a segment (the sizes alone: the counts live on the device).
 // FLAT (heads a power of two <= 64): an item is one (position, head) and the group is at least `heads` wide;
@@ -77,7 +122,7 @@ inline int sm_width(int32_t heads, int32_t num_ids, int32_t num_segments, bool* 
   const int H = heads;
   *flat = H <= 64 && (H & (H - 1)) == 0;
   const int64_t items = *flat ? (int64_t)num_ids * H : (int64_t)num_ids;
-  int G = sm_group_for((items + num_segments - 1) / num_segments);
+  int G = glx_group_for((items + num_segments - 1) / num_segments);
   if (*flat && G < H) G = H;
   return G;
 }

@@ -18,9 +18,9 @@ namespace {
 struct SmArgs {
   const float* a;          // forward: e; backward: alpha                 [num_ids, heads]
   const float* g;          // backward: grad_alpha; forward: unused       [num_ids, heads]
-  const int64_t* seg_end;  // [num_segments] inclusive prefix sums of the clamped counts, or nullptr: the implied layout
+  GlxSegLayout seg;
   float* out;              // forward: alpha_out; backward: grad_e        [num_ids, heads]
-  int32_t heads, fanout, num_ids, num_segments;
+  int32_t heads;
 };
 
 // One (segment, head set) by a group of G lanes.  The lane's items are base[i * stride], i = c, c + G, ..; the first
@@ -133,9 +133,9 @@ __global__ __launch_bounds__(256) void glx_segment_softmax_kernel(SmArgs a) {
   const int64_t first = blockIdx.x * (int64_t)kSegs;
   {
     const int64_t sg = first + threadIdx.x / G;
-    if (sg < a.num_segments) {  // the same answer in every lane of the group
+    if (sg < a.seg.num_segments) {  // the same answer in every lane of the group
       int32_t s0, s1;
-      sm_bounds(a, sg, &s0, &s1);
+      seg_bounds(a.seg, sg, &s0, &s1);
       const int64_t items = FLAT ? (int64_t)(s1 - s0) * H : (int64_t)(s1 - s0);
       if (items > 0 && items <= kSmLongItems) {
         for (int o = 0; o < outer; ++o) {
@@ -148,9 +148,9 @@ __global__ __launch_bounds__(256) void glx_segment_softmax_kernel(SmArgs a) {
   }
   for (int j = 0; j < kSegs; ++j) {  // every condition below is the same in all 256 threads
     const int64_t sg = first + j;
-    if (sg >= a.num_segments) break;
+    if (sg >= a.seg.num_segments) break;
     int32_t s0, s1;
-    sm_bounds(a, sg, &s0, &s1);
+    seg_bounds(a.seg, sg, &s0, &s1);
     const int64_t items = FLAT ? (int64_t)(s1 - s0) * H : (int64_t)(s1 - s0);
     if (items <= kSmLongItems) continue;
     for (int o = 0; o < outer; ++o) {
@@ -159,27 +159,24 @@ __global__ __launch_bounds__(256) void glx_segment_softmax_kernel(SmArgs a) {
       else sm_fwd_block(a.a + at, a.out + at, items, stride, min_off, red);
     }
   }
-  const int64_t tail = sm_tail(a);
-  const int64_t end = (int64_t)a.num_ids * H;
+  const int64_t tail = seg_tail(a.seg);
+  const int64_t end = (int64_t)a.seg.num_ids * H;
   for (int64_t i = tail * H + blockIdx.x * 256LL + threadIdx.x; i < end; i += gridDim.x * 256LL) a.out[i] = 0.0f;
 }
 
 template <bool FLAT, bool BWD>
 void sm_launch_g(const SmArgs& a, int G, hipStream_t s) {
-  const unsigned blocks = sm_blocks(G, a.heads, a.num_ids, a.num_segments);
-  switch (G) {
-    case 8: glx_segment_softmax_kernel<8, FLAT, BWD><<<blocks, 256, 0, s>>>(a); break;
-    case 16: glx_segment_softmax_kernel<16, FLAT, BWD><<<blocks, 256, 0, s>>>(a); break;
-    case 32: glx_segment_softmax_kernel<32, FLAT, BWD><<<blocks, 256, 0, s>>>(a); break;
-    default: glx_segment_softmax_kernel<64, FLAT, BWD><<<blocks, 256, 0, s>>>(a); break;
-  }
+  const unsigned blocks = sm_blocks(G, a.heads, a.seg.num_ids, a.seg.num_segments);
+  glx_for_group(G, [&](auto g) {
+    glx_segment_softmax_kernel<decltype(g)::value, FLAT, BWD><<<blocks, 256, 0, s>>>(a);
+  });
 }
 
 // the group width and the item mapping: sm_width (glx_segment_lanes.h)
 template <bool BWD>
 void sm_launch(const SmArgs& a, hipStream_t s) {
   bool flat;
-  const int G = sm_width(a.heads, a.num_ids, a.num_segments, &flat);
+  const int G = sm_width(a.heads, a.seg.num_ids, a.seg.num_segments, &flat);
   if (flat) sm_launch_g<true, BWD>(a, G, s);
   else sm_launch_g<false, BWD>(a, G, s);
 }
@@ -205,19 +202,11 @@ int sm_run(int device, bool bwd, const float* in0, const float* in1, int32_t hea
   GlxScratch lease;
   if (rc == GLX_OK) {
     if (num_segments == 0) {  // nothing was consumed
-      hipError_t e = hipMemsetAsync(a.out, 0, count * sizeof(float), st.s);
-      if (e != hipSuccess) {
-        glx_set_error("hipMemsetAsync failed: %s", hipGetErrorString(e));
-        rc = GLX_INTERNAL;
-      }
+      rc = glx_zero_f32_async(a.out, count, st.s);
     } else {
-      a.seg_end = nullptr;
-      if (cnt != nullptr) rc = glx_agg_segment_ends(d_cnt, num_segments, st.s, &lease, &a.seg_end);
+      rc = glx_seg_layout(cnt ? d_cnt : nullptr, num_ids, num_segments, st.s, &lease, &a.seg);
       if (rc == GLX_OK) {
         a.heads = heads;
-        a.fanout = num_ids / num_segments;
-        a.num_ids = num_ids;
-        a.num_segments = num_segments;
         if (bwd) sm_launch<true>(a, st.s);
         else sm_launch<false>(a, st.s);
       }

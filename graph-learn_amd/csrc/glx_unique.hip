@@ -18,7 +18,7 @@
 //            their rank (tagged with bit 31) in their slot; the last position of every part writes part_end
 //   inverse  inverse[i] = rank left in table[slot_of[i]]
 // Every output is a function of the flags, and the flags of the input alone.
-#include "glx_common.h"
+#include "glx_lane_groups.h"
 
 namespace {
 
@@ -200,7 +200,6 @@ __global__ __launch_bounds__(256) void glx_unique_inverse_kernel(uint32_t n, con
   if (i < (int64_t)n) inverse[i] = (int64_t)(table[slot_of[i]] & ~kRankTag);
 }
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // Device pointers only; device selected.  n >= 1.
 int unique_device(const UniqueParts& x, uint32_t n, int64_t* nodes, int64_t* inverse, int64_t* part_end, hipStream_t s) {
@@ -210,10 +209,10 @@ int unique_device(const UniqueParts& x, uint32_t n, int64_t* nodes, int64_t* inv
   while (cap < (uint64_t)n + n / 2) cap <<= 1;
   const int32_t tile = (int64_t)n <= kSmallIds ? kTileSmall : kTile;
   const int64_t ntiles = ((int64_t)n + tile - 1) / tile;
-  const size_t table_b = align256(cap * sizeof(uint32_t));
-  const size_t slot_b = align256((size_t)n * sizeof(uint32_t));
-  const size_t first_b = align256((size_t)(((int64_t)n + 63) / 64) * sizeof(uint64_t));
-  const size_t tiles_b = align256((size_t)ntiles * sizeof(uint32_t));
+  const size_t table_b = glx_align256(cap * sizeof(uint32_t));
+  const size_t slot_b = glx_align256((size_t)n * sizeof(uint32_t));
+  const size_t first_b = glx_align256((size_t)(((int64_t)n + 63) / 64) * sizeof(uint64_t));
+  const size_t tiles_b = glx_align256((size_t)ntiles * sizeof(uint32_t));
   GlxScratch lease;
   int rc = lease.alloc(table_b + slot_b + first_b + tiles_b, s, 1);
   if (rc != GLX_OK) return rc;
