@@ -267,6 +267,25 @@ void launch_wbwd_w(const WBwdWArgs& a, hipStream_t s) {
 
 }  // namespace
 
+// grad_x of a request whose transpose the caller holds (device pointers, op Sum or Mean): the body of
+// glx_aggregate_weighted_backward_x, and the two row gradients of glx_dot_attention_backward on one transpose
+void glx_weighted_bwd_x(int op, const GlxAggTranspose& t, const float* w, const float* grad_out, float* grad_x,
+                        int64_t num_rows, int32_t dim, int32_t heads, int32_t num_ids, int32_t num_segments,
+                        hipStream_t s) {
+  WBwdXArgs a;
+  a.t = t;
+  a.w = w;
+  a.grad_out = grad_out;
+  a.grad_x = grad_x;
+  a.num_rows = num_rows;
+  a.dim = dim;
+  a.heads = heads;
+  a.C = dim / heads;
+  a.seg = GlxSegLayout{t.seg_end, t.fanout, num_ids, num_segments};
+  if (op == GLX_AGG_SUM) launch_wbwd_x<GLX_AGG_SUM>(a, s);
+  else launch_wbwd_x<GLX_AGG_MEAN>(a, s);
+}
+
 // what the three entry points check alike, before any device use
 #define GLX_WEIGHTED_REQUIRE(who)                                                                                       \
   GLX_REQUIRE(op >= GLX_AGG_SUM && op <= GLX_AGG_PROD, "unknown aggregator id %d", op);                                 \
@@ -349,13 +368,7 @@ extern "C" int glx_aggregate_weighted_backward_x(int device, int op, const int64
     } else {
       rc = glx_agg_transpose(d_rows, cnt ? d_cnt : nullptr, num_ids, num_segments, num_rows, st.s, &lease, &a.t);
       if (rc == GLX_OK) {
-        a.num_rows = num_rows;
-        a.dim = dim;
-        a.heads = heads;
-        a.C = dim / heads;
-        a.seg = GlxSegLayout{a.t.seg_end, a.t.fanout, num_ids, num_segments};
-        if (op == GLX_AGG_SUM) launch_wbwd_x<GLX_AGG_SUM>(a, st.s);
-        else launch_wbwd_x<GLX_AGG_MEAN>(a, st.s);
+        glx_weighted_bwd_x(op, a.t, a.w, a.grad_out, a.grad_x, num_rows, dim, heads, num_ids, num_segments, st.s);
       }
     }
   }

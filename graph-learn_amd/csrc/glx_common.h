@@ -861,6 +861,11 @@ struct GlxAggTranspose {
 };
 int glx_agg_transpose(const int64_t* rows, const int32_t* cnt, int32_t n, int32_t num_segments, int64_t num_rows,
                       hipStream_t s, GlxScratch* lease, GlxAggTranspose* out);
+// glx_aggregate_weighted_backward_x on a transpose the caller holds (glx_aggregate_weighted.hip): grad_x[num_rows, dim]
+// = +0.0f plus fmul_rn(w[p, head], grad_out[s(p)]) (Mean: / count) in ascending p; device pointers, every row written.
+void glx_weighted_bwd_x(int op, const GlxAggTranspose& t, const float* w, const float* grad_out, float* grad_x,
+                        int64_t num_rows, int32_t dim, int32_t heads, int32_t num_ids, int32_t num_segments,
+                        hipStream_t s);
 // seg_end[num_segments]: inclusive prefix sums of the clamped (>= 0) counts, in `lease` (workspace slot 1).
 int glx_agg_segment_ends(const int32_t* cnt, int32_t num_segments, hipStream_t s, GlxScratch* lease,
                          const int64_t** seg_end);

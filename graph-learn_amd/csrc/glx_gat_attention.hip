@@ -51,11 +51,7 @@ __device__ __forceinline__ float gat_leaky(float x, float pre, float slope) { re
 // dropout of element idx = p * heads + h of the request: the same function going forward and going back
 template <bool DROP>
 __device__ __forceinline__ float gat_drop(const GatArgs& a, float x, int32_t idx) {
-  if (!DROP) return x;
-  const GlxPhilox b = glx_philox_block((uint32_t)idx >> 2, 0u, a.seed, a.call);
-  const int k = idx & 3;
-  const uint32_t w = k == 0 ? b.w[0] : k == 1 ? b.w[1] : k == 2 ? b.w[2] : b.w[3];
-  return w >= a.thresh ? x * a.scale : 0.0f;
+  return DROP ? sm_dropout(x, idx, a.thresh, a.scale, a.seed, a.call) : x;
 }
 
 // Item i of a segment that starts at position s0.  FLAT: the segment's [count, heads] block is one run and item i is

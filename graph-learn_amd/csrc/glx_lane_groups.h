@@ -84,9 +84,10 @@ struct GlxHeadDots {
   int32_t steps;  // SUB: column tiles a head spans (C / VEC / G, at least 1)
 };
 
-template <int G, int VEC, bool SUB, bool DIV>
-__device__ __forceinline__ void glx_head_dots(GlxRow ra, GlxRow rb, float default_attr, int32_t dim, int32_t heads,
-                                              int32_t C, GlxHeadDots hd, float div, int c, float* out) {
+// la(col) / lb(col): the VEC columns of either operand from `col` on -- a gathered row, or anything computed from one.
+template <int G, int VEC, bool SUB, bool DIV, typename LA, typename LB>
+__device__ __forceinline__ void glx_head_dots_of(LA&& la, LB&& lb, int32_t dim, int32_t heads, int32_t C, GlxHeadDots hd,
+                                                 float div, int c, float* out) {
   typedef float vec_t __attribute__((ext_vector_type(VEC)));
   if (SUB) {
     const int32_t span = G * VEC * hd.steps;  // columns per reduce: G / sub whole heads, or one
@@ -95,8 +96,8 @@ __device__ __forceinline__ void glx_head_dots(GlxRow ra, GlxRow rb, float defaul
       for (int32_t k = 0; k < hd.steps; ++k) {
         const int32_t col = col_pass + (k * G + c) * VEC;
         if (col < dim) {
-          const vec_t u = glx_row_load<VEC>(ra, col, default_attr);
-          const vec_t w = glx_row_load<VEC>(rb, col, default_attr);
+          const vec_t u = la(col);
+          const vec_t w = lb(col);
 #pragma unroll
           for (int v = 0; v < VEC; ++v) part += u[v] * w[v];
         }
@@ -111,8 +112,8 @@ __device__ __forceinline__ void glx_head_dots(GlxRow ra, GlxRow rb, float defaul
       float part = 0.0f;
       for (int32_t i = c; i < L; i += G) {
         const int32_t col = h * C + i * VEC;
-        const vec_t u = glx_row_load<VEC>(ra, col, default_attr);
-        const vec_t w = glx_row_load<VEC>(rb, col, default_attr);
+        const vec_t u = la(col);
+        const vec_t w = lb(col);
 #pragma unroll
         for (int v = 0; v < VEC; ++v) part += u[v] * w[v];
       }
@@ -121,6 +122,15 @@ __device__ __forceinline__ void glx_head_dots(GlxRow ra, GlxRow rb, float defaul
       if (c == 0) out[h] = DIV ? part / div : part;
     }
   }
+}
+
+// the two operands are gathered rows
+template <int G, int VEC, bool SUB, bool DIV>
+__device__ __forceinline__ void glx_head_dots(GlxRow ra, GlxRow rb, float default_attr, int32_t dim, int32_t heads,
+                                              int32_t C, GlxHeadDots hd, float div, int c, float* out) {
+  glx_head_dots_of<G, VEC, SUB, DIV>([&](int32_t col) { return glx_row_load<VEC>(ra, col, default_attr); },
+                                     [&](int32_t col) { return glx_row_load<VEC>(rb, col, default_attr); }, dim, heads,
+                                     C, hd, div, c, out);
 }
 
 // The host side of glx_head_dots for rows of `dim` columns, C to a head, read VEC at a time: which mapping, the group

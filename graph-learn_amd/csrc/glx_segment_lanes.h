@@ -1,5 +1,5 @@
 // The segment layout of a counts= request, and the lane mapping that the per-segment normalisations share
-// (glx_segment_softmax.hip, glx_gat_attention.hip): a group of G lanes owns one segment, a segment of more than
+// (glx_segment_softmax.hip, glx_gat_attention.hip, glx_dot_attention.hip): a group of G lanes owns one segment, a segment of more than
 // kSmLongItems items is walked by the whole workgroup, and every reduction runs in a fixed tree -- the same inputs give
 // the same bits on every call.
 #ifndef GLX_SEGMENT_LANES_H_
@@ -38,6 +38,16 @@ __device__ __forceinline__ float sm_block_reduce(float x, int min_off, float* re
   const float r = red[tid & (min_off - 1)];
   __syncthreads();  // red is free again
   return r;
+}
+
+// Dropout of element idx of a request under (seed, call): word idx & 3 of Philox block idx >> 2 (row 0); kept, and
+// scaled, iff the word reaches thresh = floor(drop_p * 2^32).  The same function going forward and going back.
+__device__ __forceinline__ float sm_dropout(float x, int32_t idx, uint32_t thresh, float scale, uint64_t seed,
+                                            uint64_t call) {
+  const GlxPhilox b = glx_philox_block((uint32_t)idx >> 2, 0u, seed, call);
+  const int k = idx & 3;
+  const uint32_t w = k == 0 ? b.w[0] : k == 1 ? b.w[1] : k == 2 ? b.w[2] : b.w[3];
+  return w >= thresh ? x * scale : 0.0f;
 }
 
 // The ragged-or-implied layout of a counts= request: segment sg is positions [seg_end[sg - 1], seg_end[sg]) (seg_end:

@@ -49,6 +49,7 @@ EXPORTS = [
     "glx_aggregate_weighted", "glx_aggregate_weighted_backward_x", "glx_aggregate_weighted_backward_w",
     "glx_segment_softmax", "glx_segment_softmax_backward",
     "glx_gat_attention", "glx_gat_attention_backward",
+    "glx_dot_attention", "glx_dot_attention_backward",
     "glx_pair_dot", "glx_pair_dot_backward",
     "glx_rows_coalesce", "glx_embedding_update",
     "glx_partition", "glx_stitch_i64", "glx_stitch_f32", "glx_aggregate_stitch",
@@ -178,6 +179,10 @@ def lib():
         L.glx_gat_attention.argtypes = [ci, vp, vp, i64, vp, i32, vp, i32, i32, f32, f32, f32, u64, u64, vp, vp, ci, vp]
         L.glx_gat_attention_backward.argtypes = [ci, vp, vp, vp, vp, i64, vp, i32, vp, i32, i32, f32, f32, f32, u64, u64,
                                                  vp, vp, vp, ci, vp]
+        L.glx_dot_attention.argtypes = [ci, vp, vp, vp, i64, i32, i32, vp, vp, vp, i32, i32, f32, f32, f32, u64, u64, vp,
+                                        vp, vp, ci, vp]
+        L.glx_dot_attention_backward.argtypes = [ci, vp, vp, vp, i64, i32, i32, vp, vp, vp, i32, i32, f32, f32, f32, u64,
+                                                 u64, vp, vp, vp, vp, vp, vp, vp, ci, vp]
         L.glx_pair_dot.argtypes = [ci, vp, i64, vp, i64, i32, i32, vp, vp, i32, i32, f32, vp, ci, vp]
         L.glx_pair_dot_backward.argtypes = [ci, ci, vp, vp, i32, i32, vp, i32, vp, i64, i32, i64, f32, vp, ci, vp]
         L.glx_rows_coalesce.argtypes = [ci, vp, i32, i64, i32, vp, vp, vp, vp, ci, vp]
@@ -885,6 +890,86 @@ def gat_attention_backward(soft, grad_alpha, s, t, rows, cnt=None, negative_slop
                                             num_segments, negative_slope, default_attr, drop_p, seed, call, pe[0],
                                             pgs[0], pgt[0], kind, _stream(kind, device)))
     return grad_e, grad_s, grad_t
+
+
+def _dot_shapes(q, k, v, rows, edge, heads):
+    """(n, num_segments, num_rows, dim) of a dot_attention request"""
+    n, dim = int(rows.shape[0]), int(q.shape[1])
+    assert int(k.shape[1]) == dim and tuple(v.shape) == tuple(k.shape), "q, k and v must have the same columns"
+    assert edge is None or tuple(edge.shape) == (n, dim), "edge must be [n, D]"
+    assert heads >= 1 and dim % heads == 0, "heads must divide D"
+    return n, int(q.shape[0]), int(k.shape[0]), dim
+
+
+def _same_table(k, v):
+    """is v the very buffer of k (one table serving as key and value)"""
+    if k is v:
+        return True
+    if _is_torch(k) and _is_torch(v):
+        return k.data_ptr() == v.data_ptr()
+    return isinstance(k, np.ndarray) and isinstance(v, np.ndarray) and k.ctypes.data == v.ctypes.data
+
+
+def dot_attention(q, k, v, rows, cnt=None, edge=None, heads=1, scale=None, default_attr=0.0, drop_p=0.0, seed=0, call=0,
+                  want_logit=False, out=None, soft_out=None, logit_out=None, device=0):
+    """Scaled dot-product attention of every segment over its positions, with an edge term on the key and on the value
+    (glx_dot_attention) -> (out[S, D], soft[n, heads], logit[n, heads] or None), float32.  q[S, D] one query per
+    segment; k, v[M, D] (they may be one buffer); rows[n] int64 (a value outside [0, M) reads a row of default_attr in
+    both tables); edge[n, D] or None; cnt[S] int32 (None: the implied layout of n // S positions per segment); column c
+    belongs to head c // (D // heads).  logit = (q . (k[rows] + edge)) * scale per head (scale None: 1 / sqrt(D // heads)
+    rounded to float32), soft its softmax over each segment (glx_segment_softmax's definition), alpha gat_attention's
+    dropout of soft under (seed, call), out the sum of alpha * (v[rows] + edge) in ascending position: bit-exact from
+    soft, an empty segment is +0.0.  No atomics: the same bits on every call.  Torch CUDA tensors are device pointers
+    on the current stream, numpy arrays host pointers."""
+    n, num_segments, num_rows, dim = _dot_shapes(q, k, v, rows, edge, heads)
+    if scale is None:
+        scale = float(np.float32(1.0) / np.sqrt(np.float32(dim // heads)))
+    res = _weighted_out(out, q, (num_segments, dim))
+    soft = _weighted_out(soft_out, q, (n, heads))
+    logit = _weighted_out(logit_out, q, (n, heads)) if (want_logit or logit_out is not None) else None
+    pq, pk, pr, pe, pc = _ptr(q), _ptr(k), _ptr(rows), _ptr(edge), _ptr(cnt)
+    pv = pk if _same_table(k, v) else _ptr(v)
+    pl, ps, po = _ptr(logit), _ptr(soft), _ptr(res)
+    kind = _kind(pq, pk, pv, pr, pe, pc, pl, ps, po)
+    if kind == PTR_DEVICE:
+        device = res.device.index or 0
+    _check(lib().glx_dot_attention(device, pq[0], pk[0], pv[0], num_rows, dim, heads, pr[0], pe[0], pc[0], n,
+                                   num_segments, scale, default_attr, drop_p, seed, call, pl[0], ps[0], po[0], kind,
+                                   _stream(kind, device)))
+    return res, soft, logit
+
+
+def dot_attention_backward(soft, grad_out, q, k, v, rows, cnt=None, edge=None, heads=1, scale=None, default_attr=0.0,
+                           drop_p=0.0, seed=0, call=0, want_q=True, want_k=True, want_v=True, want_edge=True, out=None,
+                           out_q=None, out_k=None, out_v=None, out_edge=None, device=0):
+    """Gradients of dot_attention (glx_dot_attention_backward) -> (grad_e[n, heads], grad_q[S, D], grad_k[M, D],
+    grad_v[M, D], grad_edge[n, D]; None for a gradient that was not asked for, and grad_edge is None without edge) from
+    the forward's `soft`, the gradient of its `out` and the forward's own arguments (alpha and the dropout mask are
+    recomputed from soft, seed and call).  grad_e is the gradient of the logits; grad_q and grad_edge are bit-exact
+    folds of it, grad_k and grad_v the bits of aggregate_weighted_backward_x(SUM, rows, grad_e, cnt, q, M) and of
+    aggregate_weighted_backward_x(SUM, rows, alpha, cnt, grad_out, M) on one transpose.  Every element is written; no
+    atomics: the same bits on every call."""
+    n, num_segments, num_rows, dim = _dot_shapes(q, k, v, rows, edge, heads)
+    if scale is None:
+        scale = float(np.float32(1.0) / np.sqrt(np.float32(dim // heads)))
+    grad_e = _weighted_out(out, soft, (n, heads))
+    grad_q = _weighted_out(out_q, soft, (num_segments, dim)) if (want_q or out_q is not None) else None
+    grad_k = _weighted_out(out_k, soft, (num_rows, dim)) if (want_k or out_k is not None) else None
+    grad_v = _weighted_out(out_v, soft, (num_rows, dim)) if (want_v or out_v is not None) else None
+    grad_edge = None
+    if edge is not None and (want_edge or out_edge is not None):
+        grad_edge = _weighted_out(out_edge, soft, (n, dim))
+    pq, pk, pr, pe, pc = _ptr(q), _ptr(k), _ptr(rows), _ptr(edge), _ptr(cnt)
+    pv = pk if _same_table(k, v) else _ptr(v)
+    pso, pg = _ptr(soft), _ptr(grad_out)
+    pge, pgq, pgk, pgv, pged = _ptr(grad_e), _ptr(grad_q), _ptr(grad_k), _ptr(grad_v), _ptr(grad_edge)
+    kind = _kind(pq, pk, pv, pr, pe, pc, pso, pg, pge, pgq, pgk, pgv, pged)
+    if kind == PTR_DEVICE:
+        device = grad_e.device.index or 0
+    _check(lib().glx_dot_attention_backward(device, pq[0], pk[0], pv[0], num_rows, dim, heads, pr[0], pe[0], pc[0], n,
+                                            num_segments, scale, default_attr, drop_p, seed, call, pso[0], pg[0],
+                                            pge[0], pgq[0], pgk[0], pgv[0], pged[0], kind, _stream(kind, device)))
+    return grad_e, grad_q, grad_k, grad_v, grad_edge
 
 
 def _pair_counts(ia, ib, repeat):

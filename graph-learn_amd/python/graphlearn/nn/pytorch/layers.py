@@ -3,12 +3,16 @@
 GATConv is the reference's multi-head GAT layer (graphlearn/python/nn/tf/layers/gat_conv.py:29-119) for a sampled
 batch: one row of features per distinct node, the seeds' positions among them, and the neighbours of every seed as one
 segment of a counts= request (a FullSampler hop) or of the implied layout (a fixed fan-out).
+
+TransformerConv is the layer of the reference's GPU PyTorch model (graphlearn/examples/pytorch/tgn/train_and_eval.py:38-50:
+TransformerConv(in, out // 2, heads=2, dropout=0.1, edge_dim=...)) over the same batches: scaled dot-product attention of
+every seed over its neighbours, with the edge features mapped into the key and the value.
 """
 import torch
 
-from graphlearn.nn.pytorch.segment import gat_attention, gather_rows, weighted_segment_aggregate
+from graphlearn.nn.pytorch.segment import dot_attention, gat_attention, gather_rows, weighted_segment_aggregate
 
-__all__ = ["GATConv"]
+__all__ = ["GATConv", "TransformerConv"]
 
 
 class GATConv(torch.nn.Module):
@@ -104,3 +108,79 @@ class GATConv(torch.nn.Module):
   def extra_repr(self):
     return "in_dim={}, out_dim={}, num_heads={}, concat={}, dropout={}, negative_slope={}, add_self_loops={}".format(
         self.in_dim, self.out_dim, self.num_heads, self.concat, self.dropout, self.negative_slope, self.add_self_loops)
+
+
+class TransformerConv(torch.nn.Module):
+  """out[s] = sum over the neighbours u of seed s of alpha[s, u, h] * ((W_v x_u)[h] + (W_e e_su)[h]), per head h, with
+  alpha = dropout(softmax_u(((W_q x_s)[h] . ((W_k x_u)[h] + (W_e e_su)[h])) / sqrt(out_dim))), plus W_skip x_s when
+  root_weight -- the TransformerConv of train_and_eval.py:38-50 (Shi et al., "Masked Label Prediction", 2021) without
+  its `beta` gate.  The attention, from the logits to the weighted sum, is one dot_attention call.
+
+  in_dim, out_dim   columns of x_nodes and of each head's output
+  heads             H; concat=True returns [S, H * out_dim], concat=False the mean over the heads, [S, out_dim]
+  dropout           on the attention coefficients, in training mode only, seeded like GATConv: `seed` defaults to
+                    torch.initial_seed() (read at each forward) and `call` counts this module's training forwards.
+                    Layers that share a seed share their masks position by position: give each layer its own seed.
+  edge_dim          None, or the columns of edge_attr: a bias-free linear map takes them to H * out_dim
+  root_weight       add a linear map of the seed's own features (the skip connection), of the output's shape
+  bias              of the query, key, value and skip maps
+
+  Every op is float32 on one GPU; the segments are described by counts (or the implied layout), not by explicit
+  segment ids, and there is no mask for padded neighbours beyond counts.
+  """
+
+  def __init__(self, in_dim, out_dim, heads=1, concat=True, dropout=0.0, edge_dim=None, root_weight=True, bias=True,
+               seed=None):
+    super().__init__()
+    in_dim, out_dim, heads = int(in_dim), int(out_dim), int(heads)
+    if in_dim < 1 or out_dim < 1 or heads < 1:
+      raise ValueError("TransformerConv: in_dim, out_dim and heads must be positive")
+    if not 0.0 <= float(dropout) < 1.0:
+      raise ValueError("TransformerConv: dropout must lie in [0, 1)")
+    if edge_dim is not None and int(edge_dim) < 1:
+      raise ValueError("TransformerConv: edge_dim must be positive or None")
+    self.in_dim, self.out_dim, self.heads = in_dim, out_dim, heads
+    self.concat, self.dropout = bool(concat), float(dropout)
+    self.edge_dim = None if edge_dim is None else int(edge_dim)
+    self.seed = None if seed is None else int(seed)
+    self.calls = 0  # training forwards so far: the `call` of the next dropout mask
+    self.lin_query = torch.nn.Linear(in_dim, heads * out_dim, bias=bool(bias))
+    self.lin_key = torch.nn.Linear(in_dim, heads * out_dim, bias=bool(bias))
+    self.lin_value = torch.nn.Linear(in_dim, heads * out_dim, bias=bool(bias))
+    self.lin_edge = None if self.edge_dim is None else torch.nn.Linear(self.edge_dim, heads * out_dim, bias=False)
+    if root_weight:
+      self.lin_skip = torch.nn.Linear(in_dim, heads * out_dim if self.concat else out_dim, bias=bool(bias))
+    else:
+      self.lin_skip = None
+
+  def forward(self, x_nodes, seed_local, nbr_local, counts=None, edge_attr=None):
+    """x_nodes [M, in_dim]: the features of the batch's distinct nodes; seed_local [S] int64: the seeds' rows among
+    them; nbr_local int64 (n positions, flattened): the neighbours' rows, segment s being the next counts[s] of them
+    (counts int32 [S]), or n / S each when counts is None; edge_attr [n, edge_dim]: one row per position (required iff
+    the layer has an edge map).  The query, key, value and skip maps run once per distinct node.  Returns
+    [S, H * out_dim] or [S, out_dim]."""
+    H, C = self.heads, self.out_dim
+    seed_local = seed_local.reshape(-1)
+    S = seed_local.numel()
+    if (edge_attr is None) != (self.lin_edge is None):
+      raise ValueError("TransformerConv: edge_attr is required iff the layer was built with edge_dim")
+    q = gather_rows(self.lin_query(x_nodes), seed_local)                        # [S, H * C]
+    k = self.lin_key(x_nodes)                                                   # [M, H * C]
+    v = self.lin_value(x_nodes)
+    edge = None if edge_attr is None else self.lin_edge(edge_attr.reshape(-1, self.edge_dim))
+    drop, seed, call = 0.0, 0, 0
+    if self.training and self.dropout > 0.0:
+      drop = self.dropout
+      seed = (torch.initial_seed() if self.seed is None else self.seed) & (2 ** 64 - 1)
+      call = self.calls
+      self.calls += 1
+    out = dot_attention(q, k, v, nbr_local, S, counts=counts, edge=edge, heads=H, dropout=drop, seed=seed, call=call)
+    if not self.concat:
+      out = out.view(S, H, C).mean(1)
+    if self.lin_skip is not None:
+      out = out + gather_rows(self.lin_skip(x_nodes), seed_local)
+    return out
+
+  def extra_repr(self):
+    return "in_dim={}, out_dim={}, heads={}, concat={}, dropout={}, edge_dim={}, root_weight={}".format(
+        self.in_dim, self.out_dim, self.heads, self.concat, self.dropout, self.edge_dim, self.lin_skip is not None)

@@ -1,7 +1,7 @@
 """Differentiable segment reductions, row gathers and pair scores over a device-resident matrix: the torch surface of
 glx_aggregate / glx_aggregate_arg / glx_aggregate_backward, of glx_aggregate_weighted and its two gradients, of
-glx_segment_softmax and its gradient, of glx_gat_attention and its gradients and of glx_pair_dot and its gradient
-(include/glx.h).
+glx_segment_softmax and its gradient, of glx_gat_attention and its gradients, of glx_dot_attention and its gradients
+and of glx_pair_dot and its gradient (include/glx.h).
 
 The role of tf.math.unsorted_segment_sum / unsorted_segment_mean under the reference's layers
 (graphlearn/python/nn/tf/layers/sage_conv.py:69-73, gcn_conv.py:73), for matrices that are computed on the way --
@@ -36,6 +36,15 @@ leaky_relu(s[segment] + t[index]), its softmax over each segment and dropout on 
 
 with a dropout mask that is a function of (seed, call, position, head) alone: two runs give the same bits.
 
+dot_attention is the whole of a transformer-style layer's attention (TransformerConv in the reference's
+examples/pytorch/tgn/train_and_eval.py:38-50): the scaled dot product of every seed's query with its neighbours' keys,
+the softmax over each segment, dropout, and the weighted sum of the neighbours' values, with an edge term added to key
+and value,
+
+    h = dot_attention(q[seed_local], k, v, nbr_local, S, counts=deg, edge=e, heads=2, dropout=0.1, seed=seed, call=step)
+
+one launch going forward, and neither `k[index] + e` nor `v[index] + e` is ever materialised.
+
 pair_dot is the scoring step of the reference's unsupervised models (examples/tf/sage/train.py:56-57,
 python/nn/tf/loss.py:58): the dot product of the two endpoint embeddings of an edge, and of a source with each of its
 K sampled negatives,
@@ -48,7 +57,7 @@ without the two [n, D] gathers of `(z[src].unsqueeze(1) * z[neg]).sum(-1)` and w
 import torch
 
 __all__ = ["segment_aggregate", "gather_rows", "weighted_segment_aggregate", "segment_softmax", "gat_attention",
-           "pair_dot"]
+           "dot_attention", "pair_dot"]
 
 _OPS = {"sum": 0, "mean": 1, "max": 2, "min": 3, "prod": 4}
 
@@ -404,6 +413,109 @@ def gat_attention(s, t, index, num_segments, counts=None, negative_slope=0.2, dr
     raise ValueError("{}: seed and call must fit 64 unsigned bits".format(who))
   return _GatAttention.apply(s.reshape(num_segments, heads), t.reshape(int(t.shape[0]), heads), index, counts,
                              negative_slope, dropout, seed, call, float(default_attr))
+
+
+class _DotAttention(torch.autograd.Function):
+
+  @staticmethod
+  def forward(ctx, q, k, v, edge, index, counts, heads, scale, drop_p, seed, call, default_attr):
+    qd, kd, vd = q.detach(), k.detach(), v.detach()
+    ed = None if edge is None else edge.detach()
+    out, soft, _ = _glx().dot_attention(qd, kd, vd, index, cnt=counts, edge=ed, heads=heads, scale=scale,
+                                        default_attr=default_attr, drop_p=drop_p, seed=seed, call=call)
+    ctx.cfg = (heads, scale, default_attr, drop_p, seed, call)
+    ctx.has_edge, ctx.has_counts = ed is not None, counts is not None
+    ctx.save_for_backward(*([soft, qd, kd, vd, index] + ([ed] if ed is not None else []) +
+                            ([counts] if counts is not None else [])))
+    return out
+
+  @staticmethod
+  def backward(ctx, grad):
+    _no_double_backward("dot_attention")
+    want_q, want_k, want_v, want_e = ctx.needs_input_grad[:4]
+    if not (want_q or want_k or want_v or want_e):
+      return (None,) * 12
+    saved = list(ctx.saved_tensors)
+    soft, q, k, v, index = saved[:5]
+    edge = saved[5] if ctx.has_edge else None
+    counts = saved[-1] if ctx.has_counts else None
+    heads, scale, default_attr, drop_p, seed, call = ctx.cfg
+    grad = grad.to(torch.float32).contiguous()
+    _, gq, gk, gv, ge = _glx().dot_attention_backward(soft, grad, q, k, v, index, cnt=counts, edge=edge, heads=heads,
+                                                      scale=scale, default_attr=default_attr, drop_p=drop_p, seed=seed,
+                                                      call=call, want_q=want_q, want_k=want_k, want_v=want_v,
+                                                      want_edge=want_e)
+    return (gq, gk, gv, ge) + (None,) * 8
+
+
+def dot_attention(q, k, v, index, num_segments, counts=None, edge=None, heads=1, scale=None, dropout=0.0, seed=0, call=0,
+                  default_attr=0.0):
+  """[S, D]: scaled dot-product attention of every segment over its positions.  For position p of segment sg and head
+  h (columns [h C, (h + 1) C), C = D / heads): the logit scale * (q[sg] . (k[index[p]] + edge[p])) over the head's
+  columns, its softmax over the segment's positions (segment_softmax's definition and exact rules), gat_attention's
+  dropout on the coefficients, and out[sg] = the sum over p, in ascending order, of alpha[p, h] * (v[index[p]] + edge[p])
+  -- one kernel going forward, no atomics in either direction, bit-identical on every run.
+
+  q        [S, D] contiguous float32 CUDA tensor, S == num_segments: one query per segment; may require grad
+  k, v     [M, D] like q: the key and the value of every node; may require grad, and may be one tensor (autograd then
+           adds the two gradients: one more float32 add per element)
+  index    int64 CUDA tensor of any shape (flattened, n positions): rows of k and v.  A value outside [0, M) reads a
+           row of `default_attr` in both and passes no gradient to them
+  counts   None: num_segments equal segments of n / num_segments positions; or an int32 [num_segments] tensor: segment
+           sg is the next counts[sg] positions, positions from counts.sum() on are ignored.  There is no mask for padded
+           neighbours beyond counts
+  edge     None, or [n, D] like q: the edge term of every position, added to its key and to its value; may require grad
+  scale    None: 1 / sqrt(C), rounded to float32; or a finite float
+  dropout  p in [0, 1), with gat_attention's mask under (seed, call).  Use a new `call` for every step.
+  An empty segment is 0.  Only the gradients that are needed are computed.  Anything else raises ValueError.
+  """
+  who = "dot_attention"
+  for name, x in (("q", q), ("k", k), ("v", v)) + ((("edge", edge),) if edge is not None else ()):
+    if not isinstance(x, torch.Tensor):
+      raise ValueError("{}: {} must be a torch tensor".format(who, name))
+    if x.dtype != torch.float32:
+      raise ValueError("{}: {} must be float32, not {}".format(who, name, x.dtype))
+    if not x.is_cuda or x.dim() != 2 or not x.is_contiguous():
+      raise ValueError("{}: {} must be a contiguous [N, D] CUDA tensor".format(who, name))
+    if x.device != q.device:
+      raise ValueError("{}: {} lives on {}, q on {}".format(who, name, x.device, q.device))
+  if not isinstance(index, torch.Tensor) or index.dtype != torch.int64:
+    raise ValueError("{}: index must be an int64 tensor".format(who))
+  if index.device != q.device:
+    raise ValueError("{}: index lives on {}, q on {}".format(who, index.device, q.device))
+  D, heads = int(q.shape[1]), int(heads)
+  if D < 1 or int(k.shape[1]) != D or tuple(v.shape) != tuple(k.shape):
+    raise ValueError("{}: q [S, D], k [M, D] and v [M, D] must agree on D >= 1 and M".format(who))
+  if heads < 1 or D % heads != 0:
+    raise ValueError("{}: the number of heads ({}) must divide D ({})".format(who, heads, D))
+  num_segments = int(num_segments)
+  if num_segments < 0 or int(q.shape[0]) != num_segments:
+    raise ValueError("{}: q must have one row per segment ({}), not {}".format(who, num_segments, int(q.shape[0])))
+  index = index.reshape(-1).contiguous()
+  n = index.numel()
+  if edge is not None and tuple(edge.shape) != (n, D):
+    raise ValueError("{}: edge must be [n, D] = {}, not {}".format(who, (n, D), tuple(edge.shape)))
+  if counts is not None:
+    if not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32 or counts.device != q.device:
+      raise ValueError("{}: counts must be an int32 tensor on q's device".format(who))
+    if counts.dim() != 1 or counts.numel() != num_segments:
+      raise ValueError("{}: counts must have one entry per segment".format(who))
+    counts = counts.contiguous()
+  elif num_segments == 0 or n % num_segments != 0:
+    raise ValueError("{}: without counts, index.numel() must be a multiple of num_segments".format(who))
+  if n * heads > 2 ** 31 - 1 or num_segments * D > 2 ** 31 - 1:
+    raise ValueError("{}: n * H or num_segments * D exceeds int32".format(who))
+  if scale is None:
+    scale = float(torch.tensor(1.0, dtype=torch.float32) / torch.tensor(float(D // heads), dtype=torch.float32).sqrt())
+  scale, dropout = float(scale), float(dropout)
+  if scale != scale or scale in (float("inf"), float("-inf")):
+    raise ValueError("{}: scale must be finite".format(who))
+  if not 0.0 <= dropout < 1.0:
+    raise ValueError("{}: dropout must lie in [0, 1)".format(who))
+  seed, call = int(seed), int(call)
+  if not (0 <= seed < 2 ** 64 and 0 <= call < 2 ** 64):
+    raise ValueError("{}: seed and call must fit 64 unsigned bits".format(who))
+  return _DotAttention.apply(q, k, v, edge, index, counts, heads, scale, dropout, seed, call, float(default_attr))
 
 
 class _PairDot(torch.autograd.Function):

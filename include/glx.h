@@ -42,7 +42,8 @@ extern "C" {
  * glx_aggregate_arg, glx_aggregate_backward; weighted aggregation -- glx_aggregate_weighted,
  * glx_aggregate_weighted_backward_x, glx_aggregate_weighted_backward_w; ragged segment softmax -- glx_segment_softmax,
  * glx_segment_softmax_backward; pair scores -- glx_pair_dot, glx_pair_dot_backward; trainable embedding tables --
- * glx_rows_coalesce, glx_embedding_update; fused GAT attention -- glx_gat_attention, glx_gat_attention_backward. */
+ * glx_rows_coalesce, glx_embedding_update; fused GAT attention -- glx_gat_attention, glx_gat_attention_backward; fused
+ * dot-product attention -- glx_dot_attention, glx_dot_attention_backward. */
 #define GLX_ABI_VERSION 5
 
 /* Exported symbols: libglx.so is built with -fvisibility=hidden. */
@@ -544,6 +545,60 @@ GLX_API int glx_gat_attention_backward(int device, const float* soft, const floa
                                        float default_attr, float drop_p, uint64_t seed, uint64_t call,
                                        float* grad_e_out, float* grad_s_out, float* grad_t_out, int ptr_kind,
                                        void* stream);
+
+/* ---- fused dot-product attention: the scaled dot-product ("transformer") attention of a node over its neighbours,
+ * with an edge term added to the key and to the value, and its gradients.  The layer of the reference's GPU PyTorch
+ * model, TransformerConv(in, out // 2, heads=2, dropout=0.1, edge_dim=...) (examples/pytorch/tgn/train_and_eval.py:38-50).
+ * Common to the two entry points:
+ *   q[num_segments * dim]     float32, row-major: the query, one row per segment
+ *   k, v[num_rows * dim]      float32, row-major, dense rows: the key and the value of every node; they may be one
+ *                             pointer; num_rows < 2^31
+ *   rows[num_ids]             int64 rows of k and v; a value outside [0, num_rows) reads a row of default_attr in both
+ *                             tables and receives no gradient
+ *   edge[num_ids * dim]       float32 or NULL: the edge term of every position, added to its key and to its value
+ *   heads >= 1, dim % heads == 0, C = dim / heads: column c belongs to head c / C
+ *   cnt[num_segments]         glx_aggregate_weighted's layout (clamped prefix sums cut at num_ids); NULL: the implied
+ *                             layout of num_ids / num_segments positions per segment, num_ids % num_segments == 0
+ *   scale finite;  0 <= drop_p < 1;  num_ids * heads and num_segments * dim <= INT32_MAX
+ * Arguments are checked before any device use; a device-pointer call only enqueues work (the workspace is the thread's
+ * per-(device, stream) lease).  EVERY element of every output that is asked for is written; a position that is not
+ * consumed gets +0.0f.  No float atomics: one lane group owns each segment, of any length (a hub segment is walked by
+ * its one group), with a fixed mapping and fixed trees -- the same inputs give the same bits on every call.
+ *
+ * glx_dot_attention: for a consumed position p of segment sg, head h and a column c of it
+ *     kk(p)[c] = krow(p)[c], or fadd_rn(krow(p)[c], edge[p, c]) when edge is given; vv(p)[c] the same from v
+ *     dot[p, h] = sum_c q[sg, c] * kk(p)[c]     -- glx_pair_dot's tolerance contract: the order is the mapping's,
+ *                 |dot - exact| <= C * 2^-23 * sum |terms| + 2^-126 against the float64 value of the float32 kk
+ *     e    = fmul_rn(dot, scale)
+ *     soft = glx_segment_softmax of these e: its bound and its exact rules (k == 1 is 1.0f, k equal logits are
+ *            1.0f / (float)k, -inf among finite logits is +0.0f, a NaN or +inf logit or only -inf ones make the column NaN)
+ *     alpha = glx_gat_attention's dropout of soft, word for word: element i = p * heads + h, the same counter, key,
+ *             threshold T and scale 1.0f / (1.0f - drop_p); drop_p == 0: alpha == soft and no Philox is evaluated
+ *     out[sg, c] = +0.0f, then for each consumed p in ascending order fadd_rn(out, fmul_rn(alpha[p, h], vv(p)[c])):
+ *             bit-exact, never contracted.  An empty segment is +0.0f in every column (not default_attr).
+ * logit_out (may be NULL) receives e, soft_out (required) soft; out is [num_segments * dim]. */
+GLX_API int glx_dot_attention(int device, const float* q, const float* k, const float* v, int64_t num_rows, int32_t dim,
+                              int32_t heads, const int64_t* rows, const float* edge, const int32_t* cnt,
+                              int32_t num_ids, int32_t num_segments, float scale, float default_attr, float drop_p,
+                              uint64_t seed, uint64_t call, float* logit_out, float* soft_out, float* out, int ptr_kind,
+                              void* stream);
+/* glx_dot_attention_backward: alpha and the mask are recomputed from soft (the forward's soft_out), seed and call:
+ *     ga_raw[p, h] = sum_c grad_out[sg, c] * vv(p)[c]   -- glx_aggregate_weighted_backward_w's tolerance contract
+ *     ga = keep ? fmul_rn(ga_raw, 1.0f / (1.0f - drop_p)) : +0.0f;  d = soft * (ga - sum_q soft_q * ga_q)
+ *     grad_e = fmul_rn(d, scale)                         -- glx_segment_softmax_backward's bound at |ga| + its error,
+ *                                                           plus the propagated error of ga, times |scale|
+ *     grad_q[sg, c]   = +0.0f, then in ascending p fadd_rn(., fmul_rn(grad_e[p, h], kk(p)[c])): bit-exact from grad_e
+ *     grad_edge[p, c] = fadd_rn(fmul_rn(grad_e[p, h], q[sg, c]), fmul_rn(alpha[p, h], grad_out[sg, c])): bit-exact
+ *     grad_k = the bits of glx_aggregate_weighted_backward_x(Sum, rows, w = grad_e, grad_out = q); grad_v the same
+ *              with w = alpha and grad_out = grad_out; every row is written
+ * grad_e_out is required; grad_q_out, grad_k_out, grad_v_out and grad_edge_out (which needs edge) may each be NULL
+ * (not computed). */
+GLX_API int glx_dot_attention_backward(int device, const float* q, const float* k, const float* v, int64_t num_rows,
+                                       int32_t dim, int32_t heads, const int64_t* rows, const float* edge,
+                                       const int32_t* cnt, int32_t num_ids, int32_t num_segments, float scale,
+                                       float default_attr, float drop_p, uint64_t seed, uint64_t call, const float* soft,
+                                       const float* grad_out, float* grad_e_out, float* grad_q_out, float* grad_k_out,
+                                       float* grad_v_out, float* grad_edge_out, int ptr_kind, void* stream);
 
 /* ---- pair scores: the per-pair, optionally multi-head, dot product of two gathered rows, with its gradients with
  * respect to both tables.  The reference's unsupervised models score an edge as the dot product of its two endpoint
