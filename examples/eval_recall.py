@@ -1,0 +1,92 @@
+"""Retrieval evaluation on the device: recall@k, NDCG@k and hit rate of user-to-item (u2i) and item-to-item (i2i)
+retrieval over an embedding table, the step that follows training a link-prediction / recommendation model
+(examples/train_sage_unsup.py, examples/train_node2vec.py produce such tables).
+
+The embeddings here are synthetic with PLANTED neighbours: items come in groups of `group` siblings around a centre on an
+integer lattice, a user sits next to one centre, and the ground truth of a user (or of an item) is the group.  Every
+coordinate is a small multiple of 1/8, so every score is exact in float32 and in float64 alike: the search's ids can be
+compared with a float64 brute force without a tolerance, ties included (both break them by row).
+
+The search is glx.Features.search on the item table as it lies in device memory (exact, deterministic: one fmaf chain per
+score, ties to the smaller row); the metrics are computed on the device from its ids.  Planted groups are what the L2
+metric retrieves; under the inner product long items win regardless of the group, which the lower numbers show.
+
+Exits non-zero unless two runs give the same bits and the ids equal the float64 brute force.
+Usage: python examples/eval_recall.py [--items 4000] [--users 1000] [--dim 16] [--k 10]"""
+import argparse
+import math
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "graph-learn_amd"))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+import glx  # noqa: E402
+
+
+def planted(rng, num_items, num_users, dim, group):
+    groups = num_items // group
+    centre = rng.integers(-8, 9, (groups, dim)).astype(np.float32)
+    items = np.repeat(centre, group, axis=0)
+    for j in range(group):  # sibling j leaves the centre along axis j by (j + 1) / 4
+        items[j::group, j % dim] += 0.25 * (j + 1)
+    item_ids = (10 ** 6 + 3 * rng.permutation(groups * group)).astype(np.int64)  # node ids, not row numbers
+    user_group = rng.integers(0, groups, num_users)
+    users = centre[user_group] + rng.integers(-1, 2, (num_users, dim)).astype(np.float32) / 8
+    return items, item_ids, users, user_group
+
+
+def brute64(q, x, k, metric):
+    q, x = q.astype(np.float64), x.astype(np.float64)
+    s = -(q @ x.T) if metric == "ip" else (q * q).sum(1)[:, None] + (x * x).sum(1)[None, :] - 2 * (q @ x.T)
+    return np.argsort(s, axis=1, kind="stable")[:, :k]
+
+
+def metrics(ids, truth, k):
+    """ids[n, k], truth[n, t] (device): recall@k, NDCG@k, hit rate"""
+    hit = (ids[:, :, None] == truth[:, None, :]).any(2)
+    disc = 1.0 / torch.log2(torch.arange(k, device=ids.device, dtype=torch.float32) + 2.0)
+    ideal = disc[:min(k, truth.shape[1])].sum()
+    recall = hit.sum(1).float() / min(k, truth.shape[1])
+    ndcg = (hit.float() * disc).sum(1) / ideal
+    return recall.mean().item(), ndcg.mean().item(), hit.any(1).float().mean().item()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--items", type=int, default=4000)
+    ap.add_argument("--users", type=int, default=1000)
+    ap.add_argument("--dim", type=int, default=16)
+    ap.add_argument("--k", type=int, default=10)
+    ap.add_argument("--group", type=int, default=5)
+    a = ap.parse_args()
+    rng = np.random.default_rng(0)
+    items, item_ids, users, user_group = planted(rng, a.items, a.users, a.dim, a.group)
+    table = glx.Features(items, ids=item_ids)
+    d_ids = torch.from_numpy(item_ids).cuda()
+    group_rows = torch.arange(items.shape[0], device="cuda").view(-1, a.group)
+    ok = True
+    for task, q, q_group in (("u2i", users, user_group), ("i2i", items, np.arange(items.shape[0]) // a.group)):
+        dq = torch.from_numpy(q).cuda()
+        truth = d_ids[group_rows[torch.from_numpy(q_group).cuda()]]
+        for metric in ("l2", "ip"):
+            ids, dist = table.search(dq, a.k, metric)
+            ids2, dist2 = table.search(dq, a.k, metric)
+            same_bits = bool(torch.equal(ids, ids2) and torch.equal(dist.view(torch.int32), dist2.view(torch.int32)))
+            want = item_ids[brute64(q, items, a.k, metric)]
+            exact = bool(np.array_equal(ids.cpu().numpy(), want))
+            r, n, h = metrics(ids, truth, a.k)
+            print("%s %s  recall@%d %.4f  ndcg@%d %.4f  hit rate %.4f  two runs same bits: %s  ids == float64 brute force: %s"
+                  % (task, metric, a.k, r, a.k, n, h, same_bits, exact))
+            ok = ok and same_bits and exact and not math.isnan(r)
+    if not ok:
+        print("FAILED")
+        return 1
+    print("OK")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

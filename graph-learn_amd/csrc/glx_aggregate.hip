@@ -1337,6 +1337,8 @@ extern "C" int glx_tune(const char* name, int32_t value) {
     else if (strcmp(name, "filter_span_cap") == 0) side = &sk.filter_span_cap;
     else if (strcmp(name, "filter_dedup_min_rows") == 0) side = &sk.filter_dedup_min_rows;
     else if (strcmp(name, "idmap_hash_only") == 0) side = &sk.idmap_hash_only;
+    else if (strcmp(name, "knn_chunk_rows") == 0) side = &sk.knn_chunk_rows;
+    else if (strcmp(name, "knn_query_block") == 0) side = &sk.knn_query_block;
     else if (strcmp(name, "resolve_ids") == 0) side = &sk.resolve_ids;
     else if (strcmp(name, "resolve_blocks") == 0) side = &sk.resolve_blocks;
     else if (strcmp(name, "resolve_set_share") == 0) side = &sk.resolve_set_share;
@@ -1445,6 +1447,16 @@ int glx_features_create_impl(int device, int64_t num_rows, int32_t dim, const vo
       rc = allow_arithmetic_ids ? glx_idmap_build_auto(d_ids, num_rows, &f->idmap, s) : glx_idmap_build(d_ids, num_rows, &f->idmap, s);
     }
   }
+  if (e == hipSuccess && rc == GLX_OK && f->idmap.keys != nullptr) {
+    // a hash table answers id -> row only: KNN search reports ids, so the rows' ids stay on the device (glx_knn.hip)
+    if (tmp_ids) {
+      f->knn_row_ids = tmp_ids;
+      tmp_ids = nullptr;
+    } else {
+      e = hipMalloc(&f->knn_row_ids, (size_t)num_rows * sizeof(int64_t));
+      if (e == hipSuccess) e = hipMemcpyAsync(f->knn_row_ids, ids, (size_t)num_rows * sizeof(int64_t), hipMemcpyDeviceToDevice, s);
+    }
+  }
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   if (tmp_ids) (void)hipFree(tmp_ids);
   if (e != hipSuccess || rc != GLX_OK) {
@@ -1491,6 +1503,9 @@ extern "C" void glx_features_destroy(glx_features* f) {
   if (!f) return;
   GlxDeviceGuard guard(f->device);
   if (f->X && f->owns_x) (void)hipFree(f->X);
+  if (f->knn_row_ids) (void)hipFree(f->knn_row_ids);
+  if (f->knn_xn) (void)hipFree(f->knn_xn);
+  if (f->knn_xn_ready) (void)hipEventDestroy(static_cast<hipEvent_t>(f->knn_xn_ready));
   glx_idmap_free(&f->idmap);
   delete f;
 }

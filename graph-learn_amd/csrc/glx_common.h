@@ -300,6 +300,8 @@ struct GlxSideKnobs {
   std::atomic<int64_t> resolve_own_first{-1};     // GLX_RESOLVE_OWN_FIRST=1|0: ids this rank owns skip / take the replica lookup (default: skip at world size 1 only)
   std::atomic<int64_t> resolve_peek{-1};          // GLX_RESOLVE_PEEK=0: no plain load of a set slot before the compare-and-swap (A/B)
   std::atomic<int64_t> idmap_hash_only{-1};       // GLX_IDMAP_HASH_ONLY (set = 1): feature tables keep a hash table even for arithmetic ids (A/B)
+  std::atomic<int64_t> knn_chunk_rows{-1};        // GLX_KNN_CHUNK_ROWS=n: table rows per chunk of a KNN search, the first chunk included (default: 8192 to 2^18 by the number of queries, first 2048)
+  std::atomic<int64_t> knn_query_block{-1};       // GLX_KNN_QUERY_BLOCK=n: queries per pass over the table (default: what the candidate workspace budget holds)
 };
 GlxSideKnobs& glx_side_knobs();  // glx_graph.hip
 
@@ -336,6 +338,12 @@ struct glx_features {
   bool owns_x;
   GlxIdMapStorage idmap;
   GlxIdMap map() const { return idmap.view(num_rows); }
+  // KNN search (glx_knn.hip).  knn_row_ids: the id of every row when the id map is a hash table (which answers
+  // id -> row only), else nullptr.  knn_xn: the L2 norm chain of every row, built by the first L2 search under
+  // glx_knn.hip's lock; knn_xn_ready: the hipEvent_t recorded behind that build.
+  int64_t* knn_row_ids;
+  mutable float* knn_xn;
+  mutable void* knn_xn_ready;
 };
 
 inline const char* glx_dtype_name(int dtype) {

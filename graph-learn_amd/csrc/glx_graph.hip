@@ -38,6 +38,8 @@ GlxSideKnobs& glx_side_knobs() {
     if (const char* e = getenv("GLX_FILTER_SPAN_CAP")) k.filter_span_cap = atoll(e);
     if (const char* e = getenv("GLX_FILTER_DEDUP_MIN_ROWS")) k.filter_dedup_min_rows = atoll(e);
     if (getenv("GLX_IDMAP_HASH_ONLY")) k.idmap_hash_only = 1;
+    if (const char* e = getenv("GLX_KNN_CHUNK_ROWS")) k.knn_chunk_rows = atoll(e);
+    if (const char* e = getenv("GLX_KNN_QUERY_BLOCK")) k.knn_query_block = atoll(e);
     if (const char* e = getenv("GLX_RESOLVE_IDS")) k.resolve_ids = atoll(e);
     if (const char* e = getenv("GLX_RESOLVE_BLOCKS")) k.resolve_blocks = atoll(e);
     if (const char* e = getenv("GLX_RESOLVE_SET_SHARE")) k.resolve_set_share = atoll(e);

@@ -45,6 +45,7 @@ EXPORTS = [
     "glx_graph_set_timestamps", "glx_sample_filtered", "glx_sample_full_filtered", "glx_random_walk",
     "glx_features_create", "glx_features_view", "glx_features_destroy", "glx_features_info",
     "glx_features_create_ex", "glx_features_view_ex", "glx_features_dtype",
+    "glx_knn_search", "glx_knn_merge",
     "glx_aggregate", "glx_lookup", "glx_aggregate_arg", "glx_aggregate_backward",
     "glx_aggregate_weighted", "glx_aggregate_weighted_backward_x", "glx_aggregate_weighted_backward_w",
     "glx_segment_softmax", "glx_segment_softmax_backward",
@@ -258,6 +259,8 @@ def lib():
         L.glx_probe_bandwidth.argtypes = [ci, ci, i64, i64, i32, i32, ctypes.POINTER(ctypes.c_double),
                                           ctypes.POINTER(ctypes.c_double), vp]
         L.glx_tune.argtypes = [ctypes.c_char_p, i32]
+        L.glx_knn_search.argtypes = [vp, ci, vp, i32, i32, vp, vp, ci, vp]
+        L.glx_knn_merge.argtypes = [ci, ci, i32, vp, vp, i32, i32, vp, vp, ci, vp]
         L.glx_unique.argtypes = [ci, vp, vp, i32, vp, vp, vp, ci, vp]
         L.glx_columns_create.argtypes = [ci, i64, i32, vp, vp, vp, vp, vp, vp, ci, vp, ctypes.POINTER(vp)]
         L.glx_columns_destroy.argtypes = [vp]
@@ -694,6 +697,64 @@ class Features:
         kind = _kind(pi, po)
         _check(lib().glx_lookup(self._h, pi[0], n, default_attr, po[0], kind, _stream(kind, self.device)))
         return out
+
+
+    def search(self, queries, k, metric="ip", out=None):
+        """Exact k nearest rows of every query (glx_knn_search) -> (ids[n, k] int64, dist[n, k] float32), best first.
+        queries[n, D] float32; metric "ip" (inner product, larger is better) or "l2" (squared distance by expansion,
+        smaller is better).  The score is one ascending fmaf chain over the columns, ties go to the smaller storage
+        row, NaN scores come last, k > num_rows pads with id -1 and dist -inf (ip) / +inf (l2); 1 <= k <= 1024.  ids are
+        node ids (row numbers for a table without an id map).  Numpy in, numpy out; torch CUDA tensors in, torch CUDA
+        tensors out on the current stream, nothing read back.  out=(ids, dist): buffers to write into."""
+        if metric not in KNN_METRICS:
+            raise ValueError("metric must be one of {}, not {!r}".format(sorted(KNN_METRICS), metric))
+        if queries.ndim != 2 or int(queries.shape[1]) != self.dim:
+            raise ValueError("queries must be [n, {}], not {}".format(self.dim, tuple(queries.shape)))
+        n, k = int(queries.shape[0]), int(k)
+        ids, dist = _knn_out(out, queries, n, k)
+        pq, pi, pd = _ptr(queries, None if _is_torch(queries) else np.float32), _ptr(ids), _ptr(dist)
+        kind = _kind(pq, pi, pd)
+        _check(lib().glx_knn_search(self._h, KNN_METRICS[metric], pq[0], n, k, pi[0], pd[0], kind,
+                                    _stream(kind, self.device)))
+        return ids, dist
+
+
+KNN_METRICS = {"l2": 0, "ip": 1}  # GLX_KNN_L2, GLX_KNN_IP
+
+
+def _knn_out(out, like, n, k):
+    if out is not None:
+        ids, dist = out
+        for name, buf, dtype in (("ids", ids, "int64"), ("dist", dist, "float32")):
+            if tuple(buf.shape) != (n, k) or str(buf.dtype).replace("torch.", "") != dtype:
+                raise ValueError("knn: out's {} must be {} of shape {}, not {} of shape {}".format(
+                    name, dtype, (n, k), buf.dtype, tuple(buf.shape)))
+        return ids, dist
+    if _is_torch(like):
+        import torch
+        assert like.dtype == torch.float32, like.dtype
+        return (torch.empty((n, k), dtype=torch.int64, device=like.device),
+                torch.empty((n, k), dtype=torch.float32, device=like.device))
+    return np.empty((n, k), np.int64), np.empty((n, k), np.float32)
+
+
+def knn_merge(ids, dist, metric="ip", out=None, device=0):
+    """The k best of several search results per query (glx_knn_merge): ids / dist [num_parts, n, k] -> ([n, k], [n, k]).
+    Same order as Features.search on dist; ties go to the lower part, then to the earlier position; id -1 entries are
+    absent.  Merging the searches of consecutive row ranges of one table equals the whole-table search bit for bit."""
+    if metric not in KNN_METRICS:
+        raise ValueError("metric must be one of {}, not {!r}".format(sorted(KNN_METRICS), metric))
+    if ids.ndim != 3 or tuple(ids.shape) != tuple(dist.shape):
+        raise ValueError("ids and dist must both be [num_parts, n, k]")
+    parts, n, k = (int(v) for v in ids.shape)
+    oi, od = _knn_out(out, dist, n, k)
+    pi, pd, poi, pod = _ptr(ids, None if _is_torch(ids) else np.int64), _ptr(dist, None if _is_torch(dist) else np.float32), _ptr(oi), _ptr(od)
+    kind = _kind(pi, pd, poi, pod)
+    if kind == PTR_DEVICE:
+        device = od.device.index or 0
+    _check(lib().glx_knn_merge(device, KNN_METRICS[metric], parts, pi[0], pd[0], n, k, poi[0], pod[0], kind,
+                               _stream(kind, device)))
+    return oi, od
 
 
 def aggregate_backward(op, rows, cnt, grad_out, num_rows, arg=None, out=None, device=0):

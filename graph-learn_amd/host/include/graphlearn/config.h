@@ -25,7 +25,7 @@ extern int32_t gShuffleBufferSize;      // config.cc:88 (10240: a "shuffle" trav
 // Flags of the layers around the path.  The DAG runner and the dataset read TapeCapacity / DatasetCapacity /
 // Timeout / ClientId / ClientCount (core/dag/tape.cc:85-93, core/dag/dag_dataset.cc:28-35,63-66); DeployMode is
 // recorded and checked (only kLocal is served in-process); the rest parameterise the reference's RPC service,
-// thread pools, storage layout, KNN, vineyard and actor engine -- none of which exists here -- and are kept so that
+// thread pools, storage layout, vineyard and actor engine -- none of which exists here -- and are kept so that
 // the reference's Python layer can set them (python/c/py_export.cc:38-80): stored, never read.
 extern int32_t gDeployMode;        // config.cc:77  (0 = local)
 extern int32_t gClientId;          // :78
@@ -38,6 +38,7 @@ extern int32_t gTrackerMode;       // :95 (1 = file system)
 // New (the reference has no seed flag, include/config.h:77-118): the seed of the
 // glx seeding contract, and the GPU this process' GraphStore lives on.
 extern int64_t gSamplingSeed;
+extern int32_t gKnnMetric;  // config.cc:107 (0 = L2, 1 = inner product): the metric of the "KnnOperator"
 extern int32_t gDeviceId;
 // New: the storage type of the node feature tables Noder::Build uploads (GLX_DTYPE_*: 0 float32, 1 bfloat16,
 // 2 float16).  Aggregation and lookup still accumulate and answer in float32.
@@ -68,6 +69,7 @@ int32_t GetGlobalFlagTrackerMode();
 void SetGlobalFlagUnused(const char* name, int64_t v);
 void SetGlobalFlagUnused(const char* name, const std::string& v);
 void SetGlobalFlagSamplingSeed(int64_t v);
+void SetGlobalFlagKnnMetric(int32_t v);
 void SetGlobalFlagDeviceId(int32_t v);
 void SetGlobalFlagFeatureDtype(int32_t v);
 

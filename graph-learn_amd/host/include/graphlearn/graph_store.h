@@ -86,7 +86,8 @@ struct NodeColumns {
 
 struct IndexOption {  // include/index_option.h:24-48
   std::string name;  // "sort": Build() orders every adjacency row (timestamp, else weight)
-  // the KNN index parameters: carried, never read (no KNN operator here)
+  // "knn": Noder::Build() marks the node type as searchable by the "KnnOperator".  index_type ("flat", "ivfflat",
+  // "ivfpq", "gpu_*") and its parameters are carried; every type is answered exactly by the same device search.
   std::string index_type;
   int32_t dimension = 0, nlist = 0, nprobe = 0, m = 0;
 };
@@ -223,6 +224,8 @@ public:
   Status AppendColumns(const io::SideInfo& info, io::NodeColumns* columns);
   Status Build(const IndexOption& option);
   const glx_features* Device() const { return dev_; }
+  // Build() with option.name == "knn" has indexed this type (contrib/knn/builder.cc:23-52): the device table is the index
+  bool KnnIndexed() const { return knn_indexed_; }
   int64_t GetNodeCount() const { return (int64_t)ids_.size(); }
   const std::vector<int64_t>& Ids() const { return ids_; }  // NodeStorage::GetIds, insertion order
   const std::vector<float>& Weights() const { return weights_; }  // NodeStorage::GetWeights (weighted types)
@@ -260,6 +263,7 @@ private:
   glx_features* dev_;
   glx_negative* neg_;
   glx_columns* cols_ = nullptr;
+  bool knn_indexed_ = false;
   std::mutex mtx_;
 };
 

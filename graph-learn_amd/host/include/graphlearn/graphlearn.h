@@ -8,6 +8,7 @@
 #include "graphlearn/data_source.h"
 #include "graphlearn/graph_request.h"
 #include "graphlearn/graph_store.h"
+#include "graphlearn/knn_request.h"
 #include "graphlearn/op_request.h"
 #include "graphlearn/operator.h"
 #include "graphlearn/op_runner.h"

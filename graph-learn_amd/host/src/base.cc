@@ -53,6 +53,7 @@ int32_t gTapeCapacity = 10;
 int32_t gDatasetCapacity = 10;
 int32_t gTrackerMode = 1;
 int64_t gSamplingSeed = 0;
+int32_t gKnnMetric = 0;
 int32_t gDeviceId = 0;
 int32_t gFeatureDtype = 0;
 
@@ -76,6 +77,7 @@ void SetGlobalFlagTimeout(int32_t v) { gTimeout = v; }
 void SetGlobalFlagTapeCapacity(int32_t v) { gTapeCapacity = v; }
 void SetGlobalFlagDatasetCapacity(int32_t v) { gDatasetCapacity = v; }
 void SetGlobalFlagTrackerMode(int32_t v) { gTrackerMode = v; }
+void SetGlobalFlagKnnMetric(int32_t v) { gKnnMetric = v; }
 int32_t GetGlobalFlagTrackerMode() { return gTrackerMode; }
 namespace {
 std::mutex g_unused_mtx;

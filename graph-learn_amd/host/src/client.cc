@@ -75,6 +75,10 @@ void Server::Init(const std::vector<io::EdgeSource>& edges, const std::vector<io
     status_ = io::LoadNodes(n, store_);
   }
   if (status_.ok()) status_ = store_->Build(option);
+  // a node source's own option (GraphStore::Build, graph_store.cc:252-271): "knn" indexes that type for the KnnOperator
+  for (const io::NodeSource& n : nodes) {
+    if (status_.ok() && n.option.name == "knn") status_ = store_->GetNoder(n.id_type)->Build(n.option);
+  }
   if (status_.ok()) {
     std::lock_guard<std::mutex> g(g_bound_mtx);
     op::OpFactory::GetInstance()->Set(store_);

@@ -374,8 +374,13 @@ Status Noder::UpdateNodes(const UpdateNodesRequest* req, UpdateNodesResponse*) {
   return Status::OK();
 }
 
-Status Noder::Build(const IndexOption&) {
+Status Noder::Build(const IndexOption& option) {
   std::lock_guard<std::mutex> g(mtx_);
+  if (option.name == "knn") {
+    // BuildKnnIndex (contrib/knn/builder.cc:24-27) refuses a type without float attributes; local_noder.cc:44-50
+    if (info_.f_num < 1) return error::InvalidArgument("Invalid node type or index type.");
+    knn_indexed_ = true;
+  }
   if (dev_) return Status::OK();
   if (info_.f_num <= 0) return Status::OK();  // nothing for the aggregators to read
   // the float32 attributes are rounded to GLOBAL_FLAG(FeatureDtype) on the device, while the rows are placed

@@ -208,7 +208,8 @@ class Graph(object):
   wait_for_close = close
 
   # -- the reference's other deployment entry points: its RPC client / server modes, the vineyard storage backend and the
-  # faiss KNN operator are not part of this engine; they fail by name, not by AttributeError
+  # reference's Graph.search signature are not part of this in-tree layer; they fail by name, not by
+  # AttributeError
   def _not_served(self, what):
     raise NotImplementedError(what + " is not served by this engine: it runs in process, one process per GPU "
                               "(init(task_index=rank, task_count=world_size) for several GPUs)")
@@ -232,7 +233,10 @@ class Graph(object):
     self._not_served("node_view (vineyard backend only in the reference too)")
 
   def search(self, *a, **k):
-    self._not_served("the KNN operator (contrib/knn over faiss)")
+    raise NotImplementedError(
+        "Graph.search(node_type, inputs, KnnOption) is not part of this in-tree layer: the exact KNN search runs on the "
+        "device table as g.device_features(node_type).search(queries, k, metric='ip' | 'l2'); the reference's own "
+        "signature is served by the reference's Python layer on pywrap_graphlearn (new_knn_request ... get_knn_distances)")
 
   # -- introspection ----------------------------------------------------------------
   def get_client(self):

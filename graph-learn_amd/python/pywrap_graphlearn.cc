@@ -4,7 +4,7 @@
 // tree uses is here (tests/test_refpy_names.py greps them), so `graphlearn/__init__.py` +
 // `graphlearn/python/` of the reference run on this module unchanged in local deploy mode:
 // Graph.init(), the samplers, GSL queries (the DAG API + Dataset, see host dag.h).  What the
-// engine does not have -- RPC clients / servers, KNN, vineyard, the actor engine -- exists by
+// engine does not have -- RPC clients / servers, vineyard, the actor engine -- exists by
 // name and fails when CALLED (flag setters of those layers just store their value).
 // New: set_sampling_seed / set_device_id / set_feature_dtype (the glx seeding contract, GPU placement and the
 // storage type of the node feature tables).
@@ -77,6 +77,7 @@ py::object TensorArray(const Tensor& t) {
 
 typedef py::array_t<int64_t, py::array::c_style | py::array::forcecast> I64Array;
 typedef py::array_t<int32_t, py::array::c_style | py::array::forcecast> I32Array;
+typedef py::array_t<float, py::array::c_style | py::array::forcecast> F32Array;
 
 }  // namespace
 
@@ -109,9 +110,10 @@ PYBIND11_MODULE(pywrap_graphlearn, m) {
   m.def("set_timeout", &SetGlobalFlagTimeout);
   m.def("set_tape_capacity", &SetGlobalFlagTapeCapacity);
   m.def("set_dataset_capacity", &SetGlobalFlagDatasetCapacity);
+  m.def("set_knn_metric", &SetGlobalFlagKnnMetric);  // 0 = L2, 1 = inner product (config.cc:107)
   m.def("set_tracker_mode", &SetGlobalFlagTrackerMode);
   m.def("get_tracker_mode", &GetGlobalFlagTrackerMode);
-  // flags of layers this engine does not have (thread pools, queues, storage layout, RPC, KNN, vineyard, actors):
+  // flags of layers this engine does not have (thread pools, queues, storage layout, RPC, vineyard, actors):
   // stored under their name, never read (config.h)
 #define GLX_UNUSED_INT_FLAG(pyname) m.def(pyname, [](int64_t v) { SetGlobalFlagUnused(pyname, v); })
 #define GLX_UNUSED_STR_FLAG(pyname) m.def(pyname, [](const std::string& v) { SetGlobalFlagUnused(pyname, v); })
@@ -123,7 +125,6 @@ PYBIND11_MODULE(pywrap_graphlearn, m) {
   GLX_UNUSED_INT_FLAG("set_storage_mode");
   GLX_UNUSED_INT_FLAG("set_retry_times");
   GLX_UNUSED_INT_FLAG("set_rpc_message_max_size");
-  GLX_UNUSED_INT_FLAG("set_knn_metric");
   GLX_UNUSED_INT_FLAG("set_local_node_cache_capacity");
   GLX_UNUSED_INT_FLAG("set_enable_actor");
   GLX_UNUSED_INT_FLAG("set_actor_local_shard_count");
@@ -348,12 +349,22 @@ PYBIND11_MODULE(pywrap_graphlearn, m) {
               "the in-memory client (local deploy mode) or the RCCL shard communicator (graph-learn_amd/dist.py)");
         },
         py::arg("server_id") = -1, py::arg("client_own") = true);
-  // KNN (python/operator/knn_operator.py): no KNN operator here; present by name, fails when called
-  for (const char* name : {"new_knn_request", "new_knn_response", "set_knn_request", "get_knn_ids", "get_knn_distances"}) {
-    m.def(name, [name](py::args) -> py::object {
-      throw std::runtime_error(std::string(name) + ": the KNN operator (faiss) is not part of this engine");
-    });
-  }
+  // ---- KNN (py_client.cc; python/operator/knn_operator.py:57-63) ----
+  m.def("new_knn_request", [](const std::string& node_type, int32_t k) -> OpRequest* { return new KnnRequest(node_type, k); },
+        py::return_value_policy::reference);
+  m.def("new_knn_response", []() -> OpResponse* { return new KnnResponse(); }, py::return_value_policy::reference);
+  m.def("set_knn_request", [](OpRequest* req, int32_t batch_size, int32_t dimension, F32Array inputs) {
+    if ((int64_t)inputs.size() != (int64_t)batch_size * dimension) throw std::invalid_argument("set_knn_request: inputs do not hold batch_size * dimension floats");
+    As<KnnRequest>(req, "KnnRequest")->Set(inputs.data(), batch_size, dimension);
+  });
+  m.def("get_knn_ids", [](OpResponse* res) {
+    KnnResponse* r = As<KnnResponse>(res, "KnnResponse");
+    return ViewOf<int64_t>(r, kNodeIds, (size_t)r->BatchSize() * (size_t)r->K());
+  });
+  m.def("get_knn_distances", [](OpResponse* res) {
+    KnnResponse* r = As<KnnResponse>(res, "KnnResponse");
+    return ViewOf<float>(r, kDistances, (size_t)r->BatchSize() * (size_t)r->K());
+  });
 
   // ---- GSL: the DAG definition a query is lowered to (py_client.cc:527-627; py_wrapper.h:34-130) ----
   py::class_<DagDef>(m, "DagDef").def(py::init<>());

@@ -43,7 +43,8 @@ extern "C" {
  * glx_aggregate_weighted_backward_x, glx_aggregate_weighted_backward_w; ragged segment softmax -- glx_segment_softmax,
  * glx_segment_softmax_backward; pair scores -- glx_pair_dot, glx_pair_dot_backward; trainable embedding tables --
  * glx_rows_coalesce, glx_embedding_update; fused GAT attention -- glx_gat_attention, glx_gat_attention_backward; fused
- * dot-product attention -- glx_dot_attention, glx_dot_attention_backward. */
+ * dot-product attention -- glx_dot_attention, glx_dot_attention_backward; exact KNN search -- GLX_KNN_*, glx_knn_search,
+ * glx_knn_merge. */
 #define GLX_ABI_VERSION 5
 
 /* Exported symbols: libglx.so is built with -fvisibility=hidden. */
@@ -366,6 +367,45 @@ GLX_API int glx_features_create_ex(int device, int64_t num_rows, int32_t dim, co
 GLX_API int glx_features_view_ex(int device, int64_t num_rows, int32_t dim, const void* X_device, int dtype,
                                  glx_features** out);
 GLX_API int glx_features_dtype(const glx_features* f, int* dtype);
+
+/* ---- exact KNN search: replaces the KnnOperator on the reference's flat index -- FlatKnnIndex::Search
+ * (contrib/knn/flat_index.cc:26-55), KnnRequest / KnnResponse and KnnResponse::Merge (contrib/knn/knn_request.cc:26-50,
+ * 186-202) and the index build (contrib/knn/builder.cc:23-52) -- without faiss: the flat index IS the glx_features table
+ * as it lies in device memory, no second copy.  ivfflat / ivfpq / gpu_* index types are answered exactly by this search.
+ * For a query q (dim float32 values) and a stored row x of a float32, bfloat16 or float16 table:
+ *   upcast   a half element is upcast exactly to float32 first.
+ *   ip       = +0.0f, then ip = fmaf(q[c], x[c], ip) for c = 0 .. dim-1 ascending: ONE chain over all columns, one
+ *            rounding per step (the numerics of v_mfma_f32_32x32x2_f32, of v_mfma_f32_16x16x4_f32 and of a VALU fmaf
+ *            loop alike; no split-K, no second accumulator over the columns).
+ *   GLX_KNN_IP  dist = ip; larger is better.
+ *   GLX_KNN_L2  qn, xn: the same chain of the vector with itself; d = fmaf(-2.0f, ip, fadd_rn(qn, xn));
+ *            dist = d < 0 ? +0.0f : d (a NaN stays a NaN): the squared distance by expansion, as faiss's flat index
+ *            computes it for batches; smaller is better.  xn is computed once per table, on the first L2 search
+ *            (stream-ordered, guarded for concurrent callers), and kept with the glx_features object.
+ *   order    a better dist first; equal dist (float equality, +0.0f == -0.0f): the smaller storage row (insertion order)
+ *            first; a NaN dist is worse than every number, NaNs among themselves by row.  Which NaN a NaN dist is, is
+ *            the hardware's.
+ *   output   row i of ids_out / dist_out ([num_queries, k]) holds the k best rows under that order, best first; ids_out
+ *            holds node ids -- the id the row was created with (ids_[row], flat_index.cc:52-54), the row number for a
+ *            table without an id map.  With k > num_rows the remaining slots are id = -1, dist = -inf (IP) / +inf (L2):
+ *            faiss's padding, without the reference's ids_[-1] read.
+ * Every element of both outputs is written; the same inputs give the same bits on every call; no float atomics; the
+ * table's stride and swizzle are honoured.  Limits (else GLX_INVALID_ARGUMENT): 1 <= k <= 1024; num_queries >= 0 (0 is
+ * a no-op success); num_rows < 2^31; num_queries * k < 2^31; one GPU; not under graph capture.
+ * glx_tune: "knn_chunk_rows" (GLX_KNN_CHUNK_ROWS: table rows per chunk), "knn_query_block" (GLX_KNN_QUERY_BLOCK: queries
+ * per pass over the table); results are bit-identical under every setting.
+ * glx_knn_merge is KnnResponse::Merge: ids / dist are [num_parts, num_queries, k]; the output is the k best of the
+ * num_parts * k entries of each query under the same order on dist, ties to the lower part, then to the earlier
+ * position in the part; id = -1 entries are worst (absent).  Merging the searches of consecutive row ranges of one
+ * table reproduces the whole-table search bit for bit (the reference's heap leaves the tie order to chance).
+ * num_parts >= 1, num_parts * k < 2^31. */
+#define GLX_KNN_L2 0 /* the reference's KnnMetric values: contrib/knn/config.h:21-23 with flat_index.cc:27-28 */
+#define GLX_KNN_IP 1
+GLX_API int glx_knn_search(const glx_features* f, int metric, const float* queries, int32_t num_queries, int32_t k,
+                           int64_t* ids_out, float* dist_out, int ptr_kind, void* stream);
+GLX_API int glx_knn_merge(int device, int metric, int32_t num_parts, const int64_t* ids, const float* dist,
+                          int32_t num_queries, int32_t k, int64_t* ids_out, float* dist_out, int ptr_kind,
+                          void* stream);
 
 /* ---- aggregation: replaces Aggregator::Aggregate (aggregator.cc:25-59) with
  * Sum/Mean/Max/Min/Prod Init/Agg/Final (sum_aggregator.cc:25-33,
@@ -1201,7 +1241,8 @@ GLX_API int glx_probe_bandwidth(int device, int kind, int64_t bytes, int64_t uni
  * (GLX_RESOLVE_IDS: ids per thread per pass), "resolve_blocks" (GLX_RESOLVE_BLOCKS: workgroups), "resolve_set_share"
  * (GLX_RESOLVE_SET_SHARE: the halo id set holds at least n / 1024 of a request's ids), "resolve_peek" (GLX_RESOLVE_PEEK = 0:
  * no plain load of a set slot before the compare-and-swap), "resolve_own_first" (GLX_RESOLVE_OWN_FIRST = 1 | 0: ids this
- * rank owns skip / take the replica lookup; default: skip at world size 1 only).  Test aid: "seg_epochs_before_wrap" (the
+ * rank owns skip / take the replica lookup; default: skip at world size 1 only); of the KNN search: "knn_chunk_rows",
+ * "knn_query_block" (see glx_knn_search).  Test aid: "seg_epochs_before_wrap" (the
  * calling thread's segment-word buffers hand out `value` more epochs before their counter wraps). */
 GLX_API int glx_tune(const char* name, int32_t value);
 
