@@ -339,8 +339,9 @@ struct glx_features {
   GlxIdMapStorage idmap;
   GlxIdMap map() const { return idmap.view(num_rows); }
   // KNN search (glx_knn.hip).  knn_row_ids: the id of every row when the id map is a hash table (which answers
-  // id -> row only), else nullptr.  knn_xn: the L2 norm chain of every row, built by the first L2 search under
-  // glx_knn.hip's lock; knn_xn_ready: the hipEvent_t recorded behind that build.
+  // id -> row only), else nullptr.  knn_xn: the L2 norm chain of every row, built once per owned table by the first L2
+  // search under glx_knn.hip's lock; knn_xn_ready: the hipEvent_t recorded behind that build.  A view (owns_x == false)
+  // leaves both null: its rows are the caller's to rewrite, so its norms are built per search in the call's workspace.
   int64_t* knn_row_ids;
   mutable float* knn_xn;
   mutable void* knn_xn_ready;

@@ -72,7 +72,8 @@ struct KnnTable {
   int dtype;
 };
 
-// out[r] = the chain of row r with itself; one lane per row (built once per table / once per request's queries)
+// out[r] = the chain of row r with itself; one lane per row (built once per owned table; per search for a view and for
+// the request's queries)
 __global__ __launch_bounds__(256) void knn_norms_kernel(KnnTable t, float* __restrict__ out) {
   const int64_t r = blockIdx.x * (int64_t)256 + threadIdx.x;
   if (r >= t.num_rows) return;
@@ -349,8 +350,10 @@ int knn_pow2_at_least(int32_t k) {
 
 std::mutex g_norm_mu;
 
-// xn of the table: built once, on the first L2 search, on that search's stream; later searches on other streams wait
-// for the build's event.  Concurrent first searches are serialised by the lock around the queueing (not the work).
+// xn of an OWNED table (nothing in the C ABI rewrites its rows): built once, on the first L2 search, on that search's
+// stream; later searches on other streams wait for the build's event.  Concurrent first searches are serialised by the
+// lock around the queueing (not the work).  A view reads the caller's matrix as it is at each call -- a halo buffer, an
+// embedding table under glx_embedding_update -- so its xn is built per search into the call's workspace instead.
 int knn_table_norms(const glx_features* f, const KnnTable& t, hipStream_t s, const float** xn) {
   std::lock_guard<std::mutex> lk(g_norm_mu);
   if (f->knn_xn == nullptr) {
@@ -415,8 +418,10 @@ int knn_search_device(const glx_features* f, int metric, const float* d_q, int32
   const int64_t first = knob_chunk > 0 ? chunk : (chunk < kDefaultFirstChunkRows ? chunk : kDefaultFirstChunkRows);
   a.cap = (int32_t)chunk;
 
-  // workspace: qn[num_queries] | thr[qb] | cnt[qb] | run[qb, KP] | cand[qb, cap]
-  const size_t off_thr = knn_align((size_t)num_queries * sizeof(float));
+  // workspace: qn[num_queries] | xn[num_rows] (L2 on a view) | thr[qb] | cnt[qb] | run[qb, KP] | cand[qb, cap]
+  const bool view_norms = metric == GLX_KNN_L2 && !f->owns_x;
+  const size_t off_xn = knn_align((size_t)num_queries * sizeof(float));
+  const size_t off_thr = off_xn + (view_norms ? knn_align((size_t)a.t.num_rows * sizeof(float)) : 0);
   const size_t off_cnt = off_thr + knn_align((size_t)qb * sizeof(uint32_t));
   const size_t off_run = off_cnt + knn_align((size_t)qb * sizeof(uint32_t));
   const size_t off_cand = off_run + knn_align((size_t)qb * a.KP * sizeof(uint64_t));
@@ -431,8 +436,14 @@ int knn_search_device(const glx_features* f, int metric, const float* d_q, int32
   a.run = reinterpret_cast<uint64_t*>(base + off_run);
   a.cand = reinterpret_cast<uint64_t*>(base + off_cand);
   if (metric == GLX_KNN_L2) {
-    rc = knn_table_norms(f, a.t, s, &a.xn);
-    if (rc != GLX_OK) return rc;
+    if (view_norms) {
+      float* const xn = reinterpret_cast<float*>(base + off_xn);
+      if (a.t.num_rows > 0) knn_norms_kernel<<<(unsigned)((a.t.num_rows + 255) / 256), 256, 0, s>>>(a.t, xn);
+      a.xn = xn;
+    } else {
+      rc = knn_table_norms(f, a.t, s, &a.xn);
+      if (rc != GLX_OK) return rc;
+    }
     const KnnTable qt{d_q, f->dim, 0, num_queries, f->dim, GLX_DTYPE_F32};
     knn_norms_kernel<<<(unsigned)((num_queries + 255) / 256), 256, 0, s>>>(qt, qn);
   }

@@ -380,8 +380,9 @@ GLX_API int glx_features_dtype(const glx_features* f, int* dtype);
  *   GLX_KNN_IP  dist = ip; larger is better.
  *   GLX_KNN_L2  qn, xn: the same chain of the vector with itself; d = fmaf(-2.0f, ip, fadd_rn(qn, xn));
  *            dist = d < 0 ? +0.0f : d (a NaN stays a NaN): the squared distance by expansion, as faiss's flat index
- *            computes it for batches; smaller is better.  xn is computed once per table, on the first L2 search
- *            (stream-ordered, guarded for concurrent callers), and kept with the glx_features object.
+ *            computes it for batches; smaller is better.  xn is computed once per owned table, on the first L2
+ *            search (stream-ordered, guarded for concurrent callers), and kept with the glx_features object; per
+ *            search for a view (glx_features_view*), whose rows are the caller's to rewrite between calls.
  *   order    a better dist first; equal dist (float equality, +0.0f == -0.0f): the smaller storage row (insertion order)
  *            first; a NaN dist is worse than every number, NaNs among themselves by row.  Which NaN a NaN dist is, is
  *            the hardware's.
