@@ -168,6 +168,95 @@ __device__ __forceinline__ int64_t glx_row_of(const GlxIdMap& m, int64_t id) {
   }
 }
 
+// --------------------------------------------------------- row directory ---
+// id -> (start, deg) of a graph's row in ONE aligned load, laid out once when the graph is built (glx_graph_finalize):
+// the samplers' preludes otherwise walk keys[h] -> vals[h] -> row_ptr[row], row_ptr[row + 1], four dependent random
+// accesses into three tables of which only `start` and `deg` come out.  Two forms; glx_row_dir_form_rule picks one.
+//   direct    GlxRowDirEntry at index id, ids in [0, max_id]; an id that is no row holds start = GLX_ROW_DIR_ABSENT.
+//   hashed16  GlxRowDirSlot at the slot the id has in the graph's GlxIdMap (same glx_mix64, capacity and linear
+//             probing; key = GLX_EMPTY_KEY marks a free slot): one dwordx4 load answers key match, start and degree.
+// A known row of degree 0 is an entry like any other (start < GLX_ROW_DIR_ABSENT, deg = 0): "known" and "empty" stay
+// apart.  Graphs with 2^32 - 1 edges or more keep no directory (start and degree are 32-bit, the sentinel stays free).
+enum { GLX_ROW_DIR_NONE = 0, GLX_ROW_DIR_DIRECT = 1, GLX_ROW_DIR_HASHED16 = 2 };
+#define GLX_ROW_DIR_ABSENT 0xffffffffu
+struct GlxRowDirEntry {
+  uint32_t start, deg;
+};
+struct alignas(16) GlxRowDirSlot {
+  int64_t key;
+  uint32_t start, deg;
+};
+static_assert(sizeof(GlxRowDirEntry) == 8 && sizeof(GlxRowDirSlot) == 16, "one 8-byte / one 16-byte load per lookup");
+
+struct GlxRowDir {
+  const void* table;  // nullptr: the graph keeps none (glx_row_of + row_ptr answer)
+  uint64_t mask;      // hashed16: capacity - 1
+  int64_t max_id;     // direct: the last index
+  int32_t form;       // GLX_ROW_DIR_*
+};
+
+// Which form a graph keeps.  env is the value of GLX_ROW_DIR at the build (nullptr = unset, which is kRowDirDefaultOn):
+// "0" builds none, "hash" forces hashed16, anything else takes the direct form when the smallest row id is >= 0 and its
+// (max_id + 1) * 8 bytes are no more than the cap * 16 of the hashed one (cap: the capacity of the graph's GlxIdMap),
+// else hashed16.
+constexpr bool kRowDirDefaultOn = true;
+inline int glx_row_dir_form_rule(int64_t num_rows, int64_t num_edges, int64_t min_id, int64_t max_id, uint64_t cap,
+                                 const char* env) {
+  if (num_rows <= 0 || cap == 0 || (env ? env[0] == '0' : !kRowDirDefaultOn)) return GLX_ROW_DIR_NONE;
+  if (num_edges >= (int64_t)0xffffffffll) return GLX_ROW_DIR_NONE;
+  const bool force_hash = env && strcmp(env, "hash") == 0;
+  if (!force_hash && min_id >= 0 && (uint64_t)max_id < cap * 2u) return GLX_ROW_DIR_DIRECT;
+  return GLX_ROW_DIR_HASHED16;
+}
+
+// (known, start, deg) of raw id `id`: from the directory when the graph keeps one, else from the id map and row_ptr.
+// An unknown id answers known = false, start = deg = 0.  The entry is loaded as ONE 8-byte / 16-byte vector: a struct
+// copy is split by the compiler into loads that wait for each other.
+struct GlxRowSpan {
+  int64_t start, deg;
+  bool known;
+};
+__device__ __forceinline__ GlxRowSpan glx_row_span(const GlxRowDir& d, const GlxIdMap& m,
+                                                   const int64_t* __restrict__ row_ptr, int64_t id) {
+  typedef uint32_t GlxU32x2 __attribute__((ext_vector_type(2)));
+  typedef uint32_t GlxU32x4 __attribute__((ext_vector_type(4)));
+  GlxRowSpan r = GlxRowSpan{0, 0, false};
+  if (d.table == nullptr) {
+    const int64_t row = glx_row_of(m, id);
+    if (row >= 0) {
+      r.start = row_ptr[row];
+      r.deg = row_ptr[row + 1] - r.start;
+      r.known = true;
+    }
+    return r;
+  }
+  if (d.form == GLX_ROW_DIR_DIRECT) {
+    if (id < 0 || id > d.max_id) return r;
+    const GlxU32x2 e = *reinterpret_cast<const GlxU32x2*>(static_cast<const GlxRowDirEntry*>(d.table) + id);
+    if (e.x != GLX_ROW_DIR_ABSENT) {
+      r.start = (int64_t)e.x;
+      r.deg = (int64_t)e.y;
+      r.known = true;
+    }
+    return r;
+  }
+  if (id == GLX_EMPTY_KEY) return r;
+  const GlxRowDirSlot* slots = static_cast<const GlxRowDirSlot*>(d.table);
+  uint64_t h = glx_mix64((uint64_t)id) & d.mask;
+  while (true) {
+    const GlxU32x4 e = *reinterpret_cast<const GlxU32x4*>(slots + h);
+    const int64_t k = (int64_t)(((uint64_t)e.y << 32) | e.x);
+    if (k == id) {
+      r.start = (int64_t)e.z;
+      r.deg = (int64_t)e.w;
+      r.known = true;
+      return r;
+    }
+    if (k == GLX_EMPTY_KEY) return r;
+    h = (h + 1) & d.mask;
+  }
+}
+
 struct GlxIdMapStorage {
   int64_t* keys = nullptr;
   int32_t* vals = nullptr;
@@ -324,6 +413,10 @@ struct glx_graph {
   int64_t* ts;            // [E] GetEdgeTimestamp of every slot (timestamp filters), or nullptr
   GlxIdMapStorage idmap;
   GlxIdMap map() const { return idmap.view(num_rows); }
+  void* row_dir;          // the row directory (GlxRowDirEntry[max_id + 1] or GlxRowDirSlot[idmap.cap]), or nullptr
+  int64_t row_dir_max_id;
+  int32_t row_dir_form;   // GLX_ROW_DIR_*
+  GlxRowDir dir() const { return GlxRowDir{row_dir, idmap.cap - 1, row_dir_max_id, row_dir_form}; }
 };
 
 struct glx_features {

@@ -806,6 +806,7 @@ void glx_graph_free(glx_graph* g) {
   if (g->ew20) (void)hipFree(g->ew20);
   if (g->ts) (void)hipFree(g->ts);
   glx_idmap_free(&g->idmap);
+  if (g->row_dir) (void)hipFree(g->row_dir);
   delete g;
 }
 
@@ -912,6 +913,69 @@ static int glx_graph_build_alias(glx_graph* g, hipStream_t s) {
   return GLX_OK;
 }
 
+// mm[0] = the smallest key of a hashed id map, mm[1] = the largest (mm starts at {INT64_MAX, INT64_MIN})
+__global__ void glx_row_dir_minmax_kernel(const int64_t* __restrict__ keys, uint64_t cap, long long* mm) {
+  long long lo = INT64_MAX, hi = INT64_MIN;
+  for (uint64_t h = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; h < cap; h += (uint64_t)gridDim.x * blockDim.x) {
+    const int64_t k = keys[h];
+    if (k == GLX_EMPTY_KEY) continue;
+    lo = k < lo ? k : lo;
+    hi = k > hi ? k : hi;
+  }
+  if (lo <= hi) {
+    atomicMin(&mm[0], lo);
+    atomicMax(&mm[1], hi);
+  }
+}
+
+// Both forms are filled from the id map's own slots, so a lookup answers exactly what glx_row_of + row_ptr answer
+// (duplicate ids included: the map kept the smallest row).  direct: `dir` was filled with 0xff bytes (every entry absent).
+__global__ void glx_row_dir_fill_kernel(const int64_t* __restrict__ keys, const int32_t* __restrict__ vals, uint64_t cap,
+                                        const int64_t* __restrict__ row_ptr, int form, void* __restrict__ dir) {
+  for (uint64_t h = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; h < cap; h += (uint64_t)gridDim.x * blockDim.x) {
+    const int64_t k = keys[h];
+    uint32_t start = 0, deg = 0;
+    if (k != GLX_EMPTY_KEY) {
+      const int64_t row = vals[h];
+      const int64_t b = row_ptr[row];
+      start = (uint32_t)b;
+      deg = (uint32_t)(row_ptr[row + 1] - b);
+    }
+    if (form == GLX_ROW_DIR_HASHED16) {
+      static_cast<GlxRowDirSlot*>(dir)[h] = GlxRowDirSlot{k, start, deg};
+    } else if (k != GLX_EMPTY_KEY) {
+      static_cast<GlxRowDirEntry*>(dir)[k] = GlxRowDirEntry{start, deg};
+    }
+  }
+}
+
+// The row directory of a graph whose row_ptr and hashed id map are final (glx_common.h, GlxRowDir).  GLX_ROW_DIR is
+// read once per build, like GLX_EW_PACKED.
+static int glx_graph_build_row_dir(glx_graph* g, hipStream_t s) {
+  const int64_t V = g->num_rows;
+  const uint64_t cap = g->idmap.cap;
+  if (g->idmap.keys == nullptr || V <= 0) return GLX_OK;
+  const char* env = getenv("GLX_ROW_DIR");
+  if (glx_row_dir_form_rule(V, g->num_edges, 0, 0, cap, env) == GLX_ROW_DIR_NONE) return GLX_OK;
+  GlxTemp mm;
+  GLX_HIP(hipMalloc(&mm.p, 2 * sizeof(long long)));
+  long long h_mm[2] = {INT64_MAX, INT64_MIN};
+  GLX_HIP(hipMemcpyAsync(mm.p, h_mm, sizeof(h_mm), hipMemcpyHostToDevice, s));
+  glx_row_dir_minmax_kernel<<<grid_for((int64_t)cap, 1024), 256, 0, s>>>(g->idmap.keys, cap, mm.as<long long>());
+  GLX_HIP(hipMemcpyAsync(h_mm, mm.p, sizeof(h_mm), hipMemcpyDeviceToHost, s));
+  GLX_HIP(hipStreamSynchronize(s));
+  if (h_mm[0] > h_mm[1]) return GLX_OK;  // no key at all (every id was the reserved GLX_EMPTY_KEY)
+  const int form = glx_row_dir_form_rule(V, g->num_edges, h_mm[0], h_mm[1], cap, env);
+  const size_t bytes = form == GLX_ROW_DIR_DIRECT ? ((size_t)h_mm[1] + 1) * sizeof(GlxRowDirEntry) : (size_t)cap * sizeof(GlxRowDirSlot);
+  GLX_HIP(hipMalloc(&g->row_dir, bytes));
+  if (form == GLX_ROW_DIR_DIRECT) GLX_HIP(hipMemsetAsync(g->row_dir, 0xff, bytes, s));
+  glx_row_dir_fill_kernel<<<grid_for((int64_t)cap), 256, 0, s>>>(g->idmap.keys, g->idmap.vals, cap, g->row_ptr, form, g->row_dir);
+  GLX_HIP(hipGetLastError());
+  g->row_dir_form = form;
+  g->row_dir_max_id = form == GLX_ROW_DIR_DIRECT ? h_mm[1] : 0;
+  return GLX_OK;
+}
+
 int glx_graph_finalize(glx_graph* g, const int64_t* d_ids, hipStream_t s) {
   const int64_t V = g->num_rows;
   if (g->weight) {
@@ -920,6 +984,8 @@ int glx_graph_finalize(glx_graph* g, const int64_t* d_ids, hipStream_t s) {
   }
   if (d_ids) {
     int rc = glx_idmap_build(d_ids, V, &g->idmap, s);
+    if (rc != GLX_OK) return rc;
+    rc = glx_graph_build_row_dir(g, s);
     if (rc != GLX_OK) return rc;
   }
   GLX_HIP(hipStreamSynchronize(s));
@@ -1001,6 +1067,17 @@ extern "C" int glx_graph_edge_weight_packed(const glx_graph* g, int* packed) {
 extern "C" int glx_graph_edge_weight_record_bytes(const glx_graph* g, int* bytes) {
   GLX_REQUIRE(g != nullptr && bytes != nullptr, "NULL argument");
   *bytes = g->ew20 ? 20 : g->ew ? 32 : 0;
+  return GLX_OK;
+}
+
+extern "C" int glx_graph_row_dir(const glx_graph* g, int* form, int64_t* bytes) {
+  GLX_REQUIRE(g != nullptr && form != nullptr, "NULL argument");
+  *form = g->row_dir ? g->row_dir_form : GLX_ROW_DIR_NONE;
+  if (bytes) {
+    *bytes = !g->row_dir ? 0
+             : g->row_dir_form == GLX_ROW_DIR_DIRECT ? (g->row_dir_max_id + 1) * (int64_t)sizeof(GlxRowDirEntry)
+                                                      : (int64_t)g->idmap.cap * (int64_t)sizeof(GlxRowDirSlot);
+  }
   return GLX_OK;
 }
 

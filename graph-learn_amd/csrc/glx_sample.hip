@@ -9,12 +9,19 @@
 // has batch*k of them, >> 256 CUs x 32 waves), every draw costs exactly one
 // 16-byte {nbr, eid} gather (+ one 8-byte alias gather for EdgeWeight), and the
 // [batch, k] outputs are written fully coalesced.
+//
+// Every kernel starts by turning its request row's raw id into (known, start, deg) with glx_row_span (glx_common.h):
+// ONE 8-byte load of the graph's direct row directory, or one 16-byte load per probe of the hashed one, where the id
+// map and row_ptr took keys[h] -> vals[h] -> row_ptr[row], row_ptr[row + 1].  Graphs that keep no directory (dense
+// ids, E >= 2^32 - 1, GLX_ROW_DIR=0 at the build) take that chain through the same helper.  An unknown id answers
+// start = deg = 0; a known row of degree 0 stays known (the `prefix` override applies to known rows only).
 #include "glx_common.h"
 
 namespace {
 
 struct SampleArgs {
   GlxIdMap map;
+  GlxRowDir dir;  // the graph's row directory (table == nullptr: none, map + row_ptr answer)
   const int64_t* row_ptr;
   const GlxAdj* adj;
   const GlxAlias* alias;
@@ -56,13 +63,10 @@ __global__ __launch_bounds__(256) void glx_sample_slots_kernel(SampleArgs a, int
   if (t >= total) return;
   const int32_t i = (int32_t)(t / kpairs);
   const int32_t q = (int32_t)(t - (int64_t)i * kpairs);
-  const int64_t row = glx_row_of(a.map, a.src[i]);
-  int64_t start = 0, deg = 0;
-  if (row >= 0) {
-    start = a.row_ptr[row];
-    deg = a.row_ptr[row + 1] - start;
-  }
-  if (a.prefix && row >= 0) deg = a.prefix[i];
+  const GlxRowSpan span = glx_row_span(a.dir, a.map, a.row_ptr, a.src[i]);
+  const int64_t start = span.start;
+  int64_t deg = span.deg;
+  if (a.prefix && span.known) deg = a.prefix[i];
   const int64_t obase = (a.out_rows ? a.out_rows[i] : (int64_t)i) * a.k;
   GlxPhilox blk;
   if (OP == kSlotRandom || OP == kSlotEdgeWeight || OP == kSlotEdgeWeightPacked || OP == kSlotEdgeWeightCompact) {
@@ -161,11 +165,9 @@ __global__ __launch_bounds__(256) void glx_rwor_kernel(SampleArgs a) {
   const bool active = i < a.batch;
   int64_t start = 0, deg = 0;
   if (active) {
-    const int64_t row = glx_row_of(a.map, a.src[i]);
-    if (row >= 0) {
-      start = a.row_ptr[row];
-      deg = a.row_ptr[row + 1] - start;
-    }
+    const GlxRowSpan span = glx_row_span(a.dir, a.map, a.row_ptr, a.src[i]);
+    start = span.start;
+    deg = span.deg;
   }
   if (a.prefix && active) deg = deg > 0 ? a.prefix[i] : 0;
   const int32_t m = (int32_t)(deg < a.k ? deg : a.k);
@@ -224,11 +226,9 @@ __global__ __launch_bounds__(256) void glx_rwor_small_kernel(SampleArgs a) {
   const bool active = grp < kRowsPerWave && i < a.batch;
   int64_t start = 0, deg = 0;
   if (active) {
-    const int64_t row = glx_row_of(a.map, a.src[i]);
-    if (row >= 0) {
-      start = a.row_ptr[row];
-      deg = a.row_ptr[row + 1] - start;
-    }
+    const GlxRowSpan span = glx_row_span(a.dir, a.map, a.row_ptr, a.src[i]);
+    start = span.start;
+    deg = span.deg;
   }
   if (a.prefix && active) deg = deg > 0 ? a.prefix[i] : 0;
   const int32_t m = (int32_t)(deg < a.k ? deg : a.k);
@@ -286,12 +286,9 @@ __global__ __launch_bounds__(64) void glx_rwor_lds_kernel(SampleArgs a) {
   int32_t* w = lds + k;
   int32_t* perm = lds + 2 * k;
   const int64_t i = blockIdx.x;
-  const int64_t row = glx_row_of(a.map, a.src[i]);
-  int64_t start = 0, deg = 0;
-  if (row >= 0) {
-    start = a.row_ptr[row];
-    deg = a.row_ptr[row + 1] - start;
-  }
+  const GlxRowSpan span = glx_row_span(a.dir, a.map, a.row_ptr, a.src[i]);
+  const int64_t start = span.start;
+  int64_t deg = span.deg;
   if (a.prefix) deg = deg > 0 ? a.prefix[i] : 0;
   const int32_t m = (int32_t)(deg < k ? deg : k);
   const uint32_t rr = a.rng_rows ? (uint32_t)a.rng_rows[i] : (uint32_t)i;
@@ -448,6 +445,7 @@ int glx_sample_prefix_device(const glx_graph* g, int sampler, const int64_t* d_s
                              int64_t* d_eid, hipStream_t s) {
   SampleArgs a;
   a.map = g->map();
+  a.dir = g->dir();
   a.row_ptr = g->row_ptr;
   a.adj = g->adj;
   a.alias = nullptr;
@@ -477,6 +475,7 @@ int glx_sample_scatter_device(const glx_graph* g, int sampler, const int64_t* d_
   if (batch == 0 || k == 0) return GLX_OK;
   SampleArgs a;
   a.map = g->map();
+  a.dir = g->dir();
   a.row_ptr = g->row_ptr;
   a.adj = g->adj;
   a.alias = g->alias;
@@ -516,6 +515,7 @@ extern "C" int glx_sample_ex(const glx_graph* g, int sampler, const int64_t* src
 
   SampleArgs a;
   a.map = g->map();
+  a.dir = g->dir();
   a.row_ptr = g->row_ptr;
   a.adj = g->adj;
   a.alias = g->alias;

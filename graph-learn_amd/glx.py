@@ -39,7 +39,7 @@ AGGREGATOR_IDS = {
 EXPORTS = [
     "glx_abi_version", "glx_device_count", "glx_last_error", "glx_host_register", "glx_host_unregister",
     "glx_graph_create", "glx_graph_build", "glx_graph_build_ordered", "glx_graph_destroy", "glx_graph_info", "glx_graph_export_alias",
-    "glx_graph_edge_weight_packed", "glx_graph_edge_weight_record_bytes",
+    "glx_graph_edge_weight_packed", "glx_graph_edge_weight_record_bytes", "glx_graph_row_dir",
     "glx_graph_degrees", "glx_graph_in_degrees", "glx_sample", "glx_sample_ex", "glx_sample_hops",
     "glx_graph_enable_in_degree", "glx_graph_enable_default_weight", "glx_sample_full_sizes", "glx_sample_full",
     "glx_graph_set_timestamps", "glx_sample_filtered", "glx_sample_full_filtered", "glx_random_walk",
@@ -143,6 +143,7 @@ def lib():
                                      ctypes.POINTER(ci), ctypes.POINTER(ci)]
         L.glx_graph_edge_weight_packed.argtypes = [vp, ctypes.POINTER(ci)]
         L.glx_graph_edge_weight_record_bytes.argtypes = [vp, ctypes.POINTER(ci)]
+        L.glx_graph_row_dir.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_int64)]
         L.glx_graph_export_alias.argtypes = [vp, vp, vp, ci, vp]
         L.glx_graph_build_ordered.argtypes = [ci, i64, vp, vp, vp, vp, vp, ci, ci, vp, ctypes.POINTER(vp)]
         L.glx_graph_degrees.argtypes = [vp, vp, i64, vp, ci, vp]
@@ -500,6 +501,13 @@ class Graph:
         p = ctypes.c_int(0)
         _check(lib().glx_graph_edge_weight_record_bytes(self._h, ctypes.byref(p)))
         return int(p.value)
+
+    def row_dir(self):
+        """-> (form, bytes) of the row directory the samplers look ids up in: form "direct" (8 bytes per id in
+        [0, max_id]), "hashed16" (16 bytes per slot of the id map) or None (the id map and row_ptr answer)."""
+        f, b = ctypes.c_int(0), ctypes.c_int64(0)
+        _check(lib().glx_graph_row_dir(self._h, ctypes.byref(f), ctypes.byref(b)))
+        return (None, "direct", "hashed16")[f.value], int(b.value)
 
     def export_alias(self):
         prob = np.empty(self.num_edges, np.float32)

@@ -177,6 +177,17 @@ GLX_API int glx_graph_edge_weight_packed(const glx_graph* g, int* packed);
  * GLX_EW_PACKED at the build: "0" keeps none, "32" keeps the 32-byte records where the rule would keep either,
  * anything else (or unset) is the rule above.  The answers are the same bit for bit under all three. */
 GLX_API int glx_graph_edge_weight_record_bytes(const glx_graph* g, int* bytes);
+/* *form = the row directory the graph keeps for its samplers, *bytes (optional) = its size.  A graph whose rows are
+ * named by raw ids (every glx_graph_build graph, and glx_graph_create with ids) answers "id -> (first slot, degree)"
+ * from one table laid out when it is built, in one aligned load per request row:
+ *   1 (direct)   -- {uint32 start, uint32 deg} at index id for ids in [0, max_id], start = UINT32_MAX where the id is no
+ *                   row: the smallest id is >= 0 and (max_id + 1) * 8 bytes are no more than the hashed form's;
+ *   2 (hashed16) -- {int64 key, uint32 start, uint32 deg} in the slots of the id map (2 * num_rows rounded up to a power
+ *                   of two, at least 64; 16 bytes each), INT64_MIN marking a free slot;
+ *   0 (none)     -- dense ids (no id map), no rows, or num_edges >= 2^32 - 1: the id map and row_ptr answer.
+ * GLX_ROW_DIR at the build: "0" keeps none, "hash" keeps the hashed form where the rule would keep either, anything else
+ * (or unset) is the rule above.  The answers are the same bit for bit under all three. */
+GLX_API int glx_graph_row_dir(const glx_graph* g, int* form, int64_t* bytes);
 /* EdgeWeightSampler on an UNWEIGHTED edge type: the reference reads GLOBAL_FLAG(DefaultWeight) for every edge
  * (MemoryEdgeStorage::GetWeight, memory_edge_storage.cc:97-103: an id beyond the empty weight array) and builds its
  * alias row from that (edge_weight_sampler.cc:78-92) -- with the default 0.0 every prob is 0/0 = NaN, no slot takes its
