@@ -43,6 +43,7 @@ EXPORTS = [
     "glx_graph_degrees", "glx_graph_in_degrees", "glx_sample", "glx_sample_ex", "glx_sample_hops",
     "glx_graph_enable_in_degree", "glx_graph_enable_default_weight", "glx_sample_full_sizes", "glx_sample_full",
     "glx_graph_set_timestamps", "glx_sample_filtered", "glx_sample_full_filtered", "glx_random_walk",
+    "glx_graph_has_timestamps", "glx_sample_temporal", "glx_sample_temporal_hops",
     "glx_features_create", "glx_features_view", "glx_features_destroy", "glx_features_info",
     "glx_features_create_ex", "glx_features_view_ex", "glx_features_dtype",
     "glx_knn_search", "glx_knn_merge",
@@ -77,6 +78,8 @@ EXPORTS = [
 
 
 FILTER_NONE, FILTER_EQUAL, FILTER_LARGER_THAN = 0, 1, 2
+TEMPORAL_RECENT, TEMPORAL_UNIFORM = 0, 1
+TEMPORAL_STRATEGIES = {"recent": TEMPORAL_RECENT, "uniform": TEMPORAL_UNIFORM}
 FILTER_FIELD_NONE, FILTER_FIELD_ID, FILTER_FIELD_TIMESTAMP = 0, 1, 2
 
 
@@ -156,6 +159,10 @@ def lib():
         L.glx_sample_full_sizes.argtypes = [vp, vp, i32, i32, vp, vp, ci, vp]
         L.glx_sample_full.argtypes = [vp, vp, i32, i32, vp, vp, vp, ci, vp]
         L.glx_graph_set_timestamps.argtypes = [vp, vp, ci, vp]
+        L.glx_graph_has_timestamps.argtypes = [vp, ctypes.POINTER(ci)]
+        L.glx_sample_temporal.argtypes = [vp, ci, vp, vp, vp, i32, i32, ci, i64, i64, u64, u64, vp, vp, vp, vp, ci, vp]
+        L.glx_sample_temporal_hops.argtypes = [vp, i32, ci, vp, vp, i32, vp, ci, i64, i64, u64, u64, vp, vp, vp, vp, ci,
+                                               vp]
         L.glx_random_walk.argtypes = [vp, vp, i32, i32, f32, f32, i32, f32, i64, u64, u64, vp, ci, vp]
         L.glx_sample_filtered.argtypes = [vp, ci, vp, vp, i32, i32, ci, i64, u64, u64, ctypes.POINTER(Filter), vp, vp, ci,
                                           vp]
@@ -424,6 +431,32 @@ class Graph:
         """Per-slot edge timestamps (CSR order) for a handle made from a CSR; mutates the handle."""
         p, kind = _ptr(ts_slot)
         _check(lib().glx_graph_set_timestamps(self._h, p, kind, _stream(kind, self.device)))
+
+    @property
+    def has_timestamps(self):
+        """Whether the graph keeps per-slot timestamps (what sample_temporal needs)."""
+        h = ctypes.c_int(0)
+        _check(lib().glx_graph_has_timestamps(self._h, ctypes.byref(h)))
+        return bool(h.value)
+
+    def sample_temporal(self, src, cutoff, k, strategy="recent", inclusive=False, seed=0, call_counter=0,
+                        default_neighbor_id=0, default_timestamp=-1, rng_rows=None):
+        """The neighbours of src[i] over edges with a timestamp < cutoff[i] (<= when inclusive): the k latest, latest
+        first ("recent"), or k uniform draws with replacement ("uniform").  -> (nbr[batch, k], eid[batch, k],
+        ts[batch, k] int64, cnt[batch] int32): row i holds cnt[i] sampled edges in its first slots, the others are
+        (default_neighbor_id, -1, default_timestamp).  numpy in -> numpy out, torch in -> torch out (nothing is read
+        back; runs on torch's current stream)."""
+        if isinstance(strategy, str):
+            strategy = TEMPORAL_STRATEGIES[strategy]
+        batch = int(src.shape[0])
+        nbr, eid, ts, cnt = _temporal_outputs(src, batch, k)
+        ps, pc, pr = _ptr(src), _ptr(cutoff), _ptr(rng_rows)
+        pn, pe, pt, pk = _ptr(nbr), _ptr(eid), _ptr(ts), _ptr(cnt)
+        kind = _kind(ps, pc, pr, pn)
+        _check(lib().glx_sample_temporal(self._h, strategy, ps[0], pc[0], pr[0], batch, k, 1 if inclusive else 0,
+                                         default_neighbor_id, default_timestamp, seed, call_counter, pn[0], pe[0],
+                                         pt[0], pk[0], kind, _stream(kind, self.device)))
+        return nbr, eid, ts, cnt
 
     def sample_filtered(self, sampler, src, k, filter_type, filter_field, values, seed=0, call_counter=0,
                         padding_mode=PAD_CIRCULAR, default_neighbor_id=0, retry_times=5, default_timestamp=-1,
@@ -1282,6 +1315,42 @@ def sample_hops(graphs, sampler, seeds, fanouts, seed=0, call_counter=0, padding
     pe = (ctypes.c_void_p * L)(*[_ptr(o[1])[0] for o in outs])
     _check(lib().glx_sample_hops(gh, L, sampler, _ptr(seeds)[0], int(seeds.shape[0]), fo, padding_mode,
                                  default_neighbor_id, seed, call_counter, pn, pe, kind, _stream(kind, graphs[0].device)))
+    return outs
+
+
+def _temporal_outputs(like, rows, k):
+    """(nbr, eid, ts, cnt) buffers of one temporal request of `rows` rows, of the kind of `like`."""
+    if _is_torch(like):
+        import torch
+        nbr, eid, ts = (torch.empty((rows, k), dtype=torch.int64, device=like.device) for _ in range(3))
+        return nbr, eid, ts, torch.empty(rows, dtype=torch.int32, device=like.device)
+    return (np.empty((rows, k), np.int64), np.empty((rows, k), np.int64), np.empty((rows, k), np.int64),
+            np.empty(rows, np.int32))
+
+
+def sample_temporal_hops(graphs, seeds, cutoff, fanouts, strategy="recent", inclusive=False, seed=0, call_counter=0,
+                         default_neighbor_id=0, default_timestamp=-1):
+    """Multi-hop temporal sampling: hop 0 is Graph.sample_temporal of (seeds, cutoff) on graphs[0]; request row r of
+    hop h >= 1 is slot r of hop h - 1 -- its id is that slot's neighbour, its cutoff that slot's edge timestamp -- on
+    graphs[h] with stream (seed, call_counter + h).  A default-filled slot yields a default-filled row with cnt = 0.
+    -> list over hops of (nbr, eid, ts, cnt), hop h shaped [batch * fanouts[0] * ... * fanouts[h-1], fanouts[h]]."""
+    if isinstance(strategy, str):
+        strategy = TEMPORAL_STRATEGIES[strategy]
+    L = len(fanouts)
+    assert len(graphs) == L
+    rows = int(seeds.shape[0])
+    outs = []
+    for k in fanouts:
+        outs.append(_temporal_outputs(seeds, rows, k))
+        rows *= k
+    ps, pc = _ptr(seeds), _ptr(cutoff)
+    kind = _kind(ps, pc)
+    gh = (ctypes.c_void_p * L)(*[g._h for g in graphs])
+    fo = (ctypes.c_int32 * L)(*fanouts)
+    po = [(ctypes.c_void_p * L)(*[_ptr(o[i])[0] for o in outs]) for i in range(4)]
+    _check(lib().glx_sample_temporal_hops(gh, L, strategy, ps[0], pc[0], int(seeds.shape[0]), fo, 1 if inclusive else 0,
+                                          default_neighbor_id, default_timestamp, seed, call_counter, po[0], po[1],
+                                          po[2], po[3], kind, _stream(kind, graphs[0].device)))
     return outs
 
 

@@ -21,6 +21,7 @@ from graphlearn.sampler import *  # noqa: F401,F403
 from graphlearn.traversal import *  # noqa: F401,F403
 from graphlearn.graph import Graph  # noqa: F401
 from graphlearn.loader import NeighborLoader, NeighborBatch, CompactBatch  # noqa: F401
+from graphlearn.loader import TemporalNeighborLoader, TemporalBatch, TemporalBlock  # noqa: F401
 from graphlearn.gsl import Dataset  # noqa: F401
 from graphlearn.sampler import SubGraph  # noqa: F401  (python/data/values.py SubGraph: what subgraph_sampler().get() returns)
 import graphlearn.nn as nn  # noqa: F401,E402  (gl.nn.Dataset / Data / SubGraph / HeteroSubGraph)

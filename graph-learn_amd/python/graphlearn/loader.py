@@ -41,10 +41,22 @@ with dedup=True the loader waits for the stream once per node type per batch (th
 
 Seeding: batch i of epoch e uses call counter (e * batches_per_epoch + i) * hops, so a
 (sampling seed, epoch, batch) triple always reproduces the same sample.
+
+TemporalNeighborLoader walks the events of a timestamped edge type in time order and hands every event the history of
+its end points BEFORE the event (glx_sample_temporal_hops: one cutoff per request row), for temporal models such as
+TGN / TGAT:
+
+    loader = gl.TemporalNeighborLoader(g, "interaction", "interaction", [10], batch_size=200, negatives=1)
+    for batch in loader:                 # events in ascending (t, edge id) order; never shuffled
+        batch.src, batch.dst, batch.t, batch.eid, batch.neg_dst
+        blk = batch.block("src", 0)      # role "src" | "dst" | "neg", hop 0
+        blk.nbr, blk.eid, blk.ts         # [rows, fanout] int64: neighbours over edges with ts < the row's cutoff
+        blk.cnt, blk.rel_t, blk.edge_x   # valid slots per row, cutoff - ts, the sampled edges' float attributes
+        rows, eid, ts, counts = batch.ragged("src", 0)   # the valid slots only: what dot_attention(counts=) takes
 """
 import numpy as np
 
-__all__ = ["NeighborLoader", "NeighborBatch", "CompactBatch"]
+__all__ = ["NeighborLoader", "NeighborBatch", "CompactBatch", "TemporalNeighborLoader", "TemporalBatch", "TemporalBlock"]
 
 
 _COLUMN_NAMES = ("labels", "weights", "timestamps", "int_attrs")
@@ -243,3 +255,186 @@ class NeighborLoader(object):
     if self._ncols is not None:
       batch.node_cols_nodes, batch.y = cols_nodes, y
     return batch
+
+
+_ROLES = ("src", "dst", "neg")
+
+
+class TemporalBlock(object):
+  """One hop of one role of a TemporalBatch.  Request row r is the role's seed r (hop 0) or slot r of the previous hop.
+
+    nbr, eid, ts   [rows, fanout] int64: the sampled neighbours, their edge ids and edge timestamps; a slot that holds no
+                   edge is (default neighbour id, -1, default timestamp)
+    cnt            [rows] int32: valid slots of the row -- the first cnt ("recent"), or all / none ("uniform")
+    cutoff         [rows] int64: the time the row's history ends at (strictly before it unless inclusive)
+    rel_t          [rows, fanout] int64: cutoff - ts, 0 where the slot holds no edge
+    edge_x         [rows, fanout, D] float attributes of the sampled edges (None unless asked for / the type has none)
+    edge_cols      {name: [rows, fanout (, i_num)]} columns of the sampled edges (None unless asked for)
+  """
+
+  def __init__(self, nbr, eid, ts, cnt, cutoff):
+    import torch
+    self.nbr, self.eid, self.ts, self.cnt, self.cutoff = nbr, eid, ts, cnt, cutoff
+    self.valid = torch.arange(nbr.shape[1], device=nbr.device)[None, :] < cnt[:, None]
+    self.rel_t = torch.where(self.valid, cutoff[:, None] - ts, torch.zeros_like(ts))
+    self.edge_x = self.edge_cols = None
+
+
+class TemporalBatch(object):
+  """Tensors of one batch of events (all on the GPU): src, dst, t, eid [B]; neg_dst [B, negatives]; per role in
+  ("src", "dst", "neg") a list over hops of TemporalBlock (blocks[role]; "neg" is empty without negatives).  The "neg"
+  role's seeds are neg_dst flattened, each with its event's time."""
+
+  def __init__(self, src, dst, t, eid, neg_dst, blocks):
+    self.src, self.dst, self.t, self.eid, self.neg_dst, self.blocks = src, dst, t, eid, neg_dst, blocks
+
+  def block(self, role, h):
+    return self.blocks[role][h]
+
+  def seeds(self, role):
+    """ids the role's hop 0 was sampled for"""
+    return {"src": self.src, "dst": self.dst, "neg": self.neg_dst.reshape(-1)}[role]
+
+  def ragged(self, role, h, with_positions=False):
+    """(rows, eid, ts, counts): the block's valid slots only, row after row -- the counts= layout of dot_attention and
+    TransformerConv (rows = neighbour ids, counts = cnt).  One boolean-mask compaction: the number of valid slots decides
+    the shapes, so this waits for the stream ONCE (the dense blocks never do).  with_positions=True appends the valid
+    slots' flat positions in the dense block (to gather edge_x / rel_t the same way)."""
+    blk = self.blocks[role][h]
+    at = blk.valid.reshape(-1).nonzero().reshape(-1)  # the host sync
+    out = (blk.nbr.reshape(-1)[at], blk.eid.reshape(-1)[at], blk.ts.reshape(-1)[at], blk.cnt)
+    return out + (at,) if with_positions else out
+
+
+class TemporalNeighborLoader(object):
+  """Batches of timestamped events with the temporal neighbourhoods of their end points.
+
+    graph       an initialised gl.Graph
+    events      an edge type name -- its edges are the events: end points from the store, timestamps from the type's
+                device columns, read once here -- or (src, dst, t[, eid]) arrays.  Iteration is in ascending (t, edge id)
+                order (one stable sort on the device); temporal training is not shuffled.
+    history     the timestamped edge type whose past is sampled.  Roles "src" sample its out-edges; roles "dst" / "neg"
+                sample history + "_reverse" (a heterogeneous type declared directed=False) or the type itself (a
+                homogeneous one); further hops alternate between the two.
+    fanouts     neighbours per hop
+    strategy    "recent" (the latest first) | "uniform" (with replacement)
+    inclusive   cutoffs are strict by default: an event never sees itself or its same-timestamp siblings
+    negatives   neg_dst[B, negatives] from the "random" negative sampler of `history` (what
+                graph.negative_sampler(history, negatives, "random") draws under call counter epoch * len(loader) + batch)
+  Batch i of epoch e samples role number r under call counter ((e * len(loader) + i) * 3 + r) * hops, so a (sampling
+  seed, epoch, batch) triple reproduces its batch bit for bit.  Not served here: dedup=True, the distributed store,
+  graph capture."""
+
+  def __init__(self, graph, events, history, fanouts, batch_size, strategy="recent", inclusive=False, negatives=0,
+               edge_features=True, edge_columns=(), drop_last=False):
+    import glx
+    import torch
+    from graphlearn import settings
+    for name in tuple(edge_columns):
+      if name not in _COLUMN_NAMES:
+        raise ValueError("unknown column {!r}: one of {}".format(name, _COLUMN_NAMES))
+    if strategy not in glx.TEMPORAL_STRATEGIES:
+      raise ValueError("unknown temporal strategy {!r}: one of {}".format(strategy, sorted(glx.TEMPORAL_STRATEGIES)))
+    if getattr(graph, "_shard", (0, 1))[1] > 1:
+      raise NotImplementedError("TemporalNeighborLoader does not serve the distributed store")
+    self._graph = graph
+    self._fanouts = [int(k) for k in fanouts]
+    self._batch_size = int(batch_size)
+    self._strategy, self._inclusive = strategy, bool(inclusive)
+    self._negatives = int(negatives)
+    self._drop_last = drop_last
+    self._device = torch.device("cuda", settings._MIRROR.get("device_id", 0))  # pylint: disable=protected-access
+    self._epoch = 0
+    # the two directions of the history
+    topo = graph.get_topology()
+    graph.get_edge_decoder(history)
+    if topo.get_src_type(history) == topo.get_dst_type(history):
+      twin = history
+    else:
+      twin = history + "_reverse"
+      if twin not in graph.get_edge_decoders():
+        raise ValueError("destination-side roles sample the in-edges of {!r}: edge type {!r} is missing (declare the "
+                         "type with directed=False)".format(history, twin))
+    out_types = [history if h % 2 == 0 else twin for h in range(len(self._fanouts))]
+    in_types = [twin if h % 2 == 0 else history for h in range(len(self._fanouts))]
+    self._types = {"src": out_types, "dst": in_types, "neg": in_types}
+    self._graphs = {}
+    for e in set(out_types + in_types):
+      self._graphs[e] = graph.device_graph(e)
+      if not self._graphs[e].has_timestamps:
+        raise ValueError("edge type {!r} keeps no timestamps (Decoder(timestamped=True))".format(e))
+    self._efeats, self._ecols = {}, {}
+    for e in self._graphs:
+      if edge_features:
+        try:
+          self._efeats[e] = graph.device_edge_features(e)
+        except ValueError:
+          self._efeats[e] = None  # an edge type without float attributes
+      if edge_columns:
+        self._ecols[e] = graph.device_edge_columns(e)
+    self._edge_columns = tuple(edge_columns)
+    self._negative = glx.Negative.from_graph(self._graphs[history]) if self._negatives > 0 else None
+    # the events, in (t, edge id) order
+    if isinstance(events, str):
+      server = graph.get_server()
+      src, dst = np.asarray(server.edge_src_ids(events), np.int64), np.asarray(server.edge_dst_ids(events), np.int64)
+      eid = torch.arange(src.shape[0], dtype=torch.int64, device=self._device)
+      t = graph.device_edge_columns(events).lookup(eid, ("timestamps",), settings.column_defaults())["timestamps"]
+    else:
+      src, dst, t = (np.ascontiguousarray(np.asarray(a, np.int64)) for a in events[:3])
+      t = torch.from_numpy(t).to(self._device)
+      eid = (torch.from_numpy(np.ascontiguousarray(np.asarray(events[3], np.int64))).to(self._device)
+             if len(events) > 3 else torch.arange(src.shape[0], dtype=torch.int64, device=self._device))
+    src, dst = (torch.from_numpy(np.ascontiguousarray(a)).to(self._device) for a in (src, dst))
+    by_eid = torch.sort(eid, stable=True)[1]
+    order = by_eid[torch.sort(t[by_eid], stable=True)[1]]
+    self._src, self._dst, self._t, self._eid = (a[order].contiguous() for a in (src, dst, t.to(torch.int64), eid))
+
+  def __len__(self):
+    n = self._src.shape[0]
+    return n // self._batch_size if self._drop_last else (n + self._batch_size - 1) // self._batch_size
+
+  def __iter__(self):
+    import glx
+    from graphlearn import settings
+    flags = settings._MIRROR  # pylint: disable=protected-access
+    batches, hops = len(self), len(self._fanouts)
+    for i in range(batches):
+      lo, hi = i * self._batch_size, (i + 1) * self._batch_size
+      src, dst, t, eid = (a[lo:hi] for a in (self._src, self._dst, self._t, self._eid))
+      step = self._epoch * batches + i
+      neg_dst = src.new_empty((src.shape[0], 0))
+      if self._negative is not None:
+        neg_dst = self._negative.sample(src, self._negatives, default_neighbor_id=flags["default_neighbor_id"],
+                                        seed=flags["sampling_seed"], call_counter=step)
+      seeds = {"src": (src, t), "dst": (dst, t), "neg": (neg_dst.reshape(-1), t.repeat_interleave(self._negatives))}
+      blocks = {}
+      for r, role in enumerate(_ROLES):
+        blocks[role] = []
+        if role == "neg" and self._negative is None:
+          continue
+        ids, cutoff = seeds[role]
+        out = glx.sample_temporal_hops([self._graphs[e] for e in self._types[role]], ids, cutoff, self._fanouts,
+                                       strategy=self._strategy, inclusive=self._inclusive, seed=flags["sampling_seed"],
+                                       call_counter=(step * len(_ROLES) + r) * hops,
+                                       default_neighbor_id=flags["default_neighbor_id"],
+                                       default_timestamp=flags["default_timestamp"])
+        for h, (nbr, e, ts, cnt) in enumerate(out):
+          blk = TemporalBlock(nbr, e, ts, cnt, cutoff)
+          self._with_edge_data(blk, self._types[role][h])
+          blocks[role].append(blk)
+          cutoff = ts.reshape(-1)
+      yield TemporalBatch(src, dst, t, eid, neg_dst, blocks)
+    self._epoch += 1
+
+  def _with_edge_data(self, blk, edge_type):
+    """edge_x / edge_cols of a block, gathered by its edge ids as NeighborLoader._with_edge_data does (the -1 of a slot
+    that holds no edge is unknown: the defaults)"""
+    from graphlearn import settings
+    f = self._efeats.get(edge_type)
+    if f is not None:
+      default_attr = float(settings._MIRROR.get("default_float_attr", 0.0))  # pylint: disable=protected-access
+      blk.edge_x = f.lookup(blk.eid.reshape(-1), default_attr).reshape(tuple(blk.eid.shape) + (-1,))
+    c = self._ecols.get(edge_type)
+    if c is not None:
+      blk.edge_cols = _shaped(c.lookup(blk.eid.reshape(-1), self._edge_columns, settings.column_defaults()), blk.eid.shape)

@@ -326,6 +326,49 @@ GLX_API int glx_sample_full_filtered(const glx_graph* g, const int64_t* src, int
                                      const glx_filter* filter, int64_t* nbr_out, int64_t* eid_out, int ptr_kind,
                                      void* stream);
 
+/* ---- temporal neighbour sampling: "the neighbours of v over edges that happened before t", with a cutoff of its own
+ * for every request row.  An addition of this engine (added under 5).  It stands in for the sample the reference's TGN
+ * loader takes per event (examples/pytorch/tgn/temporal_batch_loader.py:70-80: a topk sample of the whole interaction
+ * graph, which ignores time), and answers per row what the reference's timestamp filter answers for request row 0's
+ * value only (core/operator/sampler/filter.cc:74-82), over the timestamp-ascending rows that Build() lays out for a
+ * timestamped edge type (core/graph/storage/memory_adj_matrix.cc:129-148). -------------------------------------------
+ *
+ * Request row i (raw id src[i], cutoff t = cutoff[i]): c = the number of slots of the row whose timestamp is < t
+ * (<= t when inclusive != 0).  Rows are timestamp-ascending with ties in insertion order, so these are the row's first
+ * c slots; an unknown id has c = 0.  INT64_MAX with `inclusive` selects the whole row, INT64_MIN nothing.
+ *   GLX_TEMPORAL_RECENT   slot j < min(k, c) of the answer is CSR slot c - 1 - j (latest first), the other slots are
+ *                         default-filled: (default_neighbor_id, -1, default_timestamp); cnt_out[i] = min(k, c).
+ *   GLX_TEMPORAL_UNIFORM  c > 0: slot j is CSR slot bounded(draw j of row stream rr, c) under (seed, call_counter),
+ *                         rr = rng_rows ? rng_rows[i] : i -- the draw of RandomSampler (random_sampler.cc:61-63) with
+ *                         the prefix length in place of the degree -- and cnt_out[i] = k.  c == 0: the row is
+ *                         default-filled and cnt_out[i] = 0.
+ * nbr_out / eid_out / ts_out are [batch, k], row-major and dense, every element written; eid_out, ts_out and cnt_out
+ * may each be NULL.  There are no padding modes: a temporal consumer needs the mask.  batch == 0 is a no-op; k >= 1.
+ * The graph must keep per-slot timestamps (glx_graph_build_ordered with GLX_ORDER_TIMESTAMP_ASC, or
+ * glx_graph_set_timestamps on a glx_graph_create handle -- whose rows the CALLER keeps ascending; if they are not,
+ * the answer is unspecified but every load stays inside the row).  The same bits on every call; no atomics.
+ *
+ * glx_sample_temporal_hops: request row r of hop h >= 1 is slot r of hop h - 1 -- its id is that slot's neighbour and
+ * its cutoff that slot's edge timestamp (a neighbour's history before the interaction that reached it) -- and draws
+ * from graphs[h] with stream (seed, call_counter + h).  A default-filled parent slot yields a default-filled row with
+ * cnt = 0 whatever default_neighbor_id is.  Frontiers stay on the device; the result equals num_hops single calls
+ * chained by that rule.  eid_out / ts_out / cnt_out, or single entries of them, may be NULL -- except that with device
+ * pointers the outputs ARE the frontiers, so every hop but the last needs its ts_out and cnt_out.  num_hops <= 8. */
+#define GLX_TEMPORAL_RECENT 0
+#define GLX_TEMPORAL_UNIFORM 1
+GLX_API int glx_graph_has_timestamps(const glx_graph* g, int* has);
+GLX_API int glx_sample_temporal(const glx_graph* g, int strategy, const int64_t* src, const int64_t* cutoff,
+                                const int64_t* rng_rows, int32_t batch, int32_t k, int inclusive,
+                                int64_t default_neighbor_id, int64_t default_timestamp, uint64_t seed,
+                                uint64_t call_counter, int64_t* nbr_out, int64_t* eid_out, int64_t* ts_out,
+                                int32_t* cnt_out, int ptr_kind, void* stream);
+GLX_API int glx_sample_temporal_hops(const glx_graph* const* graphs, int32_t num_hops, int strategy,
+                                     const int64_t* seeds, const int64_t* cutoff, int32_t batch,
+                                     const int32_t* fanouts, int inclusive, int64_t default_neighbor_id,
+                                     int64_t default_timestamp, uint64_t seed, uint64_t call_counter,
+                                     int64_t* const* nbr_out, int64_t* const* eid_out, int64_t* const* ts_out,
+                                     int32_t* const* cnt_out, int ptr_kind, void* stream);
+
 /* ---- random walks: replaces the "RandomWalk" operator (core/operator/random_walk/
  * random_walk.cc:30-276) -- DeepWalk (:168-190) when p = q = 1 within 32 FLT_EPSILON
  * (RandomWalkRequest::IsDeepWalk, random_walk_request.cc:152-160), node2vec otherwise
