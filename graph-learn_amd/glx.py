@@ -54,6 +54,7 @@ EXPORTS = [
     "glx_dot_attention", "glx_dot_attention_backward",
     "glx_pair_dot", "glx_pair_dot_backward",
     "glx_rows_coalesce", "glx_embedding_update",
+    "glx_tgn_store_update", "glx_tgn_message", "glx_tgn_message_backward", "glx_tgn_memory_write",
     "glx_partition", "glx_stitch_i64", "glx_stitch_f32", "glx_aggregate_stitch",
     "glx_negative_create", "glx_negative_from_graph", "glx_negative_destroy", "glx_negative_info",
     "glx_negative_export", "glx_graph_enable_negative", "glx_negative_sample",
@@ -196,6 +197,11 @@ def lib():
         L.glx_pair_dot_backward.argtypes = [ci, ci, vp, vp, i32, i32, vp, i32, vp, i64, i32, i64, f32, vp, ci, vp]
         L.glx_rows_coalesce.argtypes = [ci, vp, i32, i64, i32, vp, vp, vp, vp, ci, vp]
         L.glx_embedding_update.argtypes = [ci, ci, vp, vp, vp, i64, i32, vp, vp, i32, f32, f32, f32, f32, f32, f32, vp]
+        L.glx_tgn_store_update.argtypes = [ci, i64, i32, vp, vp, vp, vp, i32, i64, vp, vp, vp, vp, vp]
+        L.glx_tgn_message.argtypes = [ci, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp,
+                                      vp]
+        L.glx_tgn_message_backward.argtypes = [ci, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.glx_tgn_memory_write.argtypes = [ci, i64, i32, vp, i32, vp, vp, vp, vp, vp]
         L.glx_partition.argtypes = [ci, vp, i64, i32, vp, vp, vp, vp]
         L.glx_stitch_i64.argtypes = [ci, vp, vp, i64, i32, vp, vp]
         L.glx_stitch_f32.argtypes = [ci, vp, vp, i64, i32, vp, vp]
@@ -1173,6 +1179,79 @@ def embedding_update(algo, W, urows, ug, state1=None, state2=None, alpha=0.0, ep
                                       beta1, c1, beta2, c2, _stream(PTR_DEVICE, device)))
 
 
+def tgn_backward_depth(n):
+    """GLX_TGN_BWD_DEPTH(n): the float32 additions on the longest path of tgn_message_backward's tree over n rows."""
+    return 72 + (int(n) + 16383) // 16384
+
+
+def _tgn_device(*tensors):
+    ptrs = [_ptr(x) for x in tensors]
+    assert _kind(*ptrs) == PTR_DEVICE, "the TGN memory lives on the device: torch CUDA tensors only"
+    first = next(x for x in tensors if x is not None)
+    assert all(x is None or x.device == first.device for x in tensors), "every tensor must live on one device"
+    return [p[0] for p in ptrs], first.device.index or 0
+
+
+def tgn_store_update(src, dst, t, raw_msg, seq_base, pend_t, pend_seq, pend_other, pend_raw):
+    """One update of the one-slot-per-node message store (glx_tgn_store_update); torch CUDA tensors only, in place, on
+    the current stream.  src, dst, t [B] int64, raw_msg [B, R] float32; pend_t, pend_seq, pend_other [N] int64,
+    pend_raw [N, R] float32.  Event p has sequence number seq_base + p (a Python int: the number of events of earlier
+    calls); the slot of node v ends up holding the event with the largest (t, seq) that ever named v as src or dst.
+    Ids outside [0, N) are dropped.  Nothing is read back."""
+    N, R, B = int(pend_t.shape[0]), int(pend_raw.shape[1]), int(src.shape[0])
+    assert int(dst.shape[0]) == B and int(t.shape[0]) == B and tuple(raw_msg.shape) == (B, R), "one event per position"
+    assert int(pend_seq.shape[0]) == N and int(pend_other.shape[0]) == N and int(pend_raw.shape[0]) == N
+    p, device = _tgn_device(src, dst, t, raw_msg, pend_t, pend_seq, pend_other, pend_raw)
+    _check(lib().glx_tgn_store_update(device, N, R, p[0], p[1], p[2], p[3], B, int(seq_base), p[4], p[5], p[6], p[7],
+                                      _stream(PTR_DEVICE, device)))
+
+
+def tgn_message(memory, last_update, pend_t, pend_seq, pend_other, pend_raw, time_w, time_b, n_id):
+    """The fused message of the nodes n_id[n] (glx_tgn_message); torch CUDA tensors only, on the current stream ->
+    (msg [n, 2M + R + T], h [n, M], dt [n] float32, t [n] int64, has [n] int32).  For a node with a pending message:
+    msg = [memory[v] | memory[other] | raw | cos(time_w * dt + time_b)], dt = float(pend_t[v] - last_update[v]),
+    t = pend_t[v]; for any other entry a zero row, dt = 0 and t = last_update[v] (0 outside the table).  h = memory[v]."""
+    import torch
+    N, M, R, T, n = int(memory.shape[0]), int(memory.shape[1]), int(pend_raw.shape[1]), int(time_w.shape[0]), int(n_id.shape[0])
+    assert int(time_b.shape[0]) == T and int(pend_raw.shape[0]) == N and int(last_update.shape[0]) == N
+    dev = memory.device
+    msg = torch.empty((n, 2 * M + R + T), dtype=torch.float32, device=dev)
+    h = torch.empty((n, M), dtype=torch.float32, device=dev)
+    dt = torch.empty((n,), dtype=torch.float32, device=dev)
+    t_out = torch.empty((n,), dtype=torch.int64, device=dev)
+    has = torch.empty((n,), dtype=torch.int32, device=dev)
+    p, device = _tgn_device(memory, last_update, pend_t, pend_seq, pend_other, pend_raw, time_w, time_b, n_id, msg, h, dt,
+                            t_out, has)
+    _check(lib().glx_tgn_message(device, N, M, R, T, p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], n, p[9], p[10],
+                                 p[11], p[12], p[13], _stream(PTR_DEVICE, device)))
+    return msg, h, dt, t_out, has
+
+
+def tgn_message_backward(grad_msg, dt, has, time_w, time_b, time_off):
+    """(grad_w [T], grad_b [T]) of the time encoding in columns [time_off, time_off + T) of grad_msg[n, width], from the
+    dt and has of tgn_message (glx_tgn_message_backward); torch CUDA tensors only.  A fixed reduction tree of
+    tgn_backward_depth(n) additions on its longest path: the same bits on every call.  Rows with has == 0 contribute
+    nothing."""
+    import torch
+    n, width, T = int(grad_msg.shape[0]), int(grad_msg.shape[1]), int(time_w.shape[0])
+    assert int(dt.shape[0]) == n and int(has.shape[0]) == n and int(time_b.shape[0]) == T
+    grad_w, grad_b = torch.empty_like(time_w), torch.empty_like(time_b)
+    p, device = _tgn_device(grad_msg, dt, has, time_w, time_b, grad_w, grad_b)
+    _check(lib().glx_tgn_message_backward(device, n, width, int(time_off), T, p[0], p[1], p[2], p[3], p[4], p[5], p[6],
+                                          _stream(PTR_DEVICE, device)))
+    return grad_w, grad_b
+
+
+def tgn_memory_write(memory, last_update, n_id, new_memory, t_new):
+    """memory[n_id[i]] = new_memory[i] and last_update[n_id[i]] = t_new[i], in place (glx_tgn_memory_write); torch CUDA
+    tensors only.  An id outside the table is skipped.  The valid ids must be distinct (not detected: a repeated id is
+    a lost update)."""
+    N, M, n = int(memory.shape[0]), int(memory.shape[1]), int(n_id.shape[0])
+    assert tuple(new_memory.shape) == (n, M) and int(t_new.shape[0]) == n and int(last_update.shape[0]) == N
+    p, device = _tgn_device(n_id, new_memory, t_new, memory, last_update)
+    _check(lib().glx_tgn_memory_write(device, N, M, p[0], n, p[1], p[2], p[3], p[4], _stream(PTR_DEVICE, device)))
+
+
 COLUMN_NAMES = ("weights", "labels", "timestamps", "int_attrs")
 COLUMNS_MAP_DENSE, COLUMNS_MAP_OWN, COLUMNS_MAP_BORROWED = 0, 1, 2
 # what a requested column answers for an id the table does not know (the reference's Default* flags, config.cc)
@@ -1380,13 +1459,15 @@ def stitch(rows, order):
     return out
 
 
-def unique(parts, return_inverse=True):
+def unique(parts, return_inverse=True, pad=None):
     """Distinct ids of the stream parts[0], parts[1], ... (1 .. 16 int64 arrays of any shape, at most 2^31 - 1 ids in
     all) in order of first occurrence -- no sort, the same answer on every run.
     -> (nodes[m], [inverse of each part, shaped like the part] or None, part_end[len(parts)]):
     nodes[inverse[p]] == parts[p], and nodes[:part_end[p]] is the distinct set of parts[0 .. p].
     Torch CUDA tensors are device pointers on the current stream (the outputs are CUDA tensors, part_end included);
-    numpy arrays are host pointers.  The device path reads m = part_end[-1] back with ONE host read, to slice nodes."""
+    numpy arrays are host pointers.  The device path reads m = part_end[-1] back with ONE host read, to slice nodes --
+    unless `pad` is given (torch only): then nothing is read back and nodes comes at its full length n, the distinct ids
+    followed by n - m copies of `pad` (an id the consumer skips, such as -1)."""
     parts = list(parts)
     assert parts, "unique() needs at least one part"
     torch_mode = _is_torch(parts[0])
@@ -1399,12 +1480,15 @@ def unique(parts, return_inverse=True):
     if torch_mode:
         import torch
         dev = parts[0].device
-        nodes = torch.empty(n, dtype=torch.int64, device=dev)
+        nodes = (torch.empty(n, dtype=torch.int64, device=dev) if pad is None
+                 else torch.full((n,), int(pad), dtype=torch.int64, device=dev))
         inverse = torch.empty(n, dtype=torch.int64, device=dev) if return_inverse else None
         part_end = torch.empty(P, dtype=torch.int64, device=dev)
         assert all(p.dtype == torch.int64 for p in parts)
         device = dev.index or 0
     else:
+        if pad is not None:
+            raise ValueError("unique(): pad needs torch CUDA tensors")
         nodes = np.empty(n, np.int64)
         inverse = np.empty(n, np.int64) if return_inverse else None
         part_end = np.empty(P, np.int64)
@@ -1415,7 +1499,7 @@ def unique(parts, return_inverse=True):
     pl = (ctypes.c_int64 * P)(*lens)
     _check(lib().glx_unique(device, pp, pl, P, _ptr(nodes)[0], _ptr(inverse)[0], _ptr(part_end)[0], kind,
                             _stream(kind, device)))
-    m = int(part_end[-1])
+    m = n if pad is not None else int(part_end[-1])
     inv = None
     if return_inverse:
         inv, at = [], 0

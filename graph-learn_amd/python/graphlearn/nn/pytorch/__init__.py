@@ -4,3 +4,4 @@ from graphlearn.nn.pytorch.segment import (dot_attention, gat_attention, gather_
                                             segment_aggregate, segment_softmax, weighted_segment_aggregate)
 from graphlearn.nn.pytorch.layers import GATConv, TransformerConv  # noqa: F401
 from graphlearn.nn.pytorch.embedding import SparseAdagrad, SparseAdam, SparseEmbedding, SparseSGD  # noqa: F401
+from graphlearn.nn.pytorch.memory import TGNMemory, TimeEncoder  # noqa: F401

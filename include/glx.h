@@ -44,7 +44,7 @@ extern "C" {
  * glx_segment_softmax_backward; pair scores -- glx_pair_dot, glx_pair_dot_backward; trainable embedding tables --
  * glx_rows_coalesce, glx_embedding_update; fused GAT attention -- glx_gat_attention, glx_gat_attention_backward; fused
  * dot-product attention -- glx_dot_attention, glx_dot_attention_backward; exact KNN search -- GLX_KNN_*, glx_knn_search,
- * glx_knn_merge. */
+ * glx_knn_merge; TGN memory -- glx_tgn_store_update, glx_tgn_message, glx_tgn_message_backward, glx_tgn_memory_write. */
 #define GLX_ABI_VERSION 5
 
 /* Exported symbols: libglx.so is built with -fvisibility=hidden. */
@@ -781,6 +781,82 @@ GLX_API int glx_rows_coalesce(int device, const int64_t* rows, int32_t n, int64_
 GLX_API int glx_embedding_update(int device, int algo, float* W, float* state1, float* state2, int64_t num_rows,
                                  int32_t dim, const int64_t* urows, const float* ug, int32_t n, float alpha, float eps,
                                  float beta1, float c1, float beta2, float c2, void* stream);
+
+/* ---- TGN memory: the device-resident message store, the fused message and the memory write of the memory module the
+ * reference's TGN example takes from torch_geometric -- TGNMemory(num_nodes, msg_dim, memory_dim, time_dim,
+ * message_module=IdentityMessage(...), aggregator_module=LastAggregator()) (examples/pytorch/tgn/train_and_eval.py:70,
+ * the imports at train_and_eval.py:27 above it; used at train_and_eval.py:118 and train_and_eval.py:130). -------------
+ * With the Last aggregator and a message function without parameters the only stored message of a node that is ever
+ * used is the node's latest event over both roles, and the store never clears a message on consumption.  So the store
+ * is ONE pending slot per node, in caller-owned DEVICE buffers (as glx_embedding_update keeps its tables):
+ *   memory      [N, M] float32   +0.0        node memory
+ *   last_update [N]    int64     0           time of the last memory write
+ *   pend_t      [N]    int64     INT64_MIN   timestamp of the node's latest event
+ *   pend_seq    [N]    int64     -1          its sequence number; -1: no message
+ *   pend_other  [N]    int64     -1          the event's other end point
+ *   pend_raw    [N, R] float32   +0.0        the event's raw message (a copy of the row)
+ * (the third column is the initial value the caller fills in).  The sequence number of position p of a
+ * glx_tgn_store_update call is seq_base + p, seq_base = the number of events passed to earlier calls since the buffers
+ * were initialised.  The slot of node v holds the event with the largest (t, seq) among all events that ever named v as
+ * src or dst; a self loop names v twice with the same content.  On a time-ordered stream this is TGNMemory +
+ * LastAggregator with the tie rule fixed -- of two events of one timestamp the larger seq wins, where
+ * LastAggregator's scatter_argmax leaves it open.  On a stream that is NOT time-ordered the rule is still total, and
+ * then DIFFERS from torch_geometric, which lets a later call overwrite a role's list whatever its timestamps are.
+ * Ids outside [0, N) are dropped everywhere.  Common to the four: all pointers are DEVICE pointers; arguments are
+ * checked before any device use; 0 <= N < 2^31; a call only enqueues work on `stream`; every element of every output
+ * is written; no float atomics; nothing is allocated, cleared or launched in proportion to N.  Limits: Last aggregator
+ * and identity message only; float32 only; one GPU (not the distributed store); no graph capture (the backward leases a
+ * workspace); a hub's candidates meet in same-address integer atomics; N * (4 M + 4 R + 32) bytes of state. */
+/* glx_tgn_store_update (bit-exact contract): applies the slot rule to the 2 * batch (event, end point) candidates of
+ * src[batch], dst[batch], t[batch], raw_msg[batch * raw_dim].  The result depends on no scheduling order: launch one
+ * raises pend_t[v] to the largest t (64-bit signed atomic max); launch two raises pend_seq[v] to the largest
+ * seq_base + p among the candidates with t[p] == pend_t[v] -- every older slot has seq < seq_base, so a slot whose t
+ * was neither beaten nor equalled stays whole; in launch three the winners write pend_other[v] and copy their raw row,
+ * one lane group per winning candidate.  A candidate loads the word first and skips the atomic when it cannot raise it,
+ * and the lanes of a wave that agree on an address issue one atomic (for the first 4 addresses a wave names).
+ * batch = 0 is a no-op; raw_dim = 0 is legal (raw_msg and pend_raw may be NULL); 0 <= seq_base, batch < 2^30. */
+GLX_API int glx_tgn_store_update(int device, int64_t num_nodes, int32_t raw_dim, const int64_t* src, const int64_t* dst,
+                                 const int64_t* t, const float* raw_msg, int32_t batch, int64_t seq_base,
+                                 int64_t* pend_t, int64_t* pend_seq, int64_t* pend_other, float* pend_raw, void* stream);
+/* glx_tgn_message: entry i < n, v = n_id[i] (repeats allowed), row width 2 M + R + T.
+ *   h_out[i]   = memory[v], or +0.0 for an id outside the table.
+ *   v inside the table and pend_seq[v] >= 0:  has_out[i] = 1, t_out[i] = pend_t[v],
+ *     dt_out[i] = (float)(pend_t[v] - last_update[v]) -- the int64 difference, then one conversion, round to nearest --
+ *     msg_out[i] = [memory[v] | memory[pend_other[v]] | pend_raw[v] | cosf(fmaf(time_w[j], dt, time_b[j])) for j < T];
+ *     a pend_other outside the table reads +0.0.  The three copied parts are bit copies; the last uses the accurate
+ *     cosf (checked against a bound).
+ *   otherwise: has_out[i] = 0, t_out[i] = last_update[v] (0 for an id outside the table), dt_out[i] = +0.0 and the
+ *     whole row is +0.0 (torch_geometric feeds the GRU a zero message for such a node).
+ * One lane group per entry; each piece moves 16 bytes at a time when its two addresses are 16-byte aligned, one word
+ * at a time otherwise (R = 3 makes every later column unaligned).  mem_dim >= 1, raw_dim >= 0, time_dim >= 0. */
+GLX_API int glx_tgn_message(int device, int64_t num_nodes, int32_t mem_dim, int32_t raw_dim, int32_t time_dim,
+                            const float* memory, const int64_t* last_update, const int64_t* pend_t,
+                            const int64_t* pend_seq, const int64_t* pend_other, const float* pend_raw,
+                            const float* time_w, const float* time_b, const int64_t* n_id, int32_t n, float* msg_out,
+                            float* h_out, float* dt_out, int64_t* t_out, int32_t* has_out, void* stream);
+/* glx_tgn_message_backward: the gradient of the time encoder through columns [time_off, time_off + time_dim) of
+ * grad_msg[n * width], from the dt[n] and has[n] glx_tgn_message wrote.  With x_ij = fmaf(time_w[j], dt[i], time_b[j])
+ * and term_ij = grad_msg[i, time_off + j] * (-sinf(x_ij)) (one rounding):
+ *   grad_b[j] = the sum over the i with has[i] != 0 of term_ij,   grad_w[j] = the same sum of term_ij * dt[i].
+ * A row with has[i] == 0 contributes nothing, whatever its gradient holds.  memory and pend_raw are constants (they are
+ * buffers, and the reference detaches the memory every batch, train_and_eval.py:134).  The sum is a FIXED tree, the
+ * same bits on every call: rows are cut into chunks of GLX_TGN_BWD_ROWS; in a chunk, wave w of 4 adds rows w, w + 4, ..
+ * ascending to +0.0 (64 additions), the four waves combine as (0 + 1) + (2 + 3) (2 additions); then per column lane l of
+ * 64 adds the partials of chunks l, l + 64, .. ascending to +0.0 (ceil(chunks / 64) additions) and the lanes combine
+ * in an xor butterfly (6 additions).  D, the float32 additions on the longest path, is GLX_TGN_BWD_DEPTH(n).
+ * n = 0 writes +0.0.  time_dim >= 1. */
+#define GLX_TGN_BWD_ROWS 256
+#define GLX_TGN_BWD_DEPTH(n) (72 + ((n) + 16383) / 16384)
+GLX_API int glx_tgn_message_backward(int device, int32_t n, int32_t width, int32_t time_off, int32_t time_dim,
+                                     const float* grad_msg, const float* dt, const int32_t* has, const float* time_w,
+                                     const float* time_b, float* grad_w, float* grad_b, void* stream);
+/* glx_tgn_memory_write (bit-exact): row i of new_memory[n * mem_dim] goes to row n_id[i] of memory, and
+ * last_update[n_id[i]] = t_new[i].  An id outside the table is skipped -- the -1 padding of a distinct-id list among
+ * them.  Rows nobody names are not touched, not even rewritten.  PRECONDITION, not detected: the valid entries name
+ * distinct rows; a repeated row is a lost update, not a fault.  (One lane group per entry.) */
+GLX_API int glx_tgn_memory_write(int device, int64_t num_nodes, int32_t mem_dim, const int64_t* n_id, int32_t n,
+                                 const float* new_memory, const int64_t* t_new, float* memory, int64_t* last_update,
+                                 void* stream);
 
 /* ---- negative sampling: replaces RandomNegativeSampler (random_negative_sampler.cc:30-63),
  * InDegreeNegativeSampler / SoftInDegreeNegativeSampler (in_degree_negative_sampler.cc:29-135)
