@@ -11,8 +11,15 @@ The search is glx.Features.search on the item table as it lies in device memory 
 score, ties to the smaller row); the metrics are computed on the device from its ids.  Planted groups are what the L2
 metric retrieves; under the inner product long items win regardless of the group, which the lower numbers show.
 
-Exits non-zero unless two runs give the same bits and the ids equal the float64 brute force.
-Usage: python examples/eval_recall.py [--items 4000] [--users 1000] [--dim 16] [--k 10]"""
+--index ivf also builds an IVF-Flat index over the item table (glx.Features.build_ivf, --nlist lists) and repeats every
+search through it with --nprobe lists probed: one more line per search with the index's own metrics and its recall
+against the exact search's ids.  The index scores rows from the same table with the same chain, so what it returns are
+exact distances; what it can miss are rows in lists it did not probe.
+
+Exits non-zero unless two runs give the same bits and the ids equal the float64 brute force (with --index ivf: and two
+index searches give the same bits, and the index with every list probed equals the exact search bit for bit).
+Usage: python examples/eval_recall.py [--items 4000] [--users 1000] [--dim 16] [--k 10]
+                                      [--index flat|ivf] [--nlist 64] [--nprobe 4]"""
 import argparse
 import math
 import os
@@ -61,10 +68,14 @@ def main():
     ap.add_argument("--dim", type=int, default=16)
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--group", type=int, default=5)
+    ap.add_argument("--index", choices=("flat", "ivf"), default="flat")
+    ap.add_argument("--nlist", type=int, default=64)
+    ap.add_argument("--nprobe", type=int, default=4)
     a = ap.parse_args()
     rng = np.random.default_rng(0)
     items, item_ids, users, user_group = planted(rng, a.items, a.users, a.dim, a.group)
     table = glx.Features(items, ids=item_ids)
+    index = table.build_ivf(a.nlist) if a.index == "ivf" else None
     d_ids = torch.from_numpy(item_ids).cuda()
     group_rows = torch.arange(items.shape[0], device="cuda").view(-1, a.group)
     ok = True
@@ -81,6 +92,19 @@ def main():
             print("%s %s  recall@%d %.4f  ndcg@%d %.4f  hit rate %.4f  two runs same bits: %s  ids == float64 brute force: %s"
                   % (task, metric, a.k, r, a.k, n, h, same_bits, exact))
             ok = ok and same_bits and exact and not math.isnan(r)
+            if index is None:
+                continue
+            got, gdist = index.search(dq, a.k, metric, nprobe=a.nprobe)
+            got2, gdist2 = index.search(dq, a.k, metric, nprobe=a.nprobe)
+            same_bits = bool(torch.equal(got, got2) and torch.equal(gdist.view(torch.int32), gdist2.view(torch.int32)))
+            full, fdist = index.search(dq, a.k, metric, nprobe=a.nlist)
+            all_lists = bool(torch.equal(full, ids) and torch.equal(fdist.view(torch.int32), dist.view(torch.int32)))
+            r, n, h = metrics(got, truth, a.k)
+            vs_flat = (got[:, :, None] == ids[:, None, :]).any(1).float().mean().item()
+            print("%s %s  ivf nlist %d nprobe %d  recall@%d %.4f  ndcg@%d %.4f  hit rate %.4f  recall vs exact %.4f  "
+                  "two runs same bits: %s  every list probed == exact search: %s"
+                  % (task, metric, a.nlist, a.nprobe, a.k, r, a.k, n, h, vs_flat, same_bits, all_lists))
+            ok = ok and same_bits and all_lists
     if not ok:
         print("FAILED")
         return 1

@@ -551,3 +551,6 @@ extern "C" int glx_knn_merge(int device, int metric, int32_t num_parts, const in
   }
   return st.finish(rc);
 }
+
+// ---- the IVF-Flat index over the same contract: glx_knn_ivf_build / _search / _info / _export / _destroy
+#include "glx_knn_ivf.h"

@@ -47,6 +47,7 @@ EXPORTS = [
     "glx_features_create", "glx_features_view", "glx_features_destroy", "glx_features_info",
     "glx_features_create_ex", "glx_features_view_ex", "glx_features_dtype",
     "glx_knn_search", "glx_knn_merge",
+    "glx_knn_ivf_build", "glx_knn_ivf_search", "glx_knn_ivf_info", "glx_knn_ivf_export", "glx_knn_ivf_destroy",
     "glx_aggregate", "glx_lookup", "glx_aggregate_arg", "glx_aggregate_backward",
     "glx_aggregate_weighted", "glx_aggregate_weighted_backward_x", "glx_aggregate_weighted_backward_w",
     "glx_segment_softmax", "glx_segment_softmax_backward",
@@ -275,6 +276,13 @@ def lib():
         L.glx_tune.argtypes = [ctypes.c_char_p, i32]
         L.glx_knn_search.argtypes = [vp, ci, vp, i32, i32, vp, vp, ci, vp]
         L.glx_knn_merge.argtypes = [ci, ci, i32, vp, vp, i32, i32, vp, vp, ci, vp]
+        L.glx_knn_ivf_build.argtypes = [vp, i32, i32, i64, vp, ci, vp, ctypes.POINTER(vp)]
+        L.glx_knn_ivf_search.argtypes = [vp, ci, vp, i32, i32, i32, vp, vp, ci, vp]
+        L.glx_knn_ivf_info.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i64),
+                                       ctypes.POINTER(i64), ctypes.POINTER(i64)]
+        L.glx_knn_ivf_export.argtypes = [vp, vp, vp, vp, ci, vp]
+        L.glx_knn_ivf_destroy.argtypes = [vp]
+        L.glx_knn_ivf_destroy.restype = None
         L.glx_unique.argtypes = [ci, vp, vp, i32, vp, vp, vp, ci, vp]
         L.glx_columns_create.argtypes = [ci, i64, i32, vp, vp, vp, vp, vp, vp, ci, vp, ctypes.POINTER(vp)]
         L.glx_columns_destroy.argtypes = [vp]
@@ -765,8 +773,89 @@ class Features:
                                     _stream(kind, self.device)))
         return ids, dist
 
+    def build_ivf(self, nlist, niter=10, train_rows=None, centroids=None):
+        """An IVF-Flat index over this table (glx_knn_ivf_build) -> KnnIvf.  nlist lists, niter Lloyd iterations over a
+        sample of train_rows rows (None: min(num_rows, 256 * nlist)), starting from centroids[nlist, D] float32 (numpy
+        or a torch CUDA tensor) when given, else from evenly spaced sample rows; niter=0 with centroids only assigns.
+        The build is deterministic.  The index keeps this table alive."""
+        return KnnIvf(self, nlist, niter, train_rows, centroids)
+
 
 KNN_METRICS = {"l2": 0, "ip": 1}  # GLX_KNN_L2, GLX_KNN_IP
+
+
+class KnnIvf:
+    """IVF-Flat index over a Features table (glx_knn_ivf): centroids and inverted lists on the device, scores from the
+    table itself.  search(..., nprobe=nlist) equals Features.search bit for bit; with fewer lists probed it equals the
+    exact search restricted to the probed lists' rows."""
+
+    def __init__(self, features, nlist, niter=10, train_rows=None, centroids=None):
+        self._h = None
+        nlist, niter = int(nlist), int(niter)
+        if centroids is not None and (centroids.ndim != 2 or tuple(centroids.shape) != (nlist, features.dim)):
+            raise ValueError("centroids must be [{}, {}], not {}".format(nlist, features.dim, tuple(centroids.shape)))
+        if _is_torch(centroids):
+            import torch
+            assert centroids.dtype == torch.float32, centroids.dtype
+        pc = _ptr(centroids, None if _is_torch(centroids) else np.float32)
+        kind = PTR_HOST if pc[1] is None else pc[1]
+        h = ctypes.c_void_p()
+        _check(lib().glx_knn_ivf_build(features._h, nlist, niter, 0 if train_rows is None else int(train_rows), pc[0],
+                                       kind, _stream(kind, features.device), ctypes.byref(h)))
+        self._h = h
+        self.features = features  # the lists index its rows: keep it alive
+        self.device = features.device
+        self.nlist, self.dim, self.num_rows = nlist, features.dim, features.num_rows
+
+    def close(self):
+        if getattr(self, "_h", None):
+            try:
+                lib().glx_knn_ivf_destroy(self._h)
+            except Exception:  # interpreter shutdown
+                pass
+            self._h = None
+
+    __del__ = close
+
+    def info(self):
+        """-> dict(nlist, dim, num_rows, longest_list, device_bytes)"""
+        nl, d = ctypes.c_int32(), ctypes.c_int32()
+        n, longest, nbytes = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        _check(lib().glx_knn_ivf_info(self._h, ctypes.byref(nl), ctypes.byref(d), ctypes.byref(n), ctypes.byref(longest),
+                                      ctypes.byref(nbytes)))
+        return {"nlist": nl.value, "dim": d.value, "num_rows": n.value, "longest_list": longest.value,
+                "device_bytes": nbytes.value}
+
+    def centroids(self):
+        """-> centroids[nlist, D] float32 (numpy)"""
+        out = np.empty((self.nlist, self.dim), np.float32)
+        _check(lib().glx_knn_ivf_export(self._h, _ptr(out)[0], None, None, PTR_HOST, None))
+        return out
+
+    def lists(self):
+        """-> (list_ptr[nlist + 1], list_rows[num_rows]) int64 (numpy): list l holds the storage rows
+        list_rows[list_ptr[l]:list_ptr[l + 1]], ascending"""
+        ptr, rows = np.empty(self.nlist + 1, np.int64), np.empty(self.num_rows, np.int64)
+        _check(lib().glx_knn_ivf_export(self._h, None, _ptr(ptr)[0], _ptr(rows)[0], PTR_HOST, None))
+        return ptr, rows
+
+    def search(self, queries, k, metric="ip", nprobe=1, out=None):
+        """The k best rows of every query among the rows of its nprobe best lists (glx_knn_ivf_search) ->
+        (ids[n, k] int64, dist[n, k] float32), best first, under Features.search's contract: the same chain, order, ids
+        and padding (slots beyond the probed lists' rows hold id -1).  nprobe == nlist probes every list and equals
+        Features.search bit for bit; otherwise 1 <= nprobe <= min(nlist, 1024).  Numpy in, numpy out; torch CUDA tensors
+        in, torch CUDA tensors out on the current stream, nothing read back.  out=(ids, dist): buffers to write into."""
+        if metric not in KNN_METRICS:
+            raise ValueError("metric must be one of {}, not {!r}".format(sorted(KNN_METRICS), metric))
+        if queries.ndim != 2 or int(queries.shape[1]) != self.dim:
+            raise ValueError("queries must be [n, {}], not {}".format(self.dim, tuple(queries.shape)))
+        n, k = int(queries.shape[0]), int(k)
+        ids, dist = _knn_out(out, queries, n, k)
+        pq, pi, pd = _ptr(queries, None if _is_torch(queries) else np.float32), _ptr(ids), _ptr(dist)
+        kind = _kind(pq, pi, pd)
+        _check(lib().glx_knn_ivf_search(self._h, KNN_METRICS[metric], pq[0], n, k, int(nprobe), pi[0], pd[0], kind,
+                                        _stream(kind, self.device)))
+        return ids, dist
 
 
 def _knn_out(out, like, n, k):

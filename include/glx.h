@@ -44,7 +44,8 @@ extern "C" {
  * glx_segment_softmax_backward; pair scores -- glx_pair_dot, glx_pair_dot_backward; trainable embedding tables --
  * glx_rows_coalesce, glx_embedding_update; fused GAT attention -- glx_gat_attention, glx_gat_attention_backward; fused
  * dot-product attention -- glx_dot_attention, glx_dot_attention_backward; exact KNN search -- GLX_KNN_*, glx_knn_search,
- * glx_knn_merge; TGN memory -- glx_tgn_store_update, glx_tgn_message, glx_tgn_message_backward, glx_tgn_memory_write. */
+ * glx_knn_merge; TGN memory -- glx_tgn_store_update, glx_tgn_message, glx_tgn_message_backward, glx_tgn_memory_write;
+ * IVF-Flat index -- glx_knn_ivf_build, glx_knn_ivf_search, glx_knn_ivf_info, glx_knn_ivf_export, glx_knn_ivf_destroy. */
 #define GLX_ABI_VERSION 5
 
 /* Exported symbols: libglx.so is built with -fvisibility=hidden. */
@@ -461,6 +462,53 @@ GLX_API int glx_knn_search(const glx_features* f, int metric, const float* queri
 GLX_API int glx_knn_merge(int device, int metric, int32_t num_parts, const int64_t* ids, const float* dist,
                           int32_t num_queries, int32_t k, int64_t* ids_out, float* dist_out, int ptr_kind,
                           void* stream);
+
+/* ---- IVF-Flat index: probed KNN search, the reference's IndexOption(index_type = "ivfflat", nlist, nprobe) --
+ * IVFFlatKnnIndex (contrib/knn/ivfflat_index.cc:25-55) as the index factory makes it (contrib/knn/index_factory.cc:32-34)
+ * -- without faiss and without a second copy of the table.  A glx_knn_ivf belongs to ONE glx_features table of N rows
+ * (float32 / bfloat16 / float16, owned or a view, id-mapped, swizzled: whatever glx_knn_search serves), which must
+ * outlive it.  It holds centroids [nlist, dim] float32, list_ptr [nlist + 1] and list_rows [N]: the storage rows of every
+ * list, ascending within a list, 4 bytes each; every row is in exactly one list.  Scores always come from the table
+ * itself: a returned dist is the contract distance of that row as the table holds it at the call (an index over a view
+ * whose rows changed since the build has stale lists, never stale distances).
+ * Build (deterministic: no RNG, no float atomic; two builds give the same bits):
+ *   sample   T = train_rows clamped to [nlist, N]; train_rows = 0 means min(N, 256 * nlist).  Sample element t is
+ *            storage row floor(t * N / T), upcast exactly to float32.
+ *   start    centroids_init [nlist, dim] float32 (host or device by ptr_kind) when given, else sample element
+ *            floor(i * T / nlist) for centroid i.
+ *   assign   a row goes to its first centroid under glx_knn_search's contract with GLX_KNN_L2, k = 1, the row as the
+ *            query and the centroids as the table: the nearest, a tie to the lower centroid, NaN distances last by
+ *            centroid.
+ *   update   niter (>= 0) Lloyd iterations, each an assign of the sample followed by: a centroid with n >= 1 sample
+ *            rows becomes acc / (float)n where acc = +0.0f and then acc = fadd_rn(acc, row) in ascending storage row
+ *            (the bits of glx_aggregate's MeanAggregator over those rows); a centroid with no row keeps its value.
+ *   lists    all N rows are assigned against the final centroids; list_rows is the stable sort of the rows by list.
+ *            niter = 0 with centroids_init is "assign only".
+ *   limits   1 <= nlist <= min(N, 65536), niter >= 0, train_rows >= 0; synchronises `stream` before it returns.
+ * Search: the probe set of a query is every list when nprobe == nlist (no coarse step), else the lists that
+ * glx_knn_search names for the query over the centroids with k = nprobe under the search's own metric, in that order
+ * (1 <= nprobe <= 1024 then).  The result is the k best rows among the rows of the probed lists under glx_knn_search's
+ * contract word for word -- the same ip chain, the same L2 formula with the same qn / xn, a better dist first, then the
+ * smaller storage row, NaN last by row, ids by the table's row -> id rule, slots beyond the number of candidates
+ * id = -1 and dist = -inf (IP) / +inf (L2).  Hence nprobe == nlist equals glx_knn_search bit for bit, and because the
+ * probe sets are nested in nprobe the set of true top-k rows a search finds never shrinks as nprobe grows.
+ * Limits (else GLX_INVALID_ARGUMENT): 1 <= k <= 1024; 1 <= nprobe <= nlist; num_queries >= 0 (0 is a no-op success);
+ * num_queries * k < 2^31 and num_queries * nprobe < 2^31; float32 queries; one GPU; not under graph capture.  No float
+ * atomics and no counters: the same inputs give the same bits on every call.  glx_tune "knn_query_block" may shrink
+ * the queries served per pass (never grow them past the 256 MiB workspace budget); the bits do not depend on it.
+ * glx_knn_ivf_info: any output may be NULL; longest_list in rows; device_bytes of centroids + list_ptr + list_rows.
+ * glx_knn_ivf_export: centroids_out [nlist, dim] float32, list_ptr_out [nlist + 1] int64, list_rows_out [N] int64, to
+ * host or device by ptr_kind; any of them may be NULL. */
+typedef struct glx_knn_ivf glx_knn_ivf;
+GLX_API int glx_knn_ivf_build(const glx_features* f, int32_t nlist, int32_t niter, int64_t train_rows,
+                              const float* centroids_init, int ptr_kind, void* stream, glx_knn_ivf** out);
+GLX_API int glx_knn_ivf_search(const glx_knn_ivf* index, int metric, const float* queries, int32_t num_queries, int32_t k,
+                               int32_t nprobe, int64_t* ids_out, float* dist_out, int ptr_kind, void* stream);
+GLX_API int glx_knn_ivf_info(const glx_knn_ivf* index, int32_t* nlist, int32_t* dim, int64_t* num_rows,
+                             int64_t* longest_list, int64_t* device_bytes);
+GLX_API int glx_knn_ivf_export(const glx_knn_ivf* index, float* centroids_out, int64_t* list_ptr_out,
+                               int64_t* list_rows_out, int ptr_kind, void* stream);
+GLX_API void glx_knn_ivf_destroy(glx_knn_ivf* index);
 
 /* ---- aggregation: replaces Aggregator::Aggregate (aggregator.cc:25-59) with
  * Sum/Mean/Max/Min/Prod Init/Agg/Final (sum_aggregator.cc:25-33,
