@@ -52,9 +52,185 @@ __global__ void glx_seg_reset_kernel(unsigned long long* words) {  // captured l
   words[1] = 0;
 }
 
-__global__ __launch_bounds__(256) void glx_seg_scan_kernel(const int32_t* __restrict__ seg, int32_t n, int32_t num_segments,
-                                                           int32_t f, unsigned long long* __restrict__ words, uint32_t epoch,
-                                                           int32_t* __restrict__ seg_start) {
+// The scan's partition of a request (round 25; tests/test_seg_scan_partition_cpu.py restates it).  A workgroup walks the
+// request grid-stride in TILES of kSegScanTile ids.  Within a tile a thread issues kSegScanLoads independent 16-byte
+// loads before it uses any: load instruction L of the tile covers the ids [L kSegScanSpan, (L + 1) kSegScanSpan) of the
+// tile, thread t its quad [4 t, 4 t + 4) of those, so consecutive lanes read consecutive 16 bytes and a wave reads 1 KiB
+// per instruction, 4 KiB per tile.  The id before a quad comes from the lane below (a cross-lane read of its last id);
+// only lane 0 of a wave loads it from memory, once per load instruction.  The tile at the end of the request, and every
+// tile of a `seg` that is not 16-byte aligned, loads its ids one by one (the same partition, the same cross-lane read).
+constexpr int kSegScanThreads = 256;
+constexpr int kSegScanLoads = 4;
+constexpr int32_t kSegScanSpan = kSegScanThreads * 4;
+constexpr int32_t kSegScanTile = kSegScanSpan * kSegScanLoads;
+constexpr int kSegScanWgPerCu = 8;  // grid = this many workgroups per CU of the device at most: every wave slot, once
+
+// (quo, rem) = (i / f, i % f) of a position, moved on by a distance whose own (d / f, d % f) the caller holds:
+// no division per id, one per thread for the start and two (uniform) for the distances
+__device__ __forceinline__ void seg_counters_advance(uint32_t& quo, uint32_t& rem, uint32_t dq, uint32_t dr, uint32_t f) {
+  quo += dq;
+  rem += dr;  // < 2 f <= 2^32 - 2
+  if (rem >= f) {
+    rem -= f;
+    ++quo;
+  }
+}
+
+// what a thread carries from tile to tile: the counters of its next quad with the distances that move them on, and what it
+// found so far (raised once per wave behind the walk)
+struct SegScanCarry {
+  uint32_t quo, rem, span_q, span_r, wrap_q, wrap_r;  // unused when f == 0
+  int32_t level, bad_at;
+};
+
+// One tile.  WHOLE: every quad of the tile is inside the request and `seg` is 16-byte aligned -- one 16-byte load per
+// quad; else id by id.  (Two instantiations, not a branch per load: behind a branch the compiler waited for each load
+// where the two sides met, and the loads of a tile went out one after the other.)
+template <bool WHOLE>
+__device__ __forceinline__ void seg_scan_tile(const int32_t* __restrict__ seg, int32_t n, int32_t num_segments, int32_t f,
+                                              int64_t t0, int lane, SegScanCarry& c, int32_t* __restrict__ seg_start) {
+  const uint32_t uf = (uint32_t)f;
+  int32_t v[kSegScanLoads][4], below[kSegScanLoads];
+#pragma unroll
+  for (int L = 0; L < kSegScanLoads; ++L) {
+    const int64_t i0 = t0 + L * kSegScanSpan + threadIdx.x * 4;
+    if (WHOLE) {
+      const int4 q = *reinterpret_cast<const int4*>(seg + i0);
+      v[L][0] = q.x; v[L][1] = q.y; v[L][2] = q.z; v[L][3] = q.w;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[L][j] = i0 + j < n ? seg[i0 + j] : 0;
+    }
+    below[L] = (lane == 0 && i0 > 0 && i0 < n) ? seg[i0 - 1] : -1;  // -1 before the first id of the request
+  }
+#pragma unroll
+  for (int L = 0; L < kSegScanLoads; ++L) {
+    const int64_t i0 = t0 + L * kSegScanSpan + threadIdx.x * 4;
+    const int32_t m = i0 >= n ? 0 : ((n - i0) < 4 ? (int32_t)(n - i0) : 4);
+    // every lane takes part in the cross-lane read; a quad that has ids has a full quad in the lane below
+    const int32_t from_lane = __shfl_up(v[L][3], 1);
+    int32_t prev = lane == 0 ? below[L] : from_lane;
+    // the id before this quad is itself out of range: a violation at or before it (its own quad reports it), so
+    // nothing from here on belongs to the request -- and `prev` is no segment to count on from.  The quad writes and
+    // reports nothing; the thread stays for its later tiles and for the wave's ballots.
+    const bool live = m > 0 && !(i0 > 0 && (prev < 0 || prev >= num_segments));
+    // The quad nearly every quad is: behind an id in range, every id its predecessor or the segment after it, and not
+    // the request's last.  Then no id is out of range (prev <= v0 <= .. <= v3 < num_segments), no run is long, and a
+    // position writes at most its own segment's entry -- straight-line code, four predicated stores.  (The general
+    // code below ran a loop per id and a loop per entry: round 25's trace showed the scan bound by the instructions
+    // it issues, some 400 per quad, not by its bytes or its wave count.)
+    const uint32_t d0 = (uint32_t)v[L][0] - (uint32_t)prev, d1 = (uint32_t)v[L][1] - (uint32_t)v[L][0],
+                   d2 = (uint32_t)v[L][2] - (uint32_t)v[L][1], d3 = (uint32_t)v[L][3] - (uint32_t)v[L][2];
+    const bool plain = (uint32_t)prev < (uint32_t)num_segments && (uint32_t)v[L][3] < (uint32_t)num_segments &&
+                       (d0 | d1 | d2 | d3) <= 1u && i0 + 4 < n;
+    if (plain) {
+      const int32_t i = (int32_t)i0;
+      if (d0) seg_start[v[L][0]] = i;
+      if (d1) seg_start[v[L][1]] = i + 1;
+      if (d2) seg_start[v[L][2]] = i + 2;
+      if (d3) seg_start[v[L][3]] = i + 3;
+      if (f > 0) {
+        uint32_t q = c.quo, r = c.rem;
+        bool nonuniform = false;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          nonuniform |= (uint32_t)v[L][j] != q;
+          const bool wraps = ++r == uf;
+          q += wraps ? 1u : 0u;
+          r = wraps ? 0u : r;
+        }
+        if (nonuniform && c.level < 1) c.level = 1;
+      }
+    } else if (live) {
+      uint32_t q = c.quo, r = c.rem;  // i / f and i % f, carried along
+      bool nonuniform = false, incomplete = false;
+      int32_t bad = n;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {  // unrolled: v[L][j] stays a register, not an indexed copy of the tile
+        if (j >= m) break;
+        const int32_t i = (int32_t)i0 + j, cur = v[L][j];
+        if (cur < 0 || cur >= num_segments || cur < prev) {  // prev == -1 before the first id
+          bad = i;
+          break;
+        }
+        if (cur != prev) {
+          if (cur - prev > kSegRunMax) incomplete = true;
+          else for (int32_t s = prev + 1; s <= cur; ++s) seg_start[s] = i;
+        }
+        if (f > 0) {
+          nonuniform |= (uint32_t)cur != q;
+          if (++r == uf) { r = 0; ++q; }
+        }
+        prev = cur;
+      }
+      if (bad == n && i0 + m == n) {  // the last ids: the segments after the last one used start (and end) at n
+        if (num_segments - prev > kSegRunMax) incomplete = true;
+        else for (int32_t s = prev + 1; s <= num_segments; ++s) seg_start[s] = n;
+      }
+      if (bad < c.bad_at) c.bad_at = bad;
+      const int32_t here = (incomplete || bad < n) ? 2 : (nonuniform ? 1 : 0);
+      if (here > c.level) c.level = here;
+    }
+    if (f > 0) {
+      if (L + 1 < kSegScanLoads) seg_counters_advance(c.quo, c.rem, c.span_q, c.span_r, uf);
+      else seg_counters_advance(c.quo, c.rem, c.wrap_q, c.wrap_r, uf);
+    }
+  }
+}
+
+__global__ __launch_bounds__(kSegScanThreads) void glx_seg_scan_kernel(const int32_t* __restrict__ seg, int32_t n,
+                                                                       int32_t num_segments, int32_t f,
+                                                                       unsigned long long* __restrict__ words, uint32_t epoch,
+                                                                       int32_t* __restrict__ seg_start) {
+  const int lane = threadIdx.x & 63;
+  const bool aligned = (reinterpret_cast<uintptr_t>(seg) & 15) == 0;
+  // the grid is at most ceil(n / kSegScanTile) workgroups, so every position below -- those past the end included --
+  // is < n + stride <= 2^31 + 2^31: 64-bit for the comparisons with n, 32-bit unsigned for the counters
+  const int64_t stride = (int64_t)gridDim.x * kSegScanTile;
+  SegScanCarry c = {0, 0, 0, 0, 0, 0, 0, n};
+  if (f > 0) {
+    const uint32_t uf = (uint32_t)f;
+    const uint32_t first = (uint32_t)blockIdx.x * (uint32_t)kSegScanTile + threadIdx.x * 4u;
+    const uint32_t wrap = (uint32_t)stride - (uint32_t)((kSegScanLoads - 1) * kSegScanSpan);  // last quad of a tile -> first of the next
+    c.quo = first / uf, c.rem = first % uf;
+    c.span_q = (uint32_t)kSegScanSpan / uf, c.span_r = (uint32_t)kSegScanSpan % uf;
+    c.wrap_q = wrap / uf, c.wrap_r = wrap % uf;
+  }
+  for (int64_t t0 = (int64_t)blockIdx.x * kSegScanTile; t0 < n; t0 += stride) {
+    if (aligned && t0 + kSegScanTile <= n) seg_scan_tile<true>(seg, n, num_segments, f, t0, lane, c, seg_start);  // uniform over the workgroup
+    else seg_scan_tile<false>(seg, n, num_segments, f, t0, lane, c, seg_start);
+  }
+  // One atomic per WAVE and word, and none once the word already says as much (round 6): a ragged request whose length
+  // divides evenly raises level 1 from nearly every thread -- 4 M atomics on one address for the headline's 16.4 M ids,
+  // which queue at the memory side: +0.78 ms on a 3.6 ms aggregate (profiles/r06/seg_ragged_probe.txt).  The words only
+  // grow, so a (coherent) read that already shows this wave's value or more makes the atomic redundant.
+  // (no thread has left: every lane of the wave is in the ballots, and lane 0 speaks for it)
+  const unsigned long long tag = (unsigned long long)epoch << 32;
+  int32_t bad_at = c.bad_at;
+  const uint64_t at2 = __ballot(c.level == 2), at1 = __ballot(c.level >= 1);
+  if (at2) {  // the first violation of the wave = the smallest bad_at (n: none, a long run of empty segments only)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const int32_t other = __shfl_xor(bad_at, o);
+      if (other < bad_at) bad_at = other;
+    }
+  }
+  const int32_t wave_level = at2 ? 2 : (at1 ? 1 : 0);
+  if (wave_level && lane == 0) {
+    if (bad_at < n) {  // the largest n - i = the first violation
+      const unsigned long long mine = tag | (uint32_t)(n - bad_at);
+      if (__hip_atomic_load(&words[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < mine) atomicMax(&words[0], mine);
+    }
+    const unsigned long long mine = tag | (uint32_t)wave_level;
+    if (__hip_atomic_load(&words[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < mine) atomicMax(&words[1], mine);
+  }
+}
+
+// The scan as it was launched through round 24 (glx_tune("seg_scan_parent", 1): same-process A/B and the equality
+// tests): one thread per quad, its own load of the id before the quad, 1 KiB per wave.
+__global__ __launch_bounds__(256) void glx_seg_scan_parent_kernel(const int32_t* __restrict__ seg, int32_t n, int32_t num_segments,
+                                                                  int32_t f, unsigned long long* __restrict__ words, uint32_t epoch,
+                                                                  int32_t* __restrict__ seg_start) {
   const int64_t i0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
   if (i0 >= n) return;
   int32_t v[4];
@@ -109,17 +285,46 @@ __global__ __launch_bounds__(256) void glx_seg_scan_kernel(const int32_t* __rest
 }
 
 // seg_start[s] = lower_bound(seg[0..valid_len), s) for every s -- only when the scan left the table incomplete.
+// The grid walks the segments grid-stride: the common case (nothing to fix) then costs a capped launch that reads the
+// level and returns, not a workgroup per 256 segments.
+constexpr int kSegFixupWgPerCu = 2;   // 256 threads each
+constexpr int kSegFixupSearches = 4;  // x 4 searches in flight per thread = a CU's 2,048 thread slots, as a full grid filled them
 __global__ void glx_seg_fixup_kernel(const int32_t* __restrict__ seg, SegState st, int32_t n, int32_t num_segments,
                                      int32_t* __restrict__ seg_start) {
   if (seg_level(st) != 2) return;
-  int32_t s = blockIdx.x * blockDim.x + threadIdx.x;
-  if (s > num_segments) return;
-  int32_t lo = 0, hi = seg_valid_len(st, n);
-  while (lo < hi) {
-    int32_t mid = lo + ((hi - lo) >> 1);
-    if (seg[mid] < s) lo = mid + 1; else hi = mid;
+  const int32_t valid_len = seg_valid_len(st, n);
+  const int64_t step = (int64_t)gridDim.x * blockDim.x;
+  // kSegFixupSearches segments a thread per pass, their searches side by side: each is a chain of dependent loads, and
+  // the capped grid has that many times fewer threads than a thread per segment had
+  for (int64_t s0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s0 <= num_segments; s0 += step * kSegFixupSearches) {
+    int32_t lo[kSegFixupSearches], hi[kSegFixupSearches];
+#pragma unroll
+    for (int k = 0; k < kSegFixupSearches; ++k) {
+      lo[k] = 0;
+      hi[k] = s0 + k * step <= num_segments ? valid_len : 0;
+    }
+    bool more = valid_len > 0;
+    while (more) {  // seg[0] exists in here: valid_len > 0
+      int32_t mid[kSegFixupSearches], at[kSegFixupSearches];
+#pragma unroll
+      for (int k = 0; k < kSegFixupSearches; ++k) {
+        mid[k] = lo[k] + ((hi[k] - lo[k]) >> 1);
+        at[k] = seg[lo[k] < hi[k] ? mid[k] : 0];
+      }
+      more = false;
+#pragma unroll
+      for (int k = 0; k < kSegFixupSearches; ++k) {
+        if (lo[k] < hi[k]) {
+          if (at[k] < s0 + k * step) lo[k] = mid[k] + 1; else hi[k] = mid[k];
+        }
+        more |= lo[k] < hi[k];
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < kSegFixupSearches; ++k) {
+      if (s0 + k * step <= num_segments) seg_start[s0 + k * step] = lo[k];
+    }
   }
-  seg_start[s] = lo;
 }
 
 // raw id -> feature row (int32, -1 = unknown id) for the hashed id map.
@@ -717,6 +922,8 @@ struct AggKnobs {
                                 // lane instead of 8-byte loads over the float32 lane-to-column map (ablation)
   std::atomic<int> repeats{0};  // GLX_AGG_REPEATS=1: Max / Min load every position of a segment, repeated rows included (ablation);
                                 // 2: first occurrences only whatever the segment length; 0 = by length (launch_agg_grp)
+  std::atomic<int> seg_parent{0};  // GLX_SEG_SCAN_PARENT=1: explicit segment_ids with the scan and fix-up launches of rounds 5..24 (A/B)
+  std::atomic<int> seg_wgs{0};     // GLX_SEG_SCAN_WGS: at most this many workgroups in the scan's grid (0 = kSegScanWgPerCu per CU)
 };
 
 AggKnobs& agg_knobs() {
@@ -738,6 +945,8 @@ AggKnobs& agg_knobs() {
     if (getenv("GLX_AGG_XCD_STRIPES")) k.stripes = env("GLX_AGG_XCD_STRIPES");
     k.chunk = env("GLX_AGG_XCD_CHUNK");
     k.half_ld16 = env("GLX_AGG_HALF_LD16");
+    k.seg_parent = env("GLX_SEG_SCAN_PARENT");
+    k.seg_wgs = env("GLX_SEG_SCAN_WGS");
     k.repeats = env("GLX_AGG_REPEATS");
   });
   return k;
@@ -1114,6 +1323,22 @@ int seg_words_for(hipStream_t s, unsigned long long** out, uint32_t* epoch) {
   *epoch = buf->epoch;
   return GLX_OK;
 }
+
+// *out = the compute units of the current device: what the bookkeeping grids are sized to.  Asked of the runtime once
+// per device (an attribute query, no stream work: allowed while a stream is being captured).
+int seg_device_cus(int* out) {
+  static std::atomic<int> known[64];
+  int dev = 0;
+  GLX_HIP(hipGetDevice(&dev));
+  int cus = (dev >= 0 && dev < 64) ? known[dev].load(std::memory_order_relaxed) : 0;
+  if (cus <= 0) {
+    GLX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    GLX_REQUIRE(cus > 0, "device %d reports %d compute units", dev, cus);
+    if (dev >= 0 && dev < 64) known[dev].store(cus, std::memory_order_relaxed);
+  }
+  *out = cus;
+  return GLX_OK;
+}
 }  // namespace
 
 // (kSegScratchExtra -- the int32 words behind seg_start[num_segments + 1] -- is declared in glx_common.h)
@@ -1147,11 +1372,28 @@ int prepare_segments(AggArgs& a, const int32_t* d_seg, int32_t num_ids, int32_t 
   const int32_t f = (num_segments > 0 && num_ids > 0 && num_ids % num_segments == 0) ? num_ids / num_segments : 0;
   st.words = words;
   st.floor_level = num_ids == 0 ? 2 : (f > 0 ? 0 : 1);
-  if (num_ids > 0) {
-    glx_seg_scan_kernel<<<(unsigned)(((int64_t)num_ids + 1023) / 1024), 256, 0, s>>>(d_seg, num_ids, num_segments, f, words,
-                                                                                   st.epoch, seg_start);
+  const bool parent = agg_knobs().seg_parent.load(std::memory_order_relaxed) != 0;
+  int64_t fixup_grid = ((int64_t)num_segments + 1 + 255) / 256;
+  if (parent) {
+    if (num_ids > 0) {
+      glx_seg_scan_parent_kernel<<<(unsigned)(((int64_t)num_ids + 1023) / 1024), 256, 0, s>>>(d_seg, num_ids, num_segments, f,
+                                                                                            words, st.epoch, seg_start);
+    }
+  } else {
+    int cus = 0;
+    int rc = seg_device_cus(&cus);
+    if (rc != GLX_OK) return rc;
+    if (num_ids > 0) {
+      // a few workgroups per CU that walk the request in tiles: a wave moves 4 KiB per tile, not 1 KiB in its life
+      int64_t grid = ((int64_t)num_ids + kSegScanTile - 1) / kSegScanTile;  // never more: the kernel's 32-bit counters
+      if (grid > (int64_t)cus * kSegScanWgPerCu) grid = (int64_t)cus * kSegScanWgPerCu;
+      const int cap = agg_knobs().seg_wgs.load(std::memory_order_relaxed);
+      if (cap > 0 && grid > cap) grid = cap;
+      glx_seg_scan_kernel<<<(unsigned)grid, kSegScanThreads, 0, s>>>(d_seg, num_ids, num_segments, f, words, st.epoch, seg_start);
+    }
+    if (fixup_grid > (int64_t)cus * kSegFixupWgPerCu) fixup_grid = (int64_t)cus * kSegFixupWgPerCu;
   }
-  glx_seg_fixup_kernel<<<(unsigned)((num_segments + 1 + 255) / 256), 256, 0, s>>>(d_seg, st, num_ids, num_segments, seg_start);
+  glx_seg_fixup_kernel<<<(unsigned)fixup_grid, 256, 0, s>>>(d_seg, st, num_ids, num_segments, seg_start);
   a.seg_start = seg_start;
   a.seg_state = st;
   return GLX_OK;
@@ -1323,6 +1565,8 @@ extern "C" int glx_tune(const char* name, int32_t value) {
   else if (strcmp(name, "agg_xcd_chunk") == 0) slot = &k.chunk;
   else if (strcmp(name, "agg_half_ld16") == 0) slot = &k.half_ld16;
   else if (strcmp(name, "agg_repeats") == 0) slot = &k.repeats;
+  else if (strcmp(name, "seg_scan_parent") == 0) slot = &k.seg_parent;
+  else if (strcmp(name, "seg_scan_wgs") == 0) slot = &k.seg_wgs;
   else if (strcmp(name, "seg_epochs_before_wrap") == 0) {
     // test aid: the calling thread's segment-word buffers hand out `value` more epochs before their counter wraps
     GLX_REQUIRE(value >= 0, "seg_epochs_before_wrap must be >= 0");

@@ -1411,7 +1411,9 @@ GLX_API int glx_probe_bandwidth(int device, int kind, int64_t bytes, int64_t uni
  * product's default.  Names: "agg_mfma" (GLX_AGG_MFMA), "agg_unroll" (GLX_AGG_UNROLL), "agg_slices" (GLX_AGG_SLICES),
  * "agg_legacy" (GLX_AGG_LEGACY), "agg_segs" (GLX_AGG_SEGS), "agg_xcd_slices" (GLX_AGG_XCD_SLICES), "agg_occupancy"
  * (GLX_AGG_OCCUPANCY), "agg_store" (GLX_AGG_STORE), "agg_repeats" (GLX_AGG_REPEATS: Max / Min load every position of a
- * segment = 1, only the first occurrence of every row = 2, by segment length = 0).  Results are
+ * segment = 1, only the first occurrence of every row = 2, by segment length = 0); of the bookkeeping of explicit
+ * segment_ids: "seg_scan_parent" (GLX_SEG_SCAN_PARENT = 1: the scan and fix-up launches of a thread per four ids and per
+ * segment), "seg_scan_wgs" (GLX_SEG_SCAN_WGS: at most this many workgroups in the scan's grid).  Results are
  * bit-identical under every setting.  Unknown name: GLX_INVALID_ARGUMENT.
  * Test knobs of the side paths, same rules, -1 restores the default: "cond_sequential" (GLX_COND_SEQUENTIAL),
  * "dist_no_bitmap" (GLX_DIST_NO_BITMAP), "filter_span_cap" (GLX_FILTER_SPAN_CAP), "filter_dedup_min_rows"
