@@ -16,10 +16,17 @@ search through it with --nprobe lists probed: one more line per search with the 
 against the exact search's ids.  The index scores rows from the same table with the same chain, so what it returns are
 exact distances; what it can miss are rows in lists it did not probe.
 
-Exits non-zero unless two runs give the same bits and the ids equal the float64 brute force (with --index ivf: and two
-index searches give the same bits, and the index with every list probed equals the exact search bit for bit).
+--index ivfpq builds an IVF-PQ index on top of that one (glx.KnnIvf.build_pq, --m sub-quantisers of 256 codewords) and
+adds a third line per search next to the IVF-Flat one: the probed lists are scanned through --m bytes of codes per row,
+and the --refine best candidates by the coded score are re-scored from the table (--refine 0 returns the coded ranking
+itself).  With --refine > 0 the distances it returns are exact too; what it can miss in addition are rows the coded score
+ranked below the first --refine.
+
+Exits non-zero unless two runs give the same bits and the ids equal the float64 brute force (with --index ivf or ivfpq:
+and two index searches give the same bits, and the index with every list probed equals the exact search bit for bit;
+with --index ivfpq and --refine > 0: and every distance the coded index returns is the exact search's for that id).
 Usage: python examples/eval_recall.py [--items 4000] [--users 1000] [--dim 16] [--k 10]
-                                      [--index flat|ivf] [--nlist 64] [--nprobe 4]"""
+                                      [--index flat|ivf|ivfpq] [--nlist 64] [--nprobe 4] [--m 4] [--refine 100]"""
 import argparse
 import math
 import os
@@ -68,14 +75,17 @@ def main():
     ap.add_argument("--dim", type=int, default=16)
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--group", type=int, default=5)
-    ap.add_argument("--index", choices=("flat", "ivf"), default="flat")
+    ap.add_argument("--index", choices=("flat", "ivf", "ivfpq"), default="flat")
     ap.add_argument("--nlist", type=int, default=64)
     ap.add_argument("--nprobe", type=int, default=4)
+    ap.add_argument("--m", type=int, default=4)
+    ap.add_argument("--refine", type=int, default=100)
     a = ap.parse_args()
     rng = np.random.default_rng(0)
     items, item_ids, users, user_group = planted(rng, a.items, a.users, a.dim, a.group)
     table = glx.Features(items, ids=item_ids)
-    index = table.build_ivf(a.nlist) if a.index == "ivf" else None
+    index = table.build_ivf(a.nlist) if a.index in ("ivf", "ivfpq") else None
+    coded = index.build_pq(a.m) if a.index == "ivfpq" else None
     d_ids = torch.from_numpy(item_ids).cuda()
     group_rows = torch.arange(items.shape[0], device="cuda").view(-1, a.group)
     ok = True
@@ -105,6 +115,28 @@ def main():
                   "two runs same bits: %s  every list probed == exact search: %s"
                   % (task, metric, a.nlist, a.nprobe, a.k, r, a.k, n, h, vs_flat, same_bits, all_lists))
             ok = ok and same_bits and all_lists
+            if coded is None:
+                continue
+            pids, pdist = coded.search(dq, a.k, metric, nprobe=a.nprobe, refine=a.refine)
+            pids2, pdist2 = coded.search(dq, a.k, metric, nprobe=a.nprobe, refine=a.refine)
+            same_bits = bool(torch.equal(pids, pids2) and torch.equal(pdist.view(torch.int32), pdist2.view(torch.int32)))
+            r, n, h = metrics(pids, truth, a.k)
+            vs_flat = (pids[:, :, None] == ids[:, None, :]).any(1).float().mean().item()
+            vs_ivf = ((pids[:, :, None] == got[:, None, :]) & (got[:, None, :] >= 0)).any(1).float().mean().item()
+            print("%s %s  ivfpq nlist %d nprobe %d m %d refine %d  recall@%d %.4f  ndcg@%d %.4f  hit rate %.4f  "
+                  "recall vs exact %.4f (ivf %.4f)  recall vs ivf %.4f  two runs same bits: %s"
+                  % (task, metric, a.nlist, a.nprobe, a.m, a.refine, a.k, r, a.k, n, h, vs_flat,
+                     (got[:, :, None] == ids[:, None, :]).any(1).float().mean().item(), vs_ivf, same_bits), end="")
+            ok = ok and same_bits
+            if a.refine > 0:  # re-ranked distances are the exact search's: look each returned id up in a full search
+                all_ids, all_dist = table.search(dq, min(items.shape[0], 1024), metric)
+                at = (pids[:, :, None] == all_ids[:, None, :])
+                found = at.any(2) & (pids >= 0)
+                exact_d = (at.float() * torch.nan_to_num(all_dist)[:, None, :]).sum(2)
+                same_d = bool(torch.equal(exact_d[found], torch.nan_to_num(pdist)[found]))
+                print("  returned distances == exact search's: %s" % same_d, end="")
+                ok = ok and same_d
+            print()
     if not ok:
         print("FAILED")
         return 1

@@ -554,3 +554,6 @@ extern "C" int glx_knn_merge(int device, int metric, int32_t num_parts, const in
 
 // ---- the IVF-Flat index over the same contract: glx_knn_ivf_build / _search / _info / _export / _destroy
 #include "glx_knn_ivf.h"
+
+// ---- the IVF-PQ index on top of it: glx_knn_ivfpq_build / _search / _info / _export / _destroy
+#include "glx_knn_ivfpq.h"

@@ -309,6 +309,44 @@ int knn_ivf_assign(const glx_knn_ivf* ix, int64_t T, int64_t chunk, float* stage
   return GLX_OK;
 }
 
+// ix->cview = a float32 view of ix->centroids for knn_search_device
+void knn_ivf_set_view(glx_knn_ivf* ix) {
+  memset(static_cast<void*>(&ix->cview), 0, sizeof(ix->cview));
+  ix->cview.device = ix->device;
+  ix->cview.num_rows = ix->nlist;
+  ix->cview.dim = ix->dim;
+  ix->cview.stride = ix->dim;
+  ix->cview.X = ix->centroids;
+  ix->cview.dtype = GLX_DTYPE_F32;
+  ix->cview.elem_size = 4;
+}
+
+// ix->centroids (allocated, viewed by ix->cview) = the start, then niter Lloyd iterations over the T-element sample of
+// ix->f.  stage [chunk, dim], dist [chunk] and assign [>= T] are the caller's.  (The IVF-PQ build trains its codebooks
+// through this too: a codebook is the centroids of a float32 table of residual sub-vectors.)
+int knn_ivf_train_device(glx_knn_ivf* ix, int32_t niter, int64_t T, const float* centroids_init, int ptr_kind,
+                         int64_t chunk, float* stage, float* dist, int64_t* assign, hipStream_t s) {
+  const int32_t nlist = ix->nlist, dim = ix->dim;
+  const KnnTable t = knn_ivf_table(ix->f);
+  if (centroids_init != nullptr) {
+    GLX_HIP(hipMemcpyAsync(ix->centroids, centroids_init, (size_t)nlist * dim * sizeof(float),
+                           ptr_kind == GLX_PTR_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
+  } else {
+    knn_ivf_stage_kernel<<<(unsigned)(((int64_t)nlist * dim + 255) / 256), 256, 0, s>>>(t, 0, nlist, T, nlist,
+                                                                                         ix->centroids);
+  }
+  for (int32_t it = 0; it < niter; ++it) {
+    int rc = knn_ivf_assign(ix, T, chunk, stage, dist, assign, s);
+    if (rc != GLX_OK) return rc;
+    GlxScratch lease;
+    GlxAggTranspose tr;
+    rc = glx_agg_transpose(assign, nullptr, (int32_t)T, 1, nlist, s, &lease, &tr);
+    if (rc != GLX_OK) return rc;
+    knn_ivf_update_kernel<<<(unsigned)((nlist + 3) / 4), 256, 0, s>>>(t, T, tr.row_ptr, tr.pos, nlist, ix->centroids);
+  }
+  return GLX_OK;
+}
+
 int knn_ivf_build_device(glx_knn_ivf* ix, int32_t niter, int64_t train_rows, const float* centroids_init, int ptr_kind,
                          hipStream_t s) {
   const glx_features* const f = ix->f;
@@ -320,15 +358,7 @@ int knn_ivf_build_device(glx_knn_ivf* ix, int32_t niter, int64_t train_rows, con
   GLX_HIP(hipMalloc(&ix->centroids, (size_t)nlist * dim * sizeof(float)));
   GLX_HIP(hipMalloc(&ix->list_ptr, (size_t)(nlist + 1) * sizeof(int32_t)));
   GLX_HIP(hipMalloc(&ix->list_rows, (size_t)N * sizeof(int32_t)));
-  memset(static_cast<void*>(&ix->cview), 0, sizeof(ix->cview));
-  ix->cview.device = ix->device;
-  ix->cview.num_rows = nlist;
-  ix->cview.dim = dim;
-  ix->cview.stride = dim;
-  ix->cview.X = ix->centroids;
-  ix->cview.dtype = GLX_DTYPE_F32;
-  ix->cview.elem_size = 4;
-  const KnnTable t = knn_ivf_table(f);
+  knn_ivf_set_view(ix);
   int64_t chunk = (int64_t)(kIvfStageBytes / ((size_t)dim * sizeof(float)));
   if (chunk < 1) chunk = 1;
   if (chunk > N) chunk = N;
@@ -336,23 +366,9 @@ int knn_ivf_build_device(glx_knn_ivf* ix, int32_t niter, int64_t train_rows, con
   GLX_HIP(hipMalloc(&stage.p, (size_t)chunk * dim * sizeof(float)));
   GLX_HIP(hipMalloc(&dist.p, (size_t)chunk * sizeof(float)));
   GLX_HIP(hipMalloc(&assign.p, (size_t)N * sizeof(int64_t)));
-  if (centroids_init != nullptr) {
-    GLX_HIP(hipMemcpyAsync(ix->centroids, centroids_init, (size_t)nlist * dim * sizeof(float),
-                           ptr_kind == GLX_PTR_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
-  } else {
-    knn_ivf_stage_kernel<<<(unsigned)(((int64_t)nlist * dim + 255) / 256), 256, 0, s>>>(t, 0, nlist, T, nlist,
-                                                                                         ix->centroids);
-  }
-  int rc;
-  for (int32_t it = 0; it < niter; ++it) {
-    rc = knn_ivf_assign(ix, T, chunk, stage.as<float>(), dist.as<float>(), assign.as<int64_t>(), s);
-    if (rc != GLX_OK) return rc;
-    GlxScratch lease;
-    GlxAggTranspose tr;
-    rc = glx_agg_transpose(assign.as<int64_t>(), nullptr, (int32_t)T, 1, nlist, s, &lease, &tr);
-    if (rc != GLX_OK) return rc;
-    knn_ivf_update_kernel<<<(unsigned)((nlist + 3) / 4), 256, 0, s>>>(t, T, tr.row_ptr, tr.pos, nlist, ix->centroids);
-  }
+  int rc = knn_ivf_train_device(ix, niter, T, centroids_init, ptr_kind, chunk, stage.as<float>(), dist.as<float>(),
+                                assign.as<int64_t>(), s);
+  if (rc != GLX_OK) return rc;
   rc = knn_ivf_assign(ix, N, chunk, stage.as<float>(), dist.as<float>(), assign.as<int64_t>(), s);
   if (rc != GLX_OK) return rc;
   std::vector<int32_t> ptr((size_t)nlist + 1);

@@ -48,6 +48,8 @@ EXPORTS = [
     "glx_features_create_ex", "glx_features_view_ex", "glx_features_dtype",
     "glx_knn_search", "glx_knn_merge",
     "glx_knn_ivf_build", "glx_knn_ivf_search", "glx_knn_ivf_info", "glx_knn_ivf_export", "glx_knn_ivf_destroy",
+    "glx_knn_ivfpq_build", "glx_knn_ivfpq_search", "glx_knn_ivfpq_info", "glx_knn_ivfpq_export",
+    "glx_knn_ivfpq_destroy",
     "glx_aggregate", "glx_lookup", "glx_aggregate_arg", "glx_aggregate_backward",
     "glx_aggregate_weighted", "glx_aggregate_weighted_backward_x", "glx_aggregate_weighted_backward_w",
     "glx_segment_softmax", "glx_segment_softmax_backward",
@@ -283,6 +285,13 @@ def lib():
         L.glx_knn_ivf_export.argtypes = [vp, vp, vp, vp, ci, vp]
         L.glx_knn_ivf_destroy.argtypes = [vp]
         L.glx_knn_ivf_destroy.restype = None
+        L.glx_knn_ivfpq_build.argtypes = [vp, i32, i32, i64, vp, ci, vp, ctypes.POINTER(vp)]
+        L.glx_knn_ivfpq_search.argtypes = [vp, ci, vp, i32, i32, i32, i32, vp, vp, ci, vp]
+        L.glx_knn_ivfpq_info.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i64),
+                                         ctypes.POINTER(i64)]
+        L.glx_knn_ivfpq_export.argtypes = [vp, vp, vp, ci, vp]
+        L.glx_knn_ivfpq_destroy.argtypes = [vp]
+        L.glx_knn_ivfpq_destroy.restype = None
         L.glx_unique.argtypes = [ci, vp, vp, i32, vp, vp, vp, ci, vp]
         L.glx_columns_create.argtypes = [ci, i64, i32, vp, vp, vp, vp, vp, vp, ci, vp, ctypes.POINTER(vp)]
         L.glx_columns_destroy.argtypes = [vp]
@@ -780,6 +789,12 @@ class Features:
         The build is deterministic.  The index keeps this table alive."""
         return KnnIvf(self, nlist, niter, train_rows, centroids)
 
+    def build_ivfpq(self, nlist, m, niter=10, train_rows=None, centroids=None, codebooks=None):
+        """An IVF-PQ index over this table -> KnnIvfPq: build_ivf(nlist, niter, train_rows, centroids) and, on top of
+        it, KnnIvf.build_pq(m, niter, train_rows, codebooks).  The returned object keeps the KnnIvf (its .ivf) and this
+        table alive."""
+        return self.build_ivf(nlist, niter, train_rows, centroids).build_pq(m, niter, train_rows, codebooks)
+
 
 KNN_METRICS = {"l2": 0, "ip": 1}  # GLX_KNN_L2, GLX_KNN_IP
 
@@ -855,6 +870,108 @@ class KnnIvf:
         kind = _kind(pq, pi, pd)
         _check(lib().glx_knn_ivf_search(self._h, KNN_METRICS[metric], pq[0], n, k, int(nprobe), pi[0], pd[0], kind,
                                         _stream(kind, self.device)))
+        return ids, dist
+
+    def build_pq(self, m, niter=10, train_rows=None, codebooks=None):
+        """An IVF-PQ index on top of this index (glx_knn_ivfpq_build) -> KnnIvfPq: m sub-quantisers of 256 codewords
+        over the rows' residuals (dim % m == 0, 1 <= m <= 64, num_rows >= 256), trained by niter Lloyd iterations over
+        a sample of train_rows rows (None: min(num_rows, 65536)), starting from codebooks[m, 256, dim / m] float32
+        (numpy or a torch CUDA tensor) when given; niter=0 with codebooks only encodes.  The build is deterministic.
+        The returned index keeps this one alive."""
+        return KnnIvfPq(self, m, niter, train_rows, codebooks)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class KnnIvfPq:
+    """IVF-PQ index on top of a KnnIvf (glx_knn_ivfpq): m codebooks and one m-byte code per row on the device.
+    search(..., refine=0) ranks the probed lists' rows by the coded (ADC) score; refine=R re-scores the R best of them
+    from the table itself, so every returned distance is Features.search's distance of that row."""
+
+    def __init__(self, ivf, m, niter=10, train_rows=None, codebooks=None):
+        self._h = None
+        m, niter = int(m), int(niter)
+        dsub = ivf.dim // m if m > 0 and ivf.dim % m == 0 else None
+        if codebooks is not None and (dsub is None or tuple(codebooks.shape) != (m, 256, dsub)):
+            raise ValueError("codebooks must be [m, 256, dim / m] = [{}, 256, {}], not {}".format(
+                m, dsub, tuple(codebooks.shape)))
+        if _is_torch(codebooks):
+            import torch
+            assert codebooks.dtype == torch.float32, codebooks.dtype
+        if not getattr(ivf, "_h", None):
+            raise ValueError("the IVF index is closed")
+        pc = _ptr(codebooks, None if _is_torch(codebooks) else np.float32)
+        kind = PTR_HOST if pc[1] is None else pc[1]
+        h = ctypes.c_void_p()
+        _check(lib().glx_knn_ivfpq_build(ivf._h, m, niter, 0 if train_rows is None else int(train_rows), pc[0], kind,
+                                         _stream(kind, ivf.device), ctypes.byref(h)))
+        self._h = h
+        self.ivf = ivf  # the codes follow its lists: keep it (and through it the table) alive
+        self.device = ivf.device
+        self.m, self.dsub, self.dim, self.num_rows = m, dsub, ivf.dim, ivf.num_rows
+
+    def close(self):
+        if getattr(self, "_h", None):
+            try:
+                lib().glx_knn_ivfpq_destroy(self._h)
+            except Exception:  # interpreter shutdown
+                pass
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _handle(self):
+        if not self._h or not self.ivf._h:
+            raise ValueError("the index is closed")
+        return self._h
+
+    def info(self):
+        """-> dict(m, dsub, num_rows, device_bytes)"""
+        m, d = ctypes.c_int32(), ctypes.c_int32()
+        n, nbytes = ctypes.c_int64(), ctypes.c_int64()
+        _check(lib().glx_knn_ivfpq_info(self._handle(), ctypes.byref(m), ctypes.byref(d), ctypes.byref(n),
+                                        ctypes.byref(nbytes)))
+        return {"m": m.value, "dsub": d.value, "num_rows": n.value, "device_bytes": nbytes.value}
+
+    def codebooks(self):
+        """-> codebooks[m, 256, dsub] float32 (numpy)"""
+        out = np.empty((self.m, 256, self.dsub), np.float32)
+        _check(lib().glx_knn_ivfpq_export(self._handle(), _ptr(out)[0], None, PTR_HOST, None))
+        return out
+
+    def codes(self):
+        """-> codes[num_rows, m] uint8 (numpy) in list order: row p is the code of storage row ivf.lists()[1][p]"""
+        out = np.empty((self.num_rows, self.m), np.uint8)
+        _check(lib().glx_knn_ivfpq_export(self._handle(), None, _ptr(out)[0], PTR_HOST, None))
+        return out
+
+    def search(self, queries, k, metric="ip", nprobe=1, refine=0, out=None):
+        """The k best rows of every query among the rows of its nprobe best lists (glx_knn_ivfpq_search) ->
+        (ids[n, k] int64, dist[n, k] float32), best first; the probe sets, ids and padding are KnnIvf.search's.
+        refine=0: ranked by the coded (ADC) score, which dist holds.  k <= refine <= 1024: the refine best by that score
+        are re-scored from the table and the k best of those returned, dist being Features.search's distance of the row
+        bit for bit.  Numpy in, numpy out; torch CUDA tensors in, torch CUDA tensors out on the current stream, nothing
+        read back.  out=(ids, dist): buffers to write into."""
+        if metric not in KNN_METRICS:
+            raise ValueError("metric must be one of {}, not {!r}".format(sorted(KNN_METRICS), metric))
+        if queries.ndim != 2 or int(queries.shape[1]) != self.dim:
+            raise ValueError("queries must be [n, {}], not {}".format(self.dim, tuple(queries.shape)))
+        n, k = int(queries.shape[0]), int(k)
+        ids, dist = _knn_out(out, queries, n, k)
+        pq, pi, pd = _ptr(queries, None if _is_torch(queries) else np.float32), _ptr(ids), _ptr(dist)
+        kind = _kind(pq, pi, pd)
+        _check(lib().glx_knn_ivfpq_search(self._handle(), KNN_METRICS[metric], pq[0], n, k, int(nprobe), int(refine),
+                                          pi[0], pd[0], kind, _stream(kind, self.device)))
         return ids, dist
 
 

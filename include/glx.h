@@ -45,7 +45,9 @@ extern "C" {
  * glx_rows_coalesce, glx_embedding_update; fused GAT attention -- glx_gat_attention, glx_gat_attention_backward; fused
  * dot-product attention -- glx_dot_attention, glx_dot_attention_backward; exact KNN search -- GLX_KNN_*, glx_knn_search,
  * glx_knn_merge; TGN memory -- glx_tgn_store_update, glx_tgn_message, glx_tgn_message_backward, glx_tgn_memory_write;
- * IVF-Flat index -- glx_knn_ivf_build, glx_knn_ivf_search, glx_knn_ivf_info, glx_knn_ivf_export, glx_knn_ivf_destroy. */
+ * IVF-Flat index -- glx_knn_ivf_build, glx_knn_ivf_search, glx_knn_ivf_info, glx_knn_ivf_export, glx_knn_ivf_destroy;
+ * IVF-PQ index -- glx_knn_ivfpq_build, glx_knn_ivfpq_search, glx_knn_ivfpq_info, glx_knn_ivfpq_export,
+ * glx_knn_ivfpq_destroy. */
 #define GLX_ABI_VERSION 5
 
 /* Exported symbols: libglx.so is built with -fvisibility=hidden. */
@@ -509,6 +511,71 @@ GLX_API int glx_knn_ivf_info(const glx_knn_ivf* index, int32_t* nlist, int32_t* 
 GLX_API int glx_knn_ivf_export(const glx_knn_ivf* index, float* centroids_out, int64_t* list_ptr_out,
                                int64_t* list_rows_out, int ptr_kind, void* stream);
 GLX_API void glx_knn_ivf_destroy(glx_knn_ivf* index);
+
+/* ---- IVF-PQ index: coded scan and exact re-rank, the reference's IndexOption(index_type = "ivfpq", nlist, nprobe, m) --
+ * IVFPQKnnIndex (contrib/knn/ivfpq_index.cc:25-56: faiss::IndexIVFPQ with 8 bits per sub-quantiser) as the index factory
+ * makes it (contrib/knn/index_factory.cc:35-37; the gpu_ivfpq form: index_factory.cc:43-45, gpu_ivfpq_index.cc:30-60)
+ * -- without faiss and without a second copy of the table.  A glx_knn_ivfpq sits on ONE glx_knn_ivf, which supplies
+ * the coarse centroids and the lists and must outlive it (and so must that index's table).  It adds m codebooks and
+ * one m-byte code per row.  "The contract" below is glx_knn_search's: the one ascending fmaf chain ip, L2 as
+ * max(0, fmaf(-2, ip, qn + xn)) with a NaN kept, and the order better dist first, then the smaller row, NaN last by row.
+ *   shape    1 <= m <= 64, dim % m == 0, dsub = dim / m; every sub-quantiser has 256 codewords (8 bits, fixed);
+ *            num_rows >= 256.  Codebooks [m, 256, dsub] float32; codes [N, m] uint8 in LIST order: position p belongs
+ *            to storage row list_rows[p] of the IVF index.
+ *   residual a row x in list l has r[c] = fsub_rn(x[c], centroid_l[c]), a half element upcast exactly first.
+ *   train    (deterministic) T = train_rows clamped to [256, N]; train_rows = 0 means min(N, 65536).  Sample element t
+ *            is storage row floor(t * N / T) (glx_knn_ivf_build's rule).  R_j is the [T, dsub] float32 matrix of the
+ *            sample's residual columns j * dsub .. (j + 1) * dsub - 1.  Codebook j is, bit for bit, the centroids that
+ *            glx_knn_ivf_build returns for a float32 table holding R_j with nlist = 256, the same niter and
+ *            train_rows = T: initial codeword i is R_j[floor(i * T / 256)], assignment is the contract's L2 search with
+ *            k = 1 (ties to the lower codeword), the update is the sequential float32 mean in ascending sample order,
+ *            an empty codeword keeps its value.  codebooks_init [m, 256, dsub] (host or device by ptr_kind) replaces
+ *            the initial codewords; codebooks_init with niter = 0 is "encode only".
+ *   encode   code j of each of the N rows is its first codeword under the contract with GLX_KNN_L2 and k = 1, the row's
+ *            residual sub-vector j as the query and codebook j as the table.
+ *   adc      the score of query q against list position p of probed list l.
+ *            GLX_KNN_IP: adc = ip(q, centroid_l), the contract chain over all dim columns, then
+ *            adc = fadd_rn(adc, lut[j][code[p][j]]) for j = 0 .. m-1 ascending; lut[j][c] is the contract ip of q's
+ *            sub-vector j with codeword c.
+ *            GLX_KNN_L2: rq[c] = fsub_rn(q[c], centroid_l[c]); adc = +0.0f, then the same ascending fadd_rn chain;
+ *            lut[j][c] is the contract L2 distance (expansion form, clamped at +0.0f, NaN kept) of rq's sub-vector j
+ *            to codeword c, the query-side norm the chain of that sub-vector with itself, the codeword norm the chain
+ *            of the codeword with itself (computed once at build).
+ *            ADC order: the contract's order applied to adc -- a better adc first, then the smaller storage row, NaN
+ *            last by row.
+ *   search   the probe sets are exactly glx_knn_ivf_search's (every list when nprobe == nlist, else the coarse search
+ *            with k = nprobe under the search's own metric).
+ *            refine = 0: the k best candidates by ADC order; dist_out holds adc (which NaN a NaN adc is, is unspecified);
+ *            ids by the table's row -> id rule; padding id = -1 with dist = -inf (IP) / +inf (L2).
+ *            k <= refine <= 1024: the R = refine best candidates by ADC order are re-scored from the TABLE with the
+ *            contract distance (the same qn / xn as glx_knn_ivf_search, xn per search for a view) and the k best of
+ *            those under glx_knn_search's order are returned with the same padding: every returned dist is the exact
+ *            search's dist of that row, bit for bit.  When the probed lists hold at most R rows the answer equals
+ *            glx_knn_ivf_search bit for bit, and with nprobe == nlist on top of that glx_knn_search.  The R best sets
+ *            are nested in R, so the set of true top-k rows found never shrinks as refine grows at a fixed nprobe.
+ *   limits   (else GLX_INVALID_ARGUMENT) 1 <= k <= 1024; refine == 0 or k <= refine <= 1024; nprobe as
+ *            glx_knn_ivf_search; num_queries >= 0 (0 is a no-op success); num_queries * max(k, refine) < 2^31; float32
+ *            queries; one GPU; not under graph capture.  glx_knn_ivfpq_build synchronises `stream` before it returns.
+ *   stale    codes, like lists, do not follow rows rewritten under a view; distances returned with refine > 0 are
+ *            still never stale.
+ * No RNG, no float atomics, no counters: the same inputs give the same bits on every call.  glx_tune "knn_query_block"
+ * may shrink the queries served per pass (the workspace stays under the flat search's 256 MiB budget); the bits do not
+ * depend on it.
+ * glx_knn_ivfpq_info: any output may be NULL; device_bytes of what the index holds on the device: the codebooks (kept
+ * twice, row-major and codeword-minor) + the codeword norms + the codes.
+ * glx_knn_ivfpq_export: codebooks_out [m, 256, dsub] float32, codes_out [N, m] uint8, to host or device by ptr_kind;
+ * either may be NULL. */
+typedef struct glx_knn_ivfpq glx_knn_ivfpq;
+GLX_API int glx_knn_ivfpq_build(const glx_knn_ivf* ivf, int32_t m, int32_t niter, int64_t train_rows,
+                                const float* codebooks_init, int ptr_kind, void* stream, glx_knn_ivfpq** out);
+GLX_API int glx_knn_ivfpq_search(const glx_knn_ivfpq* index, int metric, const float* queries, int32_t num_queries,
+                                 int32_t k, int32_t nprobe, int32_t refine, int64_t* ids_out, float* dist_out,
+                                 int ptr_kind, void* stream);
+GLX_API int glx_knn_ivfpq_info(const glx_knn_ivfpq* index, int32_t* m, int32_t* dsub, int64_t* num_rows,
+                               int64_t* device_bytes);
+GLX_API int glx_knn_ivfpq_export(const glx_knn_ivfpq* index, float* codebooks_out, uint8_t* codes_out, int ptr_kind,
+                                 void* stream);
+GLX_API void glx_knn_ivfpq_destroy(glx_knn_ivfpq* index);
 
 /* ---- aggregation: replaces Aggregator::Aggregate (aggregator.cc:25-59) with
  * Sum/Mean/Max/Min/Prod Init/Agg/Final (sum_aggregator.cc:25-33,
