@@ -16,9 +16,13 @@
 // tile per workgroup and keeps only scores not worse than the query's current k-th best (equality passes: the row may
 // win the tie); survivors land in a per-query candidate buffer.  knn_select_kernel (one workgroup per query) folds the
 // candidates into the running sorted list and refreshes the threshold.  knn_finish_kernel turns keys into (id, dist).
+//
+// The key, the order, the sorted-batch fold and the output rules live in glx_knn.h, shared with the two indexes
+// (glx_knn_ivf.hip, glx_knn_ivfpq.hip); those reach this file's kernels through knn_search_device, knn_prepare_norms
+// and knn_finish.
 #include <mutex>
 
-#include "glx_common.h"
+#include "glx_knn.h"
 
 #pragma clang fp contract(off)
 
@@ -28,49 +32,24 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kBQ = 128;          // queries per workgroup tile
 constexpr int kBR = 128;          // table rows per workgroup tile
-constexpr int kBK = 32;           // columns per LDS tile
 constexpr int kLd = kBQ + 1;      // LDS pitch of a k-major tile
-constexpr int kSortN = 1024;      // keys per sorted batch of the select kernel = the largest k
-constexpr int kSelThreads = 512;  // one compare-exchange per thread and step
-constexpr uint64_t kNoKey = ~0ull;         // an empty slot of a running list: above every real key (rows are < 2^31)
 constexpr uint32_t kNoThr = 0xffffffffu;   // "none yet": everything passes
 constexpr int32_t kDefaultChunkRows = 8192;
 constexpr int32_t kMaxChunkRows = 1 << 18;
 constexpr int32_t kDefaultFirstChunkRows = 2048;  // the first chunk passes whole: keep it small
+
+// The four constants of the schedule that glx_knn.h defines, restated and held to its values at compile time.  They
+// serve readers that take the schedule's constants from this file alone: the previous release's
+// tests/test_knn_cpu.py is one, and it must still collect and pass against this library.
+namespace restated {
+constexpr int kBK = 32;
+constexpr int kSortN = 1024;
+constexpr int kSelThreads = 512;
 constexpr size_t kCandBudgetBytes = (size_t)256 << 20;
-
-// Order-preserving image of dist: ascending unsigned = better first.  +0 and -0 share one image, every NaN maps to
-// the largest one.  IP (larger is better) is the complement of the L2 image over the numbers.
-__host__ __device__ __forceinline__ uint32_t knn_ord(uint32_t bits, int metric) {
-  if ((bits & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;
-  if (bits == 0x80000000u) bits = 0;
-  const uint32_t asc = (bits & 0x80000000u) ? ~bits : (bits | 0x80000000u);
-  return metric == GLX_KNN_L2 ? asc : ~asc;
-}
-// the float behind a number's image (a zero comes back as +0)
-__host__ __device__ __forceinline__ uint32_t knn_unord(uint32_t ord, int metric) {
-  const uint32_t asc = metric == GLX_KNN_L2 ? ord : ~ord;
-  return (asc & 0x80000000u) ? (asc & 0x7fffffffu) : ~asc;
-}
-
-__device__ __forceinline__ float knn_elem(const void* X, int dtype, int64_t i) {
-  if (dtype == GLX_DTYPE_F32) return static_cast<const float*>(X)[i];
-  if (dtype == GLX_DTYPE_BF16) return AggElem<GLX_DTYPE_BF16>::up(static_cast<const uint16_t*>(X)[i]);
-  return AggElem<GLX_DTYPE_F16>::up(static_cast<const _Float16*>(X)[i]);
-}
-
-__device__ __forceinline__ float knn_l2(float ip, float qn, float xn) {
-  const float s = qn + xn;
-  const float d = __builtin_fmaf(-2.0f, ip, s);
-  return d < 0.0f ? 0.0f : d;  // a NaN stays a NaN
-}
-
-struct KnnTable {
-  const void* X;
-  int64_t stride, swizzle_rows;
-  int32_t num_rows, dim;
-  int dtype;
-};
+static_assert(kBK == ::kBK && kSortN == ::kSortN && kSelThreads == ::kSelThreads &&
+                  kCandBudgetBytes == ::kCandBudgetBytes,
+              "the constants restated for tests/test_knn_cpu.py differ from glx_knn.h");
+}  // namespace restated
 
 // out[r] = the chain of row r with itself; one lane per row (built once per owned table; per search for a view and for
 // the request's queries)
@@ -85,18 +64,6 @@ __global__ __launch_bounds__(256) void knn_norms_kernel(KnnTable t, float* __res
   }
   out[r] = acc;
 }
-
-struct KnnArgs {
-  KnnTable t;
-  const float* queries;  // [nq, dim] of this query block
-  const float* qn;       // [nq] (L2)
-  const float* xn;       // [num_rows] (L2)
-  uint32_t* thr;         // [nq] image of the current k-th best, kNoThr = none yet
-  uint32_t* cnt;         // [nq] candidates of the current chunk
-  uint64_t* cand;        // [nq, cap]
-  uint64_t* run;         // [nq, KP] running list, ascending, kNoKey = empty
-  int32_t nq, cap, KP, k, metric;
-};
 
 __global__ __launch_bounds__(256) void knn_init_kernel(KnnArgs a) {
   const int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x;
@@ -205,58 +172,11 @@ __global__ __launch_bounds__(256) void knn_score_kernel(KnnArgs a, int32_t row0,
         base = __shfl(base, half * 32);
         if (pass) {
           const uint32_t pos = base + (uint32_t)__popc(mine & below);
-          if (pos < (uint32_t)a.cap) a.cand[(int64_t)q * a.cap + pos] = ((uint64_t)ord << 32) | (uint32_t)row;
+          // the key from the image the threshold test already holds: knn_key(dist, ...) would compute it again
+          if (pos < (uint32_t)a.cap) a.cand[(int64_t)q * a.cap + pos] = knn_key(ord, row);
         }
       }
     }
-  }
-}
-
-// ---- the k smallest keys, one workgroup of kSelThreads ------------------------------------------------------
-// v[kSortN] ascending
-__device__ __forceinline__ void knn_sort_batch(uint64_t* v, int t) {
-  for (int size = 2; size <= kSortN; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      __syncthreads();
-      const int i = 2 * t - (t & (stride - 1)), j = i + stride;
-      const bool up = (i & size) == 0;
-      const uint64_t x = v[i], y = v[j];
-      if ((x > y) == up) {
-        v[i] = y;
-        v[j] = x;
-      }
-    }
-  }
-  __syncthreads();
-}
-
-// run[KP] ascending (KP a power of two <= kSortN), v[kSortN] ascending -> run = the KP smallest of both, ascending
-__device__ __forceinline__ void knn_merge_batch(uint64_t* run, const uint64_t* v, int KP, int t) {
-  for (int i = t; i < KP; i += kSelThreads) {
-    const uint64_t x = run[i], y = v[KP - 1 - i];
-    run[i] = x < y ? x : y;  // a bitonic sequence that holds the KP smallest
-  }
-  for (int stride = KP >> 1; stride > 0; stride >>= 1) {
-    __syncthreads();
-    if (t < (KP >> 1)) {
-      const int i = 2 * t - (t & (stride - 1)), j = i + stride;
-      const uint64_t x = run[i], y = run[j];
-      if (x > y) {
-        run[i] = y;
-        run[j] = x;
-      }
-    }
-  }
-  __syncthreads();
-}
-
-template <typename Fetch>
-__device__ __forceinline__ void knn_fold(uint64_t* run, uint64_t* v, int KP, int64_t n, int t, Fetch fetch) {
-  for (int64_t base = 0; base < n; base += kSortN) {
-    __syncthreads();  // v and run of the previous batch are settled
-    for (int i = t; i < kSortN; i += kSelThreads) v[i] = base + i < n ? fetch(base + i) : kNoKey;
-    knn_sort_batch(v, t);
-    knn_merge_batch(run, v, KP, t);
   }
 }
 
@@ -288,11 +208,7 @@ __global__ __launch_bounds__(256) void knn_finish_kernel(KnnArgs a, const int64_
   if (o >= (int64_t)a.nq * a.k) return;
   const int32_t q = (int32_t)(o / a.k), j = (int32_t)(o % a.k);
   const uint64_t key = a.run[(int64_t)q * a.KP + j];
-  if (key == kNoKey) {
-    ids_out[o] = -1;
-    dist_out[o] = a.metric == GLX_KNN_L2 ? __builtin_inff() : -__builtin_inff();
-    return;
-  }
+  if (key == kNoKey) return knn_emit_absent(o, a.metric, ids_out, dist_out);
   const int64_t row = (int64_t)(uint32_t)key;
   const uint32_t ord = (uint32_t)(key >> 32);
   uint32_t bits = knn_unord(ord, a.metric);
@@ -304,7 +220,7 @@ __global__ __launch_bounds__(256) void knn_finish_kernel(KnnArgs a, const int64_
     bits = __float_as_uint(a.metric == GLX_KNN_L2 ? knn_l2(ip, a.qn[q], a.xn[row]) : ip);
   }
   dist_out[o] = __uint_as_float(bits);
-  ids_out[o] = row_ids ? row_ids[row] : (id_step > 0 ? id_base + id_step * row : row);
+  ids_out[o] = knn_row_id(row, row_ids, id_base, id_step);
 }
 
 // KnnResponse::Merge (knn_request.cc:186-202): the k best of num_parts lists per query; ties to the lower part, then
@@ -326,26 +242,19 @@ __global__ __launch_bounds__(kSelThreads) void knn_merge_kernel(KnnMergeArgs a) 
   knn_fold(srun, v, a.KP, (int64_t)a.num_parts * a.k, t, [&](int64_t i) {
     const int64_t at = slot(i);
     if (a.ids[at] == -1) return kNoKey;
-    return ((uint64_t)knn_ord(__float_as_uint(a.dist[at]), a.metric) << 32) | (uint32_t)i;
+    return knn_key(a.dist[at], (uint32_t)i, a.metric);
   });
   for (int j = t; j < a.k; j += kSelThreads) {
     const uint64_t key = srun[j];
     const int64_t o = (int64_t)q * a.k + j;
     if (key == kNoKey) {
-      a.ids_out[o] = -1;
-      a.dist_out[o] = a.metric == GLX_KNN_L2 ? __builtin_inff() : -__builtin_inff();
+      knn_emit_absent(o, a.metric, a.ids_out, a.dist_out);
     } else {
       const int64_t at = slot((int64_t)(uint32_t)key);
       a.ids_out[o] = a.ids[at];
       a.dist_out[o] = a.dist[at];
     }
   }
-}
-
-int knn_pow2_at_least(int32_t k) {
-  int p = 1;
-  while (p < k) p <<= 1;
-  return p;
 }
 
 std::mutex g_norm_mu;
@@ -382,13 +291,35 @@ int knn_table_norms(const glx_features* f, const KnnTable& t, hipStream_t s, con
   return GLX_OK;
 }
 
-size_t knn_align(size_t b) { return (b + 255) & ~(size_t)255; }
+}  // namespace
+
+int knn_prepare_norms(const glx_features* f, bool needs_l2, const float* d_q, int32_t num_queries, float* qn,
+                      float* xn_ws, hipStream_t s, const float** xn) {
+  if (!needs_l2) return GLX_OK;
+  const KnnTable t = knn_table(f);
+  if (f->owns_x) {
+    const int rc = knn_table_norms(f, t, s, xn);
+    if (rc != GLX_OK) return rc;
+  } else {
+    if (t.num_rows > 0) knn_norms_kernel<<<(unsigned)((t.num_rows + 255) / 256), 256, 0, s>>>(t, xn_ws);
+    *xn = xn_ws;
+  }
+  const KnnTable qt{d_q, f->dim, 0, num_queries, f->dim, GLX_DTYPE_F32};
+  knn_norms_kernel<<<(unsigned)((num_queries + 255) / 256), 256, 0, s>>>(qt, qn);
+  return GLX_OK;
+}
+
+void knn_finish(const KnnArgs& a, const glx_features* f, int64_t* d_ids, float* d_dist, hipStream_t s) {
+  const bool arith = f->idmap.keys == nullptr && f->idmap.step > 0;
+  knn_finish_kernel<<<(unsigned)(((int64_t)a.nq * a.k + 255) / 256), 256, 0, s>>>(
+      a, f->knn_row_ids, arith ? f->idmap.base : 0, arith ? f->idmap.step : 0, d_ids, d_dist);
+}
 
 int knn_search_device(const glx_features* f, int metric, const float* d_q, int32_t num_queries, int32_t k,
                       int64_t* d_ids, float* d_dist, hipStream_t s) {
   KnnArgs a;
   memset(&a, 0, sizeof(a));
-  a.t = KnnTable{f->X, f->stride, f->swizzle_rows, (int32_t)f->num_rows, f->dim, f->dtype};
+  a.t = knn_table(f);
   a.k = k;
   a.KP = knn_pow2_at_least(k);
   a.metric = metric;
@@ -418,37 +349,23 @@ int knn_search_device(const glx_features* f, int metric, const float* d_q, int32
   const int64_t first = knob_chunk > 0 ? chunk : (chunk < kDefaultFirstChunkRows ? chunk : kDefaultFirstChunkRows);
   a.cap = (int32_t)chunk;
 
-  // workspace: qn[num_queries] | xn[num_rows] (L2 on a view) | thr[qb] | cnt[qb] | run[qb, KP] | cand[qb, cap]
-  const bool view_norms = metric == GLX_KNN_L2 && !f->owns_x;
-  const size_t off_xn = knn_align((size_t)num_queries * sizeof(float));
-  const size_t off_thr = off_xn + (view_norms ? knn_align((size_t)a.t.num_rows * sizeof(float)) : 0);
-  const size_t off_cnt = off_thr + knn_align((size_t)qb * sizeof(uint32_t));
-  const size_t off_run = off_cnt + knn_align((size_t)qb * sizeof(uint32_t));
-  const size_t off_cand = off_run + knn_align((size_t)qb * a.KP * sizeof(uint64_t));
-  const size_t total = off_cand + (size_t)qb * a.cap * sizeof(uint64_t);
+  // workspace slot 1
+  float *qn, *xn_ws;
+  auto layout = [&](KnnCarve c) {
+    qn = c.take<float>(num_queries);
+    xn_ws = c.take<float>(a.t.num_rows, metric == GLX_KNN_L2 && !f->owns_x);
+    a.thr = c.take<uint32_t>(qb);
+    a.cnt = c.take<uint32_t>(qb);
+    a.run = c.take<uint64_t>(qb * a.KP);
+    a.cand = c.take<uint64_t>(qb * a.cap);
+    return c.off;
+  };
   GlxScratch ws;
-  int rc = ws.alloc(total, s, 1);
+  int rc = ws.alloc(layout(KnnCarve{nullptr}), s, 1);
   if (rc != GLX_OK) return rc;
-  char* const base = ws.as<char>();
-  float* const qn = reinterpret_cast<float*>(base);
-  a.thr = reinterpret_cast<uint32_t*>(base + off_thr);
-  a.cnt = reinterpret_cast<uint32_t*>(base + off_cnt);
-  a.run = reinterpret_cast<uint64_t*>(base + off_run);
-  a.cand = reinterpret_cast<uint64_t*>(base + off_cand);
-  if (metric == GLX_KNN_L2) {
-    if (view_norms) {
-      float* const xn = reinterpret_cast<float*>(base + off_xn);
-      if (a.t.num_rows > 0) knn_norms_kernel<<<(unsigned)((a.t.num_rows + 255) / 256), 256, 0, s>>>(a.t, xn);
-      a.xn = xn;
-    } else {
-      rc = knn_table_norms(f, a.t, s, &a.xn);
-      if (rc != GLX_OK) return rc;
-    }
-    const KnnTable qt{d_q, f->dim, 0, num_queries, f->dim, GLX_DTYPE_F32};
-    knn_norms_kernel<<<(unsigned)((num_queries + 255) / 256), 256, 0, s>>>(qt, qn);
-  }
-  const int64_t* const row_ids = f->knn_row_ids;
-  const bool arith = f->idmap.keys == nullptr && f->idmap.step > 0;
+  layout(KnnCarve{ws.as<char>()});
+  rc = knn_prepare_norms(f, metric == GLX_KNN_L2, d_q, num_queries, qn, xn_ws, s, &a.xn);
+  if (rc != GLX_OK) return rc;
   for (int64_t q0 = 0; q0 < num_queries; q0 += qb) {
     a.nq = (int32_t)(num_queries - q0 < qb ? num_queries - q0 : qb);
     a.queries = d_q + q0 * f->dim;
@@ -458,14 +375,11 @@ int knn_search_device(const glx_features* f, int metric, const float* d_q, int32
       const int64_t len = row0 == 0 ? first : chunk;
       const int64_t row1 = row0 + len < a.t.num_rows ? row0 + len : a.t.num_rows;
       const dim3 grid((unsigned)((row1 - row0 + kBR - 1) / kBR), (unsigned)((a.nq + kBQ - 1) / kBQ));
-      if (a.t.dtype == GLX_DTYPE_F32) knn_score_kernel<GLX_DTYPE_F32><<<grid, 256, 0, s>>>(a, (int32_t)row0, (int32_t)row1);
-      else if (a.t.dtype == GLX_DTYPE_BF16) knn_score_kernel<GLX_DTYPE_BF16><<<grid, 256, 0, s>>>(a, (int32_t)row0, (int32_t)row1);
-      else knn_score_kernel<GLX_DTYPE_F16><<<grid, 256, 0, s>>>(a, (int32_t)row0, (int32_t)row1);
+      GLX_KNN_LAUNCH_DT(a.t.dtype, knn_score_kernel, grid, 256, s, a, (int32_t)row0, (int32_t)row1);
       knn_select_kernel<<<(unsigned)a.nq, kSelThreads, 0, s>>>(a);
       row0 = row1;
     }
-    knn_finish_kernel<<<(unsigned)(((int64_t)a.nq * k + 255) / 256), 256, 0, s>>>(
-        a, row_ids, arith ? f->idmap.base : 0, arith ? f->idmap.step : 0, d_ids + q0 * k, d_dist + q0 * k);
+    knn_finish(a, f, d_ids + q0 * k, d_dist + q0 * k, s);
   }
   return GLX_OK;
 }
@@ -479,41 +393,15 @@ int knn_not_capturing(hipStream_t s) {
   return GLX_OK;
 }
 
-}  // namespace
-
-#define GLX_KNN_REQUIRE()                                                                                      \
-  GLX_REQUIRE(metric == GLX_KNN_L2 || metric == GLX_KNN_IP, "metric must be GLX_KNN_L2 (0) or GLX_KNN_IP (1), got %d", \
-              metric);                                                                                         \
-  GLX_REQUIRE(k >= 1 && k <= kSortN, "k must be in [1, %d], got %d", kSortN, k);                               \
-  GLX_REQUIRE(num_queries >= 0, "negative sizes: num_queries %d", num_queries);                                \
-  GLX_REQUIRE((int64_t)num_queries * k < INT32_MAX, "num_queries * k must be < 2^31");                         \
-  GLX_REQUIRE(ptr_kind == GLX_PTR_HOST || ptr_kind == GLX_PTR_DEVICE, "bad ptr_kind")
-
 extern "C" int glx_knn_search(const glx_features* f, int metric, const float* queries, int32_t num_queries, int32_t k,
                               int64_t* ids_out, float* dist_out, int ptr_kind, void* stream) {
   GLX_REQUIRE(f != nullptr, "features is NULL");
   GLX_KNN_REQUIRE();
   GLX_REQUIRE(f->num_rows < INT32_MAX, "num_rows must be < 2^31");
-  GLX_REQUIRE(num_queries == 0 || queries != nullptr, "queries is NULL");
-  GLX_REQUIRE(num_queries == 0 || ids_out != nullptr, "ids_out is NULL");
-  GLX_REQUIRE(num_queries == 0 || dist_out != nullptr, "dist_out is NULL");
-  if (num_queries == 0) return GLX_OK;
-  GlxDeviceGuard guard(f->device);
-  GLX_REQUIRE(guard.ok, "cannot select device %d", f->device);
-  if (ptr_kind == GLX_PTR_DEVICE) {
-    const int cap_rc = knn_not_capturing(glx_stream(stream));
-    if (cap_rc != GLX_OK) return cap_rc;
-  }
-  GlxHostStage st(f->device, ptr_kind, stream, GlxHostStage::ADMIT);
-  const float* d_q;
-  int64_t* d_ids;
-  float* d_dist;
-  st.in(&d_q, queries, (size_t)num_queries * f->dim);
-  st.out(&d_ids, ids_out, (size_t)num_queries * k);
-  st.out(&d_dist, dist_out, (size_t)num_queries * k);
-  int rc = st.begin();
-  if (rc == GLX_OK) rc = knn_search_device(f, metric, d_q, num_queries, k, d_ids, d_dist, st.s);
-  return st.finish(rc);
+  return knn_search_entry(f->device, f->dim, queries, num_queries, k, ids_out, dist_out, ptr_kind, stream,
+                          [&](const float* d_q, int64_t* d_ids, float* d_dist, hipStream_t s) {
+                            return knn_search_device(f, metric, d_q, num_queries, k, d_ids, d_dist, s);
+                          });
 }
 
 extern "C" int glx_knn_merge(int device, int metric, int32_t num_parts, const int64_t* ids, const float* dist,
@@ -528,11 +416,7 @@ extern "C" int glx_knn_merge(int device, int metric, int32_t num_parts, const in
   if (rc != GLX_OK) return rc;
   if (num_queries == 0) return GLX_OK;
   GlxDeviceGuard guard(device);
-  GLX_REQUIRE(guard.ok, "cannot select device %d", device);
-  if (ptr_kind == GLX_PTR_DEVICE) {
-    const int cap_rc = knn_not_capturing(glx_stream(stream));
-    if (cap_rc != GLX_OK) return cap_rc;
-  }
+  GLX_KNN_CALL_BEGIN(guard, device, ptr_kind == GLX_PTR_DEVICE, stream);
   GlxHostStage st(device, ptr_kind, stream, GlxHostStage::ADMIT);
   KnnMergeArgs a;
   const size_t n_in = (size_t)num_parts * num_queries * k;
@@ -551,9 +435,3 @@ extern "C" int glx_knn_merge(int device, int metric, int32_t num_parts, const in
   }
   return st.finish(rc);
 }
-
-// ---- the IVF-Flat index over the same contract: glx_knn_ivf_build / _search / _info / _export / _destroy
-#include "glx_knn_ivf.h"
-
-// ---- the IVF-PQ index on top of it: glx_knn_ivfpq_build / _search / _info / _export / _destroy
-#include "glx_knn_ivfpq.h"

@@ -1,7 +1,8 @@
 // glx IVF-PQ index over a device feature table: the reference's IVFPQKnnIndex (contrib/knn/ivfpq_index.cc:25-60, made by
-// contrib/knn/index_factory.cc; gpu_ivfpq_index.cc:30-60) without faiss and without a second copy of the table.  Included
-// at the END of glx_knn.hip, after glx_knn_ivf.h: it sits on a glx_knn_ivf (coarse centroids and lists) and shares the
-// contract helpers and the IVF build's Lloyd machinery.
+// contrib/knn/index_factory.cc; gpu_ivfpq_index.cc:30-60) without faiss and without a second copy of the table.  It sits
+// on a glx_knn_ivf (coarse centroids and lists).  The contract's device functions, the slot plan and the pass loop come
+// from glx_knn.h; the exact search (codes, coarse step, keys -> output) and the IVF build's Lloyd machinery, fill and
+// fold are reached through the launchers of glx_knn.hip and glx_knn_ivf.hip.
 //
 // Contract (DESIGN.md 4, K-knn-ivfpq; include/glx.h "IVF-PQ index").  The index adds m codebooks [m, 256, dsub] and one
 // m-byte code per row in LIST order (position p belongs to storage row list_rows[p]).  A search ranks the rows of the
@@ -18,8 +19,9 @@
 // running sum in a register.  Keys (image of adc, row) go through knn_sort_batch / knn_merge_batch into the slot's
 // RP-entry list; knn_ivf_fold_kernel folds a query's slots.  The ip(q, centroid) term of the inner-product score is one
 // sequential chain per (query, slot), computed by one lane each in a kernel of its own.  No counters, no atomics.
-#ifndef GLX_KNN_IVFPQ_H_
-#define GLX_KNN_IVFPQ_H_
+#include "glx_knn.h"
+
+#pragma clang fp contract(off)
 
 struct glx_knn_ivfpq {
   const glx_knn_ivf* ivf;  // coarse centroids and lists (not owned; outlives the index)
@@ -111,21 +113,14 @@ struct KnnPqScan {
   int32_t nlist, nprobe, p0, P, RP, metric, m, dsub;
 };
 
-// the list a (query, probe slot) scans, -1 when the coarse step named none
-__device__ __forceinline__ int64_t knn_ivfpq_slot_list(const int64_t* probe, int32_t q, int32_t nprobe, int32_t p,
-                                                       int32_t nlist) {
-  const int64_t list = probe ? probe[(int64_t)q * nprobe + p] : (int64_t)p;
-  return list >= 0 && list < nlist ? list : (int64_t)-1;
-}
-
 // cip[q, slot] = the contract chain ip(q, centroid) over all dim columns; one lane per (query, probe slot)
 __global__ __launch_bounds__(256) void knn_ivfpq_cip_kernel(KnnPqScan a, int32_t nq, float* __restrict__ cip) {
   const int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x;
   if (i >= (int64_t)nq * a.P) return;
   const int32_t q = (int32_t)(i / a.P), slot = (int32_t)(i % a.P);
-  const int64_t list = knn_ivfpq_slot_list(a.probe, q, a.nprobe, a.p0 + slot, a.nlist);
+  int64_t list;
   float acc = 0.0f;
-  if (list >= 0) {
+  if (knn_ivf_slot_list(a.probe, q, a.nprobe, a.p0 + slot, a.nlist, &list)) {
     const float* const qv = a.queries + (int64_t)q * a.t.dim;
     const float* const cv = a.centroids + list * a.t.dim;
     for (int32_t c = 0; c < a.t.dim; ++c) acc = __builtin_fmaf(qv[c], cv[c], acc);
@@ -158,9 +153,9 @@ __global__ __launch_bounds__(kSelThreads) void knn_ivfpq_scan_kernel(KnnPqScan a
   __shared__ uint64_t v[kSortN];
   const int t = threadIdx.x;
   const int32_t q = (int32_t)(blockIdx.x / (uint32_t)a.P), slot = (int32_t)(blockIdx.x % (uint32_t)a.P);
-  const int64_t list = knn_ivfpq_slot_list(a.probe, q, a.nprobe, a.p0 + slot, a.nlist);
+  int64_t list;
   int32_t l0 = 0, l1 = 0;
-  if (list >= 0) {
+  if (knn_ivf_slot_list(a.probe, q, a.nprobe, a.p0 + slot, a.nlist, &list)) {
     l0 = a.list_ptr[list];
     l1 = a.list_ptr[list + 1];
   }
@@ -213,8 +208,7 @@ __global__ __launch_bounds__(kSelThreads) void knn_ivfpq_scan_kernel(KnnPqScan a
         uint64_t key = kNoKey;
         if (p < l1) {
           const int32_t row = a.list_rows[p];
-          if (row >= 0 && row < a.t.num_rows)
-            key = ((uint64_t)knn_ord(__float_as_uint(acc[u]), a.metric) << 32) | (uint32_t)row;
+          if (row >= 0 && row < a.t.num_rows) key = knn_key(acc[u], row, a.metric);
         }
         v[u * kSelThreads + t] = key;
       }
@@ -239,11 +233,7 @@ __global__ __launch_bounds__(256) void knn_ivfpq_finish_kernel(KnnPqScan a, cons
   if (o >= (int64_t)nq * k) return;
   const int32_t q = (int32_t)(o / k), i = (int32_t)(o % k);
   const uint64_t key = run[(int64_t)q * a.RP + i];
-  if (key == kNoKey) {
-    ids_out[o] = -1;
-    dist_out[o] = a.metric == GLX_KNN_L2 ? __builtin_inff() : -__builtin_inff();
-    return;
-  }
+  if (key == kNoKey) return knn_emit_absent(o, a.metric, ids_out, dist_out);
   const int32_t row = (int32_t)(uint32_t)key;
   const uint32_t ord = (uint32_t)(key >> 32);
   uint32_t bits = knn_unord(ord, a.metric);
@@ -251,8 +241,8 @@ __global__ __launch_bounds__(256) void knn_ivfpq_finish_kernel(KnnPqScan a, cons
     bits = 0x7fc00000u;
   } else if ((bits & 0x7fffffffu) == 0 && a.metric != GLX_KNN_L2) {
     for (int32_t s = 0; s < a.nprobe; ++s) {
-      const int64_t list = knn_ivfpq_slot_list(a.probe, q, a.nprobe, s, a.nlist);
-      if (list < 0) continue;
+      int64_t list;
+      if (!knn_ivf_slot_list(a.probe, q, a.nprobe, s, a.nlist, &list)) continue;
       int32_t lo = a.list_ptr[list], hi = a.list_ptr[list + 1];  // rows ascend within a list
       while (lo < hi) {
         const int32_t mid = lo + (hi - lo) / 2;
@@ -273,132 +263,77 @@ __global__ __launch_bounds__(256) void knn_ivfpq_finish_kernel(KnnPqScan a, cons
     }
   }
   dist_out[o] = __uint_as_float(bits);
-  ids_out[o] = row_ids ? row_ids[row] : (id_step > 0 ? id_base + id_step * row : (int64_t)row);
+  ids_out[o] = knn_row_id(row, row_ids, id_base, id_step);
 }
 
 // refine > 0: out[q, 0 .. KP) = the KP best keys (image of the contract distance, row) among the rows of the first R
-// keys of cand[q, 0 .. RP); one workgroup per query, the rows gathered with knn_ivf_scan_kernel's tile pattern.
+// keys of cand[q, 0 .. RP); one workgroup per query, the rows scored by knn_score_gathered.
 template <int DT>
 __global__ __launch_bounds__(kSelThreads) void knn_ivfpq_refine_kernel(KnnArgs a, const uint64_t* __restrict__ cand,
                                                                        int32_t RP, int32_t R, uint64_t* __restrict__ out) {
-  typedef typename AggElem<DT>::raw raw_t;
   __shared__ float Bs[kBK][kIvfLd];
   __shared__ float qs[kBK];
   __shared__ int64_t rbase[kIvfRows];
   __shared__ uint64_t v[kSortN];
   const int t = threadIdx.x;
   const int32_t q = blockIdx.x;
-  const int32_t dim = a.t.dim;
-  const raw_t* const X = static_cast<const raw_t*>(a.t.X);
-  const float* const qv = a.queries + (int64_t)q * dim;
+  const float* const qv = a.queries + (int64_t)q * a.t.dim;
   const uint64_t* const mine = cand + (int64_t)q * RP;
-  const int lc = t & (kBK - 1), lr = t / kBK;
   for (int sub = 0; sub < kSortN / kIvfRows; ++sub) {
     const int32_t r0 = sub * kIvfRows;
     if (r0 >= R) {  // uniform: the batch's tail is empty
       if (t < kIvfRows) v[r0 + t] = kNoKey;
       continue;
     }
-    int32_t row = -1;
-    if (t < kIvfRows) {
-      if (r0 + t < R) {
-        const uint64_t key = mine[r0 + t];
-        if (key != kNoKey) row = (int32_t)(uint32_t)key;
-      }
-      if (row >= a.t.num_rows) row = -1;
-      rbase[t] = row >= 0 ? glx_swizzle_row(row, a.t.swizzle_rows) * a.t.stride : (int64_t)-1;
-    }
-    float acc = 0.0f;
-    for (int32_t k0 = 0; k0 < dim; k0 += kBK) {
-      __syncthreads();  // rbase is written; the previous tile has been consumed
-      const int32_t c = k0 + lc;
-#pragma unroll
-      for (int j = 0; j < kIvfRows / (kSelThreads / kBK); ++j) {
-        const int r = lr + (kSelThreads / kBK) * j;
-        const int64_t base = rbase[r];
-        float xb = 0.0f;
-        if (c < dim && base >= 0) xb = AggElem<DT>::up(X[base + c]);
-        Bs[lc][r] = xb;
-      }
-      if (t < kBK) qs[t] = k0 + t < dim ? qv[k0 + t] : 0.0f;
-      __syncthreads();
-      if (t < kIvfRows) {
-        const int n = dim - k0 < kBK ? dim - k0 : kBK;
-        for (int kk = 0; kk < n; ++kk) acc = __builtin_fmaf(qs[kk], Bs[kk][t], acc);
-      }
-    }
-    if (t < kIvfRows) {
-      uint64_t key = kNoKey;
-      if (row >= 0) {
-        const float dist = a.metric == GLX_KNN_L2 ? knn_l2(acc, a.qn[q], a.xn[row]) : acc;
-        key = ((uint64_t)knn_ord(__float_as_uint(dist), a.metric) << 32) | (uint32_t)row;
-      }
-      v[r0 + t] = key;
-    }
+    auto row_of = [&](int i) {
+      const uint64_t key = r0 + i < R ? mine[r0 + i] : kNoKey;
+      return key != kNoKey ? (int32_t)(uint32_t)key : -1;
+    };
+    knn_score_gathered<DT>(a.t, qv, a.qn, q, a.xn, a.metric, row_of, Bs, qs, rbase, v + r0);
   }
   knn_sort_batch(v, t);
   for (int i = t; i < a.KP; i += kSelThreads) out[(int64_t)q * a.KP + i] = v[i];
 }
 
-int knn_ivfpq_search_device(const glx_knn_ivfpq* px, int metric, const float* d_q, int32_t num_queries, int32_t k,
-                            int32_t nprobe, int32_t refine, int64_t* d_ids, float* d_dist, hipStream_t s) {
+}  // namespace
+
+static int knn_ivfpq_search_device(const glx_knn_ivfpq* px, int metric, const float* d_q, int32_t num_queries, int32_t k,
+                                   int32_t nprobe, int32_t refine, int64_t* d_ids, float* d_dist, hipStream_t s) {
   const glx_knn_ivf* const ix = px->ivf;
   const glx_features* const f = ix->f;
   const bool coarse = nprobe != ix->nlist;
   KnnArgs a;
   memset(&a, 0, sizeof(a));
-  a.t = knn_ivf_table(f);
+  a.t = knn_table(f);
   a.k = k;
   a.KP = knn_pow2_at_least(k);
   a.metric = metric;
   const int32_t RP = knn_pow2_at_least(refine > k ? refine : k);
-  // as knn_ivf_search_device: qb queries x P probe slots x RP keys under the flat search's candidate budget
-  const int64_t budget_keys = (int64_t)(kCandBudgetBytes / sizeof(uint64_t));
-  int64_t P = nprobe, qb = budget_keys / ((int64_t)nprobe * RP);
-  if (qb < 1) {
-    qb = 1;
-    P = budget_keys / RP;
-  }
-  if (qb > num_queries) qb = num_queries;
-  const int64_t knob_qb = glx_side_knobs().knn_query_block.load(std::memory_order_relaxed);
-  if (knob_qb > 0 && knob_qb < qb) qb = knob_qb;
-
-  // workspace (slot 2; knn_search_device leases slot 1 for the coarse step): qn[num_queries] | xn[num_rows] (L2 refine on
-  // a view) | probe[qb, nprobe] | pdist[qb, nprobe] | cip[qb, P] (IP) | cand[qb, RP] | part[qb, P, RP] | run[qb, KP]
+  const KnnSlotPlan plan = knn_slot_plan(nprobe, RP, num_queries);
   const bool exact_l2 = metric == GLX_KNN_L2 && refine > 0;
-  const bool view_norms = exact_l2 && !f->owns_x;
-  const size_t off_xn = knn_align((size_t)num_queries * sizeof(float));
-  const size_t off_probe = off_xn + (view_norms ? knn_align((size_t)a.t.num_rows * sizeof(float)) : 0);
-  const size_t off_pdist = off_probe + (coarse ? knn_align((size_t)qb * nprobe * sizeof(int64_t)) : 0);
-  const size_t off_cip = off_pdist + (coarse ? knn_align((size_t)qb * nprobe * sizeof(float)) : 0);
-  const size_t off_cand = off_cip + (metric == GLX_KNN_IP ? knn_align((size_t)qb * P * sizeof(float)) : 0);
-  const size_t off_part = off_cand + knn_align((size_t)qb * RP * sizeof(uint64_t));
-  const size_t off_run = off_part + knn_align((size_t)qb * P * RP * sizeof(uint64_t));
-  const size_t total = off_run + (refine > 0 ? (size_t)qb * a.KP * sizeof(uint64_t) : 0);
-  GlxScratch ws;
-  int rc = ws.alloc(total, s, 2);
-  if (rc != GLX_OK) return rc;
-  char* const base = ws.as<char>();
-  float* const qn = reinterpret_cast<float*>(base);
-  int64_t* const probe = coarse ? reinterpret_cast<int64_t*>(base + off_probe) : nullptr;
-  float* const pdist = coarse ? reinterpret_cast<float*>(base + off_pdist) : nullptr;
-  float* const cip = metric == GLX_KNN_IP ? reinterpret_cast<float*>(base + off_cip) : nullptr;
-  uint64_t* const cand = reinterpret_cast<uint64_t*>(base + off_cand);
-  a.run = refine > 0 ? reinterpret_cast<uint64_t*>(base + off_run) : nullptr;
-  if (exact_l2) {
-    if (view_norms) {
-      float* const xn = reinterpret_cast<float*>(base + off_xn);
-      if (a.t.num_rows > 0) knn_norms_kernel<<<(unsigned)((a.t.num_rows + 255) / 256), 256, 0, s>>>(a.t, xn);
-      a.xn = xn;
-    } else {
-      rc = knn_table_norms(f, a.t, s, &a.xn);
-      if (rc != GLX_OK) return rc;
-    }
-    const KnnTable qt{d_q, f->dim, 0, num_queries, f->dim, GLX_DTYPE_F32};
-    knn_norms_kernel<<<(unsigned)((num_queries + 255) / 256), 256, 0, s>>>(qt, qn);
-  }
   KnnPqScan sc;
   memset(&sc, 0, sizeof(sc));
+  // workspace slot 2: knn_search_device leases slot 1 for the coarse step
+  float *qn, *xn_ws, *pdist, *cip;
+  int64_t* probe;
+  uint64_t* cand;
+  auto layout = [&](KnnCarve c) {
+    qn = c.take<float>(num_queries);
+    xn_ws = c.take<float>(a.t.num_rows, exact_l2 && !f->owns_x);
+    probe = c.take<int64_t>(plan.qb * nprobe, coarse);
+    pdist = c.take<float>(plan.qb * nprobe, coarse);
+    cip = c.take<float>(plan.qb * plan.P, metric == GLX_KNN_IP);
+    cand = c.take<uint64_t>(plan.qb * RP);
+    sc.part = c.take<uint64_t>(plan.qb * plan.P * RP);
+    a.run = c.take<uint64_t>(plan.qb * a.KP, refine > 0);
+    return c.off;
+  };
+  GlxScratch ws;
+  int rc = ws.alloc(layout(KnnCarve{nullptr}), s, 2);
+  if (rc != GLX_OK) return rc;
+  layout(KnnCarve{ws.as<char>()});
+  rc = knn_prepare_norms(f, exact_l2, d_q, num_queries, qn, xn_ws, s, &a.xn);
+  if (rc != GLX_OK) return rc;
   sc.t = a.t;
   sc.centroids = ix->centroids;
   sc.cbt = px->cbt;
@@ -408,49 +343,39 @@ int knn_ivfpq_search_device(const glx_knn_ivfpq* px, int metric, const float* d_
   sc.list_ptr = ix->list_ptr;
   sc.list_rows = ix->list_rows;
   sc.probe = probe;
-  sc.part = reinterpret_cast<uint64_t*>(base + off_part);
   sc.nlist = ix->nlist;
   sc.nprobe = nprobe;
   sc.RP = RP;
   sc.metric = metric;
   sc.m = px->m;
   sc.dsub = px->dsub;
-  const int64_t* const row_ids = f->knn_row_ids;
   const bool arith = f->idmap.keys == nullptr && f->idmap.step > 0;
-  for (int64_t q0 = 0; q0 < num_queries; q0 += qb) {
-    a.nq = (int32_t)(num_queries - q0 < qb ? num_queries - q0 : qb);
-    a.queries = d_q + q0 * f->dim;
-    a.qn = qn + q0;
-    if (coarse) {
-      rc = knn_search_device(&ix->cview, metric, a.queries, a.nq, nprobe, probe, pdist, s);
-      if (rc != GLX_OK) return rc;
-    }
-    knn_ivf_fill_kernel<<<(unsigned)(((int64_t)a.nq * RP + 255) / 256), 256, 0, s>>>(cand, (int64_t)a.nq * RP);
-    sc.queries = a.queries;
-    for (int64_t p0 = 0; p0 < nprobe; p0 += P) {
-      sc.p0 = (int32_t)p0;
-      sc.P = (int32_t)(nprobe - p0 < P ? nprobe - p0 : P);
-      const int64_t slots = (int64_t)a.nq * sc.P;
-      if (cip) knn_ivfpq_cip_kernel<<<(unsigned)((slots + 255) / 256), 256, 0, s>>>(sc, a.nq, cip);
-      knn_ivfpq_scan_kernel<<<(unsigned)slots, kSelThreads, 0, s>>>(sc);
-      knn_ivf_fold_kernel<<<(unsigned)a.nq, kSelThreads, 0, s>>>(cand, sc.part, sc.P, RP);
-    }
-    const unsigned out_grid = (unsigned)(((int64_t)a.nq * k + 255) / 256);
-    const int64_t id_base = arith ? f->idmap.base : 0, id_step = arith ? f->idmap.step : 0;
-    if (refine == 0) {
-      knn_ivfpq_finish_kernel<<<out_grid, 256, 0, s>>>(sc, cand, a.nq, k, px->codebooks, row_ids, id_base, id_step,
-                                                       d_ids + q0 * k, d_dist + q0 * k);
-      continue;
-    }
-    if (a.t.dtype == GLX_DTYPE_F32) knn_ivfpq_refine_kernel<GLX_DTYPE_F32><<<(unsigned)a.nq, kSelThreads, 0, s>>>(a, cand, RP, refine, a.run);
-    else if (a.t.dtype == GLX_DTYPE_BF16) knn_ivfpq_refine_kernel<GLX_DTYPE_BF16><<<(unsigned)a.nq, kSelThreads, 0, s>>>(a, cand, RP, refine, a.run);
-    else knn_ivfpq_refine_kernel<GLX_DTYPE_F16><<<(unsigned)a.nq, kSelThreads, 0, s>>>(a, cand, RP, refine, a.run);
-    knn_finish_kernel<<<out_grid, 256, 0, s>>>(a, row_ids, id_base, id_step, d_ids + q0 * k, d_dist + q0 * k);
-  }
-  return GLX_OK;
+  return knn_ivf_passes(
+      ix, metric, d_q, num_queries, nprobe, plan, probe, pdist, cand, sc.part, RP, s,
+      [&](int64_t q0, int32_t nq, int32_t p0, int32_t P) {
+        sc.queries = d_q + q0 * f->dim;
+        sc.p0 = p0;
+        sc.P = P;
+        const int64_t slots = (int64_t)nq * P;
+        if (cip) knn_ivfpq_cip_kernel<<<(unsigned)((slots + 255) / 256), 256, 0, s>>>(sc, nq, cip);
+        knn_ivfpq_scan_kernel<<<(unsigned)slots, kSelThreads, 0, s>>>(sc);
+      },
+      [&](int64_t q0, int32_t nq) {
+        if (refine == 0) {
+          knn_ivfpq_finish_kernel<<<(unsigned)(((int64_t)nq * k + 255) / 256), 256, 0, s>>>(
+              sc, cand, nq, k, px->codebooks, f->knn_row_ids, arith ? f->idmap.base : 0, arith ? f->idmap.step : 0,
+              d_ids + q0 * k, d_dist + q0 * k);
+          return;
+        }
+        a.nq = nq;
+        a.queries = d_q + q0 * f->dim;
+        a.qn = qn + q0;
+        GLX_KNN_LAUNCH_DT(a.t.dtype, knn_ivfpq_refine_kernel, (unsigned)nq, kSelThreads, s, a, cand, RP, refine, a.run);
+        knn_finish(a, f, d_ids + q0 * k, d_dist + q0 * k, s);
+      });
 }
 
-int knn_ivfpq_build_device(glx_knn_ivfpq* px, int32_t niter, int64_t train_rows, const float* codebooks_init,
+static int knn_ivfpq_build_device(glx_knn_ivfpq* px, int32_t niter, int64_t train_rows, const float* codebooks_init,
                            int ptr_kind, hipStream_t s) {
   const glx_knn_ivf* const ix = px->ivf;
   const int64_t N = px->num_rows;
@@ -463,7 +388,7 @@ int knn_ivfpq_build_device(glx_knn_ivfpq* px, int32_t niter, int64_t train_rows,
   GLX_HIP(hipMalloc(&px->cbt, (size_t)m * book * sizeof(float)));
   GLX_HIP(hipMalloc(&px->cnorm, (size_t)m * kPqCodewords * sizeof(float)));
   GLX_HIP(hipMalloc(&px->codes, (size_t)N * m));
-  const KnnTable t = knn_ivf_table(ix->f);
+  const KnnTable t = knn_table(ix->f);
   int64_t chunk = (int64_t)(kIvfStageBytes / ((size_t)dsub * sizeof(float)));
   if (chunk > N) chunk = N;
   if (chunk < T) chunk = T;  // the sample's residual sub-vectors are staged whole: the table a codebook is trained on
@@ -476,38 +401,20 @@ int knn_ivfpq_build_device(glx_knn_ivfpq* px, int32_t niter, int64_t train_rows,
   GLX_HIP(hipMemsetAsync(row_list.p, 0, (size_t)N * sizeof(int32_t), s));
   knn_ivfpq_row_list_kernel<<<(unsigned)((N + 255) / 256), 256, 0, s>>>(ix->list_ptr, ix->list_rows, ix->nlist, (int32_t)N,
                                                                         row_list.as<int32_t>());
-  // a float32 table of T rows x dsub columns over `resid`, and an index of 256 lists over it whose centroids are
-  // codebook j in place
-  glx_features rf;
-  memset(static_cast<void*>(&rf), 0, sizeof(rf));
-  rf.device = px->device;
-  rf.num_rows = T;
-  rf.dim = dsub;
-  rf.stride = dsub;
-  rf.X = resid.p;
-  rf.dtype = GLX_DTYPE_F32;
-  rf.elem_size = 4;
-  glx_knn_ivf sub;
-  sub.f = &rf;
-  sub.device = px->device;
-  sub.nlist = kPqCodewords;
-  sub.dim = dsub;
-  sub.num_rows = T;
-  sub.longest = 0;
-  sub.list_ptr = nullptr;
-  sub.list_rows = nullptr;
+  // a float32 table of T rows x dsub columns over `resid`: the table codebook j is trained on, as 256 centroids in place
+  const glx_features rf = knn_f32_view(px->device, resid.as<float>(), T, dsub);
   const bool train = niter > 0 || codebooks_init == nullptr;
   if (!train) {
     GLX_HIP(hipMemcpyAsync(px->codebooks, codebooks_init, (size_t)m * book * sizeof(float),
                            ptr_kind == GLX_PTR_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
   }
   for (int32_t j = 0; j < m; ++j) {
-    sub.centroids = px->codebooks + (size_t)j * book;
-    knn_ivf_set_view(&sub);
+    float* const codebook = px->codebooks + (size_t)j * book;
+    const KnnTrainSet sub{knn_table(&rf), codebook, kPqCodewords, knn_f32_view(px->device, codebook, kPqCodewords, dsub)};
     if (train) {
       knn_ivfpq_stage_kernel<<<(unsigned)((T * dsub + 255) / 256), 256, 0, s>>>(
           t, ix->centroids, row_list.as<int32_t>(), ix->list_rows, 0, 0, T, T, j, dsub, ix->nlist, resid.as<float>());
-      const int rc = knn_ivf_train_device(&sub, niter, T, codebooks_init ? codebooks_init + (size_t)j * book : nullptr,
+      const int rc = knn_ivf_train_device(sub, niter, T, codebooks_init ? codebooks_init + (size_t)j * book : nullptr,
                                           ptr_kind, T, stage.as<float>(), dist.as<float>(), assign.as<int64_t>(), s);
       if (rc != GLX_OK) return rc;
     }
@@ -528,8 +435,6 @@ int knn_ivfpq_build_device(glx_knn_ivfpq* px, int32_t niter, int64_t train_rows,
   return GLX_OK;
 }
 
-}  // namespace
-
 extern "C" int glx_knn_ivfpq_build(const glx_knn_ivf* ivf, int32_t m, int32_t niter, int64_t train_rows,
                                    const float* codebooks_init, int ptr_kind, void* stream, glx_knn_ivfpq** out) {
   GLX_REQUIRE(out != nullptr, "out is NULL");
@@ -543,9 +448,7 @@ extern "C" int glx_knn_ivfpq_build(const glx_knn_ivf* ivf, int32_t m, int32_t ni
   GLX_REQUIRE(ivf->num_rows >= kPqCodewords, "num_rows must be at least %d, got %lld", kPqCodewords,
               (long long)ivf->num_rows);
   GlxDeviceGuard guard(ivf->device);
-  GLX_REQUIRE(guard.ok, "cannot select device %d", ivf->device);
-  const int cap_rc = knn_not_capturing(glx_stream(stream));
-  if (cap_rc != GLX_OK) return cap_rc;
+  GLX_KNN_CALL_BEGIN(guard, ivf->device, true, stream);
   glx_knn_ivfpq* px = new (std::nothrow) glx_knn_ivfpq();
   GLX_REQUIRE(px != nullptr, "out of host memory");
   px->ivf = ivf;
@@ -596,11 +499,7 @@ extern "C" int glx_knn_ivfpq_export(const glx_knn_ivfpq* px, float* codebooks_ou
   GLX_REQUIRE(px != nullptr, "index is NULL");
   GLX_REQUIRE(ptr_kind == GLX_PTR_HOST || ptr_kind == GLX_PTR_DEVICE, "bad ptr_kind");
   GlxDeviceGuard guard(px->device);
-  GLX_REQUIRE(guard.ok, "cannot select device %d", px->device);
-  if (ptr_kind == GLX_PTR_DEVICE) {
-    const int cap_rc = knn_not_capturing(glx_stream(stream));
-    if (cap_rc != GLX_OK) return cap_rc;
-  }
+  GLX_KNN_CALL_BEGIN(guard, px->device, ptr_kind == GLX_PTR_DEVICE, stream);
   GlxHostStage st(px->device, ptr_kind, stream, GlxHostStage::ADMIT);
   float* d_cb;
   uint8_t* d_codes;
@@ -627,33 +526,11 @@ extern "C" int glx_knn_ivfpq_search(const glx_knn_ivfpq* px, int metric, const f
   GLX_REQUIRE(refine == 0 || (refine >= k && refine <= kPqMaxRefine), "refine must be 0 or in [k = %d, %d], got %d", k,
               kPqMaxRefine, refine);
   GLX_REQUIRE((int64_t)num_queries * (refine > k ? refine : k) < INT32_MAX, "num_queries * max(k, refine) must be < 2^31");
-  GLX_REQUIRE(nprobe >= 1, "nprobe must be at least 1, got %d", nprobe);
-  GLX_REQUIRE(px != nullptr, "index is NULL");
-  const glx_knn_ivf* const ix = px->ivf;
-  GLX_REQUIRE(nprobe <= ix->nlist, "nprobe %d exceeds the index's %d lists", nprobe, ix->nlist);
-  GLX_REQUIRE(nprobe == ix->nlist || nprobe <= kIvfMaxProbe, "nprobe must be nlist (%d) or in [1, %d], got %d", ix->nlist,
-              kIvfMaxProbe, nprobe);
-  GLX_REQUIRE((int64_t)num_queries * nprobe < INT32_MAX, "num_queries * nprobe must be < 2^31");
-  GLX_REQUIRE(num_queries == 0 || queries != nullptr, "queries is NULL");
-  GLX_REQUIRE(num_queries == 0 || ids_out != nullptr, "ids_out is NULL");
-  GLX_REQUIRE(num_queries == 0 || dist_out != nullptr, "dist_out is NULL");
-  if (num_queries == 0) return GLX_OK;
-  GlxDeviceGuard guard(px->device);
-  GLX_REQUIRE(guard.ok, "cannot select device %d", px->device);
-  if (ptr_kind == GLX_PTR_DEVICE) {
-    const int cap_rc = knn_not_capturing(glx_stream(stream));
-    if (cap_rc != GLX_OK) return cap_rc;
-  }
-  GlxHostStage st(px->device, ptr_kind, stream, GlxHostStage::ADMIT);
-  const float* d_q;
-  int64_t* d_ids;
-  float* d_dist;
-  st.in(&d_q, queries, (size_t)num_queries * px->dim);
-  st.out(&d_ids, ids_out, (size_t)num_queries * k);
-  st.out(&d_dist, dist_out, (size_t)num_queries * k);
-  int rc = st.begin();
-  if (rc == GLX_OK) rc = knn_ivfpq_search_device(px, metric, d_q, num_queries, k, nprobe, refine, d_ids, d_dist, st.s);
-  return st.finish(rc);
+  const int rc = knn_ivf_check_nprobe(px ? px->ivf : nullptr, nprobe, num_queries);
+  if (rc != GLX_OK) return rc;
+  return knn_search_entry(
+      px->device, px->dim, queries, num_queries, k, ids_out, dist_out, ptr_kind, stream,
+      [&](const float* d_q, int64_t* d_ids, float* d_dist, hipStream_t s) {
+        return knn_ivfpq_search_device(px, metric, d_q, num_queries, k, nprobe, refine, d_ids, d_dist, s);
+      });
 }
-
-#endif  // GLX_KNN_IVFPQ_H_

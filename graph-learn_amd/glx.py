@@ -770,17 +770,7 @@ class Features:
         row, NaN scores come last, k > num_rows pads with id -1 and dist -inf (ip) / +inf (l2); 1 <= k <= 1024.  ids are
         node ids (row numbers for a table without an id map).  Numpy in, numpy out; torch CUDA tensors in, torch CUDA
         tensors out on the current stream, nothing read back.  out=(ids, dist): buffers to write into."""
-        if metric not in KNN_METRICS:
-            raise ValueError("metric must be one of {}, not {!r}".format(sorted(KNN_METRICS), metric))
-        if queries.ndim != 2 or int(queries.shape[1]) != self.dim:
-            raise ValueError("queries must be [n, {}], not {}".format(self.dim, tuple(queries.shape)))
-        n, k = int(queries.shape[0]), int(k)
-        ids, dist = _knn_out(out, queries, n, k)
-        pq, pi, pd = _ptr(queries, None if _is_torch(queries) else np.float32), _ptr(ids), _ptr(dist)
-        kind = _kind(pq, pi, pd)
-        _check(lib().glx_knn_search(self._h, KNN_METRICS[metric], pq[0], n, k, pi[0], pd[0], kind,
-                                    _stream(kind, self.device)))
-        return ids, dist
+        return _knn_search(lib().glx_knn_search, lambda: self._h, self.dim, self.device, queries, k, metric, out)
 
     def build_ivf(self, nlist, niter=10, train_rows=None, centroids=None):
         """An IVF-Flat index over this table (glx_knn_ivf_build) -> KnnIvf.  nlist lists, niter Lloyd iterations over a
@@ -799,10 +789,32 @@ class Features:
 KNN_METRICS = {"l2": 0, "ip": 1}  # GLX_KNN_L2, GLX_KNN_IP
 
 
-class KnnIvf:
+class _KnnIndex:
+    """close() and the context manager of an index handle; a subclass names its destroy function."""
+    _destroy = None
+
+    def close(self):
+        if getattr(self, "_h", None):
+            try:
+                getattr(lib(), self._destroy)(self._h)
+            except Exception:  # interpreter shutdown
+                pass
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class KnnIvf(_KnnIndex):
     """IVF-Flat index over a Features table (glx_knn_ivf): centroids and inverted lists on the device, scores from the
     table itself.  search(..., nprobe=nlist) equals Features.search bit for bit; with fewer lists probed it equals the
     exact search restricted to the probed lists' rows."""
+    _destroy = "glx_knn_ivf_destroy"
 
     def __init__(self, features, nlist, niter=10, train_rows=None, centroids=None):
         self._h = None
@@ -821,16 +833,6 @@ class KnnIvf:
         self.features = features  # the lists index its rows: keep it alive
         self.device = features.device
         self.nlist, self.dim, self.num_rows = nlist, features.dim, features.num_rows
-
-    def close(self):
-        if getattr(self, "_h", None):
-            try:
-                lib().glx_knn_ivf_destroy(self._h)
-            except Exception:  # interpreter shutdown
-                pass
-            self._h = None
-
-    __del__ = close
 
     def info(self):
         """-> dict(nlist, dim, num_rows, longest_list, device_bytes)"""
@@ -860,17 +862,8 @@ class KnnIvf:
         and padding (slots beyond the probed lists' rows hold id -1).  nprobe == nlist probes every list and equals
         Features.search bit for bit; otherwise 1 <= nprobe <= min(nlist, 1024).  Numpy in, numpy out; torch CUDA tensors
         in, torch CUDA tensors out on the current stream, nothing read back.  out=(ids, dist): buffers to write into."""
-        if metric not in KNN_METRICS:
-            raise ValueError("metric must be one of {}, not {!r}".format(sorted(KNN_METRICS), metric))
-        if queries.ndim != 2 or int(queries.shape[1]) != self.dim:
-            raise ValueError("queries must be [n, {}], not {}".format(self.dim, tuple(queries.shape)))
-        n, k = int(queries.shape[0]), int(k)
-        ids, dist = _knn_out(out, queries, n, k)
-        pq, pi, pd = _ptr(queries, None if _is_torch(queries) else np.float32), _ptr(ids), _ptr(dist)
-        kind = _kind(pq, pi, pd)
-        _check(lib().glx_knn_ivf_search(self._h, KNN_METRICS[metric], pq[0], n, k, int(nprobe), pi[0], pd[0], kind,
-                                        _stream(kind, self.device)))
-        return ids, dist
+        return _knn_search(lib().glx_knn_ivf_search, lambda: self._h, self.dim, self.device, queries, k, metric, out,
+                           int(nprobe))
 
     def build_pq(self, m, niter=10, train_rows=None, codebooks=None):
         """An IVF-PQ index on top of this index (glx_knn_ivfpq_build) -> KnnIvfPq: m sub-quantisers of 256 codewords
@@ -880,17 +873,12 @@ class KnnIvf:
         The returned index keeps this one alive."""
         return KnnIvfPq(self, m, niter, train_rows, codebooks)
 
-    def __enter__(self):
-        return self
 
-    def __exit__(self, *exc):
-        self.close()
-
-
-class KnnIvfPq:
+class KnnIvfPq(_KnnIndex):
     """IVF-PQ index on top of a KnnIvf (glx_knn_ivfpq): m codebooks and one m-byte code per row on the device.
     search(..., refine=0) ranks the probed lists' rows by the coded (ADC) score; refine=R re-scores the R best of them
     from the table itself, so every returned distance is Features.search's distance of that row."""
+    _destroy = "glx_knn_ivfpq_destroy"
 
     def __init__(self, ivf, m, niter=10, train_rows=None, codebooks=None):
         self._h = None
@@ -913,22 +901,6 @@ class KnnIvfPq:
         self.ivf = ivf  # the codes follow its lists: keep it (and through it the table) alive
         self.device = ivf.device
         self.m, self.dsub, self.dim, self.num_rows = m, dsub, ivf.dim, ivf.num_rows
-
-    def close(self):
-        if getattr(self, "_h", None):
-            try:
-                lib().glx_knn_ivfpq_destroy(self._h)
-            except Exception:  # interpreter shutdown
-                pass
-            self._h = None
-
-    __del__ = close
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     def _handle(self):
         if not self._h or not self.ivf._h:
@@ -962,17 +934,22 @@ class KnnIvfPq:
         are re-scored from the table and the k best of those returned, dist being Features.search's distance of the row
         bit for bit.  Numpy in, numpy out; torch CUDA tensors in, torch CUDA tensors out on the current stream, nothing
         read back.  out=(ids, dist): buffers to write into."""
-        if metric not in KNN_METRICS:
-            raise ValueError("metric must be one of {}, not {!r}".format(sorted(KNN_METRICS), metric))
-        if queries.ndim != 2 or int(queries.shape[1]) != self.dim:
-            raise ValueError("queries must be [n, {}], not {}".format(self.dim, tuple(queries.shape)))
-        n, k = int(queries.shape[0]), int(k)
-        ids, dist = _knn_out(out, queries, n, k)
-        pq, pi, pd = _ptr(queries, None if _is_torch(queries) else np.float32), _ptr(ids), _ptr(dist)
-        kind = _kind(pq, pi, pd)
-        _check(lib().glx_knn_ivfpq_search(self._handle(), KNN_METRICS[metric], pq[0], n, k, int(nprobe), int(refine),
-                                          pi[0], pd[0], kind, _stream(kind, self.device)))
-        return ids, dist
+        return _knn_search(lib().glx_knn_ivfpq_search, self._handle, self.dim, self.device, queries, k, metric, out,
+                           int(nprobe), int(refine))
+
+
+def _knn_search(call, handle, dim, device, queries, k, metric, out, *extra):
+    """The three search methods: call(handle(), metric, queries, n, k, *extra, ids, dist, ptr kind, stream)."""
+    if metric not in KNN_METRICS:
+        raise ValueError("metric must be one of {}, not {!r}".format(sorted(KNN_METRICS), metric))
+    if queries.ndim != 2 or int(queries.shape[1]) != dim:
+        raise ValueError("queries must be [n, {}], not {}".format(dim, tuple(queries.shape)))
+    n, k = int(queries.shape[0]), int(k)
+    ids, dist = _knn_out(out, queries, n, k)
+    pq, pi, pd = _ptr(queries, None if _is_torch(queries) else np.float32), _ptr(ids), _ptr(dist)
+    kind = _kind(pq, pi, pd)
+    _check(call(handle(), KNN_METRICS[metric], pq[0], n, k, *extra, pi[0], pd[0], kind, _stream(kind, device)))
+    return ids, dist
 
 
 def _knn_out(out, like, n, k):

@@ -337,6 +337,25 @@ def test_query_block_borders():
     assert knn_ref.same(ivf_search(ix, Q, 1024, knn_ref.IP, 299), want)
 
 
+def test_probe_slots_of_one_query_take_two_passes():
+    """40,000 lists of one row each, all probed with k = 513: a query's 40,000 slot lists of KP = 1,024 keys exceed the
+    workspace budget alone, so the block is one query and its slots go in passes of P = 32,768 and 7,232 that fold into
+    the same running list.  (The IVF-PQ search takes its plan from the same function, knn_slot_plan:
+    tests/test_gpu_knn_ivfpq.py has this shape too.)"""
+    N, k, KP = 40000, 513, 1024
+    budget_keys = (256 << 20) // 8
+    assert budget_keys // (N * KP) == 0  # not even one query's slots fit ...
+    P = budget_keys // KP
+    assert P == 32768 and [min(P, N - p0) for p0 in range(0, N, P)] == [32768, 7232]  # ... so they go in two passes
+    rng = np.random.default_rng(22)
+    X = rng.standard_normal((N, 2)).astype(np.float32)
+    Q = rng.standard_normal((2, 2)).astype(np.float32)
+    f = glx.Features(X)
+    ix = f.build_ivf(N, niter=0, centroids=X)
+    for metric in METRICS:
+        assert knn_ref.same(ivf_search(ix, Q, k, metric, N), gpu_search(f, Q, k, metric)), metric
+
+
 @pytest.mark.parametrize("metric", METRICS)
 def test_found_sets_are_nested_in_nprobe(metric):
     rng = np.random.default_rng(21)

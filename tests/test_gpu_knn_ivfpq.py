@@ -197,6 +197,54 @@ def test_few_candidates_equal_the_flat_index_and_the_exact_search():
             assert knn_ref.same(got, ivf_search(ix, Q, k, metric, 2)), (metric, k)
 
 
+@pytest.mark.parametrize("dtype", ["float32", "bfloat16", "float16"])
+@pytest.mark.parametrize("dim", [1, 2, 3, 31, 32, 33, 130])
+def test_refine_of_every_row_over_the_column_tile_borders(dim, dtype):
+    """The re-rank scores its rows with the function the IVF-Flat scan uses (knn_score_gathered): one column, an odd
+    count, one short of / exactly / one past a 32-column tile, several tiles with a tail; every storage type.  With
+    every list probed and refine >= num_rows the answer is Features.search on the same table, bit for bit."""
+    rng = np.random.default_rng(4800 + dim)
+    X, Q = _data(rng, 300, dim, False), _data(rng, 3, dim, False)
+    f = glx.Features(X, dtype=None if dtype == "float32" else dtype)
+    px = f.build_ivfpq(3, 1, niter=1)
+    for metric in METRICS:
+        for k in (1, 300):
+            got = pq_search(px, Q, k, metric, 3, refine=1024)
+            assert knn_ref.same(got, gpu_search(f, Q, k, metric)), (metric, k)
+            if dtype == "float32":
+                assert knn_ref.same(got, knn_ref.search(Q, X, k, metric)), (metric, k)
+
+
+@pytest.fixture(scope="module")
+def forty_thousand_lists():
+    """40,000 rows x 2 columns, every row a list of its own, m = 1; the lists, codebook and codes as the device has them"""
+    rng = np.random.default_rng(49)
+    X = rng.standard_normal((40000, 2)).astype(np.float32)
+    Q = rng.standard_normal((2, 2)).astype(np.float32)
+    ix = glx.Features(X).build_ivf(40000, niter=0, centroids=X)
+    px = ix.build_pq(1, niter=1)
+    return X, Q, px, exported(ix), exported_pq(px)
+
+
+@pytest.mark.parametrize("metric", METRICS)
+def test_probe_slots_of_one_query_take_two_passes(forty_thousand_lists, metric):
+    """The shape of test_gpu_knn_ivf.py's test of this name through the IVF-PQ search, whose slot plan is the same
+    function (knn_slot_plan): 40,000 probed slots of RP = 1,024 keys exceed the workspace budget for one query alone,
+    so the slots go in passes of 32,768 and 7,232."""
+    X, Q, px, index, pq = forty_thousand_lists
+    N, RP = 40000, 1024
+    budget_keys = (256 << 20) // 8
+    assert budget_keys // (N * RP) == 0  # not even one query's slots fit ...
+    P = budget_keys // RP
+    assert [min(P, N - p0) for p0 in range(0, N, P)] == [32768, 7232]  # ... so they go in two passes
+    want = knn_ivfpq_ref.search(Q, X, index, pq, 10, metric, N, refine=RP)
+    # every list is probed, so slot p is list p: the answer must hold rows of both passes for the case to pin the second
+    list_of = np.empty(N, np.int64)
+    list_of[index["list_rows"]] = np.repeat(np.arange(N), np.diff(index["list_ptr"]))
+    assert (list_of[want[0]] >= P).any() and (list_of[want[0]] < P).any()
+    assert knn_ref.same(pq_search(px, Q, 10, metric, N, refine=RP), want)
+
+
 @pytest.mark.parametrize("metric", METRICS)
 def test_found_sets_are_nested_in_refine(metric):
     rng = np.random.default_rng(45)

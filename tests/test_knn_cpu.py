@@ -133,15 +133,19 @@ def test_python_surface_exists():
 
 
 # ---- the host schedule (the arithmetic at the top of knn_search_device), restated ---------------------------------
-KNN_HIP = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "graph-learn_amd", "csrc", "glx_knn.hip")
+KNN_CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "graph-learn_amd", "csrc")
+KNN_HIP = (os.path.join(KNN_CSRC, "glx_knn.h"), os.path.join(KNN_CSRC, "glx_knn.hip"))
 CONST_NAMES = ("kBQ", "kBR", "kBK", "kSortN", "kSelThreads", "kDefaultChunkRows", "kMaxChunkRows",
                "kDefaultFirstChunkRows", "kCandBudgetBytes")
 
 
-def read_constants(path=KNN_HIP):
-    """The constexpr integers of glx_knn.hip, by name; a retune that moves a case off its path fails here."""
-    with open(path) as f:
-        src = f.read()
+def read_constants(paths=KNN_HIP):
+    """The constexpr integers of glx_knn.h and glx_knn.hip, by name; a retune that moves a case off its path fails
+    here."""
+    src = ""
+    for path in paths:
+        with open(path) as f:
+            src += f.read()
     out = {}
     for name in CONST_NAMES:
         m = re.search(r"constexpr\s+\w+\s+%s\s*=\s*([^;]+);" % name, src)
