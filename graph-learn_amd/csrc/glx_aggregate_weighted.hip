@@ -281,7 +281,7 @@ void glx_weighted_bwd_x(int op, const GlxAggTranspose& t, const float* w, const 
   a.dim = dim;
   a.heads = heads;
   a.C = dim / heads;
-  a.seg = GlxSegLayout{t.seg_end, t.fanout, num_ids, num_segments};
+  a.seg = glx_seg_layout_of(t, num_ids, num_segments);
   if (op == GLX_AGG_SUM) launch_wbwd_x<GLX_AGG_SUM>(a, s);
   else launch_wbwd_x<GLX_AGG_MEAN>(a, s);
 }

@@ -55,10 +55,9 @@ struct DotArgs {
   int64_t num_rows;
   int32_t dim, heads, C;
   GlxHeadDots hd;
-  float scale, default_attr, dropscale;
-  uint32_t thresh;         // keep an element iff its word >= thresh
+  float scale, default_attr;
   int32_t drop;            // drop_p != 0
-  uint64_t seed, call;
+  SmDropout dropout;
 };
 
 // Between two passes of a segment the lanes of a group hand values to EACH OTHER through global memory (logit_out /
@@ -76,7 +75,7 @@ __device__ __forceinline__ void dot_handoff() {
 }
 
 __device__ __forceinline__ float dot_drop(const DotArgs& a, float x, int32_t idx) {
-  return a.drop ? sm_dropout(x, idx, a.thresh, a.dropscale, a.seed, a.call) : x;
+  return a.drop ? sm_dropout(x, idx, a.dropout) : x;
 }
 
 // the row of position base + c, tested against the table: -1 reads default_attr
@@ -122,126 +121,55 @@ __device__ __forceinline__ void dot_pass(const DotArgs& a, const float* fix, con
   }
 }
 
-// The items of a segment for the normalisation, glx_segment_softmax's two mappings chosen at run time.  flat (heads a
-// power of two <= G): the segment's [count, heads] block is one run and item i is element s0 * heads + i -- a lane's
-// items share its head c % heads, a butterfly with strides G / 2 .. heads reduces every head at once; otherwise head
-// by head (o), item i being position s0 + i.
-struct DotItems {
-  int32_t s0, H, o, items, min_off, outer;
-  bool flat;
-  __device__ __forceinline__ int32_t idx(int32_t i) const { return flat ? s0 * H + i : (s0 + i) * H + o; }
+// What sm_forward / sm_backward (glx_segment_lanes.h) read and write here.  Forward: lg holds the dot products
+// (logit_out, or soft_out when the caller wants no logits); a register item writes its logit only when logit_out is
+// given, a spilled one parks it in lg, then its exponential in soft_out.  Backward: grad_e holds ga_raw on entry and
+// grad_e on exit.  Both restate alpha for the passes that follow.
+struct DotIo {
+  const DotArgs& a;
+  const SmItems& it;
+  float* lg;
+  static constexpr bool kSum = false;
+  __device__ __forceinline__ float logit(int32_t i) const {
+    const int32_t at = it.idx(i);
+    const float e = glx_pin(lg[at] * a.scale);
+    if (a.logit) a.logit[at] = e;
+    return e;
+  }
+  __device__ __forceinline__ float spill_logit(int32_t i) const {
+    const int32_t at = it.idx(i);
+    return lg[at] = glx_pin(lg[at] * a.scale);
+  }
+  __device__ __forceinline__ float parked_logit(int32_t i) const { return lg[it.idx(i)]; }
+  __device__ __forceinline__ void park_exp(int32_t i, float t) const { a.soft_out[it.idx(i)] = t; }
+  __device__ __forceinline__ float parked_exp(int32_t i) const { return a.soft_out[it.idx(i)]; }
+  __device__ __forceinline__ void emit_soft(int32_t i, float soft) const {
+    const int32_t at = it.idx(i);
+    a.soft_out[at] = soft;
+    if (a.drop) a.alpha[at] = dot_drop(a, soft, at);
+  }
+  __device__ __forceinline__ float soft(int32_t i) const { return a.soft[it.idx(i)]; }
+  __device__ __forceinline__ float grad(int32_t i) const {
+    const int32_t at = it.idx(i);
+    return dot_drop(a, a.grad_e[at], at);
+  }
+  __device__ __forceinline__ float emit_grad(int32_t i, float soft, float d) const {
+    const int32_t at = it.idx(i);
+    a.grad_e[at] = glx_pin(d) * a.scale;
+    if (a.drop) a.alpha[at] = dot_drop(a, soft, at);
+    return 0.0f;
+  }
 };
 
-template <int G>
-__device__ __forceinline__ DotItems dot_items(int32_t s0, int32_t s1, int32_t H) {
-  DotItems it;
-  it.flat = (H & (H - 1)) == 0 && H <= G;
-  it.s0 = s0;
-  it.H = H;
-  it.o = 0;
-  it.items = it.flat ? (s1 - s0) * H : (s1 - s0);  // at most num_ids * heads: int32
-  it.min_off = it.flat ? H : 1;
-  it.outer = it.flat ? 1 : H;
-  return it;
-}
-
-// Forward: lg holds the dot products (logit_out, or soft_out when the caller wants no logits).  Lane c owns items c,
-// c + G, ..; the first kSmR stay in registers, later ones park their logit in lg, then their exponential in soft_out
-// (the same lane writes and reads an element).
-template <int G>
-__device__ __forceinline__ void dot_softmax(const DotArgs& a, DotItems it, int c, float* lg) {
+// The normalisation of a segment by its one group, whatever its length: glx_segment_softmax's two mappings chosen at
+// run time (flat: heads a power of two <= G).
+template <int G, bool BWD>
+__device__ __forceinline__ void dot_normalise(const DotArgs& a, int32_t s0, int32_t s1, int c, float* lg) {
+  const SmGroupWalker<G> w = {c};
+  SmItems it = sm_items((a.heads & (a.heads - 1)) == 0 && a.heads <= G, s0, s1, a.heads);
   for (it.o = 0; it.o < it.outer; ++it.o) {
-    float v[kSmR];
-    float m = -INFINITY;
-#pragma unroll
-    for (int r = 0; r < kSmR; ++r) {
-      const int32_t i = c + r * G;
-      v[r] = -INFINITY;
-      if (i < it.items) {
-        const int32_t at = it.idx(i);
-        v[r] = glx_pin(lg[at] * a.scale);
-        if (a.logit) a.logit[at] = v[r];
-      }
-      m = fmaxf(m, v[r]);
-    }
-    for (int32_t i = c + kSmR * G; i < it.items; i += G) {
-      const int32_t at = it.idx(i);
-      const float e = glx_pin(lg[at] * a.scale);
-      lg[at] = e;
-      m = fmaxf(m, e);
-    }
-    m = sm_group_reduce<SmMax, G>(m, it.min_off);
-    float sum = 0.0f;
-#pragma unroll
-    for (int r = 0; r < kSmR; ++r) {
-      if (c + r * G < it.items) {
-        v[r] = expf(v[r] - m);
-        sum += v[r];
-      }
-    }
-    for (int32_t i = c + kSmR * G; i < it.items; i += G) {
-      const int32_t at = it.idx(i);
-      const float x = expf(lg[at] - m);
-      a.soft_out[at] = x;
-      sum += x;
-    }
-    sum = sm_group_reduce<SmAdd, G>(sum, it.min_off);
-#pragma unroll
-    for (int r = 0; r < kSmR; ++r) {
-      const int32_t i = c + r * G;
-      if (i < it.items) {
-        const int32_t at = it.idx(i);
-        const float soft = v[r] / sum;
-        a.soft_out[at] = soft;
-        if (a.drop) a.alpha[at] = dot_drop(a, soft, at);
-      }
-    }
-    for (int32_t i = c + kSmR * G; i < it.items; i += G) {
-      const int32_t at = it.idx(i);
-      const float soft = a.soft_out[at] / sum;
-      a.soft_out[at] = soft;
-      if (a.drop) a.alpha[at] = dot_drop(a, soft, at);
-    }
-  }
-}
-
-// Backward: grad_e holds ga_raw on entry and grad_e on exit; alpha is restated for the passes that follow.
-template <int G>
-__device__ __forceinline__ void dot_softmax_bwd(const DotArgs& a, DotItems it, int c) {
-  for (it.o = 0; it.o < it.outer; ++it.o) {
-    float av[kSmR], gv[kSmR];
-    float dot = 0.0f;
-#pragma unroll
-    for (int r = 0; r < kSmR; ++r) {
-      const int32_t i = c + r * G;
-      av[r] = gv[r] = 0.0f;
-      if (i < it.items) {
-        const int32_t at = it.idx(i);
-        av[r] = a.soft[at];
-        gv[r] = dot_drop(a, a.grad_e[at], at);
-        dot += av[r] * gv[r];
-      }
-    }
-    for (int32_t i = c + kSmR * G; i < it.items; i += G) {
-      const int32_t at = it.idx(i);
-      dot += a.soft[at] * dot_drop(a, a.grad_e[at], at);
-    }
-    dot = sm_group_reduce<SmAdd, G>(dot, it.min_off);
-#pragma unroll
-    for (int r = 0; r < kSmR; ++r) {
-      const int32_t i = c + r * G;
-      if (i < it.items) {
-        const int32_t at = it.idx(i);
-        a.grad_e[at] = glx_pin(av[r] * (gv[r] - dot)) * a.scale;
-        if (a.drop) a.alpha[at] = dot_drop(a, av[r], at);
-      }
-    }
-    for (int32_t i = c + kSmR * G; i < it.items; i += G) {
-      const int32_t at = it.idx(i);
-      const float soft = a.soft[at];
-      a.grad_e[at] = glx_pin(soft * (dot_drop(a, a.grad_e[at], at) - dot)) * a.scale;
-      if (a.drop) a.alpha[at] = dot_drop(a, soft, at);
-    }
+    if (BWD) sm_backward(w, it, DotIo{a, it, lg});
+    else sm_forward(w, it, DotIo{a, it, lg});
   }
 }
 
@@ -271,7 +199,7 @@ __global__ __launch_bounds__(256) void glx_dot_attention_kernel(DotArgs a) {
       float* const lg = a.logit ? a.logit : a.soft_out;
       dot_pass<G, VEC, SUB>(a, a.q + sg * (int64_t)a.dim, a.k, s0, s1, c, lg);
       dot_handoff<G>();
-      dot_softmax<G>(a, dot_items<G>(s0, s1, a.heads), c, lg);
+      dot_normalise<G, false>(a, s0, s1, c, lg);
       dot_handoff<G>();
     }
     float* const out = a.out + sg * (int64_t)a.dim;
@@ -330,7 +258,7 @@ __global__ __launch_bounds__(256) void glx_dot_attention_bwd_kernel(DotArgs a) {
     if (s1 > s0) {
       dot_pass<G, VEC, SUB>(a, go, a.v, s0, s1, c, a.grad_e);
       dot_handoff<G>();
-      dot_softmax_bwd<G>(a, dot_items<G>(s0, s1, a.heads), c);
+      dot_normalise<G, true>(a, s0, s1, c, nullptr);
       dot_handoff<G>();
     }
     if (a.grad_q || a.grad_edge) {
@@ -416,21 +344,6 @@ void dot_launch(const DotArgs& a, hipStream_t s) {
   else dot_launch_vec<BWD, 1>(a, s);
 }
 
-void dot_fill(DotArgs* a, int64_t num_rows, int32_t dim, int32_t heads, float scale, float default_attr, float drop_p,
-              uint64_t seed, uint64_t call) {
-  a->num_rows = num_rows;
-  a->dim = dim;
-  a->heads = heads;
-  a->C = dim / heads;
-  a->scale = scale;
-  a->default_attr = default_attr;
-  a->dropscale = 1.0f / (1.0f - drop_p);
-  a->thresh = (uint32_t)floor((double)drop_p * 4294967296.0);
-  a->drop = drop_p != 0.0f;
-  a->seed = seed;
-  a->call = call;
-}
-
 }  // namespace
 
 // what the two entry points check alike, before any device use
@@ -489,7 +402,14 @@ extern "C" int glx_dot_attention(int device, const float* q, const float* k, con
       rc = glx_seg_layout(cnt ? d_cnt : nullptr, num_ids, num_segments, st.s, &lease, &a.seg);
       if (rc == GLX_OK && drop_p != 0.0f) rc = alpha.alloc(count * sizeof(float), st.s, 2);
       if (rc == GLX_OK) {
-        dot_fill(&a, num_rows, dim, heads, scale, default_attr, drop_p, seed, call);
+        a.num_rows = num_rows;
+        a.dim = dim;
+        a.heads = heads;
+        a.C = dim / heads;
+        a.scale = scale;
+        a.default_attr = default_attr;
+        a.drop = drop_p != 0.0f;
+        a.dropout = SmDropout(drop_p, seed, call);
         a.alpha = alpha.as<float>();
         a.w = a.drop ? a.alpha : a.soft_out;
         a.soft = a.grad_out = nullptr;
@@ -554,16 +474,18 @@ extern "C" int glx_dot_attention_backward(int device, const float* q, const floa
     } else {
       const bool want_rows = (d_gk != nullptr || d_gv != nullptr) && num_rows > 0;
       GlxAggTranspose tr;
-      if (want_rows) {  // the transpose computes the segment ends on its way: the layout takes them, it scans nothing
-        rc = glx_agg_transpose(a.rows, cnt ? d_cnt : nullptr, num_ids, num_segments, num_rows, st.s, &lease, &tr);
-        if (rc == GLX_OK) rc = glx_seg_layout(nullptr, num_ids, num_segments, st.s, &lease, &a.seg);
-        if (rc == GLX_OK) a.seg.seg_end = tr.seg_end;
-      } else {
-        rc = glx_seg_layout(cnt ? d_cnt : nullptr, num_ids, num_segments, st.s, &lease, &a.seg);
-      }
+      rc = glx_seg_layout_bwd(want_rows, a.rows, cnt ? d_cnt : nullptr, num_ids, num_segments, num_rows, st.s, &lease,
+                              &tr, &a.seg);
       if (rc == GLX_OK && drop_p != 0.0f) rc = alpha.alloc(count * sizeof(float), st.s, 2);
       if (rc == GLX_OK) {
-        dot_fill(&a, num_rows, dim, heads, scale, default_attr, drop_p, seed, call);
+        a.num_rows = num_rows;
+        a.dim = dim;
+        a.heads = heads;
+        a.C = dim / heads;
+        a.scale = scale;
+        a.default_attr = default_attr;
+        a.drop = drop_p != 0.0f;
+        a.dropout = SmDropout(drop_p, seed, call);
         a.alpha = alpha.as<float>();
         a.w = a.drop ? a.alpha : a.soft;
         a.logit = a.soft_out = a.out = nullptr;

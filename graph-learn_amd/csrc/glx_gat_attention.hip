@@ -34,9 +34,8 @@ struct GatArgs {
   float* grad_s;           // backward: [num_segments, heads], or nullptr
   int64_t num_rows;
   int32_t heads;
-  float slope, default_attr, scale;
-  uint32_t thresh;         // keep an element iff its word >= thresh
-  uint64_t seed, call;
+  float slope, default_attr;
+  SmDropout drop;
 };
 
 // s[sg, h] + t[rows[p], h]: one coalesced load of rows per item, a gather of the narrow table t
@@ -48,261 +47,80 @@ __device__ __forceinline__ float gat_pre(const GatArgs& a, float sv, int32_t p, 
 
 __device__ __forceinline__ float gat_leaky(float x, float pre, float slope) { return pre > 0.0f ? x : x * slope; }
 
-// dropout of element idx = p * heads + h of the request: the same function going forward and going back
+// What sm_forward / sm_backward (glx_segment_lanes.h) read and write here, for the items of head h of a segment whose
+// s[sg, h] is sv.  Forward: a spilled item parks its logit, then its exponential, in alpha_out.  Dropout of element
+// idx = p * heads + h is the same function going forward and going back.
 template <bool DROP>
-__device__ __forceinline__ float gat_drop(const GatArgs& a, float x, int32_t idx) {
-  return DROP ? sm_dropout(x, idx, a.thresh, a.scale, a.seed, a.call) : x;
-}
-
-// Item i of a segment that starts at position s0.  FLAT: the segment's [count, heads] block is one run and item i is
-// element s0 * heads + i (position s0 + i / heads; the lane's head is fixed); otherwise item i is position s0 + i of
-// head o.
-template <bool FLAT>
-struct GatItems {
-  int32_t s0, H, o, hshift;
-  __device__ __forceinline__ int32_t idx(int32_t i) const { return FLAT ? s0 * H + i : (s0 + i) * H + o; }
-  __device__ __forceinline__ int32_t pos(int32_t i) const { return FLAT ? s0 + (i >> hshift) : s0 + i; }
+struct GatIo {
+  const GatArgs& a;
+  const SmItems& it;
+  float sv;
+  int h;
+  static constexpr bool kSum = true;  // grad_s
+  __device__ __forceinline__ float drop(float x, int32_t at) const { return DROP ? sm_dropout(x, at, a.drop) : x; }
+  __device__ __forceinline__ float logit(int32_t i) const {
+    const float pre = gat_pre(a, sv, it.pos(i), h);
+    return gat_leaky(pre, pre, a.slope);
+  }
+  __device__ __forceinline__ float spill_logit(int32_t i) const { return a.out[it.idx(i)] = logit(i); }
+  __device__ __forceinline__ float parked_logit(int32_t i) const { return a.out[it.idx(i)]; }
+  __device__ __forceinline__ void park_exp(int32_t i, float t) const { a.out[it.idx(i)] = t; }
+  __device__ __forceinline__ float parked_exp(int32_t i) const { return a.out[it.idx(i)]; }
+  __device__ __forceinline__ void emit_soft(int32_t i, float soft) const {
+    const int32_t at = it.idx(i);
+    if (a.soft_out) a.soft_out[at] = soft;
+    a.out[at] = drop(soft, at);
+  }
+  __device__ __forceinline__ float soft(int32_t i) const { return a.soft[it.idx(i)]; }
+  __device__ __forceinline__ float grad(int32_t i) const {
+    const int32_t at = it.idx(i);
+    return drop(a.g[at], at);
+  }
+  __device__ __forceinline__ float emit_grad(int32_t i, float, float d) const {
+    return a.out[it.idx(i)] = gat_leaky(d, gat_pre(a, sv, it.pos(i), h), a.slope);
+  }
 };
 
-// One (segment, head set) by a group of G lanes: lane c owns items c, c + G, ..; the first kSmR stay in registers,
-// later ones park their logit, then their exponential, in alpha_out between the passes (the same lane writes and
-// reads an element).
-template <int G, bool FLAT, bool DROP>
-__device__ __forceinline__ void gat_fwd_group(const GatArgs& a, const GatItems<FLAT>& it, float sv, int h, int32_t items,
-                                              int min_off, int c) {
-  float v[kSmR];
-  float m = -INFINITY;
-#pragma unroll
-  for (int r = 0; r < kSmR; ++r) {
-    const int32_t i = c + r * G;
-    v[r] = -INFINITY;
-    if (i < items) {
-      const float pre = gat_pre(a, sv, it.pos(i), h);
-      v[r] = gat_leaky(pre, pre, a.slope);
-    }
-    m = fmaxf(m, v[r]);
-  }
-  for (int32_t i = c + kSmR * G; i < items; i += G) {
-    const float pre = gat_pre(a, sv, it.pos(i), h);
-    const float e = gat_leaky(pre, pre, a.slope);
-    a.out[it.idx(i)] = e;
-    m = fmaxf(m, e);
-  }
-  m = sm_group_reduce<SmMax, G>(m, min_off);
-  float sum = 0.0f;
-#pragma unroll
-  for (int r = 0; r < kSmR; ++r) {
-    if (c + r * G < items) {
-      v[r] = expf(v[r] - m);
-      sum += v[r];
-    }
-  }
-  for (int32_t i = c + kSmR * G; i < items; i += G) {
-    const int32_t at = it.idx(i);
-    const float x = expf(a.out[at] - m);
-    a.out[at] = x;
-    sum += x;
-  }
-  sum = sm_group_reduce<SmAdd, G>(sum, min_off);
-#pragma unroll
-  for (int r = 0; r < kSmR; ++r) {
-    const int32_t i = c + r * G;
-    if (i < items) {
-      const int32_t at = it.idx(i);
-      const float soft = v[r] / sum;
-      if (a.soft_out) a.soft_out[at] = soft;
-      a.out[at] = gat_drop<DROP>(a, soft, at);
-    }
-  }
-  for (int32_t i = c + kSmR * G; i < items; i += G) {
-    const int32_t at = it.idx(i);
-    const float soft = a.out[at] / sum;
-    if (a.soft_out) a.soft_out[at] = soft;
-    a.out[at] = gat_drop<DROP>(a, soft, at);
-  }
-}
-
-// Returns the group's sum of grad_e (the same bits in every lane of a head).
-template <int G, bool FLAT, bool DROP>
-__device__ __forceinline__ float gat_bwd_group(const GatArgs& a, const GatItems<FLAT>& it, float sv, int h, int32_t items,
-                                               int min_off, int c) {
-  float av[kSmR], gv[kSmR];
-  float dot = 0.0f;
-#pragma unroll
-  for (int r = 0; r < kSmR; ++r) {
-    const int32_t i = c + r * G;
-    av[r] = gv[r] = 0.0f;
-    if (i < items) {
-      const int32_t at = it.idx(i);
-      av[r] = a.soft[at];
-      gv[r] = gat_drop<DROP>(a, a.g[at], at);
-      dot += av[r] * gv[r];
-    }
-  }
-  for (int32_t i = c + kSmR * G; i < items; i += G) {
-    const int32_t at = it.idx(i);
-    dot += a.soft[at] * gat_drop<DROP>(a, a.g[at], at);
-  }
-  dot = sm_group_reduce<SmAdd, G>(dot, min_off);
-  float gs = 0.0f;
-#pragma unroll
-  for (int r = 0; r < kSmR; ++r) {
-    const int32_t i = c + r * G;
-    if (i < items) {
-      const float ge = gat_leaky(av[r] * (gv[r] - dot), gat_pre(a, sv, it.pos(i), h), a.slope);
-      a.out[it.idx(i)] = ge;
-      gs += ge;
-    }
-  }
-  for (int32_t i = c + kSmR * G; i < items; i += G) {
-    const int32_t at = it.idx(i);
-    const float d = a.soft[at] * (gat_drop<DROP>(a, a.g[at], at) - dot);
-    const float ge = gat_leaky(d, gat_pre(a, sv, it.pos(i), h), a.slope);
-    a.out[at] = ge;
-    gs += ge;
-  }
-  return sm_group_reduce<SmAdd, G>(gs, min_off);
-}
-
-// A long segment by the whole workgroup: thread t owns items t, t + 256, ..
-template <bool FLAT, bool DROP>
-__device__ __forceinline__ void gat_fwd_block(const GatArgs& a, const GatItems<FLAT>& it, float sv, int h, int32_t items,
-                                              int min_off, float* red) {
-  const int tid = threadIdx.x;
-  float m = -INFINITY;
-  for (int32_t i = tid; i < items; i += 256) {
-    const float pre = gat_pre(a, sv, it.pos(i), h);
-    const float e = gat_leaky(pre, pre, a.slope);
-    a.out[it.idx(i)] = e;
-    m = fmaxf(m, e);
-  }
-  m = sm_block_reduce<SmMax>(m, min_off, red);
-  float sum = 0.0f;
-  for (int32_t i = tid; i < items; i += 256) {
-    const int32_t at = it.idx(i);
-    const float x = expf(a.out[at] - m);
-    a.out[at] = x;
-    sum += x;
-  }
-  sum = sm_block_reduce<SmAdd>(sum, min_off, red);
-  for (int32_t i = tid; i < items; i += 256) {
-    const int32_t at = it.idx(i);
-    const float soft = a.out[at] / sum;
-    if (a.soft_out) a.soft_out[at] = soft;
-    a.out[at] = gat_drop<DROP>(a, soft, at);
-  }
-}
-
-template <bool FLAT, bool DROP>
-__device__ __forceinline__ float gat_bwd_block(const GatArgs& a, const GatItems<FLAT>& it, float sv, int h, int32_t items,
-                                               int min_off, float* red) {
-  const int tid = threadIdx.x;
-  float dot = 0.0f;
-  for (int32_t i = tid; i < items; i += 256) {
-    const int32_t at = it.idx(i);
-    dot += a.soft[at] * gat_drop<DROP>(a, a.g[at], at);
-  }
-  dot = sm_block_reduce<SmAdd>(dot, min_off, red);
-  float gs = 0.0f;
-  for (int32_t i = tid; i < items; i += 256) {
-    const int32_t at = it.idx(i);
-    const float d = a.soft[at] * (gat_drop<DROP>(a, a.g[at], at) - dot);
-    const float ge = gat_leaky(d, gat_pre(a, sv, it.pos(i), h), a.slope);
-    a.out[at] = ge;
-    gs += ge;
-  }
-  return sm_block_reduce<SmAdd>(gs, min_off, red);
-}
-
-// The mapping of glx_segment_softmax_kernel: G lanes own one segment, a workgroup 256 / G consecutive segments; FLAT
-// (heads a power of two <= G) reduces every head at once with strides G / 2 .. heads, otherwise head by head.  A
-// segment of more than kSmLongItems items is left to the second phase, where the whole workgroup walks it.  Last, the
-// workgroups share the positions nobody consumed: +0.0f.  No thread leaves before the end.
+// The mapping of glx_segment_softmax_kernel (sm_segment_walk, glx_segment_lanes.h): G lanes own one segment, a
+// workgroup 256 / G consecutive segments; FLAT (heads a power of two <= G) reduces every head at once with strides
+// G / 2 .. heads, otherwise head by head.  A segment of more than kSmLongItems items is left to the second phase, where
+// the whole workgroup walks it.  Last, the workgroups share the positions nobody consumed: +0.0f.  No thread leaves
+// before the end.
 template <int G, bool FLAT, bool DROP, bool BWD>
 __global__ __launch_bounds__(256) void glx_gat_attention_kernel(GatArgs a) {
   __shared__ float red[256];
-  constexpr int kSegs = 256 / G;
-  const int c = threadIdx.x & (G - 1);
   const int H = a.heads;
-  const int min_off = FLAT ? H : 1;
-  const int outer = FLAT ? 1 : H;
-  const int64_t first = blockIdx.x * (int64_t)kSegs;
-  GatItems<FLAT> it;
-  it.H = H;
-  it.s0 = 0;
-  it.o = 0;
-  it.hshift = FLAT ? __ffs(H) - 1 : 0;
-  {
-    const int64_t sg = first + threadIdx.x / G;
-    if (sg < a.seg.num_segments) {  // the same answer in every lane of the group
-      int32_t s0, s1;
-      seg_bounds(a.seg, sg, &s0, &s1);
-      const int64_t items = FLAT ? (int64_t)(s1 - s0) * H : (int64_t)(s1 - s0);
-      it.s0 = s0;
-      if (items > 0 && items <= kSmLongItems) {
-        for (int o = 0; o < outer; ++o) {
-          const int h = FLAT ? (c & (H - 1)) : o;
-          const float sv = a.s[sg * H + h];
-          it.o = o;
-          if (BWD) {
-            const float gs = gat_bwd_group<G, FLAT, DROP>(a, it, sv, h, (int32_t)items, min_off, c);
-            if (a.grad_s && c < min_off) a.grad_s[sg * H + h] = gs;
-          } else {
-            gat_fwd_group<G, FLAT, DROP>(a, it, sv, h, (int32_t)items, min_off, c);
-          }
+  sm_segment_walk<G>(
+      a.seg, H, FLAT, red,
+      [&](const auto& w, const SmItems& it, int64_t sg) {
+        const int h = FLAT ? (w.lane() & (H - 1)) : it.o;
+        const GatIo<DROP> io = {a, it, a.s[sg * H + h], h};
+        if (BWD) {
+          const float gs = sm_backward(w, it, io);  // the same bits in every lane of a head
+          if (a.grad_s && w.lane() < it.min_off) a.grad_s[sg * H + h] = gs;
+        } else {
+          sm_forward(w, it, io);
         }
-      } else if (BWD && items == 0 && a.grad_s) {  // an empty segment: +0.0f
-        for (int h = c; h < H; h += G) a.grad_s[sg * H + h] = 0.0f;
-      }
-    }
-  }
-  for (int j = 0; j < kSegs; ++j) {  // every condition below is the same in all 256 threads
-    const int64_t sg = first + j;
-    if (sg >= a.seg.num_segments) break;
-    int32_t s0, s1;
-    seg_bounds(a.seg, sg, &s0, &s1);
-    const int64_t items = FLAT ? (int64_t)(s1 - s0) * H : (int64_t)(s1 - s0);
-    if (items <= kSmLongItems) continue;
-    it.s0 = s0;
-    for (int o = 0; o < outer; ++o) {
-      const int h = FLAT ? ((int)threadIdx.x & (H - 1)) : o;
-      const float sv = a.s[sg * H + h];
-      it.o = o;
-      if (BWD) {
-        const float gs = gat_bwd_block<FLAT, DROP>(a, it, sv, h, (int32_t)items, min_off, red);
-        if (a.grad_s && (int)threadIdx.x < min_off) a.grad_s[sg * H + h] = gs;
-      } else {
-        gat_fwd_block<FLAT, DROP>(a, it, sv, h, (int32_t)items, min_off, red);
-      }
-    }
-  }
-  const int64_t tail = seg_tail(a.seg);
-  const int64_t end = (int64_t)a.seg.num_ids * H;
-  for (int64_t i = tail * H + blockIdx.x * 256LL + threadIdx.x; i < end; i += gridDim.x * 256LL) {
-    a.out[i] = 0.0f;
-    if (!BWD && a.soft_out) a.soft_out[i] = 0.0f;
-  }
-}
-
-template <bool FLAT, bool DROP, bool BWD>
-void gat_launch_g(const GatArgs& a, int G, hipStream_t s) {
-  const unsigned blocks = sm_blocks(G, a.heads, a.seg.num_ids, a.seg.num_segments);
-  glx_for_group(G, [&](auto g) {
-    glx_gat_attention_kernel<decltype(g)::value, FLAT, DROP, BWD><<<blocks, 256, 0, s>>>(a);
-  });
+      },
+      [&](int64_t sg, int c) {  // an empty segment: +0.0f
+        if (BWD && a.grad_s) {
+          for (int h = c; h < H; h += G) a.grad_s[sg * H + h] = 0.0f;
+        }
+      },
+      [&](int64_t i) {
+        a.out[i] = 0.0f;
+        if (!BWD && a.soft_out) a.soft_out[i] = 0.0f;
+      });
 }
 
 template <bool BWD>
 void gat_launch(const GatArgs& a, bool drop, hipStream_t s) {
-  bool flat;
-  const int G = sm_width(a.heads, a.seg.num_ids, a.seg.num_segments, &flat);
-  if (flat) {
-    if (drop) gat_launch_g<true, true, BWD>(a, G, s);
-    else gat_launch_g<true, false, BWD>(a, G, s);
-  } else {
-    if (drop) gat_launch_g<false, true, BWD>(a, G, s);
-    else gat_launch_g<false, false, BWD>(a, G, s);
-  }
+  sm_for_launch(a.heads, a.seg, [&](auto g, auto flat, unsigned blocks) {
+    constexpr int kG = decltype(g)::value;
+    constexpr bool kFlat = decltype(flat)::value;
+    if (drop) glx_gat_attention_kernel<kG, kFlat, true, BWD><<<blocks, 256, 0, s>>>(a);
+    else glx_gat_attention_kernel<kG, kFlat, false, BWD><<<blocks, 256, 0, s>>>(a);
+  });
 }
 
 // grad_t: one lane per (row, head) walks the row's positions in ascending order (the transpose's stable sort), so
@@ -320,18 +138,6 @@ __global__ __launch_bounds__(256) void glx_gat_grad_t_kernel(const int32_t* __re
   float acc = 0.0f;
   for (int32_t j = l0; j < l1; ++j) acc = acc + grad_e[(int64_t)pos[j] * heads + h];
   grad_t[i] = acc;
-}
-
-void gat_fill(GatArgs* a, int64_t num_rows, int32_t heads, float negative_slope, float default_attr, float drop_p,
-              uint64_t seed, uint64_t call) {
-  a->num_rows = num_rows;
-  a->heads = heads;
-  a->slope = negative_slope;
-  a->default_attr = default_attr;
-  a->scale = 1.0f / (1.0f - drop_p);
-  a->thresh = (uint32_t)floor((double)drop_p * 4294967296.0);
-  a->seed = seed;
-  a->call = call;
 }
 
 }  // namespace
@@ -385,7 +191,11 @@ extern "C" int glx_gat_attention(int device, const float* s, const float* t, int
       if (rc == GLX_OK) {
         a.soft = a.g = nullptr;
         a.grad_s = nullptr;
-        gat_fill(&a, num_rows, heads, negative_slope, default_attr, drop_p, seed, call);
+        a.num_rows = num_rows;
+        a.heads = heads;
+        a.slope = negative_slope;
+        a.default_attr = default_attr;
+        a.drop = SmDropout(drop_p, seed, call);
         gat_launch<false>(a, drop_p != 0.0f, st.s);
       }
     }
@@ -433,16 +243,15 @@ extern "C" int glx_gat_attention_backward(int device, const float* soft, const f
     } else {
       const bool want_t = d_gt != nullptr && num_rows > 0;
       GlxAggTranspose tr;
-      if (want_t) {  // the transpose computes the segment ends on its way: the layout takes them, it scans nothing
-        rc = glx_agg_transpose(a.rows, d_cnt, num_ids, num_segments, num_rows, st.s, &lease, &tr);
-        if (rc == GLX_OK) rc = glx_seg_layout(nullptr, num_ids, num_segments, st.s, &lease, &a.seg);
-        if (rc == GLX_OK) a.seg.seg_end = tr.seg_end;
-      } else {
-        rc = glx_seg_layout(cnt ? d_cnt : nullptr, num_ids, num_segments, st.s, &lease, &a.seg);
-      }
+      rc = glx_seg_layout_bwd(want_t, a.rows, cnt ? d_cnt : nullptr, num_ids, num_segments, num_rows, st.s, &lease, &tr,
+                              &a.seg);
       if (rc == GLX_OK) {
         a.soft_out = nullptr;
-        gat_fill(&a, num_rows, heads, negative_slope, default_attr, drop_p, seed, call);
+        a.num_rows = num_rows;
+        a.heads = heads;
+        a.slope = negative_slope;
+        a.default_attr = default_attr;
+        a.drop = SmDropout(drop_p, seed, call);
         gat_launch<true>(a, drop_p != 0.0f, st.s);
         if (want_t) {
           const int64_t total = (int64_t)t_count;

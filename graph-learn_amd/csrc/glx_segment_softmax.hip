@@ -23,96 +23,37 @@ struct SmArgs {
   int32_t heads;
 };
 
-// One (segment, head set) by a group of G lanes.  The lane's items are base[i * stride], i = c, c + G, ..; the first
-// kSmR of them stay in registers between the passes, later ones are read again (and the exponentials parked in out).
-template <int G>
-__device__ __forceinline__ void sm_fwd_group(const float* __restrict__ e, float* __restrict__ out, int32_t items,
-                                             int32_t stride, int min_off, int c) {
-  float v[kSmR];
-  float m = -INFINITY;
-#pragma unroll
-  for (int r = 0; r < kSmR; ++r) {
-    const int32_t i = c + r * G;
-    v[r] = i < items ? e[i * stride] : -INFINITY;
-    m = fmaxf(m, v[r]);
-  }
-  for (int32_t i = c + kSmR * G; i < items; i += G) m = fmaxf(m, e[i * stride]);
-  m = sm_group_reduce<SmMax, G>(m, min_off);
-  float sum = 0.0f;
-#pragma unroll
-  for (int r = 0; r < kSmR; ++r) {
-    if (c + r * G < items) {
-      v[r] = expf(v[r] - m);
-      sum += v[r];
-    }
-  }
-  for (int32_t i = c + kSmR * G; i < items; i += G) {
-    const float t = expf(e[i * stride] - m);
-    out[i * stride] = t;
-    sum += t;
-  }
-  sum = sm_group_reduce<SmAdd, G>(sum, min_off);
-#pragma unroll
-  for (int r = 0; r < kSmR; ++r) {
-    const int32_t i = c + r * G;
-    if (i < items) out[i * stride] = v[r] / sum;
-  }
-  for (int32_t i = c + kSmR * G; i < items; i += G) out[i * stride] = out[i * stride] / sum;
+// What sm_forward / sm_backward (glx_segment_lanes.h) read and write here: item i of the (segment, head set) is element
+// i * stride from its first one.  a: the logits e going forward, alpha going back.  Forward: pass 2 reads e again, it
+// parks no logit; a spilled item's exponential is parked in out.
+struct SmIo {
+  const float* a;
+  const float* g;
+  float* out;
+  int32_t stride;
+  static constexpr bool kSum = false;
+  template <typename I> __device__ __forceinline__ float logit(I i) const { return a[i * stride]; }
+  template <typename I> __device__ __forceinline__ float spill_logit(I i) const { return logit(i); }
+  template <typename I> __device__ __forceinline__ float parked_logit(I i) const { return logit(i); }
+  template <typename I> __device__ __forceinline__ void park_exp(I i, float t) const { out[i * stride] = t; }
+  template <typename I> __device__ __forceinline__ float parked_exp(I i) const { return out[i * stride]; }
+  template <typename I> __device__ __forceinline__ void emit_soft(I i, float soft) const { out[i * stride] = soft; }
+  template <typename I> __device__ __forceinline__ float soft(I i) const { return a[i * stride]; }
+  template <typename I> __device__ __forceinline__ float grad(I i) const { return g[i * stride]; }
+  template <typename I> __device__ __forceinline__ float emit_grad(I i, float, float d) const { return out[i * stride] = d; }
+};
+
+// One (segment, head set) from its first element on.  The inputs never alias the output: the loads of a later item
+// may pass the stores of an earlier one.
+template <bool BWD, typename W>
+__device__ __forceinline__ void sm_one(const W& w, const SmItems& it, const float* __restrict__ a,
+                                       const float* __restrict__ g, float* __restrict__ out) {
+  const SmIo io = {a, g, out, it.flat ? 1 : it.H};
+  if (BWD) sm_backward(w, it, io);
+  else sm_forward(w, it, io);
 }
 
-template <int G>
-__device__ __forceinline__ void sm_bwd_group(const float* __restrict__ alpha, const float* __restrict__ grad,
-                                             float* __restrict__ out, int32_t items, int32_t stride, int min_off,
-                                             int c) {
-  float av[kSmR], gv[kSmR];
-  float dot = 0.0f;
-#pragma unroll
-  for (int r = 0; r < kSmR; ++r) {
-    const int32_t i = c + r * G;
-    if (i < items) {
-      av[r] = alpha[i * stride];
-      gv[r] = grad[i * stride];
-      dot += av[r] * gv[r];
-    }
-  }
-  for (int32_t i = c + kSmR * G; i < items; i += G) dot += alpha[i * stride] * grad[i * stride];
-  dot = sm_group_reduce<SmAdd, G>(dot, min_off);
-#pragma unroll
-  for (int r = 0; r < kSmR; ++r) {
-    const int32_t i = c + r * G;
-    if (i < items) out[i * stride] = av[r] * (gv[r] - dot);
-  }
-  for (int32_t i = c + kSmR * G; i < items; i += G) out[i * stride] = alpha[i * stride] * (grad[i * stride] - dot);
-}
-
-// A long segment by the whole workgroup: thread t owns items t, t + 256, ..; three passes over memory.
-__device__ __forceinline__ void sm_fwd_block(const float* __restrict__ e, float* __restrict__ out, int64_t items,
-                                             int32_t stride, int min_off, float* red) {
-  const int tid = threadIdx.x;
-  float m = -INFINITY;
-  for (int64_t i = tid; i < items; i += 256) m = fmaxf(m, e[i * stride]);
-  m = sm_block_reduce<SmMax>(m, min_off, red);
-  float sum = 0.0f;
-  for (int64_t i = tid; i < items; i += 256) {
-    const float t = expf(e[i * stride] - m);
-    out[i * stride] = t;
-    sum += t;
-  }
-  sum = sm_block_reduce<SmAdd>(sum, min_off, red);
-  for (int64_t i = tid; i < items; i += 256) out[i * stride] = out[i * stride] / sum;
-}
-
-__device__ __forceinline__ void sm_bwd_block(const float* __restrict__ alpha, const float* __restrict__ grad,
-                                             float* __restrict__ out, int64_t items, int32_t stride, int min_off,
-                                             float* red) {
-  const int tid = threadIdx.x;
-  float dot = 0.0f;
-  for (int64_t i = tid; i < items; i += 256) dot += alpha[i * stride] * grad[i * stride];
-  dot = sm_block_reduce<SmAdd>(dot, min_off, red);
-  for (int64_t i = tid; i < items; i += 256) out[i * stride] = alpha[i * stride] * (grad[i * stride] - dot);
-}
-
-// G lanes own one segment; a workgroup owns 256 / G consecutive segments.
+// sm_segment_walk's mapping (glx_segment_lanes.h): G lanes own one segment; a workgroup owns 256 / G consecutive ones.
 //   FLAT  (heads a power of two <= G)  the segment's [count, heads] block is one run of count * heads items; lane c
 //         owns items c, c + G, .. -- all of head c % heads, because heads divides G -- and a butterfly with strides
 //         G / 2 .. heads reduces every head at once.  Consecutive lanes read consecutive floats.
@@ -120,65 +61,24 @@ __device__ __forceinline__ void sm_bwd_block(const float* __restrict__ alpha, co
 //         whole group reduces.
 // A segment of more than kSmLongItems items is left to the second phase, where the whole workgroup walks it (the same
 // mapping with 256 lanes, reduced through LDS).  Last, the workgroups share the positions nobody consumed: +0.0f.
-// No thread leaves before the end: the second phase synchronises the workgroup.
 template <int G, bool FLAT, bool BWD>
 __global__ __launch_bounds__(256) void glx_segment_softmax_kernel(SmArgs a) {
   __shared__ float red[256];
-  constexpr int kSegs = 256 / G;
-  const int c = threadIdx.x & (G - 1);
-  const int H = a.heads;
-  const int32_t stride = FLAT ? 1 : H;
-  const int min_off = FLAT ? H : 1;
-  const int outer = FLAT ? 1 : H;
-  const int64_t first = blockIdx.x * (int64_t)kSegs;
-  {
-    const int64_t sg = first + threadIdx.x / G;
-    if (sg < a.seg.num_segments) {  // the same answer in every lane of the group
-      int32_t s0, s1;
-      seg_bounds(a.seg, sg, &s0, &s1);
-      const int64_t items = FLAT ? (int64_t)(s1 - s0) * H : (int64_t)(s1 - s0);
-      if (items > 0 && items <= kSmLongItems) {
-        for (int o = 0; o < outer; ++o) {
-          const int64_t at = (int64_t)s0 * H + o;
-          if (BWD) sm_bwd_group<G>(a.a + at, a.g + at, a.out + at, (int32_t)items, stride, min_off, c);
-          else sm_fwd_group<G>(a.a + at, a.out + at, (int32_t)items, stride, min_off, c);
-        }
-      }
-    }
-  }
-  for (int j = 0; j < kSegs; ++j) {  // every condition below is the same in all 256 threads
-    const int64_t sg = first + j;
-    if (sg >= a.seg.num_segments) break;
-    int32_t s0, s1;
-    seg_bounds(a.seg, sg, &s0, &s1);
-    const int64_t items = FLAT ? (int64_t)(s1 - s0) * H : (int64_t)(s1 - s0);
-    if (items <= kSmLongItems) continue;
-    for (int o = 0; o < outer; ++o) {
-      const int64_t at = (int64_t)s0 * H + o;
-      if (BWD) sm_bwd_block(a.a + at, a.g + at, a.out + at, items, stride, min_off, red);
-      else sm_fwd_block(a.a + at, a.out + at, items, stride, min_off, red);
-    }
-  }
-  const int64_t tail = seg_tail(a.seg);
-  const int64_t end = (int64_t)a.seg.num_ids * H;
-  for (int64_t i = tail * H + blockIdx.x * 256LL + threadIdx.x; i < end; i += gridDim.x * 256LL) a.out[i] = 0.0f;
-}
-
-template <bool FLAT, bool BWD>
-void sm_launch_g(const SmArgs& a, int G, hipStream_t s) {
-  const unsigned blocks = sm_blocks(G, a.heads, a.seg.num_ids, a.seg.num_segments);
-  glx_for_group(G, [&](auto g) {
-    glx_segment_softmax_kernel<decltype(g)::value, FLAT, BWD><<<blocks, 256, 0, s>>>(a);
-  });
+  sm_segment_walk<G>(
+      a.seg, a.heads, FLAT, red,
+      [&](const auto& w, const SmItems& it, int64_t) {
+        const int32_t at = it.idx(0);
+        sm_one<BWD>(w, it, a.a + at, BWD ? a.g + at : nullptr, a.out + at);
+      },
+      [](int64_t, int) {}, [&](int64_t i) { a.out[i] = 0.0f; });
 }
 
 // the group width and the item mapping: sm_width (glx_segment_lanes.h)
 template <bool BWD>
 void sm_launch(const SmArgs& a, hipStream_t s) {
-  bool flat;
-  const int G = sm_width(a.heads, a.seg.num_ids, a.seg.num_segments, &flat);
-  if (flat) sm_launch_g<true, BWD>(a, G, s);
-  else sm_launch_g<false, BWD>(a, G, s);
+  sm_for_launch(a.heads, a.seg, [&](auto g, auto flat, unsigned blocks) {
+    glx_segment_softmax_kernel<decltype(g)::value, decltype(flat)::value, BWD><<<blocks, 256, 0, s>>>(a);
+  });
 }
 
 // the body both entry points share, behind their argument checks
