@@ -22,11 +22,16 @@ and the --refine best candidates by the coded score are re-scored from the table
 itself).  With --refine > 0 the distances it returns are exact too; what it can miss in addition are rows the coded score
 ranked below the first --refine.
 
+--dtype bfloat16 | float16 | float8_e4m3fn | float8_e5m2 also stores the item table in that type (rounded on the device
+while it is uploaded) and adds one line per search: the exact search on the narrow table, its metrics and its recall
+against the float32 table's answer -- what the rounding of the stored rows costs; the queries stay float32.
+
 Exits non-zero unless two runs give the same bits and the ids equal the float64 brute force (with --index ivf or ivfpq:
 and two index searches give the same bits, and the index with every list probed equals the exact search bit for bit;
 with --index ivfpq and --refine > 0: and every distance the coded index returns is the exact search's for that id).
 Usage: python examples/eval_recall.py [--items 4000] [--users 1000] [--dim 16] [--k 10]
-                                      [--index flat|ivf|ivfpq] [--nlist 64] [--nprobe 4] [--m 4] [--refine 100]"""
+                                      [--index flat|ivf|ivfpq] [--nlist 64] [--nprobe 4] [--m 4] [--refine 100]
+                                      [--dtype float32|bfloat16|float16|float8_e4m3fn|float8_e5m2]"""
 import argparse
 import math
 import os
@@ -80,10 +85,12 @@ def main():
     ap.add_argument("--nprobe", type=int, default=4)
     ap.add_argument("--m", type=int, default=4)
     ap.add_argument("--refine", type=int, default=100)
+    ap.add_argument("--dtype", choices=sorted(dict(glx.FEATURE_DTYPES, **glx.FP8_FEATURE_DTYPES)), default="float32")
     a = ap.parse_args()
     rng = np.random.default_rng(0)
     items, item_ids, users, user_group = planted(rng, a.items, a.users, a.dim, a.group)
     table = glx.Features(items, ids=item_ids)
+    narrow = glx.Features(items, ids=item_ids, dtype=a.dtype) if a.dtype != "float32" else None
     index = table.build_ivf(a.nlist) if a.index in ("ivf", "ivfpq") else None
     coded = index.build_pq(a.m) if a.index == "ivfpq" else None
     d_ids = torch.from_numpy(item_ids).cuda()
@@ -102,6 +109,15 @@ def main():
             print("%s %s  recall@%d %.4f  ndcg@%d %.4f  hit rate %.4f  two runs same bits: %s  ids == float64 brute force: %s"
                   % (task, metric, a.k, r, a.k, n, h, same_bits, exact))
             ok = ok and same_bits and exact and not math.isnan(r)
+            if narrow is not None:
+                nids, ndist = narrow.search(dq, a.k, metric)
+                nids2, ndist2 = narrow.search(dq, a.k, metric)
+                same_bits = bool(torch.equal(nids, nids2) and torch.equal(ndist.view(torch.int32), ndist2.view(torch.int32)))
+                r, n, h = metrics(nids, truth, a.k)
+                vs_f32 = (nids[:, :, None] == ids[:, None, :]).any(1).float().mean().item()
+                print("%s %s  table stored as %s  recall@%d %.4f  ndcg@%d %.4f  hit rate %.4f  recall vs float32 table %.4f  "
+                      "two runs same bits: %s" % (task, metric, a.dtype, a.k, r, a.k, n, h, vs_f32, same_bits))
+                ok = ok and same_bits
             if index is None:
                 continue
             got, gdist = index.search(dq, a.k, metric, nprobe=a.nprobe)

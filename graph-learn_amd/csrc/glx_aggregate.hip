@@ -364,6 +364,42 @@ __host__ __device__ __forceinline__ uint16_t glx_f32_to_f16_bits(uint32_t u) {
   const uint32_t q = mant >> sh, rem = mant & ((1u << sh) - 1u), half = 1u << (sh - 1u);
   return (uint16_t)(sign | (q + ((rem > half || (rem == half && (q & 1u))) ? 1u : 0u)));  // q + 1 may be 0x400 = 2^-14
 }
+// float32 -> OCP float8, round to nearest even, bit-identical to torch.Tensor.to(torch.float8_e4m3fn /
+// torch.float8_e5m2) of a contiguous CPU tensor; integer arithmetic only.  MBITS mantissa bits under a BIAS-biased
+// exponent; `a` is |x|'s bits, below the type's overflow threshold.
+template <int MBITS, int BIAS>
+__host__ __device__ __forceinline__ uint32_t glx_f32_to_f8_finite(uint32_t a) {
+  constexpr uint32_t kDrop = 23u - MBITS;                   // float32 mantissa bits rounded off
+  constexpr uint32_t kMinNormal = (uint32_t)(127 - BIAS + 1) << 23;  // 2^(1 - BIAS)
+  if (a >= kMinNormal) {  // rebias the exponent, round; a carry out of the mantissa rounds up to the next binade
+    const uint32_t m = a - ((uint32_t)(127 - BIAS) << 23);
+    return (m + ((1u << (kDrop - 1u)) - 1u) + ((m >> kDrop) & 1u)) >> kDrop;
+  }
+  // a subnormal: round(|x| / 2^(1 - BIAS - MBITS)); |x| = mant 2^(e - 150), so shift the 24-bit significand
+  const uint32_t e = a >> 23;
+  const uint32_t sh = (uint32_t)(150 + 1 - BIAS - MBITS) - e;  // > kDrop
+  if (sh >= 25u) return 0u;  // under half the smallest subnormal (float32 subnormals and zeros included)
+  const uint32_t mant = (a & 0x7fffffu) | 0x800000u;
+  const uint32_t q = mant >> sh, rem = mant & ((1u << sh) - 1u), half = 1u << (sh - 1u);
+  return q + ((rem > half || (rem == half && (q & 1u))) ? 1u : 0u);  // q + 1 may be the smallest normal
+}
+// e4m3fn has no infinity: 464 (the tie between 448 and the absent 480) still rounds to even = 448 = 0x7E, everything
+// above it reaches the code 0x7F = NaN by the rounding's own carry -- overflow is NaN, not saturation -- and so do
+// +-inf and every NaN (sign kept).
+__host__ __device__ __forceinline__ uint8_t glx_f32_to_f8e4m3_bits(uint32_t u) {
+  const uint32_t sign = (u >> 24) & 0x80u;
+  const uint32_t a = u & 0x7fffffffu;
+  if (a >= 0x43F00000u) return (uint8_t)(sign | 0x7Fu);  // >= 480, inf, NaN
+  return (uint8_t)(sign | glx_f32_to_f8_finite<3, 7>(a));
+}
+// e5m2: 57344 is the largest number (0x7B); 61440 (the tie) and above is inf (0x7C); a NaN is sign | 0x7F.
+__host__ __device__ __forceinline__ uint8_t glx_f32_to_f8e5m2_bits(uint32_t u) {
+  const uint32_t sign = (u >> 24) & 0x80u;
+  const uint32_t a = u & 0x7fffffffu;
+  if (a > 0x7f800000u) return (uint8_t)(sign | 0x7Fu);
+  if (a >= 0x47800000u) return (uint8_t)(sign | 0x7Cu);  // >= 65536 (61440 .. 65536 round up to it below)
+  return (uint8_t)(sign | glx_f32_to_f8_finite<2, 15>(a));
+}
 
 struct AggArgs {
   const void* X;             // elements of `dtype` (X1 / X2 below: float32 only)
@@ -918,8 +954,9 @@ struct AggKnobs {
   std::atomic<int> store{0};    // GLX_AGG_STORE=1: plain output stores instead of non-temporal ones (ablation)
   std::atomic<int> stripes{-1}; // GLX_AGG_XCD_STRIPES=0: workgroup j of a slice reduces segment block j (no XCD stripes); 1 = on; -1 = default
   std::atomic<int> chunk{0};    // GLX_AGG_XCD_CHUNK: segment blocks per XCD stripe chunk (0 = kXcdStripeChunk)
-  std::atomic<int> half_ld16{0};// GLX_AGG_HALF_LD16=1: half tables in the grouped kernel with 16-byte loads of 8 columns per
-                                // lane instead of 8-byte loads over the float32 lane-to-column map (ablation)
+  std::atomic<int> half_ld16{0};// GLX_AGG_HALF_LD16=1: half and float8 tables in the grouped kernel with 8 columns per lane
+                                // (16-byte loads of halves, 8-byte loads of float8); 2: 4 columns per lane, the float32
+                                // lane-to-column map, for every type; 0 = default (launch_agg_cols: 4, float8 rows of >= 256: 8)
   std::atomic<int> repeats{0};  // GLX_AGG_REPEATS=1: Max / Min load every position of a segment, repeated rows included (ablation);
                                 // 2: first occurrences only whatever the segment length; 0 = by length (launch_agg_grp)
   std::atomic<int> seg_parent{0};  // GLX_SEG_SCAN_PARENT=1: explicit segment_ids with the scan and fix-up launches of rounds 5..24 (A/B)
@@ -1075,20 +1112,33 @@ void launch_agg_grp_g(const AggArgs& a, int lanes, int32_t num_ids, hipStream_t 
 template <int OP, int NSRC, int DT>
 void launch_agg_cols(const AggArgs& a0, int32_t num_ids, int want_xcd, hipStream_t s) {
   AggArgs a = a0;
-  // the per-segment kernel's VEC = 4 path: 4 elements per lane (16 bytes of floats, 8 of halves)
+  // the per-segment kernel's VEC = 4 path: 4 elements per lane (16 bytes of floats, 8 of halves, 4 of float8).  The
+  // tests below are in elements: a 16-byte-aligned base and a pitch that is a multiple of 4 elements keep every
+  // 4-column load aligned for every element size, one byte included -- so an odd dim, an odd view pitch or a view
+  // whose base is off by 1-3 bytes takes the scalar path.
   bool vec4 = a.dim % 4 == 0 && a.ncols % 4 == 0 && a.col0 % 4 == 0 && (reinterpret_cast<uintptr_t>(a.emb_out) & 15) == 0 &&
               (reinterpret_cast<uintptr_t>(a.X) & 15) == 0 && (a.stride % 4) == 0;
   if (NSRC > 1) {
     vec4 = vec4 && (reinterpret_cast<uintptr_t>(a.X1) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.X2) & 15) == 0 &&
            (a.stride1 % 4) == 0 && (a.stride2 % 4) == 0;
   }
-  // the grouped kernel: EV = 4 elements per lane, one load per row -- 16 bytes of floats, 8 of halves -- so a half
-  // table keeps the float32 lane-to-column map, group size and slicing.  Measured on the C3 hop-2 request
+  // the grouped kernel: EV = 4 elements per lane, one load per row -- 16 bytes of floats, 8 of halves, 4 of float8
+  // -- so a half table keeps the float32 lane-to-column map, group size and slicing.  Measured on the C3 hop-2 request
   // (profiles/r08/half_features.txt, bfloat16, same process, ms): 8-byte loads 1.24 (whole rows) / 1.33 (two slices)
   // against 16-byte loads of 8 columns per lane -- half the lanes per segment, so G = 32 at D = 256 and no scalar
   // row path -- 1.62 / 1.65, no faster than the float32 table's 1.63.  GLX_AGG_HALF_LD16=1 selects the 16-byte
   // loads (every dimension, pitch and offset a multiple of 8 elements).
-  const int ev = (DT != GLX_DTYPE_F32 && agg_knobs().half_ld16.load(std::memory_order_relaxed) != 0) ? 8 : 4;
+  // float8 turns out the other way round where rows are long (profiles/r29/fp8_features.txt, same process, ms, 4 / 8
+  // columns per lane): C3 hop-2 (D = 256) 1.04 / 0.80 on the sampled ids and 1.12 / 1.02 on uniformly random ones --
+  // 8-byte loads, two segments per wave -- but C2's shape (D = 128, G = 16) 0.50 / 0.53 and 0.83 / 0.82.  So float8
+  // rows of >= 256 columns take 8 columns per lane when every dimension, pitch and offset allows it, narrower ones
+  // keep 4.  GLX_AGG_HALF_LD16=2 selects 4 columns per lane for every type (the ablation of this rule).
+  int ev = 4;
+  if constexpr (DT != GLX_DTYPE_F32) {
+    const int ld16 = agg_knobs().half_ld16.load(std::memory_order_relaxed);
+    const bool fits8 = vec4 && a.dim % 8 == 0 && a.ncols % 8 == 0 && a.col0 % 8 == 0 && (a.stride % 8) == 0;
+    if (ld16 == 1 || (ld16 == 0 && glx_dtype_is_f8(DT) && a.ncols >= 256 && fits8)) ev = 8;
+  }
   const bool wide = vec4 && a.dim % ev == 0 && a.ncols % ev == 0 && a.col0 % ev == 0 && (a.stride % ev) == 0;
   // the grouped kernel reads row 0 in place of an unknown id's row: some row must exist
   const bool has_rows = NSRC > 1 ? (a.X2 != nullptr || a.base2 > 0) : a.num_rows > 0;
@@ -1184,17 +1234,19 @@ void launch_agg(const AggArgs& a, int32_t num_ids, hipStream_t s) {
   if (a.X1 || a.X2) launch_agg_n<OP, 3, GLX_DTYPE_F32>(a, num_ids, s);  // the distributed store: float32 only
   else if (a.dtype == GLX_DTYPE_BF16) launch_agg_n<OP, 1, GLX_DTYPE_BF16>(a, num_ids, s);
   else if (a.dtype == GLX_DTYPE_F16) launch_agg_n<OP, 1, GLX_DTYPE_F16>(a, num_ids, s);
+  else if (a.dtype == GLX_DTYPE_F8E4M3) launch_agg_n<OP, 1, GLX_DTYPE_F8E4M3>(a, num_ids, s);
+  else if (a.dtype == GLX_DTYPE_F8E5M2) launch_agg_n<OP, 1, GLX_DTYPE_F8E5M2>(a, num_ids, s);
   else launch_agg_n<OP, 1, GLX_DTYPE_F32>(a, num_ids, s);
 }
 
 // Upload: row r of the caller's dense [V, D] matrix -> its (swizzled, pitched) slot.  SRC / DST: element types of
-// the caller's matrix and of the table; float32 -> half rounds (glx_f32_to_bf16_bits / glx_f32_to_f16_bits), equal
-// types copy the bits.
+// the caller's matrix and of the table; float32 -> half / float8 rounds (glx_f32_to_bf16_bits and its siblings),
+// equal types copy the bits.
 template <int SRC, int DST>
 __global__ void glx_place_rows_kernel(const void* __restrict__ src_v, int64_t num_rows, int32_t dim,
                                       int64_t stride, int64_t swizzle_rows, void* __restrict__ dst_v) {
-  typedef typename std::conditional<SRC == GLX_DTYPE_F32, uint32_t, uint16_t>::type src_t;
-  typedef typename std::conditional<DST == GLX_DTYPE_F32, uint32_t, uint16_t>::type dst_t;
+  typedef typename std::conditional<SRC == GLX_DTYPE_F32, uint32_t, typename std::conditional<glx_dtype_is_f8(SRC), uint8_t, uint16_t>::type>::type src_t;
+  typedef typename std::conditional<DST == GLX_DTYPE_F32, uint32_t, typename std::conditional<glx_dtype_is_f8(DST), uint8_t, uint16_t>::type>::type dst_t;
   const src_t* __restrict__ src = static_cast<const src_t*>(src_v);
   dst_t* __restrict__ dst = static_cast<dst_t*>(dst_v);
   const int64_t total = num_rows * (int64_t)dim;
@@ -1205,6 +1257,8 @@ __global__ void glx_place_rows_kernel(const void* __restrict__ src_v, int64_t nu
     dst_t v;
     if constexpr (SRC == DST) v = src[t];
     else if constexpr (DST == GLX_DTYPE_BF16) v = glx_f32_to_bf16_bits(src[t]);
+    else if constexpr (DST == GLX_DTYPE_F8E4M3) v = glx_f32_to_f8e4m3_bits(src[t]);
+    else if constexpr (DST == GLX_DTYPE_F8E5M2) v = glx_f32_to_f8e5m2_bits(src[t]);
     else v = glx_f32_to_f16_bits(src[t]);
     dst[glx_swizzle_row(r, swizzle_rows) * stride + c] = v;
   }
@@ -1223,8 +1277,8 @@ __global__ __launch_bounds__(256) void glx_lookup_kernel(GlxIdMap map, const voi
   int64_t row = glx_row_of(map, ids[gid]);
   if (row >= 0) row = glx_swizzle_row(row, swizzle_rows);
   float* o = out + gid * (int64_t)dim;
-  // 4 elements per lane: a float32 table's rows as they always were; a half table's only when its rows are 8-byte
-  // aligned (a view's pitch is its dim, its base the caller's)
+  // 4 elements per lane: a float32 table's rows as they always were; a half or float8 table's only when its rows are
+  // 8-byte aligned (a view's pitch is its dim, its base the caller's; a float8 load of 4 columns needs 4 bytes)
   bool vec4 = (dim & 3) == 0;
   if constexpr (DT != GLX_DTYPE_F32) vec4 = vec4 && (stride & 3) == 0 && (reinterpret_cast<uintptr_t>(Xv) & 7) == 0;
   if (vec4) {
@@ -1609,7 +1663,7 @@ extern "C" int glx_features_create_ex(int device, int64_t num_rows, int32_t dim,
 }
 
 namespace {
-bool glx_dtype_known(int dtype) { return dtype == GLX_DTYPE_F32 || dtype == GLX_DTYPE_BF16 || dtype == GLX_DTYPE_F16; }
+bool glx_dtype_known(int dtype) { return glx_dtype_size(dtype) != 0; }
 }  // namespace
 
 int glx_features_create_impl(int device, int64_t num_rows, int32_t dim, const void* X, int x_dtype, int store_dtype,
@@ -1637,7 +1691,7 @@ int glx_features_create_impl(int device, int64_t num_rows, int32_t dim, const vo
   f->num_rows = num_rows;
   f->dim = dim;
   f->dtype = store_dtype;
-  f->elem_size = store_dtype == GLX_DTYPE_F32 ? 4 : 2;
+  f->elem_size = glx_dtype_size(store_dtype);
   f->owns_x = true;
   // Row pitch.  When a row is a multiple of 256 bytes, rows whose ids share low
   // zero bits (RMAT-style / power-of-two-structured ids are exactly the hub ids)
@@ -1658,7 +1712,7 @@ int glx_features_create_impl(int device, int64_t num_rows, int32_t dim, const vo
   GlxTemp staged;
   if (e == hipSuccess && num_rows > 0) {
     const void* d_src = X;
-    const size_t src_bytes = (size_t)num_rows * dim * (x_dtype == GLX_DTYPE_F32 ? 4 : 2);
+    const size_t src_bytes = (size_t)num_rows * dim * glx_dtype_size(x_dtype);
     if (ptr_kind == GLX_PTR_HOST) {
       e = hipMalloc(&staged.p, src_bytes);
       if (e == hipSuccess) e = hipMemcpyAsync(staged.p, X, src_bytes, hipMemcpyHostToDevice, s);
@@ -1675,6 +1729,12 @@ int glx_features_create_impl(int device, int64_t num_rows, int32_t dim, const vo
       } else if (store_dtype == GLX_DTYPE_F16) {
         place = x_dtype == GLX_DTYPE_F32 ? glx_place_rows_kernel<GLX_DTYPE_F32, GLX_DTYPE_F16>
                                          : glx_place_rows_kernel<GLX_DTYPE_F16, GLX_DTYPE_F16>;
+      } else if (store_dtype == GLX_DTYPE_F8E4M3) {
+        place = x_dtype == GLX_DTYPE_F32 ? glx_place_rows_kernel<GLX_DTYPE_F32, GLX_DTYPE_F8E4M3>
+                                         : glx_place_rows_kernel<GLX_DTYPE_F8E4M3, GLX_DTYPE_F8E4M3>;
+      } else if (store_dtype == GLX_DTYPE_F8E5M2) {
+        place = x_dtype == GLX_DTYPE_F32 ? glx_place_rows_kernel<GLX_DTYPE_F32, GLX_DTYPE_F8E5M2>
+                                         : glx_place_rows_kernel<GLX_DTYPE_F8E5M2, GLX_DTYPE_F8E5M2>;
       }
       place<<<(unsigned)blocks, 256, 0, s>>>(d_src, num_rows, dim, f->stride, f->swizzle_rows, f->X);
     }
@@ -1737,7 +1797,7 @@ extern "C" int glx_features_view_ex(int device, int64_t num_rows, int32_t dim, c
   f->swizzle_rows = 0;  // a view addresses the caller's rows as they are
   f->X = const_cast<void*>(X_device);
   f->dtype = dtype;
-  f->elem_size = dtype == GLX_DTYPE_F32 ? 4 : 2;
+  f->elem_size = glx_dtype_size(dtype);
   f->owns_x = false;
   *out = f;
   return GLX_OK;
@@ -1768,6 +1828,26 @@ extern "C" int glx_features_dtype(const glx_features* f, int* dtype) {
   GLX_REQUIRE(f != nullptr, "features is NULL");
   GLX_REQUIRE(dtype != nullptr, "dtype is NULL");
   *dtype = f->dtype;
+  return GLX_OK;
+}
+
+extern "C" int glx_features_convert_host(const float* src, int64_t n, int store_dtype, void* dst) {
+  GLX_REQUIRE(n >= 0, "negative n");
+  GLX_REQUIRE(glx_dtype_known(store_dtype), "unknown store_dtype %d", store_dtype);
+  if (n == 0) return GLX_OK;
+  GLX_REQUIRE(src && dst, "NULL data pointer");
+  if (store_dtype == GLX_DTYPE_F32) {
+    memcpy(dst, src, (size_t)n * sizeof(float));
+    return GLX_OK;
+  }
+  for (int64_t i = 0; i < n; ++i) {
+    uint32_t u;
+    memcpy(&u, src + i, sizeof(u));
+    if (store_dtype == GLX_DTYPE_BF16) static_cast<uint16_t*>(dst)[i] = glx_f32_to_bf16_bits(u);
+    else if (store_dtype == GLX_DTYPE_F16) static_cast<uint16_t*>(dst)[i] = glx_f32_to_f16_bits(u);
+    else if (store_dtype == GLX_DTYPE_F8E4M3) static_cast<uint8_t*>(dst)[i] = glx_f32_to_f8e4m3_bits(u);
+    else static_cast<uint8_t*>(dst)[i] = glx_f32_to_f8e5m2_bits(u);
+  }
   return GLX_OK;
 }
 
@@ -1826,16 +1906,12 @@ extern "C" int glx_lookup(const glx_features* f, const int64_t* node_ids, int64_
   if (rc == GLX_OK) {
     GlxKernelTimer timer(GLX_KERNEL_LOOKUP, st.s);
     const unsigned grid = (unsigned)((threads + 255) / 256);
-    if (f->dtype == GLX_DTYPE_BF16) {
-      glx_lookup_kernel<GLX_DTYPE_BF16><<<grid, 256, 0, st.s>>>(f->map(), f->X, f->stride, f->swizzle_rows, f->dim, d_ids, n,
-                                                               default_attr, d_out, G);
-    } else if (f->dtype == GLX_DTYPE_F16) {
-      glx_lookup_kernel<GLX_DTYPE_F16><<<grid, 256, 0, st.s>>>(f->map(), f->X, f->stride, f->swizzle_rows, f->dim, d_ids, n,
-                                                              default_attr, d_out, G);
-    } else {
-      glx_lookup_kernel<GLX_DTYPE_F32><<<grid, 256, 0, st.s>>>(f->map(), f->X, f->stride, f->swizzle_rows, f->dim, d_ids, n,
-                                                              default_attr, d_out, G);
-    }
+    auto lookup = glx_lookup_kernel<GLX_DTYPE_F32>;
+    if (f->dtype == GLX_DTYPE_BF16) lookup = glx_lookup_kernel<GLX_DTYPE_BF16>;
+    else if (f->dtype == GLX_DTYPE_F16) lookup = glx_lookup_kernel<GLX_DTYPE_F16>;
+    else if (f->dtype == GLX_DTYPE_F8E4M3) lookup = glx_lookup_kernel<GLX_DTYPE_F8E4M3>;
+    else if (f->dtype == GLX_DTYPE_F8E5M2) lookup = glx_lookup_kernel<GLX_DTYPE_F8E5M2>;
+    lookup<<<grid, 256, 0, st.s>>>(f->map(), f->X, f->stride, f->swizzle_rows, f->dim, d_ids, n, default_attr, d_out, G);
     timer.stop();
   }
   return st.finish(rc);

@@ -130,6 +130,8 @@ template <int OP>
 void launch_arg_fwd_dt(const ArgFwdArgs& a, int dtype, hipStream_t s) {
   if (dtype == GLX_DTYPE_BF16) launch_arg_fwd<OP, GLX_DTYPE_BF16>(a, s);
   else if (dtype == GLX_DTYPE_F16) launch_arg_fwd<OP, GLX_DTYPE_F16>(a, s);
+  else if (dtype == GLX_DTYPE_F8E4M3) launch_arg_fwd<OP, GLX_DTYPE_F8E4M3>(a, s);
+  else if (dtype == GLX_DTYPE_F8E5M2) launch_arg_fwd<OP, GLX_DTYPE_F8E5M2>(a, s);
   else launch_arg_fwd<OP, GLX_DTYPE_F32>(a, s);
 }
 

@@ -426,8 +426,8 @@ struct glx_features {
   int64_t stride;  // elements between consecutive rows (>= dim; see glx_features_create)
   int64_t swizzle_rows;  // rows [0, swizzle_rows) are stored at glx_swizzle_row(r); 0 = off
   void* X;  // [V, stride] row-major elements of `dtype`, base 256-byte aligned
-  int dtype;       // GLX_DTYPE_F32 | GLX_DTYPE_BF16 | GLX_DTYPE_F16: the storage type (accumulation is always float32)
-  int32_t elem_size;  // bytes per element: 4 or 2
+  int dtype;       // GLX_DTYPE_F32 | _BF16 | _F16 | _F8E4M3 | _F8E5M2: the storage type (accumulation is always float32)
+  int32_t elem_size;  // bytes per element: 4, 2 or 1 (glx_dtype_size)
   bool owns_x;
   GlxIdMapStorage idmap;
   GlxIdMap map() const { return idmap.view(num_rows); }
@@ -441,7 +441,25 @@ struct glx_features {
 };
 
 inline const char* glx_dtype_name(int dtype) {
-  return dtype == GLX_DTYPE_F32 ? "float32" : dtype == GLX_DTYPE_BF16 ? "bfloat16" : dtype == GLX_DTYPE_F16 ? "float16" : "?";
+  switch (dtype) {
+    case GLX_DTYPE_F32: return "float32";
+    case GLX_DTYPE_BF16: return "bfloat16";
+    case GLX_DTYPE_F16: return "float16";
+    case GLX_DTYPE_F8E4M3: return "float8_e4m3fn";
+    case GLX_DTYPE_F8E5M2: return "float8_e5m2";
+    default: return "?";
+  }
+}
+// bytes per element of a storage type (0: not a storage type)
+inline int32_t glx_dtype_size(int dtype) {
+  switch (dtype) {
+    case GLX_DTYPE_F32: return 4;
+    case GLX_DTYPE_BF16:
+    case GLX_DTYPE_F16: return 2;
+    case GLX_DTYPE_F8E4M3:
+    case GLX_DTYPE_F8E5M2: return 1;
+    default: return 0;
+  }
 }
 
 // AliasMethod::Build (alias_method.cc:57-107) for ONE distribution of `count` weights,
@@ -995,10 +1013,13 @@ __device__ __forceinline__ float agg_combine(float l, float r) {
 }
 
 // ---- storage types -----------------------------------------------------------------------------------------
-// A table stores float32, bfloat16 or float16 elements (glx_features::dtype).  Every kernel that reads one upcasts
-// each element to float32 in registers right after the load -- exact for both half types -- and then folds, finishes
-// and stores exactly as for a float32 table: a half table's results are those of the float32 table of its upcast
-// values, bit for bit.  Only the bytes per row change.
+// A table stores float32, bfloat16, float16 or OCP float8 (e4m3fn / e5m2) elements (glx_features::dtype).  Every
+// kernel that reads one upcasts each element to float32 in registers right after the load -- exact for every narrow
+// type -- and then folds, finishes and stores exactly as for a float32 table: a narrow table's results are those of
+// the float32 table of its upcast values, bit for bit.  Only the bytes per row change.
+// float8: gfx950's converts read the OCP encodings (v_cvt_f32_fp8 / v_cvt_f32_bf8, a byte of a dword each;
+// v_cvt_pk_f32_fp8 / _bf8, a word of a dword each).  A NaN code (e4m3 0x7F / 0xFF, e5m2 0x7D-0x7F / 0xFD-0xFF)
+// upcasts to a NaN whose sign and payload are the hardware's.
 template <int DT>
 struct AggElem;
 template <>
@@ -1017,7 +1038,25 @@ struct AggElem<GLX_DTYPE_F16> {
   static __device__ __forceinline__ float up(_Float16 x) { return (float)x; }
 };
 
-// VEC consecutive elements: ONE load of VEC * sizeof(raw) bytes (16 for 4 floats or 8 halves), kept raw until
+template <>
+struct AggElem<GLX_DTYPE_F8E4M3> {
+  typedef uint8_t raw;
+  static __device__ __forceinline__ float up(uint8_t x) { return __builtin_amdgcn_cvt_f32_fp8((int)x, 0); }
+  static __device__ __forceinline__ float __attribute__((ext_vector_type(2))) up2(uint32_t w, bool hi) {
+    return hi ? __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true) : __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false);
+  }
+};
+template <>
+struct AggElem<GLX_DTYPE_F8E5M2> {
+  typedef uint8_t raw;
+  static __device__ __forceinline__ float up(uint8_t x) { return __builtin_amdgcn_cvt_f32_bf8((int)x, 0); }
+  static __device__ __forceinline__ float __attribute__((ext_vector_type(2))) up2(uint32_t w, bool hi) {
+    return hi ? __builtin_amdgcn_cvt_pk_f32_bf8((int)w, true) : __builtin_amdgcn_cvt_pk_f32_bf8((int)w, false);
+  }
+};
+constexpr bool glx_dtype_is_f8(int dt) { return dt == GLX_DTYPE_F8E4M3 || dt == GLX_DTYPE_F8E5M2; }
+
+// VEC consecutive elements: ONE load of VEC * sizeof(raw) bytes (16 for 4 floats or 8 halves, 4 for 4 float8), kept raw until
 // agg_up converts them in registers -- so a batch issues all its loads before the first conversion waits for data.
 template <int DT, int VEC>
 using agg_raw_vec = typename AggElem<DT>::raw __attribute__((ext_vector_type(VEC)));
@@ -1031,6 +1070,19 @@ template <int DT, int VEC>
 __device__ __forceinline__ float __attribute__((ext_vector_type(VEC))) agg_up(agg_raw_vec<DT, VEC> q) {
   if constexpr (DT == GLX_DTYPE_F32) {
     return q;
+  } else if constexpr (glx_dtype_is_f8(DT) && VEC % 4 == 0) {
+    // a dword of four float8 elements: two packed converts (low word, high word), not four scalar ones
+    float __attribute__((ext_vector_type(VEC))) r;
+    const auto w = __builtin_bit_cast(uint32_t __attribute__((ext_vector_type(VEC / 4))), q);
+#pragma unroll
+    for (int v = 0; v < VEC / 4; ++v) {
+      const float __attribute__((ext_vector_type(2))) lo = AggElem<DT>::up2(w[v], false), hi = AggElem<DT>::up2(w[v], true);
+      r[4 * v] = lo[0];
+      r[4 * v + 1] = lo[1];
+      r[4 * v + 2] = hi[0];
+      r[4 * v + 3] = hi[1];
+    }
+    return r;
   } else {
     float __attribute__((ext_vector_type(VEC))) r;
 #pragma unroll

@@ -41,6 +41,8 @@ __device__ __forceinline__ uint64_t knn_key(float dist, uint32_t row, int metric
 __device__ __forceinline__ float knn_elem(const void* X, int dtype, int64_t i) {
   if (dtype == GLX_DTYPE_F32) return static_cast<const float*>(X)[i];
   if (dtype == GLX_DTYPE_BF16) return AggElem<GLX_DTYPE_BF16>::up(static_cast<const uint16_t*>(X)[i]);
+  if (dtype == GLX_DTYPE_F8E4M3) return AggElem<GLX_DTYPE_F8E4M3>::up(static_cast<const uint8_t*>(X)[i]);
+  if (dtype == GLX_DTYPE_F8E5M2) return AggElem<GLX_DTYPE_F8E5M2>::up(static_cast<const uint8_t*>(X)[i]);
   return AggElem<GLX_DTYPE_F16>::up(static_cast<const _Float16*>(X)[i]);
 }
 
@@ -200,12 +202,18 @@ __device__ __forceinline__ bool knn_ivf_slot_list(const int64_t* probe, int32_t 
   return *list >= 0 && *list < nlist;
 }
 
-// launch KERNEL<DT> for a table's storage type
-#define GLX_KNN_LAUNCH_DT(dtype, KERNEL, grid, block, s, ...)                                        \
-  do {                                                                                               \
-    if ((dtype) == GLX_DTYPE_F32) KERNEL<GLX_DTYPE_F32><<<grid, block, 0, s>>>(__VA_ARGS__);         \
-    else if ((dtype) == GLX_DTYPE_BF16) KERNEL<GLX_DTYPE_BF16><<<grid, block, 0, s>>>(__VA_ARGS__);  \
-    else KERNEL<GLX_DTYPE_F16><<<grid, block, 0, s>>>(__VA_ARGS__);                                  \
+// launch KERNEL<DT> for a table's storage type; an unknown type launches nothing, sets the error and *(rc) = GLX_INTERNAL
+#define GLX_KNN_LAUNCH_DT(rc, dtype, KERNEL, grid, block, s, ...)                                         \
+  do {                                                                                                    \
+    if ((dtype) == GLX_DTYPE_F32) KERNEL<GLX_DTYPE_F32><<<grid, block, 0, s>>>(__VA_ARGS__);              \
+    else if ((dtype) == GLX_DTYPE_BF16) KERNEL<GLX_DTYPE_BF16><<<grid, block, 0, s>>>(__VA_ARGS__);       \
+    else if ((dtype) == GLX_DTYPE_F16) KERNEL<GLX_DTYPE_F16><<<grid, block, 0, s>>>(__VA_ARGS__);         \
+    else if ((dtype) == GLX_DTYPE_F8E4M3) KERNEL<GLX_DTYPE_F8E4M3><<<grid, block, 0, s>>>(__VA_ARGS__);   \
+    else if ((dtype) == GLX_DTYPE_F8E5M2) KERNEL<GLX_DTYPE_F8E5M2><<<grid, block, 0, s>>>(__VA_ARGS__);   \
+    else {                                                                                                \
+      glx_set_error(#KERNEL ": no instantiation for storage dtype %d", (int)(dtype));                     \
+      *(rc) = GLX_INTERNAL;                                                                               \
+    }                                                                                                     \
   } while (0)
 
 // ---- host side ----------------------------------------------------------------------------------------------------

@@ -375,7 +375,8 @@ int knn_search_device(const glx_features* f, int metric, const float* d_q, int32
       const int64_t len = row0 == 0 ? first : chunk;
       const int64_t row1 = row0 + len < a.t.num_rows ? row0 + len : a.t.num_rows;
       const dim3 grid((unsigned)((row1 - row0 + kBR - 1) / kBR), (unsigned)((a.nq + kBQ - 1) / kBQ));
-      GLX_KNN_LAUNCH_DT(a.t.dtype, knn_score_kernel, grid, 256, s, a, (int32_t)row0, (int32_t)row1);
+      GLX_KNN_LAUNCH_DT(&rc, a.t.dtype, knn_score_kernel, grid, 256, s, a, (int32_t)row0, (int32_t)row1);
+      if (rc != GLX_OK) return rc;
       knn_select_kernel<<<(unsigned)a.nq, kSelThreads, 0, s>>>(a);
       row0 = row1;
     }

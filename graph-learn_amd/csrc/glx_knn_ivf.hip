@@ -198,14 +198,15 @@ static int knn_ivf_search_device(const glx_knn_ivf* ix, int metric, const float*
   sc.nprobe = nprobe;
   sc.KP = a.KP;
   sc.metric = metric;
-  return knn_ivf_passes(
+  int launch_rc = GLX_OK;
+  rc = knn_ivf_passes(
       ix, metric, d_q, num_queries, nprobe, plan, probe, pdist, a.run, sc.part, a.KP, s,
       [&](int64_t q0, int32_t nq, int32_t p0, int32_t P) {
         sc.queries = d_q + q0 * f->dim;
         sc.qn = qn + q0;
         sc.p0 = p0;
         sc.P = P;
-        GLX_KNN_LAUNCH_DT(a.t.dtype, knn_ivf_scan_kernel, (unsigned)((int64_t)nq * P), kSelThreads, s, sc);
+        GLX_KNN_LAUNCH_DT(&launch_rc, a.t.dtype, knn_ivf_scan_kernel, (unsigned)((int64_t)nq * P), kSelThreads, s, sc);
       },
       [&](int64_t q0, int32_t nq) {
         a.nq = nq;
@@ -213,6 +214,7 @@ static int knn_ivf_search_device(const glx_knn_ivf* ix, int metric, const float*
         a.qn = qn + q0;
         knn_finish(a, f, d_ids + q0 * k, d_dist + q0 * k, s);
       });
+  return rc != GLX_OK ? rc : launch_rc;
 }
 
 // assign[t] = the centroid of sample element t of a T-element sample, t < T: glx's L2 search with k = 1 over the

@@ -350,7 +350,8 @@ static int knn_ivfpq_search_device(const glx_knn_ivfpq* px, int metric, const fl
   sc.m = px->m;
   sc.dsub = px->dsub;
   const bool arith = f->idmap.keys == nullptr && f->idmap.step > 0;
-  return knn_ivf_passes(
+  int launch_rc = GLX_OK;
+  rc = knn_ivf_passes(
       ix, metric, d_q, num_queries, nprobe, plan, probe, pdist, cand, sc.part, RP, s,
       [&](int64_t q0, int32_t nq, int32_t p0, int32_t P) {
         sc.queries = d_q + q0 * f->dim;
@@ -370,9 +371,10 @@ static int knn_ivfpq_search_device(const glx_knn_ivfpq* px, int metric, const fl
         a.nq = nq;
         a.queries = d_q + q0 * f->dim;
         a.qn = qn + q0;
-        GLX_KNN_LAUNCH_DT(a.t.dtype, knn_ivfpq_refine_kernel, (unsigned)nq, kSelThreads, s, a, cand, RP, refine, a.run);
+        GLX_KNN_LAUNCH_DT(&launch_rc, a.t.dtype, knn_ivfpq_refine_kernel, (unsigned)nq, kSelThreads, s, a, cand, RP, refine, a.run);
         knn_finish(a, f, d_ids + q0 * k, d_dist + q0 * k, s);
       });
+  return rc != GLX_OK ? rc : launch_rc;
 }
 
 static int knn_ivfpq_build_device(glx_knn_ivfpq* px, int32_t niter, int64_t train_rows, const float* codebooks_init,

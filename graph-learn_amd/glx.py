@@ -45,7 +45,7 @@ EXPORTS = [
     "glx_graph_set_timestamps", "glx_sample_filtered", "glx_sample_full_filtered", "glx_random_walk",
     "glx_graph_has_timestamps", "glx_sample_temporal", "glx_sample_temporal_hops",
     "glx_features_create", "glx_features_view", "glx_features_destroy", "glx_features_info",
-    "glx_features_create_ex", "glx_features_view_ex", "glx_features_dtype",
+    "glx_features_create_ex", "glx_features_view_ex", "glx_features_dtype", "glx_features_convert_host",
     "glx_knn_search", "glx_knn_merge",
     "glx_knn_ivf_build", "glx_knn_ivf_search", "glx_knn_ivf_info", "glx_knn_ivf_export", "glx_knn_ivf_destroy",
     "glx_knn_ivfpq_build", "glx_knn_ivfpq_search", "glx_knn_ivfpq_info", "glx_knn_ivfpq_export",
@@ -176,6 +176,7 @@ def lib():
         L.glx_features_create_ex.argtypes = [ci, i64, i32, vp, ci, ci, vp, ci, vp, ctypes.POINTER(vp)]
         L.glx_features_view_ex.argtypes = [ci, i64, i32, vp, ci, ctypes.POINTER(vp)]
         L.glx_features_dtype.argtypes = [vp, ctypes.POINTER(ci)]
+        L.glx_features_convert_host.argtypes = [vp, i64, ci, vp]
         L.glx_features_destroy.argtypes = [vp]
         L.glx_features_destroy.restype = None
         L.glx_features_info.argtypes = [vp, ctypes.POINTER(i64), ctypes.POINTER(i32), ctypes.POINTER(ci),
@@ -617,27 +618,35 @@ class Graph:
 
 # storage types of a feature table (GLX_DTYPE_*)
 FEATURE_DTYPES = {"float32": 0, "bfloat16": 1, "float16": 2}
-_FEATURE_DTYPE_NAMES = {v: k for k, v in FEATURE_DTYPES.items()}
+# OCP float8 storage (GLX_DTYPE_F8E4M3 / GLX_DTYPE_F8E5M2): one byte per element.  e4m3fn has no infinity: float32
+# input beyond +-464 is stored as NaN, not as the largest number -- normalise such features first.
+FP8_FEATURE_DTYPES = {"float8_e4m3fn": 8, "float8_e5m2": 9}
+_ALL_FEATURE_DTYPES = dict(FEATURE_DTYPES, **FP8_FEATURE_DTYPES)
+_FEATURE_DTYPE_NAMES = {v: k for k, v in _ALL_FEATURE_DTYPES.items()}
 
 
 def _feature_dtype_of(X):
-    """float32 / bfloat16 / float16 for a torch tensor or a numpy array; anything else raises."""
+    """float32 / bfloat16 / float16 for a torch tensor or a numpy array, float8_e4m3fn / float8_e5m2 for a torch
+    tensor (numpy has no float8 type: a uint8 matrix is not a feature matrix); anything else raises."""
     name = str(X.dtype).replace("torch.", "") if _is_torch(X) else str(np.dtype(X.dtype))
-    if name not in FEATURE_DTYPES:
-        raise ValueError("a feature matrix holds float32, bfloat16 or float16, not {}".format(X.dtype))
+    if name not in _ALL_FEATURE_DTYPES:
+        raise ValueError("a feature matrix holds float32, bfloat16, float16 or (torch) float8_e4m3fn / float8_e5m2, "
+                         "not {}".format(X.dtype))
     return name
 
 
 class Features:
     """Device-resident [V, D] node features of one node type (glx_features), stored as float32 (the default),
-    bfloat16 or float16.  aggregate() and lookup() answer in float32 whatever the storage type."""
+    bfloat16, float16, float8_e4m3fn or float8_e5m2.  aggregate(), lookup() and search() answer in float32 whatever
+    the storage type."""
 
     def __init__(self, X, ids=None, device=0, view=False, dtype=None):
-        """X: float32 / bfloat16 / float16 -- numpy (float32, float16) or torch (host or CUDA).  dtype=None stores
-        X's own type; "bfloat16" / "float16" rounds float32 input on the device (round to nearest even).
+        """X: float32 / bfloat16 / float16 / float8 -- numpy (float32, float16) or torch (host or CUDA).  dtype=None
+        stores X's own type; "bfloat16" / "float16" / "float8_e4m3fn" / "float8_e5m2" rounds float32 input on the device
+        (round to nearest even, as torch's .to(); float8_e4m3fn turns overflow into NaN: it has no infinity).
         view=True: non-owning view of a torch CUDA matrix (dense ids, its own dtype); keeps X alive."""
-        if dtype is not None and dtype not in FEATURE_DTYPES:
-            raise ValueError("dtype must be None or one of {}, not {!r}".format(sorted(FEATURE_DTYPES), dtype))
+        if dtype is not None and dtype not in _ALL_FEATURE_DTYPES:
+            raise ValueError("dtype must be None or one of {}, not {!r}".format(sorted(_ALL_FEATURE_DTYPES), dtype))
         x_dtype = _feature_dtype_of(X)
         store = dtype or x_dtype
         if store != x_dtype and x_dtype != "float32":
@@ -651,21 +660,24 @@ class Features:
             self.device = device
             self._keep = X
             h = ctypes.c_void_p()
-            _check(lib().glx_features_view_ex(device, self.num_rows, self.dim, _ptr(X)[0], FEATURE_DTYPES[store],
+            _check(lib().glx_features_view_ex(device, self.num_rows, self.dim, _ptr(X)[0], _ALL_FEATURE_DTYPES[store],
                                               ctypes.byref(h)))
             self._h = h
             return
         if _is_torch(X) and not X.is_cuda:  # a host tensor: its bits as a numpy array (numpy has no bfloat16)
             import torch
             X = X.contiguous()
-            X = X.numpy() if x_dtype == "float32" else X.view(torch.int16).numpy()
+            if x_dtype == "float32":
+                X = X.numpy()
+            else:
+                X = X.view(torch.uint8 if x_dtype in FP8_FEATURE_DTYPES else torch.int16).numpy()
         ptrs = [_ptr(X), _ptr(ids)]
         kind = _kind(*ptrs)
         self.num_rows, self.dim = int(X.shape[0]), int(X.shape[1])
         self.device = device
         h = ctypes.c_void_p()
-        _check(lib().glx_features_create_ex(device, self.num_rows, self.dim, ptrs[0][0], FEATURE_DTYPES[x_dtype],
-                                            FEATURE_DTYPES[store], ptrs[1][0], kind, _stream(kind, self.device),
+        _check(lib().glx_features_create_ex(device, self.num_rows, self.dim, ptrs[0][0], _ALL_FEATURE_DTYPES[x_dtype],
+                                            _ALL_FEATURE_DTYPES[store], ptrs[1][0], kind, _stream(kind, self.device),
                                             ctypes.byref(h)))
         self._h = h
 

@@ -41,7 +41,7 @@ extern int64_t gSamplingSeed;
 extern int32_t gKnnMetric;  // config.cc:107 (0 = L2, 1 = inner product): the metric of the "KnnOperator"
 extern int32_t gDeviceId;
 // New: the storage type of the node feature tables Noder::Build uploads (GLX_DTYPE_*: 0 float32, 1 bfloat16,
-// 2 float16).  Aggregation and lookup still accumulate and answer in float32.
+// 2 float16, 8 float8_e4m3fn, 9 float8_e5m2).  Aggregation and lookup still accumulate and answer in float32.
 extern int32_t gFeatureDtype;
 
 void SetGlobalFlagPaddingMode(int32_t v);

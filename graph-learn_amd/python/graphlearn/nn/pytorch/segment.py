@@ -72,7 +72,7 @@ def _check_inputs(x, index, who):
   if not isinstance(x, torch.Tensor) or not isinstance(index, torch.Tensor):
     raise ValueError("{}: x and index must be torch tensors".format(who))
   if x.dtype != torch.float32:
-    raise ValueError("{}: x must be float32, not {} (half tables have no backward)".format(who, x.dtype))
+    raise ValueError("{}: x must be float32, not {} (half and float8 tables have no backward)".format(who, x.dtype))
   if not x.is_cuda or x.dim() != 2 or not x.is_contiguous():
     raise ValueError("{}: x must be a contiguous [N, D] CUDA tensor".format(who))
   if x.shape[1] < 1:

@@ -28,7 +28,7 @@ def column_defaults():
           "timestamps": _MIRROR["default_timestamp"], "int_attrs": _MIRROR["default_int_attr"]}
 
 # storage types of the node feature tables (include/glx.h GLX_DTYPE_*)
-_FEATURE_DTYPES = {"float32": 0, "bfloat16": 1, "float16": 2}
+_FEATURE_DTYPES = {"float32": 0, "bfloat16": 1, "float16": 2, "float8_e4m3fn": 8, "float8_e5m2": 9}
 
 
 def set_default_neighbor_id(nbr_id):
@@ -105,10 +105,12 @@ def set_device_id(device):
 
 
 def set_feature_dtype(dtype):
-  """Storage type of the node float attributes in HBM: "float32" (the default), "bfloat16" or "float16".  Half
-  tables hold half the bytes; aggregation and lookup still accumulate and answer in float32 (each result equals the
-  float32 one over the attributes rounded to `dtype`).  Takes effect for the node types Graph.init() builds after it;
-  the distributed store (sharded_store) takes float32 tables only."""
+  """Storage type of the node float attributes in HBM: "float32" (the default), "bfloat16", "float16",
+  "float8_e4m3fn" or "float8_e5m2".  Half tables hold half the bytes, float8 tables a quarter; aggregation and lookup
+  still accumulate and answer in float32 (each result equals the float32 one over the attributes rounded to `dtype`).
+  float8_e4m3fn has no infinity: an attribute beyond +-464 is stored as NaN, so normalise such attributes first.
+  Takes effect for the node types Graph.init() builds after it; the distributed store (sharded_store) takes float32
+  tables only."""
   if dtype not in _FEATURE_DTYPES:
     raise ValueError("feature dtype must be one of {}, not {!r}".format(sorted(_FEATURE_DTYPES), dtype))
   pywrap.set_feature_dtype(_FEATURE_DTYPES[dtype])

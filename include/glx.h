@@ -47,7 +47,7 @@ extern "C" {
  * glx_knn_merge; TGN memory -- glx_tgn_store_update, glx_tgn_message, glx_tgn_message_backward, glx_tgn_memory_write;
  * IVF-Flat index -- glx_knn_ivf_build, glx_knn_ivf_search, glx_knn_ivf_info, glx_knn_ivf_export, glx_knn_ivf_destroy;
  * IVF-PQ index -- glx_knn_ivfpq_build, glx_knn_ivfpq_search, glx_knn_ivfpq_info, glx_knn_ivfpq_export,
- * glx_knn_ivfpq_destroy. */
+ * glx_knn_ivfpq_destroy; float8 feature tables -- GLX_DTYPE_F8E4M3, GLX_DTYPE_F8E5M2, glx_features_convert_host. */
 #define GLX_ABI_VERSION 5
 
 /* Exported symbols: libglx.so is built with -fvisibility=hidden. */
@@ -406,15 +406,31 @@ GLX_API int glx_features_view(int device, int64_t num_rows, int32_t dim, const f
 GLX_API void glx_features_destroy(glx_features* f);
 GLX_API int glx_features_info(const glx_features* f, int64_t* num_rows, int32_t* dim, int* has_id_map,
                       int* device);
-/* Storage types of a feature table.  Aggregation and lookup read the stored elements, upcast them to float32
- * (exact) and accumulate and write float32 in the same order as for a float32 table: a half table's results equal
- * those of the float32 table holding the upcast values, bit for bit. */
+/* Storage types of a feature table.  Aggregation, lookup and the KNN searches read the stored elements, upcast them
+ * to float32 (exact) and accumulate and write float32 in the same order as for a float32 table: a half or float8
+ * table's results equal those of the float32 table holding the upcast values, bit for bit.
+ * float8 (OCP 8-bit floating point, one byte per element: a quarter of the float32 bytes; no FNUZ encodings, no
+ * per-row or per-column scale -- the stored byte IS the value):
+ *   conversion  float32 -> float8 rounds to nearest even in integer arithmetic, bit-identical to
+ *               torch.Tensor.to(torch.float8_e4m3fn / torch.float8_e5m2) of a contiguous CPU tensor.
+ *               e4m3fn has NO infinity: OVERFLOW BECOMES NaN, NOT THE LARGEST NUMBER.  |x| up to 464 (the tie, to
+ *               even) is 448 (0x7E); everything above, +-inf and every NaN is sign | 0x7F.  Features outside
+ *               [-448, 448] must be normalised before they are stored as e4m3.  Below, 2^-10 (half the smallest
+ *               subnormal, a tie) is zero and the sign of a zero is kept.
+ *               e5m2: up to 57344 is finite (0x7B); 61440 (the tie) and above is sign | 0x7C (inf); NaN is sign | 0x7F.
+ *   upcast      exact: every non-NaN code gives the float32 of torch's .float(); a NaN code (e4m3 0x7F, 0xFF; e5m2
+ *               0x7D-0x7F, 0xFD-0xFF) gives a NaN whose sign and payload are unspecified.
+ *   serves      glx_lookup, glx_aggregate (every operator), glx_aggregate_arg, glx_plan, the exact / IVF-Flat / IVF-PQ
+ *               KNN (queries stay float32).  Refuses, naming the dtype: glx_dist_store_create and the hot-row replica;
+ *               the training-path entry points take float32 matrices only. */
 #define GLX_DTYPE_F32 0
 #define GLX_DTYPE_BF16 1
 #define GLX_DTYPE_F16 2
+#define GLX_DTYPE_F8E4M3 8 /* OCP float8_e4m3fn */
+#define GLX_DTYPE_F8E5M2 9 /* OCP float8_e5m2 */
 /* glx_features_create with a storage type.  X holds [num_rows, dim] elements of x_dtype.  x_dtype == store_dtype
- * copies them as they are; x_dtype == GLX_DTYPE_F32 with a half store_dtype converts on the device while the rows
- * are placed: round to nearest even, overflow to +-inf, bit-identical to torch.Tensor.to() of a contiguous CPU
+ * copies them as they are; x_dtype == GLX_DTYPE_F32 with a half or float8 store_dtype converts on the device while
+ * the rows are placed (float8: the rule above; half): round to nearest even, overflow to +-inf, bit-identical to torch.Tensor.to() of a contiguous CPU
  * tensor for every input, NaN included (bfloat16: 0xFFFF for every NaN; float16: sign | 0x7E00 | payload >> 13).
  * Every other pair is GLX_INVALID_ARGUMENT.
  * glx_features_create(...) is glx_features_create_ex(..., GLX_DTYPE_F32, GLX_DTYPE_F32, ...). */
@@ -424,13 +440,19 @@ GLX_API int glx_features_create_ex(int device, int64_t num_rows, int32_t dim, co
 GLX_API int glx_features_view_ex(int device, int64_t num_rows, int32_t dim, const void* X_device, int dtype,
                                  glx_features** out);
 GLX_API int glx_features_dtype(const glx_features* f, int* dtype);
+/* The upload's conversion on the host, without a GPU: dst[i] = src[i] converted to store_dtype for i < n, by the very
+ * functions the device runs while it places the rows of glx_features_create_ex -- so the rounding rule can be checked
+ * against torch.Tensor.to() anywhere.  store_dtype: GLX_DTYPE_BF16 / _F16 (dst: n x 2 bytes), _F8E4M3 / _F8E5M2 (n
+ * bytes), _F32 (copies n x 4 bytes).  An addition of this engine: it stands in for the float -> storage step of
+ * NodeStorage::Add (compressed_memory_node_storage.cc:99-101), which keeps float32.  Pure host code, no HIP call. */
+GLX_API int glx_features_convert_host(const float* src, int64_t n, int store_dtype, void* dst);
 
 /* ---- exact KNN search: replaces the KnnOperator on the reference's flat index -- FlatKnnIndex::Search
  * (contrib/knn/flat_index.cc:26-55), KnnRequest / KnnResponse and KnnResponse::Merge (contrib/knn/knn_request.cc:26-50,
  * 186-202) and the index build (contrib/knn/builder.cc:23-52) -- without faiss: the flat index IS the glx_features table
  * as it lies in device memory, no second copy.  ivfflat / ivfpq / gpu_* index types are answered exactly by this search.
- * For a query q (dim float32 values) and a stored row x of a float32, bfloat16 or float16 table:
- *   upcast   a half element is upcast exactly to float32 first.
+ * For a query q (dim float32 values) and a stored row x of a float32, bfloat16, float16 or float8 table:
+ *   upcast   a half or float8 element is upcast exactly to float32 first.
  *   ip       = +0.0f, then ip = fmaf(q[c], x[c], ip) for c = 0 .. dim-1 ascending: ONE chain over all columns, one
  *            rounding per step (the numerics of v_mfma_f32_32x32x2_f32, of v_mfma_f32_16x16x4_f32 and of a VALU fmaf
  *            loop alike; no split-K, no second accumulator over the columns).
