@@ -169,7 +169,7 @@ def test_dense_responses(knobs, D, fanout):
     check(knobs, f, up, request([fanout] * Sg, 0, fanout), [fanout] * Sg, True, (D, fanout, Sg))
 
 
-@pytest.mark.parametrize("dtype", ["bfloat16", "float16"])
+@pytest.mark.parametrize("dtype", ["bfloat16", "float16", "float8_e4m3fn", "float8_e5m2"])
 def test_half_tables(knobs, dtype):
     f, up = features(256, dtype)
     for fanout, Sg in ((25, 1037), (130, 5)):
