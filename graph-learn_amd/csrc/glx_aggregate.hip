@@ -337,16 +337,11 @@ __global__ void glx_rows_kernel(GlxIdMap map, const int64_t* __restrict__ ids, i
 
 // (agg_init, agg_combine, AggElem and the raw-vector loads live in glx_common.h, shared with glx_aggregate_grad.hip)
 
-// float32 -> half for the upload, round to nearest even, bit-identical -- all 2^32 inputs -- to
-// torch.Tensor.to(torch.bfloat16 / torch.float16) of a contiguous CPU tensor, i.e. torch's vectorised conversion.
-// NaN included: the vectorised bfloat16 conversion emits 0xFFFF for every NaN (torch's scalar fallback, used for
-// strided tensors, emits 0x7FC0; the uploads convert contiguous matrices), the float16 one keeps the sign and the top
-// ten payload bits and sets the quiet bit (sign | 0x7E00 | payload >> 13).  Integer arithmetic only, so no
-// floating-point mode (denormal flushing) can change a result.
-__host__ __device__ __forceinline__ uint16_t glx_f32_to_bf16_bits(uint32_t u) {
-  if ((u & 0x7fffffffu) > 0x7f800000u) return 0xFFFF;
-  return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);  // a carry out of the mantissa rounds up to the next binade / inf
-}
+// float32 -> float16 for the upload, round to nearest even, bit-identical -- all 2^32 inputs -- to
+// torch.Tensor.to(torch.float16) of a contiguous CPU tensor, i.e. torch's vectorised conversion (the bfloat16 sibling,
+// glx_f32_to_bf16_bits, lives in glx_common.h: the training path's row gradients round with it too).  A NaN keeps the
+// sign and the top ten payload bits and sets the quiet bit (sign | 0x7E00 | payload >> 13).  Integer arithmetic only,
+// so no floating-point mode (denormal flushing) can change a result.
 __host__ __device__ __forceinline__ uint16_t glx_f32_to_f16_bits(uint32_t u) {
   const uint32_t sign = (u >> 16) & 0x8000u;
   const uint32_t a = u & 0x7fffffffu;

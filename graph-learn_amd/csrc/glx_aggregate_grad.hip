@@ -18,6 +18,8 @@
 //   reduce    glx_aggregate_bwd_kernel: the mirror image of the forward's grouped kernel -- G lanes own one TABLE row,
 //             lane c owns columns [4c, 4c + 4), the row's list entries are fetched coalesced (G at a time) and handed
 //             round with cross-lane reads, U grad_out row loads are issued before the first is folded.
+// grad_x is float32 or bfloat16 (glx_aggregate_backward_ex): the sum above is float32 either way, and a
+// bfloat16 grad_x stores it rounded once per element, to nearest even (glx_f32_to_bf16_bits), in the reduce's final store.
 // The workspace is the per-(thread, device, stream) arena; nothing is read back on the host between the launches.
 // The transpose (glx_agg_transpose, declared in glx_common.h) also serves the weighted reduce's row gradient
 // (glx_aggregate_weighted.hip).
@@ -249,9 +251,10 @@ struct BwdArgs {
   const int32_t* cnt;      // [num_segments], or nullptr: fanout (Mean's divisor)
   const int32_t* arg;      // [num_segments, dim] (Max / Min)
   const float* grad_out;   // [num_segments, dim]
-  float* grad_x;           // [num_rows, dim]
+  void* grad_x;            // [num_rows, dim] of `dtype` elements
   int64_t num_rows;
   int32_t dim, fanout;
+  int dtype;               // GLX_DTYPE_F32 or GLX_DTYPE_BF16: grad_x's element type
 };
 
 constexpr int kBwdU = 4;  // grad_out rows in flight per lane
@@ -259,9 +262,11 @@ constexpr int kBwdU = 4;  // grad_out rows in flight per lane
 // G lanes own table row r; lane c owns columns [VEC c, VEC c + VEC) of each column tile of G * VEC columns.  Lane c
 // fetches list entry base + c (its position, that position's segment and, for Mean, the divisor) and every lane of
 // the group reads entry j from lane j: the group walks its list together, so the cross-lane reads stay inside a
-// group whose lanes all run the same iterations.  Every row is written, an empty list writes zeros.
-template <int OP, int G, int VEC>
+// group whose lanes all run the same iterations.  Every row is written, an empty list writes zeros.  The sum is
+// float32 whatever DT; a bfloat16 grad_x rounds the finished sum once, in the store (agg_store).
+template <int OP, int G, int VEC, int DT>
 __global__ __launch_bounds__(256) void glx_aggregate_bwd_kernel(BwdArgs a) {
+  typedef typename AggElem<DT>::raw raw_t;
   typedef float vec_t __attribute__((ext_vector_type(VEC)));
   typedef int32_t ivec_t __attribute__((ext_vector_type(VEC)));
   constexpr bool kArg = OP == GLX_AGG_MAX || OP == GLX_AGG_MIN;
@@ -269,7 +274,7 @@ __global__ __launch_bounds__(256) void glx_aggregate_bwd_kernel(BwdArgs a) {
   const int c = threadIdx.x & (G - 1);
   if (r >= a.num_rows) return;  // whole groups leave
   const int32_t l0 = a.row_ptr[r], l1 = a.row_ptr[r + 1];
-  float* const out = a.grad_x + r * (int64_t)a.dim;
+  raw_t* const out = static_cast<raw_t*>(a.grad_x) + r * (int64_t)a.dim;
   for (int32_t col_pass = 0; col_pass < a.dim; col_pass += G * VEC) {
     const int32_t col = col_pass + c * VEC;
     const bool col_ok = col < a.dim;
@@ -324,7 +329,7 @@ __global__ __launch_bounds__(256) void glx_aggregate_bwd_kernel(BwdArgs a) {
         }
       }
     }
-    if (col_ok) *reinterpret_cast<vec_t*>(out + col) = acc;
+    if (col_ok) agg_store<DT, VEC>(out + col, acc);  // lanes past the last column store nothing
   }
 }
 
@@ -333,12 +338,16 @@ template <int OP, int VEC>
 void launch_bwd_vec(const BwdArgs& a, hipStream_t s) {
   const int G = glx_group_for((a.dim + VEC - 1) / VEC);
   const unsigned blocks = (unsigned)((a.num_rows + (256 / G) - 1) / (256 / G));
-  glx_for_group(G, [&](auto g) { glx_aggregate_bwd_kernel<OP, decltype(g)::value, VEC><<<blocks, 256, 0, s>>>(a); });
+  glx_for_group(G, [&](auto g) {
+    glx_for_train_dtype(a.dtype, [&](auto t) {
+      glx_aggregate_bwd_kernel<OP, decltype(g)::value, VEC, decltype(t)::value><<<blocks, 256, 0, s>>>(a);
+    });
+  });
 }
 
 template <int OP>
 void launch_bwd(const BwdArgs& a, hipStream_t s) {
-  bool vec4 = a.dim % 4 == 0 && glx_aligned16(a.grad_out) && glx_aligned16(a.grad_x);
+  bool vec4 = a.dim % 4 == 0 && glx_aligned16(a.grad_out) && glx_aligned_vec4(a.grad_x, a.dtype);
   if (OP == GLX_AGG_MAX || OP == GLX_AGG_MIN) vec4 = vec4 && glx_aligned16(a.arg);
   if (vec4) launch_bwd_vec<OP, 4>(a, s);
   else launch_bwd_vec<OP, 1>(a, s);
@@ -346,7 +355,8 @@ void launch_bwd(const BwdArgs& a, hipStream_t s) {
 
 // Device pointers only, device selected; num_ids, num_segments, num_rows >= 1.
 int backward_device(int op, const int64_t* rows, const int32_t* cnt, const int32_t* arg, int32_t n, int32_t num_segments,
-                    int64_t num_rows, int32_t dim, const float* grad_out, float* grad_x, hipStream_t s) {
+                    int64_t num_rows, int32_t dim, const float* grad_out, void* grad_x, int grad_x_dtype,
+                    hipStream_t s) {
   GlxScratch lease;
   GlxAggTranspose t;
   int rc = glx_agg_transpose(rows, cnt, n, num_segments, num_rows, s, &lease, &t);
@@ -362,6 +372,7 @@ int backward_device(int op, const int64_t* rows, const int32_t* cnt, const int32
   a.num_rows = num_rows;
   a.dim = dim;
   a.fanout = t.fanout;
+  a.dtype = grad_x_dtype;
   switch (op) {
     case GLX_AGG_SUM: launch_bwd<GLX_AGG_SUM>(a, s); break;
     case GLX_AGG_MEAN: launch_bwd<GLX_AGG_MEAN>(a, s); break;
@@ -424,9 +435,11 @@ extern "C" int glx_aggregate_arg(const glx_features* f, int op, const int64_t* n
   return st.finish(rc);
 }
 
-extern "C" int glx_aggregate_backward(int device, int op, const int64_t* rows, const int32_t* cnt, const int32_t* arg,
-                                      int32_t num_ids, int32_t num_segments, int64_t num_rows, int32_t dim,
-                                      const float* grad_out, float* grad_x, int ptr_kind, void* stream) {
+extern "C" int glx_aggregate_backward_ex(int device, int op, const int64_t* rows, const int32_t* cnt,
+                                         const int32_t* arg, int32_t num_ids, int32_t num_segments, int64_t num_rows,
+                                         int32_t dim, const float* grad_out, void* grad_x, int grad_x_dtype,
+                                         int ptr_kind, void* stream) {
+  GLX_REQUIRE_TRAIN_DTYPE(grad_x_dtype, "glx_aggregate_backward_ex: grad_x_dtype");
   GLX_REQUIRE(op >= GLX_AGG_SUM && op <= GLX_AGG_PROD, "unknown aggregator id %d", op);
   GLX_REQUIRE(op != GLX_AGG_PROD, "the Prod aggregator has no backward (its gradient divides by the element)");
   GLX_REQUIRE(num_ids >= 0 && num_segments >= 0 && num_rows >= 0, "negative sizes");
@@ -448,19 +461,27 @@ extern "C" int glx_aggregate_backward(int device, int op, const int64_t* rows, c
   const int64_t* d_rows;
   const int32_t *d_cnt, *d_arg = nullptr;
   const float* d_go;
-  float* d_gx;
+  void* d_gx;
   st.in(&d_rows, rows, (size_t)num_ids);
   st.in(&d_cnt, cnt, (size_t)num_segments);
   if (with_arg) st.in(&d_arg, arg, (size_t)num_segments * dim);
   st.in(&d_go, grad_out, (size_t)num_segments * dim);
-  st.out(&d_gx, grad_x, (size_t)num_rows * dim);
+  st.out_bytes(&d_gx, grad_x, (size_t)num_rows * dim * (size_t)glx_dtype_size(grad_x_dtype));
   rc = st.begin();
   if (rc == GLX_OK) {
     if (num_ids == 0 || num_segments == 0) {  // nothing was consumed: every row is zeros
-      rc = glx_zero_f32_async(d_gx, (size_t)num_rows * dim, st.s);
+      rc = glx_zero_elems_async(d_gx, (size_t)num_rows * dim, grad_x_dtype, st.s);
     } else {
-      rc = backward_device(op, d_rows, d_cnt, d_arg, num_ids, num_segments, num_rows, dim, d_go, d_gx, st.s);
+      rc = backward_device(op, d_rows, d_cnt, d_arg, num_ids, num_segments, num_rows, dim, d_go, d_gx, grad_x_dtype,
+                           st.s);
     }
   }
   return st.finish(rc);
+}
+
+extern "C" int glx_aggregate_backward(int device, int op, const int64_t* rows, const int32_t* cnt, const int32_t* arg,
+                                      int32_t num_ids, int32_t num_segments, int64_t num_rows, int32_t dim,
+                                      const float* grad_out, float* grad_x, int ptr_kind, void* stream) {
+  return glx_aggregate_backward_ex(device, op, rows, cnt, arg, num_ids, num_segments, num_rows, dim, grad_out, grad_x,
+                                   GLX_DTYPE_F32, ptr_kind, stream);
 }

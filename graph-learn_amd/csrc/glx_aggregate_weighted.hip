@@ -15,6 +15,11 @@
 //                a fixed lane-to-column mapping and a fixed cross-lane tree -- the same bits on every run, but the order
 //                over the columns is the mapping's, so this one is checked against a bound, not bit for bit
 // No float atomics anywhere.
+//
+// x is float32 or bfloat16 (the _ex entry points).  A bfloat16 x is upcast as it is loaded -- exact --
+// and folded exactly as above, so emb and grad_w stay float32 and equal the float32 call on the upcast matrix bit for
+// bit (grad_w: the same VEC, plan and tree).  A bfloat16 grad_x is the float32 sum above rounded once per element, to
+// nearest even (glx_f32_to_bf16_bits), in the kernel's final store.  w, grad_out, emb and grad_w are always float32.
 #include "glx_segment_lanes.h"
 
 // Two roundings per term: glx_fold_rn (glx_lane_groups.h) pins the product; the pragma is for the front end.
@@ -26,7 +31,8 @@ constexpr int kWU = 4;  // row loads in flight per lane
 
 // ---- forward -----------------------------------------------------------------------------------------------
 struct WFwdArgs {
-  const float* x;          // [num_rows, dim]
+  const void* x;           // [num_rows, dim] of `dtype` elements
+  int dtype;               // GLX_DTYPE_F32 or GLX_DTYPE_BF16
   const int64_t* rows;     // [num_ids]
   const float* w;          // [num_ids, heads]
   GlxSegLayout seg;
@@ -41,10 +47,12 @@ struct WFwdArgs {
 // only when C % 4 == 0: a lane's columns then share one head).  Lane c fetches position base + c of the segment (its
 // row, already tested against [0, num_rows)) and every lane of the group reads entry j from lane j; kWU row loads and
 // their weights are issued before the first is folded.  The group walks its segment together, so the cross-lane reads
-// stay inside a group whose lanes all run the same iterations.
-template <int OP, int G, int VEC>
+// stay inside a group whose lanes all run the same iterations.  A bfloat16 x is upcast as it is loaded (exact): the
+// fold is the float32 kernel's on the upcast values, in its order.
+template <int OP, int G, int VEC, int DT>
 __global__ __launch_bounds__(256) void glx_aggregate_weighted_kernel(WFwdArgs a) {
   typedef float vec_t __attribute__((ext_vector_type(VEC)));
+  const typename AggElem<DT>::raw* __restrict__ x = static_cast<const typename AggElem<DT>::raw*>(a.x);
   const int64_t gid = blockIdx.x * (int64_t)(256 / G) + threadIdx.x / G;
   const int c = threadIdx.x & (G - 1);
   if (gid >= a.seg.num_segments) return;  // whole groups leave
@@ -77,7 +85,7 @@ __global__ __launch_bounds__(256) void glx_aggregate_weighted_kernel(WFwdArgs a)
           if (j + u < m) {
             wt[u] = a.w[(int64_t)(base + j + u) * a.heads + head];
             if (row[u] >= 0) {
-              val[u] = *reinterpret_cast<const vec_t*>(a.x + row[u] * (int64_t)a.dim + col_ld);
+              val[u] = agg_load<DT, VEC>(x + row[u] * (int64_t)a.dim + col_ld);
             } else {
 #pragma unroll
               for (int v = 0; v < VEC; ++v) val[u][v] = a.default_attr;
@@ -110,13 +118,15 @@ void launch_wfwd_vec(const WFwdArgs& a, hipStream_t s) {
   const int G = glx_group_for((a.dim + VEC - 1) / VEC);
   const unsigned blocks = (unsigned)(((int64_t)a.seg.num_segments + (256 / G) - 1) / (256 / G));
   glx_for_group(G, [&](auto g) {
-    glx_aggregate_weighted_kernel<OP, decltype(g)::value, VEC><<<blocks, 256, 0, s>>>(a);
+    glx_for_train_dtype(a.dtype, [&](auto t) {
+      glx_aggregate_weighted_kernel<OP, decltype(g)::value, VEC, decltype(t)::value><<<blocks, 256, 0, s>>>(a);
+    });
   });
 }
 
 template <int OP>
 void launch_wfwd(const WFwdArgs& a, hipStream_t s) {
-  const bool vec4 = a.dim % 4 == 0 && a.C % 4 == 0 && glx_aligned16(a.x) && glx_aligned16(a.emb);
+  const bool vec4 = a.dim % 4 == 0 && a.C % 4 == 0 && glx_aligned_vec4(a.x, a.dtype) && glx_aligned16(a.emb);
   if (vec4) launch_wfwd_vec<OP, 4>(a, s);
   else launch_wfwd_vec<OP, 1>(a, s);
 }
@@ -126,7 +136,8 @@ struct WBwdXArgs {
   GlxAggTranspose t;
   const float* w;         // [num_ids, heads]
   const float* grad_out;  // [num_segments, dim]
-  float* grad_x;          // [num_rows, dim]
+  void* grad_x;           // [num_rows, dim] of `dtype` elements
+  int dtype;              // GLX_DTYPE_F32 or GLX_DTYPE_BF16
   GlxSegLayout seg;       // the transpose's segment ends and fanout: Mean's divisor
   int64_t num_rows;
   int32_t dim, heads, C;
@@ -134,15 +145,17 @@ struct WBwdXArgs {
 
 // The sibling of glx_aggregate_bwd_kernel (glx_aggregate_grad.hip) that also fetches the weight of each list entry:
 // G lanes own table row r, lane c fetches list entry base + c (its position, that position's segment and, for Mean,
-// the divisor), every lane reads entry j from lane j.  Every row is written, an empty list writes zeros.
-template <int OP, int G, int VEC>
+// the divisor), every lane reads entry j from lane j.  Every row is written, an empty list writes zeros.  The sum is
+// float32 whatever DT; a bfloat16 grad_x rounds the finished sum once, in the store (agg_store).
+template <int OP, int G, int VEC, int DT>
 __global__ __launch_bounds__(256) void glx_aggregate_weighted_bwd_x_kernel(WBwdXArgs a) {
   typedef float vec_t __attribute__((ext_vector_type(VEC)));
+  typedef typename AggElem<DT>::raw raw_t;
   const int64_t r = blockIdx.x * (int64_t)(256 / G) + threadIdx.x / G;
   const int c = threadIdx.x & (G - 1);
   if (r >= a.num_rows) return;  // whole groups leave
   const int32_t l0 = a.t.row_ptr[r], l1 = a.t.row_ptr[r + 1];
-  float* const out = a.grad_x + r * (int64_t)a.dim;
+  raw_t* const out = static_cast<raw_t*>(a.grad_x) + r * (int64_t)a.dim;
   for (int32_t col_pass = 0; col_pass < a.dim; col_pass += G * VEC) {
     const int32_t col = col_pass + c * VEC;
     const bool col_ok = col < a.dim;
@@ -191,7 +204,7 @@ __global__ __launch_bounds__(256) void glx_aggregate_weighted_bwd_x_kernel(WBwdX
         }
       }
     }
-    if (col_ok) *reinterpret_cast<vec_t*>(out + col) = acc;
+    if (col_ok) agg_store<DT, VEC>(out + col, acc);  // lanes past the last column store nothing
   }
 }
 
@@ -200,20 +213,24 @@ void launch_wbwd_x_vec(const WBwdXArgs& a, hipStream_t s) {
   const int G = glx_group_for((a.dim + VEC - 1) / VEC);
   const unsigned blocks = (unsigned)((a.num_rows + (256 / G) - 1) / (256 / G));
   glx_for_group(G, [&](auto g) {
-    glx_aggregate_weighted_bwd_x_kernel<OP, decltype(g)::value, VEC><<<blocks, 256, 0, s>>>(a);
+    glx_for_train_dtype(a.dtype, [&](auto t) {
+      glx_aggregate_weighted_bwd_x_kernel<OP, decltype(g)::value, VEC, decltype(t)::value><<<blocks, 256, 0, s>>>(a);
+    });
   });
 }
 
 template <int OP>
 void launch_wbwd_x(const WBwdXArgs& a, hipStream_t s) {
-  const bool vec4 = a.dim % 4 == 0 && a.C % 4 == 0 && glx_aligned16(a.grad_out) && glx_aligned16(a.grad_x);
+  const bool vec4 =
+      a.dim % 4 == 0 && a.C % 4 == 0 && glx_aligned16(a.grad_out) && glx_aligned_vec4(a.grad_x, a.dtype);
   if (vec4) launch_wbwd_x_vec<OP, 4>(a, s);
   else launch_wbwd_x_vec<OP, 1>(a, s);
 }
 
 // ---- gradient with respect to the weights ---------------------------------------------------------------------
 struct WBwdWArgs {
-  const float* x;          // [num_rows, dim]
+  const void* x;           // [num_rows, dim] of `dtype` elements
+  int dtype;               // GLX_DTYPE_F32 or GLX_DTYPE_BF16
   const int64_t* rows;     // [num_ids]
   GlxSegLayout seg;
   const int32_t* cnt;      // [num_segments], or nullptr
@@ -227,8 +244,8 @@ struct WBwdWArgs {
 
 // G lanes own one POSITION p and write grad_w[p, 0 .. heads): glx_head_dots (glx_lane_groups.h) of the segment's
 // grad_out row and the position's table row.  A position that was not consumed writes +0.0f; an out-of-range row
-// multiplies a row of default_attr.
-template <int OP, int G, int VEC, bool SUB>
+// multiplies a row of default_attr.  A bfloat16 x is upcast as it is loaded: the same products in the same tree.
+template <int OP, int G, int VEC, bool SUB, int DT>
 __global__ __launch_bounds__(256) void glx_aggregate_weighted_bwd_w_kernel(WBwdWArgs a) {
   const int64_t p = blockIdx.x * (int64_t)(256 / G) + threadIdx.x / G;
   const int c = threadIdx.x & (G - 1);
@@ -241,7 +258,8 @@ __global__ __launch_bounds__(256) void glx_aggregate_weighted_bwd_w_kernel(WBwdW
   }
   const float div = OP == GLX_AGG_MEAN ? (float)seg_count(a.seg, sg) : 1.0f;
   const GlxRow go = {a.grad_out + sg * (int64_t)a.dim, true};
-  const GlxRow xr = glx_row(a.x, a.rows[p], a.num_rows, a.dim);
+  const GlxRowOf<DT> xr =
+      glx_row<DT>(static_cast<const typename AggElem<DT>::raw*>(a.x), a.rows[p], a.num_rows, a.dim);
   glx_head_dots<G, VEC, SUB, OP == GLX_AGG_MEAN>(go, xr, a.default_attr, a.dim, a.heads, a.C, a.hd, div, c, out);
 }
 
@@ -252,15 +270,18 @@ void launch_wbwd_w_vec(WBwdWArgs a, hipStream_t s) {
   a.hd = plan.hd;
   const unsigned blocks = (unsigned)(((int64_t)a.seg.num_ids + (256 / G) - 1) / (256 / G));
   glx_for_group(G, [&](auto g) {
-    constexpr int kG = decltype(g)::value;
-    if (plan.sub_groups) glx_aggregate_weighted_bwd_w_kernel<OP, kG, VEC, true><<<blocks, 256, 0, s>>>(a);
-    else glx_aggregate_weighted_bwd_w_kernel<OP, kG, VEC, false><<<blocks, 256, 0, s>>>(a);
+    glx_for_train_dtype(a.dtype, [&](auto t) {
+      constexpr int kG = decltype(g)::value, kDT = decltype(t)::value;
+      if (plan.sub_groups) glx_aggregate_weighted_bwd_w_kernel<OP, kG, VEC, true, kDT><<<blocks, 256, 0, s>>>(a);
+      else glx_aggregate_weighted_bwd_w_kernel<OP, kG, VEC, false, kDT><<<blocks, 256, 0, s>>>(a);
+    });
   });
 }
 
 template <int OP>
 void launch_wbwd_w(const WBwdWArgs& a, hipStream_t s) {
-  const bool vec4 = a.dim % 4 == 0 && a.C % 4 == 0 && glx_aligned16(a.x) && glx_aligned16(a.grad_out);
+  // the same VEC, and so the same plan and reduction tree, for a bfloat16 x as for the float32 matrix of its values
+  const bool vec4 = a.dim % 4 == 0 && a.C % 4 == 0 && glx_aligned_vec4(a.x, a.dtype) && glx_aligned16(a.grad_out);
   if (vec4) launch_wbwd_w_vec<OP, 4>(a, s);
   else launch_wbwd_w_vec<OP, 1>(a, s);
 }
@@ -269,14 +290,15 @@ void launch_wbwd_w(const WBwdWArgs& a, hipStream_t s) {
 
 // grad_x of a request whose transpose the caller holds (device pointers, op Sum or Mean): the body of
 // glx_aggregate_weighted_backward_x, and the two row gradients of glx_dot_attention_backward on one transpose
-void glx_weighted_bwd_x(int op, const GlxAggTranspose& t, const float* w, const float* grad_out, float* grad_x,
+void glx_weighted_bwd_x(int op, const GlxAggTranspose& t, const float* w, const float* grad_out, void* grad_x,
                         int64_t num_rows, int32_t dim, int32_t heads, int32_t num_ids, int32_t num_segments,
-                        hipStream_t s) {
+                        hipStream_t s, int grad_x_dtype) {
   WBwdXArgs a;
   a.t = t;
   a.w = w;
   a.grad_out = grad_out;
   a.grad_x = grad_x;
+  a.dtype = grad_x_dtype;
   a.num_rows = num_rows;
   a.dim = dim;
   a.heads = heads;
@@ -300,10 +322,11 @@ void glx_weighted_bwd_x(int op, const GlxAggTranspose& t, const float* w, const 
   GLX_REQUIRE((int64_t)num_segments * dim <= INT32_MAX, "num_segments * dim exceeds int32 (tensor.h:47)");              \
   GLX_REQUIRE(ptr_kind == GLX_PTR_HOST || ptr_kind == GLX_PTR_DEVICE, "bad ptr_kind")
 
-extern "C" int glx_aggregate_weighted(int device, int op, const float* x, int64_t num_rows, int32_t dim,
-                                      const int64_t* rows, const float* w, int32_t heads, const int32_t* cnt,
-                                      int32_t num_ids, int32_t num_segments, float default_attr, float* emb_out,
-                                      int ptr_kind, void* stream) {
+extern "C" int glx_aggregate_weighted_ex(int device, int op, const void* x, int x_dtype, int64_t num_rows, int32_t dim,
+                                         const int64_t* rows, const float* w, int32_t heads, const int32_t* cnt,
+                                         int32_t num_ids, int32_t num_segments, float default_attr, float* emb_out,
+                                         int ptr_kind, void* stream) {
+  GLX_REQUIRE_TRAIN_DTYPE(x_dtype, "glx_aggregate_weighted_ex: x_dtype");
   GLX_WEIGHTED_REQUIRE("glx_aggregate_weighted");
   GLX_REQUIRE(num_rows == 0 || x != nullptr, "x is NULL");
   GLX_REQUIRE(num_ids == 0 || rows != nullptr, "rows is NULL");
@@ -316,7 +339,8 @@ extern "C" int glx_aggregate_weighted(int device, int op, const float* x, int64_
   GLX_REQUIRE(guard.ok, "cannot select device %d", device);
   GlxHostStage st(device, ptr_kind, stream, GlxHostStage::ADMIT);
   WFwdArgs a;
-  st.in(&a.x, x, (size_t)num_rows * dim);
+  a.dtype = x_dtype;
+  st.in_bytes(&a.x, x, (size_t)num_rows * dim * (size_t)glx_dtype_size(x_dtype));
   st.in(&a.rows, rows, (size_t)num_ids);
   st.in(&a.w, w, (size_t)num_ids * heads);
   st.in(&a.cnt, cnt, (size_t)num_segments);
@@ -337,10 +361,20 @@ extern "C" int glx_aggregate_weighted(int device, int op, const float* x, int64_
   return st.finish(rc);
 }
 
-extern "C" int glx_aggregate_weighted_backward_x(int device, int op, const int64_t* rows, const float* w, int32_t heads,
-                                                 const int32_t* cnt, int32_t num_ids, int32_t num_segments,
-                                                 int64_t num_rows, int32_t dim, const float* grad_out, float* grad_x,
-                                                 int ptr_kind, void* stream) {
+extern "C" int glx_aggregate_weighted(int device, int op, const float* x, int64_t num_rows, int32_t dim,
+                                      const int64_t* rows, const float* w, int32_t heads, const int32_t* cnt,
+                                      int32_t num_ids, int32_t num_segments, float default_attr, float* emb_out,
+                                      int ptr_kind, void* stream) {
+  return glx_aggregate_weighted_ex(device, op, x, GLX_DTYPE_F32, num_rows, dim, rows, w, heads, cnt, num_ids,
+                                   num_segments, default_attr, emb_out, ptr_kind, stream);
+}
+
+extern "C" int glx_aggregate_weighted_backward_x_ex(int device, int op, const int64_t* rows, const float* w,
+                                                    int32_t heads, const int32_t* cnt, int32_t num_ids,
+                                                    int32_t num_segments, int64_t num_rows, int32_t dim,
+                                                    const float* grad_out, void* grad_x, int grad_x_dtype,
+                                                    int ptr_kind, void* stream) {
+  GLX_REQUIRE_TRAIN_DTYPE(grad_x_dtype, "glx_aggregate_weighted_backward_x_ex: grad_x_dtype");
   GLX_WEIGHTED_REQUIRE("glx_aggregate_weighted_backward_x");
   GLX_REQUIRE(num_ids == 0 || rows != nullptr, "rows is NULL");
   GLX_REQUIRE(num_ids == 0 || w != nullptr, "w is NULL");
@@ -359,26 +393,37 @@ extern "C" int glx_aggregate_weighted_backward_x(int device, int op, const int64
   st.in(&a.w, w, (size_t)num_ids * heads);
   st.in(&d_cnt, cnt, (size_t)num_segments);
   st.in(&a.grad_out, grad_out, (size_t)num_segments * dim);
-  st.out(&a.grad_x, grad_x, (size_t)num_rows * dim);
+  st.out_bytes(&a.grad_x, grad_x, (size_t)num_rows * dim * (size_t)glx_dtype_size(grad_x_dtype));
   rc = st.begin();
   GlxScratch lease;
   if (rc == GLX_OK) {
     if (num_ids == 0 || num_segments == 0) {  // nothing was consumed: every row is zeros
-      rc = glx_zero_f32_async(a.grad_x, (size_t)num_rows * dim, st.s);
+      rc = glx_zero_elems_async(a.grad_x, (size_t)num_rows * dim, grad_x_dtype, st.s);
     } else {
       rc = glx_agg_transpose(d_rows, cnt ? d_cnt : nullptr, num_ids, num_segments, num_rows, st.s, &lease, &a.t);
       if (rc == GLX_OK) {
-        glx_weighted_bwd_x(op, a.t, a.w, a.grad_out, a.grad_x, num_rows, dim, heads, num_ids, num_segments, st.s);
+        glx_weighted_bwd_x(op, a.t, a.w, a.grad_out, a.grad_x, num_rows, dim, heads, num_ids, num_segments, st.s,
+                           grad_x_dtype);
       }
     }
   }
   return st.finish(rc);
 }
 
-extern "C" int glx_aggregate_weighted_backward_w(int device, int op, const float* x, int64_t num_rows, int32_t dim,
-                                                 const int64_t* rows, int32_t heads, const int32_t* cnt,
-                                                 int32_t num_ids, int32_t num_segments, float default_attr,
-                                                 const float* grad_out, float* grad_w, int ptr_kind, void* stream) {
+extern "C" int glx_aggregate_weighted_backward_x(int device, int op, const int64_t* rows, const float* w, int32_t heads,
+                                                 const int32_t* cnt, int32_t num_ids, int32_t num_segments,
+                                                 int64_t num_rows, int32_t dim, const float* grad_out, float* grad_x,
+                                                 int ptr_kind, void* stream) {
+  return glx_aggregate_weighted_backward_x_ex(device, op, rows, w, heads, cnt, num_ids, num_segments, num_rows, dim,
+                                              grad_out, grad_x, GLX_DTYPE_F32, ptr_kind, stream);
+}
+
+extern "C" int glx_aggregate_weighted_backward_w_ex(int device, int op, const void* x, int x_dtype, int64_t num_rows,
+                                                    int32_t dim, const int64_t* rows, int32_t heads,
+                                                    const int32_t* cnt, int32_t num_ids, int32_t num_segments,
+                                                    float default_attr, const float* grad_out, float* grad_w,
+                                                    int ptr_kind, void* stream) {
+  GLX_REQUIRE_TRAIN_DTYPE(x_dtype, "glx_aggregate_weighted_backward_w_ex: x_dtype");
   GLX_WEIGHTED_REQUIRE("glx_aggregate_weighted_backward_w");
   GLX_REQUIRE(num_rows == 0 || x != nullptr, "x is NULL");
   GLX_REQUIRE(num_ids == 0 || rows != nullptr, "rows is NULL");
@@ -391,7 +436,8 @@ extern "C" int glx_aggregate_weighted_backward_w(int device, int op, const float
   GLX_REQUIRE(guard.ok, "cannot select device %d", device);
   GlxHostStage st(device, ptr_kind, stream, GlxHostStage::ADMIT);
   WBwdWArgs a;
-  st.in(&a.x, x, (size_t)num_rows * dim);
+  a.dtype = x_dtype;
+  st.in_bytes(&a.x, x, (size_t)num_rows * dim * (size_t)glx_dtype_size(x_dtype));
   st.in(&a.rows, rows, (size_t)num_ids);
   st.in(&a.cnt, cnt, (size_t)num_segments);
   st.in(&a.grad_out, grad_out, (size_t)num_segments * dim);
@@ -416,4 +462,12 @@ extern "C" int glx_aggregate_weighted_backward_w(int device, int op, const float
     }
   }
   return st.finish(rc);
+}
+
+extern "C" int glx_aggregate_weighted_backward_w(int device, int op, const float* x, int64_t num_rows, int32_t dim,
+                                                 const int64_t* rows, int32_t heads, const int32_t* cnt,
+                                                 int32_t num_ids, int32_t num_segments, float default_attr,
+                                                 const float* grad_out, float* grad_w, int ptr_kind, void* stream) {
+  return glx_aggregate_weighted_backward_w_ex(device, op, x, GLX_DTYPE_F32, num_rows, dim, rows, heads, cnt, num_ids,
+                                              num_segments, default_attr, grad_out, grad_w, ptr_kind, stream);
 }

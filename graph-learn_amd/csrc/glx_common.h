@@ -983,9 +983,10 @@ int glx_agg_transpose(const int64_t* rows, const int32_t* cnt, int32_t n, int32_
                       hipStream_t s, GlxScratch* lease, GlxAggTranspose* out);
 // glx_aggregate_weighted_backward_x on a transpose the caller holds (glx_aggregate_weighted.hip): grad_x[num_rows, dim]
 // = +0.0f plus fmul_rn(w[p, head], grad_out[s(p)]) (Mean: / count) in ascending p; device pointers, every row written.
-void glx_weighted_bwd_x(int op, const GlxAggTranspose& t, const float* w, const float* grad_out, float* grad_x,
+// grad_x holds grad_x_dtype elements (GLX_DTYPE_F32 or GLX_DTYPE_BF16: the float32 sum rounded once in the store).
+void glx_weighted_bwd_x(int op, const GlxAggTranspose& t, const float* w, const float* grad_out, void* grad_x,
                         int64_t num_rows, int32_t dim, int32_t heads, int32_t num_ids, int32_t num_segments,
-                        hipStream_t s);
+                        hipStream_t s, int grad_x_dtype = GLX_DTYPE_F32);
 // seg_end[num_segments]: inclusive prefix sums of the clamped (>= 0) counts, in `lease` (workspace slot 1).
 int glx_agg_segment_ends(const int32_t* cnt, int32_t num_segments, hipStream_t s, GlxScratch* lease,
                          const int64_t** seg_end);
@@ -1096,6 +1097,41 @@ __device__ __forceinline__ float __attribute__((ext_vector_type(VEC))) agg_load(
   return agg_up<DT, VEC>(agg_load_raw<DT, VEC>(p));
 }
 
+// float32 -> bfloat16, round to nearest even, bit-identical -- all 2^32 inputs -- to torch.Tensor.to(torch.bfloat16) of
+// a contiguous CPU tensor, i.e. torch's vectorised conversion.  NaN included: that conversion emits 0xFFFF for every
+// NaN (torch's scalar fallback, used for strided tensors, emits 0x7FC0; the uploads convert contiguous matrices).
+// Integer arithmetic only, so no floating-point mode (denormal flushing) can change a result.  The uploads
+// (glx_aggregate.hip), glx_features_convert_host and the bfloat16 row gradients of the training path (agg_store) share
+// it.
+__host__ __device__ __forceinline__ uint16_t glx_f32_to_bf16_bits(uint32_t u) {
+  if ((u & 0x7fffffffu) > 0x7f800000u) return 0xFFFF;
+  return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);  // a carry out of the mantissa rounds up to the next binade / inf
+}
+
+// VEC float32 values into VEC consecutive elements of a float32 or bfloat16 matrix: ONE store of VEC * sizeof(raw)
+// bytes.  float32 stores the values as they are; bfloat16 rounds each once with glx_f32_to_bf16_bits (to nearest
+// even, NaN -> 0xFFFF, subnormals and the sign of zero kept) and packs them -- the row gradients of the training path.
+template <int DT, int VEC>
+__device__ __forceinline__ void agg_store(typename AggElem<DT>::raw* p, float __attribute__((ext_vector_type(VEC))) v) {
+  static_assert(DT == GLX_DTYPE_F32 || DT == GLX_DTYPE_BF16, "only float32 and bfloat16 have a gradient contract");
+  if constexpr (DT == GLX_DTYPE_F32) {
+    *reinterpret_cast<float __attribute__((ext_vector_type(VEC)))*>(p) = v;
+  } else {
+    agg_raw_vec<DT, VEC> q;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) q[k] = glx_f32_to_bf16_bits(__float_as_uint(v[k]));
+    *reinterpret_cast<agg_raw_vec<DT, VEC>*>(p) = q;
+  }
+}
+
+// The tables and row gradients of the training path hold float32 or bfloat16 (include/glx.h, the _ex entry points);
+// checked before any device use.
+#define GLX_REQUIRE_TRAIN_DTYPE(dt, what)                                                                               \
+  GLX_REQUIRE((dt) == GLX_DTYPE_F32 || (dt) == GLX_DTYPE_BF16,                                                          \
+              what " must be GLX_DTYPE_F32 or GLX_DTYPE_BF16, not dtype id %d: bfloat16 is the half type that has a "   \
+                   "gradient contract (float16 gradients need loss scaling, float8 has none)",                          \
+              (int)(dt))
+
 // Admission control for host-pointer calls.  The reference's servers run up to 32 pool threads on one
 // operator (in_memory_service.cc:64-71); on one GPU more than a dozen host-pointer calls in flight only contend
 // (runtime locks, copy queues: 32 unlimited threads measured 2.2e8 edges/s, 3.7e8 with 12 admitted), so the
@@ -1153,6 +1189,9 @@ struct GlxHostStage {
   void in(const T** d, const T* h, size_t n) { declare(reinterpret_cast<void**>(const_cast<T**>(d)), h, n * sizeof(T), kIn); }
   template <typename T>
   void out(T** d, T* h, size_t n) { declare(reinterpret_cast<void**>(d), h, n * sizeof(T), kOut); }
+  // a buffer whose element type the call only learns from a dtype argument: sized in bytes
+  void in_bytes(const void** d, const void* h, size_t bytes) { declare(const_cast<void**>(d), h, bytes, kIn); }
+  void out_bytes(void** d, void* h, size_t bytes) { declare(d, h, bytes, kOut); }
   template <typename T>
   void scratch(T** d, size_t n) { declare(reinterpret_cast<void**>(d), nullptr, n * sizeof(T), kScratch); }
   int begin();

@@ -24,6 +24,13 @@ inline void glx_for_group(int G, F&& f) {
 // a float4 / int4 access needs it
 inline bool glx_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// a 4-ELEMENT access of a float32 / bfloat16 matrix needs it: 16 bytes for float32, 8 for bfloat16.  Every matrix of
+// dim % 4 == 0 from an allocator that hands out 16-byte aligned blocks passes in both types, so a bfloat16 call takes
+// the VEC -- and with it the lane-to-column mapping -- the float32 call takes.
+inline bool glx_aligned_vec4(const void* p, int dtype) {
+  return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(4 * glx_dtype_size(dtype) - 1)) == 0;
+}
+
 // the pieces of one workspace lease start on 256-byte boundaries
 inline size_t glx_align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
@@ -43,26 +50,30 @@ __device__ __forceinline__ float glx_fold_rn(float acc, float w, float x) {
   return acc + glx_pin(w * x);  // the product is rounded, pinned, and the sum rounded again
 }
 
-// A gathered row of a float table; an index outside the table reads a row of default_attr instead (ok == false: `at`
-// is never read).
-struct GlxRow {
-  const float* at;
+// A gathered row of a table of DT elements (float32, or bfloat16 upcast exactly as it is loaded); an index outside the
+// table reads a row of default_attr instead (ok == false: `at` is never read).
+template <int DT>
+struct GlxRowOf {
+  const typename AggElem<DT>::raw* at;
   bool ok;
 };
+typedef GlxRowOf<GLX_DTYPE_F32> GlxRow;
 
-__device__ __forceinline__ GlxRow glx_row(const float* x, int64_t r, int64_t num_rows, int32_t dim) {
+template <int DT = GLX_DTYPE_F32>
+__device__ __forceinline__ GlxRowOf<DT> glx_row(const typename AggElem<DT>::raw* x, int64_t r, int64_t num_rows,
+                                                int32_t dim) {
   const bool in = r >= 0 && r < num_rows;
-  return GlxRow{x + (in ? r : 0) * (int64_t)dim, in};
+  return GlxRowOf<DT>{x + (in ? r : 0) * (int64_t)dim, in};
 }
 
-// VEC columns of it from `col` on
-template <int VEC>
-__device__ __forceinline__ float __attribute__((ext_vector_type(VEC))) glx_row_load(GlxRow row, int32_t col,
+// VEC columns of it from `col` on, as float32: one load of VEC elements
+template <int VEC, int DT>
+__device__ __forceinline__ float __attribute__((ext_vector_type(VEC))) glx_row_load(GlxRowOf<DT> row, int32_t col,
                                                                                      float default_attr) {
   typedef float vec_t __attribute__((ext_vector_type(VEC)));
   vec_t v;
   if (row.ok) {
-    v = *reinterpret_cast<const vec_t*>(row.at + col);
+    v = agg_load<DT, VEC>(row.at + col);
   } else {
 #pragma unroll
     for (int k = 0; k < VEC; ++k) v[k] = default_attr;
@@ -124,10 +135,10 @@ __device__ __forceinline__ void glx_head_dots_of(LA&& la, LB&& lb, int32_t dim, 
   }
 }
 
-// the two operands are gathered rows
-template <int G, int VEC, bool SUB, bool DIV>
-__device__ __forceinline__ void glx_head_dots(GlxRow ra, GlxRow rb, float default_attr, int32_t dim, int32_t heads,
-                                              int32_t C, GlxHeadDots hd, float div, int c, float* out) {
+// the two operands are gathered rows, each of its own element type
+template <int G, int VEC, bool SUB, bool DIV, int DTA, int DTB>
+__device__ __forceinline__ void glx_head_dots(GlxRowOf<DTA> ra, GlxRowOf<DTB> rb, float default_attr, int32_t dim,
+                                              int32_t heads, int32_t C, GlxHeadDots hd, float div, int c, float* out) {
   glx_head_dots_of<G, VEC, SUB, DIV>([&](int32_t col) { return glx_row_load<VEC>(ra, col, default_attr); },
                                      [&](int32_t col) { return glx_row_load<VEC>(rb, col, default_attr); }, dim, heads,
                                      C, hd, div, c, out);
@@ -152,15 +163,27 @@ inline GlxHeadDotPlan glx_head_dot_plan(int32_t dim, int32_t C, int VEC) {
   return p;
 }
 
-// +0.0f into an output that no kernel will write; nothing to do for an absent or empty one
-inline int glx_zero_f32_async(float* p, size_t count, hipStream_t s) {
+// +0.0 into `count` ELEMENTS of a float32 / bfloat16 output that no kernel will write (all bits clear is +0.0 in both;
+// the bytes are the buffer's own: a bfloat16 buffer has half of float32's); nothing to do for an absent or empty one
+inline int glx_zero_elems_async(void* p, size_t count, int dtype, hipStream_t s) {
   if (p == nullptr || count == 0) return GLX_OK;
-  hipError_t e = hipMemsetAsync(p, 0, count * sizeof(float), s);
+  hipError_t e = hipMemsetAsync(p, 0, count * (size_t)glx_dtype_size(dtype), s);
   if (e != hipSuccess) {
     glx_set_error("hipMemsetAsync failed: %s", hipGetErrorString(e));
     return GLX_INTERNAL;
   }
   return GLX_OK;
+}
+inline int glx_zero_f32_async(float* p, size_t count, hipStream_t s) {
+  return glx_zero_elems_async(p, count, GLX_DTYPE_F32, s);
+}
+
+// f(std::integral_constant<int, DT>()) for the two element types of the training path (GLX_REQUIRE_TRAIN_DTYPE has
+// passed): a kernel template takes decltype(t)::value
+template <typename F>
+inline void glx_for_train_dtype(int dtype, F&& f) {
+  if (dtype == GLX_DTYPE_BF16) f(std::integral_constant<int, GLX_DTYPE_BF16>());
+  else f(std::integral_constant<int, GLX_DTYPE_F32>());
 }
 
 #endif  // GLX_LANE_GROUPS_H_

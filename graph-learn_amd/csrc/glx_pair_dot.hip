@@ -14,6 +14,11 @@
 //              fadd_rn(., fmul_rn(g[p, head(c)], xb_row(p)[c])); side 1 (xb): pairs with ib[p] == r, factor xa_row(p)[c].
 //              An own index outside the table receives nothing.  Bit-exact.
 // No float atomics anywhere.
+//
+// The tables are float32 or bfloat16, both of one type (the _ex entry points).  bfloat16 rows are upcast
+// as they are loaded -- exact -- so out stays float32 and equals the float32 call on the upcast tables bit for bit (the
+// same VEC, plan and tree); a bfloat16 grad_self is the float32 sum above rounded once per element, to nearest even
+// (glx_f32_to_bf16_bits), in the kernel's final store.  g and out are always float32.
 #include "glx_lane_groups.h"
 
 // Two roundings per term of the backward: glx_fold_rn (glx_lane_groups.h) pins the product; the pragma is for the
@@ -26,8 +31,9 @@ constexpr int kWU = 4;  // row loads in flight per lane
 
 // ---- forward -----------------------------------------------------------------------------------------------
 struct PairFwdArgs {
-  const float* xa;     // [num_rows_a, dim]
-  const float* xb;     // [num_rows_b, dim]
+  const void* xa;      // [num_rows_a, dim] of `dtype` elements
+  const void* xb;      // [num_rows_b, dim] of `dtype` elements
+  int dtype;           // GLX_DTYPE_F32 or GLX_DTYPE_BF16, of both tables
   const int64_t* ia;   // [num_pairs / repeat]
   const int64_t* ib;   // [num_pairs]
   float* out;          // [num_pairs, heads]
@@ -39,17 +45,21 @@ struct PairFwdArgs {
 
 // G lanes own one PAIR p and write out[p, 0 .. heads): glx_head_dots (glx_lane_groups.h) of the pair's two rows.
 // The `repeat` pairs of one source are neighbouring groups of a workgroup: the shared row comes out of the L1 / L2.
-template <int G, int VEC, bool SUB>
+// bfloat16 tables are upcast as they are loaded: the same products in the same tree.
+template <int G, int VEC, bool SUB, int DT>
 __global__ __launch_bounds__(256) void glx_pair_dot_kernel(PairFwdArgs a) {
+  typedef typename AggElem<DT>::raw raw_t;
   const int64_t p = blockIdx.x * (int64_t)(256 / G) + threadIdx.x / G;
   const int c = threadIdx.x & (G - 1);
   if (p >= a.num_pairs) return;  // whole groups leave
   float* const out = a.out + p * (int64_t)a.heads;
   const int64_t ra = a.ia[p / a.repeat], rb = a.ib[p];
-  const float* const xa = (ra >= 0 && ra < a.num_rows_a) ? a.xa + ra * (int64_t)a.dim : nullptr;
-  const float* const xb = (rb >= 0 && rb < a.num_rows_b) ? a.xb + rb * (int64_t)a.dim : nullptr;
+  const raw_t* const xa =
+      (ra >= 0 && ra < a.num_rows_a) ? static_cast<const raw_t*>(a.xa) + ra * (int64_t)a.dim : nullptr;
+  const raw_t* const xb =
+      (rb >= 0 && rb < a.num_rows_b) ? static_cast<const raw_t*>(a.xb) + rb * (int64_t)a.dim : nullptr;
   // the null-pointer form, not glx_row: its clamped pointer costs this kernel up to two VGPRs
-  const GlxRow rowa = {xa, xa != nullptr}, rowb = {xb, xb != nullptr};
+  const GlxRowOf<DT> rowa = {xa, xa != nullptr}, rowb = {xb, xb != nullptr};
   glx_head_dots<G, VEC, SUB, false>(rowa, rowb, a.default_attr, a.dim, a.heads, a.C, a.hd, 1.0f, c, out);
 }
 
@@ -60,13 +70,18 @@ void launch_pair_fwd_vec(PairFwdArgs a, hipStream_t s) {
   a.hd = plan.hd;
   const unsigned blocks = (unsigned)(((int64_t)a.num_pairs + (256 / G) - 1) / (256 / G));
   glx_for_group(G, [&](auto g) {
-    if (plan.sub_groups) glx_pair_dot_kernel<decltype(g)::value, VEC, true><<<blocks, 256, 0, s>>>(a);
-    else glx_pair_dot_kernel<decltype(g)::value, VEC, false><<<blocks, 256, 0, s>>>(a);
+    glx_for_train_dtype(a.dtype, [&](auto t) {
+      constexpr int kG = decltype(g)::value, kDT = decltype(t)::value;
+      if (plan.sub_groups) glx_pair_dot_kernel<kG, VEC, true, kDT><<<blocks, 256, 0, s>>>(a);
+      else glx_pair_dot_kernel<kG, VEC, false, kDT><<<blocks, 256, 0, s>>>(a);
+    });
   });
 }
 
 void launch_pair_fwd(const PairFwdArgs& a, hipStream_t s) {
-  const bool vec4 = a.dim % 4 == 0 && a.C % 4 == 0 && glx_aligned16(a.xa) && glx_aligned16(a.xb);
+  // the same VEC, and so the same plan and reduction tree, for bfloat16 tables as for the float32 ones of their values
+  const bool vec4 =
+      a.dim % 4 == 0 && a.C % 4 == 0 && glx_aligned_vec4(a.xa, a.dtype) && glx_aligned_vec4(a.xb, a.dtype);
   if (vec4) launch_pair_fwd_vec<4>(a, s);
   else launch_pair_fwd_vec<1>(a, s);
 }
@@ -76,8 +91,9 @@ struct PairBwdArgs {
   GlxAggTranspose t;         // of the own side's index array: row r's entries are t.pos[t.row_ptr[r] .. t.row_ptr[r + 1])
   const int64_t* other_idx;  // the other side's index array
   const float* g;            // [num_pairs, heads]
-  const float* x_other;      // [num_rows_other, dim]
-  float* grad_self;          // [num_rows_self, dim]
+  const void* x_other;       // [num_rows_other, dim] of `dtype` elements
+  void* grad_self;           // [num_rows_self, dim] of `dtype` elements
+  int dtype;                 // GLX_DTYPE_F32 or GLX_DTYPE_BF16, of both
   int64_t num_rows_self, num_rows_other;
   int32_t dim, heads, C;
   int32_t own_rep;    // pairs per entry of the own index array: repeat (side 0) or 1 (side 1)
@@ -89,16 +105,19 @@ struct PairBwdArgs {
 // list of own-side entries, each expanded to own_rep consecutive pairs, is one run of (l1 - l0) * own_rep pairs in
 // ascending p (ascending entries give ascending pairs).  Lane c fetches pair base + c of the run (its number and the
 // other side's row, already tested against the table), every lane reads entry j from lane j; kWU row loads and their
-// g are issued before the first is folded.  Every row is written, an empty list writes zeros.
-template <int G, int VEC>
+// g are issued before the first is folded.  Every row is written, an empty list writes zeros.  A bfloat16 x_other is
+// upcast as it is loaded, the sum is float32, and a bfloat16 grad_self rounds the finished sum once, in the store.
+template <int G, int VEC, int DT>
 __global__ __launch_bounds__(256) void glx_pair_dot_bwd_kernel(PairBwdArgs a) {
   typedef float vec_t __attribute__((ext_vector_type(VEC)));
+  typedef typename AggElem<DT>::raw raw_t;
+  const raw_t* __restrict__ x_other = static_cast<const raw_t*>(a.x_other);
   const int64_t r = blockIdx.x * (int64_t)(256 / G) + threadIdx.x / G;
   const int c = threadIdx.x & (G - 1);
   if (r >= a.num_rows_self) return;  // whole groups leave
   const int32_t l0 = a.t.row_ptr[r];
   const int32_t total = (a.t.row_ptr[r + 1] - l0) * a.own_rep;  // at most num_pairs
-  float* const out = a.grad_self + r * (int64_t)a.dim;
+  raw_t* const out = static_cast<raw_t*>(a.grad_self) + r * (int64_t)a.dim;
   for (int32_t col_pass = 0; col_pass < a.dim; col_pass += G * VEC) {
     const int32_t col = col_pass + c * VEC;
     const bool col_ok = col < a.dim;
@@ -131,7 +150,7 @@ __global__ __launch_bounds__(256) void glx_pair_dot_bwd_kernel(PairBwdArgs a) {
           if (j + u < m) {
             gt[u] = a.g[(int64_t)pr[u] * a.heads + head];
             if (row[u] >= 0) {
-              val[u] = *reinterpret_cast<const vec_t*>(a.x_other + row[u] * (int64_t)a.dim + col_ld);
+              val[u] = agg_load<DT, VEC>(x_other + row[u] * (int64_t)a.dim + col_ld);
             } else {
 #pragma unroll
               for (int v = 0; v < VEC; ++v) val[u][v] = a.default_attr;
@@ -147,7 +166,7 @@ __global__ __launch_bounds__(256) void glx_pair_dot_bwd_kernel(PairBwdArgs a) {
         }
       }
     }
-    if (col_ok) *reinterpret_cast<vec_t*>(out + col) = acc;
+    if (col_ok) agg_store<DT, VEC>(out + col, acc);  // lanes past the last column store nothing
   }
 }
 
@@ -155,11 +174,16 @@ template <int VEC>
 void launch_pair_bwd_vec(const PairBwdArgs& a, hipStream_t s) {
   const int G = glx_group_for((a.dim + VEC - 1) / VEC);
   const unsigned blocks = (unsigned)((a.num_rows_self + (256 / G) - 1) / (256 / G));
-  glx_for_group(G, [&](auto g) { glx_pair_dot_bwd_kernel<decltype(g)::value, VEC><<<blocks, 256, 0, s>>>(a); });
+  glx_for_group(G, [&](auto g) {
+    glx_for_train_dtype(a.dtype, [&](auto t) {
+      glx_pair_dot_bwd_kernel<decltype(g)::value, VEC, decltype(t)::value><<<blocks, 256, 0, s>>>(a);
+    });
+  });
 }
 
 void launch_pair_bwd(const PairBwdArgs& a, hipStream_t s) {
-  const bool vec4 = a.dim % 4 == 0 && a.C % 4 == 0 && glx_aligned16(a.x_other) && glx_aligned16(a.grad_self);
+  const bool vec4 = a.dim % 4 == 0 && a.C % 4 == 0 && glx_aligned_vec4(a.x_other, a.dtype) &&
+                    glx_aligned_vec4(a.grad_self, a.dtype);
   if (vec4) launch_pair_bwd_vec<4>(a, s);
   else launch_pair_bwd_vec<1>(a, s);
 }
@@ -177,9 +201,11 @@ void launch_pair_bwd(const PairBwdArgs& a, hipStream_t s) {
   GLX_REQUIRE((int64_t)num_pairs * heads <= INT32_MAX, "num_pairs * heads exceeds int32");                              \
   GLX_REQUIRE(ptr_kind == GLX_PTR_HOST || ptr_kind == GLX_PTR_DEVICE, "bad ptr_kind")
 
-extern "C" int glx_pair_dot(int device, const float* xa, int64_t num_rows_a, const float* xb, int64_t num_rows_b,
-                            int32_t dim, int32_t heads, const int64_t* ia, const int64_t* ib, int32_t num_pairs,
-                            int32_t repeat, float default_attr, float* out, int ptr_kind, void* stream) {
+extern "C" int glx_pair_dot_ex(int device, const void* xa, int64_t num_rows_a, const void* xb, int64_t num_rows_b,
+                               int x_dtype, int32_t dim, int32_t heads, const int64_t* ia, const int64_t* ib,
+                               int32_t num_pairs, int32_t repeat, float default_attr, float* out, int ptr_kind,
+                               void* stream) {
+  GLX_REQUIRE_TRAIN_DTYPE(x_dtype, "glx_pair_dot_ex: x_dtype");
   GLX_PAIR_REQUIRE();
   GLX_REQUIRE(num_rows_a >= 0 && num_rows_b >= 0, "negative sizes: num_rows");
   GLX_REQUIRE(num_rows_a < INT32_MAX && num_rows_b < INT32_MAX, "num_rows must be < 2^31");
@@ -195,8 +221,9 @@ extern "C" int glx_pair_dot(int device, const float* xa, int64_t num_rows_a, con
   GLX_REQUIRE(guard.ok, "cannot select device %d", device);
   GlxHostStage st(device, ptr_kind, stream, GlxHostStage::ADMIT);
   PairFwdArgs a;
-  st.in(&a.xa, xa, (size_t)num_rows_a * dim);
-  st.in(&a.xb, xb, (size_t)num_rows_b * dim);
+  a.dtype = x_dtype;
+  st.in_bytes(&a.xa, xa, (size_t)num_rows_a * dim * (size_t)glx_dtype_size(x_dtype));
+  st.in_bytes(&a.xb, xb, (size_t)num_rows_b * dim * (size_t)glx_dtype_size(x_dtype));
   st.in(&a.ia, ia, (size_t)(num_pairs / repeat));
   st.in(&a.ib, ib, (size_t)num_pairs);
   st.out(&a.out, out, (size_t)num_pairs * heads);
@@ -215,10 +242,19 @@ extern "C" int glx_pair_dot(int device, const float* xa, int64_t num_rows_a, con
   return st.finish(rc);
 }
 
-extern "C" int glx_pair_dot_backward(int device, int side, const int64_t* ia, const int64_t* ib, int32_t num_pairs,
-                                     int32_t repeat, const float* g, int32_t heads, const float* x_other,
-                                     int64_t num_rows_other, int32_t dim, int64_t num_rows_self, float default_attr,
-                                     float* grad_self, int ptr_kind, void* stream) {
+extern "C" int glx_pair_dot(int device, const float* xa, int64_t num_rows_a, const float* xb, int64_t num_rows_b,
+                            int32_t dim, int32_t heads, const int64_t* ia, const int64_t* ib, int32_t num_pairs,
+                            int32_t repeat, float default_attr, float* out, int ptr_kind, void* stream) {
+  return glx_pair_dot_ex(device, xa, num_rows_a, xb, num_rows_b, GLX_DTYPE_F32, dim, heads, ia, ib, num_pairs, repeat,
+                         default_attr, out, ptr_kind, stream);
+}
+
+extern "C" int glx_pair_dot_backward_ex(int device, int side, const int64_t* ia, const int64_t* ib, int32_t num_pairs,
+                                        int32_t repeat, const float* g, int32_t heads, const void* x_other,
+                                        int64_t num_rows_other, int32_t dim, int64_t num_rows_self,
+                                        float default_attr, void* grad_self, int x_dtype, int ptr_kind,
+                                        void* stream) {
+  GLX_REQUIRE_TRAIN_DTYPE(x_dtype, "glx_pair_dot_backward_ex: x_dtype");
   GLX_PAIR_REQUIRE();
   GLX_REQUIRE(side == 0 || side == 1, "side must be 0 (xa) or 1 (xb), got %d", side);
   GLX_REQUIRE(num_rows_other >= 0 && num_rows_self >= 0, "negative sizes: num_rows");
@@ -237,16 +273,18 @@ extern "C" int glx_pair_dot_backward(int device, int side, const int64_t* ia, co
   const int64_t* d_ia;
   const int64_t* d_ib;
   PairBwdArgs a;
+  a.dtype = x_dtype;
+  const size_t elem = (size_t)glx_dtype_size(x_dtype);
   st.in(&d_ia, ia, (size_t)(num_pairs / repeat));
   st.in(&d_ib, ib, (size_t)num_pairs);
   st.in(&a.g, g, (size_t)num_pairs * heads);
-  st.in(&a.x_other, x_other, (size_t)num_rows_other * dim);
-  st.out(&a.grad_self, grad_self, (size_t)num_rows_self * dim);
+  st.in_bytes(&a.x_other, x_other, (size_t)num_rows_other * dim * elem);
+  st.out_bytes(&a.grad_self, grad_self, (size_t)num_rows_self * dim * elem);
   rc = st.begin();
   GlxScratch lease;
   if (rc == GLX_OK) {
     if (num_pairs == 0) {  // no pair: every row is zeros
-      rc = glx_zero_f32_async(a.grad_self, (size_t)num_rows_self * dim, st.s);
+      rc = glx_zero_elems_async(a.grad_self, (size_t)num_rows_self * dim, x_dtype, st.s);
     } else {
       // one position per segment; side 0 sorts the num_pairs / repeat entries of ia only
       const int32_t own_n = side == 0 ? num_pairs / repeat : num_pairs;
@@ -266,4 +304,12 @@ extern "C" int glx_pair_dot_backward(int device, int side, const int64_t* ia, co
     }
   }
   return st.finish(rc);
+}
+
+extern "C" int glx_pair_dot_backward(int device, int side, const int64_t* ia, const int64_t* ib, int32_t num_pairs,
+                                     int32_t repeat, const float* g, int32_t heads, const float* x_other,
+                                     int64_t num_rows_other, int32_t dim, int64_t num_rows_self, float default_attr,
+                                     float* grad_self, int ptr_kind, void* stream) {
+  return glx_pair_dot_backward_ex(device, side, ia, ib, num_pairs, repeat, g, heads, x_other, num_rows_other, dim,
+                                  num_rows_self, default_attr, grad_self, GLX_DTYPE_F32, ptr_kind, stream);
 }

@@ -56,6 +56,8 @@ EXPORTS = [
     "glx_gat_attention", "glx_gat_attention_backward",
     "glx_dot_attention", "glx_dot_attention_backward",
     "glx_pair_dot", "glx_pair_dot_backward",
+    "glx_aggregate_backward_ex", "glx_aggregate_weighted_ex", "glx_aggregate_weighted_backward_x_ex",
+    "glx_aggregate_weighted_backward_w_ex", "glx_pair_dot_ex", "glx_pair_dot_backward_ex",
     "glx_rows_coalesce", "glx_embedding_update",
     "glx_tgn_store_update", "glx_tgn_message", "glx_tgn_message_backward", "glx_tgn_memory_write",
     "glx_partition", "glx_stitch_i64", "glx_stitch_f32", "glx_aggregate_stitch",
@@ -199,7 +201,17 @@ def lib():
                                                  u64, vp, vp, vp, vp, vp, vp, vp, ci, vp]
         L.glx_pair_dot.argtypes = [ci, vp, i64, vp, i64, i32, i32, vp, vp, i32, i32, f32, vp, ci, vp]
         L.glx_pair_dot_backward.argtypes = [ci, ci, vp, vp, i32, i32, vp, i32, vp, i64, i32, i64, f32, vp, ci, vp]
-        L.glx_rows_coalesce.argtypes = [ci, vp, i32, i64, i32, vp, vp, vp, vp, ci, vp]
+        # the _ex siblings: the table pointer is followed (or, for pair_dot, the pair of tables is followed) by a dtype id
+        L.glx_aggregate_backward_ex.argtypes = [ci, ci, vp, vp, vp, i32, i32, i64, i32, vp, vp, ci, ci, vp]
+        L.glx_aggregate_weighted_ex.argtypes = [ci, ci, vp, ci, i64, i32, vp, vp, i32, vp, i32, i32, f32, vp, ci, vp]
+        L.glx_aggregate_weighted_backward_x_ex.argtypes = [ci, ci, vp, vp, i32, vp, i32, i32, i64, i32, vp, vp, ci, ci,
+                                                           vp]
+        L.glx_aggregate_weighted_backward_w_ex.argtypes = [ci, ci, vp, ci, i64, i32, vp, i32, vp, i32, i32, f32, vp, vp,
+                                                           ci, vp]
+        L.glx_pair_dot_ex.argtypes = [ci, vp, i64, vp, i64, ci, i32, i32, vp, vp, i32, i32, f32, vp, ci, vp]
+        L.glx_pair_dot_backward_ex.argtypes = [ci, ci, vp, vp, i32, i32, vp, i32, vp, i64, i32, i64, f32, vp, ci, ci,
+                                               vp]
+        L.glx_rows_coalesce.argtypes =[ci, vp, i32, i64, i32, vp, vp, vp, vp, ci, vp]
         L.glx_embedding_update.argtypes = [ci, ci, vp, vp, vp, i64, i32, vp, vp, i32, f32, f32, f32, f32, f32, f32, vp]
         L.glx_tgn_store_update.argtypes = [ci, i64, i32, vp, vp, vp, vp, i32, i64, vp, vp, vp, vp, vp]
         L.glx_tgn_message.argtypes = [ci, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp,
@@ -999,37 +1011,74 @@ def knn_merge(ids, dist, metric="ip", out=None, device=0):
     return oi, od
 
 
-def aggregate_backward(op, rows, cnt, grad_out, num_rows, arg=None, out=None, device=0):
-    """Gradient of Features.aggregate with respect to the rows of a [num_rows, D] float32 table with dense ids
-    (glx_aggregate_backward) -> grad_x[num_rows, D] float32, every row written (rows nobody references: zeros).
+# The [rows, D] matrices of the training path hold float32 or bfloat16 (the _ex entry points of include/glx.h).
+TRAIN_DTYPES = {"float32": FEATURE_DTYPES["float32"], "bfloat16": FEATURE_DTYPES["bfloat16"]}
+
+
+def _train_buf(x, what):
+    """(buffer for _ptr, dtype name) of a float32 / bfloat16 matrix of the training path: a torch CUDA tensor as it is,
+    a host torch tensor as a numpy view of its memory, a numpy float32 array, or a numpy uint16 / int16 array of
+    bfloat16 codes (numpy has no bfloat16).  Anything else raises ValueError before the call."""
+    if _is_torch(x):
+        name = str(x.dtype).replace("torch.", "")
+        if name not in TRAIN_DTYPES:
+            raise ValueError("{} must be float32 or bfloat16, not {}: bfloat16 is the half type that has a gradient "
+                             "contract (float16 gradients need loss scaling)".format(what, x.dtype))
+        if not x.is_cuda:
+            import torch
+            assert x.is_contiguous(), "host tensors must be contiguous"
+            x = x.numpy() if name == "float32" else x.view(torch.int16).numpy()
+        return x, name
+    if isinstance(x, np.ndarray) and x.dtype == np.float32:
+        return x, "float32"
+    if isinstance(x, np.ndarray) and x.dtype in (np.uint16, np.int16):
+        return x, "bfloat16"
+    raise ValueError("{} must be float32 or bfloat16 (numpy: uint16 / int16 codes), not {}".format(
+        what, getattr(x, "dtype", type(x))))
+
+
+def _train_out(out, out_dtype, like, shape, what):
+    """the row gradient of a call: (what to return, buffer for _ptr, dtype name) -- `out` in its own dtype, or a new
+    buffer of `like`'s kind holding out_dtype elements (torch: a bfloat16 tensor; numpy: the uint16 codes)"""
+    if out is not None:
+        buf, name = _train_buf(out, what)
+        return out, buf, name
+    if out_dtype not in TRAIN_DTYPES:
+        raise ValueError("{} holds float32 or bfloat16, not {!r}".format(what, out_dtype))
+    if _is_torch(like):
+        import torch
+        res = torch.empty(shape, dtype=getattr(torch, out_dtype), device=like.device)
+    else:
+        res = np.empty(shape, np.float32 if out_dtype == "float32" else np.uint16)
+    return res, res, out_dtype
+
+
+def aggregate_backward(op, rows, cnt, grad_out, num_rows, arg=None, out=None, device=0, out_dtype="float32"):
+    """Gradient of Features.aggregate with respect to the rows of a [num_rows, D] table with dense ids
+    (glx_aggregate_backward_ex) -> grad_x[num_rows, D], every row written (rows nobody references: zeros).
     rows[n] int64: the request's ids; cnt[num_segments] int32: the counts the forward returned (None: the implied
     layout of n // num_segments positions per segment); grad_out[num_segments, D] float32; arg: Max / Min only, what
-    Features.aggregate_arg recorded.  Each element adds its terms in ascending request position and no float atomic is
-    used: the same inputs give the same bits on every run.  Prod raises (its gradient divides by the element).
+    Features.aggregate_arg recorded.  Each element adds its terms in float32 in ascending request position and no float
+    atomic is used: the same inputs give the same bits on every run.  Prod raises (its gradient divides by the element).
+    out_dtype "float32" or "bfloat16" (out=: the buffer's own dtype): a bfloat16 grad_x is the float32 gradient rounded
+    once per element, to nearest even (a torch bfloat16 tensor on the device, numpy uint16 codes on the host).
     Torch CUDA tensors are device pointers on the current stream, numpy arrays host pointers."""
     if isinstance(op, str):
         op = AGGREGATOR_IDS[op]
     n = int(rows.shape[0])
     num_segments, dim = int(grad_out.shape[0]), int(grad_out.shape[1])
-    if out is not None:
-        grad_x = out
-    elif _is_torch(grad_out):
-        import torch
-        grad_x = torch.empty((num_rows, dim), dtype=torch.float32, device=grad_out.device)
-        device = grad_out.device.index or 0
-    else:
-        grad_x = np.empty((num_rows, dim), np.float32)
-    pr, pc, pa, pg, px = _ptr(rows), _ptr(cnt), _ptr(arg), _ptr(grad_out), _ptr(grad_x)
+    grad_x, buf, name = _train_out(out, out_dtype, grad_out, (num_rows, dim), "aggregate_backward: grad_x")
+    pr, pc, pa, pg, px = _ptr(rows), _ptr(cnt), _ptr(arg), _ptr(grad_out), _ptr(buf)
     kind = _kind(pr, pc, pa, pg, px)
     if kind == PTR_DEVICE:
         device = grad_x.device.index or 0
-    _check(lib().glx_aggregate_backward(device, op, pr[0], pc[0], pa[0], n, num_segments, num_rows, dim, pg[0], px[0],
-                                        kind, _stream(kind, device)))
+    _check(lib().glx_aggregate_backward_ex(device, op, pr[0], pc[0], pa[0], n, num_segments, num_rows, dim, pg[0], px[0],
+                                           TRAIN_DTYPES[name], kind, _stream(kind, device)))
     return grad_x
 
 
 def _weighted_out(out, like, shape):
-    """the output of a weighted-aggregation call and its device: `out`, or a new buffer of `like`'s kind"""
+    """the float32 output of a weighted-aggregation call: `out`, or a new buffer of `like`'s kind"""
     if out is not None:
         return out
     if _is_torch(like):
@@ -1050,38 +1099,43 @@ def aggregate_weighted(op, x, rows, w, num_segments, cnt=None, default_attr=0.0,
     w[n, heads] float32, column c belongs to head c // (D // heads); cnt[num_segments] int32 (None: the implied layout
     of n // num_segments positions per segment).  Every element folds fadd(acc, fmul(w, x)) left to right: bit-exact,
     and with all-ones weights equal to Features(x, view=True).aggregate.  Max / Min / Prod raise.
+    x may hold bfloat16 (a torch bfloat16 tensor, or numpy uint16 / int16 codes): emb stays float32 and equals the call
+    on the float32 matrix of x's values bit for bit.  Any other dtype raises ValueError.
     Torch CUDA tensors are device pointers on the current stream, numpy arrays host pointers."""
     if isinstance(op, str):
         op = AGGREGATOR_IDS[op]
     n = int(rows.shape[0])
     num_rows, dim = int(x.shape[0]), int(x.shape[1])
     heads = _weighted_heads(w, n)
-    emb = _weighted_out(out, x, (num_segments, dim))
-    px, pr, pw, pc, pe = _ptr(x), _ptr(rows), _ptr(w), _ptr(cnt), _ptr(emb)
+    xb, x_dtype = _train_buf(x, "aggregate_weighted: x")
+    emb = _weighted_out(out, xb, (num_segments, dim))
+    px, pr, pw, pc, pe = _ptr(xb), _ptr(rows), _ptr(w), _ptr(cnt), _ptr(emb)
     kind = _kind(px, pr, pw, pc, pe)
     if kind == PTR_DEVICE:
         device = emb.device.index or 0
-    _check(lib().glx_aggregate_weighted(device, op, px[0], num_rows, dim, pr[0], pw[0], heads, pc[0], n, num_segments,
-                                        default_attr, pe[0], kind, _stream(kind, device)))
+    _check(lib().glx_aggregate_weighted_ex(device, op, px[0], TRAIN_DTYPES[x_dtype], num_rows, dim, pr[0], pw[0], heads,
+                                           pc[0], n, num_segments, default_attr, pe[0], kind, _stream(kind, device)))
     return emb
 
 
-def aggregate_weighted_backward_x(op, rows, w, cnt, grad_out, num_rows, out=None, device=0):
-    """Gradient of aggregate_weighted with respect to the rows (glx_aggregate_weighted_backward_x) ->
-    grad_x[num_rows, D] float32, every row written.  aggregate_backward's contract with one more factor: each element
-    adds fmul(w[p, head], term) in ascending request position, no float atomic: the same bits on every run."""
+def aggregate_weighted_backward_x(op, rows, w, cnt, grad_out, num_rows, out=None, device=0, out_dtype="float32"):
+    """Gradient of aggregate_weighted with respect to the rows (glx_aggregate_weighted_backward_x_ex) ->
+    grad_x[num_rows, D], every row written.  aggregate_backward's contract with one more factor: each element adds
+    fmul(w[p, head], term) in float32 in ascending request position, no float atomic: the same bits on every run.
+    out_dtype / out= as in aggregate_backward: a bfloat16 grad_x is the float32 gradient rounded once per element."""
     if isinstance(op, str):
         op = AGGREGATOR_IDS[op]
     n = int(rows.shape[0])
     num_segments, dim = int(grad_out.shape[0]), int(grad_out.shape[1])
     heads = _weighted_heads(w, n)
-    grad_x = _weighted_out(out, grad_out, (num_rows, dim))
-    pr, pw, pc, pg, px = _ptr(rows), _ptr(w), _ptr(cnt), _ptr(grad_out), _ptr(grad_x)
+    grad_x, buf, name = _train_out(out, out_dtype, grad_out, (num_rows, dim), "aggregate_weighted_backward_x: grad_x")
+    pr, pw, pc, pg, px = _ptr(rows), _ptr(w), _ptr(cnt), _ptr(grad_out), _ptr(buf)
     kind = _kind(pr, pw, pc, pg, px)
     if kind == PTR_DEVICE:
         device = grad_x.device.index or 0
-    _check(lib().glx_aggregate_weighted_backward_x(device, op, pr[0], pw[0], heads, pc[0], n, num_segments, num_rows, dim,
-                                                   pg[0], px[0], kind, _stream(kind, device)))
+    _check(lib().glx_aggregate_weighted_backward_x_ex(device, op, pr[0], pw[0], heads, pc[0], n, num_segments, num_rows,
+                                                      dim, pg[0], px[0], TRAIN_DTYPES[name], kind,
+                                                      _stream(kind, device)))
     return grad_x
 
 
@@ -1089,20 +1143,24 @@ def aggregate_weighted_backward_w(op, x, rows, heads, cnt, grad_out, default_att
     """Gradient of aggregate_weighted with respect to the weights (glx_aggregate_weighted_backward_w) ->
     grad_w[n, heads] float32, every element written (a position that was not consumed: +0.0).  grad_w[p, h] is the dot
     product of grad_out[s(p)] and the gathered row over the columns of head h (Mean: / count); a fixed lane mapping
-    and reduction tree, no atomics: the same bits on every run, within C * 2^-23 * sum|terms| of the exact value."""
+    and reduction tree, no atomics: the same bits on every run, within C * 2^-23 * sum|terms| of the exact value.
+    x may hold bfloat16, as in aggregate_weighted: grad_w stays float32 and equals the call on the float32 matrix of
+    x's values bit for bit (the same mapping and tree)."""
     if isinstance(op, str):
         op = AGGREGATOR_IDS[op]
     n = int(rows.shape[0])
     num_rows, dim = int(x.shape[0]), int(x.shape[1])
     num_segments = int(grad_out.shape[0])
     assert int(grad_out.shape[1]) == dim
+    xb, x_dtype = _train_buf(x, "aggregate_weighted_backward_w: x")
     grad_w = _weighted_out(out, grad_out, (n, heads))
-    px, pr, pc, pg, pw = _ptr(x), _ptr(rows), _ptr(cnt), _ptr(grad_out), _ptr(grad_w)
+    px, pr, pc, pg, pw = _ptr(xb), _ptr(rows), _ptr(cnt), _ptr(grad_out), _ptr(grad_w)
     kind = _kind(px, pr, pc, pg, pw)
     if kind == PTR_DEVICE:
         device = grad_w.device.index or 0
-    _check(lib().glx_aggregate_weighted_backward_w(device, op, px[0], num_rows, dim, pr[0], heads, pc[0], n, num_segments,
-                                                   default_attr, pg[0], pw[0], kind, _stream(kind, device)))
+    _check(lib().glx_aggregate_weighted_backward_w_ex(device, op, px[0], TRAIN_DTYPES[x_dtype], num_rows, dim, pr[0],
+                                                      heads, pc[0], n, num_segments, default_attr, pg[0], pw[0], kind,
+                                                      _stream(kind, device)))
     return grad_w
 
 
@@ -1288,18 +1346,25 @@ def pair_dot(xa, ia, xb, ib, heads=1, repeat=1, default_attr=0.0, out=None, devi
     ia[p // repeat] of xa with row ib[p] of xb (repeat = K: a [B, K] negative-sampler response against its B sources);
     an index outside its table reads a row of default_attr; column c belongs to head c // (D // heads).  A fixed lane
     mapping and reduction tree, no atomics: the same bits on every call, within (D // heads) * 2^-23 * sum|terms| of
-    the exact value.  Torch CUDA tensors are device pointers on the current stream, numpy arrays host pointers."""
+    the exact value.  xa and xb may both hold bfloat16 (torch bfloat16 tensors, or numpy uint16 / int16 codes): out stays
+    float32 and equals the call on the float32 tables of their values bit for bit; tables of two different dtypes, or of
+    any other dtype, raise ValueError.
+    Torch CUDA tensors are device pointers on the current stream, numpy arrays host pointers."""
     n, repeat = _pair_counts(ia, ib, repeat)
     num_rows_a, dim = int(xa.shape[0]), int(xa.shape[1])
     num_rows_b = int(xb.shape[0])
     assert int(xb.shape[1]) == dim, "xa and xb must have the same number of columns"
-    res = _weighted_out(out, xa, (n, heads))
-    pa, pia, pb, pib, po = _ptr(xa), _ptr(ia), _ptr(xb), _ptr(ib), _ptr(res)
+    xa_buf, a_dtype = _train_buf(xa, "pair_dot: xa")
+    xb_buf, b_dtype = _train_buf(xb, "pair_dot: xb")
+    if a_dtype != b_dtype:
+        raise ValueError("pair_dot: xa holds {} and xb {}: both tables must have one dtype".format(a_dtype, b_dtype))
+    res = _weighted_out(out, xa_buf, (n, heads))
+    pa, pia, pb, pib, po = _ptr(xa_buf), _ptr(ia), _ptr(xb_buf), _ptr(ib), _ptr(res)
     kind = _kind(pa, pia, pb, pib, po)
     if kind == PTR_DEVICE:
         device = res.device.index or 0
-    _check(lib().glx_pair_dot(device, pa[0], num_rows_a, pb[0], num_rows_b, dim, heads, pia[0], pib[0], n, repeat,
-                              default_attr, po[0], kind, _stream(kind, device)))
+    _check(lib().glx_pair_dot_ex(device, pa[0], num_rows_a, pb[0], num_rows_b, TRAIN_DTYPES[a_dtype], dim, heads, pia[0],
+                                 pib[0], n, repeat, default_attr, po[0], kind, _stream(kind, device)))
     return res
 
 
@@ -1308,17 +1373,24 @@ def pair_dot_backward(side, ia, ib, g, x_other, num_rows_self, repeat=1, default
     grad_self[num_rows_self, D] float32, every row written.  g[n, heads] (or g[n]) is the gradient of pair_dot's output,
     x_other the other side's table.  Each element adds fmul(g[p, head], other_row(p)) over the pairs that refer to its
     row in ascending p, no float atomic: the same bits on every run.  An own index outside the table gets nothing, an
-    other-side index outside its table multiplies a row of default_attr."""
+    other-side index outside its table multiplies a row of default_attr.
+    grad_self takes x_other's dtype: for a bfloat16 x_other it is the float32 gradient (summed in float32 over the exactly
+    upcast rows) rounded once per element, to nearest even; an out= of another dtype raises ValueError."""
     n, repeat = _pair_counts(ia, ib, repeat)
     heads = _weighted_heads(g, n)
     num_rows_other, dim = int(x_other.shape[0]), int(x_other.shape[1])
-    grad = _weighted_out(out, x_other, (num_rows_self, dim))
-    pia, pib, pg, px, po = _ptr(ia), _ptr(ib), _ptr(g), _ptr(x_other), _ptr(grad)
+    xo, x_dtype = _train_buf(x_other, "pair_dot_backward: x_other")
+    grad, buf, name = _train_out(out, x_dtype, xo, (num_rows_self, dim), "pair_dot_backward: grad_self")
+    if name != x_dtype:
+        raise ValueError("pair_dot_backward: grad_self holds {} and x_other {}: both must have one dtype".format(
+            name, x_dtype))
+    pia, pib, pg, px, po = _ptr(ia), _ptr(ib), _ptr(g), _ptr(xo), _ptr(buf)
     kind = _kind(pia, pib, pg, px, po)
     if kind == PTR_DEVICE:
         device = grad.device.index or 0
-    _check(lib().glx_pair_dot_backward(device, side, pia[0], pib[0], n, repeat, pg[0], heads, px[0], num_rows_other, dim,
-                                       num_rows_self, default_attr, po[0], kind, _stream(kind, device)))
+    _check(lib().glx_pair_dot_backward_ex(device, side, pia[0], pib[0], n, repeat, pg[0], heads, px[0], num_rows_other,
+                                          dim, num_rows_self, default_attr, po[0], TRAIN_DTYPES[x_dtype], kind,
+                                          _stream(kind, device)))
     return grad
 
 

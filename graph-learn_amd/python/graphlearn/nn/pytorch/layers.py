@@ -32,8 +32,12 @@ class GATConv(torch.nn.Module):
   add_self_loops    every seed also attends to itself (gat_conv.py:85-87): its own row is inserted as one more
                     position of its segment, behind its neighbours
 
-  Every op is float32 on one GPU; the segments are described by counts (or the implied layout), not by explicit
-  segment ids.
+  Everything runs on one GPU; the segments are described by counts (or the implied layout), not by explicit segment
+  ids.  In float32 every op is float32.  Under torch.autocast("cuda", dtype=torch.bfloat16) the projection z = W x is
+  bfloat16; the two halves of the logit come out float32 (type promotion against the float32 attention parameters), so
+  gat_attention runs in float32 as ever, and weighted_segment_aggregate reads the bfloat16 z as it is: the output and
+  every parameter gradient equal, bit for bit, those of the same steps with z.float() handed to the reduce, and z's
+  gradient is the float32 one rounded once per element (segment.py).
   """
 
   def __init__(self, in_dim, out_dim, num_heads=1, concat=False, dropout=0.0, use_bias=False, negative_slope=0.2,
@@ -126,7 +130,9 @@ class TransformerConv(torch.nn.Module):
   bias              of the query, key, value and skip maps
 
   Every op is float32 on one GPU; the segments are described by counts (or the implied layout), not by explicit
-  segment ids, and there is no mask for padded neighbours beyond counts.
+  segment ids, and there is no mask for padded neighbours beyond counts.  dot_attention takes float32 only, so under
+  bfloat16 autocast -- where the query, key and value maps come out bfloat16 -- the layer raises ValueError: run it
+  outside the autocast region, or cast its projections with .float().
   """
 
   def __init__(self, in_dim, out_dim, heads=1, concat=True, dropout=0.0, edge_dim=None, root_weight=True, bias=True,

@@ -53,6 +53,16 @@ K sampled negatives,
     neg = pair_dot(z, l_src, z, l_neg.view(B, K))                      # [B, K]
 
 without the two [n, D] gathers of `(z[src].unsqueeze(1) * z[neg]).sum(-1)` and without their index_add_ backwards.
+
+bfloat16.  Under torch.autocast("cuda", dtype=torch.bfloat16) `z = relu(enc(x))` is bfloat16, and segment_aggregate,
+gather_rows, weighted_segment_aggregate and pair_dot take it as it is -- inside autocast or outside, they go by the
+dtype they are handed.  Every row is upcast exactly as it is loaded and everything else is the float32 arithmetic in the
+float32 order: the outputs are float32 and torch.equal the call on `z.float()`.  `z.grad` is bfloat16, written by the
+backward kernel itself: the float32 gradient, summed in float32, rounded ONCE per element to nearest even (within 2^-9
+relative of it; a NaN is 0xFFFF) -- no float32 [N, D] gradient is allocated.  When one bfloat16 tensor feeds two ops
+torch adds their two bfloat16 gradients in bfloat16: one more rounding, torch's.  weights, logits and incoming gradients
+stay float32; float16 (its gradients need loss scaling), float64 and float8 raise, and so do bfloat16 inputs to
+segment_softmax, gat_attention and dot_attention.
 """
 import torch
 
@@ -71,8 +81,10 @@ def _glx():
 def _check_inputs(x, index, who):
   if not isinstance(x, torch.Tensor) or not isinstance(index, torch.Tensor):
     raise ValueError("{}: x and index must be torch tensors".format(who))
-  if x.dtype != torch.float32:
-    raise ValueError("{}: x must be float32, not {} (half and float8 tables have no backward)".format(who, x.dtype))
+  if x.dtype not in (torch.float32, torch.bfloat16):
+    raise ValueError("{}: x must be float32 or bfloat16, not {} (bfloat16 is the half type whose gradient has a "
+                     "contract: float16 gradients need loss scaling, float8 tables have no backward)".format(
+                         who, x.dtype))
   if not x.is_cuda or x.dim() != 2 or not x.is_contiguous():
     raise ValueError("{}: x must be a contiguous [N, D] CUDA tensor".format(who))
   if x.shape[1] < 1:
@@ -83,6 +95,10 @@ def _check_inputs(x, index, who):
     raise ValueError("{}: index lives on {}, x on {}".format(who, index.device, x.device))
   if index.requires_grad:
     raise ValueError("{}: index carries no gradient".format(who))
+
+
+def _dtype_name(x):
+  return str(x.dtype).replace("torch.", "")
 
 
 def _no_double_backward(who):
@@ -102,7 +118,7 @@ class _SegmentAggregate(torch.autograd.Function):
       emb, cnt, arg = feats.aggregate_arg(op, index, segment_ids, num_segments, default_attr)
     else:
       emb, cnt = feats.aggregate(op, index, segment_ids, num_segments, default_attr)
-    ctx.op, ctx.num_rows = op, int(x.shape[0])
+    ctx.op, ctx.num_rows, ctx.x_dtype = op, int(x.shape[0]), _dtype_name(x)
     # the implied layout needs no counts: its segments are arithmetic
     ctx.implied = segment_ids is None
     ctx.has_arg = arg is not None
@@ -116,7 +132,9 @@ class _SegmentAggregate(torch.autograd.Function):
     index, cnt = saved[0], saved[1]
     arg = saved[2] if ctx.has_arg else None
     grad = grad.to(torch.float32).contiguous()
-    gx = _glx().aggregate_backward(ctx.op, index, None if ctx.implied else cnt, grad, ctx.num_rows, arg=arg)
+    # x.grad in x's own dtype straight from the kernel: no float32 [N, D] gradient exists for a bfloat16 x
+    gx = _glx().aggregate_backward(ctx.op, index, None if ctx.implied else cnt, grad, ctx.num_rows, arg=arg,
+                                   out_dtype=ctx.x_dtype)
     return gx, None, None, None, None, None
 
 
@@ -125,7 +143,9 @@ def segment_aggregate(x, index, num_segments, op="mean", segment_ids=None, defau
   "min"; "prod" only for an x that needs no gradient), exactly as glx.Features(x, view=True).aggregate does -- the
   engine's tuned reduce, left to right, bit-identical on every run.
 
-  x            [N, D] contiguous float32 CUDA tensor; may require grad
+  x            [N, D] contiguous float32 or bfloat16 CUDA tensor; may require grad.  The result is float32 either way
+               (bfloat16: that of x.float(), bit for bit); x.grad has x's dtype (bfloat16: the float32 gradient rounded
+               once per element)
   index        int64 CUDA tensor of any shape (flattened): rows of x; a value outside [0, N) reads a row of
                `default_attr` and receives no gradient
   segment_ids  None: num_segments equal segments of index.numel() / num_segments consecutive positions (a dense
@@ -165,7 +185,7 @@ class _GatherRows(torch.autograd.Function):
   def forward(ctx, x, index, default_attr):
     glx = _glx()
     out = glx.Features(x.detach(), view=True, device=x.device.index or 0).lookup(index, default_attr)
-    ctx.num_rows = int(x.shape[0])
+    ctx.num_rows, ctx.x_dtype = int(x.shape[0]), _dtype_name(x)
     ctx.save_for_backward(index)
     return out
 
@@ -176,13 +196,14 @@ class _GatherRows(torch.autograd.Function):
     glx = _glx()
     grad = grad.to(torch.float32).contiguous()
     # one position per segment: the Sum backward of the implied layout
-    return glx.aggregate_backward(glx.SUM, index, None, grad, ctx.num_rows), None, None
+    return glx.aggregate_backward(glx.SUM, index, None, grad, ctx.num_rows, out_dtype=ctx.x_dtype), None, None
 
 
 def gather_rows(x, index, default_attr=0.0):
   """x[index] as [*index.shape, D] -- the engine's lookup going forward, the deterministic Sum backward (one position
   per segment) going back: the replacement for `z[local[h]]` whose backward is index_add_ with float atomics.  A value
-  of index outside [0, N) reads a row of `default_attr` and receives no gradient."""
+  of index outside [0, N) reads a row of `default_attr` and receives no gradient.  x is float32 or bfloat16; the rows
+  come back as float32 (a bfloat16 x: upcast exactly), x.grad has x's dtype."""
   _check_inputs(x, index, "gather_rows")
   shape = tuple(index.shape)
   out = _GatherRows.apply(x, index.reshape(-1).contiguous(), float(default_attr))
@@ -210,7 +231,7 @@ class _WeightedSegmentAggregate(torch.autograd.Function):
     grad = grad.to(torch.float32).contiguous()
     gx = gw = None
     if ctx.needs_input_grad[0]:
-      gx = glx.aggregate_weighted_backward_x(ctx.op, index, w, counts, grad, int(x.shape[0]))
+      gx = glx.aggregate_weighted_backward_x(ctx.op, index, w, counts, grad, int(x.shape[0]), out_dtype=_dtype_name(x))
     if ctx.needs_input_grad[2]:
       gw = glx.aggregate_weighted_backward_w(ctx.op, x, index, int(w.shape[1]), counts, grad, ctx.default_attr)
     return gx, None, gw, None, None, None, None
@@ -220,10 +241,12 @@ def weighted_segment_aggregate(x, index, weights, num_segments, op="sum", counts
   """[num_segments, D]: segment s is the weighted "sum" or "mean" of the rows x[index[p]] of its positions p, each row
   scaled per head by weights[p] before it is added -- fadd(acc, fmul(w, x)) left to right, bit-identical on every run.
 
-  x        [N, D] contiguous float32 CUDA tensor; may require grad
+  x        [N, D] contiguous float32 or bfloat16 CUDA tensor; may require grad.  The result and the weights' gradient
+           are float32 either way (bfloat16: those of x.float(), bit for bit); x.grad has x's dtype (bfloat16: the
+           float32 gradient rounded once per element)
   index    int64 CUDA tensor of any shape (flattened, n positions): rows of x; a value outside [0, N) reads a row of
            `default_attr` and passes no gradient to x (its weight still gets one)
-  weights  [n] or [n, H] float32 on x's device, H dividing D: column c of a row is scaled by head c // (D // H); may
+  weights  [n] or [n, H] float32 (never bfloat16) on x's device, H dividing D: column c of a row is scaled by head c // (D // H); may
            require grad.  The gradient has the shape of `weights`; each element is a dot product over its head's
            columns with a fixed summation tree (the same bits on every run, no atomics)
   counts   None: num_segments equal segments of n / num_segments consecutive positions (a dense sampler response); or
@@ -547,8 +570,11 @@ def pair_dot(xa, ia, xb, ib, heads=None, default_attr=0.0):
   tree going forward, fadd(acc, fmul(g, row)) in ascending pair order going back, no atomics: bit-identical on every
   run.  Neither [n, D] gather is materialised.
 
-  xa, xb   [Na, D], [Nb, D] contiguous float32 CUDA tensors on one device; either may require grad, and they may be one
-           tensor (autograd then adds the two sides' gradients: one more float32 add per element)
+  xa, xb   [Na, D], [Nb, D] contiguous CUDA tensors on one device, both float32 or both bfloat16; either may require
+           grad, and they may be one tensor (autograd then adds the two sides' gradients: one more add per element, in
+           the tables' dtype -- for bfloat16 one more rounding, torch's).  The scores are float32 either way (bfloat16:
+           those of the .float() tables, bit for bit); each gradient has its table's dtype (bfloat16: the float32
+           gradient rounded once per element)
   ib       int64 CUDA tensor of any shape (n pairs): rows of xb
   ia       int64 CUDA tensor (flattened) whose numel divides n: rows of xa; pair p takes ia[p // (n / ia.numel())] -- ia
            [B] with ib [B, K] scores each source against its K candidates; ia shaped like ib scores edges one to one
@@ -561,6 +587,8 @@ def pair_dot(xa, ia, xb, ib, heads=None, default_attr=0.0):
   _check_inputs(xb, ib, who)
   if xb.device != xa.device:
     raise ValueError("{}: xb lives on {}, xa on {}".format(who, xb.device, xa.device))
+  if xb.dtype != xa.dtype:
+    raise ValueError("{}: xa is {} and xb {}: both tables must have one dtype".format(who, xa.dtype, xb.dtype))
   D = int(xa.shape[1])
   if int(xb.shape[1]) != D:
     raise ValueError("{}: xa has {} columns, xb {}".format(who, D, int(xb.shape[1])))

@@ -47,7 +47,10 @@ extern "C" {
  * glx_knn_merge; TGN memory -- glx_tgn_store_update, glx_tgn_message, glx_tgn_message_backward, glx_tgn_memory_write;
  * IVF-Flat index -- glx_knn_ivf_build, glx_knn_ivf_search, glx_knn_ivf_info, glx_knn_ivf_export, glx_knn_ivf_destroy;
  * IVF-PQ index -- glx_knn_ivfpq_build, glx_knn_ivfpq_search, glx_knn_ivfpq_info, glx_knn_ivfpq_export,
- * glx_knn_ivfpq_destroy; float8 feature tables -- GLX_DTYPE_F8E4M3, GLX_DTYPE_F8E5M2, glx_features_convert_host. */
+ * glx_knn_ivfpq_destroy; float8 feature tables -- GLX_DTYPE_F8E4M3, GLX_DTYPE_F8E5M2, glx_features_convert_host;
+ * the bfloat16 training path -- glx_aggregate_backward_ex, glx_aggregate_weighted_ex,
+ * glx_aggregate_weighted_backward_x_ex, glx_aggregate_weighted_backward_w_ex, glx_pair_dot_ex,
+ * glx_pair_dot_backward_ex. */
 #define GLX_ABI_VERSION 5
 
 /* Exported symbols: libglx.so is built with -fvisibility=hidden. */
@@ -871,6 +874,66 @@ GLX_API int glx_pair_dot_backward(int device, int side, const int64_t* ia, const
                                   int32_t repeat, const float* g, int32_t heads, const float* x_other,
                                   int64_t num_rows_other, int32_t dim, int64_t num_rows_self, float default_attr,
                                   float* grad_self, int ptr_kind, void* stream);
+
+/* ---- the bfloat16 training path (added under 5): the six entry points above that take or return a [rows, dim] matrix
+ * of the model, with that matrix in float32 or bfloat16.  They stand where their float32 siblings stand: the
+ * differentiable segment reductions under the reference's layers (python/nn/tf/layers/sage_conv.py:69-73,
+ * gcn_conv.py:52-73, gat_conv.py:96-110, ego_gat_conv.py:98-103) and the pair scores of its unsupervised models
+ * (examples/tf/sage/train.py:56-57, python/nn/tf/loss.py:58), for a model that runs under bfloat16 autocast. ----------
+ * Each _ex entry point is its sibling's signature with the table pointer turned into const void* / void* plus a dtype
+ * argument: GLX_DTYPE_F32 or GLX_DTYPE_BF16.  GLX_DTYPE_F16 and the two float8 ids are GLX_INVALID_ARGUMENT -- bfloat16
+ * is the half type that has a gradient contract: float16 gradients need loss scaling, a contract of its own -- and so
+ * is any other id; the dtype is checked before anything else, so the answer needs no device.  With GLX_DTYPE_F32 an _ex
+ * entry point IS its sibling: the six siblings are calls of it, the same kernels, launch shapes and bits.
+ *
+ * Reads (x, xa / xb, x_other in bfloat16): every element is upcast to float32 as it is loaded -- exact -- and everything
+ * downstream is the float32 kernel's arithmetic in the float32 kernel's order.  Every output that is float32 in the
+ * sibling stays float32 (emb_out, out, grad_w) and is BIT-IDENTICAL to what the sibling returns for the float32 matrix
+ * of the upcast values: the ascending-position folds (glx_aggregate_weighted_ex) and the fixed trees
+ * (glx_pair_dot_ex, glx_aggregate_weighted_backward_w_ex) alike.  The trees depend on the lane-to-column mapping, so a
+ * bfloat16 call keeps the mapping the float32 call picks for the same (dim, heads): a lane still owns 4 columns, loaded
+ * as four bfloat16 in one 8-byte access, and the alignment the 4-column path asks of a bfloat16 matrix is 4 elements =
+ * 8 bytes (16 for float32).  A matrix with dim % 4 == 0 whose base is 16-byte aligned therefore takes the same path in
+ * both types.  default_attr stays a float32 fill and is not rounded.
+ *
+ * Row gradients (grad_x, grad_self in bfloat16): let G[r, c] be exactly the float32 value the sibling writes for the
+ * same arguments.  The stored element is that value rounded ONCE, to nearest even, by the integer-arithmetic converter
+ * the uploads use -- glx_features_convert_host(.., GLX_DTYPE_BF16, ..) is the same code on the host.  So a NaN is
+ * stored as 0xFFFF, a value of magnitude 0x7F7F8000 or more as +-inf, bfloat16 subnormals are kept, and so is the sign
+ * of zero.  Accumulation never happens in bfloat16; each element is within 2^-9 relative of the float32 gradient (8
+ * significand bits).  Every row is still written, rows nobody references are +0.0 (all bits clear), nothing is
+ * written outside the num_rows * dim ELEMENTS of the buffer, element offsets are 64-bit, no float atomics, the same
+ * bits on every call.  Host buffers hold the 16-bit codes.
+ *
+ * What stays float32 in every case: w, g, grad_out, the logits and coefficients of glx_segment_softmax /
+ * glx_gat_attention / glx_dot_attention ([n, heads] arrays, a few bytes a row), glx_rows_coalesce /
+ * glx_embedding_update, the TGN entry points and the distributed store. */
+GLX_API int glx_aggregate_backward_ex(int device, int op, const int64_t* rows, const int32_t* cnt, const int32_t* arg,
+                                      int32_t num_ids, int32_t num_segments, int64_t num_rows, int32_t dim,
+                                      const float* grad_out, void* grad_x, int grad_x_dtype, int ptr_kind,
+                                      void* stream);
+GLX_API int glx_aggregate_weighted_ex(int device, int op, const void* x, int x_dtype, int64_t num_rows, int32_t dim,
+                                      const int64_t* rows, const float* w, int32_t heads, const int32_t* cnt,
+                                      int32_t num_ids, int32_t num_segments, float default_attr, float* emb_out,
+                                      int ptr_kind, void* stream);
+GLX_API int glx_aggregate_weighted_backward_x_ex(int device, int op, const int64_t* rows, const float* w, int32_t heads,
+                                                 const int32_t* cnt, int32_t num_ids, int32_t num_segments,
+                                                 int64_t num_rows, int32_t dim, const float* grad_out, void* grad_x,
+                                                 int grad_x_dtype, int ptr_kind, void* stream);
+GLX_API int glx_aggregate_weighted_backward_w_ex(int device, int op, const void* x, int x_dtype, int64_t num_rows,
+                                                 int32_t dim, const int64_t* rows, int32_t heads, const int32_t* cnt,
+                                                 int32_t num_ids, int32_t num_segments, float default_attr,
+                                                 const float* grad_out, float* grad_w, int ptr_kind, void* stream);
+/* one x_dtype for both tables */
+GLX_API int glx_pair_dot_ex(int device, const void* xa, int64_t num_rows_a, const void* xb, int64_t num_rows_b,
+                            int x_dtype, int32_t dim, int32_t heads, const int64_t* ia, const int64_t* ib,
+                            int32_t num_pairs, int32_t repeat, float default_attr, float* out, int ptr_kind,
+                            void* stream);
+/* x_other and grad_self both hold x_dtype elements */
+GLX_API int glx_pair_dot_backward_ex(int device, int side, const int64_t* ia, const int64_t* ib, int32_t num_pairs,
+                                     int32_t repeat, const float* g, int32_t heads, const void* x_other,
+                                     int64_t num_rows_other, int32_t dim, int64_t num_rows_self, float default_attr,
+                                     void* grad_self, int x_dtype, int ptr_kind, void* stream);
 
 /* ---- trainable embedding tables: the coalesced row gradient of a lookup and the sparse optimizer steps that apply it
  * in place, on the touched rows only.  The reference trains tables in two places: one EmbeddingColumn per categorical

@@ -1,0 +1,204 @@
+"""The torch surface of the bfloat16 training path: segment_aggregate, gather_rows, weighted_segment_aggregate and
+pair_dot on a bfloat16 leaf, GATConv under bfloat16 autocast, and what still raises.  Every comparison is to the bit:
+outputs against the call on x.float(), x.grad against the float32 path's gradient rounded once with torch's own
+.to(torch.bfloat16) (round to nearest even; the data is finite)."""
+import os
+import subprocess
+import sys
+
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "graph-learn_amd", "python"))
+
+from graphlearn.nn.pytorch import (GATConv, dot_attention, gat_attention, gather_rows, pair_dot,  # noqa: E402
+                                   segment_aggregate, weighted_segment_aggregate)
+
+pytestmark = pytest.mark.gpu
+N, D = 37, 36  # 9 lanes of 4 columns: a group of 16 with lanes past the last column
+
+
+def _bits16(t):
+    return t.contiguous().view(torch.int16)
+
+
+def _leafs(seed=0, n=N, d=D):
+    """a bfloat16 leaf and the float32 leaf of exactly its values"""
+    g = torch.Generator().manual_seed(seed)
+    xb = torch.randn(n, d, generator=g).to(torch.bfloat16).cuda()
+    return xb.clone().requires_grad_(True), xb.float().requires_grad_(True)
+
+
+def _both(fn, seed=0, n=N, d=D):
+    """fn(x) -> output, on the bfloat16 leaf and on its float32 twin, each sent backward with one random float32
+    gradient: (out16, out32, x16.grad, x32.grad)"""
+    x16, x32 = _leafs(seed, n, d)
+    o16, o32 = fn(x16), fn(x32)
+    go = torch.randn(o32.shape, generator=torch.Generator().manual_seed(seed + 1)).cuda()
+    o16.backward(go)
+    o32.backward(go)
+    return o16, o32, x16.grad, x32.grad
+
+
+def _check(fn, **kw):
+    o16, o32, g16, g32 = _both(fn, **kw)
+    assert o16.dtype == torch.float32 and torch.equal(o16, o32)
+    assert g16.dtype == torch.bfloat16 and g32.dtype == torch.float32
+    assert torch.isfinite(g32).all() and g32.abs().sum() > 0
+    assert torch.equal(_bits16(g16), _bits16(g32.to(torch.bfloat16)))
+
+
+def _index(n, seed=3):
+    idx = torch.randint(-1, N + 1, (n,), generator=torch.Generator().manual_seed(seed))
+    idx[:2] = torch.tensor([-1, N])
+    return idx.cuda()
+
+
+RAGGED_IDS = torch.tensor([1, 1, 1, 2, 4, 4, 4, 4, 4, 6, 6, 6], dtype=torch.int32)  # segments 0, 3, 5 and 7 are empty
+
+
+@pytest.mark.parametrize("ragged", [False, True], ids=["implied", "segment_ids"])
+@pytest.mark.parametrize("op", ["mean", "max"])
+def test_segment_aggregate_on_a_bf16_leaf(op, ragged):
+    idx = _index(12)
+    seg = RAGGED_IDS.cuda() if ragged else None
+    S = 8 if ragged else 4
+    _check(lambda x: segment_aggregate(x, idx, S, op=op, segment_ids=seg, default_attr=0.25))
+
+
+def test_gather_rows_on_a_bf16_leaf():
+    idx = _index(30).reshape(5, 6)
+    _check(lambda x: gather_rows(x, idx, default_attr=0.25))
+    x16, _ = _leafs()
+    out = gather_rows(x16, idx)
+    assert tuple(out.shape) == (5, 6, D)
+    ok = (idx >= 0) & (idx < N)
+    assert torch.equal(out[ok], x16.detach().float()[idx[ok]])  # the exact upcast of the rows
+
+
+@pytest.mark.parametrize("counts", [None, [0, 5, 1, 0, 6]], ids=["implied", "ragged"])
+@pytest.mark.parametrize("heads", [1, 3])
+def test_weighted_segment_aggregate_on_a_bf16_leaf(heads, counts):
+    idx = _index(12)
+    S = 4 if counts is None else len(counts)
+    cnt = None if counts is None else torch.tensor(counts, dtype=torch.int32).cuda()
+    w16 = torch.randn(12, heads, generator=torch.Generator().manual_seed(9)).cuda().requires_grad_(True)
+    w32 = w16.detach().clone().requires_grad_(True)
+    ws = iter([w16, w32])  # _both calls fn on the bfloat16 leaf first
+    _check(lambda x: weighted_segment_aggregate(x, idx, next(ws), S, op="mean", counts=cnt, default_attr=0.25))
+    assert w16.grad.dtype == torch.float32 and torch.equal(w16.grad, w32.grad)  # the same tree on the same values
+
+
+@pytest.mark.parametrize("heads", [None, 3])
+def test_pair_dot_on_bf16_leaves(heads):
+    ia, ib = _index(5, seed=4), _index(15, seed=5).reshape(5, 3)
+    a16, a32 = _leafs(1)
+    b16, b32 = _leafs(2, n=N + 2)
+    o16, o32 = pair_dot(a16, ia, b16, ib, heads=heads, default_attr=0.25), pair_dot(a32, ia, b32, ib, heads=heads,
+                                                                                    default_attr=0.25)
+    assert o16.dtype == torch.float32 and torch.equal(o16, o32)
+    go = torch.randn(o32.shape, generator=torch.Generator().manual_seed(6)).cuda()
+    o16.backward(go)
+    o32.backward(go)
+    for g16, g32 in ((a16.grad, a32.grad), (b16.grad, b32.grad)):
+        assert g16.dtype == torch.bfloat16 and g32.abs().sum() > 0
+        assert torch.equal(_bits16(g16), _bits16(g32.to(torch.bfloat16)))
+    with pytest.raises(ValueError):
+        pair_dot(a16, ia, b32, ib)
+
+
+def test_one_bf16_tensor_feeding_two_ops_adds_the_two_gradients_in_bf16():
+    idx_a, idx_g = _index(12), _index(7, seed=8)
+    ga = torch.randn(4, D, generator=torch.Generator().manual_seed(1)).cuda()
+    gg = torch.randn(7, D, generator=torch.Generator().manual_seed(2)).cuda()
+
+    def grad_of(use_a, use_g):
+        z, _ = _leafs()
+        loss = 0
+        if use_a:
+            loss = loss + (segment_aggregate(z, idx_a, 4, op="mean") * ga).sum()
+        if use_g:
+            loss = loss + (gather_rows(z, idx_g) * gg).sum()
+        loss.backward()
+        return z.grad
+
+    both, only_a, only_g = grad_of(True, True), grad_of(True, False), grad_of(False, True)
+    assert both.dtype == only_a.dtype == only_g.dtype == torch.bfloat16
+    # a bfloat16 add is commutative: either order of torch's accumulation gives these bits
+    assert torch.equal(_bits16(both), _bits16(only_a + only_g)) and torch.equal(_bits16(both), _bits16(only_g + only_a))
+
+
+def _gat_by_hand(layer, x_nodes, seed_local, index, counts, call):
+    """GATConv.forward step by step under the same autocast, with z.float() handed to the reduce"""
+    H, C = layer.num_heads, layer.out_dim
+    S = seed_local.numel()
+    z = layer.linear(x_nodes)
+    assert z.dtype == torch.bfloat16
+    zh = z.view(-1, H, C)
+    src_e = (zh * layer.attn_src).sum(-1).contiguous()
+    dst_e = (zh * layer.attn_dst).sum(-1).contiguous()
+    assert src_e.dtype == torch.float32 and dst_e.dtype == torch.float32  # promotion against the float32 parameters
+    s = gather_rows(src_e, seed_local)
+    index, counts = GATConv.with_self_loops(seed_local, index, counts, S)
+    alpha = gat_attention(s, dst_e, index, S, counts=counts, negative_slope=layer.negative_slope, dropout=layer.dropout,
+                          seed=layer.seed, call=call)
+    out = weighted_segment_aggregate(z.float(), index, alpha, S, counts=counts)
+    return out.view(S, H, C).mean(1) + layer.bias
+
+
+def test_gatconv_under_bf16_autocast_equals_the_float32_reduce_of_its_steps():
+    torch.manual_seed(0)
+    layer = GATConv(16, 12, num_heads=2, dropout=0.4, use_bias=True, add_self_loops=True, seed=11).cuda().train()
+    M, S = 23, 6
+    x_nodes = torch.randn(M, 16).cuda()
+    seed_local = torch.tensor([0, 5, 5, 9, 22, 3]).cuda()
+    counts = torch.tensor([3, 0, 4, 1, 5, 2], dtype=torch.int32).cuda()  # ragged, one empty segment
+    index = torch.randint(0, M, (int(counts.sum()),), generator=torch.Generator().manual_seed(2)).cuda()
+    go = torch.randn(S, 12, generator=torch.Generator().manual_seed(3)).cuda()
+    params = list(layer.parameters())
+    runs = []
+    for by_hand in (False, False, True):
+        layer.calls = 0
+        for p in params:
+            p.grad = None
+        with torch.autocast("cuda", dtype=torch.bfloat16):
+            out = _gat_by_hand(layer, x_nodes, seed_local, index, counts, 0) if by_hand else \
+                layer(x_nodes, seed_local, index, counts)
+        assert out.dtype == torch.float32
+        out.backward(go)
+        runs.append([out.detach().clone()] + [p.grad.clone() for p in params])
+    assert all(g.abs().sum() > 0 for g in runs[0])
+    for a, b, c in zip(*runs):
+        assert torch.equal(a, b)  # two runs of the layer: the same bits
+        assert torch.equal(a, c)  # the layer against its steps with a float32 z in the reduce
+
+
+def test_what_still_raises():
+    x16, x32 = _leafs()
+    idx = _index(12)
+    for bad in (x32.detach().half(), x32.detach().double()):
+        with pytest.raises(ValueError):
+            segment_aggregate(bad, idx, 4)
+        with pytest.raises(ValueError):
+            gather_rows(bad, idx)
+        with pytest.raises(ValueError):
+            weighted_segment_aggregate(bad, idx, torch.ones(12).cuda(), 4)
+        with pytest.raises(ValueError):
+            pair_dot(bad, idx, bad, idx)
+    with pytest.raises(ValueError):  # weights stay float32
+        weighted_segment_aggregate(x16, idx, torch.ones(12, dtype=torch.bfloat16).cuda(), 4)
+    q = torch.randn(4, D).cuda()
+    with pytest.raises(ValueError):  # dot_attention stays float32
+        dot_attention(q.to(torch.bfloat16), x16.detach(), x16.detach(), idx.clamp(0, N - 1), 4)
+    with pytest.raises(ValueError):
+        dot_attention(q, x16.detach(), x16.detach(), idx.clamp(0, N - 1), 4)
+
+
+def test_amp_example_trains_and_reproduces():
+    """examples/train_sage_amp.py, one short epoch (twice, inside the script) in a process of its own: it exits 0 only
+    when the loss falls inside the epoch and the two runs give the same bits"""
+    cmd = [sys.executable, os.path.join(ROOT, "examples", "train_sage_amp.py"), "1", "4096"]
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-3000:]
+    assert "the same bits: True" in r.stdout
