@@ -108,6 +108,68 @@ def test_pair_dot_on_bf16_leaves(heads):
         pair_dot(a16, ia, b32, ib)
 
 
+# ---- offset views: x = base[1:] is contiguous, starts 2 * D bytes into base, and is a non-leaf of it -----------------
+OFFSET_DIMS = {5: 1, 6: 2, 4: 1, 8: 2}  # D -> heads: x starts 10, 12, 8 and 16 bytes in
+
+
+def _offset_view(d, seed):
+    """(base, x = base[1:], a leaf clone of x): base is a bfloat16 leaf of [N + 1, d]"""
+    base = torch.randn(N + 1, d, generator=torch.Generator().manual_seed(seed)).to(torch.bfloat16).cuda()
+    base.requires_grad_(True)
+    x = base[1:]
+    assert base.data_ptr() % 16 == 0 and x.data_ptr() % 16 == (2 * d) % 16
+    assert x.is_contiguous() and not x.is_leaf
+    return base, x, base.detach()[1:].clone().requires_grad_(True)
+
+
+def _check_offset(fn, views):
+    """fn(*xs) on the offset views and on their clones: the same outputs, the same gradient bits behind row 0 of each
+    base, and nothing but zero bits in row 0"""
+    out_v, out_c = fn(*[v[1] for v in views]), fn(*[v[2] for v in views])
+    assert out_v.dtype == torch.float32 and torch.equal(out_v, out_c)
+    go = torch.randn(out_c.shape, generator=torch.Generator().manual_seed(7)).cuda()
+    out_v.backward(go)
+    out_c.backward(go)
+    for base, _, clone in views:
+        assert base.grad.dtype == torch.bfloat16 and clone.grad.abs().sum() > 0
+        assert torch.equal(_bits16(base.grad[1:]), _bits16(clone.grad))
+        assert not _bits16(base.grad[0]).any()
+
+
+@pytest.mark.parametrize("d", sorted(OFFSET_DIMS))
+@pytest.mark.parametrize("op", ["mean", "max"])
+def test_segment_aggregate_on_an_offset_view(op, d):
+    idx = _index(12)
+    _check_offset(lambda x: segment_aggregate(x, idx, 4, op=op, default_attr=0.25), [_offset_view(d, 0)])
+
+
+@pytest.mark.parametrize("d", sorted(OFFSET_DIMS))
+def test_gather_rows_on_an_offset_view(d):
+    idx = _index(30).reshape(5, 6)
+    _check_offset(lambda x: gather_rows(x, idx, default_attr=0.25), [_offset_view(d, 1)])
+
+
+@pytest.mark.parametrize("d", sorted(OFFSET_DIMS))
+def test_weighted_segment_aggregate_on_an_offset_view(d):
+    idx = _index(12)
+    heads = OFFSET_DIMS[d]
+    ws = [torch.randn(12, heads, generator=torch.Generator().manual_seed(9)).cuda().requires_grad_(True)
+          for _ in range(2)]
+    it = iter(ws)  # _check_offset calls fn on the view first
+    _check_offset(lambda x: weighted_segment_aggregate(x, idx, next(it), 4, op="mean", default_attr=0.25),
+                  [_offset_view(d, 2)])
+    # grad_w reads the offset x; at these D its alignment class is the clone's (8 and 16 bytes in: 4-element loads)
+    assert ws[0].grad.abs().sum() > 0 and torch.equal(ws[0].grad, ws[1].grad)
+
+
+@pytest.mark.parametrize("d", sorted(OFFSET_DIMS))
+def test_pair_dot_on_offset_views(d):
+    ia, ib = _index(5, seed=4), _index(15, seed=5).reshape(5, 3)
+    heads = OFFSET_DIMS[d]
+    _check_offset(lambda a, b: pair_dot(a, ia, b, ib, heads=heads, default_attr=0.25),
+                  [_offset_view(d, 3), _offset_view(d, 4)])
+
+
 def test_one_bf16_tensor_feeding_two_ops_adds_the_two_gradients_in_bf16():
     idx_a, idx_g = _index(12), _index(7, seed=8)
     ga = torch.randn(4, D, generator=torch.Generator().manual_seed(1)).cuda()
