@@ -14,9 +14,7 @@
 
 #include <new>
 
-#include <rocprim/rocprim.hpp>
-
-#include "glx_common.h"
+#include "glx_prims.h"
 
 namespace {
 
@@ -54,16 +52,6 @@ inline unsigned grid_for(int64_t n) {
   if (b < 1) b = 1;
   return (unsigned)(b < 8192 ? b : 8192);
 }
-
-#define GLX_ROCPRIM(call)                                                      \
-  do {                                                                         \
-    size_t bytes__ = 0;                                                        \
-    GLX_HIP(call(nullptr, bytes__));                                           \
-    GlxTemp tmp__;                                                             \
-    GLX_HIP(hipMalloc(&tmp__.p, bytes__ ? bytes__ : 16));                      \
-    GLX_HIP(call(tmp__.p, bytes__));                                           \
-    GLX_HIP(hipStreamSynchronize(s)); /* tmp__ is freed right after */         \
-  } while (0)
 
 int build_impl(glx_graph* g, const int64_t* src, const int64_t* dst, const float* weight,
                const int64_t* edge_ids, const int64_t* timestamp, int order, int ptr_kind, hipStream_t s) {
@@ -122,19 +110,18 @@ int build_impl(glx_graph* g, const int64_t* src, const int64_t* dst, const float
     GlxTemp tk;
     GLX_HIP(hipMalloc(&tk.p, (size_t)E * 8));
     int64_t* ts_sorted = tk.as<int64_t>();
-#define SORT_T(tmp, bytes) rocprim::radix_sort_pairs(tmp, bytes, d_ts, ts_sorted, pa, pb, n, 0, 64, s)
-    GLX_ROCPRIM(SORT_T);
-#undef SORT_T
+    GLX_TRY(glx_prim_temp(s, "graph build: sort edges by timestamp", [&](void* tmp, size_t& bytes) {
+      return rocprim::radix_sort_pairs(tmp, bytes, d_ts, ts_sorted, pa, pb, n, 0, 64, s);
+    }));
     int64_t* t = pa; pa = pb; pb = t;
   } else if (weight && order == GLX_ORDER_WEIGHT_DESC) {
     // pass 1: weight descending, stable (ties keep insertion order)
     GlxTemp wk;
     GLX_HIP(hipMalloc(&wk.p, (size_t)E * 4));
     float* w_sorted = wk.as<float>();
-#define SORT_W(tmp, bytes) \
-  rocprim::radix_sort_pairs_desc(tmp, bytes, d_w, w_sorted, pa, pb, n, 0, 32, s)
-    GLX_ROCPRIM(SORT_W);
-#undef SORT_W
+    GLX_TRY(glx_prim_temp(s, "graph build: sort edges by weight, descending", [&](void* tmp, size_t& bytes) {
+      return rocprim::radix_sort_pairs_desc(tmp, bytes, d_w, w_sorted, pa, pb, n, 0, 32, s);
+    }));
     int64_t* t = pa; pa = pb; pb = t;
   }
   // pass 2: source id ascending, stable
@@ -143,9 +130,9 @@ int build_impl(glx_graph* g, const int64_t* src, const int64_t* dst, const float
   int64_t* ka = keys_a.as<int64_t>();
   int64_t* kb = keys_b.as<int64_t>();
   glx_gather_kernel<int64_t><<<grid_for(E), 256, 0, s>>>(d_src, pa, E, ka);
-#define SORT_S(tmp, bytes) rocprim::radix_sort_pairs(tmp, bytes, ka, kb, pa, pb, n, 0, 64, s)
-  GLX_ROCPRIM(SORT_S);
-#undef SORT_S
+  GLX_TRY(glx_prim_temp(s, "graph build: sort edges by source id", [&](void* tmp, size_t& bytes) {
+    return rocprim::radix_sort_pairs(tmp, bytes, ka, kb, pa, pb, n, 0, 64, s);
+  }));
   const int64_t* sorted_src = kb;
   const int64_t* perm = pb;
   // rows = runs of equal source id
@@ -153,22 +140,20 @@ int build_impl(glx_graph* g, const int64_t* src, const int64_t* dst, const float
   GLX_HIP(hipMalloc(&uniq.p, (size_t)E * 8));
   GLX_HIP(hipMalloc(&counts.p, (size_t)E * 8));
   GLX_HIP(hipMalloc(&nruns.p, sizeof(int64_t)));
-#define RLE(tmp, bytes)                                                                        \
-  rocprim::run_length_encode(tmp, bytes, sorted_src, n, uniq.as<int64_t>(), counts.as<int64_t>(), \
-                             nruns.as<int64_t>(), s)
-  GLX_ROCPRIM(RLE);
-#undef RLE
+  GLX_TRY(glx_prim_temp(s, "graph build: run-length encode the sorted source ids", [&](void* tmp, size_t& bytes) {
+    return rocprim::run_length_encode(tmp, bytes, sorted_src, n, uniq.as<int64_t>(), counts.as<int64_t>(),
+                                      nruns.as<int64_t>(), s);
+  }));
   int64_t V = 0;
   GLX_HIP(hipMemcpyAsync(&V, nruns.p, sizeof(int64_t), hipMemcpyDeviceToHost, s));
   GLX_HIP(hipStreamSynchronize(s));
   GLX_REQUIRE(V < INT32_MAX, "more than 2^31 distinct source ids");
   g->num_rows = V;
   GLX_HIP(hipMalloc(&g->row_ptr, (size_t)(V + 1) * 8));
-#define SCAN(tmp, bytes)                                                                          \
-  rocprim::exclusive_scan(tmp, bytes, counts.as<int64_t>(), g->row_ptr, (int64_t)0, (size_t)V,   \
-                          rocprim::plus<int64_t>(), s)
-  GLX_ROCPRIM(SCAN);
-#undef SCAN
+  GLX_TRY(glx_prim_temp(s, "graph build: scan the row degrees into row_ptr", [&](void* tmp, size_t& bytes) {
+    return rocprim::exclusive_scan(tmp, bytes, counts.as<int64_t>(), g->row_ptr, (int64_t)0, (size_t)V,
+                                   rocprim::plus<int64_t>(), s);
+  }));
   glx_set_last_kernel<<<1, 1, 0, s>>>(g->row_ptr, V, E);
   GLX_HIP(hipMalloc(&g->adj, (size_t)E * sizeof(GlxAdj)));
   glx_gather_adj_kernel<<<grid_for(E), 256, 0, s>>>(d_dst, d_eid, perm, E, g->adj);

@@ -26,6 +26,13 @@ void glx_set_error(const char* fmt, ...);
     }                                                                                   \
   } while (0)
 
+// Returns the GLX_* code of a glx_prim_temp / glx_prim_leased call (glx_prims.h) that failed; the error text is set.
+#define GLX_TRY(expr)                     \
+  do {                                    \
+    const int rc__ = (expr);              \
+    if (rc__ != GLX_OK) return rc__;      \
+  } while (0)
+
 #define GLX_REQUIRE(cond, ...)         \
   do {                                 \
     if (!(cond)) {                     \
@@ -89,6 +96,7 @@ bool glx_profile_suspend(bool suspend);  // returns the previous "enabled" state
 
 // Temporary device allocation released on every exit path.  For one-off build-time allocations: hipFree
 // synchronises the device, so per-request paths stage through GlxHostStage / GlxScratch instead.
+// The temporary storage of a rocprim primitive goes through glx_prim_temp / glx_prim_leased (glx_prims.h).
 struct GlxTemp {
   void* p = nullptr;
   ~GlxTemp() {

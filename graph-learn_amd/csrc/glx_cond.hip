@@ -27,11 +27,9 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <rocprim/rocprim.hpp>
-
 #include <vector>
 
-#include "glx_common.h"
+#include "glx_prims.h"
 
 struct glx_cond_table {
   int device;
@@ -47,16 +45,6 @@ struct glx_cond_table {
 };
 
 namespace {
-
-#define GLX_ROCPRIM_C(call)                               \
-  do {                                                    \
-    size_t bytes__ = 0;                                   \
-    GLX_HIP(call(nullptr, bytes__));                      \
-    GlxTemp tmp__;                                        \
-    GLX_HIP(hipMalloc(&tmp__.p, bytes__ ? bytes__ : 16)); \
-    GLX_HIP(call(tmp__.p, bytes__));                      \
-    GLX_HIP(hipStreamSynchronize(s));                     \
-  } while (0)
 
 inline unsigned grid_of(int64_t n) {
   int64_t b = (n + 255) / 256;
@@ -411,25 +399,25 @@ extern "C" int glx_cond_table_create(int device, int64_t num_ids, const int64_t*
       GLX_HIP(hipMemcpyAsync(keys.p, cand_keys + (size_t)c * U, (size_t)U * 8, kind, s));
       glx_cond_iota_kernel<<<grid_of(U), 256, 0, s>>>(pos.as<int64_t>(), U);
       // stable: candidate order survives inside a key
-#define SORTK(tmp, bytes) \
-  rocprim::radix_sort_pairs(tmp, bytes, keys.as<int64_t>(), keys_s.as<int64_t>(), pos.as<int64_t>(), pos_s.as<int64_t>(), (size_t)U, 0, 64, s)
-      GLX_ROCPRIM_C(SORTK);
-#undef SORTK
+      GLX_TRY(glx_prim_temp(s, "conditional table: sort candidates by attribute key", [&](void* tmp, size_t& bytes) {
+        return rocprim::radix_sort_pairs(tmp, bytes, keys.as<int64_t>(), keys_s.as<int64_t>(), pos.as<int64_t>(),
+                                         pos_s.as<int64_t>(), (size_t)U, 0, 64, s);
+      }));
       int64_t* gkey = t->group_key + (size_t)c * U;
       int64_t* goff = t->group_off + (size_t)c * (U + 1);
       GLX_HIP(hipMemsetAsync(cnt.p, 0, ((size_t)U + 1) * 8, s));
-#define RLE(tmp, bytes) \
-  rocprim::run_length_encode(tmp, bytes, keys_s.as<int64_t>(), (size_t)U, gkey, cnt.as<int64_t>(), nruns.as<int64_t>(), s)
-      GLX_ROCPRIM_C(RLE);
-#undef RLE
+      GLX_TRY(glx_prim_temp(s, "conditional table: run-length encode the sorted keys", [&](void* tmp, size_t& bytes) {
+        return rocprim::run_length_encode(tmp, bytes, keys_s.as<int64_t>(), (size_t)U, gkey, cnt.as<int64_t>(),
+                                          nruns.as<int64_t>(), s);
+      }));
       int64_t G = 0;
       GLX_HIP(hipMemcpyAsync(&G, nruns.p, 8, hipMemcpyDeviceToHost, s));
       GLX_HIP(hipStreamSynchronize(s));
       GLX_HIP(hipMemcpyAsync(t->num_groups + c, nruns.p, 8, hipMemcpyDeviceToDevice, s));
-#define SCANG(tmp, bytes) \
-  rocprim::exclusive_scan(tmp, bytes, cnt.as<int64_t>(), goff, (int64_t)0, (size_t)G + 1, rocprim::plus<int64_t>(), s)
-      GLX_ROCPRIM_C(SCANG);
-#undef SCANG
+      GLX_TRY(glx_prim_temp(s, "conditional table: scan the group sizes into offsets", [&](void* tmp, size_t& bytes) {
+        return rocprim::exclusive_scan(tmp, bytes, cnt.as<int64_t>(), goff, (int64_t)0, (size_t)G + 1,
+                                       rocprim::plus<int64_t>(), s);
+      }));
       glx_cond_gather_kernel<<<grid_of(U), 256, 0, s>>>(pos_s.as<int64_t>(), t->ids, w.as<float>(), U,
                                                       t->member + (size_t)c * U, member_w.as<float>());
       rc = glx_alias_build_launch(goff, member_w.as<float>(), G, U, t->member_tab + (size_t)c * U, s);

@@ -26,9 +26,8 @@
 
 #include <chrono>
 
-#include <rocprim/rocprim.hpp>
-
 #include "glx_comm.h"
+#include "glx_prims.h"
 
 namespace {
 
@@ -869,16 +868,6 @@ inline uint64_t pow2_at_least(uint64_t x) {
   while (c < x) c <<= 1;
   return c;
 }
-
-#define GLX_ROCPRIM(call)                                             \
-  do {                                                                \
-    size_t bytes__ = 0;                                               \
-    GLX_HIP(call(nullptr, bytes__));                                  \
-    GlxTemp tmp__;                                                    \
-    GLX_HIP(hipMalloc(&tmp__.p, bytes__ ? bytes__ : 16));             \
-    GLX_HIP(call(tmp__.p, bytes__));                                  \
-    GLX_HIP(hipStreamSynchronize(s)); /* tmp__ is freed right after */ \
-  } while (0)
 
 }  // namespace
 
@@ -1738,12 +1727,12 @@ int dist_sample_full_device(glx_dist_store* st, const int64_t* src, int32_t batc
   int64_t total = 0;
   if (n > 0) {
     glx_dist_stitch_deg_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(deg_b, order, n, deg_out, deg64);
-#define SCAN_O(tmp, bytes) rocprim::exclusive_scan(tmp, bytes, deg64, offsets_out, (int64_t)0, (size_t)n, rocprim::plus<int64_t>(), s)
-    GLX_ROCPRIM(SCAN_O);
-#undef SCAN_O
-#define SCAN_S(tmp, bytes) rocprim::exclusive_scan(tmp, bytes, deg_b, src_off, (int64_t)0, (size_t)n, rocprim::plus<int64_t>(), s)
-    GLX_ROCPRIM(SCAN_S);
-#undef SCAN_S
+    GLX_TRY(glx_prim_temp(s, "partitioned full sampler: scan the row sizes into output offsets", [&](void* tmp, size_t& bytes) {
+      return rocprim::exclusive_scan(tmp, bytes, deg64, offsets_out, (int64_t)0, (size_t)n, rocprim::plus<int64_t>(), s);
+    }));
+    GLX_TRY(glx_prim_temp(s, "partitioned full sampler: scan the bucketed row sizes into arrival offsets", [&](void* tmp, size_t& bytes) {
+      return rocprim::exclusive_scan(tmp, bytes, deg_b, src_off, (int64_t)0, (size_t)n, rocprim::plus<int64_t>(), s);
+    }));
     int64_t last[2] = {0, 0};
     GLX_HIP(hipMemcpyAsync(&last[0], offsets_out + (n - 1), 8, hipMemcpyDeviceToHost, s));
     GLX_HIP(hipMemcpyAsync(&last[1], deg64 + (n - 1), 8, hipMemcpyDeviceToHost, s));
@@ -1900,9 +1889,9 @@ extern "C" int glx_dist_build_graph_replica(glx_dist_store* st, const int64_t* h
   // ascending ids: every rank then lists every owner's rows in the same order
   GLX_HIP(hipMalloc(&sorted.p, (size_t)n1 * 8));
   if (n > 0) {
-#define SORTK(tmp, bytes) rocprim::radix_sort_keys(tmp, bytes, d_hot, sorted.as<int64_t>(), (size_t)n, 0, 64, s)
-    GLX_ROCPRIM(SORTK);
-#undef SORTK
+    GLX_TRY(glx_prim_temp(s, "graph replica: sort the hot ids", [&](void* tmp, size_t& bytes) {
+      return rocprim::radix_sort_keys(tmp, bytes, d_hot, sorted.as<int64_t>(), (size_t)n, 0, 64, s);
+    }));
   }
   GLX_HIP(hipMalloc(&bucketed.p, (size_t)n1 * 8));
   GLX_HIP(hipMalloc(&order.p, (size_t)n1 * 8));
@@ -1922,11 +1911,10 @@ extern "C" int glx_dist_build_graph_replica(glx_dist_store* st, const int64_t* h
   if (c_me > 0) {
     glx_dist_rep_deg_kernel<<<(unsigned)((c_me + 255) / 256), 256, 0, s>>>(g->map(), g->row_ptr, my_ids, c_me,
                                                                           deg_mine.as<int64_t>());
-#define SCANO(tmp, bytes)                                                                                      \
-  rocprim::exclusive_scan(tmp, bytes, deg_mine.as<int64_t>(), off_mine.as<int64_t>(), (int64_t)0, (size_t)c_me, \
-                          rocprim::plus<int64_t>(), s)
-    GLX_ROCPRIM(SCANO);
-#undef SCANO
+    GLX_TRY(glx_prim_temp(s, "graph replica: scan the degrees of this rank's hot rows", [&](void* tmp, size_t& bytes) {
+      return rocprim::exclusive_scan(tmp, bytes, deg_mine.as<int64_t>(), off_mine.as<int64_t>(), (int64_t)0, (size_t)c_me,
+                                     rocprim::plus<int64_t>(), s);
+    }));
     int64_t last[2] = {0, 0};
     GLX_HIP(hipMemcpyAsync(&last[0], off_mine.as<int64_t>() + (c_me - 1), 8, hipMemcpyDeviceToHost, s));
     GLX_HIP(hipMemcpyAsync(&last[1], deg_mine.as<int64_t>() + (c_me - 1), 8, hipMemcpyDeviceToHost, s));
@@ -1975,11 +1963,10 @@ extern "C" int glx_dist_build_graph_replica(glx_dist_store* st, const int64_t* h
   // rows in owner-major order = `bucketed`; row_ptr = exclusive scan of the degrees (+ the total)
   GLX_HIP(hipMalloc(&row_ptr.p, (size_t)(n + 1) * 8));
   if (n > 0) {
-#define SCANR(tmp, bytes)                                                                                    \
-  rocprim::exclusive_scan(tmp, bytes, deg_all.as<int64_t>(), row_ptr.as<int64_t>(), (int64_t)0, (size_t)n,   \
-                          rocprim::plus<int64_t>(), s)
-    GLX_ROCPRIM(SCANR);
-#undef SCANR
+    GLX_TRY(glx_prim_temp(s, "graph replica: scan the degrees of all hot rows into row_ptr", [&](void* tmp, size_t& bytes) {
+      return rocprim::exclusive_scan(tmp, bytes, deg_all.as<int64_t>(), row_ptr.as<int64_t>(), (int64_t)0, (size_t)n,
+                                     rocprim::plus<int64_t>(), s);
+    }));
   }
   GLX_HIP(hipMemcpyAsync(row_ptr.as<int64_t>() + n, &E, 8, hipMemcpyHostToDevice, s));
   GLX_HIP(hipStreamSynchronize(s));
@@ -2737,9 +2724,9 @@ extern "C" int glx_dist_store_set_cache(glx_dist_store* st, const int64_t* hot_i
   // the replica's rows are kept in ascending id order (an id's row is then its rank among the hot ids)
   GlxTemp sorted, sorted_masked, table_sorted;
   GLX_HIP(hipMalloc(&sorted.p, (size_t)n * 8));
-#define SORTK(tmp, bytes) rocprim::radix_sort_keys(tmp, bytes, d_hot, sorted.as<int64_t>(), (size_t)n, 0, 64, s)
-  GLX_ROCPRIM(SORTK);
-#undef SORTK
+  GLX_TRY(glx_prim_temp(s, "feature replica: sort the hot ids", [&](void* tmp, size_t& bytes) {
+    return rocprim::radix_sort_keys(tmp, bytes, d_hot, sorted.as<int64_t>(), (size_t)n, 0, 64, s);
+  }));
   d_hot = sorted.as<int64_t>();
   GLX_HIP(hipMalloc(&bucketed.p, (size_t)n * 8));
   GLX_HIP(hipMalloc(&order.p, (size_t)n * 8));
@@ -2832,9 +2819,9 @@ extern "C" int glx_dist_store_set_cache(glx_dist_store* st, const int64_t* hot_i
         sorted.as<int64_t>(), sorted_masked.as<int64_t>(), n, reinterpret_cast<unsigned long long*>(member),
         reinterpret_cast<unsigned long long*>(valid), flags);
     glx_dist_bitmap_popc_kernel<<<(unsigned)((words + 255) / 256), 256, 0, s>>>(member, words, rank);
-#define SCANP(tmp, bytes) rocprim::exclusive_scan(tmp, bytes, rank, rank, 0u, (size_t)words, rocprim::plus<uint32_t>(), s)
-    GLX_ROCPRIM(SCANP);
-#undef SCANP
+    GLX_TRY(glx_prim_temp(s, "feature replica: scan the member bitmap's word counts into ranks", [&](void* tmp, size_t& bytes) {
+      return rocprim::exclusive_scan(tmp, bytes, rank, rank, 0u, (size_t)words, rocprim::plus<uint32_t>(), s);
+    }));
     glx_dist_bitmap_pack_kernel<<<(unsigned)((words + 255) / 256), 256, 0, s>>>(member, rank, words, packed);
     int h_flags[2] = {0, 0};
     GLX_HIP(hipMemcpyAsync(h_flags, flags, 8, hipMemcpyDeviceToHost, s));
@@ -2908,17 +2895,15 @@ int dst_totals(glx_dist_store* st, hipStream_t s, DstTotals* t) {
   GLX_HIP(hipMalloc(&nown.p, 8));
   t->M = 0;
   if (m > 0) {
-#define SORTP(tmp, bytes)                                                                                       \
-  rocprim::radix_sort_pairs(tmp, bytes, t->ids_in.as<int64_t>(), ids_s.as<int64_t>(), cnt_in.as<int64_t>(), \
-                            cnt_s.as<int64_t>(), m, 0, 64, s)
-    GLX_ROCPRIM(SORTP);
-#undef SORTP
-#define REDUCE(tmp, bytes)                                                                                        \
-  rocprim::reduce_by_key(tmp, bytes, ids_s.as<int64_t>(), cnt_s.as<int64_t>(), m, t->own_id.as<int64_t>(),    \
-                         t->own_cnt.as<int64_t>(), nown.as<int64_t>(), rocprim::plus<int64_t>(),                \
-                         rocprim::equal_to<int64_t>(), s)
-    GLX_ROCPRIM(REDUCE);
-#undef REDUCE
+    GLX_TRY(glx_prim_temp(s, "global in-degrees: sort the received (id, count) pairs by id", [&](void* tmp, size_t& bytes) {
+      return rocprim::radix_sort_pairs(tmp, bytes, t->ids_in.as<int64_t>(), ids_s.as<int64_t>(), cnt_in.as<int64_t>(),
+                                       cnt_s.as<int64_t>(), m, 0, 64, s);
+    }));
+    GLX_TRY(glx_prim_temp(s, "global in-degrees: sum the counts of every id", [&](void* tmp, size_t& bytes) {
+      return rocprim::reduce_by_key(tmp, bytes, ids_s.as<int64_t>(), cnt_s.as<int64_t>(), m, t->own_id.as<int64_t>(),
+                                    t->own_cnt.as<int64_t>(), nown.as<int64_t>(), rocprim::plus<int64_t>(),
+                                    rocprim::equal_to<int64_t>(), s);
+    }));
     GLX_HIP(hipMemcpyAsync(&t->M, nown.p, 8, hipMemcpyDeviceToHost, s));
     GLX_HIP(hipStreamSynchronize(s));
   }
@@ -2969,11 +2954,10 @@ extern "C" int glx_dist_hot_ids(glx_dist_store* st, int64_t want, int64_t* ids_o
   GLX_HIP(hipMalloc(&top_id.p, (size_t)(M ? M : 1) * 8));
   if (M > 0) {
     const size_t Ms = (size_t)M;
-#define SORTD(tmp, bytes)                                                                                             \
-  rocprim::radix_sort_pairs_desc(tmp, bytes, t.own_cnt.as<int64_t>(), top_cnt.as<int64_t>(), t.own_id.as<int64_t>(), \
-                                 top_id.as<int64_t>(), Ms, 0, 64, s)
-    GLX_ROCPRIM(SORTD);
-#undef SORTD
+    GLX_TRY(glx_prim_temp(s, "hot ids: sort this rank's ids by in-degree, descending", [&](void* tmp, size_t& bytes) {
+      return rocprim::radix_sort_pairs_desc(tmp, bytes, t.own_cnt.as<int64_t>(), top_cnt.as<int64_t>(), t.own_id.as<int64_t>(),
+                                            top_id.as<int64_t>(), Ms, 0, 64, s);
+    }));
   }
   const int64_t c_me = M < want ? M : want;
   // share the candidates: everyone gets every owner's list (rank-major) and merges the same way
@@ -2996,16 +2980,14 @@ extern "C" int glx_dist_hot_ids(glx_dist_store* st, int64_t want, int64_t* ids_o
   GLX_HIP(hipMalloc(&by_id_id.p, T * 8));
   GLX_HIP(hipMalloc(&fin_cnt.p, T * 8));
   GLX_HIP(hipMalloc(&fin_id.p, T * 8));
-#define SORT1(tmp, bytes)                                                                                     \
-  rocprim::radix_sort_pairs(tmp, bytes, all_id.as<int64_t>(), by_id_id.as<int64_t>(), all_cnt.as<int64_t>(), \
-                            by_id_cnt.as<int64_t>(), T, 0, 64, s)
-  GLX_ROCPRIM(SORT1);
-#undef SORT1
-#define SORT2(tmp, bytes)                                                                                            \
-  rocprim::radix_sort_pairs_desc(tmp, bytes, by_id_cnt.as<int64_t>(), fin_cnt.as<int64_t>(), by_id_id.as<int64_t>(), \
-                                 fin_id.as<int64_t>(), T, 0, 64, s)
-  GLX_ROCPRIM(SORT2);
-#undef SORT2
+  GLX_TRY(glx_prim_temp(s, "hot ids: sort the gathered candidates by id", [&](void* tmp, size_t& bytes) {
+    return rocprim::radix_sort_pairs(tmp, bytes, all_id.as<int64_t>(), by_id_id.as<int64_t>(), all_cnt.as<int64_t>(),
+                                     by_id_cnt.as<int64_t>(), T, 0, 64, s);
+  }));
+  GLX_TRY(glx_prim_temp(s, "hot ids: stable sort of the candidates by in-degree, descending", [&](void* tmp, size_t& bytes) {
+    return rocprim::radix_sort_pairs_desc(tmp, bytes, by_id_cnt.as<int64_t>(), fin_cnt.as<int64_t>(), by_id_id.as<int64_t>(),
+                                          fin_id.as<int64_t>(), T, 0, 64, s);
+  }));
   const int64_t take = (int64_t)T < want ? (int64_t)T : want;
   GLX_HIP(hipMemcpyAsync(ids_out, fin_id.p, (size_t)take * 8, hipMemcpyDeviceToHost, s));
   GLX_HIP(hipStreamSynchronize(s));
@@ -3135,11 +3117,10 @@ extern "C" int glx_dist_negative_create(glx_dist_store* st, int by_in_degree, vo
   GLX_HIP(hipMalloc(&w.p, (T ? T : 1) * 4));
   if (T > 0) {
     // ascending as signed ids (rocPRIM orders signed keys as such)
-#define SORTN(tmp, bytes)                                                                                       \
-  rocprim::radix_sort_pairs(tmp, bytes, all_id.as<int64_t>(), s_id.as<int64_t>(), all_cnt.as<int64_t>(),        \
-                            s_cnt.as<int64_t>(), T, 0, 64, s)
-    GLX_ROCPRIM(SORTN);
-#undef SORTN
+    GLX_TRY(glx_prim_temp(s, "partitioned negative table: sort the gathered candidates by id", [&](void* tmp, size_t& bytes) {
+      return rocprim::radix_sort_pairs(tmp, bytes, all_id.as<int64_t>(), s_id.as<int64_t>(), all_cnt.as<int64_t>(),
+                                       s_cnt.as<int64_t>(), T, 0, 64, s);
+    }));
     glx_dist_i64_to_f32_kernel<<<(unsigned)((T + 255) / 256), 256, 0, s>>>(s_cnt.as<int64_t>(), (int64_t)T, w.as<float>());
     GLX_HIP(hipGetLastError());
   }

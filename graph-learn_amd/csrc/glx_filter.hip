@@ -21,9 +21,7 @@
 
 #include <vector>
 
-#include <rocprim/rocprim.hpp>
-
-#include "glx_common.h"
+#include "glx_prims.h"
 
 namespace {
 
@@ -723,17 +721,6 @@ int dedup_min_rows() {
   return v < 0 ? 1024 : (int)v;
 }
 
-#define GLX_FILTER_PRIM(call_with)                                             \
-  do {                                                                         \
-    size_t bytes__ = 0;                                                        \
-    void* tmp__ = nullptr;                                                     \
-    GLX_HIP(call_with(tmp__, bytes__));                                        \
-    GlxScratch lease__;                                                        \
-    int rc__ = lease__.alloc(bytes__ ? bytes__ : 8, s, 3);                     \
-    if (rc__ != GLX_OK) return rc__;                                           \
-    GLX_HIP(call_with(lease__.p, bytes__));                                    \
-  } while (0)
-
 // EdgeWeight / InDegree under circular padding, any filter: start / deg are the request rows' (filled by the caller).
 int filtered_alias_dedup(const glx_graph* g, int sampler, const int64_t* d_rng, int32_t batch, int32_t k,
                          int64_t default_nbr, uint64_t seed, uint64_t cc, FilterDev f, const int64_t* start,
@@ -763,25 +750,25 @@ int filtered_alias_dedup(const glx_graph* g, int sampler, const int64_t* d_rng, 
   const unsigned row_blocks = (unsigned)((nb + 255) / 256);
   glx_filter_dedup_keys_kernel<<<row_blocks, 256, 0, s>>>(start, deg, f.values, same_value ? 1 : 0, batch, key1, key2, iota);
   if (same_value) {
-#define SORT1(tmp, bytes) rocprim::radix_sort_pairs(tmp, bytes, key1, k1s, iota, perm, nb, 0, 64, s)
-    GLX_FILTER_PRIM(SORT1);
-#undef SORT1
+    GLX_TRY(glx_prim_leased(s, 3, "filtered dedup: sort request rows by vertex", [&](void* tmp, size_t& bytes) {
+      return rocprim::radix_sort_pairs(tmp, bytes, key1, k1s, iota, perm, nb, 0, 64, s);
+    }));
     GLX_HIP(hipMemsetAsync(k2s, 0, nb * 8, s));
   } else {
     // by value first, then (stable) by vertex: rows of one (vertex, value) pair end up adjacent
-#define SORTA(tmp, bytes) rocprim::radix_sort_pairs(tmp, bytes, key2, k2s, iota, permA, nb, 0, 64, s)
-    GLX_FILTER_PRIM(SORTA);
-#undef SORTA
+    GLX_TRY(glx_prim_leased(s, 3, "filtered dedup: sort request rows by filter value", [&](void* tmp, size_t& bytes) {
+      return rocprim::radix_sort_pairs(tmp, bytes, key2, k2s, iota, permA, nb, 0, 64, s);
+    }));
     glx_filter_dedup_gather_kernel<<<row_blocks, 256, 0, s>>>(key1, permA, batch, k2s);  // k2s reused: key1 in A order
-#define SORTB(tmp, bytes) rocprim::radix_sort_pairs(tmp, bytes, k2s, k1s, permA, perm, nb, 0, 64, s)
-    GLX_FILTER_PRIM(SORTB);
-#undef SORTB
+    GLX_TRY(glx_prim_leased(s, 3, "filtered dedup: stable sort of the value order by vertex", [&](void* tmp, size_t& bytes) {
+      return rocprim::radix_sort_pairs(tmp, bytes, k2s, k1s, permA, perm, nb, 0, 64, s);
+    }));
     glx_filter_dedup_gather_kernel<<<row_blocks, 256, 0, s>>>(key2, perm, batch, k2s);
   }
   glx_filter_dedup_flag_kernel<<<row_blocks, 256, 0, s>>>(k1s, k2s, batch, flag);
-#define SCANF(tmp, bytes) rocprim::inclusive_scan(tmp, bytes, flag, uid1, nb, rocprim::plus<int32_t>(), s)
-  GLX_FILTER_PRIM(SCANF);
-#undef SCANF
+  GLX_TRY(glx_prim_leased(s, 3, "filtered dedup: scan the run flags into unique ids", [&](void* tmp, size_t& bytes) {
+    return rocprim::inclusive_scan(tmp, bytes, flag, uid1, nb, rocprim::plus<int32_t>(), s);
+  }));
   glx_filter_zero_kernel<<<1, 1, 0, s>>>(soff);
   glx_filter_dedup_sub_kernel<<<row_blocks, 256, 0, s>>>(flag, uid1, perm, start, deg, f.values, same_value ? 1 : 0, batch,
                                                          sub_start, sub_deg, soff + 1, sub_val, run_begin);
@@ -789,9 +776,9 @@ int filtered_alias_dedup(const glx_graph* g, int sampler, const int64_t* d_rng, 
   GLX_HIP(hipMemcpyAsync(&U, uid1 + nb - 1, 4, hipMemcpyDeviceToHost, s));
   GLX_HIP(hipStreamSynchronize(s));
   const size_t nu = (size_t)U;
-#define SCANS(tmp, bytes) rocprim::inclusive_scan(tmp, bytes, soff + 1, soff + 1, nu, rocprim::plus<int64_t>(), s)
-  GLX_FILTER_PRIM(SCANS);
-#undef SCANS
+  GLX_TRY(glx_prim_leased(s, 3, "filtered dedup: scan the unique rows' degrees", [&](void* tmp, size_t& bytes) {
+    return rocprim::inclusive_scan(tmp, bytes, soff + 1, soff + 1, nu, rocprim::plus<int64_t>(), s);
+  }));
   std::vector<int64_t> h_soff(nu + 1);
   std::vector<int32_t> h_run(nu + 1);
   GLX_HIP(hipMemcpyAsync(h_soff.data(), soff, (nu + 1) * 8, hipMemcpyDeviceToHost, s));
@@ -899,14 +886,9 @@ int filtered_general(const glx_graph* g, int sampler, const int64_t* d_src, cons
   }
   glx_filter_rows_kernel<<<row_blocks, 256, 0, s>>>(ra, start, deg, soff + 1);
   glx_filter_zero_kernel<<<1, 1, 0, s>>>(soff);
-  {
-    size_t bytes = 0;
-    GLX_HIP(rocprim::inclusive_scan(nullptr, bytes, soff + 1, soff + 1, nb, rocprim::plus<int64_t>(), s));
-    GlxScratch tmp;
-    rc = tmp.alloc(bytes, s, 3);
-    if (rc != GLX_OK) return rc;
-    GLX_HIP(rocprim::inclusive_scan(tmp.p, bytes, soff + 1, soff + 1, nb, rocprim::plus<int64_t>(), s));
-  }
+  GLX_TRY(glx_prim_leased(s, 3, "filtered sampling: scan the request rows' degrees", [&](void* tmp, size_t& bytes) {
+    return rocprim::inclusive_scan(tmp, bytes, soff + 1, soff + 1, nb, rocprim::plus<int64_t>(), s);
+  }));
   std::vector<int64_t> h_soff(nb + 1);
   GLX_HIP(hipMemcpyAsync(h_soff.data(), soff, (nb + 1) * 8, hipMemcpyDeviceToHost, s));
   GLX_HIP(hipStreamSynchronize(s));

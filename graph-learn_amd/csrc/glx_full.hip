@@ -4,9 +4,7 @@
 //   * FullSampler (full_sampler.cc:28-97): ragged "all neighbours" response.
 #include <string.h>
 
-#include <rocprim/rocprim.hpp>
-
-#include "glx_common.h"
+#include "glx_prims.h"
 
 namespace {
 
@@ -32,16 +30,6 @@ inline unsigned grid_for(int64_t n) {
   if (b < 1) b = 1;
   return (unsigned)(b < 8192 ? b : 8192);
 }
-
-#define GLX_ROCPRIM(call)                                 \
-  do {                                                    \
-    size_t bytes__ = 0;                                   \
-    GLX_HIP(call(nullptr, bytes__));                      \
-    GlxTemp tmp__;                                        \
-    GLX_HIP(hipMalloc(&tmp__.p, bytes__ ? bytes__ : 16)); \
-    GLX_HIP(call(tmp__.p, bytes__));                      \
-    GLX_HIP(hipStreamSynchronize(s));                     \
-  } while (0)
 
 // ---- FullSampler ------------------------------------------------------------
 __global__ void glx_full_sizes_kernel(GlxIdMap map, const int64_t* __restrict__ row_ptr,
@@ -87,10 +75,9 @@ int full_sizes_device(const glx_graph* g, const int64_t* d_src, int32_t batch, i
   glx_full_sizes_kernel<<<(unsigned)((batch + 255) / 256), 256, 0, s>>>(g->map(), g->row_ptr, d_src, batch,
                                                                        max_limit, d_degrees, d_offsets + 1);
   glx_set_i64_kernel<<<1, 1, 0, s>>>(d_offsets, 0);
-#define SCAN(tmp, bytes) \
-  rocprim::inclusive_scan(tmp, bytes, d_offsets + 1, d_offsets + 1, (size_t)batch, rocprim::plus<int64_t>(), s)
-  GLX_ROCPRIM(SCAN);
-#undef SCAN
+  GLX_TRY(glx_prim_temp(s, "full sampler: scan the row sizes into offsets", [&](void* tmp, size_t& bytes) {
+    return rocprim::inclusive_scan(tmp, bytes, d_offsets + 1, d_offsets + 1, (size_t)batch, rocprim::plus<int64_t>(), s);
+  }));
   GLX_HIP(hipGetLastError());
   return GLX_OK;
 }
@@ -160,14 +147,13 @@ int glx_graph_dst_counts(const glx_graph* g, GlxTemp* uniq, GlxTemp* counts, int
   GLX_HIP(hipMalloc(&nruns.p, 8));
   if (E == 0) return GLX_OK;
   glx_extract_nbr_kernel<<<grid_for(E), 256, 0, s>>>(g->adj, E, keys.as<int64_t>());
-#define SORT(tmp, bytes) rocprim::radix_sort_keys(tmp, bytes, keys.as<int64_t>(), sorted.as<int64_t>(), n, 0, 64, s)
-  GLX_ROCPRIM(SORT);
-#undef SORT
-#define RLE(tmp, bytes)                                                                                    \
-  rocprim::run_length_encode(tmp, bytes, sorted.as<int64_t>(), n, uniq->as<int64_t>(), counts->as<int64_t>(), \
-                             nruns.as<int64_t>(), s)
-  GLX_ROCPRIM(RLE);
-#undef RLE
+  GLX_TRY(glx_prim_temp(s, "in-degree: sort the destination ids", [&](void* tmp, size_t& bytes) {
+    return rocprim::radix_sort_keys(tmp, bytes, keys.as<int64_t>(), sorted.as<int64_t>(), n, 0, 64, s);
+  }));
+  GLX_TRY(glx_prim_temp(s, "in-degree: run-length encode the sorted destination ids", [&](void* tmp, size_t& bytes) {
+    return rocprim::run_length_encode(tmp, bytes, sorted.as<int64_t>(), n, uniq->as<int64_t>(), counts->as<int64_t>(),
+                                      nruns.as<int64_t>(), s);
+  }));
   GLX_HIP(hipMemcpyAsync(U, nruns.p, 8, hipMemcpyDeviceToHost, s));
   GLX_HIP(hipStreamSynchronize(s));
   return GLX_OK;

@@ -13,13 +13,9 @@
 // retry schedule exactly: candidates come in blocks of `count` draws, rejected ones are
 // skipped, after three blocks the exclusion set is dropped (kRetryTimes = 3), and
 // accepted candidates keep their draw order.
-#include <string.h>  // rocprim's texture_cache_iterator uses memset
-
-#include <rocprim/rocprim.hpp>
-
 #include <vector>
 
-#include "glx_common.h"
+#include "glx_prims.h"
 
 struct glx_negative {
   int device;
@@ -29,16 +25,6 @@ struct glx_negative {
 };
 
 namespace {
-
-#define GLX_ROCPRIM(call)                                 \
-  do {                                                    \
-    size_t bytes__ = 0;                                   \
-    GLX_HIP(call(nullptr, bytes__));                      \
-    GlxTemp tmp__;                                        \
-    GLX_HIP(hipMalloc(&tmp__.p, bytes__ ? bytes__ : 16)); \
-    GLX_HIP(call(tmp__.p, bytes__));                      \
-    GLX_HIP(hipStreamSynchronize(s));                     \
-  } while (0)
 
 inline unsigned grid_for(int64_t n) { return (unsigned)((n + 255) / 256); }
 
@@ -266,25 +252,23 @@ extern "C" int glx_negative_from_graph(const glx_graph* g, int by_in_degree, voi
     GLX_HIP(hipMalloc(&nbr_s.p, n * 8));
     GLX_HIP(hipMalloc(&eid_s.p, n * 8));
     glx_neg_split_adj_kernel<<<grid_for(E), 256, 0, s>>>(g->adj, E, nbr.as<int64_t>(), eid.as<int64_t>());
-#define SORT1(tmp, bytes)                                                                                     \
-  rocprim::radix_sort_pairs(tmp, bytes, nbr.as<int64_t>(), nbr_s.as<int64_t>(), eid.as<int64_t>(), eid_s.as<int64_t>(), \
-                            n, 0, 64, s)
-    GLX_ROCPRIM(SORT1);
-#undef SORT1
+    GLX_TRY(glx_prim_temp(s, "negative table: sort edges by destination", [&](void* tmp, size_t& bytes) {
+      return rocprim::radix_sort_pairs(tmp, bytes, nbr.as<int64_t>(), nbr_s.as<int64_t>(), eid.as<int64_t>(),
+                                       eid_s.as<int64_t>(), n, 0, 64, s);
+    }));
     GLX_HIP(hipMalloc(&uniq.p, n * 8));
     GLX_HIP(hipMalloc(&first.p, n * 8));
     GLX_HIP(hipMalloc(&cnt.p, n * 8));
     GLX_HIP(hipMalloc(&nruns.p, 8));
-#define FIRST(tmp, bytes)                                                                                          \
-  rocprim::reduce_by_key(tmp, bytes, nbr_s.as<int64_t>(), eid_s.as<int64_t>(), n, uniq.as<int64_t>(), first.as<int64_t>(), \
-                         nruns.as<int64_t>(), MinOp(), rocprim::equal_to<int64_t>(), s)
-    GLX_ROCPRIM(FIRST);
-#undef FIRST
-#define RLE(tmp, bytes)                                                                                 \
-  rocprim::run_length_encode(tmp, bytes, nbr_s.as<int64_t>(), n, nbr.as<int64_t>(), cnt.as<int64_t>(), \
-                             nruns.as<int64_t>(), s)
-    GLX_ROCPRIM(RLE);  // nbr is scratch from here on
-#undef RLE
+    GLX_TRY(glx_prim_temp(s, "negative table: first edge id of every destination", [&](void* tmp, size_t& bytes) {
+      return rocprim::reduce_by_key(tmp, bytes, nbr_s.as<int64_t>(), eid_s.as<int64_t>(), n, uniq.as<int64_t>(),
+                                    first.as<int64_t>(), nruns.as<int64_t>(), MinOp(), rocprim::equal_to<int64_t>(), s);
+    }));
+    // nbr is scratch from here on
+    GLX_TRY(glx_prim_temp(s, "negative table: in-degree of every destination", [&](void* tmp, size_t& bytes) {
+      return rocprim::run_length_encode(tmp, bytes, nbr_s.as<int64_t>(), n, nbr.as<int64_t>(), cnt.as<int64_t>(),
+                                        nruns.as<int64_t>(), s);
+    }));
     int64_t U = 0;
     GLX_HIP(hipMemcpyAsync(&U, nruns.p, 8, hipMemcpyDeviceToHost, s));
     GLX_HIP(hipStreamSynchronize(s));
@@ -295,17 +279,15 @@ extern "C" int glx_negative_from_graph(const glx_graph* g, int by_in_degree, voi
     GLX_HIP(hipMalloc(&own.t->ids, (size_t)U * 8));
     GLX_HIP(hipMalloc(&key_out.p, (size_t)U * 8));
     GLX_HIP(hipMalloc(&cnt_o.p, (size_t)U * 8));
-#define SORT2(tmp, bytes)                                                                                   \
-  rocprim::radix_sort_pairs(tmp, bytes, first.as<int64_t>(), key_out.as<int64_t>(), uniq.as<int64_t>(), own.t->ids, \
-                            (size_t)U, 0, 64, s)
-    GLX_ROCPRIM(SORT2);
-#undef SORT2
+    GLX_TRY(glx_prim_temp(s, "negative table: order the ids by first appearance", [&](void* tmp, size_t& bytes) {
+      return rocprim::radix_sort_pairs(tmp, bytes, first.as<int64_t>(), key_out.as<int64_t>(), uniq.as<int64_t>(),
+                                       own.t->ids, (size_t)U, 0, 64, s);
+    }));
     if (by_in_degree) {
-#define SORT3(tmp, bytes)                                                                                        \
-  rocprim::radix_sort_pairs(tmp, bytes, first.as<int64_t>(), key_out.as<int64_t>(), cnt.as<int64_t>(), cnt_o.as<int64_t>(), \
-                            (size_t)U, 0, 64, s)
-      GLX_ROCPRIM(SORT3);
-#undef SORT3
+      GLX_TRY(glx_prim_temp(s, "negative table: order the in-degrees by first appearance", [&](void* tmp, size_t& bytes) {
+        return rocprim::radix_sort_pairs(tmp, bytes, first.as<int64_t>(), key_out.as<int64_t>(), cnt.as<int64_t>(),
+                                         cnt_o.as<int64_t>(), (size_t)U, 0, 64, s);
+      }));
       GlxTemp w;
       GLX_HIP(hipMalloc(&w.p, (size_t)U * 4));
       glx_neg_to_float_kernel<<<grid_for(U), 256, 0, s>>>(cnt_o.as<int64_t>(), U, w.as<float>());
@@ -383,11 +365,10 @@ extern "C" int glx_graph_enable_negative(glx_graph* g, void* stream) {
     glx_neg_iota_u32_kernel<<<grid_for(E), 256, 0, s>>>(iota.as<uint32_t>(), E);
     // every row's neighbour ids in ascending order, each with the CSR slot it sits in: the membership test of
     // strict negative sampling is a binary search, an id == value filter finds its hits the same way
-#define SEGSORT(tmp, bytes)                                                                                    \
-  rocprim::segmented_radix_sort_pairs(tmp, bytes, nbr.as<int64_t>(), sorted, iota.as<uint32_t>(), slots,    \
-                                      (unsigned int)E, (unsigned int)V, g->row_ptr, g->row_ptr + 1, 0, 64, s)
-    GLX_ROCPRIM(SEGSORT);
-#undef SEGSORT
+    GLX_TRY(glx_prim_temp(s, "sorted row index: sort every row's neighbour ids", [&](void* tmp, size_t& bytes) {
+      return rocprim::segmented_radix_sort_pairs(tmp, bytes, nbr.as<int64_t>(), sorted, iota.as<uint32_t>(), slots,
+                                                 (unsigned int)E, (unsigned int)V, g->row_ptr, g->row_ptr + 1, 0, 64, s);
+    }));
   }
   own2.p = nullptr;
   g->slot_sorted = slots;

@@ -17,9 +17,7 @@
 // reference's sizes: its response tensors are N^2 entries themselves).
 #include <string.h>
 
-#include <rocprim/rocprim.hpp>
-
-#include "glx_common.h"
+#include "glx_prims.h"
 
 namespace {
 
@@ -120,16 +118,6 @@ __global__ __launch_bounds__(256) void glx_sub_match_kernel(const int64_t* __res
   if (!FILL && lane == 0) counts[i] = 2 * done;
 }
 
-#define GLX_ROCPRIM_SUB(call)                              \
-  do {                                                     \
-    size_t bytes__ = 0;                                    \
-    GLX_HIP(call(nullptr, bytes__));                       \
-    GlxTemp tmp__;                                         \
-    GLX_HIP(hipMalloc(&tmp__.p, bytes__ ? bytes__ : 16));  \
-    GLX_HIP(call(tmp__.p, bytes__));                       \
-    GLX_HIP(hipStreamSynchronize(s));                      \
-  } while (0)
-
 int induce_device(const int64_t* d_nodes, int32_t n, const int64_t* d_off, const int64_t* d_nbr, const int64_t* d_eid,
                   int32_t* d_row, int32_t* d_col, int64_t* d_eout, int64_t capacity, int64_t* count_out, hipStream_t s) {
   GlxTemp caps, tab_off, counts, out_off, tab;
@@ -142,9 +130,10 @@ int induce_device(const int64_t* d_nodes, int32_t n, const int64_t* d_off, const
   const unsigned g1 = (unsigned)((n + 255) / 256);
   const unsigned gw = (unsigned)(((int64_t)n * 64 + 255) / 256);
   glx_sub_caps_kernel<<<g1, 256, 0, s>>>(d_off, n, caps.as<int64_t>());
-#define SCAN_C(tmp, bytes) rocprim::exclusive_scan(tmp, bytes, caps.as<int64_t>(), tab_off.as<int64_t>(), (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), s)
-  GLX_ROCPRIM_SUB(SCAN_C);
-#undef SCAN_C
+  GLX_TRY(glx_prim_temp(s, "sub-graph induce: scan the hash table capacities", [&](void* tmp, size_t& bytes) {
+    return rocprim::exclusive_scan(tmp, bytes, caps.as<int64_t>(), tab_off.as<int64_t>(), (int64_t)0, (size_t)n + 1,
+                                   rocprim::plus<int64_t>(), s);
+  }));
   int64_t total_slots = 0;
   GLX_HIP(hipMemcpyAsync(&total_slots, tab_off.as<int64_t>() + n, 8, hipMemcpyDeviceToHost, s));
   GLX_HIP(hipStreamSynchronize(s));
@@ -154,9 +143,10 @@ int induce_device(const int64_t* d_nodes, int32_t n, const int64_t* d_off, const
   glx_sub_build_kernel<<<gw, 256, 0, s>>>(d_off, d_nbr, n, tab_off.as<int64_t>(), tab.as<SubTab>());
   glx_sub_match_kernel<false><<<gw, 256, 0, s>>>(d_nodes, n, d_off, d_eid, tab_off.as<int64_t>(), tab.as<SubTab>(),
                                                  counts.as<int64_t>(), nullptr, nullptr, nullptr, nullptr, 0);
-#define SCAN_O(tmp, bytes) rocprim::exclusive_scan(tmp, bytes, counts.as<int64_t>(), out_off.as<int64_t>(), (int64_t)0, (size_t)n + 1, rocprim::plus<int64_t>(), s)
-  GLX_ROCPRIM_SUB(SCAN_O);
-#undef SCAN_O
+  GLX_TRY(glx_prim_temp(s, "sub-graph induce: scan the edge counts into output offsets", [&](void* tmp, size_t& bytes) {
+    return rocprim::exclusive_scan(tmp, bytes, counts.as<int64_t>(), out_off.as<int64_t>(), (int64_t)0, (size_t)n + 1,
+                                   rocprim::plus<int64_t>(), s);
+  }));
   int64_t total = 0;
   GLX_HIP(hipMemcpyAsync(&total, out_off.as<int64_t>() + n, 8, hipMemcpyDeviceToHost, s));
   GLX_HIP(hipStreamSynchronize(s));
