@@ -23,10 +23,23 @@
 // The workspace is the per-(thread, device, stream) arena; nothing is read back on the host between the launches.
 // The transpose (glx_agg_transpose, declared in glx_common.h) also serves the weighted reduce's row gradient
 // (glx_aggregate_weighted.hip).
+//
+// The CHUNKED order (glx_aggregate_backward_chunked) is a second, opt-in contract for the
+// same terms: a row's list is cut into chunks of GLX_COALESCE_CHUNK entries (entries, selected by a Max / Min arg or
+// not), a chunk's partial is +0.0f plus its terms in ascending position, and grad_x[r] is +0.0f plus the partials in
+// ascending chunk.  A list of at most one chunk's entries gets the default order's bits.  Three launches after the
+// transpose and a chunk directory built from row_ptr on the device (glx_agg_chunks: one scan, one search per work
+// item; nothing is read back):
+//   short    the per-row kernel above, which leaves the rows of more than one chunk alone
+//   chunk    one lane group per (long row, chunk) work item, the same walk into a float32 partial sum
+//   combine  one lane group per long row adds its partial sums in order and stores in grad_x's dtype
+// Every row is still written exactly once, and nothing proportional to [num_rows, dim] is allocated: the partial sums
+// take at most (num_ids / 128 + 1) * dim floats.
 #include <string.h>  // rocprim's texture_cache_iterator uses memset
 
 #include <rocprim/rocprim.hpp>
 
+#include "glx_prims.h"
 #include "glx_segment_lanes.h"
 
 namespace {
@@ -258,109 +271,118 @@ struct BwdArgs {
 };
 
 constexpr int kBwdU = 4;  // grad_out rows in flight per lane
+constexpr int kChunk = GLX_COALESCE_CHUNK;
 
-// G lanes own table row r; lane c owns columns [VEC c, VEC c + VEC) of each column tile of G * VEC columns.  Lane c
-// fetches list entry base + c (its position, that position's segment and, for Mean, the divisor) and every lane of
-// the group reads entry j from lane j: the group walks its list together, so the cross-lane reads stay inside a
-// group whose lanes all run the same iterations.  Every row is written, an empty list writes zeros.  The sum is
-// float32 whatever DT; a bfloat16 grad_x rounds the finished sum once, in the store (agg_store).
-template <int OP, int G, int VEC, int DT>
-__global__ __launch_bounds__(256) void glx_aggregate_bwd_kernel(BwdArgs a) {
-  typedef typename AggElem<DT>::raw raw_t;
+// The term of one list entry for the lane's VEC columns from `col` on: Sum g, Mean g / float(count), Max / Min g where
+// arg names the entry's position (an entry arg does not select adds nothing, and is still a list entry).
+template <int OP, int VEC>
+struct BwdTerm {
   typedef float vec_t __attribute__((ext_vector_type(VEC)));
   typedef int32_t ivec_t __attribute__((ext_vector_type(VEC)));
-  constexpr bool kArg = OP == GLX_AGG_MAX || OP == GLX_AGG_MIN;
+  static constexpr bool kArg = OP == GLX_AGG_MAX || OP == GLX_AGG_MIN;
+  static constexpr bool kDiv = OP == GLX_AGG_MEAN;
+  struct Loaded {
+    vec_t g;
+    ivec_t w;
+  };
+  const BwdArgs& a;
+  int32_t col;
+  // the RAW count, not seg_count: counts that promise more than the request has still divide by what they say
+  __device__ __forceinline__ float divisor(int32_t seg) const { return (float)(a.cnt ? a.cnt[seg] : a.fanout); }
+  __device__ __forceinline__ void load(Loaded* ld, int32_t, int32_t seg) const {
+    const int64_t at = (int64_t)seg * a.dim + col;
+    ld->g = *reinterpret_cast<const vec_t*>(a.grad_out + at);
+    if (kArg) ld->w = *reinterpret_cast<const ivec_t*>(a.arg + at);
+  }
+  __device__ __forceinline__ void fold(vec_t* acc, const Loaded& ld, int32_t p, float dv) const {
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+      if (kArg) {
+        if (ld.w[v] == p) (*acc)[v] = (*acc)[v] + ld.g[v];
+      } else if (kDiv) {
+        (*acc)[v] = (*acc)[v] + ld.g[v] / dv;
+      } else {
+        (*acc)[v] = (*acc)[v] + ld.g[v];
+      }
+    }
+  }
+};
+
+// G lanes own table row r and walk its whole list (glx_list_fold, glx_lane_groups.h): the ascending-position order.
+// Every row is written, an empty list writes zeros.  SHORT (the chunked order): a row of more than kChunk entries is
+// left to the chunk and combine kernels; every other row gets exactly what the default order gives it.
+template <int OP, int G, int VEC, int DT, bool SHORT>
+__global__ __launch_bounds__(256) void glx_aggregate_bwd_kernel(BwdArgs a) {
+  typedef typename AggElem<DT>::raw raw_t;
   const int64_t r = blockIdx.x * (int64_t)(256 / G) + threadIdx.x / G;
   const int c = threadIdx.x & (G - 1);
   if (r >= a.num_rows) return;  // whole groups leave
   const int32_t l0 = a.row_ptr[r], l1 = a.row_ptr[r + 1];
-  raw_t* const out = static_cast<raw_t*>(a.grad_x) + r * (int64_t)a.dim;
-  for (int32_t col_pass = 0; col_pass < a.dim; col_pass += G * VEC) {
-    const int32_t col = col_pass + c * VEC;
-    const bool col_ok = col < a.dim;
-    const int32_t col_ld = col_ok ? col : 0;  // lanes past the end re-read the first columns, unused
-    vec_t acc;
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) acc[v] = 0.0f;
-    for (int32_t base = l0; base < l1; base += G) {
-      int32_t my_pos = 0, my_seg = 0;
-      float my_div = 1.0f;
-      if (base + c < l1) {
-        my_pos = a.pos[base + c];
-        my_seg = a.seg_of ? a.seg_of[my_pos] : my_pos / a.fanout;
-        // the RAW count, not seg_count: counts that promise more than the request has still divide by what they say
-        if (OP == GLX_AGG_MEAN) my_div = (float)(a.cnt ? a.cnt[my_seg] : a.fanout);
-      }
-      const int32_t m = (l1 - base) < G ? (l1 - base) : G;
-      for (int32_t j = 0; j < m; j += kBwdU) {
-        int32_t p[kBwdU];
-        int64_t at[kBwdU];
-        float dv[kBwdU];
-#pragma unroll
-        for (int u = 0; u < kBwdU; ++u) {
-          const int src = (j + u) & (G - 1);
-          p[u] = __shfl(my_pos, src, G);
-          at[u] = (int64_t)__shfl(my_seg, src, G) * a.dim + col_ld;
-          dv[u] = OP == GLX_AGG_MEAN ? __shfl(my_div, src, G) : 1.0f;
-        }
-        vec_t g[kBwdU];
-        ivec_t w[kBwdU];
-#pragma unroll
-        for (int u = 0; u < kBwdU; ++u) {
-          if (j + u < m) {
-            g[u] = *reinterpret_cast<const vec_t*>(a.grad_out + at[u]);
-            if (kArg) w[u] = *reinterpret_cast<const ivec_t*>(a.arg + at[u]);
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < kBwdU; ++u) {
-          if (j + u < m) {
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) {
-              if (kArg) {
-                if (w[u][v] == p[u]) acc[v] = acc[v] + g[u][v];
-              } else if (OP == GLX_AGG_MEAN) {
-                acc[v] = acc[v] + g[u][v] / dv[u];
-              } else {
-                acc[v] = acc[v] + g[u][v];
-              }
-            }
-          }
-        }
-      }
-    }
-    if (col_ok) agg_store<DT, VEC>(out + col, acc);  // lanes past the last column store nothing
-  }
+  if (SHORT && l1 - l0 > kChunk) return;
+  const GlxPosList L = {a.pos, a.seg_of, a.fanout};
+  glx_list_fold<G, VEC, kBwdU, DT>(L, l0, l1, c, a.dim, static_cast<raw_t*>(a.grad_x) + r * (int64_t)a.dim,
+                                   [&](int32_t col) { return BwdTerm<OP, VEC>{a, col}; });
+}
+
+// G lanes own work item t of the chunk directory: chunk t - slot0[row] of a long row, at most kChunk entries, folded
+// by the same walk into the item's float32 partial sum.  The launch covers max_items; items past the directory's count
+// leave.
+template <int OP, int G, int VEC>
+__global__ __launch_bounds__(256) void glx_aggregate_bwd_chunk_kernel(BwdArgs a, GlxAggChunks ch) {
+  const int64_t t = blockIdx.x * (int64_t)(256 / G) + threadIdx.x / G;
+  const int c = threadIdx.x & (G - 1);
+  if (t >= ch.max_items || t >= ch.slot0[ch.num_rows]) return;  // whole groups leave
+  const int32_t r = ch.item_row[t];
+  const int32_t l0 = a.row_ptr[r] + ((int32_t)t - ch.slot0[r]) * kChunk, end = a.row_ptr[r + 1];
+  const int32_t l1 = end - l0 > kChunk ? l0 + kChunk : end;
+  const GlxPosList L = {a.pos, a.seg_of, a.fanout};
+  glx_list_fold<G, VEC, kBwdU, GLX_DTYPE_F32>(L, l0, l1, c, a.dim, ch.partial + t * (int64_t)a.dim,
+                                              [&](int32_t col) { return BwdTerm<OP, VEC>{a, col}; });
 }
 
 // the smallest group that covers a row in one tile; rows wider than 64 lanes take column tiles
 template <int OP, int VEC>
-void launch_bwd_vec(const BwdArgs& a, hipStream_t s) {
+void launch_bwd_vec(const BwdArgs& a, const GlxAggChunks* ch, hipStream_t s) {
   const int G = glx_group_for((a.dim + VEC - 1) / VEC);
   const unsigned blocks = (unsigned)((a.num_rows + (256 / G) - 1) / (256 / G));
   glx_for_group(G, [&](auto g) {
+    constexpr int kG = decltype(g)::value;
     glx_for_train_dtype(a.dtype, [&](auto t) {
-      glx_aggregate_bwd_kernel<OP, decltype(g)::value, VEC, decltype(t)::value><<<blocks, 256, 0, s>>>(a);
+      if (ch == nullptr) glx_aggregate_bwd_kernel<OP, kG, VEC, decltype(t)::value, false><<<blocks, 256, 0, s>>>(a);
+      else glx_aggregate_bwd_kernel<OP, kG, VEC, decltype(t)::value, true><<<blocks, 256, 0, s>>>(a);
     });
+    if (ch != nullptr) {
+      const unsigned cblocks = (unsigned)(((int64_t)ch->max_items + (256 / kG) - 1) / (256 / kG));
+      glx_aggregate_bwd_chunk_kernel<OP, kG, VEC><<<cblocks, 256, 0, s>>>(a, *ch);
+    }
   });
+  if (ch != nullptr) glx_agg_chunks_combine(*ch, a.grad_x, a.dtype, a.dim, VEC == 4, s);
 }
 
+// ch == nullptr: the default order; otherwise the chunked one over that directory
 template <int OP>
-void launch_bwd(const BwdArgs& a, hipStream_t s) {
+void launch_bwd(const BwdArgs& a, const GlxAggChunks* ch, hipStream_t s) {
   bool vec4 = a.dim % 4 == 0 && glx_aligned16(a.grad_out) && glx_aligned_vec4(a.grad_x, a.dtype);
   if (OP == GLX_AGG_MAX || OP == GLX_AGG_MIN) vec4 = vec4 && glx_aligned16(a.arg);
-  if (vec4) launch_bwd_vec<OP, 4>(a, s);
-  else launch_bwd_vec<OP, 1>(a, s);
+  if (vec4) launch_bwd_vec<OP, 4>(a, ch, s);
+  else launch_bwd_vec<OP, 1>(a, ch, s);
 }
 
 // Device pointers only, device selected; num_ids, num_segments, num_rows >= 1.
 int backward_device(int op, const int64_t* rows, const int32_t* cnt, const int32_t* arg, int32_t n, int32_t num_segments,
-                    int64_t num_rows, int32_t dim, const float* grad_out, void* grad_x, int grad_x_dtype,
+                    int64_t num_rows, int32_t dim, const float* grad_out, void* grad_x, int grad_x_dtype, bool chunked,
                     hipStream_t s) {
-  GlxScratch lease;
+  GlxScratch lease, chunk_lease;
   GlxAggTranspose t;
   int rc = glx_agg_transpose(rows, cnt, n, num_segments, num_rows, s, &lease, &t);
   if (rc != GLX_OK) return rc;
+  GlxAggChunks chunks;
+  const GlxAggChunks* ch = nullptr;
+  if (chunked) {
+    rc = glx_agg_chunks(t, n, num_rows, dim, s, &chunk_lease, &chunks);
+    if (rc != GLX_OK) return rc;
+    ch = &chunks;
+  }
   BwdArgs a;
   a.row_ptr = t.row_ptr;
   a.pos = t.pos;
@@ -374,16 +396,117 @@ int backward_device(int op, const int64_t* rows, const int32_t* cnt, const int32
   a.fanout = t.fanout;
   a.dtype = grad_x_dtype;
   switch (op) {
-    case GLX_AGG_SUM: launch_bwd<GLX_AGG_SUM>(a, s); break;
-    case GLX_AGG_MEAN: launch_bwd<GLX_AGG_MEAN>(a, s); break;
-    case GLX_AGG_MAX: launch_bwd<GLX_AGG_MAX>(a, s); break;
-    default: launch_bwd<GLX_AGG_MIN>(a, s); break;
+    case GLX_AGG_SUM: launch_bwd<GLX_AGG_SUM>(a, ch, s); break;
+    case GLX_AGG_MEAN: launch_bwd<GLX_AGG_MEAN>(a, ch, s); break;
+    case GLX_AGG_MAX: launch_bwd<GLX_AGG_MAX>(a, ch, s); break;
+    default: launch_bwd<GLX_AGG_MIN>(a, ch, s); break;
   }
   GLX_HIP(hipGetLastError());
   return GLX_OK;
 }
 
+// ---- the chunk directory and the combine pass of the chunked order ------------------------------------------
+// chunks of row r: ceil(entries / kChunk) for a list of more than kChunk entries, none otherwise (and none for the
+// extra element num_rows, which makes the exclusive scan end with the total)
+struct LongRowChunks {
+  const int32_t* row_ptr;
+  int64_t num_rows;
+  __device__ int32_t operator()(int64_t r) const {
+    if (r >= num_rows) return 0;
+    const int32_t len = row_ptr[r + 1] - row_ptr[r];
+    return len > kChunk ? (len + kChunk - 1) / kChunk : 0;
+  }
+};
+
+// work item t belongs to the last row whose first slot is at or below t (rows without chunks share their successor's)
+__global__ __launch_bounds__(256) void glx_bwd_chunk_items_kernel(const int32_t* __restrict__ slot0, int64_t num_rows,
+                                                                  int32_t max_items, int32_t* __restrict__ item_row) {
+  const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (t >= max_items || t >= slot0[num_rows]) return;
+  int64_t lo = 0, hi = num_rows;  // the first index whose slot0 exceeds t: slot0[num_rows] does
+  while (lo < hi) {
+    const int64_t mid = lo + ((hi - lo) >> 1);
+    if (slot0[mid] > t) hi = mid; else lo = mid + 1;
+  }
+  item_row[t] = (int32_t)(lo - 1);
+}
+
+// G lanes own work item t and leave unless it is the first of its row; lane c owns columns [VEC c, VEC c + VEC) of
+// each column tile.  kBwdU partial-sum loads are issued before the first is added.
+template <int G, int VEC, int DT>
+__global__ __launch_bounds__(256) void glx_bwd_chunk_combine_kernel(GlxAggChunks ch, void* grad_x, int32_t dim) {
+  typedef float vec_t __attribute__((ext_vector_type(VEC)));
+  typedef typename AggElem<DT>::raw raw_t;
+  const int64_t t = blockIdx.x * (int64_t)(256 / G) + threadIdx.x / G;
+  const int c = threadIdx.x & (G - 1);
+  if (t >= ch.max_items || t >= ch.slot0[ch.num_rows]) return;  // whole groups leave
+  const int32_t r = ch.item_row[t];
+  if (ch.slot0[r] != t) return;
+  const int32_t chunks = ch.slot0[r + 1] - (int32_t)t;
+  raw_t* const out = static_cast<raw_t*>(grad_x) + r * (int64_t)dim;
+  for (int32_t col = c * VEC; col < dim; col += G * VEC) {
+    vec_t acc;
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) acc[v] = 0.0f;
+    for (int32_t k = 0; k < chunks; k += kBwdU) {
+      vec_t val[kBwdU];
+#pragma unroll
+      for (int u = 0; u < kBwdU; ++u) {
+        if (k + u < chunks) val[u] = *reinterpret_cast<const vec_t*>(ch.partial + (t + k + u) * dim + col);
+      }
+#pragma unroll
+      for (int u = 0; u < kBwdU; ++u) {
+        if (k + u < chunks) {
+#pragma unroll
+          for (int v = 0; v < VEC; ++v) acc[v] = acc[v] + val[u][v];
+        }
+      }
+    }
+    agg_store<DT, VEC>(out + col, acc);
+  }
+}
+
 }  // namespace
+
+int glx_agg_chunks(const GlxAggTranspose& t, int32_t n, int64_t num_rows, int32_t dim, hipStream_t s, GlxScratch* lease,
+                   GlxAggChunks* out) {
+  const int32_t max_items = n / (kChunk / 2) + 1;
+  const size_t slot_b = glx_align256((size_t)(num_rows + 1) * sizeof(int32_t));
+  const size_t item_b = glx_align256((size_t)max_items * sizeof(int32_t));
+  const size_t part_b = (size_t)max_items * dim * sizeof(float);
+  int rc = lease->alloc(slot_b + item_b + part_b, s, 2);
+  if (rc != GLX_OK) return rc;
+  char* at = lease->as<char>();
+  int32_t* slot0 = reinterpret_cast<int32_t*>(at);
+  int32_t* item_row = reinterpret_cast<int32_t*>(at + slot_b);
+  const auto counts =
+      rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), LongRowChunks{t.row_ptr, num_rows});
+  GLX_TRY(glx_prim_leased(s, 3, "chunked row gradient: scan the long rows' chunk counts", [&](void* tmp, size_t& bytes) {
+    return rocprim::exclusive_scan(tmp, bytes, counts, slot0, (int32_t)0, (size_t)(num_rows + 1),
+                                   rocprim::plus<int32_t>(), s);
+  }));
+  glx_bwd_chunk_items_kernel<<<(unsigned)(((int64_t)max_items + 255) / 256), 256, 0, s>>>(slot0, num_rows, max_items,
+                                                                                           item_row);
+  out->slot0 = slot0;
+  out->item_row = item_row;
+  out->partial = reinterpret_cast<float*>(at + slot_b + item_b);
+  out->num_rows = num_rows;
+  out->max_items = max_items;
+  return GLX_OK;
+}
+
+void glx_agg_chunks_combine(const GlxAggChunks& ch, void* grad_x, int grad_x_dtype, int32_t dim, bool vec4,
+                            hipStream_t s) {
+  const int G = glx_group_for(vec4 ? dim / 4 : dim);
+  const unsigned blocks = (unsigned)(((int64_t)ch.max_items + (256 / G) - 1) / (256 / G));
+  glx_for_group(G, [&](auto g) {
+    glx_for_train_dtype(grad_x_dtype, [&](auto t) {
+      constexpr int kG = decltype(g)::value, kDT = decltype(t)::value;
+      if (vec4) glx_bwd_chunk_combine_kernel<kG, 4, kDT><<<blocks, 256, 0, s>>>(ch, grad_x, dim);
+      else glx_bwd_chunk_combine_kernel<kG, 1, kDT><<<blocks, 256, 0, s>>>(ch, grad_x, dim);
+    });
+  });
+}
 
 extern "C" int glx_aggregate_arg(const glx_features* f, int op, const int64_t* node_ids, const int32_t* segment_ids,
                                  int32_t num_ids, int32_t num_segments, float default_attr, float* emb_out,
@@ -435,11 +558,11 @@ extern "C" int glx_aggregate_arg(const glx_features* f, int op, const int64_t* n
   return st.finish(rc);
 }
 
-extern "C" int glx_aggregate_backward_ex(int device, int op, const int64_t* rows, const int32_t* cnt,
-                                         const int32_t* arg, int32_t num_ids, int32_t num_segments, int64_t num_rows,
-                                         int32_t dim, const float* grad_out, void* grad_x, int grad_x_dtype,
-                                         int ptr_kind, void* stream) {
-  GLX_REQUIRE_TRAIN_DTYPE(grad_x_dtype, "glx_aggregate_backward_ex: grad_x_dtype");
+// the body of glx_aggregate_backward_ex and glx_aggregate_backward_chunked, which have checked grad_x_dtype
+static int aggregate_backward(int device, int op, const int64_t* rows, const int32_t* cnt, const int32_t* arg,
+                              int32_t num_ids, int32_t num_segments, int64_t num_rows, int32_t dim,
+                              const float* grad_out, void* grad_x, int grad_x_dtype, bool chunked, int ptr_kind,
+                              void* stream) {
   GLX_REQUIRE(op >= GLX_AGG_SUM && op <= GLX_AGG_PROD, "unknown aggregator id %d", op);
   GLX_REQUIRE(op != GLX_AGG_PROD, "the Prod aggregator has no backward (its gradient divides by the element)");
   GLX_REQUIRE(num_ids >= 0 && num_segments >= 0 && num_rows >= 0, "negative sizes");
@@ -473,10 +596,28 @@ extern "C" int glx_aggregate_backward_ex(int device, int op, const int64_t* rows
       rc = glx_zero_elems_async(d_gx, (size_t)num_rows * dim, grad_x_dtype, st.s);
     } else {
       rc = backward_device(op, d_rows, d_cnt, d_arg, num_ids, num_segments, num_rows, dim, d_go, d_gx, grad_x_dtype,
-                           st.s);
+                           chunked, st.s);
     }
   }
   return st.finish(rc);
+}
+
+extern "C" int glx_aggregate_backward_ex(int device, int op, const int64_t* rows, const int32_t* cnt,
+                                         const int32_t* arg, int32_t num_ids, int32_t num_segments, int64_t num_rows,
+                                         int32_t dim, const float* grad_out, void* grad_x, int grad_x_dtype,
+                                         int ptr_kind, void* stream) {
+  GLX_REQUIRE_TRAIN_DTYPE(grad_x_dtype, "glx_aggregate_backward_ex: grad_x_dtype");
+  return aggregate_backward(device, op, rows, cnt, arg, num_ids, num_segments, num_rows, dim, grad_out, grad_x,
+                            grad_x_dtype, false, ptr_kind, stream);
+}
+
+extern "C" int glx_aggregate_backward_chunked(int device, int op, const int64_t* rows, const int32_t* cnt,
+                                              const int32_t* arg, int32_t num_ids, int32_t num_segments,
+                                              int64_t num_rows, int32_t dim, const float* grad_out, void* grad_x,
+                                              int grad_x_dtype, int ptr_kind, void* stream) {
+  GLX_REQUIRE_TRAIN_DTYPE(grad_x_dtype, "glx_aggregate_backward_chunked: grad_x_dtype");
+  return aggregate_backward(device, op, rows, cnt, arg, num_ids, num_segments, num_rows, dim, grad_out, grad_x,
+                            grad_x_dtype, true, ptr_kind, stream);
 }
 
 extern "C" int glx_aggregate_backward(int device, int op, const int64_t* rows, const int32_t* cnt, const int32_t* arg,

@@ -15,6 +15,10 @@
 //                a fixed lane-to-column mapping and a fixed cross-lane tree -- the same bits on every run, but the order
 //                over the columns is the mapping's, so this one is checked against a bound, not bit for bit
 // No float atomics anywhere.
+//   grad_x, chunked  (glx_aggregate_weighted_backward_x_chunked; K5-bwd-chunked) the same terms in a second, opt-in
+//                order: chunks of GLX_COALESCE_CHUNK list entries, a chunk's partial +0.0f plus its terms in ascending
+//                p, grad_x[r] +0.0f plus the partials in ascending chunk.  The directory and the combine pass are
+//                glx_aggregate_grad.hip's (glx_agg_chunks, glx_agg_chunks_combine).
 //
 // x is float32 or bfloat16 (the _ex entry points).  A bfloat16 x is upcast as it is loaded -- exact --
 // and folded exactly as above, so emb and grad_w stay float32 and equal the float32 call on the upcast matrix bit for
@@ -143,88 +147,90 @@ struct WBwdXArgs {
   int32_t dim, heads, C;
 };
 
-// The sibling of glx_aggregate_bwd_kernel (glx_aggregate_grad.hip) that also fetches the weight of each list entry:
-// G lanes own table row r, lane c fetches list entry base + c (its position, that position's segment and, for Mean,
-// the divisor), every lane reads entry j from lane j.  Every row is written, an empty list writes zeros.  The sum is
-// float32 whatever DT; a bfloat16 grad_x rounds the finished sum once, in the store (agg_store).
-template <int OP, int G, int VEC, int DT>
-__global__ __launch_bounds__(256) void glx_aggregate_weighted_bwd_x_kernel(WBwdXArgs a) {
+// The term of one list entry for the lane's VEC columns from `col` on (one head: VEC = 4 only when C % 4 == 0):
+// fmul_rn(w[p, head], t), t = g (Sum) or g / float(count) (Mean), added through glx_fold_rn -- two roundings.
+template <int OP, int VEC>
+struct WBwdXTerm {
   typedef float vec_t __attribute__((ext_vector_type(VEC)));
+  static constexpr bool kDiv = OP == GLX_AGG_MEAN;
+  struct Loaded {
+    vec_t g;
+    float wt;
+  };
+  const WBwdXArgs& a;
+  int32_t col, head;
+  __device__ __forceinline__ float divisor(int32_t seg) const { return (float)seg_count(a.seg, seg); }
+  __device__ __forceinline__ void load(Loaded* ld, int32_t p, int32_t seg) const {
+    ld->g = *reinterpret_cast<const vec_t*>(a.grad_out + ((int64_t)seg * a.dim + col));
+    ld->wt = a.w[(int64_t)p * a.heads + head];
+  }
+  __device__ __forceinline__ void fold(vec_t* acc, const Loaded& ld, int32_t, float dv) const {
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+      const float t = kDiv ? ld.g[v] / dv : ld.g[v];
+      (*acc)[v] = glx_fold_rn((*acc)[v], ld.wt, t);
+    }
+  }
+};
+
+// The sibling of glx_aggregate_bwd_kernel (glx_aggregate_grad.hip) whose term also fetches the weight of each list
+// entry: G lanes own table row r and walk its whole list (glx_list_fold, glx_lane_groups.h).  Every row is written,
+// an empty list writes zeros.  SHORT (the chunked order): a row of more than GLX_COALESCE_CHUNK entries is left to the
+// chunk and combine kernels.
+template <int OP, int G, int VEC, int DT, bool SHORT>
+__global__ __launch_bounds__(256) void glx_aggregate_weighted_bwd_x_kernel(WBwdXArgs a) {
   typedef typename AggElem<DT>::raw raw_t;
   const int64_t r = blockIdx.x * (int64_t)(256 / G) + threadIdx.x / G;
   const int c = threadIdx.x & (G - 1);
   if (r >= a.num_rows) return;  // whole groups leave
   const int32_t l0 = a.t.row_ptr[r], l1 = a.t.row_ptr[r + 1];
-  raw_t* const out = static_cast<raw_t*>(a.grad_x) + r * (int64_t)a.dim;
-  for (int32_t col_pass = 0; col_pass < a.dim; col_pass += G * VEC) {
-    const int32_t col = col_pass + c * VEC;
-    const bool col_ok = col < a.dim;
-    const int32_t col_ld = col_ok ? col : 0;  // lanes past the end re-read the first columns, unused
-    const int32_t head = col_ld / a.C;
-    vec_t acc;
-#pragma unroll
-    for (int v = 0; v < VEC; ++v) acc[v] = 0.0f;
-    for (int32_t base = l0; base < l1; base += G) {
-      int32_t my_pos = 0, my_seg = 0;
-      float my_div = 1.0f;
-      if (base + c < l1) {
-        my_pos = a.t.pos[base + c];
-        my_seg = a.t.seg_of ? a.t.seg_of[my_pos] : my_pos / a.t.fanout;
-        if (OP == GLX_AGG_MEAN) my_div = (float)seg_count(a.seg, my_seg);
-      }
-      const int32_t m = (l1 - base) < G ? (l1 - base) : G;
-      for (int32_t j = 0; j < m; j += kWU) {
-        int64_t at[kWU], wat[kWU];
-        float dv[kWU];
-#pragma unroll
-        for (int u = 0; u < kWU; ++u) {
-          const int src = (j + u) & (G - 1);
-          wat[u] = (int64_t)__shfl(my_pos, src, G) * a.heads + head;
-          at[u] = (int64_t)__shfl(my_seg, src, G) * a.dim + col_ld;
-          dv[u] = OP == GLX_AGG_MEAN ? __shfl(my_div, src, G) : 1.0f;
-        }
-        vec_t g[kWU];
-        float wt[kWU];
-#pragma unroll
-        for (int u = 0; u < kWU; ++u) {
-          if (j + u < m) {
-            g[u] = *reinterpret_cast<const vec_t*>(a.grad_out + at[u]);
-            wt[u] = a.w[wat[u]];
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < kWU; ++u) {
-          if (j + u < m) {
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) {
-              const float t = OP == GLX_AGG_MEAN ? g[u][v] / dv[u] : g[u][v];
-              acc[v] = glx_fold_rn(acc[v], wt[u], t);
-            }
-          }
-        }
-      }
-    }
-    if (col_ok) agg_store<DT, VEC>(out + col, acc);  // lanes past the last column store nothing
-  }
+  if (SHORT && l1 - l0 > GLX_COALESCE_CHUNK) return;
+  const GlxPosList L = {a.t.pos, a.t.seg_of, a.t.fanout};
+  glx_list_fold<G, VEC, kWU, DT>(L, l0, l1, c, a.dim, static_cast<raw_t*>(a.grad_x) + r * (int64_t)a.dim,
+                                 [&](int32_t col) { return WBwdXTerm<OP, VEC>{a, col, col / a.C}; });
+}
+
+// G lanes own work item t of the chunk directory: one chunk of a long row, folded by the same walk into the item's
+// float32 partial sum.  The launch covers max_items; items past the directory's count leave.
+template <int OP, int G, int VEC>
+__global__ __launch_bounds__(256) void glx_aggregate_weighted_bwd_x_chunk_kernel(WBwdXArgs a, GlxAggChunks ch) {
+  const int64_t t = blockIdx.x * (int64_t)(256 / G) + threadIdx.x / G;
+  const int c = threadIdx.x & (G - 1);
+  if (t >= ch.max_items || t >= ch.slot0[ch.num_rows]) return;  // whole groups leave
+  const int32_t r = ch.item_row[t];
+  const int32_t l0 = a.t.row_ptr[r] + ((int32_t)t - ch.slot0[r]) * GLX_COALESCE_CHUNK, end = a.t.row_ptr[r + 1];
+  const int32_t l1 = end - l0 > GLX_COALESCE_CHUNK ? l0 + GLX_COALESCE_CHUNK : end;
+  const GlxPosList L = {a.t.pos, a.t.seg_of, a.t.fanout};
+  glx_list_fold<G, VEC, kWU, GLX_DTYPE_F32>(L, l0, l1, c, a.dim, ch.partial + t * (int64_t)a.dim,
+                                            [&](int32_t col) { return WBwdXTerm<OP, VEC>{a, col, col / a.C}; });
 }
 
 template <int OP, int VEC>
-void launch_wbwd_x_vec(const WBwdXArgs& a, hipStream_t s) {
+void launch_wbwd_x_vec(const WBwdXArgs& a, const GlxAggChunks* ch, hipStream_t s) {
   const int G = glx_group_for((a.dim + VEC - 1) / VEC);
   const unsigned blocks = (unsigned)((a.num_rows + (256 / G) - 1) / (256 / G));
   glx_for_group(G, [&](auto g) {
+    constexpr int kG = decltype(g)::value;
     glx_for_train_dtype(a.dtype, [&](auto t) {
-      glx_aggregate_weighted_bwd_x_kernel<OP, decltype(g)::value, VEC, decltype(t)::value><<<blocks, 256, 0, s>>>(a);
+      constexpr int kDT = decltype(t)::value;
+      if (ch == nullptr) glx_aggregate_weighted_bwd_x_kernel<OP, kG, VEC, kDT, false><<<blocks, 256, 0, s>>>(a);
+      else glx_aggregate_weighted_bwd_x_kernel<OP, kG, VEC, kDT, true><<<blocks, 256, 0, s>>>(a);
     });
+    if (ch != nullptr) {
+      const unsigned cblocks = (unsigned)(((int64_t)ch->max_items + (256 / kG) - 1) / (256 / kG));
+      glx_aggregate_weighted_bwd_x_chunk_kernel<OP, kG, VEC><<<cblocks, 256, 0, s>>>(a, *ch);
+    }
   });
+  if (ch != nullptr) glx_agg_chunks_combine(*ch, a.grad_x, a.dtype, a.dim, VEC == 4, s);
 }
 
+// ch == nullptr: the default order; otherwise the chunked one over that directory
 template <int OP>
-void launch_wbwd_x(const WBwdXArgs& a, hipStream_t s) {
+void launch_wbwd_x(const WBwdXArgs& a, const GlxAggChunks* ch, hipStream_t s) {
   const bool vec4 =
       a.dim % 4 == 0 && a.C % 4 == 0 && glx_aligned16(a.grad_out) && glx_aligned_vec4(a.grad_x, a.dtype);
-  if (vec4) launch_wbwd_x_vec<OP, 4>(a, s);
-  else launch_wbwd_x_vec<OP, 1>(a, s);
+  if (vec4) launch_wbwd_x_vec<OP, 4>(a, ch, s);
+  else launch_wbwd_x_vec<OP, 1>(a, ch, s);
 }
 
 // ---- gradient with respect to the weights ---------------------------------------------------------------------
@@ -290,9 +296,17 @@ void launch_wbwd_w(const WBwdWArgs& a, hipStream_t s) {
 
 // grad_x of a request whose transpose the caller holds (device pointers, op Sum or Mean): the body of
 // glx_aggregate_weighted_backward_x, and the two row gradients of glx_dot_attention_backward on one transpose
-void glx_weighted_bwd_x(int op, const GlxAggTranspose& t, const float* w, const float* grad_out, void* grad_x,
-                        int64_t num_rows, int32_t dim, int32_t heads, int32_t num_ids, int32_t num_segments,
-                        hipStream_t s, int grad_x_dtype) {
+int glx_weighted_bwd_x(int op, const GlxAggTranspose& t, const float* w, const float* grad_out, void* grad_x,
+                       int64_t num_rows, int32_t dim, int32_t heads, int32_t num_ids, int32_t num_segments,
+                       hipStream_t s, int grad_x_dtype, bool chunked) {
+  GlxScratch chunk_lease;  // ends on return: the launches below are queued by then
+  GlxAggChunks chunks;
+  const GlxAggChunks* ch = nullptr;
+  if (chunked) {
+    const int rc = glx_agg_chunks(t, num_ids, num_rows, dim, s, &chunk_lease, &chunks);
+    if (rc != GLX_OK) return rc;
+    ch = &chunks;
+  }
   WBwdXArgs a;
   a.t = t;
   a.w = w;
@@ -304,8 +318,9 @@ void glx_weighted_bwd_x(int op, const GlxAggTranspose& t, const float* w, const 
   a.heads = heads;
   a.C = dim / heads;
   a.seg = glx_seg_layout_of(t, num_ids, num_segments);
-  if (op == GLX_AGG_SUM) launch_wbwd_x<GLX_AGG_SUM>(a, s);
-  else launch_wbwd_x<GLX_AGG_MEAN>(a, s);
+  if (op == GLX_AGG_SUM) launch_wbwd_x<GLX_AGG_SUM>(a, ch, s);
+  else launch_wbwd_x<GLX_AGG_MEAN>(a, ch, s);
+  return GLX_OK;
 }
 
 // what the three entry points check alike, before any device use
@@ -369,12 +384,12 @@ extern "C" int glx_aggregate_weighted(int device, int op, const float* x, int64_
                                    num_segments, default_attr, emb_out, ptr_kind, stream);
 }
 
-extern "C" int glx_aggregate_weighted_backward_x_ex(int device, int op, const int64_t* rows, const float* w,
-                                                    int32_t heads, const int32_t* cnt, int32_t num_ids,
-                                                    int32_t num_segments, int64_t num_rows, int32_t dim,
-                                                    const float* grad_out, void* grad_x, int grad_x_dtype,
-                                                    int ptr_kind, void* stream) {
-  GLX_REQUIRE_TRAIN_DTYPE(grad_x_dtype, "glx_aggregate_weighted_backward_x_ex: grad_x_dtype");
+// the body of glx_aggregate_weighted_backward_x_ex and glx_aggregate_weighted_backward_x_chunked, which have checked
+// grad_x_dtype
+static int weighted_backward_x(int device, int op, const int64_t* rows, const float* w, int32_t heads,
+                               const int32_t* cnt, int32_t num_ids, int32_t num_segments, int64_t num_rows,
+                               int32_t dim, const float* grad_out, void* grad_x, int grad_x_dtype, bool chunked,
+                               int ptr_kind, void* stream) {
   GLX_WEIGHTED_REQUIRE("glx_aggregate_weighted_backward_x");
   GLX_REQUIRE(num_ids == 0 || rows != nullptr, "rows is NULL");
   GLX_REQUIRE(num_ids == 0 || w != nullptr, "w is NULL");
@@ -402,12 +417,32 @@ extern "C" int glx_aggregate_weighted_backward_x_ex(int device, int op, const in
     } else {
       rc = glx_agg_transpose(d_rows, cnt ? d_cnt : nullptr, num_ids, num_segments, num_rows, st.s, &lease, &a.t);
       if (rc == GLX_OK) {
-        glx_weighted_bwd_x(op, a.t, a.w, a.grad_out, a.grad_x, num_rows, dim, heads, num_ids, num_segments, st.s,
-                           grad_x_dtype);
+        rc = glx_weighted_bwd_x(op, a.t, a.w, a.grad_out, a.grad_x, num_rows, dim, heads, num_ids, num_segments, st.s,
+                                grad_x_dtype, chunked);
       }
     }
   }
   return st.finish(rc);
+}
+
+extern "C" int glx_aggregate_weighted_backward_x_ex(int device, int op, const int64_t* rows, const float* w,
+                                                    int32_t heads, const int32_t* cnt, int32_t num_ids,
+                                                    int32_t num_segments, int64_t num_rows, int32_t dim,
+                                                    const float* grad_out, void* grad_x, int grad_x_dtype,
+                                                    int ptr_kind, void* stream) {
+  GLX_REQUIRE_TRAIN_DTYPE(grad_x_dtype, "glx_aggregate_weighted_backward_x_ex: grad_x_dtype");
+  return weighted_backward_x(device, op, rows, w, heads, cnt, num_ids, num_segments, num_rows, dim, grad_out, grad_x,
+                             grad_x_dtype, false, ptr_kind, stream);
+}
+
+extern "C" int glx_aggregate_weighted_backward_x_chunked(int device, int op, const int64_t* rows, const float* w,
+                                                         int32_t heads, const int32_t* cnt, int32_t num_ids,
+                                                         int32_t num_segments, int64_t num_rows, int32_t dim,
+                                                         const float* grad_out, void* grad_x, int grad_x_dtype,
+                                                         int ptr_kind, void* stream) {
+  GLX_REQUIRE_TRAIN_DTYPE(grad_x_dtype, "glx_aggregate_weighted_backward_x_chunked: grad_x_dtype");
+  return weighted_backward_x(device, op, rows, w, heads, cnt, num_ids, num_segments, num_rows, dim, grad_out, grad_x,
+                             grad_x_dtype, true, ptr_kind, stream);
 }
 
 extern "C" int glx_aggregate_weighted_backward_x(int device, int op, const int64_t* rows, const float* w, int32_t heads,

@@ -50,6 +50,71 @@ __device__ __forceinline__ float glx_fold_rn(float acc, float w, float x) {
   return acc + glx_pin(w * x);  // the product is rounded, pinned, and the sum rounded again
 }
 
+// The list walk of the row gradients (glx_aggregate_grad.hip, glx_aggregate_weighted.hip): a group of G lanes (lane c)
+// folds entries [l0, l1) of a transposed list -- a whole row's list in the default order, one chunk of it in the chunked
+// order -- into out[0 .. dim), which holds DT elements.  Lane c owns columns [VEC c, VEC c + VEC) of each column tile
+// of G * VEC columns.  It fetches list entry base + c (its position, that position's segment and, where the term
+// divides, the divisor) and every lane of the group reads entry j from lane j: the group walks its list together, so
+// the cross-lane reads stay inside a group whose lanes all run the same iterations.  U term loads are issued before the
+// first is folded.  The sum starts at +0.0f and is float32 whatever DT; a bfloat16 `out` rounds the finished sum once,
+// in the store (agg_store).  An empty list writes zeros.
+// term_of(col) makes the term of one column tile (col: the lane's first column, 0 for a lane past the last one):
+//   TERM::kDiv                    does the term divide (Mean)?
+//   divisor(seg)                  the divisor of an entry of segment seg, fetched once per entry
+//   load(&ld, p, seg)             issues the loads of entry (position p, segment seg) into a TERM::Loaded
+//   fold(&acc, ld, p, dv)         adds the entry's term to the VEC accumulators, in one rounding per add
+struct GlxPosList {
+  const int32_t* pos;     // request positions by (row, position): GlxAggTranspose's
+  const int32_t* seg_of;  // segment of a position, or nullptr: position / fanout
+  int32_t fanout;
+};
+
+template <int G, int VEC, int U, int DT, typename TERM_OF>
+__device__ __forceinline__ void glx_list_fold(const GlxPosList& L, int32_t l0, int32_t l1, int c, int32_t dim,
+                                              typename AggElem<DT>::raw* out, TERM_OF&& term_of) {
+  typedef float vec_t __attribute__((ext_vector_type(VEC)));
+  for (int32_t col_pass = 0; col_pass < dim; col_pass += G * VEC) {
+    const int32_t col = col_pass + c * VEC;
+    const bool col_ok = col < dim;
+    const auto term = term_of(col_ok ? col : 0);  // lanes past the end re-read the first columns, unused
+    typedef typename std::remove_const<decltype(term)>::type TERM;
+    vec_t acc;
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) acc[v] = 0.0f;
+    for (int32_t base = l0; base < l1; base += G) {
+      int32_t my_pos = 0, my_seg = 0;
+      float my_div = 1.0f;
+      if (base + c < l1) {
+        my_pos = L.pos[base + c];
+        my_seg = L.seg_of ? L.seg_of[my_pos] : my_pos / L.fanout;
+        if (TERM::kDiv) my_div = term.divisor(my_seg);
+      }
+      const int32_t m = (l1 - base) < G ? (l1 - base) : G;
+      for (int32_t j = 0; j < m; j += U) {
+        int32_t p[U], sg[U];
+        float dv[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int src = (j + u) & (G - 1);
+          p[u] = __shfl(my_pos, src, G);
+          sg[u] = __shfl(my_seg, src, G);
+          dv[u] = TERM::kDiv ? __shfl(my_div, src, G) : 1.0f;
+        }
+        typename TERM::Loaded ld[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          if (j + u < m) term.load(&ld[u], p[u], sg[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          if (j + u < m) term.fold(&acc, ld[u], p[u], dv[u]);
+        }
+      }
+    }
+    if (col_ok) agg_store<DT, VEC>(out + col, acc);  // lanes past the last column store nothing
+  }
+}
+
 // A gathered row of a table of DT elements (float32, or bfloat16 upcast exactly as it is loaded); an index outside the
 // table reads a row of default_attr instead (ok == false: `at` is never read).
 template <int DT>

@@ -58,6 +58,7 @@ EXPORTS = [
     "glx_pair_dot", "glx_pair_dot_backward",
     "glx_aggregate_backward_ex", "glx_aggregate_weighted_ex", "glx_aggregate_weighted_backward_x_ex",
     "glx_aggregate_weighted_backward_w_ex", "glx_pair_dot_ex", "glx_pair_dot_backward_ex",
+    "glx_aggregate_backward_chunked", "glx_aggregate_weighted_backward_x_chunked",
     "glx_rows_coalesce", "glx_embedding_update",
     "glx_tgn_store_update", "glx_tgn_message", "glx_tgn_message_backward", "glx_tgn_memory_write",
     "glx_partition", "glx_stitch_i64", "glx_stitch_f32", "glx_aggregate_stitch",
@@ -211,6 +212,9 @@ def lib():
         L.glx_pair_dot_ex.argtypes = [ci, vp, i64, vp, i64, ci, i32, i32, vp, vp, i32, i32, f32, vp, ci, vp]
         L.glx_pair_dot_backward_ex.argtypes = [ci, ci, vp, vp, i32, i32, vp, i32, vp, i64, i32, i64, f32, vp, ci, ci,
                                                vp]
+        # the chunked order of the two row gradients: their _ex siblings' arguments
+        L.glx_aggregate_backward_chunked.argtypes = L.glx_aggregate_backward_ex.argtypes
+        L.glx_aggregate_weighted_backward_x_chunked.argtypes = L.glx_aggregate_weighted_backward_x_ex.argtypes
         L.glx_rows_coalesce.argtypes =[ci, vp, i32, i64, i32, vp, vp, vp, vp, ci, vp]
         L.glx_embedding_update.argtypes = [ci, ci, vp, vp, vp, i64, i32, vp, vp, i32, f32, f32, f32, f32, f32, f32, vp]
         L.glx_tgn_store_update.argtypes = [ci, i64, i32, vp, vp, vp, vp, i32, i64, vp, vp, vp, vp, vp]
@@ -1053,7 +1057,8 @@ def _train_out(out, out_dtype, like, shape, what):
     return res, res, out_dtype
 
 
-def aggregate_backward(op, rows, cnt, grad_out, num_rows, arg=None, out=None, device=0, out_dtype="float32"):
+def aggregate_backward(op, rows, cnt, grad_out, num_rows, arg=None, out=None, device=0, out_dtype="float32",
+                       chunked=False):
     """Gradient of Features.aggregate with respect to the rows of a [num_rows, D] table with dense ids
     (glx_aggregate_backward_ex) -> grad_x[num_rows, D], every row written (rows nobody references: zeros).
     rows[n] int64: the request's ids; cnt[num_segments] int32: the counts the forward returned (None: the implied
@@ -1062,6 +1067,12 @@ def aggregate_backward(op, rows, cnt, grad_out, num_rows, arg=None, out=None, de
     atomic is used: the same inputs give the same bits on every run.  Prod raises (its gradient divides by the element).
     out_dtype "float32" or "bfloat16" (out=: the buffer's own dtype): a bfloat16 grad_x is the float32 gradient rounded
     once per element, to nearest even (a torch bfloat16 tensor on the device, numpy uint16 codes on the host).
+    chunked=True (glx_aggregate_backward_chunked) sums the same terms in the CHUNKED order instead: a row's list of
+    positions is cut into chunks of COALESCE_CHUNK (256) entries -- entries, whether a Max / Min arg selects them or
+    not -- each chunk is summed from +0.0 in ascending position by its own lane group, and the row is +0.0 plus the
+    partial sums in ascending chunk.  A row referenced at most 256 times gets the default bits; Sum equals rows_coalesce
+    of the gathered grad_out rows; still no atomics and the same bits on every call, a bfloat16 grad_x still rounded
+    once.  For requests in which a few hub rows take a large share of the positions.
     Torch CUDA tensors are device pointers on the current stream, numpy arrays host pointers."""
     if isinstance(op, str):
         op = AGGREGATOR_IDS[op]
@@ -1072,8 +1083,9 @@ def aggregate_backward(op, rows, cnt, grad_out, num_rows, arg=None, out=None, de
     kind = _kind(pr, pc, pa, pg, px)
     if kind == PTR_DEVICE:
         device = grad_x.device.index or 0
-    _check(lib().glx_aggregate_backward_ex(device, op, pr[0], pc[0], pa[0], n, num_segments, num_rows, dim, pg[0], px[0],
-                                           TRAIN_DTYPES[name], kind, _stream(kind, device)))
+    entry = lib().glx_aggregate_backward_chunked if chunked else lib().glx_aggregate_backward_ex
+    _check(entry(device, op, pr[0], pc[0], pa[0], n, num_segments, num_rows, dim, pg[0], px[0], TRAIN_DTYPES[name], kind,
+                 _stream(kind, device)))
     return grad_x
 
 
@@ -1118,11 +1130,15 @@ def aggregate_weighted(op, x, rows, w, num_segments, cnt=None, default_attr=0.0,
     return emb
 
 
-def aggregate_weighted_backward_x(op, rows, w, cnt, grad_out, num_rows, out=None, device=0, out_dtype="float32"):
+def aggregate_weighted_backward_x(op, rows, w, cnt, grad_out, num_rows, out=None, device=0, out_dtype="float32",
+                                  chunked=False):
     """Gradient of aggregate_weighted with respect to the rows (glx_aggregate_weighted_backward_x_ex) ->
     grad_x[num_rows, D], every row written.  aggregate_backward's contract with one more factor: each element adds
     fmul(w[p, head], term) in float32 in ascending request position, no float atomic: the same bits on every run.
-    out_dtype / out= as in aggregate_backward: a bfloat16 grad_x is the float32 gradient rounded once per element."""
+    out_dtype / out= as in aggregate_backward: a bfloat16 grad_x is the float32 gradient rounded once per element.
+    chunked=True (glx_aggregate_weighted_backward_x_chunked): aggregate_backward's chunked order over the same
+    two-rounding terms -- chunks of 256 list entries summed apart, partial sums added in chunk order; a row referenced
+    at most 256 times gets the default bits."""
     if isinstance(op, str):
         op = AGGREGATOR_IDS[op]
     n = int(rows.shape[0])
@@ -1133,9 +1149,9 @@ def aggregate_weighted_backward_x(op, rows, w, cnt, grad_out, num_rows, out=None
     kind = _kind(pr, pw, pc, pg, px)
     if kind == PTR_DEVICE:
         device = grad_x.device.index or 0
-    _check(lib().glx_aggregate_weighted_backward_x_ex(device, op, pr[0], pw[0], heads, pc[0], n, num_segments, num_rows,
-                                                      dim, pg[0], px[0], TRAIN_DTYPES[name], kind,
-                                                      _stream(kind, device)))
+    entry = lib().glx_aggregate_weighted_backward_x_chunked if chunked else lib().glx_aggregate_weighted_backward_x_ex
+    _check(entry(device, op, pr[0], pw[0], heads, pc[0], n, num_segments, num_rows, dim, pg[0], px[0],
+                 TRAIN_DTYPES[name], kind, _stream(kind, device)))
     return grad_x
 
 

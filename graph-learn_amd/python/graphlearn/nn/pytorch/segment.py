@@ -54,6 +54,14 @@ K sampled negatives,
 
 without the two [n, D] gathers of `(z[src].unsqueeze(1) * z[neg]).sum(-1)` and without their index_add_ backwards.
 
+Hub rows.  By default one lane group adds all the terms of a row, in ascending position; a row that thousands of
+positions name -- the hubs an EdgeWeight sampler keeps drawing -- makes the whole backward wait for that one walk.
+segment_aggregate, gather_rows and weighted_segment_aggregate take chunked_grad=True to sum x.grad in the CHUNKED order
+instead (glx_aggregate_backward_chunked, glx_aggregate_weighted_backward_x_chunked): chunks of 256 of a row's positions
+are summed apart, each from +0.0 in ascending position, and the partial sums are added in chunk order.  As
+deterministic as the default, the default's bits for every row named at most 256 times, other bits beyond; forward
+outputs do not depend on the flag.  pair_dot, gat_attention and dot_attention have no such flag.
+
 bfloat16.  Under torch.autocast("cuda", dtype=torch.bfloat16) `z = relu(enc(x))` is bfloat16, and segment_aggregate,
 gather_rows, weighted_segment_aggregate and pair_dot take it as it is -- inside autocast or outside, they go by the
 dtype they are handed.  Every row is upcast exactly as it is loaded and everything else is the float32 arithmetic in the
@@ -110,8 +118,9 @@ def _no_double_backward(who):
 class _SegmentAggregate(torch.autograd.Function):
 
   @staticmethod
-  def forward(ctx, x, index, segment_ids, num_segments, op, default_attr):
+  def forward(ctx, x, index, segment_ids, num_segments, op, default_attr, chunked_grad):
     glx = _glx()
+    ctx.chunked = chunked_grad  # selects the backward entry point only
     feats = glx.Features(x.detach(), view=True, device=x.device.index or 0)
     arg = None
     if op in (glx.MAX, glx.MIN):
@@ -134,11 +143,11 @@ class _SegmentAggregate(torch.autograd.Function):
     grad = grad.to(torch.float32).contiguous()
     # x.grad in x's own dtype straight from the kernel: no float32 [N, D] gradient exists for a bfloat16 x
     gx = _glx().aggregate_backward(ctx.op, index, None if ctx.implied else cnt, grad, ctx.num_rows, arg=arg,
-                                   out_dtype=ctx.x_dtype)
-    return gx, None, None, None, None, None
+                                   out_dtype=ctx.x_dtype, chunked=ctx.chunked)
+    return gx, None, None, None, None, None, None
 
 
-def segment_aggregate(x, index, num_segments, op="mean", segment_ids=None, default_attr=0.0):
+def segment_aggregate(x, index, num_segments, op="mean", segment_ids=None, default_attr=0.0, chunked_grad=False):
   """[num_segments, D]: segment s reduces the rows x[index[p]] of its positions p with `op` ("sum", "mean", "max",
   "min"; "prod" only for an x that needs no gradient), exactly as glx.Features(x, view=True).aggregate does -- the
   engine's tuned reduce, left to right, bit-identical on every run.
@@ -151,6 +160,11 @@ def segment_aggregate(x, index, num_segments, op="mean", segment_ids=None, defau
   segment_ids  None: num_segments equal segments of index.numel() / num_segments consecutive positions (a dense
                sampler response); or an int32 tensor like index, consumed with the reference's cursor rule
                (non-decreasing ids in [0, num_segments); everything behind the first violation is ignored)
+  chunked_grad False: x.grad adds its terms in ascending request position.  True: the CHUNKED order
+               (glx_aggregate_backward_chunked) -- a row's positions are cut into chunks of 256, each chunk summed from
+               +0.0 by its own lane group, the partial sums added in chunk order: as deterministic, other bits for a
+               row referenced more than 256 times, the same bits otherwise.  For batches with hub rows.  The forward
+               does not depend on it
   Empty segments are `default_attr` and pass no gradient on.  Anything else raises ValueError.
   """
   _check_inputs(x, index, "segment_aggregate")
@@ -176,16 +190,17 @@ def segment_aggregate(x, index, num_segments, op="mean", segment_ids=None, defau
     glx = _glx()
     feats = glx.Features(x.detach(), view=True, device=x.device.index or 0)
     return feats.aggregate(glx.PROD, index, segment_ids, num_segments, float(default_attr))[0]
-  return _SegmentAggregate.apply(x, index, segment_ids, num_segments, _OPS[op], float(default_attr))
+  return _SegmentAggregate.apply(x, index, segment_ids, num_segments, _OPS[op], float(default_attr),
+                                 bool(chunked_grad))
 
 
 class _GatherRows(torch.autograd.Function):
 
   @staticmethod
-  def forward(ctx, x, index, default_attr):
+  def forward(ctx, x, index, default_attr, chunked_grad):
     glx = _glx()
     out = glx.Features(x.detach(), view=True, device=x.device.index or 0).lookup(index, default_attr)
-    ctx.num_rows, ctx.x_dtype = int(x.shape[0]), _dtype_name(x)
+    ctx.num_rows, ctx.x_dtype, ctx.chunked = int(x.shape[0]), _dtype_name(x), chunked_grad
     ctx.save_for_backward(index)
     return out
 
@@ -196,28 +211,32 @@ class _GatherRows(torch.autograd.Function):
     glx = _glx()
     grad = grad.to(torch.float32).contiguous()
     # one position per segment: the Sum backward of the implied layout
-    return glx.aggregate_backward(glx.SUM, index, None, grad, ctx.num_rows, out_dtype=ctx.x_dtype), None, None
+    gx = glx.aggregate_backward(glx.SUM, index, None, grad, ctx.num_rows, out_dtype=ctx.x_dtype, chunked=ctx.chunked)
+    return gx, None, None, None
 
 
-def gather_rows(x, index, default_attr=0.0):
+def gather_rows(x, index, default_attr=0.0, chunked_grad=False):
   """x[index] as [*index.shape, D] -- the engine's lookup going forward, the deterministic Sum backward (one position
   per segment) going back: the replacement for `z[local[h]]` whose backward is index_add_ with float atomics.  A value
   of index outside [0, N) reads a row of `default_attr` and receives no gradient.  x is float32 or bfloat16; the rows
-  come back as float32 (a bfloat16 x: upcast exactly), x.grad has x's dtype."""
+  come back as float32 (a bfloat16 x: upcast exactly), x.grad has x's dtype.  chunked_grad=True sums x.grad in
+  segment_aggregate's chunked order (a row gathered more than 256 times: partial sums of 256 positions each, added in
+  order -- the bits of glx.rows_coalesce); the rows that come back do not depend on it."""
   _check_inputs(x, index, "gather_rows")
   shape = tuple(index.shape)
-  out = _GatherRows.apply(x, index.reshape(-1).contiguous(), float(default_attr))
+  out = _GatherRows.apply(x, index.reshape(-1).contiguous(), float(default_attr), bool(chunked_grad))
   return out.reshape(shape + (int(x.shape[1]),))
 
 
 class _WeightedSegmentAggregate(torch.autograd.Function):
 
   @staticmethod
-  def forward(ctx, x, index, weights, counts, num_segments, op, default_attr):
+  def forward(ctx, x, index, weights, counts, num_segments, op, default_attr, chunked_grad):
     glx = _glx()
     xd, wd = x.detach(), weights.detach()
     emb = glx.aggregate_weighted(op, xd, index, wd, num_segments, cnt=counts, default_attr=default_attr)
     ctx.op, ctx.default_attr, ctx.has_counts = op, default_attr, counts is not None
+    ctx.chunked = chunked_grad  # selects the row gradient's entry point only
     ctx.save_for_backward(*([xd, index, wd] + ([counts] if counts is not None else [])))
     return emb
 
@@ -231,13 +250,15 @@ class _WeightedSegmentAggregate(torch.autograd.Function):
     grad = grad.to(torch.float32).contiguous()
     gx = gw = None
     if ctx.needs_input_grad[0]:
-      gx = glx.aggregate_weighted_backward_x(ctx.op, index, w, counts, grad, int(x.shape[0]), out_dtype=_dtype_name(x))
+      gx = glx.aggregate_weighted_backward_x(ctx.op, index, w, counts, grad, int(x.shape[0]), out_dtype=_dtype_name(x),
+                                             chunked=ctx.chunked)
     if ctx.needs_input_grad[2]:
       gw = glx.aggregate_weighted_backward_w(ctx.op, x, index, int(w.shape[1]), counts, grad, ctx.default_attr)
-    return gx, None, gw, None, None, None, None
+    return gx, None, gw, None, None, None, None, None
 
 
-def weighted_segment_aggregate(x, index, weights, num_segments, op="sum", counts=None, default_attr=0.0):
+def weighted_segment_aggregate(x, index, weights, num_segments, op="sum", counts=None, default_attr=0.0,
+                               chunked_grad=False):
   """[num_segments, D]: segment s is the weighted "sum" or "mean" of the rows x[index[p]] of its positions p, each row
   scaled per head by weights[p] before it is added -- fadd(acc, fmul(w, x)) left to right, bit-identical on every run.
 
@@ -252,6 +273,8 @@ def weighted_segment_aggregate(x, index, weights, num_segments, op="sum", counts
   counts   None: num_segments equal segments of n / num_segments consecutive positions (a dense sampler response); or
            an int32 [num_segments] tensor: segment s is the next counts[s] positions, positions from counts.sum() on are
            ignored and get a zero weight gradient
+  chunked_grad  True: x.grad sums its terms in segment_aggregate's chunked order
+           (glx_aggregate_weighted_backward_x_chunked); the result and the weights' gradient do not depend on it
   Empty segments are `default_attr` and pass no gradient on.  Anything else raises ValueError.
   """
   who = "weighted_segment_aggregate"
@@ -284,7 +307,7 @@ def weighted_segment_aggregate(x, index, weights, num_segments, op="sum", counts
   if num_segments * D > 2 ** 31 - 1 or n * heads > 2 ** 31 - 1:
     raise ValueError("{}: num_segments * D or n * H exceeds int32".format(who))
   out = _WeightedSegmentAggregate.apply(x, index, weights.reshape(n, heads).contiguous(), counts, num_segments,
-                                        _OPS[op], float(default_attr))
+                                        _OPS[op], float(default_attr), bool(chunked_grad))
   return out
 
 

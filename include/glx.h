@@ -50,7 +50,8 @@ extern "C" {
  * glx_knn_ivfpq_destroy; float8 feature tables -- GLX_DTYPE_F8E4M3, GLX_DTYPE_F8E5M2, glx_features_convert_host;
  * the bfloat16 training path -- glx_aggregate_backward_ex, glx_aggregate_weighted_ex,
  * glx_aggregate_weighted_backward_x_ex, glx_aggregate_weighted_backward_w_ex, glx_pair_dot_ex,
- * glx_pair_dot_backward_ex. */
+ * glx_pair_dot_backward_ex; chunked row gradients -- glx_aggregate_backward_chunked,
+ * glx_aggregate_weighted_backward_x_chunked. */
 #define GLX_ABI_VERSION 5
 
 /* Exported symbols: libglx.so is built with -fvisibility=hidden. */
@@ -981,6 +982,48 @@ GLX_API int glx_rows_coalesce(int device, const int64_t* rows, int32_t n, int64_
 GLX_API int glx_embedding_update(int device, int algo, float* W, float* state1, float* state2, int64_t num_rows,
                                  int32_t dim, const int64_t* urows, const float* ug, int32_t n, float alpha, float eps,
                                  float beta1, float c1, float beta2, float c2, void* stream);
+
+/* ---- chunked row gradients (K5-bwd-chunked): a second, named summation order for the row gradients of the
+ * differentiable segment reductions under the reference's layers (python/nn/tf/layers/sage_conv.py:69-73,
+ * gcn_conv.py:52-73, gat_conv.py:96-110, ego_gat_conv.py:98-103), for requests in which a few rows -- the hubs an
+ * EdgeWeight sampler keeps drawing -- are referenced far more often than the rest. ----------------------------------
+ * glx_aggregate_backward_chunked takes glx_aggregate_backward_ex's arguments, glx_aggregate_weighted_backward_x_chunked
+ * those of glx_aggregate_weighted_backward_x_ex, with the same checks in the same order (grad_x_dtype first, before any
+ * device use; GLX_DTYPE_F32 or GLX_DTYPE_BF16), the same segment layouts, host and device pointers.  The _ex entry
+ * points and their float32 siblings are untouched: the ascending-position order stays the default, and this one is
+ * chosen per call.
+ *
+ * The list of table row r is the consumed, in-range request positions p_0 < p_1 < ... with rows[p] == r.  An entry that
+ * a Max / Min arg does not select is still a list entry: chunk boundaries count ENTRIES, not selected terms.  The list
+ * is cut into chunks of GLX_COALESCE_CHUNK consecutive entries.  The TERMS are exactly the default order's:
+ * grad_out[s(p), c] (Sum); grad_out[s(p), c] / float(cnt[s(p)]) (Mean, the raw count as in glx_aggregate_backward);
+ * grad_out[s(p), c] where arg[s(p), c] == p and no add otherwise (Max / Min); fmul_rn(w[p, head(c)], t) with t the Sum
+ * or Mean term and count(s) as in glx_aggregate_weighted_backward_x (weighted: two roundings, never an FMA).
+ *     partial_k[c]  = +0.0f, then one fadd_rn per selected term of chunk k, in ascending p
+ *     grad_x[r, c]  = +0.0f, then one fadd_rn per partial, in ascending k
+ * Consequences: a row whose list has at most GLX_COALESCE_CHUNK entries gets the default order's bits; for Sum the
+ * result equals glx_rows_coalesce applied to g[p] = grad_out[s(p)] over the consumed positions, bit for bit; EVERY row
+ * of grad_x is written, exactly once; a row nobody references is all bits clear; no float atomics; the same inputs give
+ * the same bits on every call.  A bfloat16 grad_x: partials and the combine are float32 and the finished sum is rounded
+ * ONCE, in the final store -- the float32 chunked result pushed through the converter of the _ex entry points -- and no
+ * float32 [num_rows, dim] buffer is allocated.
+ * (The transpose of glx_aggregate_backward; a chunk directory built on the device from its row offsets -- one scan, one
+ * search per work item; one lane group per short row, one per chunk of a long row, one per long row to combine.  The
+ * number of long rows and of chunks never reaches the host: no read-back, no synchronisation.  A list of L >
+ * GLX_COALESCE_CHUNK entries has fewer than L / 128 chunks, so the partial sums take at most (num_ids / 128 + 1) * dim
+ * floats of the calling thread's workspace, beside the transpose.)
+ * Still summed by one lane group per list, in ascending position: glx_pair_dot_backward, grad_t of
+ * glx_gat_attention_backward, grad_k / grad_v of glx_dot_attention_backward (and its long segments); Prod has no
+ * backward; the distributed store has none either; request plans (graph capture) do not cover the backward. */
+GLX_API int glx_aggregate_backward_chunked(int device, int op, const int64_t* rows, const int32_t* cnt,
+                                           const int32_t* arg, int32_t num_ids, int32_t num_segments, int64_t num_rows,
+                                           int32_t dim, const float* grad_out, void* grad_x, int grad_x_dtype,
+                                           int ptr_kind, void* stream);
+GLX_API int glx_aggregate_weighted_backward_x_chunked(int device, int op, const int64_t* rows, const float* w,
+                                                      int32_t heads, const int32_t* cnt, int32_t num_ids,
+                                                      int32_t num_segments, int64_t num_rows, int32_t dim,
+                                                      const float* grad_out, void* grad_x, int grad_x_dtype,
+                                                      int ptr_kind, void* stream);
 
 /* ---- TGN memory: the device-resident message store, the fused message and the memory write of the memory module the
  * reference's TGN example takes from torch_geometric -- TGNMemory(num_nodes, msg_dim, memory_dim, time_dim,
