@@ -23,8 +23,28 @@
 // One lane group per segment, of any length: a hub segment is walked by its one group.  EVERY element of every output
 // that is asked for is written; a position that is not consumed gets +0.0f, an empty segment +0.0f in every column.
 // No float atomics: the lane mapping and the trees are fixed, so the same inputs give the same bits on every call.
+//
+// The CHUNKED order (K5-dot-attn-chunked: glx_dot_attention_chunked, glx_dot_attention_backward_chunked; opt-in).  A
+// segment of more than GLX_COALESCE_CHUNK = 256 positions is LONG and is cut into chunks of 256 positions; every other
+// segment goes through the kernels above, restricted to short segments, and keeps the default order's bits.  A chunk
+// directory over the SEGMENTS is built on the device (dot_chunk_dir: one scan, one search per work item, as
+// glx_agg_chunks does over rows); neither the number of long segments nor of chunks reaches the host.  Then, per
+// direction:
+//   pass       one lane group per chunk: the dot products of its positions (the logits' / ga_raw), by the default
+//              order's own dot_pass, so logit_out has the default's bits
+//   normalise  one workgroup per long segment (SmBlockWalker): the softmax / its gradient in a fixed tree over the
+//              256 threads -- the definition, exact rules and bound of K5-sm, other bits than one lane group's tree
+//   fold       one lane group per chunk: partial_j = +0.0f, then the chunk's terms in ascending p (backward: grad_q's
+//              terms, and the chunk's rows of grad_edge)
+//   combine    one lane group per long segment: +0.0f, then one fadd_rn per partial in ascending j
+//              (glx_agg_chunks_combine)
+// A chunk's passes meet across kernel boundaries; inside a kernel a group still lies in one wavefront.  The launches
+// cover num_ids / 128 + 1 work items (a long segment of L positions has fewer than L / 128 chunks) and the partial sums
+// take that many rows of dim floats; idle work items leave when the directory says so.  grad_k / grad_v are the
+// chunked row gradient as it stands (glx_weighted_bwd_x, chunked).
 #include <math.h>
 
+#include "glx_prims.h"
 #include "glx_segment_lanes.h"
 
 // Two roundings per term of the folds: glx_fold_rn (glx_lane_groups.h) pins the product; the pragma is for the front
@@ -34,6 +54,7 @@
 namespace {
 
 constexpr int kWU = 4;  // row loads in flight per lane
+constexpr int kChunk = GLX_COALESCE_CHUNK;  // the chunked order: positions of a long segment to a chunk
 
 struct DotArgs {
   const float* q;          // [num_segments, dim]
@@ -181,20 +202,123 @@ __device__ __forceinline__ void dot_zero_tail(const GlxSegLayout& seg, float* p,
   for (int64_t i = first; i < end; i += gridDim.x * 256LL) p[i] = 0.0f;
 }
 
+// dst[0 .. dim) = +0.0f, then fadd_rn(., fmul_rn(w[p, h], vv(p)[c])) over positions [s0, s1) in ascending p: lane c
+// owns columns [VEC c, VEC c + VEC) of each column tile of G * VEC columns.  The walk is repeated per column tile: for
+// dim > G * VEC (512 columns at float4, or 100 read float by float) the rows indices, their shuffles and the alpha
+// loads are repeated per tile -- [n, H]-sized traffic, small beside the rows, and one tile at the tested and measured
+// shapes (dim <= 256 at float4).  An empty range writes +0.0f.
+template <int G, int VEC>
+__device__ __forceinline__ void dot_fold_out(const DotArgs& a, int32_t s0, int32_t s1, int c, float* dst) {
+  typedef float vec_t __attribute__((ext_vector_type(VEC)));
+  for (int32_t col_pass = 0; col_pass < a.dim; col_pass += G * VEC) {
+    const int32_t col = col_pass + c * VEC;
+    const bool col_ok = col < a.dim;
+    const int32_t col_ld = col_ok ? col : 0;  // lanes past the end re-read the first columns, unused
+    const int32_t head = col_ld / a.C;
+    vec_t acc;
+#pragma unroll
+    for (int t = 0; t < VEC; ++t) acc[t] = 0.0f;
+    for (int32_t base = s0; base < s1; base += G) {
+      const int32_t my_row = dot_my_row(a, base + c, s1);
+      const int32_t m = (s1 - base) < G ? (s1 - base) : G;
+      for (int32_t j = 0; j < m; j += kWU) {
+        int32_t row[kWU];
+#pragma unroll
+        for (int u = 0; u < kWU; ++u) row[u] = __shfl(my_row, (j + u) & (G - 1), G);
+        vec_t val[kWU];
+        float wt[kWU];
+#pragma unroll
+        for (int u = 0; u < kWU; ++u) {
+          if (j + u < m) {
+            wt[u] = a.w[(int64_t)(base + j + u) * a.heads + head];
+            val[u] = dot_row_vec<VEC>(a, a.v, row[u], base + j + u, col_ld);
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < kWU; ++u) {
+          if (j + u < m) {
+#pragma unroll
+            for (int t = 0; t < VEC; ++t) acc[t] = glx_fold_rn(acc[t], wt[u], val[u][t]);
+          }
+        }
+      }
+    }
+    if (col_ok) *reinterpret_cast<vec_t*>(dst + col) = acc;  // an empty range: +0.0f
+  }
+}
+
+// One pass over kk(p), p = s0 .. s1 of segment sg: gq[0 .. dim) (unless nullptr) = +0.0f, then
+// fadd_rn(., fmul_rn(grad_e[p, h], kk(p)[c])) in ascending p, and the rows [s0, s1) of grad_edge when it is asked for.
+// dot_fold_out's lane mapping.
+template <int G, int VEC>
+__device__ __forceinline__ void dot_fold_back(const DotArgs& a, int64_t sg, int32_t s0, int32_t s1, int c, float* gq) {
+  typedef float vec_t __attribute__((ext_vector_type(VEC)));
+  const float* const go = a.grad_out + sg * (int64_t)a.dim;
+  const float* const qr = a.q + sg * (int64_t)a.dim;
+  for (int32_t col_pass = 0; col_pass < a.dim; col_pass += G * VEC) {
+    const int32_t col = col_pass + c * VEC;
+    const bool col_ok = col < a.dim;
+    const int32_t col_ld = col_ok ? col : 0;  // lanes past the end re-read the first columns, unused
+    const int32_t head = col_ld / a.C;
+    const vec_t qv = *reinterpret_cast<const vec_t*>(qr + col_ld);
+    const vec_t gov = *reinterpret_cast<const vec_t*>(go + col_ld);
+    vec_t acc;
+#pragma unroll
+    for (int t = 0; t < VEC; ++t) acc[t] = 0.0f;
+    for (int32_t base = s0; base < s1; base += G) {
+      const int32_t my_row = gq ? dot_my_row(a, base + c, s1) : -1;
+      const int32_t m = (s1 - base) < G ? (s1 - base) : G;
+      for (int32_t j = 0; j < m; j += kWU) {
+        int32_t row[kWU];
+#pragma unroll
+        for (int u = 0; u < kWU; ++u) row[u] = __shfl(my_row, (j + u) & (G - 1), G);
+        vec_t val[kWU];
+        float ge[kWU], al[kWU];
+#pragma unroll
+        for (int u = 0; u < kWU; ++u) {
+          if (j + u < m) {
+            const int64_t at = (int64_t)(base + j + u) * a.heads + head;
+            ge[u] = a.grad_e[at];
+            if (a.grad_edge) al[u] = a.w[at];
+            if (gq) val[u] = dot_row_vec<VEC>(a, a.k, row[u], base + j + u, col_ld);
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < kWU; ++u) {
+          if (j + u < m) {
+            if (gq) {
+#pragma unroll
+              for (int t = 0; t < VEC; ++t) acc[t] = glx_fold_rn(acc[t], ge[u], val[u][t]);
+            }
+            if (a.grad_edge && col_ok) {
+              vec_t d;
+#pragma unroll
+              for (int t = 0; t < VEC; ++t) d[t] = glx_pin(ge[u] * qv[t]) + glx_pin(al[u] * gov[t]);
+              *reinterpret_cast<vec_t*>(a.grad_edge + (base + j + u) * (int64_t)a.dim + col) = d;
+            }
+          }
+        }
+      }
+    }
+    if (gq && col_ok) *reinterpret_cast<vec_t*>(gq + col) = acc;
+  }
+}
+
 // G lanes own one segment, a workgroup 256 / G consecutive segments.  Three passes, each by the whole group: the
 // logits (one glx_head_dots per position over q and kk), the normalisation, and glx_aggregate_weighted's fold over
-// alpha and vv -- lane c owns columns [VEC c, VEC c + VEC) of each column tile of G * VEC columns.  The fold walks the
-// whole segment once per column tile: for dim > G * VEC (512 columns at float4, or 100 read float by float) the rows
-// indices, their shuffles and the alpha loads are repeated per tile -- [n, H]-sized traffic, small beside the rows, and
-// one tile at the tested and measured shapes (dim <= 256 at float4).
-template <int G, int VEC, bool SUB>
+// alpha and vv (dot_fold_out).  SHORT (the chunked order): a segment of more than kChunk positions is left to the chunk
+// kernels below; every other segment gets exactly what the default order gives it.
+template <int G, int VEC, bool SUB, bool SHORT>
 __global__ __launch_bounds__(256) void glx_dot_attention_kernel(DotArgs a) {
-  typedef float vec_t __attribute__((ext_vector_type(VEC)));
   const int64_t sg = blockIdx.x * (int64_t)(256 / G) + threadIdx.x / G;
   const int c = threadIdx.x & (G - 1);
-  if (sg < a.seg.num_segments) {  // the same answer in every lane of the group
-    int32_t s0, s1;
+  int32_t s0 = 0, s1 = 0;
+  bool mine = sg < a.seg.num_segments;  // the same answer in every lane of the group
+  if (mine) {
     seg_bounds(a.seg, sg, &s0, &s1);
+    if (SHORT) mine = s1 - s0 <= kChunk;
+  }
+  if (mine) {
     if (s1 > s0) {
       float* const lg = a.logit ? a.logit : a.soft_out;
       dot_pass<G, VEC, SUB>(a, a.q + sg * (int64_t)a.dim, a.k, s0, s1, c, lg);
@@ -202,121 +326,161 @@ __global__ __launch_bounds__(256) void glx_dot_attention_kernel(DotArgs a) {
       dot_normalise<G, false>(a, s0, s1, c, lg);
       dot_handoff<G>();
     }
-    float* const out = a.out + sg * (int64_t)a.dim;
-    for (int32_t col_pass = 0; col_pass < a.dim; col_pass += G * VEC) {
-      const int32_t col = col_pass + c * VEC;
-      const bool col_ok = col < a.dim;
-      const int32_t col_ld = col_ok ? col : 0;  // lanes past the end re-read the first columns, unused
-      const int32_t head = col_ld / a.C;
-      vec_t acc;
-#pragma unroll
-      for (int t = 0; t < VEC; ++t) acc[t] = 0.0f;
-      for (int32_t base = s0; base < s1; base += G) {
-        const int32_t my_row = dot_my_row(a, base + c, s1);
-        const int32_t m = (s1 - base) < G ? (s1 - base) : G;
-        for (int32_t j = 0; j < m; j += kWU) {
-          int32_t row[kWU];
-#pragma unroll
-          for (int u = 0; u < kWU; ++u) row[u] = __shfl(my_row, (j + u) & (G - 1), G);
-          vec_t val[kWU];
-          float wt[kWU];
-#pragma unroll
-          for (int u = 0; u < kWU; ++u) {
-            if (j + u < m) {
-              wt[u] = a.w[(int64_t)(base + j + u) * a.heads + head];
-              val[u] = dot_row_vec<VEC>(a, a.v, row[u], base + j + u, col_ld);
-            }
-          }
-#pragma unroll
-          for (int u = 0; u < kWU; ++u) {
-            if (j + u < m) {
-#pragma unroll
-              for (int t = 0; t < VEC; ++t) acc[t] = glx_fold_rn(acc[t], wt[u], val[u][t]);
-            }
-          }
-        }
-      }
-      if (col_ok) *reinterpret_cast<vec_t*>(out + col) = acc;  // an empty segment: +0.0f
-    }
+    dot_fold_out<G, VEC>(a, s0, s1, c, a.out + sg * (int64_t)a.dim);
   }
   dot_zero_tail(a.seg, a.logit, a.heads);
   dot_zero_tail(a.seg, a.soft_out, a.heads);
 }
 
 // The same mapping going back: ga_raw (one glx_head_dots per position over grad_out and vv, parked in grad_e), the
-// softmax gradient in a fixed tree, then one pass over kk that folds grad_q and writes the rows of grad_edge.
-template <int G, int VEC, bool SUB>
+// softmax gradient in a fixed tree, then one pass over kk that folds grad_q and writes the rows of grad_edge
+// (dot_fold_back).  SHORT as above.
+template <int G, int VEC, bool SUB, bool SHORT>
 __global__ __launch_bounds__(256) void glx_dot_attention_bwd_kernel(DotArgs a) {
-  typedef float vec_t __attribute__((ext_vector_type(VEC)));
   const int64_t sg = blockIdx.x * (int64_t)(256 / G) + threadIdx.x / G;
   const int c = threadIdx.x & (G - 1);
-  if (sg < a.seg.num_segments) {  // the same answer in every lane of the group
-    int32_t s0, s1;
+  int32_t s0 = 0, s1 = 0;
+  bool mine = sg < a.seg.num_segments;  // the same answer in every lane of the group
+  if (mine) {
     seg_bounds(a.seg, sg, &s0, &s1);
-    const float* const go = a.grad_out + sg * (int64_t)a.dim;
-    const float* const qr = a.q + sg * (int64_t)a.dim;
+    if (SHORT) mine = s1 - s0 <= kChunk;
+  }
+  if (mine) {
     if (s1 > s0) {
-      dot_pass<G, VEC, SUB>(a, go, a.v, s0, s1, c, a.grad_e);
+      dot_pass<G, VEC, SUB>(a, a.grad_out + sg * (int64_t)a.dim, a.v, s0, s1, c, a.grad_e);
       dot_handoff<G>();
       dot_normalise<G, true>(a, s0, s1, c, nullptr);
       dot_handoff<G>();
     }
     if (a.grad_q || a.grad_edge) {
-      for (int32_t col_pass = 0; col_pass < a.dim; col_pass += G * VEC) {
-        const int32_t col = col_pass + c * VEC;
-        const bool col_ok = col < a.dim;
-        const int32_t col_ld = col_ok ? col : 0;  // lanes past the end re-read the first columns, unused
-        const int32_t head = col_ld / a.C;
-        const vec_t qv = *reinterpret_cast<const vec_t*>(qr + col_ld);
-        const vec_t gov = *reinterpret_cast<const vec_t*>(go + col_ld);
-        vec_t acc;
-#pragma unroll
-        for (int t = 0; t < VEC; ++t) acc[t] = 0.0f;
-        for (int32_t base = s0; base < s1; base += G) {
-          const int32_t my_row = a.grad_q ? dot_my_row(a, base + c, s1) : -1;
-          const int32_t m = (s1 - base) < G ? (s1 - base) : G;
-          for (int32_t j = 0; j < m; j += kWU) {
-            int32_t row[kWU];
-#pragma unroll
-            for (int u = 0; u < kWU; ++u) row[u] = __shfl(my_row, (j + u) & (G - 1), G);
-            vec_t val[kWU];
-            float ge[kWU], al[kWU];
-#pragma unroll
-            for (int u = 0; u < kWU; ++u) {
-              if (j + u < m) {
-                const int64_t at = (int64_t)(base + j + u) * a.heads + head;
-                ge[u] = a.grad_e[at];
-                if (a.grad_edge) al[u] = a.w[at];
-                if (a.grad_q) val[u] = dot_row_vec<VEC>(a, a.k, row[u], base + j + u, col_ld);
-              }
-            }
-#pragma unroll
-            for (int u = 0; u < kWU; ++u) {
-              if (j + u < m) {
-                if (a.grad_q) {
-#pragma unroll
-                  for (int t = 0; t < VEC; ++t) acc[t] = glx_fold_rn(acc[t], ge[u], val[u][t]);
-                }
-                if (a.grad_edge && col_ok) {
-                  vec_t d;
-#pragma unroll
-                  for (int t = 0; t < VEC; ++t) d[t] = glx_pin(ge[u] * qv[t]) + glx_pin(al[u] * gov[t]);
-                  *reinterpret_cast<vec_t*>(a.grad_edge + (base + j + u) * (int64_t)a.dim + col) = d;
-                }
-              }
-            }
-          }
-        }
-        if (a.grad_q && col_ok) *reinterpret_cast<vec_t*>(a.grad_q + sg * (int64_t)a.dim + col) = acc;
-      }
+      dot_fold_back<G, VEC>(a, sg, s0, s1, c, a.grad_q ? a.grad_q + sg * (int64_t)a.dim : nullptr);
     }
   }
   dot_zero_tail(a.seg, a.grad_e, a.heads);
   dot_zero_tail(a.seg, a.grad_edge, a.dim);
 }
 
+// ---- the chunked order ----------------------------------------------------------------------------------------
+// The chunk directory is a GlxAggChunks whose "rows" are the SEGMENTS: slot0[sg] the first work item / partial slot of
+// segment sg (slot0[num_segments] the number of work items), item_row[t] the segment of work item t, whose chunk is
+// t - slot0[segment].  The combine pass is glx_agg_chunks_combine itself.
+
+// chunks of segment sg: ceil(L / kChunk) for L > kChunk consumed positions, none otherwise (and none for the extra
+// element num_segments, which makes the exclusive scan end with the total)
+struct LongSegChunks {
+  GlxSegLayout seg;
+  __device__ int32_t operator()(int64_t sg) const {
+    if (sg >= seg.num_segments) return 0;
+    int32_t s0, s1;
+    seg_bounds(seg, sg, &s0, &s1);
+    return s1 - s0 > kChunk ? (s1 - s0 + kChunk - 1) / kChunk : 0;
+  }
+};
+
+// work item t belongs to the last segment whose first slot is at or below t (segments without chunks share their
+// successor's)
+__global__ __launch_bounds__(256) void glx_dot_chunk_items_kernel(const int32_t* __restrict__ slot0,
+                                                                  int32_t num_segments, int32_t max_items,
+                                                                  int32_t* __restrict__ item_seg) {
+  const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (t >= max_items || t >= slot0[num_segments]) return;
+  int32_t lo = 0, hi = num_segments;  // the first index whose slot0 exceeds t: slot0[num_segments] does
+  while (lo < hi) {
+    const int32_t mid = lo + ((hi - lo) >> 1);
+    if (slot0[mid] > t) hi = mid; else lo = mid + 1;
+  }
+  item_seg[t] = lo - 1;
+}
+
+// The directory and the partial sums of one request in one lease of workspace slot 5 (the scan's temporary passes
+// through slot 3, and is given back before glx_weighted_bwd_x wants it).
+int dot_chunk_dir(const GlxSegLayout& seg, int32_t dim, hipStream_t s, GlxScratch* lease, GlxAggChunks* out) {
+  const int32_t max_items = seg.num_ids / (kChunk / 2) + 1;
+  const size_t slot_b = glx_align256((size_t)(seg.num_segments + 1) * sizeof(int32_t));
+  const size_t item_b = glx_align256((size_t)max_items * sizeof(int32_t));
+  const size_t part_b = (size_t)max_items * dim * sizeof(float);
+  const int rc = lease->alloc(slot_b + item_b + part_b, s, 5);
+  if (rc != GLX_OK) return rc;
+  char* const at = lease->as<char>();
+  int32_t* const slot0 = reinterpret_cast<int32_t*>(at);
+  int32_t* const item_seg = reinterpret_cast<int32_t*>(at + slot_b);
+  const auto counts = rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), LongSegChunks{seg});
+  GLX_TRY(glx_prim_leased(s, 3, "chunked dot attention: scan the long segments' chunk counts",
+                          [&](void* tmp, size_t& bytes) {
+                            return rocprim::exclusive_scan(tmp, bytes, counts, slot0, (int32_t)0,
+                                                           (size_t)(seg.num_segments + 1), rocprim::plus<int32_t>(), s);
+                          }));
+  glx_dot_chunk_items_kernel<<<(unsigned)(((int64_t)max_items + 255) / 256), 256, 0, s>>>(slot0, seg.num_segments,
+                                                                                           max_items, item_seg);
+  out->slot0 = slot0;
+  out->item_row = item_seg;
+  out->partial = reinterpret_cast<float*>(at + slot_b + item_b);
+  out->num_rows = seg.num_segments;
+  out->max_items = max_items;
+  return GLX_OK;
+}
+
+// the segment of work item t and the positions [*c0, *c1) of its chunk; false: t is past the directory
+__device__ __forceinline__ bool dot_chunk_of(const DotArgs& a, const GlxAggChunks& ch, int64_t t, int32_t* sg,
+                                             int32_t* c0, int32_t* c1) {
+  if (t >= ch.max_items || t >= ch.slot0[ch.num_rows]) return false;
+  *sg = ch.item_row[t];
+  int32_t s0, s1;
+  seg_bounds(a.seg, *sg, &s0, &s1);
+  *c0 = s0 + ((int32_t)t - ch.slot0[*sg]) * kChunk;
+  *c1 = s1 - *c0 > kChunk ? *c0 + kChunk : s1;
+  return true;
+}
+
+// G lanes own work item t: the dot products of its chunk's positions, where the per-segment kernels park theirs (the
+// logits' in logit_out or soft_out; ga_raw in grad_e).  Whole groups leave past the directory.
+template <int G, int VEC, bool SUB, bool BWD>
+__global__ __launch_bounds__(256) void glx_dot_chunk_pass_kernel(DotArgs a, GlxAggChunks ch) {
+  const int64_t t = blockIdx.x * (int64_t)(256 / G) + threadIdx.x / G;
+  const int c = threadIdx.x & (G - 1);
+  int32_t sg, c0, c1;
+  if (!dot_chunk_of(a, ch, t, &sg, &c0, &c1)) return;
+  if (BWD) dot_pass<G, VEC, SUB>(a, a.grad_out + sg * (int64_t)a.dim, a.v, c0, c1, c, a.grad_e);
+  else dot_pass<G, VEC, SUB>(a, a.q + sg * (int64_t)a.dim, a.k, c0, c1, c, a.logit ? a.logit : a.soft_out);
+}
+
+// The workgroup owns work item t and leaves unless it is the first of its segment: the normalisation of one long
+// segment by 256 threads, K5-sm's long-segment walk.  A thread parks and reads back its own items only; what the pass
+// kernel wrote arrived with the kernel boundary.  Every condition is the same in all 256 threads.
+template <bool BWD>
+__global__ __launch_bounds__(256) void glx_dot_chunk_norm_kernel(DotArgs a, GlxAggChunks ch) {
+  __shared__ float red[256];
+  const int64_t t = blockIdx.x;
+  if (t >= ch.max_items || t >= ch.slot0[ch.num_rows]) return;
+  const int32_t sg = ch.item_row[t];
+  if (ch.slot0[sg] != t) return;
+  int32_t s0, s1;
+  seg_bounds(a.seg, sg, &s0, &s1);
+  const SmBlockWalker w = {red};
+  float* const lg = a.logit ? a.logit : a.soft_out;
+  SmItems it = sm_items((a.heads & (a.heads - 1)) == 0 && a.heads <= 64, s0, s1, a.heads);
+  for (it.o = 0; it.o < it.outer; ++it.o) {
+    if (BWD) sm_backward(w, it, DotIo{a, it, nullptr});
+    else sm_forward(w, it, DotIo{a, it, lg});
+  }
+}
+
+// G lanes own work item t: the fold of its chunk into the item's partial sum, by the per-segment kernels' own walk
+// (backward: grad_q's terms -- unless grad_q is not asked for -- and the chunk's rows of grad_edge).
+template <int G, int VEC, bool BWD>
+__global__ __launch_bounds__(256) void glx_dot_chunk_fold_kernel(DotArgs a, GlxAggChunks ch) {
+  const int64_t t = blockIdx.x * (int64_t)(256 / G) + threadIdx.x / G;
+  const int c = threadIdx.x & (G - 1);
+  int32_t sg, c0, c1;
+  if (!dot_chunk_of(a, ch, t, &sg, &c0, &c1)) return;
+  float* const part = ch.partial + t * (int64_t)a.dim;
+  if (BWD) dot_fold_back<G, VEC>(a, sg, c0, c1, c, a.grad_q ? part : nullptr);
+  else dot_fold_out<G, VEC>(a, c0, c1, c, part);
+}
+
+// ch == nullptr: the default order, one launch; otherwise the chunked one over that directory
 template <bool BWD, int VEC>
-void dot_launch_vec(DotArgs a, hipStream_t s) {
+void dot_launch_vec(DotArgs a, const GlxAggChunks* ch, hipStream_t s) {
   const GlxHeadDotPlan plan = glx_head_dot_plan(a.dim, a.C, VEC);
   const int G = plan.G;
   a.hd = plan.hd;
@@ -324,24 +488,36 @@ void dot_launch_vec(DotArgs a, hipStream_t s) {
   const unsigned blocks = sm_blocks(G, BWD && a.grad_edge ? a.dim : a.heads, a.seg.num_ids, a.seg.num_segments);
   glx_for_group(G, [&](auto g) {
     constexpr int kG = decltype(g)::value;
-    if (BWD) {
-      if (plan.sub_groups) glx_dot_attention_bwd_kernel<kG, VEC, true><<<blocks, 256, 0, s>>>(a);
-      else glx_dot_attention_bwd_kernel<kG, VEC, false><<<blocks, 256, 0, s>>>(a);
-    } else {
-      if (plan.sub_groups) glx_dot_attention_kernel<kG, VEC, true><<<blocks, 256, 0, s>>>(a);
-      else glx_dot_attention_kernel<kG, VEC, false><<<blocks, 256, 0, s>>>(a);
-    }
+    const auto launch = [&](auto sub) {
+      constexpr bool kSub = decltype(sub)::value;
+      if (ch == nullptr) {
+        if (BWD) glx_dot_attention_bwd_kernel<kG, VEC, kSub, false><<<blocks, 256, 0, s>>>(a);
+        else glx_dot_attention_kernel<kG, VEC, kSub, false><<<blocks, 256, 0, s>>>(a);
+        return;
+      }
+      if (BWD) glx_dot_attention_bwd_kernel<kG, VEC, kSub, true><<<blocks, 256, 0, s>>>(a);
+      else glx_dot_attention_kernel<kG, VEC, kSub, true><<<blocks, 256, 0, s>>>(a);
+      const unsigned cblocks = (unsigned)(((int64_t)ch->max_items + (256 / kG) - 1) / (256 / kG));
+      glx_dot_chunk_pass_kernel<kG, VEC, kSub, BWD><<<cblocks, 256, 0, s>>>(a, *ch);
+      glx_dot_chunk_norm_kernel<BWD><<<(unsigned)ch->max_items, 256, 0, s>>>(a, *ch);
+      if (!BWD || a.grad_q || a.grad_edge) glx_dot_chunk_fold_kernel<kG, VEC, BWD><<<cblocks, 256, 0, s>>>(a, *ch);
+    };
+    if (plan.sub_groups) launch(std::true_type());
+    else launch(std::false_type());
   });
+  if (ch != nullptr && (!BWD || a.grad_q)) {
+    glx_agg_chunks_combine(*ch, BWD ? a.grad_q : a.out, GLX_DTYPE_F32, a.dim, VEC == 4, s);
+  }
 }
 
 // float4 row accesses when every row pointer allows them and a lane's four columns share a head
 template <bool BWD>
-void dot_launch(const DotArgs& a, hipStream_t s) {
+void dot_launch(const DotArgs& a, const GlxAggChunks* ch, hipStream_t s) {
   bool vec4 = a.C % 4 == 0 && glx_aligned16(a.q) && glx_aligned16(a.k) && glx_aligned16(a.v) && glx_aligned16(a.edge);
   if (BWD) vec4 = vec4 && glx_aligned16(a.grad_out) && glx_aligned16(a.grad_q) && glx_aligned16(a.grad_edge);
   else vec4 = vec4 && glx_aligned16(a.out);
-  if (vec4) dot_launch_vec<BWD, 4>(a, s);
-  else dot_launch_vec<BWD, 1>(a, s);
+  if (vec4) dot_launch_vec<BWD, 4>(a, ch, s);
+  else dot_launch_vec<BWD, 1>(a, ch, s);
 }
 
 }  // namespace
@@ -364,8 +540,14 @@ void dot_launch(const DotArgs& a, hipStream_t s) {
   GLX_REQUIRE(num_segments == 0 || q != nullptr, "q is NULL");                                                  \
   GLX_REQUIRE(num_rows == 0 || (k != nullptr && v != nullptr), "k or v is NULL")
 
-extern "C" int glx_dot_attention(int device, const float* q, const float* k, const float* v, int64_t num_rows,
-                                 int32_t dim, int32_t heads, const int64_t* rows, const float* edge,
+// Workspace slots.  The default order keeps alpha in slot 2.  The chunked backward calls the chunked
+// glx_weighted_bwd_x, which leases slots 2 and 3 itself while alpha is still being read: the chunked order keeps alpha
+// in slot 4 and its directory and partial sums in slot 5 (dot_chunk_dir).
+constexpr int kAlphaSlot = 2, kAlphaSlotChunked = 4;
+
+// the body of glx_dot_attention (chunked == false: its launches, its bits) and of glx_dot_attention_chunked
+static int dot_attention_forward(bool chunked, int device, const float* q, const float* k, const float* v,
+                                 int64_t num_rows, int32_t dim, int32_t heads, const int64_t* rows, const float* edge,
                                  const int32_t* cnt, int32_t num_ids, int32_t num_segments, float scale,
                                  float default_attr, float drop_p, uint64_t seed, uint64_t call, float* logit_out,
                                  float* soft_out, float* out, int ptr_kind, void* stream) {
@@ -392,7 +574,8 @@ extern "C" int glx_dot_attention(int device, const float* q, const float* k, con
   st.out(&a.out, out, out_count);
   rc = st.begin();
   if (v == k) a.v = a.k;  // one table: staged once
-  GlxScratch lease, alpha;
+  GlxScratch lease, alpha, chunk_lease;
+  GlxAggChunks chunks;
   if (rc == GLX_OK) {
     if (num_ids == 0 || num_segments == 0) {  // nothing was consumed: empty segments, positions of no segment
       rc = glx_zero_f32_async(a.out, out_count, st.s);
@@ -400,7 +583,10 @@ extern "C" int glx_dot_attention(int device, const float* q, const float* k, con
       if (rc == GLX_OK) rc = glx_zero_f32_async(a.logit, count, st.s);
     } else {
       rc = glx_seg_layout(cnt ? d_cnt : nullptr, num_ids, num_segments, st.s, &lease, &a.seg);
-      if (rc == GLX_OK && drop_p != 0.0f) rc = alpha.alloc(count * sizeof(float), st.s, 2);
+      if (rc == GLX_OK && drop_p != 0.0f) {
+        rc = alpha.alloc(count * sizeof(float), st.s, chunked ? kAlphaSlotChunked : kAlphaSlot);
+      }
+      if (rc == GLX_OK && chunked) rc = dot_chunk_dir(a.seg, dim, st.s, &chunk_lease, &chunks);
       if (rc == GLX_OK) {
         a.num_rows = num_rows;
         a.dim = dim;
@@ -414,20 +600,39 @@ extern "C" int glx_dot_attention(int device, const float* q, const float* k, con
         a.w = a.drop ? a.alpha : a.soft_out;
         a.soft = a.grad_out = nullptr;
         a.grad_e = a.grad_q = a.grad_edge = nullptr;
-        dot_launch<false>(a, st.s);
+        dot_launch<false>(a, chunked ? &chunks : nullptr, st.s);
       }
     }
   }
   return st.finish(rc);
 }
 
-extern "C" int glx_dot_attention_backward(int device, const float* q, const float* k, const float* v, int64_t num_rows,
-                                          int32_t dim, int32_t heads, const int64_t* rows, const float* edge,
-                                          const int32_t* cnt, int32_t num_ids, int32_t num_segments, float scale,
-                                          float default_attr, float drop_p, uint64_t seed, uint64_t call,
-                                          const float* soft, const float* grad_out, float* grad_e_out,
-                                          float* grad_q_out, float* grad_k_out, float* grad_v_out, float* grad_edge_out,
-                                          int ptr_kind, void* stream) {
+extern "C" int glx_dot_attention(int device, const float* q, const float* k, const float* v, int64_t num_rows,
+                                 int32_t dim, int32_t heads, const int64_t* rows, const float* edge,
+                                 const int32_t* cnt, int32_t num_ids, int32_t num_segments, float scale,
+                                 float default_attr, float drop_p, uint64_t seed, uint64_t call, float* logit_out,
+                                 float* soft_out, float* out, int ptr_kind, void* stream) {
+  return dot_attention_forward(false, device, q, k, v, num_rows, dim, heads, rows, edge, cnt, num_ids, num_segments,
+                               scale, default_attr, drop_p, seed, call, logit_out, soft_out, out, ptr_kind, stream);
+}
+
+extern "C" int glx_dot_attention_chunked(int device, const float* q, const float* k, const float* v, int64_t num_rows,
+                                         int32_t dim, int32_t heads, const int64_t* rows, const float* edge,
+                                         const int32_t* cnt, int32_t num_ids, int32_t num_segments, float scale,
+                                         float default_attr, float drop_p, uint64_t seed, uint64_t call,
+                                         float* logit_out, float* soft_out, float* out, int ptr_kind, void* stream) {
+  return dot_attention_forward(true, device, q, k, v, num_rows, dim, heads, rows, edge, cnt, num_ids, num_segments,
+                               scale, default_attr, drop_p, seed, call, logit_out, soft_out, out, ptr_kind, stream);
+}
+
+// the body of glx_dot_attention_backward (chunked == false: its launches, its bits) and of
+// glx_dot_attention_backward_chunked
+static int dot_attention_backward(bool chunked, int device, const float* q, const float* k, const float* v,
+                                  int64_t num_rows, int32_t dim, int32_t heads, const int64_t* rows, const float* edge,
+                                  const int32_t* cnt, int32_t num_ids, int32_t num_segments, float scale,
+                                  float default_attr, float drop_p, uint64_t seed, uint64_t call, const float* soft,
+                                  const float* grad_out, float* grad_e_out, float* grad_q_out, float* grad_k_out,
+                                  float* grad_v_out, float* grad_edge_out, int ptr_kind, void* stream) {
   GLX_DOT_ATTENTION_REQUIRE();
   GLX_REQUIRE(num_ids == 0 || soft != nullptr, "soft is NULL");
   GLX_REQUIRE(num_segments == 0 || grad_out != nullptr, "grad_out is NULL");
@@ -464,6 +669,7 @@ extern "C" int glx_dot_attention_backward(int device, const float* q, const floa
   rc = st.begin();
   if (v == k) a.v = a.k;  // one table: staged once
   GlxScratch lease, alpha;
+  GlxAggChunks chunks;
   if (rc == GLX_OK) {
     if (num_ids == 0 || num_segments == 0) {  // nothing was consumed: every output is zeros
       rc = glx_zero_f32_async(a.grad_e, count, st.s);
@@ -476,7 +682,9 @@ extern "C" int glx_dot_attention_backward(int device, const float* q, const floa
       GlxAggTranspose tr;
       rc = glx_seg_layout_bwd(want_rows, a.rows, cnt ? d_cnt : nullptr, num_ids, num_segments, num_rows, st.s, &lease,
                               &tr, &a.seg);
-      if (rc == GLX_OK && drop_p != 0.0f) rc = alpha.alloc(count * sizeof(float), st.s, 2);
+      if (rc == GLX_OK && drop_p != 0.0f) {
+        rc = alpha.alloc(count * sizeof(float), st.s, chunked ? kAlphaSlotChunked : kAlphaSlot);
+      }
       if (rc == GLX_OK) {
         a.num_rows = num_rows;
         a.dim = dim;
@@ -489,15 +697,49 @@ extern "C" int glx_dot_attention_backward(int device, const float* q, const floa
         a.alpha = alpha.as<float>();
         a.w = a.drop ? a.alpha : a.soft;
         a.logit = a.soft_out = a.out = nullptr;
-        dot_launch<true>(a, st.s);
-        if (want_rows && d_gk) {
-          glx_weighted_bwd_x(GLX_AGG_SUM, tr, a.grad_e, a.q, d_gk, num_rows, dim, heads, num_ids, num_segments, st.s);
+        if (chunked) {
+          GlxScratch chunk_lease;  // ends with the block: the launches that use it are queued by then
+          rc = dot_chunk_dir(a.seg, dim, st.s, &chunk_lease, &chunks);
+          if (rc == GLX_OK) dot_launch<true>(a, &chunks, st.s);
+        } else {
+          dot_launch<true>(a, nullptr, st.s);
         }
-        if (want_rows && d_gv) {
-          glx_weighted_bwd_x(GLX_AGG_SUM, tr, a.w, a.grad_out, d_gv, num_rows, dim, heads, num_ids, num_segments, st.s);
+        // the default mode of glx_weighted_bwd_x returns GLX_OK; the chunked one leases inside the call
+        if (rc == GLX_OK && want_rows && d_gk) {
+          rc = glx_weighted_bwd_x(GLX_AGG_SUM, tr, a.grad_e, a.q, d_gk, num_rows, dim, heads, num_ids, num_segments,
+                                  st.s, GLX_DTYPE_F32, chunked);
+        }
+        if (rc == GLX_OK && want_rows && d_gv) {
+          rc = glx_weighted_bwd_x(GLX_AGG_SUM, tr, a.w, a.grad_out, d_gv, num_rows, dim, heads, num_ids, num_segments,
+                                  st.s, GLX_DTYPE_F32, chunked);
         }
       }
     }
   }
   return st.finish(rc);
+}
+
+extern "C" int glx_dot_attention_backward(int device, const float* q, const float* k, const float* v, int64_t num_rows,
+                                          int32_t dim, int32_t heads, const int64_t* rows, const float* edge,
+                                          const int32_t* cnt, int32_t num_ids, int32_t num_segments, float scale,
+                                          float default_attr, float drop_p, uint64_t seed, uint64_t call,
+                                          const float* soft, const float* grad_out, float* grad_e_out,
+                                          float* grad_q_out, float* grad_k_out, float* grad_v_out, float* grad_edge_out,
+                                          int ptr_kind, void* stream) {
+  return dot_attention_backward(false, device, q, k, v, num_rows, dim, heads, rows, edge, cnt, num_ids, num_segments,
+                                scale, default_attr, drop_p, seed, call, soft, grad_out, grad_e_out, grad_q_out,
+                                grad_k_out, grad_v_out, grad_edge_out, ptr_kind, stream);
+}
+
+extern "C" int glx_dot_attention_backward_chunked(int device, const float* q, const float* k, const float* v,
+                                                  int64_t num_rows, int32_t dim, int32_t heads, const int64_t* rows,
+                                                  const float* edge, const int32_t* cnt, int32_t num_ids,
+                                                  int32_t num_segments, float scale, float default_attr, float drop_p,
+                                                  uint64_t seed, uint64_t call, const float* soft,
+                                                  const float* grad_out, float* grad_e_out, float* grad_q_out,
+                                                  float* grad_k_out, float* grad_v_out, float* grad_edge_out,
+                                                  int ptr_kind, void* stream) {
+  return dot_attention_backward(true, device, q, k, v, num_rows, dim, heads, rows, edge, cnt, num_ids, num_segments,
+                                scale, default_attr, drop_p, seed, call, soft, grad_out, grad_e_out, grad_q_out,
+                                grad_k_out, grad_v_out, grad_edge_out, ptr_kind, stream);
 }

@@ -59,6 +59,7 @@ EXPORTS = [
     "glx_aggregate_backward_ex", "glx_aggregate_weighted_ex", "glx_aggregate_weighted_backward_x_ex",
     "glx_aggregate_weighted_backward_w_ex", "glx_pair_dot_ex", "glx_pair_dot_backward_ex",
     "glx_aggregate_backward_chunked", "glx_aggregate_weighted_backward_x_chunked",
+    "glx_dot_attention_chunked", "glx_dot_attention_backward_chunked",
     "glx_rows_coalesce", "glx_embedding_update",
     "glx_tgn_store_update", "glx_tgn_message", "glx_tgn_message_backward", "glx_tgn_memory_write",
     "glx_partition", "glx_stitch_i64", "glx_stitch_f32", "glx_aggregate_stitch",
@@ -215,6 +216,9 @@ def lib():
         # the chunked order of the two row gradients: their _ex siblings' arguments
         L.glx_aggregate_backward_chunked.argtypes = L.glx_aggregate_backward_ex.argtypes
         L.glx_aggregate_weighted_backward_x_chunked.argtypes = L.glx_aggregate_weighted_backward_x_ex.argtypes
+        # the chunked order of dot-product attention: the default entry points' arguments
+        L.glx_dot_attention_chunked.argtypes = L.glx_dot_attention.argtypes
+        L.glx_dot_attention_backward_chunked.argtypes = L.glx_dot_attention_backward.argtypes
         L.glx_rows_coalesce.argtypes =[ci, vp, i32, i64, i32, vp, vp, vp, vp, ci, vp]
         L.glx_embedding_update.argtypes = [ci, ci, vp, vp, vp, i64, i32, vp, vp, i32, f32, f32, f32, f32, f32, f32, vp]
         L.glx_tgn_store_update.argtypes = [ci, i64, i32, vp, vp, vp, vp, i32, i64, vp, vp, vp, vp, vp]
@@ -1288,7 +1292,7 @@ def _same_table(k, v):
 
 
 def dot_attention(q, k, v, rows, cnt=None, edge=None, heads=1, scale=None, default_attr=0.0, drop_p=0.0, seed=0, call=0,
-                  want_logit=False, out=None, soft_out=None, logit_out=None, device=0):
+                  want_logit=False, out=None, soft_out=None, logit_out=None, device=0, chunked=False):
     """Scaled dot-product attention of every segment over its positions, with an edge term on the key and on the value
     (glx_dot_attention) -> (out[S, D], soft[n, heads], logit[n, heads] or None), float32.  q[S, D] one query per
     segment; k, v[M, D] (they may be one buffer); rows[n] int64 (a value outside [0, M) reads a row of default_attr in
@@ -1297,7 +1301,12 @@ def dot_attention(q, k, v, rows, cnt=None, edge=None, heads=1, scale=None, defau
     rounded to float32), soft its softmax over each segment (glx_segment_softmax's definition), alpha gat_attention's
     dropout of soft under (seed, call), out the sum of alpha * (v[rows] + edge) in ascending position: bit-exact from
     soft, an empty segment is +0.0.  No atomics: the same bits on every call.  Torch CUDA tensors are device pointers
-    on the current stream, numpy arrays host pointers."""
+    on the current stream, numpy arrays host pointers.
+    chunked=True (glx_dot_attention_chunked) is the CHUNKED order, for requests with hub segments: a segment of more
+    than 256 positions is cut into chunks of 256, its softmax runs in a fixed tree over one workgroup (the same
+    definition, rules and bound; other bits) and its `out` adds each chunk from +0.0 in ascending position, then the
+    partial sums in chunk order.  logit has the default's bits everywhere, and so has every output of a segment of at
+    most 256 positions; as deterministic as the default."""
     n, num_segments, num_rows, dim = _dot_shapes(q, k, v, rows, edge, heads)
     if scale is None:
         scale = float(np.float32(1.0) / np.sqrt(np.float32(dim // heads)))
@@ -1310,22 +1319,27 @@ def dot_attention(q, k, v, rows, cnt=None, edge=None, heads=1, scale=None, defau
     kind = _kind(pq, pk, pv, pr, pe, pc, pl, ps, po)
     if kind == PTR_DEVICE:
         device = res.device.index or 0
-    _check(lib().glx_dot_attention(device, pq[0], pk[0], pv[0], num_rows, dim, heads, pr[0], pe[0], pc[0], n,
-                                   num_segments, scale, default_attr, drop_p, seed, call, pl[0], ps[0], po[0], kind,
-                                   _stream(kind, device)))
+    entry = lib().glx_dot_attention_chunked if chunked else lib().glx_dot_attention
+    _check(entry(device, pq[0], pk[0], pv[0], num_rows, dim, heads, pr[0], pe[0], pc[0], n, num_segments, scale,
+                 default_attr, drop_p, seed, call, pl[0], ps[0], po[0], kind, _stream(kind, device)))
     return res, soft, logit
 
 
 def dot_attention_backward(soft, grad_out, q, k, v, rows, cnt=None, edge=None, heads=1, scale=None, default_attr=0.0,
                            drop_p=0.0, seed=0, call=0, want_q=True, want_k=True, want_v=True, want_edge=True, out=None,
-                           out_q=None, out_k=None, out_v=None, out_edge=None, device=0):
+                           out_q=None, out_k=None, out_v=None, out_edge=None, device=0, chunked=False):
     """Gradients of dot_attention (glx_dot_attention_backward) -> (grad_e[n, heads], grad_q[S, D], grad_k[M, D],
     grad_v[M, D], grad_edge[n, D]; None for a gradient that was not asked for, and grad_edge is None without edge) from
     the forward's `soft`, the gradient of its `out` and the forward's own arguments (alpha and the dropout mask are
     recomputed from soft, seed and call).  grad_e is the gradient of the logits; grad_q and grad_edge are bit-exact
     folds of it, grad_k and grad_v the bits of aggregate_weighted_backward_x(SUM, rows, grad_e, cnt, q, M) and of
     aggregate_weighted_backward_x(SUM, rows, alpha, cnt, grad_out, M) on one transpose.  Every element is written; no
-    atomics: the same bits on every call."""
+    atomics: the same bits on every call.
+    chunked=True (glx_dot_attention_backward_chunked) is dot_attention's CHUNKED order going back: the softmax gradient
+    of a segment of more than 256 positions runs over one workgroup, its grad_q is summed chunk by chunk (each chunk of
+    256 positions from +0.0, the partial sums in chunk order), and grad_k / grad_v are the bits of
+    aggregate_weighted_backward_x(..., chunked=True).  A request without such segments and without rows named more than
+    256 times gets the default's bits in every output."""
     n, num_segments, num_rows, dim = _dot_shapes(q, k, v, rows, edge, heads)
     if scale is None:
         scale = float(np.float32(1.0) / np.sqrt(np.float32(dim // heads)))
@@ -1343,9 +1357,10 @@ def dot_attention_backward(soft, grad_out, q, k, v, rows, cnt=None, edge=None, h
     kind = _kind(pq, pk, pv, pr, pe, pc, pso, pg, pge, pgq, pgk, pgv, pged)
     if kind == PTR_DEVICE:
         device = grad_e.device.index or 0
-    _check(lib().glx_dot_attention_backward(device, pq[0], pk[0], pv[0], num_rows, dim, heads, pr[0], pe[0], pc[0], n,
-                                            num_segments, scale, default_attr, drop_p, seed, call, pso[0], pg[0],
-                                            pge[0], pgq[0], pgk[0], pgv[0], pged[0], kind, _stream(kind, device)))
+    entry = lib().glx_dot_attention_backward_chunked if chunked else lib().glx_dot_attention_backward
+    _check(entry(device, pq[0], pk[0], pv[0], num_rows, dim, heads, pr[0], pe[0], pc[0], n, num_segments, scale,
+                 default_attr, drop_p, seed, call, pso[0], pg[0], pge[0], pgq[0], pgk[0], pgv[0], pged[0], kind,
+                 _stream(kind, device)))
     return grad_e, grad_q, grad_k, grad_v, grad_edge
 
 

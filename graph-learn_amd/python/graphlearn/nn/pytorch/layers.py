@@ -128,6 +128,10 @@ class TransformerConv(torch.nn.Module):
   edge_dim          None, or the columns of edge_attr: a bias-free linear map takes them to H * out_dim
   root_weight       add a linear map of the seed's own features (the skip connection), of the output's shape
   bias              of the query, key, value and skip maps
+  chunked           passed to dot_attention: True sums a hub seed's neighbours (a segment of more than 256 positions)
+                    chunk by chunk over many lane groups, in both directions, and the key and value gradients of a node
+                    named more than 256 times likewise -- another fixed order, as deterministic as the default; a batch
+                    without such seeds and nodes gets the default's bits.  For FullSampler hops over power-law seeds
 
   Every op is float32 on one GPU; the segments are described by counts (or the implied layout), not by explicit
   segment ids, and there is no mask for padded neighbours beyond counts.  dot_attention takes float32 only, so under
@@ -136,7 +140,7 @@ class TransformerConv(torch.nn.Module):
   """
 
   def __init__(self, in_dim, out_dim, heads=1, concat=True, dropout=0.0, edge_dim=None, root_weight=True, bias=True,
-               seed=None):
+               seed=None, chunked=False):
     super().__init__()
     in_dim, out_dim, heads = int(in_dim), int(out_dim), int(heads)
     if in_dim < 1 or out_dim < 1 or heads < 1:
@@ -149,6 +153,7 @@ class TransformerConv(torch.nn.Module):
     self.concat, self.dropout = bool(concat), float(dropout)
     self.edge_dim = None if edge_dim is None else int(edge_dim)
     self.seed = None if seed is None else int(seed)
+    self.chunked = bool(chunked)
     self.calls = 0  # training forwards so far: the `call` of the next dropout mask
     self.lin_query = torch.nn.Linear(in_dim, heads * out_dim, bias=bool(bias))
     self.lin_key = torch.nn.Linear(in_dim, heads * out_dim, bias=bool(bias))
@@ -180,7 +185,8 @@ class TransformerConv(torch.nn.Module):
       seed = (torch.initial_seed() if self.seed is None else self.seed) & (2 ** 64 - 1)
       call = self.calls
       self.calls += 1
-    out = dot_attention(q, k, v, nbr_local, S, counts=counts, edge=edge, heads=H, dropout=drop, seed=seed, call=call)
+    out = dot_attention(q, k, v, nbr_local, S, counts=counts, edge=edge, heads=H, dropout=drop, seed=seed, call=call,
+                        chunked=self.chunked)
     if not self.concat:
       out = out.view(S, H, C).mean(1)
     if self.lin_skip is not None:
@@ -188,5 +194,6 @@ class TransformerConv(torch.nn.Module):
     return out
 
   def extra_repr(self):
-    return "in_dim={}, out_dim={}, heads={}, concat={}, dropout={}, edge_dim={}, root_weight={}".format(
-        self.in_dim, self.out_dim, self.heads, self.concat, self.dropout, self.edge_dim, self.lin_skip is not None)
+    return "in_dim={}, out_dim={}, heads={}, concat={}, dropout={}, edge_dim={}, root_weight={}, chunked={}".format(
+        self.in_dim, self.out_dim, self.heads, self.concat, self.dropout, self.edge_dim, self.lin_skip is not None,
+        self.chunked)

@@ -60,7 +60,10 @@ segment_aggregate, gather_rows and weighted_segment_aggregate take chunked_grad=
 instead (glx_aggregate_backward_chunked, glx_aggregate_weighted_backward_x_chunked): chunks of 256 of a row's positions
 are summed apart, each from +0.0 in ascending position, and the partial sums are added in chunk order.  As
 deterministic as the default, the default's bits for every row named at most 256 times, other bits beyond; forward
-outputs do not depend on the flag.  pair_dot, gat_attention and dot_attention have no such flag.
+outputs do not depend on the flag.  dot_attention takes chunked=True, which covers BOTH directions: a hub SEGMENT (more
+than 256 positions) has its softmax computed by one workgroup and its out / grad_q summed chunk by chunk, and k.grad /
+v.grad are summed in the chunked order above (glx_dot_attention_chunked, glx_dot_attention_backward_chunked).  pair_dot
+and gat_attention have no such flag: pair_dot's gradients and gat_attention's gradient of t stay unsplit.
 
 bfloat16.  Under torch.autocast("cuda", dtype=torch.bfloat16) `z = relu(enc(x))` is bfloat16, and segment_aggregate,
 gather_rows, weighted_segment_aggregate and pair_dot take it as it is -- inside autocast or outside, they go by the
@@ -464,12 +467,13 @@ def gat_attention(s, t, index, num_segments, counts=None, negative_slope=0.2, dr
 class _DotAttention(torch.autograd.Function):
 
   @staticmethod
-  def forward(ctx, q, k, v, edge, index, counts, heads, scale, drop_p, seed, call, default_attr):
+  def forward(ctx, q, k, v, edge, index, counts, heads, scale, drop_p, seed, call, default_attr, chunked):
     qd, kd, vd = q.detach(), k.detach(), v.detach()
     ed = None if edge is None else edge.detach()
     out, soft, _ = _glx().dot_attention(qd, kd, vd, index, cnt=counts, edge=ed, heads=heads, scale=scale,
-                                        default_attr=default_attr, drop_p=drop_p, seed=seed, call=call)
+                                        default_attr=default_attr, drop_p=drop_p, seed=seed, call=call, chunked=chunked)
     ctx.cfg = (heads, scale, default_attr, drop_p, seed, call)
+    ctx.chunked = chunked  # selects the entry point of both directions
     ctx.has_edge, ctx.has_counts = ed is not None, counts is not None
     ctx.save_for_backward(*([soft, qd, kd, vd, index] + ([ed] if ed is not None else []) +
                             ([counts] if counts is not None else [])))
@@ -480,7 +484,7 @@ class _DotAttention(torch.autograd.Function):
     _no_double_backward("dot_attention")
     want_q, want_k, want_v, want_e = ctx.needs_input_grad[:4]
     if not (want_q or want_k or want_v or want_e):
-      return (None,) * 12
+      return (None,) * 13
     saved = list(ctx.saved_tensors)
     soft, q, k, v, index = saved[:5]
     edge = saved[5] if ctx.has_edge else None
@@ -490,12 +494,12 @@ class _DotAttention(torch.autograd.Function):
     _, gq, gk, gv, ge = _glx().dot_attention_backward(soft, grad, q, k, v, index, cnt=counts, edge=edge, heads=heads,
                                                       scale=scale, default_attr=default_attr, drop_p=drop_p, seed=seed,
                                                       call=call, want_q=want_q, want_k=want_k, want_v=want_v,
-                                                      want_edge=want_e)
-    return (gq, gk, gv, ge) + (None,) * 8
+                                                      want_edge=want_e, chunked=ctx.chunked)
+    return (gq, gk, gv, ge) + (None,) * 9
 
 
 def dot_attention(q, k, v, index, num_segments, counts=None, edge=None, heads=1, scale=None, dropout=0.0, seed=0, call=0,
-                  default_attr=0.0):
+                  default_attr=0.0, chunked=False):
   """[S, D]: scaled dot-product attention of every segment over its positions.  For position p of segment sg and head
   h (columns [h C, (h + 1) C), C = D / heads): the logit scale * (q[sg] . (k[index[p]] + edge[p])) over the head's
   columns, its softmax over the segment's positions (segment_softmax's definition and exact rules), gat_attention's
@@ -513,6 +517,12 @@ def dot_attention(q, k, v, index, num_segments, counts=None, edge=None, heads=1,
   edge     None, or [n, D] like q: the edge term of every position, added to its key and to its value; may require grad
   scale    None: 1 / sqrt(C), rounded to float32; or a finite float
   dropout  p in [0, 1), with gat_attention's mask under (seed, call).  Use a new `call` for every step.
+  chunked  True: the CHUNKED order in both directions, for batches with hub segments (glx_dot_attention_chunked,
+           glx_dot_attention_backward_chunked).  A segment of more than 256 positions is normalised by one workgroup and
+           its sums (out, q.grad) add chunks of 256 positions apart, each from +0.0 in ascending position, then the
+           partial sums in chunk order; k.grad and v.grad use weighted_segment_aggregate's chunked_grad order.  As
+           deterministic as the default.  The forward of a request without such segments, and the gradients of one that
+           also names no row more than 256 times, are the default's bits
   An empty segment is 0.  Only the gradients that are needed are computed.  Anything else raises ValueError.
   """
   who = "dot_attention"
@@ -561,7 +571,8 @@ def dot_attention(q, k, v, index, num_segments, counts=None, edge=None, heads=1,
   seed, call = int(seed), int(call)
   if not (0 <= seed < 2 ** 64 and 0 <= call < 2 ** 64):
     raise ValueError("{}: seed and call must fit 64 unsigned bits".format(who))
-  return _DotAttention.apply(q, k, v, edge, index, counts, heads, scale, dropout, seed, call, float(default_attr))
+  return _DotAttention.apply(q, k, v, edge, index, counts, heads, scale, dropout, seed, call, float(default_attr),
+                             bool(chunked))
 
 
 class _PairDot(torch.autograd.Function):

@@ -835,6 +835,44 @@ GLX_API int glx_dot_attention_backward(int device, const float* q, const float* 
                                        float default_attr, float drop_p, uint64_t seed, uint64_t call, const float* soft,
                                        const float* grad_out, float* grad_e_out, float* grad_q_out, float* grad_k_out,
                                        float* grad_v_out, float* grad_edge_out, int ptr_kind, void* stream);
+/* The CHUNKED order of dot-product attention (K5-dot-attn-chunked): opt-in, for requests with hub segments -- a
+ * FullSampler hop over power-law seeds -- which the entry points above leave to one lane group each.  The two entry
+ * points take exactly the arguments of glx_dot_attention / glx_dot_attention_backward, make the same checks in the same
+ * order before any device use, and accept host or device pointers; the entry points above are untouched.
+ * Segment sg consumes positions [s0, s1), L = s1 - s0.  L <= GLX_COALESCE_CHUNK (256) is SHORT, otherwise LONG; chunk j
+ * of a long segment holds positions [s0 + 256 j, min(s0 + 256 (j + 1), s1)).
+ *     logit_out   the default entry point's bits at every position (a position's dot product depends on the
+ *                 (dim, heads, alignment) plan alone, not on which lane group evaluates it)
+ *     short segments: the default entry point's bits in every output (soft_out, out, grad_e, grad_q, grad_edge)
+ *     soft_out of a long segment: the same definition, exact rules and bound (glx_segment_softmax's), computed by one
+ *                 workgroup per segment in a fixed tree over its 256 threads: bits that may differ from the default's
+ *                 and are the same on every call; likewise the softmax gradient inside grad_e
+ *     dropout     word for word the default's: element i = p * heads + h, the same counter, key and threshold
+ *     out[sg, c]  partial_j[c] = +0.0f, then fadd_rn(., fmul_rn(alpha[p, h], vv(p)[c])) over chunk j in ascending p;
+ *                 out[sg, c] = +0.0f, then one fadd_rn per partial in ascending j: bit-exact from alpha, never an FMA
+ *     grad_q      the same two-level order over fmul_rn(grad_e[p, h], kk(p)[c]): bit-exact from grad_e
+ *     grad_edge   the per-position formula, unchanged
+ *     grad_k, grad_v   the bits of glx_aggregate_weighted_backward_x_chunked(Sum) with (w, grad_out) = (grad_e, q) /
+ *                 (alpha, grad_out), on one transpose: rows named more than 256 times are chunked as well
+ * EVERY element of every output that is asked for is written, an unconsumed position and an empty segment +0.0f; no
+ * float atomics; the same inputs give the same bits on every call.  The chunk directory over the segments is built on
+ * the device (one scan, one search per work item): the number of long segments and of chunks never reaches the host,
+ * and a device-pointer call never synchronises.  A long segment of L positions has fewer than L / 128 chunks, so the
+ * partial sums take at most (num_ids / 128 + 1) * dim floats of the calling thread's workspace per direction, beside
+ * the [num_ids, heads] alpha under dropout and, going back, the transpose and the row gradient's own partial sums.
+ * grad_q_out, grad_k_out, grad_v_out and grad_edge_out may each be NULL, as above. */
+GLX_API int glx_dot_attention_chunked(int device, const float* q, const float* k, const float* v, int64_t num_rows,
+                                      int32_t dim, int32_t heads, const int64_t* rows, const float* edge,
+                                      const int32_t* cnt, int32_t num_ids, int32_t num_segments, float scale,
+                                      float default_attr, float drop_p, uint64_t seed, uint64_t call, float* logit_out,
+                                      float* soft_out, float* out, int ptr_kind, void* stream);
+GLX_API int glx_dot_attention_backward_chunked(int device, const float* q, const float* k, const float* v,
+                                               int64_t num_rows, int32_t dim, int32_t heads, const int64_t* rows,
+                                               const float* edge, const int32_t* cnt, int32_t num_ids,
+                                               int32_t num_segments, float scale, float default_attr, float drop_p,
+                                               uint64_t seed, uint64_t call, const float* soft, const float* grad_out,
+                                               float* grad_e_out, float* grad_q_out, float* grad_k_out,
+                                               float* grad_v_out, float* grad_edge_out, int ptr_kind, void* stream);
 
 /* ---- pair scores: the per-pair, optionally multi-head, dot product of two gathered rows, with its gradients with
  * respect to both tables.  The reference's unsupervised models score an edge as the dot product of its two endpoint
@@ -1012,9 +1050,10 @@ GLX_API int glx_embedding_update(int device, int algo, float* W, float* state1, 
  * number of long rows and of chunks never reaches the host: no read-back, no synchronisation.  A list of L >
  * GLX_COALESCE_CHUNK entries has fewer than L / 128 chunks, so the partial sums take at most (num_ids / 128 + 1) * dim
  * floats of the calling thread's workspace, beside the transpose.)
- * Still summed by one lane group per list, in ascending position: glx_pair_dot_backward, grad_t of
- * glx_gat_attention_backward, grad_k / grad_v of glx_dot_attention_backward (and its long segments); Prod has no
- * backward; the distributed store has none either; request plans (graph capture) do not cover the backward. */
+ * Still summed by one lane group per list, in ascending position: glx_pair_dot_backward and grad_t of
+ * glx_gat_attention_backward (dot-product attention has a chunked order of its own, for its long segments and for
+ * grad_k / grad_v: glx_dot_attention_chunked, glx_dot_attention_backward_chunked); Prod has no backward; the
+ * distributed store has none either; request plans (graph capture) do not cover the backward. */
 GLX_API int glx_aggregate_backward_chunked(int device, int op, const int64_t* rows, const int32_t* cnt,
                                            const int32_t* arg, int32_t num_ids, int32_t num_segments, int64_t num_rows,
                                            int32_t dim, const float* grad_out, void* grad_x, int grad_x_dtype,
