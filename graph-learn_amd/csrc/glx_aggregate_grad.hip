@@ -15,9 +15,9 @@
 //   sort      STABLE radix sort of (key, p) over ceil(log2(num_rows + 1)) bits: row r's positions end up contiguous
 //             and ascending
 //   row_ptr   row_ptr[r] = lower bound of r in the sorted keys, r in [0, num_rows]
-//   reduce    glx_aggregate_bwd_kernel: the mirror image of the forward's grouped kernel -- G lanes own one TABLE row,
-//             lane c owns columns [4c, 4c + 4), the row's list entries are fetched coalesced (G at a time) and handed
-//             round with cross-lane reads, U grad_out row loads are issued before the first is folded.
+//   reduce    glx_row_grad_kernel (glx_chunks.h): the mirror image of the forward's grouped kernel -- G lanes own one
+//             TABLE row, lane c owns columns [4c, 4c + 4), the row's list entries are fetched coalesced (G at a time)
+//             and handed round with cross-lane reads, U grad_out row loads are issued before the first is folded.
 // grad_x is float32 or bfloat16 (glx_aggregate_backward_ex): the sum above is float32 either way, and a
 // bfloat16 grad_x stores it rounded once per element, to nearest even (glx_f32_to_bf16_bits), in the reduce's final store.
 // The workspace is the per-(thread, device, stream) arena; nothing is read back on the host between the launches.
@@ -25,22 +25,11 @@
 // (glx_aggregate_weighted.hip).
 //
 // The CHUNKED order (glx_aggregate_backward_chunked) is a second, opt-in contract for the
-// same terms: a row's list is cut into chunks of GLX_COALESCE_CHUNK entries (entries, selected by a Max / Min arg or
-// not), a chunk's partial is +0.0f plus its terms in ascending position, and grad_x[r] is +0.0f plus the partials in
-// ascending chunk.  A list of at most one chunk's entries gets the default order's bits.  Three launches after the
-// transpose and a chunk directory built from row_ptr on the device (glx_agg_chunks: one scan, one search per work
-// item; nothing is read back):
-//   short    the per-row kernel above, which leaves the rows of more than one chunk alone
-//   chunk    one lane group per (long row, chunk) work item, the same walk into a float32 partial sum
-//   combine  one lane group per long row adds its partial sums in order and stores in grad_x's dtype
-// Every row is still written exactly once, and nothing proportional to [num_rows, dim] is allocated: the partial sums
-// take at most (num_ids / 128 + 1) * dim floats.
-#include <string.h>  // rocprim's texture_cache_iterator uses memset
-
-#include <rocprim/rocprim.hpp>
-
-#include "glx_prims.h"
-#include "glx_segment_lanes.h"
+// same terms, over the chunks of a row's list (entries, selected by a Max / Min arg or not): glx_chunks.h has the
+// order, the chunk directory and the kernels, which are the ones of the default order; this file has the term, and the
+// two kernels of the chunked order that are no templates of a request (the directory's items, the combine).  Every row
+// is still written exactly once, and nothing proportional to [num_rows, dim] is allocated.
+#include "glx_chunks.h"
 
 namespace {
 
@@ -184,8 +173,8 @@ __global__ __launch_bounds__(256) void glx_bwd_row_ptr_kernel(const uint32_t* __
 
 }  // namespace
 
-// The transpose of one request (glx_common.h): keys, stable sort, row_ptr.  One lease of workspace slot 1 holds every
-// piece; it ends with the caller's GlxScratch.
+// The transpose of one request (glx_common.h): keys, stable sort, row_ptr.  One lease of workspace slot kSlotRequest
+// holds every piece; it ends with the caller's GlxScratch.
 int glx_agg_transpose(const int64_t* rows, const int32_t* cnt, int32_t n, int32_t num_segments, int64_t num_rows,
                       hipStream_t s, GlxScratch* lease, GlxAggTranspose* out) {
   int bits = 1;
@@ -203,7 +192,7 @@ int glx_agg_transpose(const int64_t* rows, const int32_t* cnt, int32_t n, int32_
   const size_t ids_b = glx_align256((size_t)n * sizeof(int32_t));
   const size_t end_b = ragged ? glx_align256((size_t)num_segments * sizeof(int64_t)) : 0;
   const size_t ptr_b = glx_align256((size_t)(num_rows + 1) * sizeof(int32_t));
-  int rc = lease->alloc(tmp_b + (ragged ? 5 : 4) * ids_b + end_b + ptr_b, s, 1);
+  int rc = lease->alloc(tmp_b + (ragged ? 5 : 4) * ids_b + end_b + ptr_b, s, kSlotRequest);
   if (rc != GLX_OK) return rc;
   char* at = lease->as<char>();
   void* tmp = at;
@@ -238,14 +227,15 @@ int glx_agg_transpose(const int64_t* rows, const int32_t* cnt, int32_t n, int32_
   return GLX_OK;
 }
 
-// Inclusive prefix sums of the clamped counts (the segment ends of a ragged request), in a lease of workspace slot 1.
+// Inclusive prefix sums of the clamped counts (the segment ends of a ragged request), in a lease of workspace slot
+// kSlotRequest.
 int glx_agg_segment_ends(const int32_t* cnt, int32_t num_segments, hipStream_t s, GlxScratch* lease,
                          const int64_t** seg_end) {
   size_t scan_tmp = 0;
   GLX_HIP(rocprim::inclusive_scan(nullptr, scan_tmp, rocprim::make_transform_iterator(cnt, ClampCount()),
                                   static_cast<int64_t*>(nullptr), (size_t)num_segments, rocprim::plus<int64_t>(), s));
   const size_t tmp_b = glx_align256(scan_tmp);
-  int rc = lease->alloc(tmp_b + (size_t)num_segments * sizeof(int64_t), s, 1);
+  int rc = lease->alloc(tmp_b + (size_t)num_segments * sizeof(int64_t), s, kSlotRequest);
   if (rc != GLX_OK) return rc;
   int64_t* ends = reinterpret_cast<int64_t*>(lease->as<char>() + tmp_b);
   GLX_HIP(rocprim::inclusive_scan(lease->p, scan_tmp, rocprim::make_transform_iterator(cnt, ClampCount()), ends,
@@ -271,7 +261,6 @@ struct BwdArgs {
 };
 
 constexpr int kBwdU = 4;  // grad_out rows in flight per lane
-constexpr int kChunk = GLX_COALESCE_CHUNK;
 
 // The term of one list entry for the lane's VEC columns from `col` on: Sum g, Mean g / float(count), Max / Min g where
 // arg names the entry's position (an entry arg does not select adds nothing, and is still a list entry).
@@ -308,64 +297,28 @@ struct BwdTerm {
   }
 };
 
-// G lanes own table row r and walk its whole list (glx_list_fold, glx_lane_groups.h): the ascending-position order.
-// Every row is written, an empty list writes zeros.  SHORT (the chunked order): a row of more than kChunk entries is
-// left to the chunk and combine kernels; every other row gets exactly what the default order gives it.
-template <int OP, int G, int VEC, int DT, bool SHORT>
-__global__ __launch_bounds__(256) void glx_aggregate_bwd_kernel(BwdArgs a) {
-  typedef typename AggElem<DT>::raw raw_t;
-  const int64_t r = blockIdx.x * (int64_t)(256 / G) + threadIdx.x / G;
-  const int c = threadIdx.x & (G - 1);
-  if (r >= a.num_rows) return;  // whole groups leave
-  const int32_t l0 = a.row_ptr[r], l1 = a.row_ptr[r + 1];
-  if (SHORT && l1 - l0 > kChunk) return;
-  const GlxPosList L = {a.pos, a.seg_of, a.fanout};
-  glx_list_fold<G, VEC, kBwdU, DT>(L, l0, l1, c, a.dim, static_cast<raw_t*>(a.grad_x) + r * (int64_t)a.dim,
-                                   [&](int32_t col) { return BwdTerm<OP, VEC>{a, col}; });
-}
-
-// G lanes own work item t of the chunk directory: chunk t - slot0[row] of a long row, at most kChunk entries, folded
-// by the same walk into the item's float32 partial sum.  The launch covers max_items; items past the directory's count
-// leave.
-template <int OP, int G, int VEC>
-__global__ __launch_bounds__(256) void glx_aggregate_bwd_chunk_kernel(BwdArgs a, GlxAggChunks ch) {
-  const int64_t t = blockIdx.x * (int64_t)(256 / G) + threadIdx.x / G;
-  const int c = threadIdx.x & (G - 1);
-  if (t >= ch.max_items || t >= ch.slot0[ch.num_rows]) return;  // whole groups leave
-  const int32_t r = ch.item_row[t];
-  const int32_t l0 = a.row_ptr[r] + ((int32_t)t - ch.slot0[r]) * kChunk, end = a.row_ptr[r + 1];
-  const int32_t l1 = end - l0 > kChunk ? l0 + kChunk : end;
-  const GlxPosList L = {a.pos, a.seg_of, a.fanout};
-  glx_list_fold<G, VEC, kBwdU, GLX_DTYPE_F32>(L, l0, l1, c, a.dim, ch.partial + t * (int64_t)a.dim,
-                                              [&](int32_t col) { return BwdTerm<OP, VEC>{a, col}; });
-}
-
-// the smallest group that covers a row in one tile; rows wider than 64 lanes take column tiles
-template <int OP, int VEC>
-void launch_bwd_vec(const BwdArgs& a, const GlxAggChunks* ch, hipStream_t s) {
-  const int G = glx_group_for((a.dim + VEC - 1) / VEC);
-  const unsigned blocks = (unsigned)((a.num_rows + (256 / G) - 1) / (256 / G));
-  glx_for_group(G, [&](auto g) {
-    constexpr int kG = decltype(g)::value;
-    glx_for_train_dtype(a.dtype, [&](auto t) {
-      if (ch == nullptr) glx_aggregate_bwd_kernel<OP, kG, VEC, decltype(t)::value, false><<<blocks, 256, 0, s>>>(a);
-      else glx_aggregate_bwd_kernel<OP, kG, VEC, decltype(t)::value, true><<<blocks, 256, 0, s>>>(a);
-    });
-    if (ch != nullptr) {
-      const unsigned cblocks = (unsigned)(((int64_t)ch->max_items + (256 / kG) - 1) / (256 / kG));
-      glx_aggregate_bwd_chunk_kernel<OP, kG, VEC><<<cblocks, 256, 0, s>>>(a, *ch);
-    }
-  });
-  if (ch != nullptr) glx_agg_chunks_combine(*ch, a.grad_x, a.dtype, a.dim, VEC == 4, s);
-}
+// the request of glx_row_grad_launch (glx_chunks.h)
+template <int OP>
+struct BwdReq {
+  static constexpr int kU = kBwdU;
+  BwdArgs a;
+  __host__ __device__ const int32_t* row_ptr() const { return a.row_ptr; }
+  __device__ GlxPosList list() const { return {a.pos, a.seg_of, a.fanout}; }
+  __host__ __device__ int64_t num_rows() const { return a.num_rows; }
+  __host__ __device__ int32_t dim() const { return a.dim; }
+  __host__ __device__ void* grad_x() const { return a.grad_x; }
+  int dtype() const { return a.dtype; }
+  template <int VEC>
+  __device__ BwdTerm<OP, VEC> term(int32_t col) const { return {a, col}; }
+};
 
 // ch == nullptr: the default order; otherwise the chunked one over that directory
 template <int OP>
-void launch_bwd(const BwdArgs& a, const GlxAggChunks* ch, hipStream_t s) {
+void launch_bwd(const BwdArgs& a, const GlxChunkDir* ch, hipStream_t s) {
   bool vec4 = a.dim % 4 == 0 && glx_aligned16(a.grad_out) && glx_aligned_vec4(a.grad_x, a.dtype);
   if (OP == GLX_AGG_MAX || OP == GLX_AGG_MIN) vec4 = vec4 && glx_aligned16(a.arg);
-  if (vec4) launch_bwd_vec<OP, 4>(a, ch, s);
-  else launch_bwd_vec<OP, 1>(a, ch, s);
+  if (vec4) glx_row_grad_launch<4>(BwdReq<OP>{a}, ch, s);
+  else glx_row_grad_launch<1>(BwdReq<OP>{a}, ch, s);
 }
 
 // Device pointers only, device selected; num_ids, num_segments, num_rows >= 1.
@@ -376,10 +329,10 @@ int backward_device(int op, const int64_t* rows, const int32_t* cnt, const int32
   GlxAggTranspose t;
   int rc = glx_agg_transpose(rows, cnt, n, num_segments, num_rows, s, &lease, &t);
   if (rc != GLX_OK) return rc;
-  GlxAggChunks chunks;
-  const GlxAggChunks* ch = nullptr;
+  GlxChunkDir chunks;
+  const GlxChunkDir* ch = nullptr;
   if (chunked) {
-    rc = glx_agg_chunks(t, n, num_rows, dim, s, &chunk_lease, &chunks);
+    rc = glx_row_chunk_dir(t, n, num_rows, dim, s, &chunk_lease, &chunks);
     if (rc != GLX_OK) return rc;
     ch = &chunks;
   }
@@ -405,45 +358,33 @@ int backward_device(int op, const int64_t* rows, const int32_t* cnt, const int32
   return GLX_OK;
 }
 
-// ---- the chunk directory and the combine pass of the chunked order ------------------------------------------
-// chunks of row r: ceil(entries / kChunk) for a list of more than kChunk entries, none otherwise (and none for the
-// extra element num_rows, which makes the exclusive scan end with the total)
-struct LongRowChunks {
-  const int32_t* row_ptr;
-  int64_t num_rows;
-  __device__ int32_t operator()(int64_t r) const {
-    if (r >= num_rows) return 0;
-    const int32_t len = row_ptr[r + 1] - row_ptr[r];
-    return len > kChunk ? (len + kChunk - 1) / kChunk : 0;
-  }
-};
-
-// work item t belongs to the last row whose first slot is at or below t (rows without chunks share their successor's)
-__global__ __launch_bounds__(256) void glx_bwd_chunk_items_kernel(const int32_t* __restrict__ slot0, int64_t num_rows,
-                                                                  int32_t max_items, int32_t* __restrict__ item_row) {
+// ---- the items and the combine pass of the chunked order (glx_chunks.h) ---------------------------------------
+// work item t belongs to the last list whose first slot is at or below t (lists without chunks share their successor's)
+__global__ __launch_bounds__(256) void glx_chunk_items_kernel(const int32_t* __restrict__ slot0, int64_t num_lists,
+                                                              int32_t max_items, int32_t* __restrict__ item_list) {
   const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (t >= max_items || t >= slot0[num_rows]) return;
-  int64_t lo = 0, hi = num_rows;  // the first index whose slot0 exceeds t: slot0[num_rows] does
+  if (t >= max_items || t >= slot0[num_lists]) return;
+  int64_t lo = 0, hi = num_lists;  // the first index whose slot0 exceeds t: slot0[num_lists] does
   while (lo < hi) {
     const int64_t mid = lo + ((hi - lo) >> 1);
     if (slot0[mid] > t) hi = mid; else lo = mid + 1;
   }
-  item_row[t] = (int32_t)(lo - 1);
+  item_list[t] = (int32_t)(lo - 1);
 }
 
-// G lanes own work item t and leave unless it is the first of its row; lane c owns columns [VEC c, VEC c + VEC) of
+// G lanes own work item t and leave unless it is the first of its list; lane c owns columns [VEC c, VEC c + VEC) of
 // each column tile.  kBwdU partial-sum loads are issued before the first is added.
 template <int G, int VEC, int DT>
-__global__ __launch_bounds__(256) void glx_bwd_chunk_combine_kernel(GlxAggChunks ch, void* grad_x, int32_t dim) {
+__global__ __launch_bounds__(256) void glx_chunks_combine_kernel(GlxChunkDir ch, void* dst, int32_t dim) {
   typedef float vec_t __attribute__((ext_vector_type(VEC)));
   typedef typename AggElem<DT>::raw raw_t;
   const int64_t t = blockIdx.x * (int64_t)(256 / G) + threadIdx.x / G;
   const int c = threadIdx.x & (G - 1);
-  if (t >= ch.max_items || t >= ch.slot0[ch.num_rows]) return;  // whole groups leave
-  const int32_t r = ch.item_row[t];
-  if (ch.slot0[r] != t) return;
+  if (GLX_CHUNK_IDLE(ch, t)) return;  // whole groups leave
+  const int32_t r = ch.item_list[t];
+  if (!GLX_CHUNK_FIRST(ch, t, r)) return;
   const int32_t chunks = ch.slot0[r + 1] - (int32_t)t;
-  raw_t* const out = static_cast<raw_t*>(grad_x) + r * (int64_t)dim;
+  raw_t* const out = static_cast<raw_t*>(dst) + r * (int64_t)dim;
   for (int32_t col = c * VEC; col < dim; col += G * VEC) {
     vec_t acc;
 #pragma unroll
@@ -468,42 +409,25 @@ __global__ __launch_bounds__(256) void glx_bwd_chunk_combine_kernel(GlxAggChunks
 
 }  // namespace
 
-int glx_agg_chunks(const GlxAggTranspose& t, int32_t n, int64_t num_rows, int32_t dim, hipStream_t s, GlxScratch* lease,
-                   GlxAggChunks* out) {
-  const int32_t max_items = n / (kChunk / 2) + 1;
-  const size_t slot_b = glx_align256((size_t)(num_rows + 1) * sizeof(int32_t));
-  const size_t item_b = glx_align256((size_t)max_items * sizeof(int32_t));
-  const size_t part_b = (size_t)max_items * dim * sizeof(float);
-  int rc = lease->alloc(slot_b + item_b + part_b, s, 2);
-  if (rc != GLX_OK) return rc;
-  char* at = lease->as<char>();
-  int32_t* slot0 = reinterpret_cast<int32_t*>(at);
-  int32_t* item_row = reinterpret_cast<int32_t*>(at + slot_b);
-  const auto counts =
-      rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), LongRowChunks{t.row_ptr, num_rows});
-  GLX_TRY(glx_prim_leased(s, 3, "chunked row gradient: scan the long rows' chunk counts", [&](void* tmp, size_t& bytes) {
-    return rocprim::exclusive_scan(tmp, bytes, counts, slot0, (int32_t)0, (size_t)(num_rows + 1),
-                                   rocprim::plus<int32_t>(), s);
-  }));
-  glx_bwd_chunk_items_kernel<<<(unsigned)(((int64_t)max_items + 255) / 256), 256, 0, s>>>(slot0, num_rows, max_items,
-                                                                                           item_row);
-  out->slot0 = slot0;
-  out->item_row = item_row;
-  out->partial = reinterpret_cast<float*>(at + slot_b + item_b);
-  out->num_rows = num_rows;
-  out->max_items = max_items;
-  return GLX_OK;
+void glx_chunk_items(const int32_t* slot0, int64_t num_lists, int32_t max_items, int32_t* item_list, hipStream_t s) {
+  glx_chunk_items_kernel<<<(unsigned)(((int64_t)max_items + 255) / 256), 256, 0, s>>>(slot0, num_lists, max_items,
+                                                                                       item_list);
 }
 
-void glx_agg_chunks_combine(const GlxAggChunks& ch, void* grad_x, int grad_x_dtype, int32_t dim, bool vec4,
-                            hipStream_t s) {
+int glx_row_chunk_dir(const GlxAggTranspose& t, int32_t n, int64_t num_rows, int32_t dim, hipStream_t s,
+                      GlxScratch* lease, GlxChunkDir* out) {
+  return glx_chunk_dir(GlxRowLists{t.row_ptr}, num_rows, n, dim, kSlotRowChunks,
+                       "chunked row gradient: scan the long rows' chunk counts", s, lease, out);
+}
+
+void glx_chunks_combine(const GlxChunkDir& ch, void* out, int out_dtype, int32_t dim, bool vec4, hipStream_t s) {
   const int G = glx_group_for(vec4 ? dim / 4 : dim);
   const unsigned blocks = (unsigned)(((int64_t)ch.max_items + (256 / G) - 1) / (256 / G));
   glx_for_group(G, [&](auto g) {
-    glx_for_train_dtype(grad_x_dtype, [&](auto t) {
+    glx_for_train_dtype(out_dtype, [&](auto t) {
       constexpr int kG = decltype(g)::value, kDT = decltype(t)::value;
-      if (vec4) glx_bwd_chunk_combine_kernel<kG, 4, kDT><<<blocks, 256, 0, s>>>(ch, grad_x, dim);
-      else glx_bwd_chunk_combine_kernel<kG, 1, kDT><<<blocks, 256, 0, s>>>(ch, grad_x, dim);
+      if (vec4) glx_chunks_combine_kernel<kG, 4, kDT><<<blocks, 256, 0, s>>>(ch, out, dim);
+      else glx_chunks_combine_kernel<kG, 1, kDT><<<blocks, 256, 0, s>>>(ch, out, dim);
     });
   });
 }
@@ -536,7 +460,9 @@ extern "C" int glx_aggregate_arg(const glx_features* f, int op, const int64_t* n
   st.out(&d_arg, arg_out, (size_t)num_segments * f->dim);
   int rc = st.begin();
   GlxScratch lease;
-  if (rc == GLX_OK) rc = lease.alloc(((size_t)num_segments + 1 + kSegScratchExtra) * sizeof(int32_t), st.s, 1);
+  if (rc == GLX_OK) {
+    rc = lease.alloc(((size_t)num_segments + 1 + kSegScratchExtra) * sizeof(int32_t), st.s, kSlotRequest);
+  }
   ArgFwdArgs a;
   if (rc == GLX_OK) rc = glx_segments_prepare(d_seg, num_ids, num_segments, lease.as<int32_t>(), st.s, &a.seg);
   if (rc == GLX_OK) {

@@ -16,15 +16,13 @@
 //                over the columns is the mapping's, so this one is checked against a bound, not bit for bit
 // No float atomics anywhere.
 //   grad_x, chunked  (glx_aggregate_weighted_backward_x_chunked; K5-bwd-chunked) the same terms in a second, opt-in
-//                order: chunks of GLX_COALESCE_CHUNK list entries, a chunk's partial +0.0f plus its terms in ascending
-//                p, grad_x[r] +0.0f plus the partials in ascending chunk.  The directory and the combine pass are
-//                glx_aggregate_grad.hip's (glx_agg_chunks, glx_agg_chunks_combine).
+//                order, over the chunks of a row's list: glx_chunks.h has the order, the directory and the kernels.
 //
 // x is float32 or bfloat16 (the _ex entry points).  A bfloat16 x is upcast as it is loaded -- exact --
 // and folded exactly as above, so emb and grad_w stay float32 and equal the float32 call on the upcast matrix bit for
 // bit (grad_w: the same VEC, plan and tree).  A bfloat16 grad_x is the float32 sum above rounded once per element, to
 // nearest even (glx_f32_to_bf16_bits), in the kernel's final store.  w, grad_out, emb and grad_w are always float32.
-#include "glx_segment_lanes.h"
+#include "glx_chunks.h"
 
 // Two roundings per term: glx_fold_rn (glx_lane_groups.h) pins the product; the pragma is for the front end.
 #pragma clang fp contract(off)
@@ -173,64 +171,28 @@ struct WBwdXTerm {
   }
 };
 
-// The sibling of glx_aggregate_bwd_kernel (glx_aggregate_grad.hip) whose term also fetches the weight of each list
-// entry: G lanes own table row r and walk its whole list (glx_list_fold, glx_lane_groups.h).  Every row is written,
-// an empty list writes zeros.  SHORT (the chunked order): a row of more than GLX_COALESCE_CHUNK entries is left to the
-// chunk and combine kernels.
-template <int OP, int G, int VEC, int DT, bool SHORT>
-__global__ __launch_bounds__(256) void glx_aggregate_weighted_bwd_x_kernel(WBwdXArgs a) {
-  typedef typename AggElem<DT>::raw raw_t;
-  const int64_t r = blockIdx.x * (int64_t)(256 / G) + threadIdx.x / G;
-  const int c = threadIdx.x & (G - 1);
-  if (r >= a.num_rows) return;  // whole groups leave
-  const int32_t l0 = a.t.row_ptr[r], l1 = a.t.row_ptr[r + 1];
-  if (SHORT && l1 - l0 > GLX_COALESCE_CHUNK) return;
-  const GlxPosList L = {a.t.pos, a.t.seg_of, a.t.fanout};
-  glx_list_fold<G, VEC, kWU, DT>(L, l0, l1, c, a.dim, static_cast<raw_t*>(a.grad_x) + r * (int64_t)a.dim,
-                                 [&](int32_t col) { return WBwdXTerm<OP, VEC>{a, col, col / a.C}; });
-}
-
-// G lanes own work item t of the chunk directory: one chunk of a long row, folded by the same walk into the item's
-// float32 partial sum.  The launch covers max_items; items past the directory's count leave.
-template <int OP, int G, int VEC>
-__global__ __launch_bounds__(256) void glx_aggregate_weighted_bwd_x_chunk_kernel(WBwdXArgs a, GlxAggChunks ch) {
-  const int64_t t = blockIdx.x * (int64_t)(256 / G) + threadIdx.x / G;
-  const int c = threadIdx.x & (G - 1);
-  if (t >= ch.max_items || t >= ch.slot0[ch.num_rows]) return;  // whole groups leave
-  const int32_t r = ch.item_row[t];
-  const int32_t l0 = a.t.row_ptr[r] + ((int32_t)t - ch.slot0[r]) * GLX_COALESCE_CHUNK, end = a.t.row_ptr[r + 1];
-  const int32_t l1 = end - l0 > GLX_COALESCE_CHUNK ? l0 + GLX_COALESCE_CHUNK : end;
-  const GlxPosList L = {a.t.pos, a.t.seg_of, a.t.fanout};
-  glx_list_fold<G, VEC, kWU, GLX_DTYPE_F32>(L, l0, l1, c, a.dim, ch.partial + t * (int64_t)a.dim,
-                                            [&](int32_t col) { return WBwdXTerm<OP, VEC>{a, col, col / a.C}; });
-}
-
-template <int OP, int VEC>
-void launch_wbwd_x_vec(const WBwdXArgs& a, const GlxAggChunks* ch, hipStream_t s) {
-  const int G = glx_group_for((a.dim + VEC - 1) / VEC);
-  const unsigned blocks = (unsigned)((a.num_rows + (256 / G) - 1) / (256 / G));
-  glx_for_group(G, [&](auto g) {
-    constexpr int kG = decltype(g)::value;
-    glx_for_train_dtype(a.dtype, [&](auto t) {
-      constexpr int kDT = decltype(t)::value;
-      if (ch == nullptr) glx_aggregate_weighted_bwd_x_kernel<OP, kG, VEC, kDT, false><<<blocks, 256, 0, s>>>(a);
-      else glx_aggregate_weighted_bwd_x_kernel<OP, kG, VEC, kDT, true><<<blocks, 256, 0, s>>>(a);
-    });
-    if (ch != nullptr) {
-      const unsigned cblocks = (unsigned)(((int64_t)ch->max_items + (256 / kG) - 1) / (256 / kG));
-      glx_aggregate_weighted_bwd_x_chunk_kernel<OP, kG, VEC><<<cblocks, 256, 0, s>>>(a, *ch);
-    }
-  });
-  if (ch != nullptr) glx_agg_chunks_combine(*ch, a.grad_x, a.dtype, a.dim, VEC == 4, s);
-}
+// the request of glx_row_grad_launch (glx_chunks.h)
+template <int OP>
+struct WBwdXReq {
+  static constexpr int kU = kWU;
+  WBwdXArgs a;
+  __host__ __device__ const int32_t* row_ptr() const { return a.t.row_ptr; }
+  __device__ GlxPosList list() const { return {a.t.pos, a.t.seg_of, a.t.fanout}; }
+  __host__ __device__ int64_t num_rows() const { return a.num_rows; }
+  __host__ __device__ int32_t dim() const { return a.dim; }
+  __host__ __device__ void* grad_x() const { return a.grad_x; }
+  int dtype() const { return a.dtype; }
+  template <int VEC>
+  __device__ WBwdXTerm<OP, VEC> term(int32_t col) const { return {a, col, col / a.C}; }
+};
 
 // ch == nullptr: the default order; otherwise the chunked one over that directory
 template <int OP>
-void launch_wbwd_x(const WBwdXArgs& a, const GlxAggChunks* ch, hipStream_t s) {
+void launch_wbwd_x(const WBwdXArgs& a, const GlxChunkDir* ch, hipStream_t s) {
   const bool vec4 =
       a.dim % 4 == 0 && a.C % 4 == 0 && glx_aligned16(a.grad_out) && glx_aligned_vec4(a.grad_x, a.dtype);
-  if (vec4) launch_wbwd_x_vec<OP, 4>(a, ch, s);
-  else launch_wbwd_x_vec<OP, 1>(a, ch, s);
+  if (vec4) glx_row_grad_launch<4>(WBwdXReq<OP>{a}, ch, s);
+  else glx_row_grad_launch<1>(WBwdXReq<OP>{a}, ch, s);
 }
 
 // ---- gradient with respect to the weights ---------------------------------------------------------------------
@@ -300,10 +262,10 @@ int glx_weighted_bwd_x(int op, const GlxAggTranspose& t, const float* w, const f
                        int64_t num_rows, int32_t dim, int32_t heads, int32_t num_ids, int32_t num_segments,
                        hipStream_t s, int grad_x_dtype, bool chunked) {
   GlxScratch chunk_lease;  // ends on return: the launches below are queued by then
-  GlxAggChunks chunks;
-  const GlxAggChunks* ch = nullptr;
+  GlxChunkDir chunks;
+  const GlxChunkDir* ch = nullptr;
   if (chunked) {
-    const int rc = glx_agg_chunks(t, num_ids, num_rows, dim, s, &chunk_lease, &chunks);
+    const int rc = glx_row_chunk_dir(t, num_ids, num_rows, dim, s, &chunk_lease, &chunks);
     if (rc != GLX_OK) return rc;
     ch = &chunks;
   }

@@ -977,9 +977,9 @@ int glx_segments_prepare(const int32_t* d_seg, int32_t num_ids, int32_t num_segm
 
 // The transpose of one aggregation request (glx_aggregate_grad.hip), shared by the gradients with respect to the rows:
 // the consumed, in-range positions in a STABLE order by (row, position).  Row r's positions are
-// pos[row_ptr[r] .. row_ptr[r + 1]), ascending.  Everything lives in `lease` (workspace slot 1) and is valid for work
-// queued on `s` until the lease ends.  Device pointers; n, num_segments, num_rows >= 1; cnt may be nullptr (the implied
-// layout of n / num_segments positions per segment).
+// pos[row_ptr[r] .. row_ptr[r + 1]), ascending.  Everything lives in `lease` (kSlotRequest of GlxTrainSlot,
+// glx_chunks.h) and is valid for work queued on `s` until the lease ends.  Device pointers; n, num_segments,
+// num_rows >= 1; cnt may be nullptr (the implied layout of n / num_segments positions per segment).
 struct GlxAggTranspose {
   const int32_t* row_ptr;  // [num_rows + 1] into pos
   const int32_t* pos;      // request positions by (row, position)
@@ -993,32 +993,12 @@ int glx_agg_transpose(const int64_t* rows, const int32_t* cnt, int32_t n, int32_
 // = +0.0f plus fmul_rn(w[p, head], grad_out[s(p)]) (Mean: / count) in ascending p; device pointers, every row written.
 // grad_x holds grad_x_dtype elements (GLX_DTYPE_F32 or GLX_DTYPE_BF16: the float32 sum rounded once in the store).
 // chunked (K5-bwd-chunked): rows of more than GLX_COALESCE_CHUNK entries are reduced chunk by chunk and their partial
-// sums added in chunk order; the directory and the partial sums are leased inside the call (slots 2 and 3), which can
-// therefore fail.  The default mode returns GLX_OK.
+// sums added in chunk order; the directory and the partial sums are leased inside the call (GlxTrainSlot,
+// glx_chunks.h), which can therefore fail.  The default mode returns GLX_OK.
 int glx_weighted_bwd_x(int op, const GlxAggTranspose& t, const float* w, const float* grad_out, void* grad_x,
                        int64_t num_rows, int32_t dim, int32_t heads, int32_t num_ids, int32_t num_segments,
                        hipStream_t s, int grad_x_dtype = GLX_DTYPE_F32, bool chunked = false);
-// The chunk directory of a transpose (glx_aggregate_grad.hip), for the chunked row gradients: row r is LONG when its
-// list has more than GLX_COALESCE_CHUNK entries, and then has ceil(entries / GLX_COALESCE_CHUNK) chunks; a short row
-// has none.  Built on the device from row_ptr; the host learns neither the number of long rows nor of chunks.  A long
-// row of L entries has fewer than L / (GLX_COALESCE_CHUNK / 2) chunks, so n / (GLX_COALESCE_CHUNK / 2) + 1 work items
-// and partial-sum rows hold every request of n positions.  Everything lives in `lease` (workspace slot 2; the scan's
-// temporary passes through slot 3).
-struct GlxAggChunks {
-  const int32_t* slot0;     // [num_rows + 1] exclusive scan of the rows' chunk counts: row r's first work item / partial
-                            // slot; slot0[num_rows] = the number of work items
-  const int32_t* item_row;  // [max_items] the row of work item t; its chunk is t - slot0[row]
-  float* partial;           // [max_items, dim] partial sum of work item t
-  int64_t num_rows;
-  int32_t max_items;        // n / (GLX_COALESCE_CHUNK / 2) + 1
-};
-int glx_agg_chunks(const GlxAggTranspose& t, int32_t n, int64_t num_rows, int32_t dim, hipStream_t s, GlxScratch* lease,
-                   GlxAggChunks* out);
-// One lane group per long row: grad_x[r] = +0.0f plus the row's partial sums in ascending chunk, one fadd_rn each,
-// stored as grad_x_dtype elements (bfloat16: rounded once, here).  vec4: the 4-column mapping of the reduce before it.
-void glx_agg_chunks_combine(const GlxAggChunks& ch, void* grad_x, int grad_x_dtype, int32_t dim, bool vec4,
-                            hipStream_t s);
-// seg_end[num_segments]: inclusive prefix sums of the clamped (>= 0) counts, in `lease` (workspace slot 1).
+// seg_end[num_segments]: inclusive prefix sums of the clamped (>= 0) counts, in `lease` (kSlotRequest).
 int glx_agg_segment_ends(const int32_t* cnt, int32_t num_segments, hipStream_t s, GlxScratch* lease,
                          const int64_t** seg_end);
 

@@ -26,10 +26,8 @@
 //
 // The CHUNKED order (K5-dot-attn-chunked: glx_dot_attention_chunked, glx_dot_attention_backward_chunked; opt-in).  A
 // segment of more than GLX_COALESCE_CHUNK = 256 positions is LONG and is cut into chunks of 256 positions; every other
-// segment goes through the kernels above, restricted to short segments, and keeps the default order's bits.  A chunk
-// directory over the SEGMENTS is built on the device (dot_chunk_dir: one scan, one search per work item, as
-// glx_agg_chunks does over rows); neither the number of long segments nor of chunks reaches the host.  Then, per
-// direction:
+// segment goes through the kernels above, restricted to short segments, and keeps the default order's bits.  The chunk
+// directory is glx_chunks.h's, over the SEGMENTS (GlxSegLists).  Then, per direction:
 //   pass       one lane group per chunk: the dot products of its positions (the logits' / ga_raw), by the default
 //              order's own dot_pass, so logit_out has the default's bits
 //   normalise  one workgroup per long segment (SmBlockWalker): the softmax / its gradient in a fixed tree over the
@@ -37,15 +35,12 @@
 //   fold       one lane group per chunk: partial_j = +0.0f, then the chunk's terms in ascending p (backward: grad_q's
 //              terms, and the chunk's rows of grad_edge)
 //   combine    one lane group per long segment: +0.0f, then one fadd_rn per partial in ascending j
-//              (glx_agg_chunks_combine)
-// A chunk's passes meet across kernel boundaries; inside a kernel a group still lies in one wavefront.  The launches
-// cover num_ids / 128 + 1 work items (a long segment of L positions has fewer than L / 128 chunks) and the partial sums
-// take that many rows of dim floats; idle work items leave when the directory says so.  grad_k / grad_v are the
-// chunked row gradient as it stands (glx_weighted_bwd_x, chunked).
+//              (glx_chunks_combine)
+// A chunk's passes meet across kernel boundaries; inside a kernel a group still lies in one wavefront.  grad_k / grad_v
+// are the chunked row gradient as it stands (glx_weighted_bwd_x, chunked).
 #include <math.h>
 
-#include "glx_prims.h"
-#include "glx_segment_lanes.h"
+#include "glx_chunks.h"
 
 // Two roundings per term of the folds: glx_fold_rn (glx_lane_groups.h) pins the product; the pragma is for the front
 // end.
@@ -54,7 +49,6 @@
 namespace {
 
 constexpr int kWU = 4;  // row loads in flight per lane
-constexpr int kChunk = GLX_COALESCE_CHUNK;  // the chunked order: positions of a long segment to a chunk
 
 struct DotArgs {
   const float* q;          // [num_segments, dim]
@@ -306,8 +300,8 @@ __device__ __forceinline__ void dot_fold_back(const DotArgs& a, int64_t sg, int3
 
 // G lanes own one segment, a workgroup 256 / G consecutive segments.  Three passes, each by the whole group: the
 // logits (one glx_head_dots per position over q and kk), the normalisation, and glx_aggregate_weighted's fold over
-// alpha and vv (dot_fold_out).  SHORT (the chunked order): a segment of more than kChunk positions is left to the chunk
-// kernels below; every other segment gets exactly what the default order gives it.
+// alpha and vv (dot_fold_out).  SHORT (the chunked order): a segment of more than kGlxChunk positions is left to the
+// chunk kernels below; every other segment gets exactly what the default order gives it.
 template <int G, int VEC, bool SUB, bool SHORT>
 __global__ __launch_bounds__(256) void glx_dot_attention_kernel(DotArgs a) {
   const int64_t sg = blockIdx.x * (int64_t)(256 / G) + threadIdx.x / G;
@@ -316,7 +310,7 @@ __global__ __launch_bounds__(256) void glx_dot_attention_kernel(DotArgs a) {
   bool mine = sg < a.seg.num_segments;  // the same answer in every lane of the group
   if (mine) {
     seg_bounds(a.seg, sg, &s0, &s1);
-    if (SHORT) mine = s1 - s0 <= kChunk;
+    if (SHORT) mine = s1 - s0 <= kGlxChunk;
   }
   if (mine) {
     if (s1 > s0) {
@@ -343,7 +337,7 @@ __global__ __launch_bounds__(256) void glx_dot_attention_bwd_kernel(DotArgs a) {
   bool mine = sg < a.seg.num_segments;  // the same answer in every lane of the group
   if (mine) {
     seg_bounds(a.seg, sg, &s0, &s1);
-    if (SHORT) mine = s1 - s0 <= kChunk;
+    if (SHORT) mine = s1 - s0 <= kGlxChunk;
   }
   if (mine) {
     if (s1 > s0) {
@@ -361,81 +355,21 @@ __global__ __launch_bounds__(256) void glx_dot_attention_bwd_kernel(DotArgs a) {
 }
 
 // ---- the chunked order ----------------------------------------------------------------------------------------
-// The chunk directory is a GlxAggChunks whose "rows" are the SEGMENTS: slot0[sg] the first work item / partial slot of
-// segment sg (slot0[num_segments] the number of work items), item_row[t] the segment of work item t, whose chunk is
-// t - slot0[segment].  The combine pass is glx_agg_chunks_combine itself.
+// The chunk directory (glx_chunks.h) is over the SEGMENTS, GlxSegLists{a.seg}: a work item is a chunk of a long
+// segment's positions, its partial sum a row of out or grad_q.
 
-// chunks of segment sg: ceil(L / kChunk) for L > kChunk consumed positions, none otherwise (and none for the extra
-// element num_segments, which makes the exclusive scan end with the total)
-struct LongSegChunks {
-  GlxSegLayout seg;
-  __device__ int32_t operator()(int64_t sg) const {
-    if (sg >= seg.num_segments) return 0;
-    int32_t s0, s1;
-    seg_bounds(seg, sg, &s0, &s1);
-    return s1 - s0 > kChunk ? (s1 - s0 + kChunk - 1) / kChunk : 0;
-  }
-};
-
-// work item t belongs to the last segment whose first slot is at or below t (segments without chunks share their
-// successor's)
-__global__ __launch_bounds__(256) void glx_dot_chunk_items_kernel(const int32_t* __restrict__ slot0,
-                                                                  int32_t num_segments, int32_t max_items,
-                                                                  int32_t* __restrict__ item_seg) {
-  const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (t >= max_items || t >= slot0[num_segments]) return;
-  int32_t lo = 0, hi = num_segments;  // the first index whose slot0 exceeds t: slot0[num_segments] does
-  while (lo < hi) {
-    const int32_t mid = lo + ((hi - lo) >> 1);
-    if (slot0[mid] > t) hi = mid; else lo = mid + 1;
-  }
-  item_seg[t] = lo - 1;
-}
-
-// The directory and the partial sums of one request in one lease of workspace slot 5 (the scan's temporary passes
-// through slot 3, and is given back before glx_weighted_bwd_x wants it).
-int dot_chunk_dir(const GlxSegLayout& seg, int32_t dim, hipStream_t s, GlxScratch* lease, GlxAggChunks* out) {
-  const int32_t max_items = seg.num_ids / (kChunk / 2) + 1;
-  const size_t slot_b = glx_align256((size_t)(seg.num_segments + 1) * sizeof(int32_t));
-  const size_t item_b = glx_align256((size_t)max_items * sizeof(int32_t));
-  const size_t part_b = (size_t)max_items * dim * sizeof(float);
-  const int rc = lease->alloc(slot_b + item_b + part_b, s, 5);
-  if (rc != GLX_OK) return rc;
-  char* const at = lease->as<char>();
-  int32_t* const slot0 = reinterpret_cast<int32_t*>(at);
-  int32_t* const item_seg = reinterpret_cast<int32_t*>(at + slot_b);
-  const auto counts = rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), LongSegChunks{seg});
-  GLX_TRY(glx_prim_leased(s, 3, "chunked dot attention: scan the long segments' chunk counts",
-                          [&](void* tmp, size_t& bytes) {
-                            return rocprim::exclusive_scan(tmp, bytes, counts, slot0, (int32_t)0,
-                                                           (size_t)(seg.num_segments + 1), rocprim::plus<int32_t>(), s);
-                          }));
-  glx_dot_chunk_items_kernel<<<(unsigned)(((int64_t)max_items + 255) / 256), 256, 0, s>>>(slot0, seg.num_segments,
-                                                                                           max_items, item_seg);
-  out->slot0 = slot0;
-  out->item_row = item_seg;
-  out->partial = reinterpret_cast<float*>(at + slot_b + item_b);
-  out->num_rows = seg.num_segments;
-  out->max_items = max_items;
-  return GLX_OK;
-}
-
-// the segment of work item t and the positions [*c0, *c1) of its chunk; false: t is past the directory
-__device__ __forceinline__ bool dot_chunk_of(const DotArgs& a, const GlxAggChunks& ch, int64_t t, int32_t* sg,
+// the segment of work item t and the positions [*c0, *c1) of its chunk (glx_chunk_of); false: t is past the directory
+__device__ __forceinline__ bool dot_chunk_of(const DotArgs& a, const GlxChunkDir& ch, int64_t t, int32_t* sg,
                                              int32_t* c0, int32_t* c1) {
-  if (t >= ch.max_items || t >= ch.slot0[ch.num_rows]) return false;
-  *sg = ch.item_row[t];
-  int32_t s0, s1;
-  seg_bounds(a.seg, *sg, &s0, &s1);
-  *c0 = s0 + ((int32_t)t - ch.slot0[*sg]) * kChunk;
-  *c1 = s1 - *c0 > kChunk ? *c0 + kChunk : s1;
+  if (GLX_CHUNK_IDLE(ch, t)) return false;
+  glx_chunk_of(ch, GlxSegLists{a.seg}, t, sg, c0, c1);
   return true;
 }
 
 // G lanes own work item t: the dot products of its chunk's positions, where the per-segment kernels park theirs (the
 // logits' in logit_out or soft_out; ga_raw in grad_e).  Whole groups leave past the directory.
 template <int G, int VEC, bool SUB, bool BWD>
-__global__ __launch_bounds__(256) void glx_dot_chunk_pass_kernel(DotArgs a, GlxAggChunks ch) {
+__global__ __launch_bounds__(256) void glx_dot_chunk_pass_kernel(DotArgs a, GlxChunkDir ch) {
   const int64_t t = blockIdx.x * (int64_t)(256 / G) + threadIdx.x / G;
   const int c = threadIdx.x & (G - 1);
   int32_t sg, c0, c1;
@@ -448,12 +382,12 @@ __global__ __launch_bounds__(256) void glx_dot_chunk_pass_kernel(DotArgs a, GlxA
 // segment by 256 threads, K5-sm's long-segment walk.  A thread parks and reads back its own items only; what the pass
 // kernel wrote arrived with the kernel boundary.  Every condition is the same in all 256 threads.
 template <bool BWD>
-__global__ __launch_bounds__(256) void glx_dot_chunk_norm_kernel(DotArgs a, GlxAggChunks ch) {
+__global__ __launch_bounds__(256) void glx_dot_chunk_norm_kernel(DotArgs a, GlxChunkDir ch) {
   __shared__ float red[256];
   const int64_t t = blockIdx.x;
-  if (t >= ch.max_items || t >= ch.slot0[ch.num_rows]) return;
-  const int32_t sg = ch.item_row[t];
-  if (ch.slot0[sg] != t) return;
+  if (GLX_CHUNK_IDLE(ch, t)) return;
+  const int32_t sg = ch.item_list[t];
+  if (!GLX_CHUNK_FIRST(ch, t, sg)) return;
   int32_t s0, s1;
   seg_bounds(a.seg, sg, &s0, &s1);
   const SmBlockWalker w = {red};
@@ -468,7 +402,7 @@ __global__ __launch_bounds__(256) void glx_dot_chunk_norm_kernel(DotArgs a, GlxA
 // G lanes own work item t: the fold of its chunk into the item's partial sum, by the per-segment kernels' own walk
 // (backward: grad_q's terms -- unless grad_q is not asked for -- and the chunk's rows of grad_edge).
 template <int G, int VEC, bool BWD>
-__global__ __launch_bounds__(256) void glx_dot_chunk_fold_kernel(DotArgs a, GlxAggChunks ch) {
+__global__ __launch_bounds__(256) void glx_dot_chunk_fold_kernel(DotArgs a, GlxChunkDir ch) {
   const int64_t t = blockIdx.x * (int64_t)(256 / G) + threadIdx.x / G;
   const int c = threadIdx.x & (G - 1);
   int32_t sg, c0, c1;
@@ -480,7 +414,7 @@ __global__ __launch_bounds__(256) void glx_dot_chunk_fold_kernel(DotArgs a, GlxA
 
 // ch == nullptr: the default order, one launch; otherwise the chunked one over that directory
 template <bool BWD, int VEC>
-void dot_launch_vec(DotArgs a, const GlxAggChunks* ch, hipStream_t s) {
+void dot_launch_vec(DotArgs a, const GlxChunkDir* ch, hipStream_t s) {
   const GlxHeadDotPlan plan = glx_head_dot_plan(a.dim, a.C, VEC);
   const int G = plan.G;
   a.hd = plan.hd;
@@ -506,13 +440,13 @@ void dot_launch_vec(DotArgs a, const GlxAggChunks* ch, hipStream_t s) {
     else launch(std::false_type());
   });
   if (ch != nullptr && (!BWD || a.grad_q)) {
-    glx_agg_chunks_combine(*ch, BWD ? a.grad_q : a.out, GLX_DTYPE_F32, a.dim, VEC == 4, s);
+    glx_chunks_combine(*ch, BWD ? a.grad_q : a.out, GLX_DTYPE_F32, a.dim, VEC == 4, s);
   }
 }
 
 // float4 row accesses when every row pointer allows them and a lane's four columns share a head
 template <bool BWD>
-void dot_launch(const DotArgs& a, const GlxAggChunks* ch, hipStream_t s) {
+void dot_launch(const DotArgs& a, const GlxChunkDir* ch, hipStream_t s) {
   bool vec4 = a.C % 4 == 0 && glx_aligned16(a.q) && glx_aligned16(a.k) && glx_aligned16(a.v) && glx_aligned16(a.edge);
   if (BWD) vec4 = vec4 && glx_aligned16(a.grad_out) && glx_aligned16(a.grad_q) && glx_aligned16(a.grad_edge);
   else vec4 = vec4 && glx_aligned16(a.out);
@@ -540,10 +474,12 @@ void dot_launch(const DotArgs& a, const GlxAggChunks* ch, hipStream_t s) {
   GLX_REQUIRE(num_segments == 0 || q != nullptr, "q is NULL");                                                  \
   GLX_REQUIRE(num_rows == 0 || (k != nullptr && v != nullptr), "k or v is NULL")
 
-// Workspace slots.  The default order keeps alpha in slot 2.  The chunked backward calls the chunked
-// glx_weighted_bwd_x, which leases slots 2 and 3 itself while alpha is still being read: the chunked order keeps alpha
-// in slot 4 and its directory and partial sums in slot 5 (dot_chunk_dir).
-constexpr int kAlphaSlot = 2, kAlphaSlotChunked = 4;
+// The segment directory and the partial sums of one request: a lease of slot kSlotSegChunks (GlxTrainSlot,
+// glx_chunks.h, which also says where alpha lives)
+static int dot_chunk_dir(const GlxSegLayout& seg, int32_t dim, hipStream_t s, GlxScratch* lease, GlxChunkDir* out) {
+  return glx_chunk_dir(GlxSegLists{seg}, seg.num_segments, seg.num_ids, dim, kSlotSegChunks,
+                       "chunked dot attention: scan the long segments' chunk counts", s, lease, out);
+}
 
 // the body of glx_dot_attention (chunked == false: its launches, its bits) and of glx_dot_attention_chunked
 static int dot_attention_forward(bool chunked, int device, const float* q, const float* k, const float* v,
@@ -575,7 +511,7 @@ static int dot_attention_forward(bool chunked, int device, const float* q, const
   rc = st.begin();
   if (v == k) a.v = a.k;  // one table: staged once
   GlxScratch lease, alpha, chunk_lease;
-  GlxAggChunks chunks;
+  GlxChunkDir chunks;
   if (rc == GLX_OK) {
     if (num_ids == 0 || num_segments == 0) {  // nothing was consumed: empty segments, positions of no segment
       rc = glx_zero_f32_async(a.out, out_count, st.s);
@@ -584,7 +520,7 @@ static int dot_attention_forward(bool chunked, int device, const float* q, const
     } else {
       rc = glx_seg_layout(cnt ? d_cnt : nullptr, num_ids, num_segments, st.s, &lease, &a.seg);
       if (rc == GLX_OK && drop_p != 0.0f) {
-        rc = alpha.alloc(count * sizeof(float), st.s, chunked ? kAlphaSlotChunked : kAlphaSlot);
+        rc = alpha.alloc(count * sizeof(float), st.s, chunked ? kSlotAlphaChunked : kSlotAlpha);
       }
       if (rc == GLX_OK && chunked) rc = dot_chunk_dir(a.seg, dim, st.s, &chunk_lease, &chunks);
       if (rc == GLX_OK) {
@@ -669,7 +605,7 @@ static int dot_attention_backward(bool chunked, int device, const float* q, cons
   rc = st.begin();
   if (v == k) a.v = a.k;  // one table: staged once
   GlxScratch lease, alpha;
-  GlxAggChunks chunks;
+  GlxChunkDir chunks;
   if (rc == GLX_OK) {
     if (num_ids == 0 || num_segments == 0) {  // nothing was consumed: every output is zeros
       rc = glx_zero_f32_async(a.grad_e, count, st.s);
@@ -683,7 +619,7 @@ static int dot_attention_backward(bool chunked, int device, const float* q, cons
       rc = glx_seg_layout_bwd(want_rows, a.rows, cnt ? d_cnt : nullptr, num_ids, num_segments, num_rows, st.s, &lease,
                               &tr, &a.seg);
       if (rc == GLX_OK && drop_p != 0.0f) {
-        rc = alpha.alloc(count * sizeof(float), st.s, chunked ? kAlphaSlotChunked : kAlphaSlot);
+        rc = alpha.alloc(count * sizeof(float), st.s, chunked ? kSlotAlphaChunked : kSlotAlpha);
       }
       if (rc == GLX_OK) {
         a.num_rows = num_rows;

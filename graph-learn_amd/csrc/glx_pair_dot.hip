@@ -101,8 +101,8 @@ struct PairBwdArgs {
   float default_attr;
 };
 
-// The sibling of glx_aggregate_weighted_bwd_x_kernel with the factor's row gathered too: G lanes own table row r.  Its
-// list of own-side entries, each expanded to own_rep consecutive pairs, is one run of (l1 - l0) * own_rep pairs in
+// The sibling of K5-w's glx_row_grad_kernel (glx_chunks.h) with the factor's row gathered too: G lanes own table row r.
+// Its list of own-side entries, each expanded to own_rep consecutive pairs, is one run of (l1 - l0) * own_rep pairs in
 // ascending p (ascending entries give ascending pairs).  Lane c fetches pair base + c of the run (its number and the
 // other side's row, already tested against the table), every lane reads entry j from lane j; kWU row loads and their
 // g are issued before the first is folded.  Every row is written, an empty list writes zeros.  A bfloat16 x_other is

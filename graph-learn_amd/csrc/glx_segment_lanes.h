@@ -76,7 +76,7 @@ __device__ __forceinline__ bool seg_of_position(const GlxSegLayout& L, int64_t p
 }
 
 // The layout of a request of num_segments >= 1 segments; d_cnt: the counts on the device, or nullptr.  A ragged request
-// scans its counts into `lease` (workspace slot 1).
+// scans its counts into `lease` (kSlotRequest of GlxTrainSlot, glx_chunks.h).
 inline int glx_seg_layout(const int32_t* d_cnt, int32_t num_ids, int32_t num_segments, hipStream_t s, GlxScratch* lease,
                           GlxSegLayout* L) {
   L->seg_end = nullptr;
