@@ -1155,7 +1155,7 @@ struct GlxHostCallSlot {
   GlxHostCallSlot& operator=(const GlxHostCallSlot&) = delete;
 };
 
-// Device-visible alias of a host buffer the caller pinned with glx_host_register, nullptr for anything else
+// Device-visible alias of a host buffer pinned with glx_host_register or taken from glx_host_alloc, nullptr for anything else
 // (pageable memory, and memory pinned by other means: glx trusts its own registry only).  Host-pointer calls let
 // their kernels write results
 // straight into such a buffer -- the response crosses PCIe once, as the kernel's own coalesced stores, with no
@@ -1187,7 +1187,7 @@ static inline hipStream_t glx_host_call_stream(void* s, int device) {
 struct GlxHostStage {
   enum : int {
     ADMIT = 1,          // hold a GlxHostCallSlot for the call
-    DIRECT_PINNED = 2,  // outputs wholly inside a glx_host_register range are written directly (glx_mapped_ptr)
+    DIRECT_PINNED = 2,  // outputs wholly inside a glx_host_register / glx_host_alloc range are written directly (glx_mapped_ptr)
   };
   const bool host;
   const hipStream_t s;

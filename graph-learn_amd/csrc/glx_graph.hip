@@ -64,11 +64,15 @@ extern "C" int glx_device_count(int* count) {
 }
 
 namespace {
-// The ranges pinned through glx_host_register.  Host-pointer calls write straight into a caller buffer only when it
-// lies in one of THESE (glx_mapped_ptr): what the runtime itself reports about an arbitrary pointer also covers
-// ranges other code registered -- and, after unregistrations of ranges that shared pages, was seen to be stale.
+// The ranges pinned through glx_host_register and glx_host_alloc.  Host-pointer calls write straight into a caller
+// buffer only when it lies in one of THESE (glx_mapped_ptr): what the runtime itself reports about an arbitrary pointer
+// also covers ranges other code registered -- and, after unregistrations of ranges that shared pages, was seen to be stale.
+struct PinnedRange {
+  size_t bytes;
+  bool owned;  // allocated by glx_host_alloc (released by glx_host_free), not a caller's range that was registered
+};
 std::mutex g_pinned_mtx;
-std::map<uintptr_t, size_t> g_pinned;
+std::map<uintptr_t, PinnedRange> g_pinned;
 }  // namespace
 
 extern "C" int glx_host_register(void* p, uint64_t bytes) {
@@ -111,7 +115,7 @@ extern "C" int glx_host_register(void* p, uint64_t bytes) {
     return e == hipErrorOutOfMemory ? GLX_RESOURCE_EXHAUSTED : GLX_UNAVAILABLE;
   }
   std::lock_guard<std::mutex> g(g_pinned_mtx);
-  g_pinned[reinterpret_cast<uintptr_t>(p)] = (size_t)bytes;
+  g_pinned[reinterpret_cast<uintptr_t>(p)] = PinnedRange{(size_t)bytes, false};
   return GLX_OK;
 }
 
@@ -119,12 +123,54 @@ extern "C" int glx_host_unregister(void* p) {
   GLX_REQUIRE(p != nullptr, "bad buffer");
   {
     std::lock_guard<std::mutex> g(g_pinned_mtx);
-    g_pinned.erase(reinterpret_cast<uintptr_t>(p));
+    auto it = g_pinned.find(reinterpret_cast<uintptr_t>(p));
+    GLX_REQUIRE(it == g_pinned.end() || !it->second.owned,
+                "glx_host_unregister: the buffer came from glx_host_alloc; release it with glx_host_free");
+    if (it != g_pinned.end()) g_pinned.erase(it);
   }
   hipError_t e = hipHostUnregister(p);
   if (e != hipSuccess) {
     (void)hipGetLastError();
     glx_set_error("hipHostUnregister failed: %s", hipGetErrorString(e));
+    return GLX_UNAVAILABLE;
+  }
+  return GLX_OK;
+}
+
+extern "C" int glx_host_alloc(uint64_t bytes, void** out) {
+  GLX_REQUIRE(out != nullptr, "out is NULL");
+  *out = nullptr;
+  GLX_REQUIRE(bytes > 0, "bad size");
+  int n = 0;
+  int rc = glx_device_count(&n);
+  if (rc != GLX_OK) return rc;
+  void* p = nullptr;
+  hipError_t e = hipHostMalloc(&p, (size_t)bytes, hipHostMallocPortable);
+  if (e != hipSuccess || p == nullptr) {
+    (void)hipGetLastError();
+    glx_set_error("hipHostMalloc(%llu bytes) failed: %s", (unsigned long long)bytes, hipGetErrorString(e));
+    return e == hipErrorOutOfMemory ? GLX_RESOURCE_EXHAUSTED : GLX_UNAVAILABLE;
+  }
+  {
+    std::lock_guard<std::mutex> g(g_pinned_mtx);
+    g_pinned[reinterpret_cast<uintptr_t>(p)] = PinnedRange{(size_t)bytes, true};
+  }
+  *out = p;
+  return GLX_OK;
+}
+
+extern "C" int glx_host_free(void* p) {
+  GLX_REQUIRE(p != nullptr, "bad buffer");
+  {
+    std::lock_guard<std::mutex> g(g_pinned_mtx);
+    auto it = g_pinned.find(reinterpret_cast<uintptr_t>(p));
+    GLX_REQUIRE(it != g_pinned.end() && it->second.owned, "glx_host_free: not a buffer glx_host_alloc returned");
+    g_pinned.erase(it);
+  }
+  hipError_t e = hipHostFree(p);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    glx_set_error("hipHostFree failed: %s", hipGetErrorString(e));
     return GLX_UNAVAILABLE;
   }
   return GLX_OK;
@@ -180,7 +226,8 @@ void* glx_mapped_ptr(const void* host_ptr, size_t bytes) {
     auto it = g_pinned.upper_bound(a);
     if (it == g_pinned.begin()) return nullptr;
     --it;
-    if (a >= it->first + it->second || bytes > it->first + it->second - a) return nullptr;  // not (wholly) in a range glx_host_register pinned
+    const size_t span = it->second.bytes;
+    if (a >= it->first + span || bytes > it->first + span - a) return nullptr;  // not (wholly) in a range pinned here
   }
   void* dev = nullptr;
   if (hipHostGetDevicePointer(&dev, const_cast<void*>(host_ptr), 0) != hipSuccess) {

@@ -38,6 +38,7 @@ AGGREGATOR_IDS = {
 
 EXPORTS = [
     "glx_abi_version", "glx_device_count", "glx_last_error", "glx_host_register", "glx_host_unregister",
+    "glx_host_alloc", "glx_host_free",
     "glx_graph_create", "glx_graph_build", "glx_graph_build_ordered", "glx_graph_destroy", "glx_graph_info", "glx_graph_export_alias",
     "glx_graph_edge_weight_packed", "glx_graph_edge_weight_record_bytes", "glx_graph_row_dir",
     "glx_graph_degrees", "glx_graph_in_degrees", "glx_sample", "glx_sample_ex", "glx_sample_hops",
@@ -146,6 +147,8 @@ def lib():
         L.glx_device_count.argtypes = [ctypes.POINTER(ci)]
         L.glx_host_register.argtypes = [vp, u64]
         L.glx_host_unregister.argtypes = [vp]
+        L.glx_host_alloc.argtypes = [u64, ctypes.POINTER(vp)]
+        L.glx_host_free.argtypes = [vp]
         L.glx_graph_create.argtypes = [ci, i64, i64, vp, vp, vp, vp, vp, ci, vp, ctypes.POINTER(vp)]
         L.glx_graph_build.argtypes = [ci, i64, vp, vp, vp, vp, ci, ci, vp, ctypes.POINTER(vp)]
         L.glx_graph_destroy.argtypes = [vp]
@@ -334,6 +337,19 @@ def device_count():
     n = ctypes.c_int(0)
     _check(lib().glx_device_count(ctypes.byref(n)))
     return n.value
+
+
+def host_alloc(nbytes):
+    """`nbytes` of pinned host memory (glx_host_alloc) as a uint8 numpy array; host-pointer calls write outputs that
+    lie inside it directly.  Views of it must not outlive host_free()."""
+    p = ctypes.c_void_p()
+    _check(lib().glx_host_alloc(nbytes, ctypes.byref(p)))
+    return np.ctypeslib.as_array((ctypes.c_uint8 * nbytes).from_address(p.value))
+
+
+def host_free(block):
+    """releases an array host_alloc() returned"""
+    _check(lib().glx_host_free(ctypes.c_void_p(block.ctypes.data)))
 
 
 def _is_torch(x):

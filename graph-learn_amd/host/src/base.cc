@@ -109,12 +109,12 @@ GLX_TENSOR_KEYS(GLX_DEFINE_TENSOR_KEY)
 // device->host copy into pageable memory bounces through the runtime's staging buffers (one
 // extra pass over every response byte, serialised between the pool threads), a copy into
 // registered memory is a single DMA straight into the response.  BlockPool recycles large
-// blocks (>= 64 KiB, power-of-two classes, at most kPoolCap bytes pinned in all; anonymous mappings of the pool's own,
-// never the malloc heap -- see Take()) across requests and
-// registers each block with the GPU runtime ONCE, when it is first obtained
-// (glx_host_register; pinning costs milliseconds, recycling a pinned block nothing);
-// small tensors use the ordinary heap.  Without a GPU runtime registration fails and the
-// block simply stays pageable.
+// blocks (>= 64 KiB, power-of-two classes, at most kPoolCap bytes pinned in all; pinned memory of the GPU runtime's
+// own, never the malloc heap -- see Take() and NewBlock()) across requests and
+// obtains each block from the GPU runtime ONCE
+// (glx_host_alloc; pinning costs milliseconds, recycling a pinned block nothing);
+// small tensors use the ordinary heap.  Without a GPU runtime the allocation fails and the
+// block is a pageable mapping.
 namespace {
 class BlockPool {
 public:
@@ -149,8 +149,8 @@ public:
       if (posix_memalign(&p, 4096, 1ull << c) != 0) throw std::bad_alloc();
       return p;
     }
-    // The pool's blocks live in anonymous mappings of their OWN, 2 MiB aligned and whole 2 MiB granules -- never in the
-    // malloc heap (round 6).  A process that has hipHostRegister-ed ranges of its heap and ALSO holds heap memory
+    // The pool's blocks are whole 2 MiB granules of pinned memory the runtime allocates (NewBlock; anonymous mappings of
+    // their OWN, 2 MiB aligned, where nothing can be pinned) -- never in the malloc heap (round 6).  A process that has hipHostRegister-ed ranges of its heap and ALSO holds heap memory
     // marked MADV_HUGEPAGE (numpy does that to every array of 4 MiB or more) gets "an illegal memory access" from
     // later pageable host-to-device copies on ROCm 7.0 -- reproduced without any glx code in
     // scripts/r06/repro/hostreg_pageable.hip (registered ranges cut from the heap: a fault within ~50 rounds; cut from
@@ -164,9 +164,8 @@ public:
     std::lock_guard<std::mutex> g(map_mtx_);
     if (bytes_c < kGranule) {
       if (slab_left_ < bytes_c) {
-        slab_ = MapAligned(kGranule, kGranule);
+        slab_ = NewBlock(kGranule, kGranule);
         slab_left_ = kGranule;
-        if (pin_) (void)glx_host_register(slab_, kGranule);  // best effort: an unregistered block is only slower
       }
       void* p = slab_;
       slab_ = static_cast<char*>(slab_) + bytes_c;
@@ -175,8 +174,7 @@ public:
       owned_.insert(p);
       return p;
     }
-    void* p = MapAligned(bytes_c, kGranule);
-    if (pin_) (void)glx_host_register(p, bytes_c);
+    void* p = NewBlock(bytes_c, kGranule);
     {
       std::lock_guard<std::mutex> g2(mtx_);
       owned_.insert(p);
@@ -200,6 +198,15 @@ public:
   }
 
 private:
+  // One block of the pool, never released: pinned memory the GPU runtime allocates itself (glx_host_alloc: page aligned,
+  // outside the heap) -- not every host can pin memory the process already has (glx.h), so the pool no longer maps its
+  // blocks and registers them.  Best effort: without a GPU runtime, beyond what the host lets a process pin, or with
+  // pinning off, the block is an anonymous mapping of the pool's own and stays pageable, which is only slower.
+  void* NewBlock(size_t bytes, size_t align) {
+    void* p = nullptr;
+    if (pin_ && glx_host_alloc(bytes, &p) == GLX_OK) return p;
+    return MapAligned(bytes, align);
+  }
   // `bytes` (a multiple of `align`) of zero pages in a private anonymous mapping, aligned to `align`; never unmapped
   static void* MapAligned(size_t bytes, size_t align) {
     void* m = mmap(nullptr, bytes + align, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);

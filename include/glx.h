@@ -120,9 +120,18 @@ GLX_API const char* glx_last_error(void);
  * scripts/r06/repro/hostreg_pageable.hip shows it with the runtime alone (registered ranges cut from the heap: a fault
  * within ~50 rounds of copies; cut from mappings of their own: none in 600), unregistered or not.  The C++ layer's
  * response pool (host/src/base.cc) follows the rule; long-lived pools that never unregister are the intended use.
- * A range inside the process's brk heap is refused with GLX_INVALID_ARGUMENT (GLX_HOST_REGISTER_HEAP=1 lifts the check). */
+ * A range inside the process's brk heap is refused with GLX_INVALID_ARGUMENT (GLX_HOST_REGISTER_HEAP=1 lifts the check).
+ * Not every host can pin memory a process already has (virtual machines with a passed-through GPU: hipHostRegister fails
+ * with "invalid value"): glx_host_register reports GLX_UNAVAILABLE there and names the runtime call; take the buffer
+ * from glx_host_alloc instead. */
 GLX_API int glx_host_register(void* p, uint64_t bytes);
 GLX_API int glx_host_unregister(void* p);
+/* Pinned host memory of glx's own (hipHostMalloc, page aligned, visible to every device), for hosts where
+ * glx_host_register is unavailable and for callers who need not bring their own memory.  The block counts as one
+ * registered range: host-pointer calls write outputs that lie wholly inside it directly.  glx_host_free releases a
+ * block of glx_host_alloc and nothing else (GLX_INVALID_ARGUMENT); glx_host_unregister refuses such a block. */
+GLX_API int glx_host_alloc(uint64_t bytes, void** out);
+GLX_API int glx_host_free(void* p);
 
 /* ---- graph storage: replaces GraphStorage::GetNeighbors / GetOutEdges /
  * GetEdgeWeight (graph_storage.h:40-57) + CompressedMemoryAdjMatrix

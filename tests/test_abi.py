@@ -80,6 +80,7 @@ def test_distributed_entry_points_fail_loudly_without_gpu():
     assert L.glx_plan_create(None, 1, 0, None, 1, 1, 0, 0, None, 0, 0.0, ctypes.byref(h)) == 3
     a = np.zeros(16, np.int64)
     assert L.glx_host_register(ctypes.c_void_p(a.ctypes.data), a.nbytes) == 14
+    assert L.glx_host_alloc(4096, ctypes.byref(h)) == 14 and not h.value
 
 
 def test_argument_validation_needs_no_gpu():

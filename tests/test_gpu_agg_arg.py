@@ -6,8 +6,6 @@ padded) tables, special values, the segment bookkeeping, the chain into the back
 Tolerance 0: emb bit for bit (sign of zero and NaN payloads included), cnt and arg as integers.  Every call writes into
 canaries (emb NaN, cnt and arg -7), so an element the kernel leaves out shows; every call is made twice; every case is
 checked against agg_backward_ref.fold_arg over the float32 values of the table and against Features.aggregate."""
-import ctypes
-import mmap
 import os
 import subprocess
 import sys
@@ -60,18 +58,13 @@ def _canaries(S, D):
 
 
 class Pinned:
-    """One glx_host_register-ed range (a private anonymous mapping of its own, as test_gpu_host_stage.py pins its
-    buffers); outputs are carved out of it 4 bytes past a 16-byte boundary: the directly written pinned path."""
+    """One range of pinned host memory (glx_host_alloc, as test_gpu_host_stage.py pins its buffers); outputs are
+    carved out of it 4 bytes past a 16-byte boundary: the directly written pinned path."""
     SPAN = 4 << 20
 
     def __init__(self):
-        gran = 2 << 20
-        self.mm = mmap.mmap(-1, self.SPAN + gran, flags=mmap.MAP_PRIVATE | mmap.MAP_ANONYMOUS)
-        raw = np.frombuffer(self.mm, np.uint8)
-        off = (-raw.ctypes.data) % gran
-        self.raw = raw[off:off + self.SPAN]
-        rc = glx.lib().glx_host_register(ctypes.c_void_p(self.raw.ctypes.data), self.SPAN)
-        assert rc == 0, glx.lib().glx_last_error()
+        self.raw = glx.host_alloc(self.SPAN)
+        assert self.raw.ctypes.data % 16 == 0
 
     def carve(self, arrays):
         out, at = [], 0
@@ -86,9 +79,8 @@ class Pinned:
         return tuple(out)
 
     def close(self):
-        assert glx.lib().glx_host_unregister(ctypes.c_void_p(self.raw.ctypes.data)) == 0
+        glx.host_free(self.raw)
         del self.raw
-        self.mm = None
 
 
 @pytest.fixture(scope="module")
@@ -194,7 +186,7 @@ def test_unroll_tail_and_long_segments(dim, op):
 @pytest.mark.parametrize("dim", cases.MISALIGNED_DIMS)
 def test_misaligned_pointers_equal_the_aligned_result(dim, how, op, pinned):
     """a multiple of 4 forced down the scalar path (table, emb or arg 4 bytes off; numpy outputs; numpy outputs 4 bytes
-    into a registered range, written directly), at the segment counts of the scalar path's G"""
+    into a pinned range, written directly), at the segment counts of the scalar path's G"""
     for case in cases.launch_path_cases(dim, True):
         aligned = check_view(case, OPS[op])
         assert _same(check_view(case, OPS[op], how, pinned), aligned), (case, how)

@@ -1,13 +1,12 @@
-"""Host-pointer staging (GlxHostStage) of every per-request entry point: pageable numpy buffers, numpy buffers pinned
-with glx_host_register, and torch device tensors give bit-identical answers, size-dependent responses included; empty
+"""Host-pointer staging (GlxHostStage) of every per-request entry point: pageable numpy buffers, numpy buffers in pinned
+memory of glx_host_alloc, and torch device tensors give bit-identical answers, size-dependent responses included; empty
 requests work; a request refused after its staging began leaves the thread's workspace lease free for the next one; two
 host threads on one device do not disturb each other.
 
 The pinned variant runs in a process of its own (this file as a script), like tests/scripts/pinned_host_check.py: pinned
-ranges are whole anonymous mappings, and the process ends right after it unregisters them."""
+ranges are whole blocks of glx_host_alloc, and the process ends right after it frees them."""
 import ctypes
 import itertools
-import mmap
 import os
 import subprocess
 import sys
@@ -206,14 +205,10 @@ def _pinned_main():
 
     def pinned(a):
         a = np.ascontiguousarray(a)
-        span = max((a.nbytes + 4095) // 4096 * 4096, 4096)
-        gran = 2 << 20  # whole pages of an anonymous mapping of their own, never a range of the malloc heap
-        mm = mmap.mmap(-1, span + gran, flags=mmap.MAP_PRIVATE | mmap.MAP_ANONYMOUS)
-        raw = np.frombuffer(mm, np.uint8)
-        off = (-raw.ctypes.data) % gran
-        b = raw[off:off + a.nbytes].view(a.dtype).reshape(a.shape)
-        assert L.glx_host_register(ctypes.c_void_p(b.ctypes.data), span) == 0, L.glx_last_error()
-        owners.append((mm, raw, b))
+        span = max((a.nbytes + 4095) // 4096 * 4096, 4096)  # whole pages of pinned memory of their own (glx_host_alloc)
+        raw = glx.host_alloc(span)
+        b = raw[:a.nbytes].view(a.dtype).reshape(a.shape)
+        owners.append(raw)
         b[...] = a
         return b
 
@@ -237,8 +232,8 @@ def _pinned_main():
     look = pinned(np.zeros((n, D), np.float32))
     assert L.glx_lookup(f._h, vp(src.ctypes.data), n, ctypes.c_float(0.0), vp(look.ctypes.data), glx.PTR_HOST, None) == 0
     assert look.tobytes() == want["lookup"].tobytes()
-    for _, _, b in owners:
-        assert L.glx_host_unregister(ctypes.c_void_p(b.ctypes.data)) == 0
+    for raw in owners:
+        glx.host_free(raw)
     print("PINNED_STAGE_OK")
 
 

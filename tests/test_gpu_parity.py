@@ -768,9 +768,9 @@ def test_alias_tables_of_long_and_odd_rows_bit_exact():
 
 
 def test_pinned_host_buffers_are_written_directly():
-    """Host-pointer calls write their results straight into caller buffers pinned with glx_host_register (no
-    staging copy); the answers equal those of pageable buffers, for sampling (plain and filtered) and aggregation,
-    and registration can be undone.  The body (tests/scripts/pinned_host_check.py) runs in a process of its own: after
+    """Host-pointer calls write their results straight into pinned caller buffers (glx_host_alloc; glx_host_register
+    where the runtime can pin memory the process already has) with no staging copy; the answers equal those of pageable
+    buffers, for sampling (plain and filtered) and aggregation, and the pinning can be undone.  The body (tests/scripts/pinned_host_check.py) runs in a process of its own: after
     hipHostUnregister the ROCm 7.0 runtime was seen to fault on later pageable copies of the same process -- once in
     ~10 runs of this suite the NEXT test's first host-to-device copy returned "an illegal memory access" (or the process
     aborted) and took every later GPU test with it.  GLX_TEST_PINNED_INPROC=1 runs the body here (scripts/r06/crash_hunt.sh)."""

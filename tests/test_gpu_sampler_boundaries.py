@@ -14,8 +14,6 @@ Each case below sits on both sides of one of those choices:
   * rows longer than 2^24, where the float cast of the alias variate decides the slot;
   * the multi-hop driver at the new fanouts.
 """
-import ctypes
-import mmap
 import os
 import subprocess
 import sys
@@ -295,14 +293,14 @@ def device_graph(og):
 def _offset_outputs_check(backend):
     """Every slot-kernel sampler at even and odd k into outputs that start 8 bytes past a 16-byte boundary, against the
     oracle and the same call into fresh outputs; the elements on either side of the outputs stay untouched.
-    backend: "torch" (device pointers: the kernel writes at the offset), "pinned" (numpy buffers in a range registered
-    with glx_host_register: the kernel writes straight into them, at the offset), "numpy" (pageable: staged through an
+    backend: "torch" (device pointers: the kernel writes at the offset), "pinned" (numpy buffers in a range of
+    glx_host_alloc: the kernel writes straight into them, at the offset), "numpy" (pageable: staged through an
     aligned device workspace; only the host copy lands at the offset)."""
     import torch
     orc = Oracle()
     og = make_graph(orc, [0, 1, 2, 3, 5, 8, 17, 40, 97, 300], seed=5)
     dev = device_graph(og)
-    L, owners = glx.lib(), []
+    owners = []
 
     def buffer(n):
         if backend == "torch":
@@ -310,15 +308,10 @@ def _offset_outputs_check(backend):
             return buf, (1 if buf.data_ptr() % 16 == 0 else 2)
         if backend == "numpy":
             buf = np.full(n + 4, -111, np.int64)
-        else:  # whole pages of an anonymous mapping of its own, never a range of the malloc heap (include/glx.h)
-            span = ((n + 4) * 8 + 4095) // 4096 * 4096
-            gran = 2 << 20
-            mm = mmap.mmap(-1, span + gran, flags=mmap.MAP_PRIVATE | mmap.MAP_ANONYMOUS)
-            raw = np.frombuffer(mm, np.uint8)
-            o = (-raw.ctypes.data) % gran
-            buf = raw[o:o + (n + 4) * 8].view(np.int64)
-            assert L.glx_host_register(ctypes.c_void_p(buf.ctypes.data), span) == 0, L.glx_last_error()
-            owners.append((mm, raw, buf))
+        else:  # whole pages of pinned memory of its own (glx_host_alloc)
+            raw = glx.host_alloc(((n + 4) * 8 + 4095) // 4096 * 4096)
+            buf = raw[:(n + 4) * 8].view(np.int64)
+            owners.append(raw)
             buf[...] = -111
         return buf, (1 if buf.ctypes.data % 16 == 0 else 2)
 
@@ -343,8 +336,8 @@ def _offset_outputs_check(backend):
             for buf, off in ((host(bn), on), (host(be), oe)):
                 assert (buf[:off] == -111).all() and (buf[off + n:] == -111).all(), (name, pad, k)
     dev.close()
-    for _, _, b in owners:
-        assert L.glx_host_unregister(ctypes.c_void_p(b.ctypes.data)) == 0
+    for raw in owners:
+        glx.host_free(raw)
     print("OFFSET_OUTPUTS_OK")
 
 
@@ -352,7 +345,7 @@ def _offset_outputs_check(backend):
 def test_slot_samplers_into_outputs_offset_by_one_element(backend):
     """The pair store of glx_sample_slots_kernel is one 16-byte store when the pair's address is 16-byte aligned and two
     8-byte stores otherwise: outputs that start 8 bytes past a 16-byte boundary take the second form for every pair
-    (device pointers and pinned host buffers; pageable host buffers are staged).  Pinned buffers are registered in a
+    (device pointers and pinned host buffers; pageable host buffers are staged).  Pinned buffers are allocated in a
     process of their own (this file as a script), like tests/test_gpu_host_stage.py's."""
     if backend != "pinned":
         _offset_outputs_check(backend)
