@@ -30,7 +30,7 @@ Exits non-zero unless two runs give the same bits and the ids equal the float64 
 and two index searches give the same bits, and the index with every list probed equals the exact search bit for bit;
 with --index ivfpq and --refine > 0: and every distance the coded index returns is the exact search's for that id).
 Usage: python examples/eval_recall.py [--items 4000] [--users 1000] [--dim 16] [--k 10]
-                                      [--index flat|ivf|ivfpq] [--nlist 64] [--nprobe 4] [--m 4] [--refine 100]
+                                      [--index flat|ivf|ivfpq] [--nlist 64] [--nprobe 4] [--schedule query|list] [--m 4] [--refine 100]
                                       [--dtype float32|bfloat16|float16|float8_e4m3fn|float8_e5m2]"""
 import argparse
 import math
@@ -83,6 +83,8 @@ def main():
     ap.add_argument("--index", choices=("flat", "ivf", "ivfpq"), default="flat")
     ap.add_argument("--nlist", type=int, default=64)
     ap.add_argument("--nprobe", type=int, default=4)
+    ap.add_argument("--schedule", choices=("query", "list"), default="query",
+                    help="with --index ivf: the IVF-Flat search's schedule (both return the same bits)")
     ap.add_argument("--m", type=int, default=4)
     ap.add_argument("--refine", type=int, default=100)
     ap.add_argument("--dtype", choices=sorted(dict(glx.FEATURE_DTYPES, **glx.FP8_FEATURE_DTYPES)), default="float32")
@@ -120,10 +122,10 @@ def main():
                 ok = ok and same_bits
             if index is None:
                 continue
-            got, gdist = index.search(dq, a.k, metric, nprobe=a.nprobe)
-            got2, gdist2 = index.search(dq, a.k, metric, nprobe=a.nprobe)
+            got, gdist = index.search(dq, a.k, metric, nprobe=a.nprobe, schedule=a.schedule)
+            got2, gdist2 = index.search(dq, a.k, metric, nprobe=a.nprobe, schedule=a.schedule)
             same_bits = bool(torch.equal(got, got2) and torch.equal(gdist.view(torch.int32), gdist2.view(torch.int32)))
-            full, fdist = index.search(dq, a.k, metric, nprobe=a.nlist)
+            full, fdist = index.search(dq, a.k, metric, nprobe=a.nlist, schedule=a.schedule)
             all_lists = bool(torch.equal(full, ids) and torch.equal(fdist.view(torch.int32), dist.view(torch.int32)))
             r, n, h = metrics(got, truth, a.k)
             vs_flat = (got[:, :, None] == ids[:, None, :]).any(1).float().mean().item()

@@ -1632,6 +1632,7 @@ extern "C" int glx_tune(const char* name, int32_t value) {
     else if (strcmp(name, "idmap_hash_only") == 0) side = &sk.idmap_hash_only;
     else if (strcmp(name, "knn_chunk_rows") == 0) side = &sk.knn_chunk_rows;
     else if (strcmp(name, "knn_query_block") == 0) side = &sk.knn_query_block;
+    else if (strcmp(name, "knn_list_cand_cap") == 0) side = &sk.knn_list_cand_cap;
     else if (strcmp(name, "resolve_ids") == 0) side = &sk.resolve_ids;
     else if (strcmp(name, "resolve_blocks") == 0) side = &sk.resolve_blocks;
     else if (strcmp(name, "resolve_set_share") == 0) side = &sk.resolve_set_share;

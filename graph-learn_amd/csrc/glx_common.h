@@ -399,6 +399,7 @@ struct GlxSideKnobs {
   std::atomic<int64_t> idmap_hash_only{-1};       // GLX_IDMAP_HASH_ONLY (set = 1): feature tables keep a hash table even for arithmetic ids (A/B)
   std::atomic<int64_t> knn_chunk_rows{-1};        // GLX_KNN_CHUNK_ROWS=n: table rows per chunk of a KNN search, the first chunk included (default: 8192 to 2^18 by the number of queries, first 2048)
   std::atomic<int64_t> knn_query_block{-1};       // GLX_KNN_QUERY_BLOCK=n: queries per pass over the table (default: what the candidate workspace budget holds)
+  std::atomic<int64_t> knn_list_cand_cap{-1};     // GLX_KNN_LIST_CAND_CAP=n: candidate keys per query of the list-major IVF-Flat search (test / probe aid; it only shrinks the default: what the candidate workspace budget holds)
 };
 GlxSideKnobs& glx_side_knobs();  // glx_graph.hip
 

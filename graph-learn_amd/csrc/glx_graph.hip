@@ -40,6 +40,7 @@ GlxSideKnobs& glx_side_knobs() {
     if (getenv("GLX_IDMAP_HASH_ONLY")) k.idmap_hash_only = 1;
     if (const char* e = getenv("GLX_KNN_CHUNK_ROWS")) k.knn_chunk_rows = atoll(e);
     if (const char* e = getenv("GLX_KNN_QUERY_BLOCK")) k.knn_query_block = atoll(e);
+    if (const char* e = getenv("GLX_KNN_LIST_CAND_CAP")) k.knn_list_cand_cap = atoll(e);
     if (const char* e = getenv("GLX_RESOLVE_IDS")) k.resolve_ids = atoll(e);
     if (const char* e = getenv("GLX_RESOLVE_BLOCKS")) k.resolve_blocks = atoll(e);
     if (const char* e = getenv("GLX_RESOLVE_SET_SHARE")) k.resolve_set_share = atoll(e);

@@ -264,8 +264,24 @@ void knn_finish(const KnnArgs& a, const glx_features* f, int64_t* d_ids, float* 
 // glx_knn_ivf.hip
 // keys[n] = kNoKey
 void knn_ivf_fill(uint64_t* keys, int64_t n, hipStream_t s);
-// run[q] = the KP smallest of run[q] and part[q, P, KP], q < nq
-void knn_ivf_fold(uint64_t* run, const uint64_t* part, int32_t nq, int32_t P, int32_t KP, hipStream_t s);
+// run[q] = the KP smallest of run[q] and part[q, P, KP], q < nq; with `only`, of the queries with only[q] != 0
+void knn_ivf_fold(uint64_t* run, const uint64_t* part, int32_t nq, int32_t P, int32_t KP, hipStream_t s,
+                  const int32_t* only = nullptr);
+struct KnnIvfScan {
+  KnnTable t;
+  const float* queries;      // [nq, dim] of this query block
+  const float* qn;           // [nq] (L2)
+  const float* xn;           // [num_rows] (L2)
+  const int32_t* list_ptr;   // [nlist + 1]
+  const int32_t* list_rows;  // [num_rows]
+  const int64_t* probe;      // [nq, nprobe] the lists of every query, best first; nullptr: probe slot p is list p
+  const int32_t* only;       // [nq] or nullptr: a workgroup of a query with only[q] == 0 returns at once
+  uint64_t* part;            // [nq, P, KP] the sorted list of every (query, probe slot) of this pass, kNoKey = empty
+  int32_t nlist, nprobe, p0, P, KP, metric;
+};
+
+// knn_ivf_scan_kernel over nq queries x sc.P probe slots from sc.p0 on: part[q, slot] = the KP best keys of the slot's list
+int knn_ivf_scan(const KnnIvfScan& sc, int32_t nq, hipStream_t s);
 // both index searches' checks of nprobe, in the order the entry points report them (ix == nullptr: "index is NULL")
 int knn_ivf_check_nprobe(const glx_knn_ivf* ix, int32_t nprobe, int32_t num_queries);
 
@@ -324,6 +340,12 @@ int knn_ivf_passes(const glx_knn_ivf* ix, int metric, const float* d_q, int32_t 
   }
   return GLX_OK;
 }
+
+// glx_knn_ivf_list.hip
+// the IVF-Flat search under GLX_KNN_SCHED_LIST on device pointers (workspace slots 2 and 3): the bits of the
+// query-major knn_ivf_search_device
+int knn_ivf_search_list_device(const glx_knn_ivf* ix, int metric, const float* d_q, int32_t num_queries, int32_t k,
+                               int32_t nprobe, int64_t* d_ids, float* d_dist, hipStream_t s);
 
 // ---- entry points -------------------------------------------------------------------------------------------------
 #define GLX_KNN_REQUIRE()                                                                                      \

@@ -17,6 +17,8 @@
 // knn_score_gathered.  The keys of 1,024 rows form one sorted batch that is merged into the slot's KP-entry list
 // (knn_sort_batch / knn_merge_batch: the body of knn_fold); knn_ivf_fold_kernel then folds a query's slot lists into
 // its running list and knn_finish_kernel turns keys into (id, dist).  No counters, no atomics of any kind.
+// glx_knn_ivf_search_ex's other schedule, list-major on the matrix cores, is glx_knn_ivf_list.hip; it reaches the scan
+// and the fold here through knn_ivf_scan and knn_ivf_fold (`only`: the queries it redoes query-major).
 #include <vector>
 
 #include "glx_knn.h"
@@ -84,21 +86,10 @@ __global__ __launch_bounds__(256) void knn_ivf_widen_kernel(const int32_t* __res
   if (i < n) out[i] = in[i];
 }
 
-struct KnnIvfScan {
-  KnnTable t;
-  const float* queries;      // [nq, dim] of this query block
-  const float* qn;           // [nq] (L2)
-  const float* xn;           // [num_rows] (L2)
-  const int32_t* list_ptr;   // [nlist + 1]
-  const int32_t* list_rows;  // [num_rows]
-  const int64_t* probe;      // [nq, nprobe] the lists of every query, best first; nullptr: probe slot p is list p
-  uint64_t* part;            // [nq, P, KP] the sorted list of every (query, probe slot) of this pass, kNoKey = empty
-  int32_t nlist, nprobe, p0, P, KP, metric;
-};
-
 // The KP best keys of one list for one query.  Block b serves query b / P and probe slot p0 + b % P.
 template <int DT>
 __global__ __launch_bounds__(kSelThreads) void knn_ivf_scan_kernel(KnnIvfScan a) {
+  if (a.only != nullptr && a.only[blockIdx.x / (uint32_t)a.P] == 0) return;  // uniform: not this query's path
   __shared__ float Bs[kBK][kIvfLd];
   __shared__ float qs[kBK];
   __shared__ int64_t rbase[kIvfRows];
@@ -137,10 +128,11 @@ __global__ __launch_bounds__(kSelThreads) void knn_ivf_scan_kernel(KnnIvfScan a)
 // run[q] = the KP smallest of run[q] and the P * KP keys of the query's slot lists; one workgroup per query
 __global__ __launch_bounds__(kSelThreads) void knn_ivf_fold_kernel(uint64_t* __restrict__ run_all,
                                                                    const uint64_t* __restrict__ part, int32_t P,
-                                                                   int32_t KP) {
+                                                                   int32_t KP, const int32_t* __restrict__ only) {
   __shared__ uint64_t srun[kSortN];
   __shared__ uint64_t v[kSortN];
   const int q = blockIdx.x, t = threadIdx.x;
+  if (only != nullptr && only[q] == 0) return;  // uniform: the query's slot lists were not scanned
   uint64_t* const run = run_all + (int64_t)q * KP;
   const uint64_t* const mine = part + (int64_t)q * P * KP;
   for (int i = t; i < KP; i += kSelThreads) srun[i] = run[i];
@@ -154,8 +146,15 @@ void knn_ivf_fill(uint64_t* keys, int64_t n, hipStream_t s) {
   knn_ivf_fill_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(keys, n);
 }
 
-void knn_ivf_fold(uint64_t* run, const uint64_t* part, int32_t nq, int32_t P, int32_t KP, hipStream_t s) {
-  knn_ivf_fold_kernel<<<(unsigned)nq, kSelThreads, 0, s>>>(run, part, P, KP);
+void knn_ivf_fold(uint64_t* run, const uint64_t* part, int32_t nq, int32_t P, int32_t KP, hipStream_t s,
+                  const int32_t* only) {
+  knn_ivf_fold_kernel<<<(unsigned)nq, kSelThreads, 0, s>>>(run, part, P, KP, only);
+}
+
+int knn_ivf_scan(const KnnIvfScan& sc, int32_t nq, hipStream_t s) {
+  int rc = GLX_OK;
+  GLX_KNN_LAUNCH_DT(&rc, sc.t.dtype, knn_ivf_scan_kernel, (unsigned)((int64_t)nq * sc.P), kSelThreads, s, sc);
+  return rc;
 }
 
 static int knn_ivf_search_device(const glx_knn_ivf* ix, int metric, const float* d_q, int32_t num_queries, int32_t k,
@@ -206,7 +205,8 @@ static int knn_ivf_search_device(const glx_knn_ivf* ix, int metric, const float*
         sc.qn = qn + q0;
         sc.p0 = p0;
         sc.P = P;
-        GLX_KNN_LAUNCH_DT(&launch_rc, a.t.dtype, knn_ivf_scan_kernel, (unsigned)((int64_t)nq * P), kSelThreads, s, sc);
+        const int scan_rc = knn_ivf_scan(sc, nq, s);
+        if (scan_rc != GLX_OK) launch_rc = scan_rc;
       },
       [&](int64_t q0, int32_t nq) {
         a.nq = nq;
@@ -387,15 +387,25 @@ extern "C" int glx_knn_ivf_export(const glx_knn_ivf* ix, float* centroids_out, i
   return st.finish(rc);
 }
 
-extern "C" int glx_knn_ivf_search(const glx_knn_ivf* ix, int metric, const float* queries, int32_t num_queries, int32_t k,
-                                  int32_t nprobe, int64_t* ids_out, float* dist_out, int ptr_kind, void* stream) {
+extern "C" int glx_knn_ivf_search_ex(const glx_knn_ivf* ix, int metric, const float* queries, int32_t num_queries,
+                                     int32_t k, int32_t nprobe, int schedule, int64_t* ids_out, float* dist_out,
+                                     int ptr_kind, void* stream) {
   GLX_KNN_REQUIRE();
   const int rc = knn_ivf_check_nprobe(ix, nprobe, num_queries);
   if (rc != GLX_OK) return rc;
+  GLX_REQUIRE(schedule == GLX_KNN_SCHED_QUERY || schedule == GLX_KNN_SCHED_LIST,
+              "schedule must be GLX_KNN_SCHED_QUERY (0) or GLX_KNN_SCHED_LIST (1), got %d", schedule);
   return knn_search_entry(ix->device, ix->dim, queries, num_queries, k, ids_out, dist_out, ptr_kind, stream,
                           [&](const float* d_q, int64_t* d_ids, float* d_dist, hipStream_t s) {
-                            return knn_ivf_search_device(ix, metric, d_q, num_queries, k, nprobe, d_ids, d_dist, s);
+                            return (schedule == GLX_KNN_SCHED_LIST ? knn_ivf_search_list_device : knn_ivf_search_device)(
+                                ix, metric, d_q, num_queries, k, nprobe, d_ids, d_dist, s);
                           });
+}
+
+extern "C" int glx_knn_ivf_search(const glx_knn_ivf* ix, int metric, const float* queries, int32_t num_queries, int32_t k,
+                                  int32_t nprobe, int64_t* ids_out, float* dist_out, int ptr_kind, void* stream) {
+  return glx_knn_ivf_search_ex(ix, metric, queries, num_queries, k, nprobe, GLX_KNN_SCHED_QUERY, ids_out, dist_out,
+                               ptr_kind, stream);
 }
 
 int knn_ivf_check_nprobe(const glx_knn_ivf* ix, int32_t nprobe, int32_t num_queries) {

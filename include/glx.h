@@ -533,6 +533,23 @@ GLX_API int glx_knn_merge(int device, int metric, int32_t num_parts, const int64
  * num_queries * k < 2^31 and num_queries * nprobe < 2^31; float32 queries; one GPU; not under graph capture.  No float
  * atomics and no counters: the same inputs give the same bits on every call.  glx_tune "knn_query_block" may shrink
  * the queries served per pass (never grow them past the 256 MiB workspace budget); the bits do not depend on it.
+ * glx_knn_ivf_search_ex: glx_knn_ivf_search with a choice of schedule; every check, limit and output bit above holds for
+ * both, and glx_knn_ivf_search is this call with GLX_KNN_SCHED_QUERY.  Any other schedule value is
+ * GLX_INVALID_ARGUMENT and writes nothing.
+ *   GLX_KNN_SCHED_QUERY  one workgroup per (query, probed list) on the vector pipe (the default).
+ *   GLX_KNN_SCHED_LIST   opt-in, list-major: each query's best list is scanned as above and sets the query's threshold
+ *            (the image of its k-th key); the (list, query) pairs of the other probe ranks are sorted by list on the
+ *            device and one workgroup per (list, tile of 128 queries) scores the list's rows against those queries with
+ *            v_mfma_f32_32x32x2_f32 -- the same chain.  Scores not worse than the threshold are compacted into a
+ *            per-query candidate buffer with integer counters (they never decide a result) and folded into the
+ *            query's list; a query with more survivors than the buffer holds is redone by the query-major scan, on the
+ *            device, never truncated.  The result equals GLX_KNN_SCHED_QUERY bit for bit (ids, distances, tie order,
+ *            padding, NaN / inf / signed zeros) and is the same on every call; no float atomics; no host
+ *            synchronisation beyond the query-major path's.  The workspace is the same 256 MiB budget plus
+ *            16 bytes per (query, probed list); glx_tune "knn_list_cand_cap" (GLX_KNN_LIST_CAND_CAP) may shrink the
+ *            candidate buffer per query (a test and measurement aid; the bits do not depend on it).  There is no
+ *            automatic choice between the schedules.  Like the lists themselves, neither schedule follows rows
+ *            rewritten under a view since the build.
  * glx_knn_ivf_info: any output may be NULL; longest_list in rows; device_bytes of centroids + list_ptr + list_rows.
  * glx_knn_ivf_export: centroids_out [nlist, dim] float32, list_ptr_out [nlist + 1] int64, list_rows_out [N] int64, to
  * host or device by ptr_kind; any of them may be NULL. */
@@ -541,6 +558,11 @@ GLX_API int glx_knn_ivf_build(const glx_features* f, int32_t nlist, int32_t nite
                               const float* centroids_init, int ptr_kind, void* stream, glx_knn_ivf** out);
 GLX_API int glx_knn_ivf_search(const glx_knn_ivf* index, int metric, const float* queries, int32_t num_queries, int32_t k,
                                int32_t nprobe, int64_t* ids_out, float* dist_out, int ptr_kind, void* stream);
+#define GLX_KNN_SCHED_QUERY 0
+#define GLX_KNN_SCHED_LIST 1
+GLX_API int glx_knn_ivf_search_ex(const glx_knn_ivf* index, int metric, const float* queries, int32_t num_queries,
+                                  int32_t k, int32_t nprobe, int schedule, int64_t* ids_out, float* dist_out,
+                                  int ptr_kind, void* stream);
 GLX_API int glx_knn_ivf_info(const glx_knn_ivf* index, int32_t* nlist, int32_t* dim, int64_t* num_rows,
                              int64_t* longest_list, int64_t* device_bytes);
 GLX_API int glx_knn_ivf_export(const glx_knn_ivf* index, float* centroids_out, int64_t* list_ptr_out,
@@ -1666,7 +1688,7 @@ GLX_API int glx_probe_bandwidth(int device, int kind, int64_t bytes, int64_t uni
  * (GLX_RESOLVE_SET_SHARE: the halo id set holds at least n / 1024 of a request's ids), "resolve_peek" (GLX_RESOLVE_PEEK = 0:
  * no plain load of a set slot before the compare-and-swap), "resolve_own_first" (GLX_RESOLVE_OWN_FIRST = 1 | 0: ids this
  * rank owns skip / take the replica lookup; default: skip at world size 1 only); of the KNN search: "knn_chunk_rows",
- * "knn_query_block" (see glx_knn_search).  Test aid: "seg_epochs_before_wrap" (the
+ * "knn_query_block" (see glx_knn_search), "knn_list_cand_cap" (see glx_knn_ivf_search_ex).  Test aid: "seg_epochs_before_wrap" (the
  * calling thread's segment-word buffers hand out `value` more epochs before their counter wraps). */
 GLX_API int glx_tune(const char* name, int32_t value);
 
