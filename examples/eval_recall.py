@@ -26,12 +26,16 @@ ranked below the first --refine.
 while it is uploaded) and adds one line per search: the exact search on the narrow table, its metrics and its recall
 against the float32 table's answer -- what the rounding of the stored rows costs; the queries stay float32.
 
+--precision half (with --dtype bfloat16 | float16) adds one more line per search: the half-precision scan of the narrow
+table on the 16-bit matrix cores (glx.Features.search(..., precision="half")), its metrics and its recall@k against the
+exact search of the same table.  --refine R re-scores its R best with the exact chain first (default: no re-rank).
+
 Exits non-zero unless two runs give the same bits and the ids equal the float64 brute force (with --index ivf or ivfpq:
 and two index searches give the same bits, and the index with every list probed equals the exact search bit for bit;
 with --index ivfpq and --refine > 0: and every distance the coded index returns is the exact search's for that id).
 Usage: python examples/eval_recall.py [--items 4000] [--users 1000] [--dim 16] [--k 10]
                                       [--index flat|ivf|ivfpq] [--nlist 64] [--nprobe 4] [--schedule query|list] [--m 4] [--refine 100]
-                                      [--dtype float32|bfloat16|float16|float8_e4m3fn|float8_e5m2]"""
+                                      [--dtype float32|bfloat16|float16|float8_e4m3fn|float8_e5m2] [--precision float32|half]"""
 import argparse
 import math
 import os
@@ -86,9 +90,14 @@ def main():
     ap.add_argument("--schedule", choices=("query", "list"), default="query",
                     help="with --index ivf: the IVF-Flat search's schedule (both return the same bits)")
     ap.add_argument("--m", type=int, default=4)
-    ap.add_argument("--refine", type=int, default=100)
+    ap.add_argument("--refine", type=int, default=None, help="ivfpq: default 100; --precision half: default 0")
+    ap.add_argument("--precision", choices=sorted(glx.KNN_PRECISIONS), default="float32")
     ap.add_argument("--dtype", choices=sorted(dict(glx.FEATURE_DTYPES, **glx.FP8_FEATURE_DTYPES)), default="float32")
     a = ap.parse_args()
+    if a.precision == "half" and a.dtype not in ("bfloat16", "float16"):
+        ap.error("--precision half needs --dtype bfloat16 or float16")
+    half_refine = a.refine or 0
+    a.refine = 100 if a.refine is None else a.refine
     rng = np.random.default_rng(0)
     items, item_ids, users, user_group = planted(rng, a.items, a.users, a.dim, a.group)
     table = glx.Features(items, ids=item_ids)
@@ -119,6 +128,16 @@ def main():
                 vs_f32 = (nids[:, :, None] == ids[:, None, :]).any(1).float().mean().item()
                 print("%s %s  table stored as %s  recall@%d %.4f  ndcg@%d %.4f  hit rate %.4f  recall vs float32 table %.4f  "
                       "two runs same bits: %s" % (task, metric, a.dtype, a.k, r, a.k, n, h, vs_f32, same_bits))
+                ok = ok and same_bits
+            if a.precision == "half":
+                hids, hdist = narrow.search(dq, a.k, metric, precision="half", refine=half_refine)
+                hids2, hdist2 = narrow.search(dq, a.k, metric, precision="half", refine=half_refine)
+                same_bits = bool(torch.equal(hids, hids2) and torch.equal(hdist.view(torch.int32), hdist2.view(torch.int32)))
+                r, n, h = metrics(hids, truth, a.k)
+                vs_exact = (hids[:, :, None] == nids[:, None, :]).any(1).float().mean().item()
+                print("%s %s  half scan of the %s table, refine %d  recall@%d %.4f  ndcg@%d %.4f  hit rate %.4f  "
+                      "recall vs exact search %.4f  two runs same bits: %s"
+                      % (task, metric, a.dtype, half_refine, a.k, r, a.k, n, h, vs_exact, same_bits))
                 ok = ok and same_bits
             if index is None:
                 continue

@@ -1120,6 +1120,29 @@ __host__ __device__ __forceinline__ uint16_t glx_f32_to_bf16_bits(uint32_t u) {
   return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);  // a carry out of the mantissa rounds up to the next binade / inf
 }
 
+// float32 -> float16 for the upload, round to nearest even, bit-identical -- all 2^32 inputs -- to
+// torch.Tensor.to(torch.float16) of a contiguous CPU tensor, i.e. torch's vectorised conversion (the sibling of
+// glx_f32_to_bf16_bits above; the half-precision KNN scan rounds its queries with both).  A NaN keeps the
+// sign and the top ten payload bits and sets the quiet bit (sign | 0x7E00 | payload >> 13).  Integer arithmetic only,
+// so no floating-point mode (denormal flushing) can change a result.
+__host__ __device__ __forceinline__ uint16_t glx_f32_to_f16_bits(uint32_t u) {
+  const uint32_t sign = (u >> 16) & 0x8000u;
+  const uint32_t a = u & 0x7fffffffu;
+  if (a > 0x7f800000u) return (uint16_t)(sign | 0x7E00u | ((a >> 13) & 0x3FFu));  // NaN: quiet, top payload bits
+  if (a >= 0x477FF000u) return (uint16_t)(sign | 0x7C00u);  // >= 65520 (half-way past 65504, ties to even = 2^16): inf
+  if (a >= 0x38800000u) {  // a normal half (>= 2^-14): rebias the exponent by 127 - 15, round off 13 mantissa bits
+    const uint32_t m = a - 0x38000000u;
+    return (uint16_t)(sign | ((m + 0xFFFu + ((m >> 13) & 1u)) >> 13));
+  }
+  // a half subnormal: round(|x| / 2^-24); |x| = mant 2^(e - 150), so shift the 24-bit significand by 126 - e
+  const uint32_t e = a >> 23;
+  const uint32_t sh = 126u - e;  // >= 14
+  if (sh >= 25u) return (uint16_t)sign;  // < 2^-25 (float32 subnormals and zeros included): +-0
+  const uint32_t mant = (a & 0x7fffffu) | 0x800000u;
+  const uint32_t q = mant >> sh, rem = mant & ((1u << sh) - 1u), half = 1u << (sh - 1u);
+  return (uint16_t)(sign | (q + ((rem > half || (rem == half && (q & 1u))) ? 1u : 0u)));  // q + 1 may be 0x400 = 2^-14
+}
+
 // VEC float32 values into VEC consecutive elements of a float32 or bfloat16 matrix: ONE store of VEC * sizeof(raw)
 // bytes.  float32 stores the values as they are; bfloat16 rounds each once with glx_f32_to_bf16_bits (to nearest
 // even, NaN -> 0xFFFF, subnormals and the sign of zero kept) and packs them -- the row gradients of the training path.

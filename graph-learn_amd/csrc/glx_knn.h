@@ -10,11 +10,17 @@
 
 #pragma clang fp contract(off)
 
+constexpr int kBQ = 128;          // queries per workgroup tile of a score kernel
+constexpr int kBR = 128;          // table rows per workgroup tile
 constexpr int kBK = 32;           // columns per LDS tile
 constexpr int kSortN = 1024;      // keys per sorted batch of the select kernel = the largest k
 constexpr int kSelThreads = 512;  // one compare-exchange per thread and step
 constexpr uint64_t kNoKey = ~0ull;  // an empty slot of a running list: above every real key (rows are < 2^31)
 constexpr size_t kCandBudgetBytes = (size_t)256 << 20;
+constexpr uint32_t kNoThr = 0xffffffffu;  // a threshold of "none yet": everything passes
+constexpr int32_t kDefaultChunkRows = 8192;
+constexpr int32_t kMaxChunkRows = 1 << 18;
+constexpr int32_t kDefaultFirstChunkRows = 2048;  // the first chunk passes whole: keep it small
 constexpr int kIvfRows = 256;         // rows per gathered scoring pass, one lane each
 constexpr int kIvfLd = kIvfRows + 1;  // LDS pitch of a k-major row tile
 constexpr size_t kIvfStageBytes = (size_t)64 << 20;  // float32 staging of the rows one assign call takes as queries
@@ -85,6 +91,51 @@ struct KnnArgs {
   uint64_t* run;         // [nq, KP] running list, ascending, kNoKey = empty
   int32_t nq, cap, KP, k, metric;
 };
+
+// The epilogue of a score kernel's (kBQ queries x kBR rows) tile at (qbase, rbase): four waves as 2 x 2, the wave at
+// (wq, wr) holding 64 x 64 scores as four 32x32 matrix-core accumulators -- the result layout of every 32x32xK
+// instruction: register r of lane (l31, half) is query (r & 3) + 8 * (r >> 2) + 4 * half, row l31.  Scores not worse than
+// the query's threshold (equality passes) go into the per-query candidate buffers as keys: for one register the 32 lanes
+// of a half-wave share a query, so one ballot and one counter add per (half-wave, register).  Rows from row1 and queries
+// from a.nq on are masked.
+typedef float knn_f32x16 __attribute__((ext_vector_type(16)));
+__device__ __forceinline__ void knn_tile_epilogue(const KnnArgs& a, const knn_f32x16 (&acc)[2][2], int32_t qbase,
+                                                  int32_t rbase, int32_t row1, int wq, int wr, int l31, int half) {
+  const uint32_t below = (1u << l31) - 1u;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int32_t row = rbase + wr + j * 32 + l31;
+    const bool rok = row < row1;
+    const float xn = (a.metric == GLX_KNN_L2 && rok) ? a.xn[row] : 0.0f;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int32_t q = qbase + wq + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+        const bool qok = q < a.nq;
+        float dist = acc[i][j][r];
+        uint32_t thr = 0;
+        if (qok) {
+          thr = a.thr[q];
+          if (a.metric == GLX_KNN_L2) dist = knn_l2(dist, a.qn[q], xn);
+        }
+        const uint32_t ord = knn_ord(__float_as_uint(dist), a.metric);
+        const bool pass = qok && rok && ord <= thr;
+        const uint64_t ball = __ballot(pass);
+        if (ball == 0) continue;  // wave-uniform
+        const uint32_t mine = (uint32_t)(ball >> (32 * half));
+        uint32_t base = 0;
+        if (l31 == 0 && mine != 0) base = atomicAdd(&a.cnt[q], (uint32_t)__popc(mine));
+        base = __shfl(base, half * 32);
+        if (pass) {
+          const uint32_t pos = base + (uint32_t)__popc(mine & below);
+          // the key from the image the threshold test already holds: knn_key(dist, ...) would compute it again
+          if (pos < (uint32_t)a.cap) a.cand[(int64_t)q * a.cap + pos] = knn_key(ord, row);
+        }
+      }
+    }
+  }
+}
 
 // ---- the k smallest keys, one workgroup of kSelThreads ------------------------------------------------------
 // v[kSortN] ascending
@@ -251,15 +302,87 @@ struct KnnCarve {
 
 // glx_knn.hip
 int knn_not_capturing(hipStream_t s);
+// knn_norms_kernel: out[r] = the chain of row r of t with itself
+void knn_norms(const KnnTable& t, float* out, hipStream_t s);
+// knn_init_kernel: a.run empty, a.thr "none yet", a.cnt zero;  knn_select_kernel: the chunk's candidates folded into a.run
+void knn_init(const KnnArgs& a, hipStream_t s);
+void knn_select(const KnnArgs& a, hipStream_t s);
 // the exact search on device pointers (workspace slot 1)
 int knn_search_device(const glx_features* f, int metric, const float* d_q, int32_t num_queries, int32_t k,
                       int64_t* d_ids, float* d_dist, hipStream_t s);
 // needs_l2: qn[num_queries] = the queries' norms and *xn = the table's -- an owned table's are built once and kept, a
-// view's are built into xn_ws[num_rows] on every call
-int knn_prepare_norms(const glx_features* f, bool needs_l2, const float* d_q, int32_t num_queries, float* qn,
-                      float* xn_ws, hipStream_t s, const float** xn);
+// view's are built into xn_ws[num_rows] on every call.  d_q holds q_dtype elements at a pitch of q_stride (0: dim).
+int knn_prepare_norms(const glx_features* f, bool needs_l2, const void* d_q, int32_t num_queries, float* qn,
+                      float* xn_ws, hipStream_t s, const float** xn, int q_dtype = GLX_DTYPE_F32, int64_t q_stride = 0);
 // knn_finish_kernel: a.run[a.nq, a.KP] -> (node id of f, dist)[a.nq, a.k]
 void knn_finish(const KnnArgs& a, const glx_features* f, int64_t* d_ids, float* d_dist, hipStream_t s);
+
+
+// The chunk walk of the exact search and of its half-precision scan (glx_knn_half.hip).  The candidate buffer holds qb
+// queries x chunk rows under the budget.  Many queries: blocks of 4,096 and chunks of 8,192 rows.  Few queries: the
+// chunk grows instead (up to 2^18 rows), so that a launch still fills the device and a 10 M-row table is not a thousand
+// launches of a few workgroups.  "knn_chunk_rows" and "knn_query_block" override both; no bit depends on either.
+struct KnnChunkPlan {
+  int64_t qb, chunk, first;  // queries per block, rows per chunk (= a.cap), rows of the first chunk
+};
+inline KnnChunkPlan knn_chunk_plan(int64_t num_rows, int32_t num_queries) {
+  const GlxSideKnobs& knobs = glx_side_knobs();
+  const int64_t knob_chunk = knobs.knn_chunk_rows.load(std::memory_order_relaxed);
+  const int64_t knob_qb = knobs.knn_query_block.load(std::memory_order_relaxed);
+  auto round_up = [](int64_t x, int64_t m) { return (x + m - 1) / m * m; };
+  const int64_t rows_up = round_up(num_rows > 0 ? num_rows : 1, kBR);
+  const int64_t budget_keys = (int64_t)(kCandBudgetBytes / sizeof(uint64_t));
+  int64_t qb, chunk;
+  if (knob_chunk > 0) {
+    chunk = round_up(knob_chunk, kBR);
+    qb = budget_keys / chunk / kBQ * kBQ;
+  } else {
+    qb = round_up(num_queries, kBQ);
+    if (qb > budget_keys / kDefaultChunkRows) qb = budget_keys / kDefaultChunkRows;
+    chunk = budget_keys / qb / kBR * kBR;
+    if (chunk > kMaxChunkRows) chunk = kMaxChunkRows;
+  }
+  if (chunk > rows_up) chunk = rows_up;
+  if (knob_qb > 0) qb = round_up(knob_qb, kBQ);
+  if (qb < kBQ) qb = kBQ;
+  if (qb > round_up(num_queries, kBQ)) qb = round_up(num_queries, kBQ);
+  const int64_t first = knob_chunk > 0 ? chunk : (chunk < kDefaultFirstChunkRows ? chunk : kDefaultFirstChunkRows);
+  return KnnChunkPlan{qb, chunk, first};
+}
+// Per block of plan.qb queries (a.nq, a.queries and a.qn set to the block's): a.run starts empty, then per chunk of rows
+// score(q0, row0, row1, grid) launches the score kernel over grid = (row tiles, query tiles) and the select folds its
+// candidates into a.run; then finish(q0).
+template <typename Score, typename Finish>
+int knn_chunk_passes(KnnArgs& a, const KnnChunkPlan& plan, const float* d_q, const float* qn, int32_t num_queries,
+                     hipStream_t s, Score score, Finish finish) {
+  for (int64_t q0 = 0; q0 < num_queries; q0 += plan.qb) {
+    a.nq = (int32_t)(num_queries - q0 < plan.qb ? num_queries - q0 : plan.qb);
+    a.queries = d_q + q0 * a.t.dim;
+    a.qn = qn + q0;
+    knn_init(a, s);
+    for (int64_t row0 = 0; row0 < a.t.num_rows;) {
+      const int64_t len = row0 == 0 ? plan.first : plan.chunk;
+      const int64_t row1 = row0 + len < a.t.num_rows ? row0 + len : a.t.num_rows;
+      const dim3 grid((unsigned)((row1 - row0 + kBR - 1) / kBR), (unsigned)((a.nq + kBQ - 1) / kBQ));
+      const int rc = score(q0, (int32_t)row0, (int32_t)row1, grid);
+      if (rc != GLX_OK) return rc;
+      knn_select(a, s);
+      row0 = row1;
+    }
+    finish(q0);
+  }
+  return GLX_OK;
+}
+
+// glx_knn_ivfpq.hip
+// knn_ivfpq_refine_kernel: a.run[q, 0 .. a.KP) = the a.KP best keys, under the exact search's chain against a.queries,
+// among the rows of the first R keys of cand[q, 0 .. RP), q < a.nq
+int knn_refine(const KnnArgs& a, const uint64_t* cand, int32_t RP, int32_t R, hipStream_t s);
+
+// glx_knn_half.hip
+// the half-precision scan (GLX_KNN_PREC_HALF of glx_knn_search_ex) on device pointers (workspace slot 1)
+int knn_search_half_device(const glx_features* f, int metric, const float* d_q, int32_t num_queries, int32_t k,
+                           int32_t refine, int64_t* d_ids, float* d_dist, hipStream_t s);
 
 // glx_knn_ivf.hip
 // keys[n] = kNoKey

@@ -28,15 +28,7 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kBQ = 128;          // queries per workgroup tile
-constexpr int kBR = 128;          // table rows per workgroup tile
 constexpr int kLd = kBQ + 1;      // LDS pitch of a k-major tile
-constexpr uint32_t kNoThr = 0xffffffffu;   // "none yet": everything passes
-constexpr int32_t kDefaultChunkRows = 8192;
-constexpr int32_t kMaxChunkRows = 1 << 18;
-constexpr int32_t kDefaultFirstChunkRows = 2048;  // the first chunk passes whole: keep it small
 
 // The four constants of the schedule that glx_knn.h defines, restated and held to its values at compile time.  They
 // serve readers that take the schedule's constants from this file alone: the previous release's
@@ -92,7 +84,7 @@ __global__ __launch_bounds__(256) void knn_score_kernel(KnnArgs a, int32_t row0,
   const int32_t rbase = row0 + blockIdx.x * kBR;
   const int32_t dim = a.t.dim, dim_even = dim & ~1;
   const raw_t* const X = static_cast<const raw_t*>(a.t.X);
-  f32x16 acc[2][2];
+  knn_f32x16 acc[2][2];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -143,41 +135,7 @@ __global__ __launch_bounds__(256) void knn_score_kernel(KnnArgs a, int32_t row0,
         }
     }
   }
-  // ---- epilogue: threshold filter, survivors as keys into the per-query buffers
-  const uint32_t below = (1u << l31) - 1u;
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int32_t row = rbase + wr + j * 32 + l31;
-    const bool rok = row < row1;
-    const float xn = (a.metric == GLX_KNN_L2 && rok) ? a.xn[row] : 0.0f;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int32_t q = qbase + wq + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-        const bool qok = q < a.nq;
-        float dist = acc[i][j][r];
-        uint32_t thr = 0;
-        if (qok) {
-          thr = a.thr[q];
-          if (a.metric == GLX_KNN_L2) dist = knn_l2(dist, a.qn[q], xn);
-        }
-        const uint32_t ord = knn_ord(__float_as_uint(dist), a.metric);
-        const bool pass = qok && rok && ord <= thr;
-        const uint64_t ball = __ballot(pass);
-        if (ball == 0) continue;  // wave-uniform
-        const uint32_t mine = (uint32_t)(ball >> (32 * half));
-        uint32_t base = 0;
-        if (l31 == 0 && mine != 0) base = atomicAdd(&a.cnt[q], (uint32_t)__popc(mine));
-        base = __shfl(base, half * 32);
-        if (pass) {
-          const uint32_t pos = base + (uint32_t)__popc(mine & below);
-          // the key from the image the threshold test already holds: knn_key(dist, ...) would compute it again
-          if (pos < (uint32_t)a.cap) a.cand[(int64_t)q * a.cap + pos] = knn_key(ord, row);
-        }
-      }
-    }
-  }
+  knn_tile_epilogue(a, acc, qbase, rbase, row1, wq, wr, l31, half);
 }
 
 __global__ __launch_bounds__(kSelThreads) void knn_select_kernel(KnnArgs a) {
@@ -293,19 +251,26 @@ int knn_table_norms(const glx_features* f, const KnnTable& t, hipStream_t s, con
 
 }  // namespace
 
-int knn_prepare_norms(const glx_features* f, bool needs_l2, const float* d_q, int32_t num_queries, float* qn,
-                      float* xn_ws, hipStream_t s, const float** xn) {
+void knn_norms(const KnnTable& t, float* out, hipStream_t s) {
+  if (t.num_rows > 0) knn_norms_kernel<<<(unsigned)((t.num_rows + 255) / 256), 256, 0, s>>>(t, out);
+}
+void knn_init(const KnnArgs& a, hipStream_t s) {
+  knn_init_kernel<<<(unsigned)(((int64_t)a.nq * a.KP + 255) / 256), 256, 0, s>>>(a);
+}
+void knn_select(const KnnArgs& a, hipStream_t s) { knn_select_kernel<<<(unsigned)a.nq, kSelThreads, 0, s>>>(a); }
+
+int knn_prepare_norms(const glx_features* f, bool needs_l2, const void* d_q, int32_t num_queries, float* qn,
+                      float* xn_ws, hipStream_t s, const float** xn, int q_dtype, int64_t q_stride) {
   if (!needs_l2) return GLX_OK;
   const KnnTable t = knn_table(f);
   if (f->owns_x) {
     const int rc = knn_table_norms(f, t, s, xn);
     if (rc != GLX_OK) return rc;
   } else {
-    if (t.num_rows > 0) knn_norms_kernel<<<(unsigned)((t.num_rows + 255) / 256), 256, 0, s>>>(t, xn_ws);
+    knn_norms(t, xn_ws, s);
     *xn = xn_ws;
   }
-  const KnnTable qt{d_q, f->dim, 0, num_queries, f->dim, GLX_DTYPE_F32};
-  knn_norms_kernel<<<(unsigned)((num_queries + 255) / 256), 256, 0, s>>>(qt, qn);
+  knn_norms(KnnTable{d_q, q_stride > 0 ? q_stride : f->dim, 0, num_queries, f->dim, q_dtype}, qn, s);
   return GLX_OK;
 }
 
@@ -323,31 +288,9 @@ int knn_search_device(const glx_features* f, int metric, const float* d_q, int32
   a.k = k;
   a.KP = knn_pow2_at_least(k);
   a.metric = metric;
-  const GlxSideKnobs& knobs = glx_side_knobs();
-  const int64_t knob_chunk = knobs.knn_chunk_rows.load(std::memory_order_relaxed);
-  const int64_t knob_qb = knobs.knn_query_block.load(std::memory_order_relaxed);
-  auto round_up = [](int64_t x, int64_t m) { return (x + m - 1) / m * m; };
-  // The candidate buffer holds qb queries x chunk rows under the budget.  Many queries: blocks of 4,096 and chunks
-  // of 8,192 rows.  Few queries: the chunk grows instead (up to 2^18 rows), so that a launch still fills the device and a
-  // 10 M-row table is not a thousand launches of a few workgroups.
-  const int64_t rows_up = round_up(a.t.num_rows > 0 ? a.t.num_rows : 1, kBR);
-  const int64_t budget_keys = (int64_t)(kCandBudgetBytes / sizeof(uint64_t));
-  int64_t qb, chunk;
-  if (knob_chunk > 0) {
-    chunk = round_up(knob_chunk, kBR);
-    qb = budget_keys / chunk / kBQ * kBQ;
-  } else {
-    qb = round_up(num_queries, kBQ);
-    if (qb > budget_keys / kDefaultChunkRows) qb = budget_keys / kDefaultChunkRows;
-    chunk = budget_keys / qb / kBR * kBR;
-    if (chunk > kMaxChunkRows) chunk = kMaxChunkRows;
-  }
-  if (chunk > rows_up) chunk = rows_up;
-  if (knob_qb > 0) qb = round_up(knob_qb, kBQ);
-  if (qb < kBQ) qb = kBQ;
-  if (qb > round_up(num_queries, kBQ)) qb = round_up(num_queries, kBQ);
-  const int64_t first = knob_chunk > 0 ? chunk : (chunk < kDefaultFirstChunkRows ? chunk : kDefaultFirstChunkRows);
-  a.cap = (int32_t)chunk;
+  const KnnChunkPlan plan = knn_chunk_plan(a.t.num_rows, num_queries);
+  const int64_t qb = plan.qb;
+  a.cap = (int32_t)plan.chunk;
 
   // workspace slot 1
   float *qn, *xn_ws;
@@ -366,23 +309,13 @@ int knn_search_device(const glx_features* f, int metric, const float* d_q, int32
   layout(KnnCarve{ws.as<char>()});
   rc = knn_prepare_norms(f, metric == GLX_KNN_L2, d_q, num_queries, qn, xn_ws, s, &a.xn);
   if (rc != GLX_OK) return rc;
-  for (int64_t q0 = 0; q0 < num_queries; q0 += qb) {
-    a.nq = (int32_t)(num_queries - q0 < qb ? num_queries - q0 : qb);
-    a.queries = d_q + q0 * f->dim;
-    a.qn = qn + q0;
-    knn_init_kernel<<<(unsigned)(((int64_t)a.nq * a.KP + 255) / 256), 256, 0, s>>>(a);
-    for (int64_t row0 = 0; row0 < a.t.num_rows;) {
-      const int64_t len = row0 == 0 ? first : chunk;
-      const int64_t row1 = row0 + len < a.t.num_rows ? row0 + len : a.t.num_rows;
-      const dim3 grid((unsigned)((row1 - row0 + kBR - 1) / kBR), (unsigned)((a.nq + kBQ - 1) / kBQ));
-      GLX_KNN_LAUNCH_DT(&rc, a.t.dtype, knn_score_kernel, grid, 256, s, a, (int32_t)row0, (int32_t)row1);
-      if (rc != GLX_OK) return rc;
-      knn_select_kernel<<<(unsigned)a.nq, kSelThreads, 0, s>>>(a);
-      row0 = row1;
-    }
-    knn_finish(a, f, d_ids + q0 * k, d_dist + q0 * k, s);
-  }
-  return GLX_OK;
+  return knn_chunk_passes(
+      a, plan, d_q, qn, num_queries, s,
+      [&](int64_t, int32_t row0, int32_t row1, dim3 grid) {
+        GLX_KNN_LAUNCH_DT(&rc, a.t.dtype, knn_score_kernel, grid, 256, s, a, row0, row1);
+        return rc;
+      },
+      [&](int64_t q0) { knn_finish(a, f, d_ids + q0 * k, d_dist + q0 * k, s); });
 }
 
 int knn_not_capturing(hipStream_t s) {

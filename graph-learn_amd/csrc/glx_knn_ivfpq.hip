@@ -297,6 +297,12 @@ __global__ __launch_bounds__(kSelThreads) void knn_ivfpq_refine_kernel(KnnArgs a
 
 }  // namespace
 
+int knn_refine(const KnnArgs& a, const uint64_t* cand, int32_t RP, int32_t R, hipStream_t s) {
+  int rc = GLX_OK;
+  GLX_KNN_LAUNCH_DT(&rc, a.t.dtype, knn_ivfpq_refine_kernel, (unsigned)a.nq, kSelThreads, s, a, cand, RP, R, a.run);
+  return rc;
+}
+
 static int knn_ivfpq_search_device(const glx_knn_ivfpq* px, int metric, const float* d_q, int32_t num_queries, int32_t k,
                                    int32_t nprobe, int32_t refine, int64_t* d_ids, float* d_dist, hipStream_t s) {
   const glx_knn_ivf* const ix = px->ivf;
@@ -371,7 +377,7 @@ static int knn_ivfpq_search_device(const glx_knn_ivfpq* px, int metric, const fl
         a.nq = nq;
         a.queries = d_q + q0 * f->dim;
         a.qn = qn + q0;
-        GLX_KNN_LAUNCH_DT(&launch_rc, a.t.dtype, knn_ivfpq_refine_kernel, (unsigned)nq, kSelThreads, s, a, cand, RP, refine, a.run);
+        if (launch_rc == GLX_OK) launch_rc = knn_refine(a, cand, RP, refine, s);
         knn_finish(a, f, d_ids + q0 * k, d_dist + q0 * k, s);
       });
   return rc != GLX_OK ? rc : launch_rc;

@@ -47,7 +47,7 @@ EXPORTS = [
     "glx_graph_has_timestamps", "glx_sample_temporal", "glx_sample_temporal_hops",
     "glx_features_create", "glx_features_view", "glx_features_destroy", "glx_features_info",
     "glx_features_create_ex", "glx_features_view_ex", "glx_features_dtype", "glx_features_convert_host",
-    "glx_knn_search", "glx_knn_merge",
+    "glx_knn_search", "glx_knn_search_ex", "glx_knn_merge",
     "glx_knn_ivf_build", "glx_knn_ivf_search", "glx_knn_ivf_search_ex", "glx_knn_ivf_info", "glx_knn_ivf_export", "glx_knn_ivf_destroy",
     "glx_knn_ivfpq_build", "glx_knn_ivfpq_search", "glx_knn_ivfpq_info", "glx_knn_ivfpq_export",
     "glx_knn_ivfpq_destroy",
@@ -301,6 +301,7 @@ def lib():
                                           ctypes.POINTER(ctypes.c_double), vp]
         L.glx_tune.argtypes = [ctypes.c_char_p, i32]
         L.glx_knn_search.argtypes = [vp, ci, vp, i32, i32, vp, vp, ci, vp]
+        L.glx_knn_search_ex.argtypes = [vp, ci, vp, i32, i32, ci, i32, vp, vp, ci, vp]
         L.glx_knn_merge.argtypes = [ci, ci, i32, vp, vp, i32, i32, vp, vp, ci, vp]
         L.glx_knn_ivf_build.argtypes = [vp, i32, i32, i64, vp, ci, vp, ctypes.POINTER(vp)]
         L.glx_knn_ivf_search.argtypes = [vp, ci, vp, i32, i32, i32, vp, vp, ci, vp]
@@ -812,14 +813,27 @@ class Features:
         return out
 
 
-    def search(self, queries, k, metric="ip", out=None):
+    def search(self, queries, k, metric="ip", out=None, precision="float32", refine=0):
         """Exact k nearest rows of every query (glx_knn_search) -> (ids[n, k] int64, dist[n, k] float32), best first.
         queries[n, D] float32; metric "ip" (inner product, larger is better) or "l2" (squared distance by expansion,
         smaller is better).  The score is one ascending fmaf chain over the columns, ties go to the smaller storage
         row, NaN scores come last, k > num_rows pads with id -1 and dist -inf (ip) / +inf (l2); 1 <= k <= 1024.  ids are
         node ids (row numbers for a table without an id map).  Numpy in, numpy out; torch CUDA tensors in, torch CUDA
-        tensors out on the current stream, nothing read back.  out=(ids, dist): buffers to write into."""
-        return _knn_search(lib().glx_knn_search, lambda: self._h, self.dim, self.device, queries, k, metric, out)
+        tensors out on the current stream, nothing read back.  out=(ids, dist): buffers to write into.
+        precision="half" (glx_knn_search_ex; a bfloat16 / float16 table only) scans on the 16-bit matrix cores instead:
+        the queries are rounded to the table's dtype and the score is the matrix cores' float32 accumulator, close to
+        but not the fmaf chain; order, ids and padding stay.  refine=0 returns the k best by that score; k <= refine <=
+        1024 re-scores the refine best with the fmaf chain against the float32 queries and returns the k best of those,
+        every distance being the default search's distance of its row.  With precision="half" a torch tensor of the
+        table's own dtype is accepted as queries (upcast exactly: its rounding is the identity)."""
+        if precision not in KNN_PRECISIONS:
+            raise ValueError("precision must be one of {}, not {!r}".format(sorted(KNN_PRECISIONS), precision))
+        if precision == "float32" and refine == 0:
+            return _knn_search(lib().glx_knn_search, lambda: self._h, self.dim, self.device, queries, k, metric, out)
+        if precision == "half" and _is_torch(queries) and str(queries.dtype) == "torch." + self.dtype:
+            queries = queries.float()
+        return _knn_search(lib().glx_knn_search_ex, lambda: self._h, self.dim, self.device, queries, k, metric, out,
+                           KNN_PRECISIONS[precision], int(refine))
 
     def build_ivf(self, nlist, niter=10, train_rows=None, centroids=None):
         """An IVF-Flat index over this table (glx_knn_ivf_build) -> KnnIvf.  nlist lists, niter Lloyd iterations over a
@@ -837,6 +851,7 @@ class Features:
 
 KNN_METRICS = {"l2": 0, "ip": 1}  # GLX_KNN_L2, GLX_KNN_IP
 KNN_IVF_SCHEDULES = {"query": 0, "list": 1}  # GLX_KNN_SCHED_QUERY, GLX_KNN_SCHED_LIST
+KNN_PRECISIONS = {"float32": 0, "half": 1}  # GLX_KNN_PREC_F32, GLX_KNN_PREC_HALF
 
 
 class _KnnIndex:

@@ -51,7 +51,7 @@ extern "C" {
  * the bfloat16 training path -- glx_aggregate_backward_ex, glx_aggregate_weighted_ex,
  * glx_aggregate_weighted_backward_x_ex, glx_aggregate_weighted_backward_w_ex, glx_pair_dot_ex,
  * glx_pair_dot_backward_ex; chunked row gradients -- glx_aggregate_backward_chunked,
- * glx_aggregate_weighted_backward_x_chunked. */
+ * glx_aggregate_weighted_backward_x_chunked; the half-precision KNN scan -- GLX_KNN_PREC_*, glx_knn_search_ex. */
 #define GLX_ABI_VERSION 5
 
 /* Exported symbols: libglx.so is built with -fvisibility=hidden. */
@@ -491,11 +491,39 @@ GLX_API int glx_features_convert_host(const float* src, int64_t n, int store_dty
  * num_parts * k entries of each query under the same order on dist, ties to the lower part, then to the earlier
  * position in the part; id = -1 entries are worst (absent).  Merging the searches of consecutive row ranges of one
  * table reproduces the whole-table search bit for bit (the reference's heap leaves the tie order to chance).
- * num_parts >= 1, num_parts * k < 2^31. */
+ * num_parts >= 1, num_parts * k < 2^31.
+ *
+ * glx_knn_search_ex: glx_knn_search with a choice of precision (an addition of this engine; the flat index of
+ * flat_index.cc has none).  GLX_KNN_PREC_F32 is glx_knn_search itself and requires refine == 0.  GLX_KNN_PREC_HALF is an
+ * opt-in scan on the 16-bit matrix cores (contract K-knn-half) over a bfloat16 or float16 table, read as it lies in
+ * device memory -- no second copy; a table of any other storage type is GLX_INVALID_ARGUMENT:
+ *   queries  arrive as float32 and are rounded once per search to the table's type, to nearest even, by the uploads'
+ *            converter (glx_features_convert_host): q^.  A float16 query beyond +-65504 becomes +-inf.
+ *   ip       the float32 accumulator of v_mfma_f32_32x32x16_bf16 / _f16: +0.0f, then one 32x32x16 step per block of 16
+ *            columns, ascending, over the exact products q^[c] * x[c]; columns from dim up are zero in both operands.
+ *            Not the fmaf chain: it may differ from glx_knn_search's ip in the last bits.  It equals the exact dot
+ *            product whenever every partial sum is representable (small integers); otherwise
+ *            |ip - exact(q^ . x)| <= dim * 2^-23 * sum_c |q^[c] x[c]| (derived: each addition errs by at most one
+ *            float32 ulp of its largest addend).  A (query, row) has the same bits on every call, whatever num_queries,
+ *            k, the chunking, the query block, the pointer kind or its place in a tile.  Whether the matrix cores flush
+ *            subnormal operands is the hardware's (profiles/knn_half/probe.txt records what was seen).
+ *   dist     GLX_KNN_IP: ip.  GLX_KNN_L2: the formula above with qn the fmaf chain of q^ with itself and xn the table's
+ *            norms as above.  A zero dist is returned as +0.0f and a NaN as 0x7fc00000.  Order, ties, ids and padding are
+ *            glx_knn_search's.
+ *   refine   0: the k best by that dist, which is returned.  k <= refine <= 1024: the refine best are re-scored from the
+ *            table under glx_knn_search's contract against the float32 queries as given (IVF-PQ's re-rank) and the k
+ *            best of those returned: every returned dist is glx_knn_search's dist of that row.
+ * glx_knn_search's limits apply, and num_queries * max(k, refine) < 2^31.  No float atomics.  A rejected call names
+ * the argument in glx_last_error and leaves the outputs untouched. */
 #define GLX_KNN_L2 0 /* the reference's KnnMetric values: contrib/knn/config.h:21-23 with flat_index.cc:27-28 */
 #define GLX_KNN_IP 1
 GLX_API int glx_knn_search(const glx_features* f, int metric, const float* queries, int32_t num_queries, int32_t k,
                            int64_t* ids_out, float* dist_out, int ptr_kind, void* stream);
+#define GLX_KNN_PREC_F32 0
+#define GLX_KNN_PREC_HALF 1
+GLX_API int glx_knn_search_ex(const glx_features* f, int metric, const float* queries, int32_t num_queries, int32_t k,
+                              int precision, int32_t refine, int64_t* ids_out, float* dist_out, int ptr_kind,
+                              void* stream);
 GLX_API int glx_knn_merge(int device, int metric, int32_t num_parts, const int64_t* ids, const float* dist,
                           int32_t num_queries, int32_t k, int64_t* ids_out, float* dist_out, int ptr_kind,
                           void* stream);
