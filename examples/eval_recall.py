@@ -26,9 +26,10 @@ ranked below the first --refine.
 while it is uploaded) and adds one line per search: the exact search on the narrow table, its metrics and its recall
 against the float32 table's answer -- what the rounding of the stored rows costs; the queries stay float32.
 
---precision half (with --dtype bfloat16 | float16) adds one more line per search: the half-precision scan of the narrow
-table on the 16-bit matrix cores (glx.Features.search(..., precision="half")), its metrics and its recall@k against the
-exact search of the same table.  --refine R re-scores its R best with the exact chain first (default: no re-rank).
+--precision half (with --dtype bfloat16 | float16 | float8_e4m3fn | float8_e5m2) adds one more line per search: the
+half-precision scan of the narrow table on the 16-bit matrix cores (glx.Features.search(..., precision="half"); a float8
+table is scanned as bfloat16), its metrics and its recall@k against the exact search of the same table.  --refine R
+re-scores its R best with the exact chain first (default: no re-rank).
 
 Exits non-zero unless two runs give the same bits and the ids equal the float64 brute force (with --index ivf or ivfpq:
 and two index searches give the same bits, and the index with every list probed equals the exact search bit for bit;
@@ -94,8 +95,8 @@ def main():
     ap.add_argument("--precision", choices=sorted(glx.KNN_PRECISIONS), default="float32")
     ap.add_argument("--dtype", choices=sorted(dict(glx.FEATURE_DTYPES, **glx.FP8_FEATURE_DTYPES)), default="float32")
     a = ap.parse_args()
-    if a.precision == "half" and a.dtype not in ("bfloat16", "float16"):
-        ap.error("--precision half needs --dtype bfloat16 or float16")
+    if a.precision == "half" and a.dtype == "float32":
+        ap.error("--precision half needs a narrow --dtype: bfloat16, float16, float8_e4m3fn or float8_e5m2")
     half_refine = a.refine or 0
     a.refine = 100 if a.refine is None else a.refine
     rng = np.random.default_rng(0)

@@ -1,26 +1,51 @@
 // glx KNN search, half-precision scan (GLX_KNN_PREC_HALF of glx_knn_search_ex): a bfloat16 / float16 table is scored on
 // the 16-bit matrix cores, v_mfma_f32_32x32x16_bf16 / _f16, from the words as they lie in HBM -- no upcast, no second
-// copy.  An opt-in second precision next to the exact search (glx_knn.hip), which keeps its bits.
+// copy.  A float8 table (e4m3fn / e5m2) is scored by the same bfloat16 loop behind a row front that widens its bytes in
+// registers.  An opt-in second precision next to the exact search (glx_knn.hip), which keeps its bits.
 //
-// Contract (DESIGN.md 4, K-knn-half; include/glx.h).  The float32 queries are rounded once per search to the table's
-// type (nearest even, the uploads' converter): q^.  ip(q, r) is the matrix cores' float32 accumulator: +0.0f, then one
-// 32x32x16 step per block of 16 columns, ascending, over the exact products q^[c] * x[r][c]; columns from dim up are
-// zero in both operands.  The steps of a (query, row) never depend on the schedule, so neither do its bits.  IP: dist =
-// ip.  L2: knn_l2(ip, qn, xn), qn the VALU norm chain over q^, xn the table's cached norms.  Order, key, ids and padding
-// are the exact search's; a zero distance comes back as +0.0f and a NaN as 0x7fc00000.  refine > 0: the scan keeps the
-// refine best, knn_refine (IVF-PQ's re-rank) re-scores them with the exact search's fmaf chain against the float32
-// queries as given, and the k best of those are returned with the exact search's distances.
+// Contract (DESIGN.md 4, K-knn-half; include/glx.h).  The float32 queries are rounded once per search to the scan type
+// -- the table's type, bfloat16 for a float8 table (nearest even, the uploads' converter): q^.  ip(q, r) is the matrix
+// cores' float32 accumulator: +0.0f, then one 32x32x16 step per block of 16 columns, ascending, over the exact products
+// q^[c] * x[r][c]; columns from dim up are zero in both operands.  The steps of a (query, row) never depend on the
+// schedule, so neither do its bits.  IP: dist = ip.  L2: knn_l2(ip, qn, xn), qn the VALU norm chain over q^, xn the
+// table's cached norms.  Order, key, ids and padding are the exact search's; a zero distance comes back as +0.0f and a
+// NaN as 0x7fc00000.  refine > 0: the scan keeps the refine best, knn_refine (IVF-PQ's re-rank) re-scores them with the
+// exact search's fmaf chain against the float32 queries as given, and the k best of those are returned with the exact
+// search's distances.
+// float8: every e4m3fn and e5m2 code is a bfloat16 number (3 / 2 mantissa bits in 7, float32's exponent range), so the
+// widening rounds nothing and the MFMA sees the operands of the bfloat16 table T16 that holds the same values; xn is the
+// float32 chain over the same upcast values.  A search of a float8 table therefore returns what the same search of T16
+// returns -- ids, distance bits, tie order, padding, NaN last by row -- on every call and under every chunking, and
+// with refine > 0 the exact search's distances of those rows, which the two tables share as well.  The queries are not
+// rounded to float8 and the float8 / scaled MFMA instructions are not used: 3 or 2 mantissa bits in q^ would add an error
+// of 2^-4 / 2^-3 per element to the table's own, and the scores are not what bounds the scan.
 //
 // Schedule.  knn_chunk_passes: the exact search's chunks, query blocks, init and select.  Per chunk,
 // knn_score_half_kernel computes the exact search's tile: 128 queries x 128 rows, four waves as 2 x 2, four 32x32
 // accumulators per wave across the whole column loop, and the shared epilogue (knn_tile_epilogue).  In front of it:
 //   queries   knn_round_queries_kernel writes q^ as [num_queries, dim rounded up to 8] 16-bit words, zero past dim, so
 //             every query load is one aligned 16-byte load.
-//   rows      raw 16-bit words go global -> registers -> LDS, eight columns (16 bytes) a lane, where the table's base
-//             and pitch are 16-byte aligned; element by element otherwise (a view at an odd offset or pitch) and in the
-//             tail group of dim % 8 columns, which is zero-filled.  No load touches a byte outside [row, row + 2 * dim) of
-//             a row in [row0, row1): a vector load over the tail would bring the next row's first columns into a padded
-//             operand, where a NaN gives 0 * NaN, and on the last row it would leave the allocation.
+//   rows      raw elements go global -> registers -> LDS, a group of eight columns a lane and load: 16 bytes of a 16-bit
+//             table where its base and pitch are 16-byte aligned, 8 bytes of a float8 table where its base and pitch
+//             (the pitch is in elements = bytes) are 8-byte aligned; element by element otherwise (a view at an odd
+//             offset or pitch) and in the tail group of dim % 8 columns, which is zero-filled.  No load touches a byte
+//             outside [row, row + dim) elements of a row in [row0, row1): a vector load over the tail would bring the
+//             next row's first columns into a padded operand, where a NaN gives 0 * NaN, and on the last row it would
+//             leave the allocation.
+//   float8    a lane keeps the group -> (tile row, group) map of the 16-bit front: group t & 7 of tile rows t >> 3 + 32 j,
+//             j < 4.  A row's stage is then 64 contiguous bytes read by eight consecutive lanes, 8 bytes each, and a
+//             wave's load covers eight rows; the four loads of a stage stay raw (8 VGPRs, half the 16-bit front's)
+//             while the current stage's MFMA steps run and are widened on the way into LDS: v_cvt_pk_f32_fp8 / _bf8
+//             per pair of codes, then v_perm_b32 takes the two high halves as one dword.  The float32 of a number or an
+//             infinity has a zero low half, so that is exact.  Both converters return 0xFFC00000 for every NaN code
+//             (e4m3fn 0x7F / 0xFF, e5m2 0x7D-0x7F / 0xFD-0xFF; read back from an MI355X over all 256 codes): the high
+//             half 0xFFC0 is a quiet NaN word already, so nothing is forced.  A 16-byte load that feeds two groups was
+//             not taken: it halves the load instructions of a front that is not the bound
+//             (profiles/knn_half/probe.txt: epilogue and select are), needs 16-byte alignment plus an 8-byte and an
+//             element path behind it for the stage's last piece, and gives a lane two adjacent 16-byte LDS stores per
+//             load, which the bank analysis below does not cover.  Keeping the bytes in LDS and widening at operand
+//             read was not built either: every operand is read by two waves, so it doubles the conversions and puts
+//             them between the MFMA steps, to save LDS that already fits two workgroups per CU.
 //   LDS       a stage is 64 columns: tiles of 128 rows x 64 words, row-major at a pitch of 144 bytes (128 + 16).  The
 //             operand of step s is lane l: row l & 31, columns 16 s + 8 (l >> 5) .. + 7 -- one 16-byte read.  Rows 144
 //             bytes apart start 16 bytes further round a 128-byte line each, so eight consecutive lanes (the lanes a
@@ -28,7 +53,8 @@
 //             256-byte line; a stage's writes put eight consecutive lanes on one row's 128 contiguous bytes.  Derived
 //             from the addresses, not measured.  Two buffers of (A, B): 2 * 2 * 128 * 144 = 73,728 bytes, two
 //             workgroups (eight waves) per CU of 160 KB.  The next stage's global loads are issued before the current
-//             stage's MFMA steps and stored to the other buffer after them: one barrier per stage.
+//             stage's MFMA steps and stored to the other buffer after them: one barrier per stage.  A float8 table
+//             stores the same words at the same addresses.
 #include "glx_knn.h"
 
 #pragma clang fp contract(off)
@@ -68,16 +94,48 @@ __device__ __forceinline__ knn_f32x16 knn_half_mfma(uint4 a, uint4 b, knn_f32x16
   }
 }
 
-// columns [c0, c0 + 8) of the row at p (p[0] is column 0) as one 16-byte group, zero from dim on.  vec: p + c0 is
-// 16-byte aligned whenever c0 is a multiple of 8.
-__device__ __forceinline__ uint4 knn_half_group(const uint16_t* p, int32_t c0, int32_t dim, bool vec) {
-  if (c0 + 8 <= dim && vec) return *reinterpret_cast<const uint4*>(p + c0);
-  uint32_t w[4] = {0u, 0u, 0u, 0u};
+// columns [c0, c0 + 8) of the row at p (p[0] is column 0) as one group G of eight elements E, zero from dim on.  vec:
+// p + c0 is aligned to sizeof(G) whenever c0 is a multiple of 8.
+template <typename G, typename E>
+__device__ __forceinline__ G knn_half_group(const E* p, int32_t c0, int32_t dim, bool vec) {
+  if (c0 + 8 <= dim && vec) return *reinterpret_cast<const G*>(p + c0);
+  constexpr int kPer = 4 / (int)sizeof(E);  // elements per dword
+  struct {
+    uint32_t w[sizeof(G) / 4];
+  } v = {};
 #pragma unroll
   for (int e = 0; e < 8; ++e)
-    if (c0 + e < dim) w[e >> 1] |= (uint32_t)p[c0 + e] << (16 * (e & 1));
-  return make_uint4(w[0], w[1], w[2], w[3]);
+    if (c0 + e < dim) v.w[e / kPer] |= (uint32_t)p[c0 + e] << (8 * (int)sizeof(E) * (e % kPer));
+  return __builtin_bit_cast(G, v);
 }
+
+// The row front of a storage type: `elem` as the table stores it, `group` = eight of them as one load, kScan = the
+// 16-bit type the queries are rounded to and the MFMA runs in, words() = a group as the eight 16-bit words of an operand.
+template <int DT>
+struct HalfRow {
+  typedef uint16_t elem;
+  typedef uint4 group;
+  static constexpr int kScan = DT;
+  static __device__ __forceinline__ uint4 words(uint4 g) { return g; }
+};
+// float8: each pair of codes to two float32 (exact), whose high halves are the bfloat16 words (exact: see the header)
+template <int DT>
+struct HalfRowF8 {
+  typedef uint8_t elem;
+  typedef uint2 group;
+  static constexpr int kScan = GLX_DTYPE_BF16;
+  static __device__ __forceinline__ uint32_t pair(uint32_t codes, bool hi) {
+    const float __attribute__((ext_vector_type(2))) f = AggElem<DT>::up2(codes, hi);
+    return __builtin_amdgcn_perm(__float_as_uint(f.y), __float_as_uint(f.x), 0x07060302u);  // f.y's high half : f.x's
+  }
+  static __device__ __forceinline__ uint4 words(uint2 g) {
+    return make_uint4(pair(g.x, false), pair(g.x, true), pair(g.y, false), pair(g.y, true));
+  }
+};
+template <>
+struct HalfRow<GLX_DTYPE_F8E4M3> : HalfRowF8<GLX_DTYPE_F8E4M3> {};
+template <>
+struct HalfRow<GLX_DTYPE_F8E5M2> : HalfRowF8<GLX_DTYPE_F8E5M2> {};
 
 // One (128 queries x 128 rows) tile of half-precision scores for rows [row0, row1), filtered into the candidate
 // buffers.  qh: the rounded queries of this block, [a.nq, qld].  Rows past row1 and queries past a.nq are zero operands
@@ -93,13 +151,15 @@ __global__ __launch_bounds__(256, 2) void knn_score_half_kernel(KnnArgs a, const
   const int32_t qbase = blockIdx.y * kBQ;
   const int32_t rbase = row0 + blockIdx.x * kBR;
   const int32_t dim = a.t.dim;
-  const uint16_t* const X = static_cast<const uint16_t*>(a.t.X);
-  const bool vec = (reinterpret_cast<uintptr_t>(X) & 15) == 0 && (a.t.stride & 7) == 0;
+  typedef typename HalfRow<DT>::elem elem_t;
+  typedef typename HalfRow<DT>::group group_t;
+  const elem_t* const X = static_cast<const elem_t*>(a.t.X);
+  const bool vec = (reinterpret_cast<uintptr_t>(X) & (sizeof(group_t) - 1)) == 0 && (a.t.stride & 7) == 0;
   const int g = t & (kHalfGroups - 1), lr = t / kHalfGroups;  // the lane's group, and its first tile row
 
   // the lane's kHalfLoads queries and rows are the same in every stage
   const uint16_t* qp[kHalfLoads];
-  const uint16_t* xp[kHalfLoads];
+  const elem_t* xp[kHalfLoads];
 #pragma unroll
   for (int j = 0; j < kHalfLoads; ++j) {
     const int r = lr + (256 / kHalfGroups) * j;
@@ -107,19 +167,19 @@ __global__ __launch_bounds__(256, 2) void knn_score_half_kernel(KnnArgs a, const
     qp[j] = q < a.nq ? qh + (int64_t)q * qld : nullptr;
     xp[j] = row < row1 ? X + glx_swizzle_row(row, a.t.swizzle_rows) * a.t.stride : nullptr;
   }
-  auto fetch = [&](int32_t k0, uint4 (&qa)[kHalfLoads], uint4 (&xb)[kHalfLoads]) {
+  auto fetch = [&](int32_t k0, uint4 (&qa)[kHalfLoads], group_t (&xb)[kHalfLoads]) {
     const int32_t c0 = k0 + 8 * g;
 #pragma unroll
     for (int j = 0; j < kHalfLoads; ++j) {
       qa[j] = (qp[j] && c0 < qld) ? *reinterpret_cast<const uint4*>(qp[j] + c0) : make_uint4(0u, 0u, 0u, 0u);
-      xb[j] = (xp[j] && c0 < dim) ? knn_half_group(xp[j], c0, dim, vec) : make_uint4(0u, 0u, 0u, 0u);
+      xb[j] = (xp[j] && c0 < dim) ? knn_half_group<group_t>(xp[j], c0, dim, vec) : group_t{};
     }
   };
-  auto stash = [&](int buf, const uint4 (&qa)[kHalfLoads], const uint4 (&xb)[kHalfLoads]) {
+  auto stash = [&](int buf, const uint4 (&qa)[kHalfLoads], const group_t (&xb)[kHalfLoads]) {
 #pragma unroll
     for (int j = 0; j < kHalfLoads; ++j) {
       As[buf][lr + (256 / kHalfGroups) * j][g] = qa[j];
-      Bs[buf][lr + (256 / kHalfGroups) * j][g] = xb[j];
+      Bs[buf][lr + (256 / kHalfGroups) * j][g] = HalfRow<DT>::words(xb[j]);
     }
   };
 
@@ -130,7 +190,8 @@ __global__ __launch_bounds__(256, 2) void knn_score_half_kernel(KnnArgs a, const
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-  uint4 qa[kHalfLoads], xb[kHalfLoads];
+  uint4 qa[kHalfLoads];
+  group_t xb[kHalfLoads];
   fetch(0, qa, xb);
   stash(0, qa, xb);
   __syncthreads();  // stage 0 is in LDS
@@ -143,10 +204,10 @@ __global__ __launch_bounds__(256, 2) void knn_score_half_kernel(KnnArgs a, const
     for (int s = 0; s < steps; ++s) {
       const uint4 a0 = As[buf][wq + l31][2 * s + half], a1 = As[buf][wq + 32 + l31][2 * s + half];
       const uint4 b0 = Bs[buf][wr + l31][2 * s + half], b1 = Bs[buf][wr + 32 + l31][2 * s + half];
-      acc[0][0] = knn_half_mfma<DT>(a0, b0, acc[0][0]);
-      acc[0][1] = knn_half_mfma<DT>(a0, b1, acc[0][1]);
-      acc[1][0] = knn_half_mfma<DT>(a1, b0, acc[1][0]);
-      acc[1][1] = knn_half_mfma<DT>(a1, b1, acc[1][1]);
+      acc[0][0] = knn_half_mfma<HalfRow<DT>::kScan>(a0, b0, acc[0][0]);
+      acc[0][1] = knn_half_mfma<HalfRow<DT>::kScan>(a0, b1, acc[0][1]);
+      acc[1][0] = knn_half_mfma<HalfRow<DT>::kScan>(a1, b0, acc[1][0]);
+      acc[1][1] = knn_half_mfma<HalfRow<DT>::kScan>(a1, b1, acc[1][1]);
     }
     if (ahead) stash(buf ^ 1, qa, xb);
     __syncthreads();  // the next stage is stored; this one has been consumed
@@ -171,6 +232,17 @@ __global__ __launch_bounds__(256) void knn_half_finish_kernel(KnnArgs a, const i
 }
 
 }  // namespace
+
+// knn_score_half_kernel of the table's storage type
+static void knn_score_half(const KnnArgs& a, const uint16_t* qh, int32_t qld, int32_t row0, int32_t row1, dim3 grid,
+                           hipStream_t s) {
+  switch (a.t.dtype) {
+    case GLX_DTYPE_BF16: knn_score_half_kernel<GLX_DTYPE_BF16><<<grid, 256, 0, s>>>(a, qh, qld, row0, row1); break;
+    case GLX_DTYPE_F16: knn_score_half_kernel<GLX_DTYPE_F16><<<grid, 256, 0, s>>>(a, qh, qld, row0, row1); break;
+    case GLX_DTYPE_F8E4M3: knn_score_half_kernel<GLX_DTYPE_F8E4M3><<<grid, 256, 0, s>>>(a, qh, qld, row0, row1); break;
+    default: knn_score_half_kernel<GLX_DTYPE_F8E5M2><<<grid, 256, 0, s>>>(a, qh, qld, row0, row1); break;
+  }
+}
 
 int knn_search_half_device(const glx_features* f, int metric, const float* d_q, int32_t num_queries, int32_t k,
                            int32_t refine, int64_t* d_ids, float* d_dist, hipStream_t s) {
@@ -208,12 +280,13 @@ int knn_search_half_device(const glx_features* f, int metric, const float* d_q, 
   if (rc != GLX_OK) return rc;
   layout(KnnCarve{ws.as<char>()});
   const unsigned round_grid = (unsigned)(((int64_t)num_queries * qld + 255) / 256);
-  if (a.t.dtype == GLX_DTYPE_BF16) {
+  const int scan = a.t.dtype == GLX_DTYPE_F16 ? GLX_DTYPE_F16 : GLX_DTYPE_BF16;  // a float8 table scans as bfloat16
+  if (scan == GLX_DTYPE_BF16) {
     knn_round_queries_kernel<GLX_DTYPE_BF16><<<round_grid, 256, 0, s>>>(d_q, num_queries, a.t.dim, qld, qh);
   } else {
     knn_round_queries_kernel<GLX_DTYPE_F16><<<round_grid, 256, 0, s>>>(d_q, num_queries, a.t.dim, qld, qh);
   }
-  rc = knn_prepare_norms(f, l2, qh, num_queries, qn_half, xn_ws, s, &a.xn, a.t.dtype, qld);
+  rc = knn_prepare_norms(f, l2, qh, num_queries, qn_half, xn_ws, s, &a.xn, scan, qld);
   if (rc != GLX_OK) return rc;
   x.xn = a.xn;
   if (qn_exact) knn_norms(KnnTable{d_q, a.t.dim, 0, num_queries, a.t.dim, GLX_DTYPE_F32}, qn_exact, s);
@@ -222,9 +295,7 @@ int knn_search_half_device(const glx_features* f, int metric, const float* d_q, 
   rc = knn_chunk_passes(
       a, plan, d_q, qn_half, num_queries, s,
       [&](int64_t q0, int32_t row0, int32_t row1, dim3 grid) {
-        const uint16_t* const qb = qh + q0 * qld;
-        if (a.t.dtype == GLX_DTYPE_BF16) knn_score_half_kernel<GLX_DTYPE_BF16><<<grid, 256, 0, s>>>(a, qb, qld, row0, row1);
-        else knn_score_half_kernel<GLX_DTYPE_F16><<<grid, 256, 0, s>>>(a, qb, qld, row0, row1);
+        knn_score_half(a, qh + q0 * qld, qld, row0, row1, grid, s);
         return GLX_OK;
       },
       [&](int64_t q0) {
@@ -253,8 +324,9 @@ extern "C" int glx_knn_search_ex(const glx_features* f, int metric, const float*
     GLX_REQUIRE(refine == 0, "refine must be 0 with precision GLX_KNN_PREC_F32, got %d", refine);
     return glx_knn_search(f, metric, queries, num_queries, k, ids_out, dist_out, ptr_kind, stream);
   }
-  GLX_REQUIRE(f->dtype == GLX_DTYPE_BF16 || f->dtype == GLX_DTYPE_F16,
-              "precision GLX_KNN_PREC_HALF needs a bfloat16 or float16 table, this one stores %s", glx_dtype_name(f->dtype));
+  GLX_REQUIRE(f->dtype == GLX_DTYPE_BF16 || f->dtype == GLX_DTYPE_F16 || glx_dtype_is_f8(f->dtype),
+              "precision GLX_KNN_PREC_HALF needs a bfloat16, float16 or float8 table, this one stores %s",
+              glx_dtype_name(f->dtype));
   GLX_REQUIRE(refine == 0 || (refine >= k && refine <= kSortN), "refine must be 0 or in [k = %d, %d], got %d", k, kSortN,
               refine);
   GLX_REQUIRE((int64_t)num_queries * (refine > k ? refine : k) < INT32_MAX, "num_queries * max(k, refine) must be < 2^31");

@@ -820,17 +820,20 @@ class Features:
         row, NaN scores come last, k > num_rows pads with id -1 and dist -inf (ip) / +inf (l2); 1 <= k <= 1024.  ids are
         node ids (row numbers for a table without an id map).  Numpy in, numpy out; torch CUDA tensors in, torch CUDA
         tensors out on the current stream, nothing read back.  out=(ids, dist): buffers to write into.
-        precision="half" (glx_knn_search_ex; a bfloat16 / float16 table only) scans on the 16-bit matrix cores instead:
-        the queries are rounded to the table's dtype and the score is the matrix cores' float32 accumulator, close to
-        but not the fmaf chain; order, ids and padding stay.  refine=0 returns the k best by that score; k <= refine <=
-        1024 re-scores the refine best with the fmaf chain against the float32 queries and returns the k best of those,
-        every distance being the default search's distance of its row.  With precision="half" a torch tensor of the
-        table's own dtype is accepted as queries (upcast exactly: its rounding is the identity)."""
+        precision="half" (glx_knn_search_ex; a bfloat16, float16 or float8 table, not a float32 one) scans on the 16-bit
+        matrix cores instead: the queries are rounded to the table's scan type -- its dtype, bfloat16 for a float8 table,
+        whose bytes are widened to bfloat16 exactly on their way to the matrix cores -- and the score is the matrix
+        cores' float32 accumulator, close to but not the fmaf chain; order, ids and padding stay.  A float8 table
+        returns, bit for bit, what the bfloat16 table of the same values returns.  refine=0 returns the k best by that
+        score; k <= refine <= 1024 re-scores the refine best with the fmaf chain against the float32 queries and returns
+        the k best of those, every distance being the default search's distance of its row.  With precision="half" a
+        torch tensor of the table's scan type is accepted as queries (upcast exactly: its rounding is the identity)."""
         if precision not in KNN_PRECISIONS:
             raise ValueError("precision must be one of {}, not {!r}".format(sorted(KNN_PRECISIONS), precision))
         if precision == "float32" and refine == 0:
             return _knn_search(lib().glx_knn_search, lambda: self._h, self.dim, self.device, queries, k, metric, out)
-        if precision == "half" and _is_torch(queries) and str(queries.dtype) == "torch." + self.dtype:
+        scan = "bfloat16" if self.dtype in FP8_FEATURE_DTYPES else self.dtype
+        if precision == "half" and _is_torch(queries) and str(queries.dtype) == "torch." + scan:
             queries = queries.float()
         return _knn_search(lib().glx_knn_search_ex, lambda: self._h, self.dim, self.device, queries, k, metric, out,
                            KNN_PRECISIONS[precision], int(refine))

@@ -495,10 +495,19 @@ GLX_API int glx_features_convert_host(const float* src, int64_t n, int store_dty
  *
  * glx_knn_search_ex: glx_knn_search with a choice of precision (an addition of this engine; the flat index of
  * flat_index.cc has none).  GLX_KNN_PREC_F32 is glx_knn_search itself and requires refine == 0.  GLX_KNN_PREC_HALF is an
- * opt-in scan on the 16-bit matrix cores (contract K-knn-half) over a bfloat16 or float16 table, read as it lies in
- * device memory -- no second copy; a table of any other storage type is GLX_INVALID_ARGUMENT:
- *   queries  arrive as float32 and are rounded once per search to the table's type, to nearest even, by the uploads'
- *            converter (glx_features_convert_host): q^.  A float16 query beyond +-65504 becomes +-inf.
+ * opt-in scan on the 16-bit matrix cores (contract K-knn-half) over a bfloat16, float16, float8_e4m3fn or float8_e5m2
+ * table, read as it lies in device memory -- no second copy; a float32 table is GLX_INVALID_ARGUMENT:
+ *   queries  arrive as float32 and are rounded once per search to the scan type -- the table's type; bfloat16 for a
+ *            float8 table -- to nearest even, by the uploads' converter (glx_features_convert_host): q^.  A float16
+ *            query beyond +-65504 becomes +-inf.
+ *   float8   every e4m3fn / e5m2 code is a bfloat16 number, so a row's bytes are widened to bfloat16 in registers without
+ *            rounding and scored by the bfloat16 loop.  For a float8 table T8 and the bfloat16 table T16 that holds the
+ *            same values, the search of T8 returns what the same search of T16 returns -- ids, distance bits, tie order,
+ *            padding, NaN last by row -- on every call and under every chunking; with refine > 0 every returned dist is
+ *            glx_knn_search's dist of that row on T8, which is its dist on T16 (the chain sees the same float32
+ *            values; which NaN a NaN dist is, is the hardware's).  The queries are never rounded to float8 and the
+ *            float8 / scaled matrix instructions are not used: 3 or 2 mantissa bits in q^ would add an error of 2^-4 /
+ *            2^-3 per element to the table's own, and the scores are not what bounds the scan.
  *   ip       the float32 accumulator of v_mfma_f32_32x32x16_bf16 / _f16: +0.0f, then one 32x32x16 step per block of 16
  *            columns, ascending, over the exact products q^[c] * x[c]; columns from dim up are zero in both operands.
  *            Not the fmaf chain: it may differ from glx_knn_search's ip in the last bits.  It equals the exact dot

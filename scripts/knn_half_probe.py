@@ -4,7 +4,7 @@ Per shape the default search, the half scan and the half scan with refine=1024 a
 (and min..max) of --reps timed calls after --warmup, device events around the engine call; recall@k of the half
 answers against the default answer.  Then, per dtype, the largest |ip - exact| / bound seen on a Gaussian sample (float64
 over the rounded operands; bound = dim * 2^-23 * sum|terms|, the contract's) and whether a subnormal operand contributed
-to a score.  A measurement, not a test.
+to a score.  A measurement, not a test.  float8 tables: scripts/knn_half_fp8_probe.py, whose legs span two tables.
 Usage: python scripts/knn_half_probe.py [--rows 10000000] [--dim 128] [--reps 10] [--warmup 3] [--out profiles/knn_half/probe.txt]"""
 import argparse
 import os
