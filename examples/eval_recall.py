@@ -31,12 +31,16 @@ half-precision scan of the narrow table on the 16-bit matrix cores (glx.Features
 table is scanned as bfloat16), its metrics and its recall@k against the exact search of the same table.  --refine R
 re-scores its R best with the exact chain first (default: no re-rank).
 
+--tile narrow runs every flat search above through the 32-query tiles (glx.Features.search(..., tile="narrow")): the
+same bits, a shorter time for a handful of users per call.
+
 Exits non-zero unless two runs give the same bits and the ids equal the float64 brute force (with --index ivf or ivfpq:
 and two index searches give the same bits, and the index with every list probed equals the exact search bit for bit;
 with --index ivfpq and --refine > 0: and every distance the coded index returns is the exact search's for that id).
 Usage: python examples/eval_recall.py [--items 4000] [--users 1000] [--dim 16] [--k 10]
                                       [--index flat|ivf|ivfpq] [--nlist 64] [--nprobe 4] [--schedule query|list] [--m 4] [--refine 100]
-                                      [--dtype float32|bfloat16|float16|float8_e4m3fn|float8_e5m2] [--precision float32|half]"""
+                                      [--dtype float32|bfloat16|float16|float8_e4m3fn|float8_e5m2] [--precision float32|half]
+                                      [--tile wide|narrow]"""
 import argparse
 import math
 import os
@@ -93,6 +97,7 @@ def main():
     ap.add_argument("--m", type=int, default=4)
     ap.add_argument("--refine", type=int, default=None, help="ivfpq: default 100; --precision half: default 0")
     ap.add_argument("--precision", choices=sorted(glx.KNN_PRECISIONS), default="float32")
+    ap.add_argument("--tile", choices=sorted(glx.KNN_TILES), default="wide", help="the flat searches' score tile")
     ap.add_argument("--dtype", choices=sorted(dict(glx.FEATURE_DTYPES, **glx.FP8_FEATURE_DTYPES)), default="float32")
     a = ap.parse_args()
     if a.precision == "half" and a.dtype == "float32":
@@ -112,8 +117,8 @@ def main():
         dq = torch.from_numpy(q).cuda()
         truth = d_ids[group_rows[torch.from_numpy(q_group).cuda()]]
         for metric in ("l2", "ip"):
-            ids, dist = table.search(dq, a.k, metric)
-            ids2, dist2 = table.search(dq, a.k, metric)
+            ids, dist = table.search(dq, a.k, metric, tile=a.tile)
+            ids2, dist2 = table.search(dq, a.k, metric, tile=a.tile)
             same_bits = bool(torch.equal(ids, ids2) and torch.equal(dist.view(torch.int32), dist2.view(torch.int32)))
             want = item_ids[brute64(q, items, a.k, metric)]
             exact = bool(np.array_equal(ids.cpu().numpy(), want))
@@ -122,8 +127,8 @@ def main():
                   % (task, metric, a.k, r, a.k, n, h, same_bits, exact))
             ok = ok and same_bits and exact and not math.isnan(r)
             if narrow is not None:
-                nids, ndist = narrow.search(dq, a.k, metric)
-                nids2, ndist2 = narrow.search(dq, a.k, metric)
+                nids, ndist = narrow.search(dq, a.k, metric, tile=a.tile)
+                nids2, ndist2 = narrow.search(dq, a.k, metric, tile=a.tile)
                 same_bits = bool(torch.equal(nids, nids2) and torch.equal(ndist.view(torch.int32), ndist2.view(torch.int32)))
                 r, n, h = metrics(nids, truth, a.k)
                 vs_f32 = (nids[:, :, None] == ids[:, None, :]).any(1).float().mean().item()
@@ -131,8 +136,8 @@ def main():
                       "two runs same bits: %s" % (task, metric, a.dtype, a.k, r, a.k, n, h, vs_f32, same_bits))
                 ok = ok and same_bits
             if a.precision == "half":
-                hids, hdist = narrow.search(dq, a.k, metric, precision="half", refine=half_refine)
-                hids2, hdist2 = narrow.search(dq, a.k, metric, precision="half", refine=half_refine)
+                hids, hdist = narrow.search(dq, a.k, metric, precision="half", refine=half_refine, tile=a.tile)
+                hids2, hdist2 = narrow.search(dq, a.k, metric, precision="half", refine=half_refine, tile=a.tile)
                 same_bits = bool(torch.equal(hids, hids2) and torch.equal(hdist.view(torch.int32), hdist2.view(torch.int32)))
                 r, n, h = metrics(hids, truth, a.k)
                 vs_exact = (hids[:, :, None] == nids[:, None, :]).any(1).float().mean().item()

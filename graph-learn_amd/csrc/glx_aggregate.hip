@@ -1522,6 +1522,9 @@ void launch_agg_stitch(bool vec4, const float* parts, const int32_t* cnts, int32
 
 }  // namespace
 
+// seg_device_cus for other files: the narrow KNN tile's walk (glx_knn_narrow.hip) is sized to it as well
+int glx_device_cus(int* out) { return seg_device_cus(out); }
+
 // glx_dist.hip: segmented reduce over pre-resolved virtual rows of up to three sources
 // (own shard, hot-row replica, halo rows); vrows[i] = -1 is the default row.
 int glx_aggregate_vrows_device(const GlxRowSource* src, int nsrc, int32_t dim, int op, const int32_t* vrows,

@@ -64,6 +64,7 @@ int glx_init_device(int device);
 int glx_scratch_alloc(void** p, size_t bytes, hipStream_t s, int slot);
 void glx_scratch_free(void* p, hipStream_t s);
 void glx_scratch_trim(hipStream_t s, int slot, size_t keep_bytes);  // also ends the lease of what it frees
+int glx_device_cus(int* out);  // glx_aggregate.hip: *out = the compute units of the current device, asked once
 
 // One workspace lease, ended on every exit path.
 struct GlxScratch {

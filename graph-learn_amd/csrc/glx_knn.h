@@ -92,23 +92,25 @@ struct KnnArgs {
   int32_t nq, cap, KP, k, metric;
 };
 
-// The epilogue of a score kernel's (kBQ queries x kBR rows) tile at (qbase, rbase): four waves as 2 x 2, the wave at
-// (wq, wr) holding 64 x 64 scores as four 32x32 matrix-core accumulators -- the result layout of every 32x32xK
-// instruction: register r of lane (l31, half) is query (r & 3) + 8 * (r >> 2) + 4 * half, row l31.  Scores not worse than
+// The epilogue of a score kernel's tile at (qbase, rbase): the wave at (wq, wr) holds (32 NI) x (32 NJ) scores as an
+// [NI][NJ] grid of 32x32 matrix-core accumulators -- 2 x 2 for the (kBQ queries x kBR rows) tile, whose four waves sit
+// as 2 x 2; 1 x 2 for the narrow tile (glx_knn_narrow.hip), whose four waves share 32 queries.  The result layout of
+// every 32x32xK instruction: register r of lane (l31, half) is query (r & 3) + 8 * (r >> 2) + 4 * half, row l31.  Scores not worse than
 // the query's threshold (equality passes) go into the per-query candidate buffers as keys: for one register the 32 lanes
 // of a half-wave share a query, so one ballot and one counter add per (half-wave, register).  Rows from row1 and queries
 // from a.nq on are masked.
 typedef float knn_f32x16 __attribute__((ext_vector_type(16)));
-__device__ __forceinline__ void knn_tile_epilogue(const KnnArgs& a, const knn_f32x16 (&acc)[2][2], int32_t qbase,
+template <int NI, int NJ>
+__device__ __forceinline__ void knn_tile_epilogue(const KnnArgs& a, const knn_f32x16 (&acc)[NI][NJ], int32_t qbase,
                                                   int32_t rbase, int32_t row1, int wq, int wr, int l31, int half) {
   const uint32_t below = (1u << l31) - 1u;
 #pragma unroll
-  for (int j = 0; j < 2; ++j) {
+  for (int j = 0; j < NJ; ++j) {
     const int32_t row = rbase + wr + j * 32 + l31;
     const bool rok = row < row1;
     const float xn = (a.metric == GLX_KNN_L2 && rok) ? a.xn[row] : 0.0f;
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
+    for (int i = 0; i < NI; ++i) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int32_t q = qbase + wq + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
@@ -136,6 +138,62 @@ __device__ __forceinline__ void knn_tile_epilogue(const KnnArgs& a, const knn_f3
     }
   }
 }
+
+// ---- the half-precision scan's operands (glx_knn_half.hip, glx_knn_narrow.hip) ---------------------------------------
+typedef __bf16 knn_bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 knn_f16x8 __attribute__((ext_vector_type(8)));
+
+template <int DT>
+__device__ __forceinline__ knn_f32x16 knn_half_mfma(uint4 a, uint4 b, knn_f32x16 c) {
+  if constexpr (DT == GLX_DTYPE_BF16) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(knn_bf16x8, a), __builtin_bit_cast(knn_bf16x8, b), c, 0, 0, 0);
+  } else {
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(knn_f16x8, a), __builtin_bit_cast(knn_f16x8, b), c, 0, 0, 0);
+  }
+}
+
+// columns [c0, c0 + 8) of the row at p (p[0] is column 0) as one group G of eight elements E, zero from dim on.  vec:
+// p + c0 is aligned to sizeof(G) whenever c0 is a multiple of 8.
+template <typename G, typename E>
+__device__ __forceinline__ G knn_half_group(const E* p, int32_t c0, int32_t dim, bool vec) {
+  if (c0 + 8 <= dim && vec) return *reinterpret_cast<const G*>(p + c0);
+  constexpr int kPer = 4 / (int)sizeof(E);  // elements per dword
+  struct {
+    uint32_t w[sizeof(G) / 4];
+  } v = {};
+#pragma unroll
+  for (int e = 0; e < 8; ++e)
+    if (c0 + e < dim) v.w[e / kPer] |= (uint32_t)p[c0 + e] << (8 * (int)sizeof(E) * (e % kPer));
+  return __builtin_bit_cast(G, v);
+}
+
+// The row front of a storage type: `elem` as the table stores it, `group` = eight of them as one load, kScan = the
+// 16-bit type the queries are rounded to and the MFMA runs in, words() = a group as the eight 16-bit words of an operand.
+template <int DT>
+struct HalfRow {
+  typedef uint16_t elem;
+  typedef uint4 group;
+  static constexpr int kScan = DT;
+  static __device__ __forceinline__ uint4 words(uint4 g) { return g; }
+};
+// float8: each pair of codes to two float32 (exact), whose high halves are the bfloat16 words (exact: see the header of glx_knn_half.hip)
+template <int DT>
+struct HalfRowF8 {
+  typedef uint8_t elem;
+  typedef uint2 group;
+  static constexpr int kScan = GLX_DTYPE_BF16;
+  static __device__ __forceinline__ uint32_t pair(uint32_t codes, bool hi) {
+    const float __attribute__((ext_vector_type(2))) f = AggElem<DT>::up2(codes, hi);
+    return __builtin_amdgcn_perm(__float_as_uint(f.y), __float_as_uint(f.x), 0x07060302u);  // f.y's high half : f.x's
+  }
+  static __device__ __forceinline__ uint4 words(uint2 g) {
+    return make_uint4(pair(g.x, false), pair(g.x, true), pair(g.y, false), pair(g.y, true));
+  }
+};
+template <>
+struct HalfRow<GLX_DTYPE_F8E4M3> : HalfRowF8<GLX_DTYPE_F8E4M3> {};
+template <>
+struct HalfRow<GLX_DTYPE_F8E5M2> : HalfRowF8<GLX_DTYPE_F8E5M2> {};
 
 // ---- the k smallest keys, one workgroup of kSelThreads ------------------------------------------------------
 // v[kSortN] ascending
@@ -307,9 +365,9 @@ void knn_norms(const KnnTable& t, float* out, hipStream_t s);
 // knn_init_kernel: a.run empty, a.thr "none yet", a.cnt zero;  knn_select_kernel: the chunk's candidates folded into a.run
 void knn_init(const KnnArgs& a, hipStream_t s);
 void knn_select(const KnnArgs& a, hipStream_t s);
-// the exact search on device pointers (workspace slot 1)
+// the exact search on device pointers (workspace slot 1); tile: GLX_KNN_TILE_WIDE (knn_score_kernel) or _NARROW
 int knn_search_device(const glx_features* f, int metric, const float* d_q, int32_t num_queries, int32_t k,
-                      int64_t* d_ids, float* d_dist, hipStream_t s);
+                      int64_t* d_ids, float* d_dist, hipStream_t s, int tile = GLX_KNN_TILE_WIDE);
 // needs_l2: qn[num_queries] = the queries' norms and *xn = the table's -- an owned table's are built once and kept, a
 // view's are built into xn_ws[num_rows] on every call.  d_q holds q_dtype elements at a pitch of q_stride (0: dim).
 int knn_prepare_norms(const glx_features* f, bool needs_l2, const void* d_q, int32_t num_queries, float* qn,
@@ -322,32 +380,34 @@ void knn_finish(const KnnArgs& a, const glx_features* f, int64_t* d_ids, float* 
 // queries x chunk rows under the budget.  Many queries: blocks of 4,096 and chunks of 8,192 rows.  Few queries: the
 // chunk grows instead (up to 2^18 rows), so that a launch still fills the device and a 10 M-row table is not a thousand
 // launches of a few workgroups.  "knn_chunk_rows" and "knn_query_block" override both; no bit depends on either.
+// bq x br is the score kernel's tile, which blocks and chunks are rounded to: kBQ x kBR, or the narrow tile's 32 x 256.
 struct KnnChunkPlan {
   int64_t qb, chunk, first;  // queries per block, rows per chunk (= a.cap), rows of the first chunk
+  int32_t bq, br;            // the tile
 };
-inline KnnChunkPlan knn_chunk_plan(int64_t num_rows, int32_t num_queries) {
+inline KnnChunkPlan knn_chunk_plan(int64_t num_rows, int32_t num_queries, int32_t bq = kBQ, int32_t br = kBR) {
   const GlxSideKnobs& knobs = glx_side_knobs();
   const int64_t knob_chunk = knobs.knn_chunk_rows.load(std::memory_order_relaxed);
   const int64_t knob_qb = knobs.knn_query_block.load(std::memory_order_relaxed);
   auto round_up = [](int64_t x, int64_t m) { return (x + m - 1) / m * m; };
-  const int64_t rows_up = round_up(num_rows > 0 ? num_rows : 1, kBR);
+  const int64_t rows_up = round_up(num_rows > 0 ? num_rows : 1, br);
   const int64_t budget_keys = (int64_t)(kCandBudgetBytes / sizeof(uint64_t));
   int64_t qb, chunk;
   if (knob_chunk > 0) {
-    chunk = round_up(knob_chunk, kBR);
-    qb = budget_keys / chunk / kBQ * kBQ;
+    chunk = round_up(knob_chunk, br);
+    qb = budget_keys / chunk / bq * bq;
   } else {
-    qb = round_up(num_queries, kBQ);
+    qb = round_up(num_queries, bq);
     if (qb > budget_keys / kDefaultChunkRows) qb = budget_keys / kDefaultChunkRows;
-    chunk = budget_keys / qb / kBR * kBR;
+    chunk = budget_keys / qb / br * br;
     if (chunk > kMaxChunkRows) chunk = kMaxChunkRows;
   }
   if (chunk > rows_up) chunk = rows_up;
-  if (knob_qb > 0) qb = round_up(knob_qb, kBQ);
-  if (qb < kBQ) qb = kBQ;
-  if (qb > round_up(num_queries, kBQ)) qb = round_up(num_queries, kBQ);
+  if (knob_qb > 0) qb = round_up(knob_qb, bq);
+  if (qb < bq) qb = bq;
+  if (qb > round_up(num_queries, bq)) qb = round_up(num_queries, bq);
   const int64_t first = knob_chunk > 0 ? chunk : (chunk < kDefaultFirstChunkRows ? chunk : kDefaultFirstChunkRows);
-  return KnnChunkPlan{qb, chunk, first};
+  return KnnChunkPlan{qb, chunk, first, bq, br};
 }
 // Per block of plan.qb queries (a.nq, a.queries and a.qn set to the block's): a.run starts empty, then per chunk of rows
 // score(q0, row0, row1, grid) launches the score kernel over grid = (row tiles, query tiles) and the select folds its
@@ -363,7 +423,7 @@ int knn_chunk_passes(KnnArgs& a, const KnnChunkPlan& plan, const float* d_q, con
     for (int64_t row0 = 0; row0 < a.t.num_rows;) {
       const int64_t len = row0 == 0 ? plan.first : plan.chunk;
       const int64_t row1 = row0 + len < a.t.num_rows ? row0 + len : a.t.num_rows;
-      const dim3 grid((unsigned)((row1 - row0 + kBR - 1) / kBR), (unsigned)((a.nq + kBQ - 1) / kBQ));
+      const dim3 grid((unsigned)((row1 - row0 + plan.br - 1) / plan.br), (unsigned)((a.nq + plan.bq - 1) / plan.bq));
       const int rc = score(q0, (int32_t)row0, (int32_t)row1, grid);
       if (rc != GLX_OK) return rc;
       knn_select(a, s);
@@ -382,7 +442,17 @@ int knn_refine(const KnnArgs& a, const uint64_t* cand, int32_t RP, int32_t R, hi
 // glx_knn_half.hip
 // the half-precision scan (GLX_KNN_PREC_HALF of glx_knn_search_ex) on device pointers (workspace slot 1)
 int knn_search_half_device(const glx_features* f, int metric, const float* d_q, int32_t num_queries, int32_t k,
-                           int32_t refine, int64_t* d_ids, float* d_dist, hipStream_t s);
+                           int32_t refine, int64_t* d_ids, float* d_dist, hipStream_t s, int tile = GLX_KNN_TILE_WIDE);
+
+// glx_knn_narrow.hip
+constexpr int kNarrowBQ = 32;   // queries per workgroup tile of a narrow score kernel
+constexpr int kNarrowBR = 256;  // table rows per workgroup tile: 64 per wave
+// the narrow score kernels over rows [row0, row1) of a.t: tiles = (row tiles, query tiles) of kNarrowBR x kNarrowBQ as
+// knn_chunk_passes counts them; the launch walks the row tiles with a grid sized to the device.  qh: the rounded queries
+// of the block, [a.nq, qld] (the half scan)
+int knn_score_narrow(const KnnArgs& a, int32_t row0, int32_t row1, dim3 tiles, hipStream_t s);
+int knn_score_narrow_half(const KnnArgs& a, const uint16_t* qh, int32_t qld, int32_t row0, int32_t row1, dim3 tiles,
+                          hipStream_t s);
 
 // glx_knn_ivf.hip
 // keys[n] = kNoKey

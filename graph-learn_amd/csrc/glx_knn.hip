@@ -281,14 +281,16 @@ void knn_finish(const KnnArgs& a, const glx_features* f, int64_t* d_ids, float* 
 }
 
 int knn_search_device(const glx_features* f, int metric, const float* d_q, int32_t num_queries, int32_t k,
-                      int64_t* d_ids, float* d_dist, hipStream_t s) {
+                      int64_t* d_ids, float* d_dist, hipStream_t s, int tile) {
+  const bool narrow = tile == GLX_KNN_TILE_NARROW;
   KnnArgs a;
   memset(&a, 0, sizeof(a));
   a.t = knn_table(f);
   a.k = k;
   a.KP = knn_pow2_at_least(k);
   a.metric = metric;
-  const KnnChunkPlan plan = knn_chunk_plan(a.t.num_rows, num_queries);
+  const KnnChunkPlan plan = narrow ? knn_chunk_plan(a.t.num_rows, num_queries, kNarrowBQ, kNarrowBR)
+                                   : knn_chunk_plan(a.t.num_rows, num_queries);
   const int64_t qb = plan.qb;
   a.cap = (int32_t)plan.chunk;
 
@@ -312,6 +314,7 @@ int knn_search_device(const glx_features* f, int metric, const float* d_q, int32
   return knn_chunk_passes(
       a, plan, d_q, qn, num_queries, s,
       [&](int64_t, int32_t row0, int32_t row1, dim3 grid) {
+        if (narrow) return knn_score_narrow(a, row0, row1, grid, s);
         GLX_KNN_LAUNCH_DT(&rc, a.t.dtype, knn_score_kernel, grid, 256, s, a, row0, row1);
         return rc;
       },

@@ -22,7 +22,9 @@
 //
 // Schedule.  knn_chunk_passes: the exact search's chunks, query blocks, init and select.  Per chunk,
 // knn_score_half_kernel computes the exact search's tile: 128 queries x 128 rows, four waves as 2 x 2, four 32x32
-// accumulators per wave across the whole column loop, and the shared epilogue (knn_tile_epilogue).  In front of it:
+// accumulators per wave across the whole column loop, and the shared epilogue (knn_tile_epilogue).  The row fronts
+// (HalfRow, knn_half_group) and the MFMA step live in glx_knn.h: the narrow tile (glx_knn_narrow.hip) uses them too.
+// In front of the tile:
 //   queries   knn_round_queries_kernel writes q^ as [num_queries, dim rounded up to 8] 16-bit words, zero past dim, so
 //             every query load is one aligned 16-byte load.
 //   rows      raw elements go global -> registers -> LDS, a group of eight columns a lane and load: 16 bytes of a 16-bit
@@ -61,9 +63,6 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int kHalfBK = 64;                 // columns per stage
 constexpr int kHalfGroups = kHalfBK / 8;    // 16-byte groups per tile row
 constexpr int kHalfLd = kHalfGroups + 1;    // LDS pitch in 16-byte units: 144 bytes
@@ -84,58 +83,6 @@ __global__ __launch_bounds__(256) void knn_round_queries_kernel(const float* __r
   }
   out[i] = v;
 }
-
-template <int DT>
-__device__ __forceinline__ knn_f32x16 knn_half_mfma(uint4 a, uint4 b, knn_f32x16 c) {
-  if constexpr (DT == GLX_DTYPE_BF16) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  } else {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  }
-}
-
-// columns [c0, c0 + 8) of the row at p (p[0] is column 0) as one group G of eight elements E, zero from dim on.  vec:
-// p + c0 is aligned to sizeof(G) whenever c0 is a multiple of 8.
-template <typename G, typename E>
-__device__ __forceinline__ G knn_half_group(const E* p, int32_t c0, int32_t dim, bool vec) {
-  if (c0 + 8 <= dim && vec) return *reinterpret_cast<const G*>(p + c0);
-  constexpr int kPer = 4 / (int)sizeof(E);  // elements per dword
-  struct {
-    uint32_t w[sizeof(G) / 4];
-  } v = {};
-#pragma unroll
-  for (int e = 0; e < 8; ++e)
-    if (c0 + e < dim) v.w[e / kPer] |= (uint32_t)p[c0 + e] << (8 * (int)sizeof(E) * (e % kPer));
-  return __builtin_bit_cast(G, v);
-}
-
-// The row front of a storage type: `elem` as the table stores it, `group` = eight of them as one load, kScan = the
-// 16-bit type the queries are rounded to and the MFMA runs in, words() = a group as the eight 16-bit words of an operand.
-template <int DT>
-struct HalfRow {
-  typedef uint16_t elem;
-  typedef uint4 group;
-  static constexpr int kScan = DT;
-  static __device__ __forceinline__ uint4 words(uint4 g) { return g; }
-};
-// float8: each pair of codes to two float32 (exact), whose high halves are the bfloat16 words (exact: see the header)
-template <int DT>
-struct HalfRowF8 {
-  typedef uint8_t elem;
-  typedef uint2 group;
-  static constexpr int kScan = GLX_DTYPE_BF16;
-  static __device__ __forceinline__ uint32_t pair(uint32_t codes, bool hi) {
-    const float __attribute__((ext_vector_type(2))) f = AggElem<DT>::up2(codes, hi);
-    return __builtin_amdgcn_perm(__float_as_uint(f.y), __float_as_uint(f.x), 0x07060302u);  // f.y's high half : f.x's
-  }
-  static __device__ __forceinline__ uint4 words(uint2 g) {
-    return make_uint4(pair(g.x, false), pair(g.x, true), pair(g.y, false), pair(g.y, true));
-  }
-};
-template <>
-struct HalfRow<GLX_DTYPE_F8E4M3> : HalfRowF8<GLX_DTYPE_F8E4M3> {};
-template <>
-struct HalfRow<GLX_DTYPE_F8E5M2> : HalfRowF8<GLX_DTYPE_F8E5M2> {};
 
 // One (128 queries x 128 rows) tile of half-precision scores for rows [row0, row1), filtered into the candidate
 // buffers.  qh: the rounded queries of this block, [a.nq, qld].  Rows past row1 and queries past a.nq are zero operands
@@ -245,7 +192,8 @@ static void knn_score_half(const KnnArgs& a, const uint16_t* qh, int32_t qld, in
 }
 
 int knn_search_half_device(const glx_features* f, int metric, const float* d_q, int32_t num_queries, int32_t k,
-                           int32_t refine, int64_t* d_ids, float* d_dist, hipStream_t s) {
+                           int32_t refine, int64_t* d_ids, float* d_dist, hipStream_t s, int tile) {
+  const bool narrow = tile == GLX_KNN_TILE_NARROW;
   const bool l2 = metric == GLX_KNN_L2;
   KnnArgs a;  // the scan: the refine best (k without refine) by the half score
   memset(&a, 0, sizeof(a));
@@ -253,7 +201,8 @@ int knn_search_half_device(const glx_features* f, int metric, const float* d_q, 
   a.k = refine > 0 ? refine : k;
   a.KP = knn_pow2_at_least(a.k);
   a.metric = metric;
-  const KnnChunkPlan plan = knn_chunk_plan(a.t.num_rows, num_queries);
+  const KnnChunkPlan plan = narrow ? knn_chunk_plan(a.t.num_rows, num_queries, kNarrowBQ, kNarrowBR)
+                                   : knn_chunk_plan(a.t.num_rows, num_queries);
   a.cap = (int32_t)plan.chunk;
   KnnArgs x = a;  // the re-rank: the k best of those by the exact search's chain
   x.k = k;
@@ -295,6 +244,7 @@ int knn_search_half_device(const glx_features* f, int metric, const float* d_q, 
   rc = knn_chunk_passes(
       a, plan, d_q, qn_half, num_queries, s,
       [&](int64_t q0, int32_t row0, int32_t row1, dim3 grid) {
+        if (narrow) return knn_score_narrow_half(a, qh + q0 * qld, qld, row0, row1, grid, s);
         knn_score_half(a, qh + q0 * qld, qld, row0, row1, grid, s);
         return GLX_OK;
       },
@@ -316,23 +266,6 @@ int knn_search_half_device(const glx_features* f, int metric, const float* d_q, 
 extern "C" int glx_knn_search_ex(const glx_features* f, int metric, const float* queries, int32_t num_queries, int32_t k,
                                  int precision, int32_t refine, int64_t* ids_out, float* dist_out, int ptr_kind,
                                  void* stream) {
-  GLX_REQUIRE(f != nullptr, "features is NULL");
-  GLX_KNN_REQUIRE();
-  GLX_REQUIRE(precision == GLX_KNN_PREC_F32 || precision == GLX_KNN_PREC_HALF,
-              "precision must be GLX_KNN_PREC_F32 (0) or GLX_KNN_PREC_HALF (1), got %d", precision);
-  if (precision == GLX_KNN_PREC_F32) {
-    GLX_REQUIRE(refine == 0, "refine must be 0 with precision GLX_KNN_PREC_F32, got %d", refine);
-    return glx_knn_search(f, metric, queries, num_queries, k, ids_out, dist_out, ptr_kind, stream);
-  }
-  GLX_REQUIRE(f->dtype == GLX_DTYPE_BF16 || f->dtype == GLX_DTYPE_F16 || glx_dtype_is_f8(f->dtype),
-              "precision GLX_KNN_PREC_HALF needs a bfloat16, float16 or float8 table, this one stores %s",
-              glx_dtype_name(f->dtype));
-  GLX_REQUIRE(refine == 0 || (refine >= k && refine <= kSortN), "refine must be 0 or in [k = %d, %d], got %d", k, kSortN,
-              refine);
-  GLX_REQUIRE((int64_t)num_queries * (refine > k ? refine : k) < INT32_MAX, "num_queries * max(k, refine) must be < 2^31");
-  GLX_REQUIRE(f->num_rows < INT32_MAX, "num_rows must be < 2^31");
-  return knn_search_entry(f->device, f->dim, queries, num_queries, k, ids_out, dist_out, ptr_kind, stream,
-                          [&](const float* d_q, int64_t* d_ids, float* d_dist, hipStream_t s) {
-                            return knn_search_half_device(f, metric, d_q, num_queries, k, refine, d_ids, d_dist, s);
-                          });
+  return glx_knn_search_tiled(f, metric, queries, num_queries, k, precision, refine, GLX_KNN_TILE_WIDE, ids_out, dist_out,
+                              ptr_kind, stream);
 }

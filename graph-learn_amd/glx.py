@@ -47,7 +47,7 @@ EXPORTS = [
     "glx_graph_has_timestamps", "glx_sample_temporal", "glx_sample_temporal_hops",
     "glx_features_create", "glx_features_view", "glx_features_destroy", "glx_features_info",
     "glx_features_create_ex", "glx_features_view_ex", "glx_features_dtype", "glx_features_convert_host",
-    "glx_knn_search", "glx_knn_search_ex", "glx_knn_merge",
+    "glx_knn_search", "glx_knn_search_ex", "glx_knn_search_tiled", "glx_knn_merge",
     "glx_knn_ivf_build", "glx_knn_ivf_search", "glx_knn_ivf_search_ex", "glx_knn_ivf_info", "glx_knn_ivf_export", "glx_knn_ivf_destroy",
     "glx_knn_ivfpq_build", "glx_knn_ivfpq_search", "glx_knn_ivfpq_info", "glx_knn_ivfpq_export",
     "glx_knn_ivfpq_destroy",
@@ -302,6 +302,7 @@ def lib():
         L.glx_tune.argtypes = [ctypes.c_char_p, i32]
         L.glx_knn_search.argtypes = [vp, ci, vp, i32, i32, vp, vp, ci, vp]
         L.glx_knn_search_ex.argtypes = [vp, ci, vp, i32, i32, ci, i32, vp, vp, ci, vp]
+        L.glx_knn_search_tiled.argtypes = [vp, ci, vp, i32, i32, ci, i32, ci, vp, vp, ci, vp]
         L.glx_knn_merge.argtypes = [ci, ci, i32, vp, vp, i32, i32, vp, vp, ci, vp]
         L.glx_knn_ivf_build.argtypes = [vp, i32, i32, i64, vp, ci, vp, ctypes.POINTER(vp)]
         L.glx_knn_ivf_search.argtypes = [vp, ci, vp, i32, i32, i32, vp, vp, ci, vp]
@@ -813,7 +814,7 @@ class Features:
         return out
 
 
-    def search(self, queries, k, metric="ip", out=None, precision="float32", refine=0):
+    def search(self, queries, k, metric="ip", out=None, precision="float32", refine=0, tile="wide"):
         """Exact k nearest rows of every query (glx_knn_search) -> (ids[n, k] int64, dist[n, k] float32), best first.
         queries[n, D] float32; metric "ip" (inner product, larger is better) or "l2" (squared distance by expansion,
         smaller is better).  The score is one ascending fmaf chain over the columns, ties go to the smaller storage
@@ -827,16 +828,24 @@ class Features:
         returns, bit for bit, what the bfloat16 table of the same values returns.  refine=0 returns the k best by that
         score; k <= refine <= 1024 re-scores the refine best with the fmaf chain against the float32 queries and returns
         the k best of those, every distance being the default search's distance of its row.  With precision="half" a
-        torch tensor of the table's scan type is accepted as queries (upcast exactly: its rounding is the identity)."""
+        torch tensor of the table's scan type is accepted as queries (upcast exactly: its rounding is the identity).
+        tile="narrow" (glx_knn_search_tiled) scores through 32-query tiles that stream the table once per 32 queries, for
+        requests of few queries; it returns the bits of tile="wide" at the same precision and refine.  No automatic
+        choice is made."""
         if precision not in KNN_PRECISIONS:
             raise ValueError("precision must be one of {}, not {!r}".format(sorted(KNN_PRECISIONS), precision))
-        if precision == "float32" and refine == 0:
+        if tile not in KNN_TILES:
+            raise ValueError("tile must be one of {}, not {!r}".format(sorted(KNN_TILES), tile))
+        if precision == "float32" and refine == 0 and tile == "wide":
             return _knn_search(lib().glx_knn_search, lambda: self._h, self.dim, self.device, queries, k, metric, out)
         scan = "bfloat16" if self.dtype in FP8_FEATURE_DTYPES else self.dtype
         if precision == "half" and _is_torch(queries) and str(queries.dtype) == "torch." + scan:
             queries = queries.float()
-        return _knn_search(lib().glx_knn_search_ex, lambda: self._h, self.dim, self.device, queries, k, metric, out,
-                           KNN_PRECISIONS[precision], int(refine))
+        if tile == "wide":
+            return _knn_search(lib().glx_knn_search_ex, lambda: self._h, self.dim, self.device, queries, k, metric, out,
+                               KNN_PRECISIONS[precision], int(refine))
+        return _knn_search(lib().glx_knn_search_tiled, lambda: self._h, self.dim, self.device, queries, k, metric, out,
+                           KNN_PRECISIONS[precision], int(refine), KNN_TILES[tile])
 
     def build_ivf(self, nlist, niter=10, train_rows=None, centroids=None):
         """An IVF-Flat index over this table (glx_knn_ivf_build) -> KnnIvf.  nlist lists, niter Lloyd iterations over a
@@ -855,6 +864,7 @@ class Features:
 KNN_METRICS = {"l2": 0, "ip": 1}  # GLX_KNN_L2, GLX_KNN_IP
 KNN_IVF_SCHEDULES = {"query": 0, "list": 1}  # GLX_KNN_SCHED_QUERY, GLX_KNN_SCHED_LIST
 KNN_PRECISIONS = {"float32": 0, "half": 1}  # GLX_KNN_PREC_F32, GLX_KNN_PREC_HALF
+KNN_TILES = {"wide": 0, "narrow": 1}  # GLX_KNN_TILE_WIDE, GLX_KNN_TILE_NARROW
 
 
 class _KnnIndex:

@@ -51,7 +51,8 @@ extern "C" {
  * the bfloat16 training path -- glx_aggregate_backward_ex, glx_aggregate_weighted_ex,
  * glx_aggregate_weighted_backward_x_ex, glx_aggregate_weighted_backward_w_ex, glx_pair_dot_ex,
  * glx_pair_dot_backward_ex; chunked row gradients -- glx_aggregate_backward_chunked,
- * glx_aggregate_weighted_backward_x_chunked; the half-precision KNN scan -- GLX_KNN_PREC_*, glx_knn_search_ex. */
+ * glx_aggregate_weighted_backward_x_chunked; the half-precision KNN scan -- GLX_KNN_PREC_*, glx_knn_search_ex;
+ * the narrow KNN tile -- GLX_KNN_TILE_*, glx_knn_search_tiled. */
 #define GLX_ABI_VERSION 5
 
 /* Exported symbols: libglx.so is built with -fvisibility=hidden. */
@@ -523,7 +524,18 @@ GLX_API int glx_features_convert_host(const float* src, int64_t n, int store_dty
  *            table under glx_knn_search's contract against the float32 queries as given (IVF-PQ's re-rank) and the k
  *            best of those returned: every returned dist is glx_knn_search's dist of that row.
  * glx_knn_search's limits apply, and num_queries * max(k, refine) < 2^31.  No float atomics.  A rejected call names
- * the argument in glx_last_error and leaves the outputs untouched. */
+ * the argument in glx_last_error and leaves the outputs untouched.
+ *
+ * glx_knn_search_tiled: glx_knn_search_ex with a choice of the score kernels' tile (an addition of this engine as well).
+ * GLX_KNN_TILE_WIDE is glx_knn_search_ex itself: 128 queries x 128 rows per workgroup, a request padded to 128 queries.
+ * GLX_KNN_TILE_NARROW is an opt-in for requests of few queries (contract K-knn-narrow): 32 queries x 256 rows per
+ * workgroup, the query rows kept in LDS while the workgroup walks the table, so a request of up to 32 queries streams
+ * the table once and multiplies a quarter of the padding.  More than 32 queries are legal; every 32 read the table
+ * again.  For every input NARROW returns the bits WIDE returns at the same precision and refine -- ids, distance bits,
+ * tie order, padding, NaN last, the +0.0f zero and the canonical NaN of the half scan -- on every call and under every
+ * chunking: a (query, row)'s score is the same instruction sequence over the same operands in both tiles.  There is no
+ * automatic choice.  Any other tile value is GLX_INVALID_ARGUMENT, names the argument in glx_last_error and writes
+ * nothing; every other check, limit and output rule is glx_knn_search_ex's, host and device pointers alike. */
 #define GLX_KNN_L2 0 /* the reference's KnnMetric values: contrib/knn/config.h:21-23 with flat_index.cc:27-28 */
 #define GLX_KNN_IP 1
 GLX_API int glx_knn_search(const glx_features* f, int metric, const float* queries, int32_t num_queries, int32_t k,
@@ -533,6 +545,11 @@ GLX_API int glx_knn_search(const glx_features* f, int metric, const float* queri
 GLX_API int glx_knn_search_ex(const glx_features* f, int metric, const float* queries, int32_t num_queries, int32_t k,
                               int precision, int32_t refine, int64_t* ids_out, float* dist_out, int ptr_kind,
                               void* stream);
+#define GLX_KNN_TILE_WIDE 0   /* glx_knn_search_ex itself */
+#define GLX_KNN_TILE_NARROW 1 /* opt-in: 32-query tiles, the table streamed once per 32 queries */
+GLX_API int glx_knn_search_tiled(const glx_features* f, int metric, const float* queries, int32_t num_queries, int32_t k,
+                                 int precision, int32_t refine, int tile, int64_t* ids_out, float* dist_out,
+                                 int ptr_kind, void* stream);
 GLX_API int glx_knn_merge(int device, int metric, int32_t num_parts, const int64_t* ids, const float* dist,
                           int32_t num_queries, int32_t k, int64_t* ids_out, float* dist_out, int ptr_kind,
                           void* stream);
