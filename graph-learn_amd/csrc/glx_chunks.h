@@ -2,7 +2,8 @@
 // list of more than GLX_COALESCE_CHUNK entries is LONG and is cut into chunks of that many entries; a chunk's partial
 // is +0.0f plus its terms in ascending entry, the list's sum +0.0f plus its partials in ascending chunk.  Every other
 // list is short, has no chunk, and keeps the default order's bits.  This header is the one place that knows
-//   the lists        GlxRowLists (a table row's transposed list of positions), GlxSegLists (a segment's positions)
+//   the lists        GlxRowLists (a table row's transposed list of positions), GlxSegLists (a segment's positions),
+//                    GlxPairRuns (a table row's run of pairs)
 //   the directory    GlxChunkDir, built on the device by glx_chunk_dir: one scan, one search per work item; neither the
 //                    number of long lists nor of chunks reaches the host
 //   a chunk          GLX_CHUNK_IDLE: work item t is past the directory; glx_chunk_of: t is entries [c0, c1) of its
@@ -21,9 +22,11 @@ constexpr int kGlxChunk = GLX_COALESCE_CHUNK;
 // The workspace slots (GlxScratch, glx_common.h) of the training path.  A slot has one lease at a time, so a call that
 // leases inside another call's lease needs a slot of its own: each line says who holds the slot, and for how long.
 enum GlxTrainSlot {
-  kSlotRequest = 1,       // the request's transpose or segment ends: the entry point, for its whole body
+  kSlotRequest = 1,       // the request's transpose or segment ends: the entry point, for its whole body (pair_dot's
+                          // backward: the own side's transpose)
   kSlotRowChunks = 2,     // the row directory and its partial sums: the chunked row gradient, inside glx_weighted_bwd_x
-                          // or the aggregate backward
+                          // or the aggregate backward; the run directory of chunked pair_dot's backward and the row
+                          // directory of chunked GAT attention's grad_t, which call neither
   kSlotAlpha = 2,         // the same slot: dot attention's alpha in the default order, whose row gradients lease none
   kSlotChunkScan = 3,     // the temporary of glx_chunk_dir's scan: given back before the builder returns
   kSlotAlphaChunked = 4,  // dot attention's alpha in the chunked order: read across the chunked glx_weighted_bwd_x
@@ -42,6 +45,17 @@ struct GlxSegLists {
   GlxSegLayout seg;  // the consumed positions of a segment
   __device__ __forceinline__ void bounds(int64_t i, int32_t* begin, int32_t* end) const {
     seg_bounds(seg, i, begin, end);
+  }
+};
+// A table row's RUN of pairs (glx_pair_dot.hip): its transposed list of own-side entries, each expanded to own_rep
+// consecutive pairs.  The bounds are in pair units -- pair e of the run is pair e % own_rep of entry
+// pos[row_ptr[i] + e / own_rep] -- so a chunk may begin or end inside one entry's expansion.  At most num_pairs in all.
+struct GlxPairRuns {
+  const int32_t* row_ptr;  // the own side's transpose's
+  int32_t own_rep;         // pairs per own-side entry
+  __device__ __forceinline__ void bounds(int64_t i, int32_t* begin, int32_t* end) const {
+    *begin = row_ptr[i] * own_rep;
+    *end = row_ptr[i + 1] * own_rep;
   }
 };
 

@@ -14,10 +14,17 @@
 //   backward  ga = keep ? grad_alpha * scale : +0.0f (the mask is recomputed); d = soft * (ga - sum_q soft_q * ga_q);
 //             grad_e = pre > 0 ? d : d * negative_slope; grad_s[sg, h] = the segment's sum of grad_e, by the same
 //             lane group; grad_t[r, h] = +0.0f plus grad_e[p, h] over the consumed p with rows[p] == r in ascending p
+//   chunked   glx_gat_attention_backward_chunked: grad_e and grad_s are the default's, from
+//             the same kernel; grad_t is summed in the CHUNKED order of glx_chunks.h -- a row named more than 256 times
+//             is cut into chunks of 256 entries, partial[t, h] = +0.0f plus grad_e[p, h] in ascending p, the row +0.0f
+//             plus its partials in ascending chunk; a row named at most 256 times keeps the default's bits.  By
+//             construction the bits of glx_aggregate_backward_chunked(Sum) of grad_e with one position per segment and
+//             dim = heads.
 // EVERY element of every output is written; a position that is not consumed gets +0.0f.  No float atomics: the lane
 // mapping and the trees are fixed (glx_segment_lanes.h), so the same inputs give the same bits on every call.
 #include <math.h>
 
+#include "glx_chunks.h"
 #include "glx_segment_lanes.h"
 
 namespace {
@@ -125,7 +132,9 @@ void gat_launch(const GatArgs& a, bool drop, hipStream_t s) {
 
 // grad_t: one lane per (row, head) walks the row's positions in ascending order (the transpose's stable sort), so
 // the bits are those of glx_aggregate_backward(Sum) with one position per segment.  Rows of `heads` floats are too
-// narrow for that kernel's 8 .. 64-lane row groups.
+// narrow for that kernel's 8 .. 64-lane row groups.  SHORT (the chunked order): a row named more than kGlxChunk times
+// is left to the chunk and combine kernels.
+template <bool SHORT>
 __global__ __launch_bounds__(256) void glx_gat_grad_t_kernel(const int32_t* __restrict__ row_ptr,
                                                              const int32_t* __restrict__ pos,
                                                              const float* __restrict__ grad_e,
@@ -135,9 +144,29 @@ __global__ __launch_bounds__(256) void glx_gat_grad_t_kernel(const int32_t* __re
   const int64_t r = i / heads;
   const int32_t h = (int32_t)(i - r * heads);
   const int32_t l0 = row_ptr[r], l1 = row_ptr[r + 1];
+  if (SHORT && l1 - l0 > kGlxChunk) return;
   float acc = 0.0f;
   for (int32_t j = l0; j < l1; ++j) acc = acc + grad_e[(int64_t)pos[j] * heads + h];
   grad_t[i] = acc;
+}
+
+// The chunk pass of grad_t's chunked order: one lane per (work item, head) of the row directory -- not a lane group,
+// the rows are `heads` floats wide -- walks the entries [c0, c1) of its chunk in ascending position into
+// partial[t, h].  Neighbouring lanes are the heads of one chunk, then the next chunk: a hub row's chunks run side by
+// side.  Lanes past the directory leave.
+__global__ __launch_bounds__(256) void glx_gat_grad_t_chunk_kernel(const int32_t* __restrict__ row_ptr,
+                                                                   const int32_t* __restrict__ pos,
+                                                                   const float* __restrict__ grad_e, GlxChunkDir ch,
+                                                                   int32_t heads) {
+  const int64_t i = blockIdx.x * 256LL + threadIdx.x;
+  const int64_t t = i / heads;
+  const int32_t h = (int32_t)(i - t * heads);
+  if (GLX_CHUNK_IDLE(ch, t)) return;
+  int32_t r, c0, c1;
+  glx_chunk_of(ch, GlxRowLists{row_ptr}, t, &r, &c0, &c1);
+  float acc = 0.0f;
+  for (int32_t j = c0; j < c1; ++j) acc = acc + grad_e[(int64_t)pos[j] * heads + h];
+  ch.partial[i] = acc;
 }
 
 }  // namespace
@@ -203,12 +232,12 @@ extern "C" int glx_gat_attention(int device, const float* s, const float* t, int
   return st.finish(rc);
 }
 
-extern "C" int glx_gat_attention_backward(int device, const float* soft, const float* grad_alpha, const float* s,
-                                          const float* t, int64_t num_rows, const int64_t* rows, int32_t heads,
-                                          const int32_t* cnt, int32_t num_ids, int32_t num_segments,
-                                          float negative_slope, float default_attr, float drop_p, uint64_t seed,
-                                          uint64_t call, float* grad_e_out, float* grad_s_out, float* grad_t_out,
-                                          int ptr_kind, void* stream) {
+// the body of glx_gat_attention_backward and glx_gat_attention_backward_chunked
+static int gat_attention_backward(const float* soft, const float* grad_alpha, const float* s, const float* t,
+                                  int64_t num_rows, const int64_t* rows, int32_t heads, const int32_t* cnt,
+                                  int32_t num_ids, int32_t num_segments, float negative_slope, float default_attr,
+                                  float drop_p, uint64_t seed, uint64_t call, float* grad_e_out, float* grad_s_out,
+                                  float* grad_t_out, bool chunked, int device, int ptr_kind, void* stream) {
   GLX_GAT_REQUIRE();
   GLX_REQUIRE(num_ids == 0 || soft != nullptr, "soft is NULL");
   GLX_REQUIRE(num_ids == 0 || grad_alpha != nullptr, "grad_alpha is NULL");
@@ -234,7 +263,7 @@ extern "C" int glx_gat_attention_backward(int device, const float* soft, const f
   st.out(&a.grad_s, grad_s_out, s_count);
   st.out(&d_gt, grad_t_out, t_count);
   rc = st.begin();
-  GlxScratch lease;
+  GlxScratch lease, chunk_lease;
   if (rc == GLX_OK) {
     if (num_ids == 0 || num_segments == 0) {  // nothing was consumed: every output is zeros
       rc = glx_zero_f32_async(a.out, count, st.s);
@@ -245,6 +274,10 @@ extern "C" int glx_gat_attention_backward(int device, const float* soft, const f
       GlxAggTranspose tr;
       rc = glx_seg_layout_bwd(want_t, a.rows, cnt ? d_cnt : nullptr, num_ids, num_segments, num_rows, st.s, &lease, &tr,
                               &a.seg);
+      GlxChunkDir chunks;
+      if (rc == GLX_OK && want_t && chunked) {
+        rc = glx_row_chunk_dir(tr, num_ids, num_rows, heads, st.s, &chunk_lease, &chunks);
+      }
       if (rc == GLX_OK) {
         a.soft_out = nullptr;
         a.num_rows = num_rows;
@@ -255,11 +288,41 @@ extern "C" int glx_gat_attention_backward(int device, const float* soft, const f
         gat_launch<true>(a, drop_p != 0.0f, st.s);
         if (want_t) {
           const int64_t total = (int64_t)t_count;
-          glx_gat_grad_t_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st.s>>>(tr.row_ptr, tr.pos, a.out, d_gt, total,
-                                                                                 heads);
+          const unsigned blocks = (unsigned)((total + 255) / 256);
+          if (!chunked) {
+            glx_gat_grad_t_kernel<false><<<blocks, 256, 0, st.s>>>(tr.row_ptr, tr.pos, a.out, d_gt, total, heads);
+          } else {
+            const unsigned cblocks = (unsigned)(((int64_t)chunks.max_items * heads + 255) / 256);
+            glx_gat_grad_t_kernel<true><<<blocks, 256, 0, st.s>>>(tr.row_ptr, tr.pos, a.out, d_gt, total, heads);
+            glx_gat_grad_t_chunk_kernel<<<cblocks, 256, 0, st.s>>>(tr.row_ptr, tr.pos, a.out, chunks, heads);
+            glx_chunks_combine(chunks, d_gt, GLX_DTYPE_F32, heads, false, st.s);
+          }
         }
       }
     }
   }
   return st.finish(rc);
+}
+
+extern "C" int glx_gat_attention_backward(int device, const float* soft, const float* grad_alpha, const float* s,
+                                          const float* t, int64_t num_rows, const int64_t* rows, int32_t heads,
+                                          const int32_t* cnt, int32_t num_ids, int32_t num_segments,
+                                          float negative_slope, float default_attr, float drop_p, uint64_t seed,
+                                          uint64_t call, float* grad_e_out, float* grad_s_out, float* grad_t_out,
+                                          int ptr_kind, void* stream) {
+  return gat_attention_backward(soft, grad_alpha, s, t, num_rows, rows, heads, cnt, num_ids, num_segments,
+                                negative_slope, default_attr, drop_p, seed, call, grad_e_out, grad_s_out, grad_t_out,
+                                false, device, ptr_kind, stream);
+}
+
+extern "C" int glx_gat_attention_backward_chunked(int device, const float* soft, const float* grad_alpha,
+                                                  const float* s, const float* t, int64_t num_rows,
+                                                  const int64_t* rows, int32_t heads, const int32_t* cnt,
+                                                  int32_t num_ids, int32_t num_segments, float negative_slope,
+                                                  float default_attr, float drop_p, uint64_t seed, uint64_t call,
+                                                  float* grad_e_out, float* grad_s_out, float* grad_t_out,
+                                                  int ptr_kind, void* stream) {
+  return gat_attention_backward(soft, grad_alpha, s, t, num_rows, rows, heads, cnt, num_ids, num_segments,
+                                negative_slope, default_attr, drop_p, seed, call, grad_e_out, grad_s_out, grad_t_out,
+                                true, device, ptr_kind, stream);
 }

@@ -13,12 +13,19 @@
 //   backward   side 0 (xa): grad[r, c] = +0.0f, then for each pair p with ia[p / repeat] == r in ascending p
 //              fadd_rn(., fmul_rn(g[p, head(c)], xb_row(p)[c])); side 1 (xb): pairs with ib[p] == r, factor xa_row(p)[c].
 //              An own index outside the table receives nothing.  Bit-exact.
+//   chunked    glx_pair_dot_backward_chunked: the same terms in the CHUNKED order of
+//              glx_chunks.h.  A table row's RUN is its own-side entries in ascending entry, each expanded to own_rep
+//              (side 0: repeat, side 1: 1) consecutive pairs: L pairs in ascending p.  A run with L > 256 is long:
+//              chunk j is pairs [256 j, min(256 j + 256, L)) of the run -- with repeat > 1 a boundary may fall inside one
+//              entry's expansion -- a chunk's partial is +0.0f plus its terms in ascending pair, the row +0.0f plus its
+//              partials in ascending chunk.  Every other row keeps the default's bits; every row is written once.
 // No float atomics anywhere.
 //
 // The tables are float32 or bfloat16, both of one type (the _ex entry points).  bfloat16 rows are upcast
 // as they are loaded -- exact -- so out stays float32 and equals the float32 call on the upcast tables bit for bit (the
 // same VEC, plan and tree); a bfloat16 grad_self is the float32 sum above rounded once per element, to nearest even
 // (glx_f32_to_bf16_bits), in the kernel's final store.  g and out are always float32.
+#include "glx_chunks.h"
 #include "glx_lane_groups.h"
 
 // Two roundings per term of the backward: glx_fold_rn (glx_lane_groups.h) pins the product; the pragma is for the
@@ -107,7 +114,9 @@ struct PairBwdArgs {
 // other side's row, already tested against the table), every lane reads entry j from lane j; kWU row loads and their
 // g are issued before the first is folded.  Every row is written, an empty list writes zeros.  A bfloat16 x_other is
 // upcast as it is loaded, the sum is float32, and a bfloat16 grad_self rounds the finished sum once, in the store.
-template <int G, int VEC, int DT>
+// SHORT (the chunked order): a run of more than kGlxChunk pairs is left to the chunk and combine kernels; every other
+// row gets exactly what the default order gives it.
+template <int G, int VEC, int DT, bool SHORT>
 __global__ __launch_bounds__(256) void glx_pair_dot_bwd_kernel(PairBwdArgs a) {
   typedef float vec_t __attribute__((ext_vector_type(VEC)));
   typedef typename AggElem<DT>::raw raw_t;
@@ -117,6 +126,7 @@ __global__ __launch_bounds__(256) void glx_pair_dot_bwd_kernel(PairBwdArgs a) {
   if (r >= a.num_rows_self) return;  // whole groups leave
   const int32_t l0 = a.t.row_ptr[r];
   const int32_t total = (a.t.row_ptr[r + 1] - l0) * a.own_rep;  // at most num_pairs
+  if (SHORT && total > kGlxChunk) return;
   raw_t* const out = static_cast<raw_t*>(a.grad_self) + r * (int64_t)a.dim;
   for (int32_t col_pass = 0; col_pass < a.dim; col_pass += G * VEC) {
     const int32_t col = col_pass + c * VEC;
@@ -170,22 +180,102 @@ __global__ __launch_bounds__(256) void glx_pair_dot_bwd_kernel(PairBwdArgs a) {
   }
 }
 
+// G lanes own work item t of the run directory: pairs [e0, e1) of a long run -- counted from the run's first pair, as
+// the walk above counts -- folded into the item's float32 partial sum in ascending pair.  The walk is the kernel's
+// above, spelled out a second time and not shared through a function: behind one, the default order's instantiations
+// come out with other register counts (GLX_CHUNK_IDLE's reason, glx_chunks.h).  Whole groups leave past
+// the directory.
+template <int G, int VEC, int DT>
+__global__ __launch_bounds__(256) void glx_pair_dot_bwd_chunk_kernel(PairBwdArgs a, GlxChunkDir ch) {
+  typedef float vec_t __attribute__((ext_vector_type(VEC)));
+  typedef typename AggElem<DT>::raw raw_t;
+  const raw_t* __restrict__ x_other = static_cast<const raw_t*>(a.x_other);
+  const int64_t t = blockIdx.x * (int64_t)(256 / G) + threadIdx.x / G;
+  const int c = threadIdx.x & (G - 1);
+  if (GLX_CHUNK_IDLE(ch, t)) return;
+  int32_t r, c0, c1;
+  glx_chunk_of(ch, GlxPairRuns{a.t.row_ptr, a.own_rep}, t, &r, &c0, &c1);
+  const int32_t l0 = a.t.row_ptr[r];
+  const int32_t e0 = c0 - l0 * a.own_rep, e1 = c1 - l0 * a.own_rep;
+  float* const out = ch.partial + t * (int64_t)a.dim;
+  for (int32_t col_pass = 0; col_pass < a.dim; col_pass += G * VEC) {
+    const int32_t col = col_pass + c * VEC;
+    const bool col_ok = col < a.dim;
+    const int32_t col_ld = col_ok ? col : 0;
+    const int32_t head = col_ld / a.C;
+    vec_t acc;
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) acc[v] = 0.0f;
+    for (int32_t base = e0; base < e1; base += G) {
+      int32_t my_p = 0, my_row = -1;
+      if (base + c < e1) {
+        const int32_t e = base + c;
+        my_p = a.t.pos[l0 + e / a.own_rep] * a.own_rep + e % a.own_rep;
+        const int64_t o = a.other_idx[my_p / a.other_rep];
+        my_row = (o >= 0 && o < a.num_rows_other) ? (int32_t)o : -1;
+      }
+      const int32_t m = (e1 - base) < G ? (e1 - base) : G;
+      for (int32_t j = 0; j < m; j += kWU) {
+        int32_t pr[kWU], row[kWU];
+#pragma unroll
+        for (int u = 0; u < kWU; ++u) {
+          const int src = (j + u) & (G - 1);
+          pr[u] = __shfl(my_p, src, G);
+          row[u] = __shfl(my_row, src, G);
+        }
+        vec_t val[kWU];
+        float gt[kWU];
+#pragma unroll
+        for (int u = 0; u < kWU; ++u) {
+          if (j + u < m) {
+            gt[u] = a.g[(int64_t)pr[u] * a.heads + head];
+            if (row[u] >= 0) {
+              val[u] = agg_load<DT, VEC>(x_other + row[u] * (int64_t)a.dim + col_ld);
+            } else {
+#pragma unroll
+              for (int v = 0; v < VEC; ++v) val[u][v] = a.default_attr;
+            }
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < kWU; ++u) {
+          if (j + u < m) {
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) acc[v] = glx_fold_rn(acc[v], gt[u], val[u][v]);
+          }
+        }
+      }
+    }
+    if (col_ok) agg_store<GLX_DTYPE_F32, VEC>(out + col, acc);
+  }
+}
+
+// ch == nullptr: the default order, one launch; otherwise the chunked one over that directory -- short runs, chunks,
+// combine (glx_row_grad_launch's shape).
 template <int VEC>
-void launch_pair_bwd_vec(const PairBwdArgs& a, hipStream_t s) {
+void launch_pair_bwd_vec(const PairBwdArgs& a, const GlxChunkDir* ch, hipStream_t s) {
   const int G = glx_group_for((a.dim + VEC - 1) / VEC);
   const unsigned blocks = (unsigned)((a.num_rows_self + (256 / G) - 1) / (256 / G));
   glx_for_group(G, [&](auto g) {
     glx_for_train_dtype(a.dtype, [&](auto t) {
-      glx_pair_dot_bwd_kernel<decltype(g)::value, VEC, decltype(t)::value><<<blocks, 256, 0, s>>>(a);
+      constexpr int kG = decltype(g)::value, kDT = decltype(t)::value;
+      if (ch == nullptr) {
+        glx_pair_dot_bwd_kernel<kG, VEC, kDT, false><<<blocks, 256, 0, s>>>(a);
+      } else {
+        const unsigned cblocks = (unsigned)(((int64_t)ch->max_items + (256 / kG) - 1) / (256 / kG));
+        glx_pair_dot_bwd_kernel<kG, VEC, kDT, true><<<blocks, 256, 0, s>>>(a);
+        glx_pair_dot_bwd_chunk_kernel<kG, VEC, kDT><<<cblocks, 256, 0, s>>>(a, *ch);
+      }
     });
   });
+  if (ch != nullptr) glx_chunks_combine(*ch, a.grad_self, a.dtype, a.dim, VEC == 4, s);
 }
 
-void launch_pair_bwd(const PairBwdArgs& a, hipStream_t s) {
+void launch_pair_bwd(const PairBwdArgs& a, const GlxChunkDir* ch, hipStream_t s) {
   const bool vec4 = a.dim % 4 == 0 && a.C % 4 == 0 && glx_aligned_vec4(a.x_other, a.dtype) &&
                     glx_aligned_vec4(a.grad_self, a.dtype);
-  if (vec4) launch_pair_bwd_vec<4>(a, s);
-  else launch_pair_bwd_vec<1>(a, s);
+  if (vec4) launch_pair_bwd_vec<4>(a, ch, s);
+  else launch_pair_bwd_vec<1>(a, ch, s);
 }
 
 }  // namespace
@@ -249,12 +339,11 @@ extern "C" int glx_pair_dot(int device, const float* xa, int64_t num_rows_a, con
                          default_attr, out, ptr_kind, stream);
 }
 
-extern "C" int glx_pair_dot_backward_ex(int device, int side, const int64_t* ia, const int64_t* ib, int32_t num_pairs,
-                                        int32_t repeat, const float* g, int32_t heads, const void* x_other,
-                                        int64_t num_rows_other, int32_t dim, int64_t num_rows_self,
-                                        float default_attr, void* grad_self, int x_dtype, int ptr_kind,
-                                        void* stream) {
-  GLX_REQUIRE_TRAIN_DTYPE(x_dtype, "glx_pair_dot_backward_ex: x_dtype");
+// the body of glx_pair_dot_backward_ex and glx_pair_dot_backward_chunked, which have checked x_dtype
+static int pair_dot_backward(int device, int side, const int64_t* ia, const int64_t* ib, int32_t num_pairs,
+                             int32_t repeat, const float* g, int32_t heads, const void* x_other, int64_t num_rows_other,
+                             int32_t dim, int64_t num_rows_self, float default_attr, void* grad_self, int x_dtype,
+                             bool chunked, int ptr_kind, void* stream) {
   GLX_PAIR_REQUIRE();
   GLX_REQUIRE(side == 0 || side == 1, "side must be 0 (xa) or 1 (xb), got %d", side);
   GLX_REQUIRE(num_rows_other >= 0 && num_rows_self >= 0, "negative sizes: num_rows");
@@ -281,7 +370,7 @@ extern "C" int glx_pair_dot_backward_ex(int device, int side, const int64_t* ia,
   st.in_bytes(&a.x_other, x_other, (size_t)num_rows_other * dim * elem);
   st.out_bytes(&a.grad_self, grad_self, (size_t)num_rows_self * dim * elem);
   rc = st.begin();
-  GlxScratch lease;
+  GlxScratch lease, chunk_lease;
   if (rc == GLX_OK) {
     if (num_pairs == 0) {  // no pair: every row is zeros
       rc = glx_zero_elems_async(a.grad_self, (size_t)num_rows_self * dim, x_dtype, st.s);
@@ -289,6 +378,12 @@ extern "C" int glx_pair_dot_backward_ex(int device, int side, const int64_t* ia,
       // one position per segment; side 0 sorts the num_pairs / repeat entries of ia only
       const int32_t own_n = side == 0 ? num_pairs / repeat : num_pairs;
       rc = glx_agg_transpose(side == 0 ? d_ia : d_ib, nullptr, own_n, own_n, num_rows_self, st.s, &lease, &a.t);
+      a.own_rep = side == 0 ? repeat : 1;
+      GlxChunkDir chunks;
+      if (rc == GLX_OK && chunked) {  // the runs hold at most num_pairs pairs in all
+        rc = glx_chunk_dir(GlxPairRuns{a.t.row_ptr, a.own_rep}, num_rows_self, num_pairs, dim, kSlotRowChunks,
+                           "chunked pair_dot backward: scan the long runs' chunk counts", st.s, &chunk_lease, &chunks);
+      }
       if (rc == GLX_OK) {
         a.other_idx = side == 0 ? d_ib : d_ia;
         a.num_rows_self = num_rows_self;
@@ -296,14 +391,33 @@ extern "C" int glx_pair_dot_backward_ex(int device, int side, const int64_t* ia,
         a.dim = dim;
         a.heads = heads;
         a.C = dim / heads;
-        a.own_rep = side == 0 ? repeat : 1;
         a.other_rep = side == 0 ? 1 : repeat;
         a.default_attr = default_attr;
-        launch_pair_bwd(a, st.s);
+        launch_pair_bwd(a, chunked ? &chunks : nullptr, st.s);
       }
     }
   }
   return st.finish(rc);
+}
+
+extern "C" int glx_pair_dot_backward_ex(int device, int side, const int64_t* ia, const int64_t* ib, int32_t num_pairs,
+                                        int32_t repeat, const float* g, int32_t heads, const void* x_other,
+                                        int64_t num_rows_other, int32_t dim, int64_t num_rows_self,
+                                        float default_attr, void* grad_self, int x_dtype, int ptr_kind,
+                                        void* stream) {
+  GLX_REQUIRE_TRAIN_DTYPE(x_dtype, "glx_pair_dot_backward_ex: x_dtype");
+  return pair_dot_backward(device, side, ia, ib, num_pairs, repeat, g, heads, x_other, num_rows_other, dim,
+                           num_rows_self, default_attr, grad_self, x_dtype, false, ptr_kind, stream);
+}
+
+extern "C" int glx_pair_dot_backward_chunked(int device, int side, const int64_t* ia, const int64_t* ib,
+                                             int32_t num_pairs, int32_t repeat, const float* g, int32_t heads,
+                                             const void* x_other, int64_t num_rows_other, int32_t dim,
+                                             int64_t num_rows_self, float default_attr, void* grad_self, int x_dtype,
+                                             int ptr_kind, void* stream) {
+  GLX_REQUIRE_TRAIN_DTYPE(x_dtype, "glx_pair_dot_backward_chunked: x_dtype");
+  return pair_dot_backward(device, side, ia, ib, num_pairs, repeat, g, heads, x_other, num_rows_other, dim,
+                           num_rows_self, default_attr, grad_self, x_dtype, true, ptr_kind, stream);
 }
 
 extern "C" int glx_pair_dot_backward(int device, int side, const int64_t* ia, const int64_t* ib, int32_t num_pairs,

@@ -61,6 +61,7 @@ EXPORTS = [
     "glx_aggregate_weighted_backward_w_ex", "glx_pair_dot_ex", "glx_pair_dot_backward_ex",
     "glx_aggregate_backward_chunked", "glx_aggregate_weighted_backward_x_chunked",
     "glx_dot_attention_chunked", "glx_dot_attention_backward_chunked",
+    "glx_pair_dot_backward_chunked", "glx_gat_attention_backward_chunked",
     "glx_rows_coalesce", "glx_embedding_update",
     "glx_tgn_store_update", "glx_tgn_message", "glx_tgn_message_backward", "glx_tgn_memory_write",
     "glx_partition", "glx_stitch_i64", "glx_stitch_f32", "glx_aggregate_stitch",
@@ -222,6 +223,8 @@ def lib():
         # the chunked order of dot-product attention: the default entry points' arguments
         L.glx_dot_attention_chunked.argtypes = L.glx_dot_attention.argtypes
         L.glx_dot_attention_backward_chunked.argtypes = L.glx_dot_attention_backward.argtypes
+        L.glx_pair_dot_backward_chunked.argtypes = L.glx_pair_dot_backward_ex.argtypes
+        L.glx_gat_attention_backward_chunked.argtypes = L.glx_gat_attention_backward.argtypes
         L.glx_rows_coalesce.argtypes =[ci, vp, i32, i64, i32, vp, vp, vp, vp, ci, vp]
         L.glx_embedding_update.argtypes = [ci, ci, vp, vp, vp, i64, i32, vp, vp, i32, f32, f32, f32, f32, f32, f32, vp]
         L.glx_tgn_store_update.argtypes = [ci, i64, i32, vp, vp, vp, vp, i32, i64, vp, vp, vp, vp, vp]
@@ -1301,13 +1304,18 @@ def gat_attention(s, t, rows, cnt=None, negative_slope=0.2, default_attr=0.0, dr
 
 
 def gat_attention_backward(soft, grad_alpha, s, t, rows, cnt=None, negative_slope=0.2, default_attr=0.0, drop_p=0.0,
-                           seed=0, call=0, want_s=True, want_t=True, out=None, out_s=None, out_t=None, device=0):
+                           seed=0, call=0, want_s=True, want_t=True, out=None, out_s=None, out_t=None, device=0,
+                           chunked=False):
     """Gradients of gat_attention (glx_gat_attention_backward) -> (grad_e[n, heads], grad_s[S, heads] or None,
     grad_t[M, heads] or None) from the forward's `soft`, the gradient of its `alpha` and the forward's own arguments
     (the dropout mask is recomputed from seed and call).  grad_e is the gradient of the logits before leaky_relu;
     grad_s sums it per segment (a fixed tree), grad_t per row of t in ascending position (the bits of
     aggregate_backward(SUM, rows, None, grad_e, M)).  Every element is written; no atomics: the same bits on every
-    call.  want_s / want_t = False skips that gradient."""
+    call.  want_s / want_t = False skips that gradient.
+    chunked=True (glx_gat_attention_backward_chunked) sums grad_t in the CHUNKED order: a row of t named more than 256
+    times is cut into chunks of 256 entries, each summed from +0.0 in ascending position by a lane of its own, and the
+    row is +0.0 plus the partial sums in ascending chunk (the bits of aggregate_backward(SUM, rows, None, grad_e, M,
+    chunked=True)).  grad_e and grad_s, and every row named at most 256 times, keep the default bits."""
     n, num_segments, num_rows, heads = _gat_shapes(s, t, rows)
     grad_e = _weighted_out(out, soft, (n, heads))
     grad_s = _weighted_out(out_s, soft, (num_segments, heads)) if (want_s or out_s is not None) else None
@@ -1317,9 +1325,9 @@ def gat_attention_backward(soft, grad_alpha, s, t, rows, cnt=None, negative_slop
     kind = _kind(pso, pg, ps, pt, pr, pc, pe, pgs, pgt)
     if kind == PTR_DEVICE:
         device = grad_e.device.index or 0
-    _check(lib().glx_gat_attention_backward(device, pso[0], pg[0], ps[0], pt[0], num_rows, pr[0], heads, pc[0], n,
-                                            num_segments, negative_slope, default_attr, drop_p, seed, call, pe[0],
-                                            pgs[0], pgt[0], kind, _stream(kind, device)))
+    entry = lib().glx_gat_attention_backward_chunked if chunked else lib().glx_gat_attention_backward
+    _check(entry(device, pso[0], pg[0], ps[0], pt[0], num_rows, pr[0], heads, pc[0], n, num_segments, negative_slope,
+                 default_attr, drop_p, seed, call, pe[0], pgs[0], pgt[0], kind, _stream(kind, device)))
     return grad_e, grad_s, grad_t
 
 
@@ -1449,14 +1457,20 @@ def pair_dot(xa, ia, xb, ib, heads=1, repeat=1, default_attr=0.0, out=None, devi
     return res
 
 
-def pair_dot_backward(side, ia, ib, g, x_other, num_rows_self, repeat=1, default_attr=0.0, out=None, device=0):
+def pair_dot_backward(side, ia, ib, g, x_other, num_rows_self, repeat=1, default_attr=0.0, out=None, device=0,
+                      chunked=False):
     """Gradient of pair_dot with respect to xa (side 0) or xb (side 1) (glx_pair_dot_backward) ->
     grad_self[num_rows_self, D] float32, every row written.  g[n, heads] (or g[n]) is the gradient of pair_dot's output,
     x_other the other side's table.  Each element adds fmul(g[p, head], other_row(p)) over the pairs that refer to its
     row in ascending p, no float atomic: the same bits on every run.  An own index outside the table gets nothing, an
     other-side index outside its table multiplies a row of default_attr.
     grad_self takes x_other's dtype: for a bfloat16 x_other it is the float32 gradient (summed in float32 over the exactly
-    upcast rows) rounded once per element, to nearest even; an out= of another dtype raises ValueError."""
+    upcast rows) rounded once per element, to nearest even; an out= of another dtype raises ValueError.
+    chunked=True (glx_pair_dot_backward_chunked) sums the same terms in the CHUNKED order: a row's run of pairs (its
+    entries in ascending order, each expanded to `repeat` pairs on side 0) of more than 256 pairs is cut into chunks of
+    256 pairs, each summed from +0.0 in ascending pair by its own lane group, and the row is +0.0 plus the partial sums
+    in ascending chunk.  A run of at most 256 pairs gets the default bits; still no atomics, the same bits on every
+    call, a bfloat16 grad_self still rounded once.  For batches whose negatives keep naming a few popular rows."""
     n, repeat = _pair_counts(ia, ib, repeat)
     heads = _weighted_heads(g, n)
     num_rows_other, dim = int(x_other.shape[0]), int(x_other.shape[1])
@@ -1469,9 +1483,9 @@ def pair_dot_backward(side, ia, ib, g, x_other, num_rows_self, repeat=1, default
     kind = _kind(pia, pib, pg, px, po)
     if kind == PTR_DEVICE:
         device = grad.device.index or 0
-    _check(lib().glx_pair_dot_backward_ex(device, side, pia[0], pib[0], n, repeat, pg[0], heads, px[0], num_rows_other,
-                                          dim, num_rows_self, default_attr, po[0], TRAIN_DTYPES[x_dtype], kind,
-                                          _stream(kind, device)))
+    entry = lib().glx_pair_dot_backward_chunked if chunked else lib().glx_pair_dot_backward_ex
+    _check(entry(device, side, pia[0], pib[0], n, repeat, pg[0], heads, px[0], num_rows_other, dim, num_rows_self,
+                 default_attr, po[0], TRAIN_DTYPES[x_dtype], kind, _stream(kind, device)))
     return grad
 
 

@@ -31,6 +31,10 @@ class GATConv(torch.nn.Module):
                     [N, H * out_dim] output unless H == 1.)
   add_self_loops    every seed also attends to itself (gat_conv.py:85-87): its own row is inserted as one more
                     position of its segment, behind its neighbours
+  chunked_grad      passed to gat_attention and to weighted_segment_aggregate: True sums the gradients of the rows a
+                    batch names more than 256 times -- the hub neighbours -- chunk by chunk, 256 positions from +0.0
+                    each, the partial sums in chunk order (segment.py).  The output does not depend on it, and a batch
+                    without such rows gets the default's gradients bit for bit.
 
   Everything runs on one GPU; the segments are described by counts (or the implied layout), not by explicit segment
   ids.  In float32 every op is float32.  Under torch.autocast("cuda", dtype=torch.bfloat16) the projection z = W x is
@@ -41,7 +45,7 @@ class GATConv(torch.nn.Module):
   """
 
   def __init__(self, in_dim, out_dim, num_heads=1, concat=False, dropout=0.0, use_bias=False, negative_slope=0.2,
-               add_self_loops=True, seed=None):
+               add_self_loops=True, seed=None, chunked_grad=False):
     super().__init__()
     in_dim, out_dim, num_heads = int(in_dim), int(out_dim), int(num_heads)
     if in_dim < 1 or out_dim < 1 or num_heads < 1:
@@ -51,6 +55,7 @@ class GATConv(torch.nn.Module):
     self.in_dim, self.out_dim, self.num_heads = in_dim, out_dim, num_heads
     self.concat, self.dropout, self.negative_slope = bool(concat), float(dropout), float(negative_slope)
     self.add_self_loops = bool(add_self_loops)
+    self.chunked_grad = bool(chunked_grad)
     self.seed = None if seed is None else int(seed)
     self.calls = 0  # training forwards so far: the `call` of the next dropout mask
     self.linear = torch.nn.Linear(in_dim, num_heads * out_dim, bias=False)
@@ -101,8 +106,9 @@ class GATConv(torch.nn.Module):
       call = self.calls
       self.calls += 1
     alpha = gat_attention(s, dst_e, index, S, counts=counts, negative_slope=self.negative_slope, dropout=drop,
-                          seed=seed, call=call)
-    out = weighted_segment_aggregate(z, index, alpha, S, counts=counts)        # [S, H * C]
+                          seed=seed, call=call, chunked_grad=self.chunked_grad)
+    out = weighted_segment_aggregate(z, index, alpha, S, counts=counts,        # [S, H * C]
+                                     chunked_grad=self.chunked_grad)
     if not self.concat:
       out = out.view(S, H, C).mean(1)
     if self.bias is not None:

@@ -63,7 +63,10 @@ deterministic as the default, the default's bits for every row named at most 256
 outputs do not depend on the flag.  dot_attention takes chunked=True, which covers BOTH directions: a hub SEGMENT (more
 than 256 positions) has its softmax computed by one workgroup and its out / grad_q summed chunk by chunk, and k.grad /
 v.grad are summed in the chunked order above (glx_dot_attention_chunked, glx_dot_attention_backward_chunked).  pair_dot
-and gat_attention have no such flag: pair_dot's gradients and gat_attention's gradient of t stay unsplit.
+and gat_attention take chunked_grad=True as well (glx_pair_dot_backward_chunked, glx_gat_attention_backward_chunked):
+pair_dot sums both tables' gradients over chunks of 256 PAIRS of a row's run -- the popular item that in-degree
+negatives keep drawing, or one source scored against more than 256 candidates -- and gat_attention sums t.grad over
+chunks of 256 positions; GATConv(chunked_grad=True) passes the flag to both of its ops.
 
 bfloat16.  Under torch.autocast("cuda", dtype=torch.bfloat16) `z = relu(enc(x))` is bfloat16, and segment_aggregate,
 gather_rows, weighted_segment_aggregate and pair_dot take it as it is -- inside autocast or outside, they go by the
@@ -376,11 +379,12 @@ def segment_softmax(e, num_segments, counts=None):
 class _GatAttention(torch.autograd.Function):
 
   @staticmethod
-  def forward(ctx, s, t, index, counts, slope, drop_p, seed, call, default_attr):
+  def forward(ctx, s, t, index, counts, slope, drop_p, seed, call, default_attr, chunked_grad):
     sd, td = s.detach(), t.detach()
     alpha, soft = _glx().gat_attention(sd, td, index, cnt=counts, negative_slope=slope, default_attr=default_attr,
                                        drop_p=drop_p, seed=seed, call=call, want_soft=drop_p != 0.0)
     ctx.cfg = (slope, default_attr, drop_p, seed, call)
+    ctx.chunked = chunked_grad  # selects t.grad's entry point only
     ctx.has_counts = counts is not None
     ctx.save_for_backward(*([alpha if soft is None else soft, sd, td, index] + ([counts] if counts is not None else [])))
     return alpha
@@ -390,7 +394,7 @@ class _GatAttention(torch.autograd.Function):
     _no_double_backward("gat_attention")
     want_s, want_t = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
     if not (want_s or want_t):
-      return (None,) * 9
+      return (None,) * 10
     saved = ctx.saved_tensors
     soft, s, t, index = saved[:4]
     counts = saved[4] if ctx.has_counts else None
@@ -398,12 +402,12 @@ class _GatAttention(torch.autograd.Function):
     grad = grad.to(torch.float32).contiguous()
     _, gs, gt = _glx().gat_attention_backward(soft, grad, s, t, index, cnt=counts, negative_slope=slope,
                                               default_attr=default_attr, drop_p=drop_p, seed=seed, call=call,
-                                              want_s=want_s, want_t=want_t)
-    return (gs, gt) + (None,) * 7
+                                              want_s=want_s, want_t=want_t, chunked=ctx.chunked)
+    return (gs, gt) + (None,) * 8
 
 
 def gat_attention(s, t, index, num_segments, counts=None, negative_slope=0.2, dropout=0.0, seed=0, call=0,
-                  default_attr=0.0):
+                  default_attr=0.0, chunked_grad=False):
   """[n, H] attention coefficients of a GAT layer: for position p of segment sg and head h the logit
   leaky_relu(s[sg, h] + t[index[p], h], negative_slope), its softmax over the segment's positions (segment_softmax's
   definition and exact rules) and dropout on the result -- one kernel going forward, one going back, no atomics,
@@ -420,6 +424,9 @@ def gat_attention(s, t, index, num_segments, counts=None, negative_slope=0.2, dr
   dropout  p in [0, 1): element (p, h) is kept, and scaled by 1 / (1 - p), iff word (p H + h) % 4 of Philox4x32-10
            block (p H + h) // 4 under (seed, call) is >= floor(p 2^32) -- the engine's contract generator; the
            backward recomputes the mask.  Use a new `call` for every step.
+  chunked_grad  True: t.grad is summed in segment_aggregate's chunked order (glx_gat_attention_backward_chunked) -- a
+           row of t named more than 256 times: partial sums of 256 positions each, added in chunk order; the result and
+           s.grad do not depend on it
   Only the gradients that are needed are computed.  Anything else raises ValueError.
   """
   who = "gat_attention"
@@ -461,7 +468,7 @@ def gat_attention(s, t, index, num_segments, counts=None, negative_slope=0.2, dr
   if not (0 <= seed < 2 ** 64 and 0 <= call < 2 ** 64):
     raise ValueError("{}: seed and call must fit 64 unsigned bits".format(who))
   return _GatAttention.apply(s.reshape(num_segments, heads), t.reshape(int(t.shape[0]), heads), index, counts,
-                             negative_slope, dropout, seed, call, float(default_attr))
+                             negative_slope, dropout, seed, call, float(default_attr), bool(chunked_grad))
 
 
 class _DotAttention(torch.autograd.Function):
@@ -578,10 +585,11 @@ def dot_attention(q, k, v, index, num_segments, counts=None, edge=None, heads=1,
 class _PairDot(torch.autograd.Function):
 
   @staticmethod
-  def forward(ctx, xa, ia, xb, ib, heads, repeat, default_attr):
+  def forward(ctx, xa, ia, xb, ib, heads, repeat, default_attr, chunked_grad):
     xad, xbd = xa.detach(), xb.detach()
     out = _glx().pair_dot(xad, ia, xbd, ib, heads=heads, repeat=repeat, default_attr=default_attr)
     ctx.repeat, ctx.default_attr = repeat, default_attr
+    ctx.chunked = chunked_grad  # selects the backward entry point only
     ctx.save_for_backward(xad, ia, xbd, ib)
     return out
 
@@ -593,13 +601,15 @@ class _PairDot(torch.autograd.Function):
     grad = grad.to(torch.float32).contiguous()
     ga = gb = None
     if ctx.needs_input_grad[0]:
-      ga = glx.pair_dot_backward(0, ia, ib, grad, xb, int(xa.shape[0]), repeat=ctx.repeat, default_attr=ctx.default_attr)
+      ga = glx.pair_dot_backward(0, ia, ib, grad, xb, int(xa.shape[0]), repeat=ctx.repeat, default_attr=ctx.default_attr,
+                                 chunked=ctx.chunked)
     if ctx.needs_input_grad[2]:
-      gb = glx.pair_dot_backward(1, ia, ib, grad, xa, int(xb.shape[0]), repeat=ctx.repeat, default_attr=ctx.default_attr)
-    return ga, None, gb, None, None, None, None
+      gb = glx.pair_dot_backward(1, ia, ib, grad, xa, int(xb.shape[0]), repeat=ctx.repeat, default_attr=ctx.default_attr,
+                                 chunked=ctx.chunked)
+    return ga, None, gb, None, None, None, None, None
 
 
-def pair_dot(xa, ia, xb, ib, heads=None, default_attr=0.0):
+def pair_dot(xa, ia, xb, ib, heads=None, default_attr=0.0, chunked_grad=False):
   """The score of every pair (ia, ib): the dot product of row ia of xa with row ib of xb, per head -- a fixed summation
   tree going forward, fadd(acc, fmul(g, row)) in ascending pair order going back, no atomics: bit-identical on every
   run.  Neither [n, D] gather is materialised.
@@ -613,6 +623,10 @@ def pair_dot(xa, ia, xb, ib, heads=None, default_attr=0.0):
   ia       int64 CUDA tensor (flattened) whose numel divides n: rows of xa; pair p takes ia[p // (n / ia.numel())] -- ia
            [B] with ib [B, K] scores each source against its K candidates; ia shaped like ib scores edges one to one
   heads    None: a tensor of ib's shape; H (dividing D): ib.shape + (H,), column c belongs to head c // (D // H)
+  chunked_grad  True: both gradients are summed in the CHUNKED order (glx_pair_dot_backward_chunked) -- a row's run of
+           pairs (side xa: its entries of ia, each expanded to its n / ia.numel() candidates) of more than 256 pairs is
+           cut into chunks of 256, each summed from +0.0 in ascending pair, the partial sums added in chunk order; a
+           shorter run gets the default's bits, and the scores do not depend on it
   An index outside its table reads a row of `default_attr` and receives no gradient.  Only the gradients that are
   needed are computed.  Anything else raises ValueError.
   """
@@ -637,5 +651,5 @@ def pair_dot(xa, ia, xb, ib, heads=None, default_attr=0.0):
   if n * H > 2 ** 31 - 1:
     raise ValueError("{}: n * H exceeds int32".format(who))
   repeat = n // m if n else 1
-  out = _PairDot.apply(xa, ia, xb, ib, H, repeat, float(default_attr))
+  out = _PairDot.apply(xa, ia, xb, ib, H, repeat, float(default_attr), bool(chunked_grad))
   return out.reshape(shape if heads is None else shape + (H,))

@@ -51,7 +51,8 @@ extern "C" {
  * the bfloat16 training path -- glx_aggregate_backward_ex, glx_aggregate_weighted_ex,
  * glx_aggregate_weighted_backward_x_ex, glx_aggregate_weighted_backward_w_ex, glx_pair_dot_ex,
  * glx_pair_dot_backward_ex; chunked row gradients -- glx_aggregate_backward_chunked,
- * glx_aggregate_weighted_backward_x_chunked; the half-precision KNN scan -- GLX_KNN_PREC_*, glx_knn_search_ex;
+ * glx_aggregate_weighted_backward_x_chunked, glx_pair_dot_backward_chunked, glx_gat_attention_backward_chunked; the
+ * half-precision KNN scan -- GLX_KNN_PREC_*, glx_knn_search_ex;
  * the narrow KNN tile -- GLX_KNN_TILE_*, glx_knn_search_tiled. */
 #define GLX_ABI_VERSION 5
 
@@ -1135,10 +1136,10 @@ GLX_API int glx_embedding_update(int device, int algo, float* W, float* state1, 
  * number of long rows and of chunks never reaches the host: no read-back, no synchronisation.  A list of L >
  * GLX_COALESCE_CHUNK entries has fewer than L / 128 chunks, so the partial sums take at most (num_ids / 128 + 1) * dim
  * floats of the calling thread's workspace, beside the transpose.)
- * Still summed by one lane group per list, in ascending position: glx_pair_dot_backward and grad_t of
- * glx_gat_attention_backward (dot-product attention has a chunked order of its own, for its long segments and for
- * grad_k / grad_v: glx_dot_attention_chunked, glx_dot_attention_backward_chunked); Prod has no backward; the
- * distributed store has none either; request plans (graph capture) do not cover the backward. */
+ * Pair scores and GAT attention's grad_t have the same order under their own entry points, below; dot-product attention
+ * has a chunked order of its own, for its long segments and for grad_k / grad_v (glx_dot_attention_chunked,
+ * glx_dot_attention_backward_chunked).  Prod has no backward; the distributed store has none either; request plans
+ * (graph capture) do not cover the backward. */
 GLX_API int glx_aggregate_backward_chunked(int device, int op, const int64_t* rows, const int32_t* cnt,
                                            const int32_t* arg, int32_t num_ids, int32_t num_segments, int64_t num_rows,
                                            int32_t dim, const float* grad_out, void* grad_x, int grad_x_dtype,
@@ -1148,6 +1149,39 @@ GLX_API int glx_aggregate_weighted_backward_x_chunked(int device, int op, const 
                                                       int32_t num_segments, int64_t num_rows, int32_t dim,
                                                       const float* grad_out, void* grad_x, int grad_x_dtype,
                                                       int ptr_kind, void* stream);
+/* glx_pair_dot_backward_chunked (K5-dot-chunked) takes glx_pair_dot_backward_ex's arguments, with the same checks in
+ * the same order (x_dtype first), host and device pointers.  The terms are the default's: fmul_rn(g[p, head(c)],
+ * other_row(p)[c]); an other index outside its table reads default_attr, an own index outside its table receives
+ * nothing.  A table row's RUN is its own-side entries in ascending entry, each expanded to own_rep consecutive pairs
+ * (side 0: own_rep = repeat; side 1: own_rep = 1): L = entries * own_rep pairs in ascending p, the run the default
+ * walks.  A run with L > GLX_COALESCE_CHUNK is long: chunk j is pairs [256 j, min(256 j + 256, L)) of the RUN, so with
+ * repeat > 1 a chunk boundary may fall inside one entry's expansion, and one entry with repeat > 256 is a long run.
+ *     partial_j[c]    = +0.0f, then one fadd_rn per term of chunk j, in ascending pair
+ *     grad_self[r, c] = +0.0f, then one fadd_rn per partial, in ascending j
+ * Every other row keeps the default order's bits; every row is written exactly once, a row nobody names is all bits
+ * clear; no float atomics; the same bits on every call; a bfloat16 grad_self is the float32 sum rounded once, in the
+ * combine.  (The own side's transpose; a chunk directory over the runs, in pair units, built on the device and never
+ * read back; one lane group per short run, one per chunk -- the default kernel's walk, the other side's rows gathered
+ * -- one per long run to combine.  At most (num_pairs / 128 + 1) * dim floats of partial sums.)
+ *
+ * glx_gat_attention_backward_chunked (K5-gat-chunked) takes glx_gat_attention_backward's arguments.  grad_e and grad_s
+ * come from the same kernel and have the default's bits.  grad_t is summed in the chunked order: a row named more than
+ * GLX_COALESCE_CHUNK times by the consumed positions is cut into chunks of that many entries, partial[t, h] = +0.0f plus
+ * grad_e[p, h] in ascending p, grad_t[r, h] = +0.0f plus the row's partials in ascending chunk; a row named at most 256
+ * times keeps the default's bits; every row is written.  By construction the bits of
+ * glx_aggregate_backward_chunked(Sum) of grad_e with one position per segment and dim = heads.  (One lane per (chunk,
+ * head); at most (num_ids / 128 + 1) * heads floats of partial sums.) */
+GLX_API int glx_pair_dot_backward_chunked(int device, int side, const int64_t* ia, const int64_t* ib,
+                                          int32_t num_pairs, int32_t repeat, const float* g, int32_t heads,
+                                          const void* x_other, int64_t num_rows_other, int32_t dim,
+                                          int64_t num_rows_self, float default_attr, void* grad_self, int x_dtype,
+                                          int ptr_kind, void* stream);
+GLX_API int glx_gat_attention_backward_chunked(int device, const float* soft, const float* grad_alpha, const float* s,
+                                               const float* t, int64_t num_rows, const int64_t* rows, int32_t heads,
+                                               const int32_t* cnt, int32_t num_ids, int32_t num_segments,
+                                               float negative_slope, float default_attr, float drop_p, uint64_t seed,
+                                               uint64_t call, float* grad_e_out, float* grad_s_out, float* grad_t_out,
+                                               int ptr_kind, void* stream);
 
 /* ---- TGN memory: the device-resident message store, the fused message and the memory write of the memory module the
  * reference's TGN example takes from torch_geometric -- TGNMemory(num_nodes, msg_dim, memory_dim, time_dim,
