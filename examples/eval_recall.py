@@ -29,7 +29,9 @@ against the float32 table's answer -- what the rounding of the stored rows costs
 --precision half (with --dtype bfloat16 | float16 | float8_e4m3fn | float8_e5m2) adds one more line per search: the
 half-precision scan of the narrow table on the 16-bit matrix cores (glx.Features.search(..., precision="half"); a float8
 table is scanned as bfloat16), its metrics and its recall@k against the exact search of the same table.  --refine R
-re-scores its R best with the exact chain first (default: no re-rank).
+re-scores its R best with the exact chain first (default: no re-rank).  Together with --index ivf it also builds an
+IVF-Flat index over the narrow table and adds the half-precision list-major scan of the probed lists
+(glx.KnnIvf.search(..., schedule="list", precision="half")), which with every list probed must equal the flat half scan.
 
 --tile narrow runs every flat search above through the 32-query tiles (glx.Features.search(..., tile="narrow")): the
 same bits, a shorter time for a handful of users per call.
@@ -110,6 +112,8 @@ def main():
     narrow = glx.Features(items, ids=item_ids, dtype=a.dtype) if a.dtype != "float32" else None
     index = table.build_ivf(a.nlist) if a.index in ("ivf", "ivfpq") else None
     coded = index.build_pq(a.m) if a.index == "ivfpq" else None
+    # --precision half with --index ivf: the half-precision list-major scan over an index of the narrow table
+    half_index = narrow.build_ivf(a.nlist) if a.precision == "half" and a.index == "ivf" else None
     d_ids = torch.from_numpy(item_ids).cuda()
     group_rows = torch.arange(items.shape[0], device="cuda").view(-1, a.group)
     ok = True
@@ -158,6 +162,20 @@ def main():
                   "two runs same bits: %s  every list probed == exact search: %s"
                   % (task, metric, a.nlist, a.nprobe, a.k, r, a.k, n, h, vs_flat, same_bits, all_lists))
             ok = ok and same_bits and all_lists
+            if half_index is not None:
+                kw = dict(schedule="list", precision="half", refine=half_refine)
+                got, gdist = half_index.search(dq, a.k, metric, nprobe=a.nprobe, **kw)
+                got2, gdist2 = half_index.search(dq, a.k, metric, nprobe=a.nprobe, **kw)
+                same_bits = bool(torch.equal(got, got2) and torch.equal(gdist.view(torch.int32), gdist2.view(torch.int32)))
+                full, fdist = half_index.search(dq, a.k, metric, nprobe=a.nlist, **kw)
+                all_lists = bool(torch.equal(full, hids) and torch.equal(fdist.view(torch.int32), hdist.view(torch.int32)))
+                r, n, h = metrics(got, truth, a.k)
+                vs_flat = (got[:, :, None] == ids[:, None, :]).any(1).float().mean().item()
+                print("%s %s  ivf half scan of the %s table, nlist %d nprobe %d refine %d  recall@%d %.4f  ndcg@%d %.4f  "
+                      "hit rate %.4f  recall vs exact %.4f  two runs same bits: %s  every list probed == flat half scan: %s"
+                      % (task, metric, a.dtype, a.nlist, a.nprobe, half_refine, a.k, r, a.k, n, h, vs_flat, same_bits,
+                         all_lists))
+                ok = ok and same_bits and all_lists
             if coded is None:
                 continue
             pids, pdist = coded.search(dq, a.k, metric, nprobe=a.nprobe, refine=a.refine)

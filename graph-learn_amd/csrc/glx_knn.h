@@ -443,6 +443,12 @@ int knn_refine(const KnnArgs& a, const uint64_t* cand, int32_t RP, int32_t R, hi
 // the half-precision scan (GLX_KNN_PREC_HALF of glx_knn_search_ex) on device pointers (workspace slot 1)
 int knn_search_half_device(const glx_features* f, int metric, const float* d_q, int32_t num_queries, int32_t k,
                            int32_t refine, int64_t* d_ids, float* d_dist, hipStream_t s, int tile = GLX_KNN_TILE_WIDE);
+// knn_round_queries_kernel: out[q, c] = d_q[q, c] rounded to `scan` (GLX_DTYPE_BF16 or _F16) for c < dim, zero for
+// dim <= c < ld -- q^ of the half-precision scans
+void knn_round_queries(const float* d_q, int64_t num_queries, int32_t dim, int32_t ld, int scan, uint16_t* out,
+                       hipStream_t s);
+// knn_half_finish_kernel: a.run[a.nq, a.KP] -> (node id of f, the half scan's dist)[a.nq, a.k]
+void knn_half_finish(const KnnArgs& a, const glx_features* f, int64_t* d_ids, float* d_dist, hipStream_t s);
 
 // glx_knn_narrow.hip
 constexpr int kNarrowBQ = 32;   // queries per workgroup tile of a narrow score kernel
@@ -539,6 +545,9 @@ int knn_ivf_passes(const glx_knn_ivf* ix, int metric, const float* d_q, int32_t 
 // query-major knn_ivf_search_device
 int knn_ivf_search_list_device(const glx_knn_ivf* ix, int metric, const float* d_q, int32_t num_queries, int32_t k,
                                int32_t nprobe, int64_t* d_ids, float* d_dist, hipStream_t s);
+// knn_list_start_kernel and knn_list_tiles_kernel over sorted pair keys in [0, nkeys]: start[l] = the first pair whose
+// key is >= l, tile_off[l] = the first 128-query tile of key l, l <= nkeys (glx_knn_ivf_half.hip sorts by group and list)
+void knn_list_starts(const uint32_t* key, int32_t pairs, int32_t nkeys, int32_t* start, int32_t* tile_off, hipStream_t s);
 
 // ---- entry points -------------------------------------------------------------------------------------------------
 #define GLX_KNN_REQUIRE()                                                                                      \

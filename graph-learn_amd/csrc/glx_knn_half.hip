@@ -191,6 +191,22 @@ static void knn_score_half(const KnnArgs& a, const uint16_t* qh, int32_t qld, in
   }
 }
 
+void knn_round_queries(const float* d_q, int64_t num_queries, int32_t dim, int32_t ld, int scan, uint16_t* out,
+                       hipStream_t s) {
+  const unsigned grid = (unsigned)((num_queries * ld + 255) / 256);
+  if (scan == GLX_DTYPE_BF16) {
+    knn_round_queries_kernel<GLX_DTYPE_BF16><<<grid, 256, 0, s>>>(d_q, num_queries, dim, ld, out);
+  } else {
+    knn_round_queries_kernel<GLX_DTYPE_F16><<<grid, 256, 0, s>>>(d_q, num_queries, dim, ld, out);
+  }
+}
+
+void knn_half_finish(const KnnArgs& a, const glx_features* f, int64_t* d_ids, float* d_dist, hipStream_t s) {
+  const bool arith = f->idmap.keys == nullptr && f->idmap.step > 0;
+  knn_half_finish_kernel<<<(unsigned)(((int64_t)a.nq * a.k + 255) / 256), 256, 0, s>>>(
+      a, f->knn_row_ids, arith ? f->idmap.base : 0, arith ? f->idmap.step : 0, d_ids, d_dist);
+}
+
 int knn_search_half_device(const glx_features* f, int metric, const float* d_q, int32_t num_queries, int32_t k,
                            int32_t refine, int64_t* d_ids, float* d_dist, hipStream_t s, int tile) {
   const bool narrow = tile == GLX_KNN_TILE_NARROW;
@@ -228,18 +244,12 @@ int knn_search_half_device(const glx_features* f, int metric, const float* d_q, 
   int rc = ws.alloc(layout(KnnCarve{nullptr}), s, 1);
   if (rc != GLX_OK) return rc;
   layout(KnnCarve{ws.as<char>()});
-  const unsigned round_grid = (unsigned)(((int64_t)num_queries * qld + 255) / 256);
   const int scan = a.t.dtype == GLX_DTYPE_F16 ? GLX_DTYPE_F16 : GLX_DTYPE_BF16;  // a float8 table scans as bfloat16
-  if (scan == GLX_DTYPE_BF16) {
-    knn_round_queries_kernel<GLX_DTYPE_BF16><<<round_grid, 256, 0, s>>>(d_q, num_queries, a.t.dim, qld, qh);
-  } else {
-    knn_round_queries_kernel<GLX_DTYPE_F16><<<round_grid, 256, 0, s>>>(d_q, num_queries, a.t.dim, qld, qh);
-  }
+  knn_round_queries(d_q, num_queries, a.t.dim, qld, scan, qh, s);
   rc = knn_prepare_norms(f, l2, qh, num_queries, qn_half, xn_ws, s, &a.xn, scan, qld);
   if (rc != GLX_OK) return rc;
   x.xn = a.xn;
   if (qn_exact) knn_norms(KnnTable{d_q, a.t.dim, 0, num_queries, a.t.dim, GLX_DTYPE_F32}, qn_exact, s);
-  const bool arith = f->idmap.keys == nullptr && f->idmap.step > 0;
   int refine_rc = GLX_OK;
   rc = knn_chunk_passes(
       a, plan, d_q, qn_half, num_queries, s,
@@ -250,8 +260,7 @@ int knn_search_half_device(const glx_features* f, int metric, const float* d_q, 
       },
       [&](int64_t q0) {
         if (refine == 0) {
-          knn_half_finish_kernel<<<(unsigned)(((int64_t)a.nq * k + 255) / 256), 256, 0, s>>>(
-              a, f->knn_row_ids, arith ? f->idmap.base : 0, arith ? f->idmap.step : 0, d_ids + q0 * k, d_dist + q0 * k);
+          knn_half_finish(a, f, d_ids + q0 * k, d_dist + q0 * k, s);
           return;
         }
         x.nq = a.nq;

@@ -315,6 +315,11 @@ __global__ __launch_bounds__(kSelThreads) void knn_list_select_kernel(uint64_t* 
 
 }  // namespace
 
+void knn_list_starts(const uint32_t* key, int32_t pairs, int32_t nkeys, int32_t* start, int32_t* tile_off, hipStream_t s) {
+  knn_list_start_kernel<<<(unsigned)((nkeys + 1 + 255) / 256), 256, 0, s>>>(key, pairs, nkeys, start);
+  knn_list_tiles_kernel<<<1, 1024, 0, s>>>(start, nkeys, tile_off);
+}
+
 int knn_ivf_search_list_device(const glx_knn_ivf* ix, int metric, const float* d_q, int32_t num_queries, int32_t k,
                                int32_t nprobe, int64_t* d_ids, float* d_dist, hipStream_t s) {
   const glx_features* const f = ix->f;
@@ -418,8 +423,7 @@ int knn_ivf_search_list_device(const glx_knn_ivf* ix, int metric, const float* d
         return rocprim::radix_sort_pairs(tmp, bytes, key_in, key_out, val_in, val_out, (size_t)pairs, 0, sort_bits, s);
       });
       if (rc != GLX_OK) return rc;
-      knn_list_start_kernel<<<(unsigned)((ix->nlist + 1 + 255) / 256), 256, 0, s>>>(key_out, pairs, ix->nlist, start);
-      knn_list_tiles_kernel<<<1, 1024, 0, s>>>(start, ix->nlist, tile_off);
+      knn_list_starts(key_out, pairs, ix->nlist, start, tile_off, s);
       // sum of ceil(c_l / 128) over the lists with pairs <= pairs / 128 + the lists with pairs; surplus workgroups exit
       const int64_t grid = pairs / kListBQ + (ix->nlist < pairs ? ix->nlist : pairs);
       GLX_KNN_LAUNCH_DT(&rc, a.t.dtype, knn_list_score_kernel, (unsigned)grid, 256, s, la);

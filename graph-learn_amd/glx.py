@@ -48,7 +48,7 @@ EXPORTS = [
     "glx_features_create", "glx_features_view", "glx_features_destroy", "glx_features_info",
     "glx_features_create_ex", "glx_features_view_ex", "glx_features_dtype", "glx_features_convert_host",
     "glx_knn_search", "glx_knn_search_ex", "glx_knn_search_tiled", "glx_knn_merge",
-    "glx_knn_ivf_build", "glx_knn_ivf_search", "glx_knn_ivf_search_ex", "glx_knn_ivf_info", "glx_knn_ivf_export", "glx_knn_ivf_destroy",
+    "glx_knn_ivf_build", "glx_knn_ivf_search", "glx_knn_ivf_search_ex", "glx_knn_ivf_search_prec", "glx_knn_ivf_info", "glx_knn_ivf_export", "glx_knn_ivf_destroy",
     "glx_knn_ivfpq_build", "glx_knn_ivfpq_search", "glx_knn_ivfpq_info", "glx_knn_ivfpq_export",
     "glx_knn_ivfpq_destroy",
     "glx_aggregate", "glx_lookup", "glx_aggregate_arg", "glx_aggregate_backward",
@@ -310,6 +310,7 @@ def lib():
         L.glx_knn_ivf_build.argtypes = [vp, i32, i32, i64, vp, ci, vp, ctypes.POINTER(vp)]
         L.glx_knn_ivf_search.argtypes = [vp, ci, vp, i32, i32, i32, vp, vp, ci, vp]
         L.glx_knn_ivf_search_ex.argtypes = [vp, ci, vp, i32, i32, i32, ci, vp, vp, ci, vp]
+        L.glx_knn_ivf_search_prec.argtypes = [vp, ci, vp, i32, i32, i32, ci, ci, i32, vp, vp, ci, vp]
         L.glx_knn_ivf_info.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i64),
                                        ctypes.POINTER(i64), ctypes.POINTER(i64)]
         L.glx_knn_ivf_export.argtypes = [vp, vp, vp, vp, ci, vp]
@@ -937,18 +938,27 @@ class KnnIvf(_KnnIndex):
         _check(lib().glx_knn_ivf_export(self._h, None, _ptr(ptr)[0], _ptr(rows)[0], PTR_HOST, None))
         return ptr, rows
 
-    def search(self, queries, k, metric="ip", nprobe=1, out=None, schedule="query"):
+    def search(self, queries, k, metric="ip", nprobe=1, out=None, schedule="query", precision="float32", refine=0):
         """The k best rows of every query among the rows of its nprobe best lists (glx_knn_ivf_search_ex) ->
         (ids[n, k] int64, dist[n, k] float32), best first, under Features.search's contract: the same chain, order, ids
         and padding (slots beyond the probed lists' rows hold id -1).  nprobe == nlist probes every list and equals
         Features.search bit for bit; otherwise 1 <= nprobe <= min(nlist, 1024).  Numpy in, numpy out; torch CUDA tensors
         in, torch CUDA tensors out on the current stream, nothing read back.  out=(ids, dist): buffers to write into.
         schedule: "query" (one workgroup per query and probed list) or "list" (opt-in: a list is scored once against
-        all the queries that probe it, on the matrix cores); both return the same bits."""
+        all the queries that probe it, on the matrix cores); both return the same bits.
+        precision="half" (glx_knn_ivf_search_prec; schedule="list" and a bfloat16, float16 or float8 table only) scores
+        the probed lists on the 16-bit matrix cores under Features.search(precision="half")'s contract: the same rounded
+        queries, the same score bits, refine as there.  The probe sets stay the float32 coarse step's; nprobe == nlist
+        equals Features.search(precision="half", refine=refine) bit for bit.  No automatic choice is made."""
         if schedule not in KNN_IVF_SCHEDULES:
             raise ValueError("schedule must be one of {}, not {!r}".format(sorted(KNN_IVF_SCHEDULES), schedule))
-        return _knn_search(lib().glx_knn_ivf_search_ex, lambda: self._h, self.dim, self.device, queries, k, metric, out,
-                           int(nprobe), KNN_IVF_SCHEDULES[schedule])
+        if precision not in KNN_PRECISIONS:
+            raise ValueError("precision must be one of {}, not {!r}".format(sorted(KNN_PRECISIONS), precision))
+        if precision == "float32" and refine == 0:
+            return _knn_search(lib().glx_knn_ivf_search_ex, lambda: self._h, self.dim, self.device, queries, k, metric,
+                               out, int(nprobe), KNN_IVF_SCHEDULES[schedule])
+        return _knn_search(lib().glx_knn_ivf_search_prec, lambda: self._h, self.dim, self.device, queries, k, metric, out,
+                           int(nprobe), KNN_IVF_SCHEDULES[schedule], KNN_PRECISIONS[precision], int(refine))
 
     def build_pq(self, m, niter=10, train_rows=None, codebooks=None):
         """An IVF-PQ index on top of this index (glx_knn_ivfpq_build) -> KnnIvfPq: m sub-quantisers of 256 codewords

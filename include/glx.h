@@ -53,7 +53,8 @@ extern "C" {
  * glx_pair_dot_backward_ex; chunked row gradients -- glx_aggregate_backward_chunked,
  * glx_aggregate_weighted_backward_x_chunked, glx_pair_dot_backward_chunked, glx_gat_attention_backward_chunked; the
  * half-precision KNN scan -- GLX_KNN_PREC_*, glx_knn_search_ex;
- * the narrow KNN tile -- GLX_KNN_TILE_*, glx_knn_search_tiled. */
+ * the narrow KNN tile -- GLX_KNN_TILE_*, glx_knn_search_tiled;
+ * the half-precision IVF-Flat search -- glx_knn_ivf_search_prec. */
 #define GLX_ABI_VERSION 5
 
 /* Exported symbols: libglx.so is built with -fvisibility=hidden. */
@@ -605,6 +606,36 @@ GLX_API int glx_knn_merge(int device, int metric, int32_t num_parts, const int64
  *            candidate buffer per query (a test and measurement aid; the bits do not depend on it).  There is no
  *            automatic choice between the schedules.  Like the lists themselves, neither schedule follows rows
  *            rewritten under a view since the build.
+ * glx_knn_ivf_search_prec: glx_knn_ivf_search_ex with a choice of precision (GLX_KNN_PREC_* of glx_knn_search_ex).
+ * GLX_KNN_PREC_F32 requires refine == 0 and is glx_knn_ivf_search_ex with that schedule, in every bit and check.
+ * GLX_KNN_PREC_HALF (contract K-knn-ivf-half) scores the probed lists on the 16-bit matrix cores, list-major, from a
+ * bfloat16, float16, float8_e4m3fn or float8_e5m2 table as it lies in device memory.  It requires GLX_KNN_SCHED_LIST; the
+ * query-major schedule and a float32 table are GLX_INVALID_ARGUMENT, named (`schedule`, the dtype) in glx_last_error,
+ * and nothing is written.
+ *   probes   exactly glx_knn_ivf_search's: the coarse step stays the float32 contract search over the centroids from
+ *            the float32 queries as given; nprobe == nlist probes every list with no coarse step.
+ *   score    glx_knn_search_ex HALF's, word for word: q^ is the query rounded once to the scan type (the table's type,
+ *            bfloat16 for a float8 table, whose bytes are widened exactly); ip is +0.0f and then one 32x32x16 step per
+ *            block of 16 columns, ascending, zero from dim on; GLX_KNN_IP: ip, GLX_KNN_L2: the formula above with qn the
+ *            chain over q^ and xn the table's norms.  The steps of a (query, row) never depend on the tile, list or
+ *            round that scored it, so neither do its bits.
+ *   result   the k best rows, by the exact search's (image, storage row) key, among the rows of the probed lists;
+ *            padding, ids, +0.0f for a zero and 0x7fc00000 for a NaN as in glx_knn_search_ex HALF.  With nprobe == nlist
+ *            the result equals glx_knn_search_ex(..., GLX_KNN_PREC_HALF, refine) bit for bit, and a float8 table returns
+ *            what the bfloat16 table of the same values returns.
+ *   refine   k <= refine <= 1024: the scan keeps the refine best, which are re-scored with glx_knn_search's chain
+ *            against the float32 queries; the k best of those are returned with glx_knn_search's distances.
+ *   schedule the probe ranks are cut into groups of R = max(1, cap / longest list) ranks behind rank 0, cap being the
+ *            candidate keys the 256 MiB budget gives a query of the block; after every group a select folds the
+ *            survivors into the query's list and refreshes its threshold (the image of its k-th, or refine-th, key), which
+ *            filters the next group.  A query meets at most cap rows in a group, so the candidate buffer cannot
+ *            overflow: nothing is redone and nothing truncated.  A query block whose cap would be below the longest
+ *            list shrinks; a list longer than the budget's 2^25 keys, or more than 2^24 (group, list) keys, is
+ *            GLX_INVALID_ARGUMENT before anything is written.  glx_tune "knn_list_cand_cap" shrinks cap for this path
+ *            too, never below the longest list (1: one round per probe rank), and "knn_query_block" the block; the bits
+ *            depend on neither.
+ * Limits are glx_knn_ivf_search's, plus num_queries * max(k, refine) < 2^31.  No float atomics, integer atomics only
+ * compact, nothing is read back to the host: the same inputs give the same bits on every call.
  * glx_knn_ivf_info: any output may be NULL; longest_list in rows; device_bytes of centroids + list_ptr + list_rows.
  * glx_knn_ivf_export: centroids_out [nlist, dim] float32, list_ptr_out [nlist + 1] int64, list_rows_out [N] int64, to
  * host or device by ptr_kind; any of them may be NULL. */
@@ -618,6 +649,9 @@ GLX_API int glx_knn_ivf_search(const glx_knn_ivf* index, int metric, const float
 GLX_API int glx_knn_ivf_search_ex(const glx_knn_ivf* index, int metric, const float* queries, int32_t num_queries,
                                   int32_t k, int32_t nprobe, int schedule, int64_t* ids_out, float* dist_out,
                                   int ptr_kind, void* stream);
+GLX_API int glx_knn_ivf_search_prec(const glx_knn_ivf* index, int metric, const float* queries, int32_t num_queries,
+                                    int32_t k, int32_t nprobe, int schedule, int precision, int32_t refine,
+                                    int64_t* ids_out, float* dist_out, int ptr_kind, void* stream);
 GLX_API int glx_knn_ivf_info(const glx_knn_ivf* index, int32_t* nlist, int32_t* dim, int64_t* num_rows,
                              int64_t* longest_list, int64_t* device_bytes);
 GLX_API int glx_knn_ivf_export(const glx_knn_ivf* index, float* centroids_out, int64_t* list_ptr_out,
