@@ -33,6 +33,11 @@ re-scores its R best with the exact chain first (default: no re-rank).  Together
 IVF-Flat index over the narrow table and adds the half-precision list-major scan of the probed lists
 (glx.KnnIvf.search(..., schedule="list", precision="half")), which with every list probed must equal the flat half scan.
 
+--split adds one more line per search: the split scan of the float32 table on the bfloat16 matrix cores
+(glx.Features.search(..., split=True); three bfloat16 pieces per number, six piece products per column), its metrics and
+its recall@k against the exact search; --refine R re-scores its R best with the exact chain first (default: no re-rank).
+It has the wide tile only.
+
 --tile narrow runs every flat search above through the 32-query tiles (glx.Features.search(..., tile="narrow")): the
 same bits, a shorter time for a handful of users per call.
 
@@ -42,7 +47,7 @@ with --index ivfpq and --refine > 0: and every distance the coded index returns 
 Usage: python examples/eval_recall.py [--items 4000] [--users 1000] [--dim 16] [--k 10]
                                       [--index flat|ivf|ivfpq] [--nlist 64] [--nprobe 4] [--schedule query|list] [--m 4] [--refine 100]
                                       [--dtype float32|bfloat16|float16|float8_e4m3fn|float8_e5m2] [--precision float32|half]
-                                      [--tile wide|narrow]"""
+                                      [--tile wide|narrow] [--split]"""
 import argparse
 import math
 import os
@@ -100,6 +105,7 @@ def main():
     ap.add_argument("--refine", type=int, default=None, help="ivfpq: default 100; --precision half: default 0")
     ap.add_argument("--precision", choices=sorted(glx.KNN_PRECISIONS), default="float32")
     ap.add_argument("--tile", choices=sorted(glx.KNN_TILES), default="wide", help="the flat searches' score tile")
+    ap.add_argument("--split", action="store_true", help="add the split scan of the float32 table (--refine as for half)")
     ap.add_argument("--dtype", choices=sorted(dict(glx.FEATURE_DTYPES, **glx.FP8_FEATURE_DTYPES)), default="float32")
     a = ap.parse_args()
     if a.precision == "half" and a.dtype == "float32":
@@ -148,6 +154,16 @@ def main():
                 print("%s %s  half scan of the %s table, refine %d  recall@%d %.4f  ndcg@%d %.4f  hit rate %.4f  "
                       "recall vs exact search %.4f  two runs same bits: %s"
                       % (task, metric, a.dtype, half_refine, a.k, r, a.k, n, h, vs_exact, same_bits))
+                ok = ok and same_bits
+            if a.split:
+                sids, sdist = table.search(dq, a.k, metric, split=True, refine=half_refine)
+                sids2, sdist2 = table.search(dq, a.k, metric, split=True, refine=half_refine)
+                same_bits = bool(torch.equal(sids, sids2) and torch.equal(sdist.view(torch.int32), sdist2.view(torch.int32)))
+                r, n, h = metrics(sids, truth, a.k)
+                vs_exact = (sids[:, :, None] == ids[:, None, :]).any(1).float().mean().item()
+                print("%s %s  split scan of the float32 table, refine %d  recall@%d %.4f  ndcg@%d %.4f  hit rate %.4f  "
+                      "recall vs exact search %.4f  two runs same bits: %s"
+                      % (task, metric, half_refine, a.k, r, a.k, n, h, vs_exact, same_bits))
                 ok = ok and same_bits
             if index is None:
                 continue

@@ -195,6 +195,18 @@ struct HalfRow<GLX_DTYPE_F8E4M3> : HalfRowF8<GLX_DTYPE_F8E4M3> {};
 template <>
 struct HalfRow<GLX_DTYPE_F8E5M2> : HalfRowF8<GLX_DTYPE_F8E5M2> {};
 
+// columns [c, c + 4) of the float32 row at p as raw words, zero from dim on: one 16-byte load where p + c is 16-byte
+// aligned (vec) and the quad lies inside dim, element loads otherwise (glx_knn_narrow.hip, glx_knn_split.hip)
+__device__ __forceinline__ uint4 knn_f32_quad(const float* p, int32_t c, int32_t dim, bool vec) {
+  if (c + 4 <= dim && vec) return *reinterpret_cast<const uint4*>(p + c);
+  uint4 v = make_uint4(0u, 0u, 0u, 0u);
+  if (c < dim) v.x = __float_as_uint(p[c]);
+  if (c + 1 < dim) v.y = __float_as_uint(p[c + 1]);
+  if (c + 2 < dim) v.z = __float_as_uint(p[c + 2]);
+  if (c + 3 < dim) v.w = __float_as_uint(p[c + 3]);
+  return v;
+}
+
 // ---- the k smallest keys, one workgroup of kSelThreads ------------------------------------------------------
 // v[kSortN] ascending
 __device__ __forceinline__ void knn_sort_batch(uint64_t* v, int t) {
@@ -450,8 +462,14 @@ void knn_round_queries(const float* d_q, int64_t num_queries, int32_t dim, int32
 // knn_half_finish_kernel: a.run[a.nq, a.KP] -> (node id of f, the half scan's dist)[a.nq, a.k]
 void knn_half_finish(const KnnArgs& a, const glx_features* f, int64_t* d_ids, float* d_dist, hipStream_t s);
 
+// glx_knn_split.hip
+// the three-way bfloat16 split scan of a float32 table (GLX_KNN_PREC_SPLIT of glx_knn_search_ex) on device pointers
+// (workspace slot 1); the wide tile only
+int knn_search_split_device(const glx_features* f, int metric, const float* d_q, int32_t num_queries, int32_t k,
+                            int32_t refine, int64_t* d_ids, float* d_dist, hipStream_t s);
+
 // glx_knn_narrow.hip
-constexpr int kNarrowBQ = 32;   // queries per workgroup tile of a narrow score kernel
+constexpr int kNarrowBQ = 32;  // queries per workgroup tile of a narrow score kernel
 constexpr int kNarrowBR = 256;  // table rows per workgroup tile: 64 per wave
 // the narrow score kernels over rows [row0, row1) of a.t: tiles = (row tiles, query tiles) of kNarrowBR x kNarrowBQ as
 // knn_chunk_passes counts them; the launch walks the row tiles with a grid sized to the device.  qh: the rounded queries

@@ -59,19 +59,10 @@ constexpr int kWgPerCu = 2;   // what the 81,920 bytes of LDS allow
 
 __device__ __forceinline__ int narrow_sw(int r) { return (r ^ (r >> 3)) & 7; }
 
-// eight float32 columns: two 16-byte loads where p + c0 is 16-byte aligned (vec) and the quad lies inside dim
+// eight float32 columns: two quads of knn_f32_quad
 struct NarrowF32Group {
   uint4 lo, hi;
 };
-__device__ __forceinline__ uint4 narrow_f32_quad(const float* p, int32_t c, int32_t dim, bool vec) {
-  if (c + 4 <= dim && vec) return *reinterpret_cast<const uint4*>(p + c);
-  uint4 v = make_uint4(0u, 0u, 0u, 0u);
-  if (c < dim) v.x = __float_as_uint(p[c]);
-  if (c + 1 < dim) v.y = __float_as_uint(p[c + 1]);
-  if (c + 2 < dim) v.z = __float_as_uint(p[c + 2]);
-  if (c + 3 < dim) v.w = __float_as_uint(p[c + 3]);
-  return v;
-}
 
 // The row front of the exact kernel: group = eight stored elements as loaded, up8 = their float32 values.
 template <int DT>
@@ -99,7 +90,7 @@ struct NarrowExactRow<GLX_DTYPE_F32> {
   typedef float elem;
   typedef NarrowF32Group group;
   static __device__ __forceinline__ group load(const float* p, int32_t c0, int32_t dim, bool vec) {
-    return group{narrow_f32_quad(p, c0, dim, vec), narrow_f32_quad(p, c0 + 4, dim, vec)};
+    return group{knn_f32_quad(p, c0, dim, vec), knn_f32_quad(p, c0 + 4, dim, vec)};
   }
   static __device__ __forceinline__ void up8(group g, float (&f)[8]) {
     const uint32_t w[8] = {g.lo.x, g.lo.y, g.lo.z, g.lo.w, g.hi.x, g.hi.y, g.hi.z, g.hi.w};
@@ -337,8 +328,8 @@ extern "C" int glx_knn_search_tiled(const glx_features* f, int metric, const flo
               "tile must be GLX_KNN_TILE_WIDE (0) or GLX_KNN_TILE_NARROW (1), got %d", tile);
   GLX_REQUIRE(f != nullptr, "features is NULL");
   GLX_KNN_REQUIRE();
-  GLX_REQUIRE(precision == GLX_KNN_PREC_F32 || precision == GLX_KNN_PREC_HALF,
-              "precision must be GLX_KNN_PREC_F32 (0) or GLX_KNN_PREC_HALF (1), got %d", precision);
+  GLX_REQUIRE(precision == GLX_KNN_PREC_F32 || precision == GLX_KNN_PREC_HALF || precision == GLX_KNN_PREC_SPLIT,
+              "precision must be GLX_KNN_PREC_F32 (0), GLX_KNN_PREC_HALF (1) or GLX_KNN_PREC_SPLIT (2), got %d", precision);
   if (precision == GLX_KNN_PREC_F32) {
     GLX_REQUIRE(refine == 0, "refine must be 0 with precision GLX_KNN_PREC_F32, got %d", refine);
     GLX_REQUIRE(f->num_rows < INT32_MAX, "num_rows must be < 2^31");
@@ -347,15 +338,24 @@ extern "C" int glx_knn_search_tiled(const glx_features* f, int metric, const flo
                               return knn_search_device(f, metric, d_q, num_queries, k, d_ids, d_dist, s, tile);
                             });
   }
-  GLX_REQUIRE(f->dtype == GLX_DTYPE_BF16 || f->dtype == GLX_DTYPE_F16 || glx_dtype_is_f8(f->dtype),
-              "precision GLX_KNN_PREC_HALF needs a bfloat16, float16 or float8 table, this one stores %s",
-              glx_dtype_name(f->dtype));
+  const bool split = precision == GLX_KNN_PREC_SPLIT;
+  if (split) {
+    GLX_REQUIRE(f->dtype == GLX_DTYPE_F32, "precision GLX_KNN_PREC_SPLIT needs a float32 table, this one stores %s",
+                glx_dtype_name(f->dtype));
+    GLX_REQUIRE(tile == GLX_KNN_TILE_WIDE, "tile must be GLX_KNN_TILE_WIDE (0) with precision GLX_KNN_PREC_SPLIT, got %d",
+                tile);
+  } else {
+    GLX_REQUIRE(f->dtype == GLX_DTYPE_BF16 || f->dtype == GLX_DTYPE_F16 || glx_dtype_is_f8(f->dtype),
+                "precision GLX_KNN_PREC_HALF needs a bfloat16, float16 or float8 table, this one stores %s",
+                glx_dtype_name(f->dtype));
+  }
   GLX_REQUIRE(refine == 0 || (refine >= k && refine <= kSortN), "refine must be 0 or in [k = %d, %d], got %d", k, kSortN,
               refine);
   GLX_REQUIRE((int64_t)num_queries * (refine > k ? refine : k) < INT32_MAX, "num_queries * max(k, refine) must be < 2^31");
   GLX_REQUIRE(f->num_rows < INT32_MAX, "num_rows must be < 2^31");
   return knn_search_entry(f->device, f->dim, queries, num_queries, k, ids_out, dist_out, ptr_kind, stream,
                           [&](const float* d_q, int64_t* d_ids, float* d_dist, hipStream_t s) {
+                            if (split) return knn_search_split_device(f, metric, d_q, num_queries, k, refine, d_ids, d_dist, s);
                             return knn_search_half_device(f, metric, d_q, num_queries, k, refine, d_ids, d_dist, s, tile);
                           });
 }

@@ -818,7 +818,7 @@ class Features:
         return out
 
 
-    def search(self, queries, k, metric="ip", out=None, precision="float32", refine=0, tile="wide"):
+    def search(self, queries, k, metric="ip", out=None, precision="float32", refine=0, tile="wide", split=False):
         """Exact k nearest rows of every query (glx_knn_search) -> (ids[n, k] int64, dist[n, k] float32), best first.
         queries[n, D] float32; metric "ip" (inner product, larger is better) or "l2" (squared distance by expansion,
         smaller is better).  The score is one ascending fmaf chain over the columns, ties go to the smaller storage
@@ -834,12 +834,21 @@ class Features:
         the k best of those, every distance being the default search's distance of its row.  With precision="half" a
         torch tensor of the table's scan type is accepted as queries (upcast exactly: its rounding is the identity).
         tile="narrow" (glx_knn_search_tiled) scores through 32-query tiles that stream the table once per 32 queries, for
-        requests of few queries; it returns the bits of tile="wide" at the same precision and refine.  No automatic
-        choice is made."""
+        requests of few queries; it returns the bits of tile="wide" at the same precision and refine.
+        split=True (GLX_KNN_PREC_SPLIT; precision="float32", a float32 table and tile="wide" only) scores a float32
+        table on the bfloat16 matrix cores: every number of the table and of the queries is the sum of three bfloat16
+        pieces, and six piece products per column give a float32-grade score -- within the bound in include/glx.h of
+        the exact dot product, equal to the default search on integer data, but not the fmaf chain's bits; a row that
+        holds an infinity scores NaN.  refine works as with precision="half".  No automatic choice is made."""
         if precision not in KNN_PRECISIONS:
             raise ValueError("precision must be one of {}, not {!r}".format(sorted(KNN_PRECISIONS), precision))
         if tile not in KNN_TILES:
             raise ValueError("tile must be one of {}, not {!r}".format(sorted(KNN_TILES), tile))
+        if split:
+            if precision != "float32":
+                raise ValueError("split=True needs precision=\"float32\", not {!r}".format(precision))
+            return _knn_search(lib().glx_knn_search_tiled, lambda: self._h, self.dim, self.device, queries, k, metric, out,
+                               2, int(refine), KNN_TILES[tile])  # GLX_KNN_PREC_SPLIT
         if precision == "float32" and refine == 0 and tile == "wide":
             return _knn_search(lib().glx_knn_search, lambda: self._h, self.dim, self.device, queries, k, metric, out)
         scan = "bfloat16" if self.dtype in FP8_FEATURE_DTYPES else self.dtype

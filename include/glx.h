@@ -527,6 +527,33 @@ GLX_API int glx_features_convert_host(const float* src, int64_t n, int store_dty
  *            best of those returned: every returned dist is glx_knn_search's dist of that row.
  * glx_knn_search's limits apply, and num_queries * max(k, refine) < 2^31.  No float atomics.  A rejected call names
  * the argument in glx_last_error and leaves the outputs untouched.
+ * GLX_KNN_PREC_SPLIT is an opt-in scan of a float32 table on the bfloat16 matrix cores (contract K-knn-split), read as
+ * it lies in device memory -- no second copy, no rounded queries; any other table is GLX_INVALID_ARGUMENT:
+ *   split    every float32 v of the table and of the queries is three bfloat16 pieces: h = bf16(v), r1 = v - h (exact),
+ *            m = bf16(r1), r2 = r1 - m (exact), l = bf16(r2), each to nearest even by the uploads' converter.  Then
+ *            v == h + m + l, unless a piece falls below bfloat16's subnormal range: |v - (h + m + l)| <= 2^-134.  A
+ *            finite v whose h would round to +-inf (magnitudes from 0x7F7F8000 up) keeps the truncated word u >> 16;
+ *            +-inf is (v, 0, 0); a NaN is (0x7FC0 / 0xFFC0, 0, 0).
+ *   ip       the float32 accumulator of v_mfma_f32_32x32x16_bf16: +0.0f, then per block of 16 columns, ascending, six
+ *            32x32x16 steps over the piece pairs (ql, xh), (qh, xl), (qm, xm), (qm, xh), (qh, xm), (qh, xh) in that
+ *            order, the smallest magnitudes first; (qm, xl), (ql, xm) and (ql, xl) are dropped.  Columns from dim up
+ *            are zero in every piece.  A (query, row) has the same bits on every call, whatever num_queries, k, the
+ *            chunking, the query block, the pointer kind or its place in a tile.  Against the exact dot product of the
+ *            float32 operands, with S = sum_c |q[c] x[c]|:
+ *              |ip - exact(q . x)| <= (6.2 dim + 2) 2^-23 S + 2^-133 sum_c (|q[c]| + |x[c]|) + 6 dim 2^-126
+ *            (derived, no run: |h| <= (1 + 2^-8) |v|, |m| <= 2^-7 |v|, |l| <= 2^-16 |v|, so the six pairs' terms sum to
+ *            at most 1.03 S, and each of their 6 dim additions errs by at most one float32 ulp of that, the half scan's
+ *            bound per pair; the dropped pairs are at most 2 * 2^-23 |q[c] x[c]| a column; pieces lost below 2^-133
+ *            change a product by at most 2^-133 (|q[c]| + |x[c]|); a sum below float32's normal range may lose 2^-126
+ *            per addition, whether the matrix cores keep subnormal sums being the hardware's).  Where every product and
+ *            partial sum is an integer below 2^24 and the operands have at most 16 significant bits, ip is exact and
+ *            has glx_knn_search's bits.  An infinite element meets zero m and l pieces of the other operand as
+ *            0 * inf: that (query, row) scores NaN.
+ *   dist     GLX_KNN_IP: ip.  GLX_KNN_L2: the formula above with glx_knn_search's own qn (the fmaf chain over the
+ *            queries as given) and xn.  Order, ties, ids, padding, NaN last by row, the +0.0f zero, the 0x7fc00000 NaN
+ *            and refine are GLX_KNN_PREC_HALF's.
+ *   limits   GLX_KNN_PREC_HALF's; glx_knn_search_tiled accepts it with GLX_KNN_TILE_WIDE only, and
+ *            glx_knn_ivf_search_prec does not accept it: both name the argument and write nothing.
  *
  * glx_knn_search_tiled: glx_knn_search_ex with a choice of the score kernels' tile (an addition of this engine as well).
  * GLX_KNN_TILE_WIDE is glx_knn_search_ex itself: 128 queries x 128 rows per workgroup, a request padded to 128 queries.
@@ -544,6 +571,7 @@ GLX_API int glx_knn_search(const glx_features* f, int metric, const float* queri
                            int64_t* ids_out, float* dist_out, int ptr_kind, void* stream);
 #define GLX_KNN_PREC_F32 0
 #define GLX_KNN_PREC_HALF 1
+#define GLX_KNN_PREC_SPLIT 2 /* float32 tables: three bfloat16 pieces per number, glx_knn_search_ex / _tiled only */
 GLX_API int glx_knn_search_ex(const glx_features* f, int metric, const float* queries, int32_t num_queries, int32_t k,
                               int precision, int32_t refine, int64_t* ids_out, float* dist_out, int ptr_kind,
                               void* stream);
