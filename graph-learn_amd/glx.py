@@ -821,8 +821,9 @@ class Features:
     def search(self, queries, k, metric="ip", out=None, precision="float32", refine=0, tile="wide", split=False):
         """Exact k nearest rows of every query (glx_knn_search) -> (ids[n, k] int64, dist[n, k] float32), best first.
         queries[n, D] float32; metric "ip" (inner product, larger is better) or "l2" (squared distance by expansion,
-        smaller is better).  The score is one ascending fmaf chain over the columns, ties go to the smaller storage
-        row, NaN scores come last, k > num_rows pads with id -1 and dist -inf (ip) / +inf (l2); 1 <= k <= 1024.  ids are
+        smaller is better).  The score is one ascending fmaf chain over the columns, ties go to the smaller row
+        (the logical row number, whatever slot stores it), NaN scores come last, k > num_rows pads with id -1 and dist
+        -inf (ip) / +inf (l2); 1 <= k <= 1024.  ids are
         node ids (row numbers for a table without an id map).  Numpy in, numpy out; torch CUDA tensors in, torch CUDA
         tensors out on the current stream, nothing read back.  out=(ids, dist): buffers to write into.
         precision="half" (glx_knn_search_ex; a bfloat16, float16 or float8 table, not a float32 one) scans on the 16-bit
@@ -941,8 +942,8 @@ class KnnIvf(_KnnIndex):
         return out
 
     def lists(self):
-        """-> (list_ptr[nlist + 1], list_rows[num_rows]) int64 (numpy): list l holds the storage rows
-        list_rows[list_ptr[l]:list_ptr[l + 1]], ascending"""
+        """-> (list_ptr[nlist + 1], list_rows[num_rows]) int64 (numpy): list l holds the rows (the logical row
+        numbers, whatever slots store them) list_rows[list_ptr[l]:list_ptr[l + 1]], ascending"""
         ptr, rows = np.empty(self.nlist + 1, np.int64), np.empty(self.num_rows, np.int64)
         _check(lib().glx_knn_ivf_export(self._h, None, _ptr(ptr)[0], _ptr(rows)[0], PTR_HOST, None))
         return ptr, rows

@@ -479,8 +479,9 @@ GLX_API int glx_features_convert_host(const float* src, int64_t n, int store_dty
  *            search (stream-ordered, guarded for concurrent callers), and kept with the glx_features object; per
  *            search for a view (glx_features_view*), whose rows are the caller's to rewrite between calls.
  *   order    a better dist first; equal dist (float equality, +0.0f == -0.0f): the smaller storage row (insertion order)
- *            first; a NaN dist is worse than every number, NaNs among themselves by row.  Which NaN a NaN dist is, is
- *            the hardware's.
+ *            first -- here and below a "storage row" is the LOGICAL row number, the row's position in the matrix the
+ *            table was created from, whatever slot the swizzle of an owned table stores it in; a NaN dist is worse
+ *            than every number, NaNs among themselves by row.  Which NaN a NaN dist is, is the hardware's.
  *   output   row i of ids_out / dist_out ([num_queries, k]) holds the k best rows under that order, best first; ids_out
  *            holds node ids -- the id the row was created with (ids_[row], flat_index.cc:52-54), the row number for a
  *            table without an id map.  With k > num_rows the remaining slots are id = -1, dist = -inf (IP) / +inf (L2):

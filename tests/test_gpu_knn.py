@@ -206,9 +206,10 @@ def test_table_layout():
         f = glx.Features(X, ids=ids)
         for metric in METRICS:
             assert knn_ref.same(gpu_search(f, Q, 600, metric), knn_ref.search(Q, X, 600, metric, ids=ids))
-    # from 4,096 rows on an owned table is stored swizzled; a view reads the caller's rows in order
+    # an owned table of 4,096 rows and more has a swizzle bound, but block 0 of the swizzle is the identity: at 4,096 + 500
+    # rows no row moves (tests/test_gpu_knn_swizzle.py has the tables on which rows move); a view reads the caller's rows
     X = rng.standard_normal((4096 + 500, 6)).astype(np.float32)
-    X[4000:4200] = X[100:300]  # ties across the swizzle's blocks: the order is by LOGICAL row
+    X[4000:4200] = X[100:300]  # ties across the border of block 0: the order is by row
     Q = X[rng.integers(0, X.shape[0], 30)] + np.float32(0.25)
     owned, dX = glx.Features(X), _cuda(X)
     view = glx.Features(dX, view=True)

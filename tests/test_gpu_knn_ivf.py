@@ -84,7 +84,8 @@ def test_build_equals_the_restatement(dtype, train_rows):
 
 
 def test_build_defaults_and_centroid_forms():
-    """the default sample of a table beyond 256 * nlist rows, a swizzled table, non-integer data; planted centroids from
+    """the default sample of a table beyond 256 * nlist rows, an owned table beyond 4,096 rows (block 0 of the
+    swizzle: no row moves), non-integer data; planted centroids from
     the host and from the device"""
     rng = np.random.default_rng(12)
     X = rng.standard_normal((4096 + 700, 6)).astype(np.float32)
@@ -257,9 +258,10 @@ def test_table_layouts():
         ix = f.build_ivf(6, niter=2)
         assert same_index(exported(ix), knn_ivf_ref.build(X, 6, niter=2))
         check_against_both(f, ix, X, Q, (1, 600), (1, 5), ids=ids)
-    # from 4,096 rows on an owned table is stored swizzled: lists hold LOGICAL rows
+    # an owned table of 4,096 rows and more has a swizzle bound, but block 0 of the swizzle is the identity: no row moves
+    # here (tests/test_gpu_knn_swizzle.py has the tables on which rows move); lists hold rows
     X = rng.standard_normal((4096 + 500, 6)).astype(np.float32)
-    X[4000:4200] = X[100:300]  # ties across the swizzle's blocks
+    X[4000:4200] = X[100:300]  # ties across the border of block 0
     Q = X[rng.integers(0, X.shape[0], 12)] + np.float32(0.25)
     owned = glx.Features(X)
     ix = owned.build_ivf(9, niter=2)

@@ -420,9 +420,11 @@ def test_table_layouts():
         pq = exported_pq(px)
         assert same_pq(pq, knn_ivfpq_ref.build(X, index, 3, niter=1))
         check_searches(px, X, Q, index, pq, cases, ids=ids)
-    # from 4,096 rows on an owned table is stored swizzled with a padded stride: codes follow LOGICAL rows
+    # an owned table of 4,096 rows and more has a swizzle bound, but block 0 of the swizzle is the identity and the pitch
+    # is dim: no row moves here (tests/test_gpu_knn_swizzle.py has the tables on which rows move and the padded pitch);
+    # codes follow rows
     X = rng.standard_normal((4096 + 500, 6)).astype(np.float32)
-    X[4000:4200] = X[100:300]  # ties across the swizzle's blocks
+    X[4000:4200] = X[100:300]  # ties across the border of block 0
     Q = X[rng.integers(0, X.shape[0], 12)] + np.float32(0.25)
     owned = glx.Features(X)
     ix = owned.build_ivf(9, niter=1)

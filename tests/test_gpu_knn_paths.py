@@ -215,8 +215,9 @@ def test_half_tables_of_subnormals_give_the_bits_of_the_upcast_table(dtype):
 # ---- 5. layout combinations and the empty table ---------------------------------------------------------------------
 @pytest.mark.parametrize("dtype", ["bfloat16", "float16"])
 def test_half_swizzled_id_mapped_tables(dtype):
-    """half storage, the swizzle of an owned table of 4,096 rows and more, and an id map, all at once; L2 puts the
-    norms kernel through swizzle and half storage together.  Ties across the swizzle's blocks go by LOGICAL row."""
+    """half storage, an owned table of 4,096 rows and more (a swizzle bound of 4,096, though block 0 of the swizzle is
+    the identity: no row moves here, tests/test_gpu_knn_swizzle.py has the tables on which rows move), and an id map, all
+    at once; L2 puts the norms kernel through half storage.  Ties across the border of block 0 go by row."""
     import torch
     rng = np.random.default_rng(31)
     n = 4096 + 300
